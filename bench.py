@@ -25,6 +25,11 @@ scaling (every GPU holds nx^3 zones, the box grows along x3 at the same dx); --s
 nx^3 box into N slabs (BASELINE configs[3]: 512^3 on 8 GPUs = 64-plane slabs).
 
 Prints ONE JSON line (rank 0).  `value` = active zones advanced per second by the whole job.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that line needs: set-up, spin-up, warm-up, the N timed
+steps.  Everything else it can measure or check moves behind --full: per-kernel times and the rooflines built on them, the state
+check, the burst-regime window, the driver-path windows, the CPU leg, the strong-scaling window of N>1 and the --pmc-pass
+children.  --dump-outputs DIR writes what the timed path handed its caller after the last timed step (dump_outputs).
 """
 import argparse
 import importlib
@@ -263,6 +268,10 @@ def bench_smr(a, aa, torch, rank, world, local):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(a.dump_outputs, {f"cons_L{l}{sfx}": g for l, g in enumerate(grids)},
+                     {"time_dt": [m.time, m.dt], "subcycles": trace[-1] if trace else []} if rank == 0 else {}, share=world)
     zones = 2 * nx ** 3 * world
     lv = aa.config.levels(par, run)
     if a.smr_deck:
@@ -304,6 +313,38 @@ def bench_smr(a, aa, torch, rank, world, local):
         dist.destroy_process_group()
     else:
         m.close()
+
+
+DUMP_STATE_BYTES = 48 << 20     # --dump-outputs: the conserved state of all Grids, whole or sampled (64 MB in all with the rest)
+DUMP_SEED = 20240917            # the zones of a sampled state: the same ones in every run of the same arguments
+
+
+def dump_outputs(path, grids, scalars, share=1):
+    """--dump-outputs DIR: what the timed path handed its caller after its last timed step, as DIR/<name>.npy in float64.
+    `grids` (name -> lib.Grid): the active zones of each Grid's conserved state, [k][j][i][var] as aa_download_cons returns
+    it -- whole while it fits its part of DUMP_STATE_BYTES (`share` = how many processes dump beside this one), else a fixed
+    seeded sample of zones, (zones, var), with their flat active-zone indices k*Nx2*Nx1 + j*Nx1 + i in <name>_index.npy.
+    `scalars` (name -> numbers): what the step returns besides the state (time, dt, sub-cycles)."""
+    import numpy as np
+    NG = importlib.import_module(PKG + ".config").NGHOST
+    os.makedirs(path, exist_ok=True)
+    part = DUMP_STATE_BYTES // (max(1, len(grids)) * max(1, share))
+    for name, g in grids.items():
+        nx1, nx2, nx3 = g.cfg.Nx
+        U = g.download()
+        A = U[NG:NG + nx3, NG:NG + nx2, NG:NG + nx1]
+        nv, nz = A.shape[-1], nx1 * nx2 * nx3
+        if nz * nv * 8 <= part:
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(A))
+        else:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, nz, part // (8 * (nv + 1))))
+            k, r = np.divmod(idx, nx1 * nx2)
+            j, i = np.divmod(r, nx1)
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(A[k, j, i]))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+        del U, A
+    for name, v in scalars.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def spin_up(drv, mode, log):
@@ -360,9 +401,10 @@ class Ctx:
         self.torch.cuda.synchronize()
 
 
-def run_window(c, strong, spinup, steps, warmup, nslab=1):
+def run_window(c, strong, spinup, steps, warmup, nslab=1, dump=None):
     """One Driver from the deck's initial state: spin-up, warm-up, then EXACTLY `steps` timed steps between barrier +
-    synchronize pairs, MAX over ranks.  Returns the raw measurements (rank 0 builds the JSON from them)."""
+    synchronize pairs, MAX over ranks.  Returns the raw measurements (rank 0 builds the JSON from them).  `dump`: the
+    directory of --dump-outputs (the headline window only)."""
     a, aa, torch = c.a, c.aa, c.torch
     nx, world = a.nx, c.world
     p2 = a.p2 if nslab == 1 else 1                       # Grids along x2 (pencils); the rest of the ranks along x3
@@ -406,7 +448,7 @@ def run_window(c, strong, spinup, steps, warmup, nslab=1):
     t_spin = time.time() - t_spin
     for _ in range(warmup):
         drv.step()
-    hist0 = drv.history()
+    hist0 = drv.history() if a.full else None
     eng.g.profile_reset()
     if not a.no_kernel_times:
         eng.g.profile_enable(True)
@@ -426,7 +468,10 @@ def run_window(c, strong, spinup, steps, warmup, nslab=1):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         c.dist.all_reduce(t, op=c.dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    hist1 = drv.history()      # volume integrals (dump_history.c): a NaN or Inf anywhere in the state shows up here
+    hist1 = drv.history() if a.full else None      # volume integrals (dump_history.c): a NaN or Inf anywhere in the state shows up here
+    if dump:
+        dump_outputs(dump, {"cons" + (f"_rank{c.rank}" if world > 1 else ""): eng.g},
+                     {"time_dt": [drv.time, drv.dt], "subcycles": drv.niter_trace[-1:]} if c.rank == 0 else {}, share=world)
     w = {"run": run, "nx": nx, "nx3": nx3, "strong": strong, "elapsed": elapsed, "steps": steps, "warmup": warmup, "prof": prof,
          "nsync": nsync, "hist0": hist0, "hist1": hist1, "spin_log": spin_log, "t_spin": t_spin, "t_setup": t_setup,
          "niter": list(drv.niter_trace), "dt": drv.dt, "time": drv.time, "hbm": eng.g.device_bytes(), "spinup": spinup, "nx2": nx2, "p2": p2,
@@ -489,7 +534,11 @@ def pmc_passes(argv):
     if not exe:
         sys.stderr.write("[bench] --pmc-pass: rocprofv3 is not on PATH; roofline.traffic stays with the committed profile\n")
         return
-    keep = [x for x in argv if x not in ("--pmc-pass",)]
+    keep, skip = [], False
+    for x in argv:      # (the children neither count again nor write the outputs of --dump-outputs)
+        if not skip and x != "--pmc-pass" and not x.startswith("--dump-outputs"):
+            keep.append(x)
+        skip = x == "--dump-outputs"
 
     def bench_name(n):
         """rocprofv3's kernel name -> the name bench.py's event profiler books the launch under (hydro chain of the CTU integrator)"""
@@ -578,14 +627,15 @@ def analyse(c, w):
                    "radiation_subcycles_per_step": nsub, "subcycle_trace": niter,
                    "final_dt": w["dt"], "final_time": w["time"], "hbm_resident_GB": w["hbm"] / 1e9, "setup_s": w["t_setup"]},
     }
-    # the state that was timed: finite everywhere, mass and energy of the box before / after (outflow
+    # the state that was timed (--full): finite everywhere, mass and energy of the box before / after (outflow
     # boundaries: not conserved to round-off), no sub-cycle loop at its iteration limit
-    fin = all(math.isfinite(float(x)) for x in hist1)
-    out["state_check"] = {"finite": fin, "mass_before": float(hist0[0]), "mass_after": float(hist1[0]),
-                          "mass_rel_change": float(hist1[0] / hist0[0] - 1.0) if hist0[0] else None,
-                          "energy_rel_change": float(hist1[1] / hist0[1] - 1.0) if hist0[1] else None,
-                          "max_subcycles": max(niter) if niter else 0, "maxiter": run.maxiter,
-                          "ok": bool(fin and (not run.ion or max(niter) < run.maxiter))}
+    if hist1 is not None:
+        fin = all(math.isfinite(float(x)) for x in hist1)
+        out["state_check"] = {"finite": fin, "mass_before": float(hist0[0]), "mass_after": float(hist1[0]),
+                              "mass_rel_change": float(hist1[0] / hist0[0] - 1.0) if hist0[0] else None,
+                              "energy_rel_change": float(hist1[1] / hist0[1] - 1.0) if hist0[1] else None,
+                              "max_subcycles": max(niter) if niter else 0, "maxiter": run.maxiter,
+                              "ok": bool(fin and (not run.ion or max(niter) < run.maxiter))}
     out["host_syncs_per_step"] = w["nsync"] / steps
     # new_dt costs one read-back per step (two with several ranks: the slab's own and the all-reduce's)
     out["host_syncs_per_subcycle"] = (w["nsync"] / steps - (2.0 if c.multi else 1.0)) / max(nsub, 1e-30) if run.ion else None
@@ -687,7 +737,7 @@ def main():
                          "or a number (0: the start-up transient; 19 at 512^3: the burst of sub-cycles)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong", "both"],
                     help="N>1: weak (nx^3 per GPU, the box grows along x3), strong (ONE nx^3 box cut into N x3 slabs: BASELINE "
-                         "configs[3]) or both (default for N>1: the weak line with the strong window under `strong_scaling`)")
+                         "configs[3]) or both (default for N>1 with --full: the weak line with the strong window under `strong_scaling`)")
     ap.add_argument("--strong", action="store_true", help="same as --scaling strong")
     ap.add_argument("--p2", type=int, default=1, metavar="P2",
                     help="N>1: P2 Grids along x2 and N/P2 along x3 (x2 x x3 pencils, init_mesh.c:526-620) instead of x3 slabs")
@@ -716,9 +766,20 @@ def main():
                     help="count roofline.traffic in this run: two child processes under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE) before "
                          "the timed windows; otherwise the committed profile is quoted while the kernel sources are unchanged")
     ap.add_argument("--no-kernel-times", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline window: per-kernel times, rooflines and the state check of the timed "
+                         "region, the burst-regime window, the driver-path windows, the CPU leg, N>1's strong-scaling window, "
+                         "--pmc-pass (each can still be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(the conserved state, whole or a fixed seeded sample of zones, time and dt, sub-cycles)")
     a = ap.parse_args()
     if a.strong:
         a.scaling = "strong"
+    if not a.full:
+        if a.pmc_pass or a.burst_window:
+            ap.error("--pmc-pass and --burst-window are measurements of --full")
+        a.no_kernel_times = a.no_cpu_baseline = a.no_burst = a.no_driver_window = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and not a.inlib:
         self_launch(a, sys.argv[1:])        # does not return
@@ -751,16 +812,16 @@ def main():
     if a.inlib:
         # one process, N slabs behind the C entry points (strong scaling of ONE nx^3 box; the slabs sit on the devices of
         # AA_SLAB_DEVICES, all on the current one by default = a rehearsal)
-        w = run_window(c, True, a.spinup, a.steps, a.warmup, nslab=a.inlib)
+        w = run_window(c, True, a.spinup, a.steps, a.warmup, nslab=a.inlib, dump=a.dump_outputs)
         out = analyse(c, w)
         out["n_gpus"] = a.inlib
         out["config"]["slab_devices"] = os.environ.get("AA_SLAB_DEVICES", "all slabs on the current device (rehearsal, not a measurement)")
         print(json.dumps(out))
         return
 
-    mode = a.scaling or ("both" if world > 1 else "weak")
+    mode = a.scaling or ("both" if world > 1 and a.full else "weak")
     first_strong = (mode == "strong")
-    w = run_window(c, first_strong, a.spinup, a.steps, a.warmup)
+    w = run_window(c, first_strong, a.spinup, a.steps, a.warmup, dump=a.dump_outputs)
     out = analyse(c, w) if rank == 0 else None
     if mode == "both" and world > 1:
         # BASELINE's metric is also quoted on ONE 512^3 box over N GPUs (configs[3]): the same job times that window too

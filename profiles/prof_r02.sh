@@ -4,7 +4,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline"
 rm -rf $R/gpurun_out/r02_trace $R/gpurun_out/r02_fetch $R/gpurun_out/r02_write $R/gpurun_out/r02_sq
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/r02_trace -o t --output-format csv -- python3 $R/bench.py $ARGS > $R/gpurun_out/r02_bench_under_rocprof.json 2> $R/gpurun_out/r02_trace.log
 echo trace done

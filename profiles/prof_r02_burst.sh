@@ -3,7 +3,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd /tmp && export TMPDIR=/tmp
-ARGS="--spinup 19 --steps 6 --warmup 0 --no-cpu-baseline"
+ARGS="--full --spinup 19 --steps 6 --warmup 0 --no-cpu-baseline"
 rm -rf $R/gpurun_out/r02_burst_trace $R/gpurun_out/r02_burst_fetch $R/gpurun_out/r02_burst_write $R/gpurun_out/r02_burst_sq
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/r02_burst_trace -o t --output-format csv -- python3 $R/bench.py $ARGS > $R/gpurun_out/r02_burst_bench_under_rocprof.json 2> $R/gpurun_out/r02_burst_trace.log
 echo trace done

@@ -10,8 +10,8 @@ set -e
 W=${1:-stationary}
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd /tmp && export TMPDIR=/tmp
-if [ "$W" = burst ]; then ARGS="--spinup burst --steps 6 --warmup 0 --no-burst --no-cpu-baseline"; STEPS=6; P=r03_burst; WL="ioniz_sphere 512x512x512, burst regime (--spinup burst)"
-else ARGS="--steps 20 --warmup 5 --no-burst --no-cpu-baseline"; STEPS=20; P=r03; WL="ioniz_sphere 512x512x512"; fi
+if [ "$W" = burst ]; then ARGS="--full --spinup burst --steps 6 --warmup 0 --no-burst --no-cpu-baseline"; STEPS=6; P=r03_burst; WL="ioniz_sphere 512x512x512, burst regime (--spinup burst)"
+else ARGS="--full --steps 20 --warmup 5 --no-burst --no-cpu-baseline"; STEPS=20; P=r03; WL="ioniz_sphere 512x512x512"; fi
 O=$R/gpurun_out
 rm -rf $O/${P}_trace $O/${P}_fetch $O/${P}_write $O/${P}_sq
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/${P}_trace -o t --output-format csv -- python3 $R/bench.py $ARGS > $O/${P}_bench_under_rocprof.json 2> $O/${P}_trace.log

@@ -18,9 +18,9 @@ for r in rows[:10]:
 P
   rm -rf $R/gpurun_out/pw_$name
 }
-run blast --problem blast --steps 10 --warmup 2
-run ifront256 --problem ifront --nx 256 --steps 10 --warmup 2
-run vl --integrator vl --steps 10 --warmup 2 --spinup 30
-run ppm --order 3 --steps 10 --warmup 2 --spinup 30
-run smr --smr --steps 10 --warmup 2
+run blast --full --problem blast --steps 10 --warmup 2
+run ifront256 --full --problem ifront --nx 256 --steps 10 --warmup 2
+run vl --full --integrator vl --steps 10 --warmup 2 --spinup 30
+run ppm --full --order 3 --steps 10 --warmup 2 --spinup 30
+run smr --full --smr --steps 10 --warmup 2
 cat $OUT

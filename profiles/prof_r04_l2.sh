@@ -5,7 +5,7 @@
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out
-ARGS="--steps 4 --warmup 1 --no-burst --no-cpu-baseline --no-kernel-times"
+ARGS="--full --steps 4 --warmup 1 --no-burst --no-cpu-baseline --no-kernel-times"
 rocprofv3 -L > $O/r04_counters_list.txt 2>&1
 rm -rf $O/r04_l2a $O/r04_l2b
 timeout -k 10 400 rocprofv3 --pmc TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_READ_sum -d $O/r04_l2a -o a --output-format csv -- python3 $R/bench.py $ARGS > /dev/null 2> $O/r04_l2a.log || { echo "pass a failed"; tail -5 $O/r04_l2a.log; }

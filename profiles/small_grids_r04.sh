@@ -13,10 +13,10 @@ print(f"{name:10s} ms/step {d['ms_per_step']:.4f}  value {d['value']:.3e}  nsub 
 if k: print("   " + "  ".join(f"{a} {b*1e3:.0f}us" + (f"/{n[a]:.0f}" if a in n else "") for a, b in list(k.items())[:16]), flush=True)
 P
 }
-run nx80 --nx 80 --steps 40 --warmup 5
-run nx128nk --nx 128 --steps 40 --warmup 5 --no-kernel-times
-run deck2nk --smr --smr-deck --steps 40 --warmup 10 --no-kernel-times
-run nx128 --nx 128 --steps 40 --warmup 5
-run nx192 --nx 192 --steps 20 --warmup 5
-run deck2 --smr --smr-deck --steps 40 --warmup 10
-AA_SMR_DEEP_RADIATION=fixed run deck5 --smr --smr-deck --smr-levels 5 --steps 10 --warmup 10
+run nx80 --full --nx 80 --steps 40 --warmup 5
+run nx128nk --full --nx 128 --steps 40 --warmup 5 --no-kernel-times
+run deck2nk --full --smr --smr-deck --steps 40 --warmup 10 --no-kernel-times
+run nx128 --full --nx 128 --steps 40 --warmup 5
+run nx192 --full --nx 192 --steps 20 --warmup 5
+run deck2 --full --smr --smr-deck --steps 40 --warmup 10
+AA_SMR_DEEP_RADIATION=fixed run deck5 --full --smr --smr-deck --smr-levels 5 --steps 10 --warmup 10

@@ -27,7 +27,7 @@ def run_bench(*args, env=None, launcher=()):
 
 
 def test_one_json_line_with_roofline_and_cpu_baseline():
-    d = run_bench("--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2")
+    d = run_bench("--full", "--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "phases", "step_roofline", "state_check"):
         assert k in d, k
@@ -65,7 +65,7 @@ def test_second_window_times_the_burst_regime():
     """N = 1: after the headline window a second Driver is spun up to the first burst of radiation sub-cycles behind the
     dt-doubling phase and a few steps are timed there, so that the sub-cycle kernel's roofline fraction on 64 B per cell is a
     number of the driver's own run (`regimes.burst`)."""
-    d = run_bench("--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--burst-window", "--no-cpu-baseline", "--no-driver-window")
+    d = run_bench("--full", "--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--burst-window", "--no-cpu-baseline", "--no-driver-window")
     b = d["regimes"]["burst"]
     assert d["regimes"]["stationary"]["ms_per_step"] == d["ms_per_step"]
     assert b["steps"] == 3 and b["spinup_steps"] >= 4 and b["nsub"] >= 2 and b["ms_per_step"] > 0
@@ -75,12 +75,12 @@ def test_second_window_times_the_burst_regime():
 
 def test_gpus_n_without_a_launcher_starts_its_own_ranks():
     """`python bench.py --gpus 2` as the driver types it (no torchrun around it): the program starts its ranks as child
-    processes, relays their ONE JSON line and exit code.  Default for N > 1: the weak-scaling line with the strong-scaling
+    processes, relays their ONE JSON line and exit code.  With --full, N > 1 gives the weak-scaling line with the strong-scaling
     window (ONE nx^3 box cut into N slabs: BASELINE configs[3]) of the same job under `strong_scaling`.  Rehearsed with both
     ranks on cuda:0 over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["AA_BENCH_REHEARSAL"] = "1"
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--nx", "64", "--steps", "2", "--warmup", "1",
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--nx", "64", "--steps", "2", "--warmup", "1",
                          "--spinup", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, timeout=900, env=env)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.strip().startswith("{")]
@@ -95,8 +95,8 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks():
 def test_slabs_inside_the_library_as_a_bench_mode():
     """--inlib N: one process, aa_params.nslab = N (csrc/slabs.hip), the path of the drop-in executables; rehearsed with both
     slabs on the one device.  The radiation sub-cycle may cost ONE host round trip there too."""
-    d = run_bench("--inlib", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline")
-    one = run_bench("--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
+    d = run_bench("--full", "--inlib", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline")
+    one = run_bench("--full", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and "inside the library" in d["config"]["partition"]
     assert d["config"]["subcycle_trace"] == one["config"]["subcycle_trace"] and d["state_check"]["ok"] is True
     assert abs(d["state_check"]["mass_after"] / one["state_check"]["mass_after"] - 1) < 1e-12
@@ -106,7 +106,7 @@ def test_slabs_inside_the_library_as_a_bench_mode():
 def test_other_workloads_keep_the_contract():
     for args in (("--problem", "blast", "--nx", "48"), ("--smr", "--nx", "32"), ("--integrator", "vl", "--nx", "48"), ("--order", "3", "--nx", "48"),
                  ("--strict", "--nx", "48")):
-        d = run_bench(*args, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--spinup", "1", "--no-driver-window")
+        d = run_bench("--full", *args, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--spinup", "1", "--no-driver-window")
         assert d["value"] > 0 and d["roofline"]["achieved"] > 0 and "workload" in d["config"]
 
 
@@ -115,7 +115,7 @@ def test_two_ranks_rehearsed_on_one_gpu(strong):
     """The N>1 path of bench.py (torchrun, one rank per GPU) with both ranks on cuda:0 over gloo: not a measurement,
     but every collective of the real run is issued.  The radiation sub-cycle may cost ONE host round trip."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    d = run_bench("--gpus", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", *(("--strong",) if strong else ("--no-cpu-baseline",)),
+    d = run_bench("--full", "--gpus", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", *(("--strong",) if strong else ("--no-cpu-baseline",)),
                   env={"AA_BENCH_REHEARSAL": "1"},
                   launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                             "--master-port", str(port)))
@@ -146,7 +146,7 @@ def test_one_rank_over_rccl():
     memory all go through RCCL (the point-to-point halo needs a second GPU and stays unrehearsed on this backend).
     Same answer as the plain one-GPU run."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    args = ("--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
+    args = ("--full", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
     d = run_bench(*args, env={"AA_FORCE_DISTRIBUTED": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": "0",
                               "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     one = run_bench(*args)
@@ -159,11 +159,11 @@ def test_one_rank_over_rccl():
 def test_two_ranks_as_pencils():
     """bench.py --gpus 2 --p2 2: the two ranks cut x2 instead of x3 (x2 x x3 pencils 2x1), rehearsed on the one GPU over gloo."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    d = run_bench("--gpus", "2", "--p2", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--scaling", "strong",
+    d = run_bench("--full", "--gpus", "2", "--p2", "2", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--scaling", "strong",
                   env={"AA_BENCH_REHEARSAL": "1"},
                   launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                             "--master-port", str(port)))
-    one = run_bench("--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
+    one = run_bench("--full", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-cpu-baseline", "--no-driver-window")
     assert d["n_gpus"] == 2 and "pencils 2x1" in d["config"]["partition"] and d["state_check"]["ok"] is True
     assert d["config"]["subcycle_trace"] == one["config"]["subcycle_trace"]
     assert abs(d["state_check"]["mass_after"] / one["state_check"]["mass_after"] - 1) < 1e-9
@@ -174,7 +174,7 @@ def test_driver_path_window_beside_the_aa_step_line():
     sub-cycle loop inside the library with the all-gather as its callback (aa_ion_radtransfer_3d_gather), new_dt's all-reduce.  The
     same invocation times that path too, on a one-rank RCCL communicator (`driver_path`), so that a 1 -> N curve can be read like
     for like: same sub-cycle counts, ONE host round trip per sub-cycle, and what the host side costs per step."""
-    d = run_bench("--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--burst-window", "--no-cpu-baseline")
+    d = run_bench("--full", "--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--burst-window", "--no-cpu-baseline")
     p = d["driver_path"]
     assert "error" not in p, p
     assert p["steps"] == 3 and p["ms_per_step"] > 0 and p["nsub"] == d["config"]["radiation_subcycles_per_step"]
@@ -182,7 +182,7 @@ def test_driver_path_window_beside_the_aa_step_line():
     assert p["host_syncs_per_subcycle"] <= 1.0 + 1e-9 and "nccl" in p["what"]
     assert p["burst"]["nsub"] == d["regimes"]["burst"]["nsub"] and p["burst"]["host_syncs_per_subcycle"] <= 1.0 + 1e-9
     # the sub-cycle loop as Python wrote it before (three crossings per sub-cycle) still gives the same run
-    q = run_bench("--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline",
+    q = run_bench("--full", "--nx", "64", "--steps", "3", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline",
                   env={"AA_DRIVER_PY_SUBCYCLES": "1"})["driver_path"]
     assert q["nsub"] == p["nsub"] and q["host_syncs_per_subcycle"] <= 1.0 + 1e-9
 
@@ -191,11 +191,52 @@ def test_traffic_is_quoted_with_its_source():
     """roofline.traffic comes from the committed PMC passes of this command only while the kernel sources still have the fingerprint
     recorded with them (`traffic_source`); --pmc-pass counts it in the run itself (children under rocprofv3)."""
     import shutil
-    d = run_bench("--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline", "--no-driver-window")
+    d = run_bench("--full", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline", "--no-driver-window")
     assert d["roofline"]["traffic"] is None                     # (no profile of a 64^3 workload is committed)
     if shutil.which("rocprofv3"):
-        d = run_bench("--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline", "--no-driver-window",
+        d = run_bench("--full", "--nx", "64", "--steps", "2", "--warmup", "1", "--spinup", "2", "--no-burst", "--no-cpu-baseline", "--no-driver-window",
                       "--pmc-pass")
         r = d["roofline"]
         assert r["traffic_source"]["kind"].startswith("pmc-pass") and r["traffic"] > r["bytes_per_launch"] > 0
         assert r["traffic"] < 40 * r["bytes_per_launch"]
+
+
+def test_plain_run_times_the_headline_window_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is the headline window alone (no per-kernel times, state check, second window, driver path or
+    CPU leg), with the line's own keys.  --dump-outputs writes the state after the last timed step: a 128^3 state is larger
+    than the dump's budget, so a fixed seeded sample of zones, the same in every run of the same arguments -- and the same
+    bits, since the default build is deterministic."""
+    import numpy as np
+    args = ("--nx", "128", "--steps", "3", "--warmup", "1", "--spinup", "2")
+    d = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    for k in ("roofline", "phases", "kernel_ms_per_step", "state_check", "regimes", "driver_path", "cpu_baseline"):
+        assert k not in d, k
+    assert d["metric"] == "cell-updates/sec (hydro+ion-rad step)" and d["unit"] == "cell-updates/s" and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert abs(d["value"] - 128 ** 3 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert set(a) == {"cons.npy", "cons_index.npy", "time_dt.npy", "subcycles.npy"}
+    assert all(x.dtype == np.float64 for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    cons, idx = a["cons.npy"], a["cons_index.npy"]
+    assert cons.ndim == 2 and cons.shape == (idx.size, 6) and idx.size > 100000 and np.isfinite(cons).all() and (cons[:, 0] > 0).all()
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < 128 ** 3
+    assert a["time_dt.npy"].tolist() == [d["config"]["final_time"], d["config"]["final_dt"]]
+    assert a["subcycles.npy"].tolist() == d["config"]["subcycle_trace"][-1:]
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    for name, x in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / name), x), name
+
+
+def test_dump_of_a_small_grid_is_the_whole_state(tmp_path):
+    """A state within the dump's budget is written whole, active zones [k][j][i][var], as the --full run of the same arguments
+    computes it."""
+    import numpy as np
+    args = ("--nx", "48", "--problem", "blast", "--steps", "2", "--warmup", "1", "--spinup", "1")
+    run_bench(*args, "--dump-outputs", str(tmp_path / "plain"))
+    run_bench("--full", *args, "--no-cpu-baseline", "--no-driver-window", "--dump-outputs", str(tmp_path / "full"))
+    u = np.load(tmp_path / "plain" / "cons.npy")
+    assert u.shape == (48, 48, 48, 5) and u.dtype == np.float64 and np.isfinite(u).all()
+    assert not (tmp_path / "plain" / "cons_index.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "full" / "cons.npy"), u)

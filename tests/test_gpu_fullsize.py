@@ -202,7 +202,7 @@ def test_driver_path_agrees_with_aa_step_at_512():
     import json
     import subprocess
     import sys
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"],
                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, timeout=1200)
     assert pr.returncode == 0, pr.stderr[-2000:]
     d = json.loads([ln for ln in pr.stdout.splitlines() if ln.strip().startswith("{")][-1])
