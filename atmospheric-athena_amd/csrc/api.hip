@@ -98,6 +98,11 @@ int aa_create(const aa_params *p, aa_grid **out)
     c.mailbox = env("AA_MAILBOX", 1); c.mailbox_spin_us = env("AA_MAILBOX_SPIN_US", 300);
     c.bc_one = env("AA_BC_ONE", 1); c.fuse_pick = env("AA_ION_FUSE_PICK", 1); c.pin_one = env("AA_PIN_ONE", 1);
     c.edge_overlap = env("AA_EDGE_OVERLAP", 0);
+    c.sw_chunk = env("AA_SW_CHUNK", 0); c.vp_kc = env("AA_VP_KC", 0);
+    if (c.sw_chunk < 0 || c.sw_chunk > 4096 || c.vp_kc < 0 || c.vp_kc > 4096) {
+      const int sw = c.sw_chunk, vp = c.vp_kc; delete g;
+      return fail(-1, "[aa_create]: AA_SW_CHUNK=%d AA_VP_KC=%d: each must be 0 (by size) or 1..4096", sw, vp);
+    }
   }
   d.Nx1 = p->Nx[0]; d.Nx2 = p->Nx[1]; d.Nx3 = p->Nx[2];
   d.N1 = d.Nx1 + 2*AA_NGHOST; d.N2 = d.Nx2 + 2*AA_NGHOST; d.N3 = d.Nx3 + 2*AA_NGHOST;
@@ -416,6 +421,7 @@ int aa_apply_pinned_cells(aa_grid *g)
     launch_pinned(g->d, 5 + g->p.nscal, g->npin, g->pin_idx, g->pin_val, g->st);
     if (g->cfl_ready) launch_pinned_cfl(g->d, g->npin, g->pin_idx, g->sc, g->st);
   }
+  if (g->npin > 0) g->active_dirty = true;      // active zones written: aa_download_ghost_zones must move the whole block
   return 0;
 }
 

@@ -100,6 +100,9 @@ struct LaunchCfg {
   int x1_flat = 1;           // AA_X1_FLAT=0: the x1 first-pass sweep with a block per piece of a row
   int slopes_march = 1;      // AA_SLOPES_MARCH=0: the PPM slope arrays along x2 / x3 one zone per thread
   int ca_kc = 0, fu_kc = 0;  // AA_CA_KC / AA_FU_KC: planes per block of k_correct_all / k_flux2_update (0: by size)
+  int sw_chunk = 0;          // AA_SW_CHUNK: interfaces / cells per thread of k_sweep_march and k_slopes_march (0: by size)
+  int vp_kc = 0;             // AA_VP_KC: planes per block of k_vl_predict (0: by size)
+                             // (both 0 .. 4096; aa_create refuses anything else)
   int ion_pass_cap = 4096;   // AA_ION_PASS_BLOCKS: most blocks of a k_ion_pass launch
   int pitch_align = 1;       // AA_PITCH_ALIGN=0: dense device rows
   int mailbox = 1;           // AA_MAILBOX=0: scalars come back by hipMemcpyAsync + hipStreamSynchronize instead of the polled mailbox

@@ -2197,8 +2197,8 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
 #ifndef SW_CHUNK
 #define SW_CHUNK 32
 #endif
-    int chunk = SW_CHUNK;
-    while (chunk > 4 && (long)nblk(ni*nt, 64)*((nfaces + chunk - 1)/chunk) < 4096) chunk >>= 1;
+    int chunk = g.cfg.sw_chunk > 0 ? g.cfg.sw_chunk : SW_CHUNK;          // (AA_SW_CHUNK overrides)
+    if (g.cfg.sw_chunk <= 0) while (chunk > 4 && (long)nblk(ni*nt, 64)*((nfaces + chunk - 1)/chunk) < 4096) chunk >>= 1;
     dim3 grid(nblk(ni*nt, 64), (nfaces + chunk - 1)/chunk);
     if (dir == 1) hipLaunchKernelGGL((k_sweep_march<NS, 1, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt);
     else          hipLaunchKernelGGL((k_sweep_march<NS, 2, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt);
@@ -2223,8 +2223,8 @@ static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *
   if (march && dir != 0) {
     const long nq = march_slots(g), nt = (dir == 1 ? g.ke - g.ks : g.je - g.js) + 5;
     const int ncell = (dir == 1 ? g.je - g.js : g.ke - g.ks) + 7;
-    int chunk = 32;
-    while (chunk > 4 && (long)nblk(nq*nt, 64)*((ncell + chunk - 1)/chunk) < 4096) chunk >>= 1;
+    int chunk = g.cfg.sw_chunk > 0 ? g.cfg.sw_chunk : 32;                // (AA_SW_CHUNK overrides)
+    if (g.cfg.sw_chunk <= 0) while (chunk > 4 && (long)nblk(nq*nt, 64)*((ncell + chunk - 1)/chunk) < 4096) chunk >>= 1;
     dim3 gm(nblk(nq*nt, 64), (ncell + chunk - 1)/chunk);
     if (dir == 1) hipLaunchKernelGGL((k_slopes_march<NS, 1>), gm, dim3(64), 0, st, g, src, chunk);
     else          hipLaunchKernelGGL((k_slopes_march<NS, 2>), gm, dim3(64), 0, st, g, src, chunk);
@@ -2323,11 +2323,11 @@ static void vl_flux1_impl(const DevGrid &g, int dir, hipStream_t st)
 void launch_vl_flux1(const DevGrid &g, int nscal, int dir, hipStream_t st)
 { if (nscal) vl_flux1_impl<1>(g, dir, st); else vl_flux1_impl<0>(g, dir, st); }
 // donor-cell fluxes + U^{n+1/2} in one kernel (what launch_vl_flux1 x3 + launch_vl_uhalf do)
-void launch_vl_predict(const DevGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
+void launch_vl_predict(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
 {
   const int ni = g.ie - g.is + 7, nj = g.je - g.js + 7, nk = g.ke - g.ks + 7;
-  int kc = 32;
-  while (kc > 4 && (long)nblk(ni, 63)*nblk(nj, VP_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
+  int kc = g.cfg.vp_kc > 0 ? g.cfg.vp_kc : 32;                             // (AA_VP_KC overrides)
+  if (g.cfg.vp_kc <= 0) while (kc > 4 && (long)nblk(ni, 63)*nblk(nj, VP_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
   dim3 grid(nblk(ni, 63), nblk(nj, VP_TJ - 1), (nk + kc - 1)/kc), blk(64, VP_TJ);
   if (nscal) { if (grav) hipLaunchKernelGGL((k_vl_predict<1, true>), grid, blk, 0, st, g, dt, kc);
                else      hipLaunchKernelGGL((k_vl_predict<1, false>), grid, blk, 0, st, g, dt, kc); }

@@ -230,10 +230,11 @@ def ion_path(request, monkeypatch):
 
 
 @pytest.mark.parametrize("strict", [True, False])
-@pytest.mark.parametrize("nx,nsteps", [((16, 8, 8), 3), ((8, 12, 16), 4), ((32, 16, 16), 3), ((100, 8, 6), 3), ((192, 6, 5), 2)])
+@pytest.mark.parametrize("nx,nsteps", [((16, 8, 8), 3), ((8, 12, 16), 4), ((32, 16, 16), 3), ((100, 8, 6), 3), ((192, 6, 5), 2), ((48, 40, 30), 2)])
 def test_ifront_vs_oracle(aa, lib, nx, nsteps, strict, ion_path):
     """Hydro + ion radiation.  Same sub-cycle counts; fields within 1e-9 of each field's max
-    (device exp/pow differ from glibc in the last bits)."""
+    (device exp/pow differ from glibc in the last bits).  48x40x30: 1200 rays, so k_ion_reduce_pick folds 300 partial records
+    with every one of its 256 threads looping over several (16 per thread at 512^3; at most one on the other shapes)."""
     o, g, nv, trace = run_pair(aa, lib, "ifront", nx, nsteps, strict)
     assert [t[0] for t in trace] == [t[1] for t in trace], trace
     for (_, _, dto, dtg, to, tg) in trace:
@@ -273,9 +274,10 @@ def test_ifront_golden_fixture(aa, lib, fused_rates, ion_path):
 
 
 @pytest.mark.parametrize("strict", [True, False])
-@pytest.mark.parametrize("nx,nsteps", [((20, 20, 20), 1), ((24, 16, 12), 2), ((40, 40, 40), 2)])
+@pytest.mark.parametrize("nx,nsteps", [((20, 20, 20), 1), ((24, 16, 12), 2), ((40, 40, 40), 2), ((48, 40, 40), 2)])
 def test_ioniz_sphere_vs_oracle(aa, lib, nx, nsteps, strict, fused_rates, ion_path):
-    """Hydro + static gravity (potential tables) + ion radiation + per-step core reset."""
+    """Hydro + static gravity (potential tables) + ion radiation + per-step core reset.  48x40x40 = 76 800 zones: above the
+    65 536 from which k_ion_rates / k_ion_update of the two-kernel path (ion_path "tile") grid-stride, as at 512^3."""
     o, g, nv, trace = run_pair(aa, lib, "ioniz_sphere", nx, nsteps, strict)
     assert [t[0] for t in trace] == [t[1] for t in trace], trace
     for (_, _, dto, dtg, to, tg) in trace:

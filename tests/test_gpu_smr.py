@@ -75,6 +75,17 @@ def test_blast_three_levels_vs_reference(aa, lib, name, strict):
         m.close()
 
 
+@pytest.mark.parametrize("fu_kc", ["1", "3"])
+def test_blast_three_levels_at_short_chunks_vs_reference(aa, lib, fu_kc, monkeypatch):
+    """The kept x3 faces of k_flux2_update at every chunk boundary (the single-writer rule round 4's race broke): the three-level
+    fixture in the strict build with k_flux2_update at 1 and 3 planes per block (32 at 512^3) behind k_correct_all at 3 (64
+    there; odd, so chunks also start on odd planes), bit for bit against the reference's run."""
+    monkeypatch.setenv("AA_CORRECT_ALL", "1")
+    monkeypatch.setenv("AA_CA_KC", "3")
+    monkeypatch.setenv("AA_FU_KC", fu_kc)
+    test_blast_three_levels_vs_reference(aa, lib, "smr_blast_3lev_s6", True)
+
+
 @pytest.mark.parametrize("name", ["smr_blast_3lev_s6", "smr_blast_3lev_edge_s8", "smr_blast_2dom_s6", "smr_blast_tree_s5"])
 def test_levels_on_the_big_grid_kernels_vs_reference(aa, lib, name, monkeypatch):
     """The levels of the fixtures are small enough for the tile kernels; Grids of 4e5 zones or more (the 80^3 root of the reference's own

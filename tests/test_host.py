@@ -258,6 +258,30 @@ def test_boundary_docs_match_the_shim():
     assert "nslab > 1" in hdr and "AA_NGPU" in doc
 
 
+# knobs of the drop-in shim (host/athena_shim.c): they choose how the reference's main loop drives the library, not what a kernel
+# launch looks like, and are outside the guard below
+SHIM_KNOBS = {"AA_SYNC_EVERY", "AA_GHOST_REFRESH", "AA_DEVICE", "AA_COHERENCE", "AA_REVALIDATE_EVERY", "AA_INTEGRATOR", "AA_ORDER",
+              "AA_H_CORRECTION"}
+
+
+def test_every_library_knob_is_named_by_a_test():
+    """Every environment knob the library reads -- env("AA_...") in aa_create, getenv("AA_...") anywhere in csrc/*.hip -- is named
+    by at least one test under tests/ (this file aside), so that no launch choice arrives untested.  A knob only the shim reads must
+    be one of SHIM_KNOBS."""
+    import glob
+    csrc = "".join(open(p).read() for p in sorted(glob.glob(os.path.join(PKGDIR, "csrc", "*.hip"))))
+    lib_knobs = set(re.findall(r'\b(?:get)?env\("(AA_\w+)"', csrc))
+    assert {"AA_CA_KC", "AA_SW_CHUNK", "AA_VP_KC", "AA_ION_PASS_BLOCKS", "AA_CORRECT_ALL", "AA_NGPU"} <= lib_knobs
+    here = os.path.abspath(__file__)
+    tests = [p for p in glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True) if os.path.abspath(p) != here]
+    corpus = "".join(open(p).read() for p in tests)
+    unnamed = sorted(k for k in lib_knobs if not re.search(r"\b%s\b" % k, corpus))
+    assert not unnamed, f"library knobs no test names: {unnamed}"
+    shim = open(os.path.join(PKGDIR, "host", "athena_shim.c")).read()
+    shim_only = set(re.findall(r'getenv\("(AA_\w+)"\)', shim)) - lib_knobs
+    assert shim_only <= SHIM_KNOBS, f"knobs of the shim not listed as such: {sorted(shim_only - SHIM_KNOBS)}"
+
+
 def test_committed_traffic_profile_belongs_to_the_kernel_sources():
     """bench.py quotes roofline.traffic from profiles/r04_traffic.json only while the kernel sources have the fingerprint recorded in
     it; a kernel change without a new `profiles/prof_r04.sh` run must not pass unnoticed."""

@@ -33,5 +33,12 @@ for ca in ("0", "1"):
         same = ia == ib == ic and all(np.array_equal(x, y, equal_nan=True) and np.array_equal(x, z, equal_nan=True) for x, y, z in zip(a, b, c))
         bad += not same
         print(f"AA_CORRECT_ALL={ca} {label}: three runs identical: {same}", flush=True)
+# k_flux2_update at 3 planes per block (32 at 512^3): a kept x3 face at every third plane of every level, each written by one block only
+os.environ["AA_CORRECT_ALL"] = "1"; os.environ["AA_FU_KC"] = "3"
+a, ia = mesh("smr_blast_3lev_edge_s8", "blast", False); b, ib = mesh("smr_blast_3lev_edge_s8", "blast", False); c, ic = mesh("smr_blast_3lev_edge_s8", "blast", False)
+same = ia == ib == ic and all(np.array_equal(x, y, equal_nan=True) and np.array_equal(x, z, equal_nan=True) for x, y, z in zip(a, b, c))
+bad += not same
+print(f"AA_CORRECT_ALL=1 AA_FU_KC=3 mesh blast 3lev: three runs identical: {same}", flush=True)
+del os.environ["AA_FU_KC"]
 print("nondeterministic cases:", bad)
 sys.exit(1 if bad else 0)
