@@ -98,6 +98,8 @@ int aa_create(const aa_params *p, aa_grid **out)
     c.mailbox = env("AA_MAILBOX", 1); c.mailbox_spin_us = env("AA_MAILBOX_SPIN_US", 300);
     c.bc_one = env("AA_BC_ONE", 1); c.fuse_pick = env("AA_ION_FUSE_PICK", 1); c.pin_one = env("AA_PIN_ONE", 1);
     c.edge_overlap = env("AA_EDGE_OVERLAP", 0);
+    // (not a launch choice of a kernel of the step: kept with the Grid, not in LaunchCfg) floats per half of the dumps' bounce buffer
+    g->dump_chunk = env("AA_DUMP_CHUNK_FLOATS", 1 << 23); if (g->dump_chunk < 4) g->dump_chunk = 4; if (g->dump_chunk > (1 << 28)) g->dump_chunk = 1 << 28;
     c.sw_chunk = env("AA_SW_CHUNK", 0); c.vp_kc = env("AA_VP_KC", 0);
     if (c.sw_chunk < 0 || c.sw_chunk > 4096 || c.vp_kc < 0 || c.vp_kc > 4096) {
       const int sw = c.sw_chunk, vp = c.vp_kc; delete g;
@@ -217,6 +219,7 @@ void aa_destroy(aa_grid *g)
   if (g->link) { slabs_destroy(g); return; }          // a composite handle, whether or not it has slabs yet
   hipStreamSynchronize(g->st);
   prof_drain(g);
+  dump_release(g);
   hipFree(g->pool); hipFree(g->sc); hipHostFree(g->mb);
   for (hipEvent_t ev : g->ev_pool) hipEventDestroy(ev);
   if (g->ion_part) hipFree(g->ion_part);

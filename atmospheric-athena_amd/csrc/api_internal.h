@@ -65,6 +65,11 @@ struct aa_grid {
   // device; every entry point of the C-ABI forwards to the slabs and does the neighbour exchange / reductions
   std::vector<aa_grid*> slab;
   struct SlabLink *link = nullptr;
+  // data dumps (dump.hip): the page-locked bounce buffer (two halves of dump_cap floats), the stream of its copies, and the events
+  // "piece staged" [0..1] / "piece on the host" [2..3] of either half; made by the first aa_dump_section
+  int dump_chunk = 1 << 23;            // AA_DUMP_CHUNK_FLOATS at aa_create: floats per half asked for (4 .. 2^28)
+  float *dump_host = nullptr; size_t dump_cap = 0;
+  hipStream_t dump_st = nullptr; hipEvent_t dump_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool prof = false;
   std::vector<ProfEntry> pe;
   std::vector<hipEvent_t> ev_pool;     // events of drained scopes, reused (a small Grid's step is ~25 scopes: creating 50 events per step showed)
@@ -117,6 +122,8 @@ int slabs_fetch_scalars(aa_grid *g);
 int slabs_ion_finish(aa_grid *g);
 int slabs_ion_run_phased(aa_grid *g, double limit, int *niter_out, double *dt_done_out);
 int slabs_history(aa_grid *g, double *sums);
+int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
+void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away
 void slabs_push_state(aa_grid *g);
 // evaluation of a StaticGravPot callback at zone centres and lower faces of a Grid (api.hip)
 void aa_eval_grav_tables(const aa_params &p, const double dx[3], int N1, int N2, int N3, aa_gravpot_fn fn, std::vector<double> t[4]);

@@ -272,6 +272,22 @@ int slabs_download_cons(aa_grid *g, double *U)
   }
   return 0;
 }
+// a section of a data dump (dump.hip): every slab stages its own planes on its own device and lands them at its k offset
+// of the caller's one payload (sections are [k][j][i]: a slab's share is contiguous)
+int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst)
+{
+  DevGuard keep;
+  HALO_FLUSH(g);
+  SlabLink *L = g->link;
+  g->inner_swept = false;
+  const long long per_plane = aa_dump_section_floats(g, fmt, section)/g->p.Nx[2];
+  for (int s = 0; s < L->n; s++) {
+    SLAB_DEV(L, s);
+    int rc = aa_dump_section(g->slab[s], fmt, prim, section, host_dst + (size_t)L->k0[s]*(size_t)per_plane);
+    if (rc) return rc;
+  }
+  return 0;
+}
 int slabs_upload_edgeflux(aa_grid *g, const double *ef)
 {
   DevGuard keep;

@@ -129,7 +129,13 @@ class HipEngine:
     def bvals_side(self, dir: int, side: int): self.g.bvals_mhd_side(dir, side)
     def sync(self): self.g.sync()
     def download(self) -> np.ndarray: return self.g.download()
+    def download_edgeflux(self) -> np.ndarray: return self.g.download_edgeflux()
     def history(self) -> np.ndarray: return self.g.history()
+
+    def write_dump(self, path: str, fmt, prim: bool, time: float, dt: float):
+        """dump_vtk / dump_binary of this slab: the payload comes from the device in file order (csrc/dump.hip)"""
+        self.g.write_dump(path, fmt, prim, time=time, dt=dt)
+
     def close(self): self.g.close()
 
 
@@ -147,6 +153,7 @@ class Driver:
         self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict)
         self.time, self.dt, self.nstep = 0.0, 0.0, 0
         self.niter_trace: List[int] = []
+        self._hst = {}            # HistoryWriter per <outputN> block with out_fmt = hst
         self._halo = {}           # messages in flight per axis (2: x2, 3: x3): post .. finish
         self._py_syncs = 0        # host round trips of collectives issued from here (bench: host_syncs_per_step)
         # AA_FORCE_DISTRIBUTED=1 runs the Python-orchestrated loop (with its collectives) even on one
@@ -193,6 +200,60 @@ class Driver:
         s = self.history()
         if self.rank == 0:
             writer.dump(self.time, self.dt, s, vol, self.run.nscal)
+
+    # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
+    def write_dump(self, out, outputs):
+        """dump_vtk / dump_binary of this rank's Grid (level 0, domain 0) for one <outputN> block."""
+        from . import dumps
+        if out.level not in (-1, 0) or out.domain not in (-1, 0):
+            return
+        g, r = self.grid, self.run
+        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, out.out_fmt))
+        if hasattr(self.eng, "write_dump"):
+            self.eng.write_dump(path, out.out_fmt, out.prim, self.time, self.dt)
+        else:                                     # an engine without a device: the same payload from its host block
+            ng = 4
+            U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng]
+            dumps.write_dump_from_block(path, out.out_fmt, U, prim=out.prim, gamma=r.gamma, nscal=r.nscal, nx=g.Nx,
+                                        minx=g.MinX, dx=r.dx, time=self.time, dt=self.dt)
+
+    def write_history(self, out, outputs):
+        from .history import HistoryWriter
+        if out.level not in (-1, 0) or out.domain not in (-1, 0):
+            return
+        w = self._hst.get(out.n)
+        if w is None:
+            w = self._hst[out.n] = HistoryWriter(outputs.dir, outputs.basename, 0, 0, out.dat_fmt)
+        self.dump_history(w)                      # (every rank takes part in the sum; rank 0 writes)
+        rel = os.path.relpath(w.path, outputs.dir)
+        if self.rank == 0 and rel not in outputs.written:
+            outputs.written.append(rel)
+
+    def write_restart(self, out, outputs):
+        """dump_restart (restart.c:463-983): this rank's Grid under the parameter table as it stands now."""
+        from . import dumps, restart
+        ng = 4
+        par = outputs.par
+        par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
+        par.blocks["time"]["nstep"] = "%d" % self.nstep
+        U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
+        ef = None
+        if self.run.ion:
+            if not hasattr(self.eng, "download_edgeflux"):
+                raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
+            ef = self.eng.download_edgeflux()
+        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
+        restart.write_rst(path, restart.par_dump(par), self.nstep, self.time, self.dt, U, ef)
+
+    def data_output(self, outputs, flag: int):
+        """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
+        outputs.data_output(self, flag)
+
+    def main(self, outputs):
+        """(`run` is taken: the RunConfig of this Driver.)  main.c:501-743: start, forced output, the loop up to <time>tlim / nlim with data_output(0) at the top of every
+        pass, forced output.  Every rank of a multi-rank run calls it and writes its own Grid."""
+        from . import outputs as _outputs
+        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
     def exchange_x3(self):
         """bvals_mhd.c:423-493 for the x3 direction."""
@@ -410,6 +471,63 @@ class Driver:
         self.bvals_mhd(exchange=not self.eng.has_radiation())
         self.niter_trace.append(niter)
         return niter
+
+
+class MeshRun:
+    """main() of the reference built with STATIC_MESH_REFINEMENT for a lib.Mesh (all levels on one GPU; the loop itself is
+    aa_mesh_step): what outputs.run / OutputSet.data_output need -- time, nstep, start, step and the three writers, which loop
+    over the Domains like dump_vtk / dump_binary / dump_history / dump_restart do."""
+
+    def __init__(self, mesh, run: RunConfig):
+        self.mesh, self.run = mesh, run
+        self._hst = {}
+
+    time = property(lambda s: s.mesh.time)
+    dt = property(lambda s: s.mesh.dt)
+    nstep = property(lambda s: s.mesh.nstep)
+
+    def start(self): self.mesh.start()
+    def step(self): return self.mesh.step()
+
+    def write_dump(self, out, outputs):
+        for rel in self.mesh.write_dump(outputs.dir, outputs.basename, out.num, out.out_fmt, out.prim, out.level, out.domain):
+            outputs.written.append(rel)
+
+    def write_history(self, out, outputs):
+        from .history import HistoryWriter
+        t, dt, _ = self.mesh.state()
+        for g, (l, d) in zip(self.mesh.lev, self.mesh.domain_numbers()):
+            if out.level not in (-1, l) or out.domain not in (-1, d):
+                continue
+            w = self._hst.get((out.n, l, d))
+            if w is None:
+                w = self._hst[(out.n, l, d)] = HistoryWriter(outputs.dir, outputs.basename, l, d, out.dat_fmt)
+            vol = 1.0
+            for a in range(3):
+                vol *= g.cfg.Nx[a] * (self.run.dx[a] / float(1 << l))
+            w.dump(t, dt, g.history(), vol, self.run.nscal)
+            rel = os.path.relpath(w.path, outputs.dir)
+            if rel not in outputs.written:
+                outputs.written.append(rel)
+
+    def write_restart(self, out, outputs):
+        """one file for all levels (restart.c:531-770)"""
+        from . import dumps, restart
+        ng = 4
+        t, dt, n = self.mesh.state()
+        par = outputs.par
+        par.blocks.setdefault("time", {})["time"] = "%e" % t
+        par.blocks["time"]["nstep"] = "%d" % n
+        levels = [(g.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal], g.download_edgeflux() if self.run.ion else None)
+                  for g in self.mesh.lev]
+        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
+        restart.write_rst_levels(path, restart.par_dump(par), n, t, dt, levels)
+
+    def data_output(self, outputs, flag: int): outputs.data_output(self, flag)
+
+    def main(self, outputs):
+        from . import outputs as _outputs
+        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
 
 # ==================================================================================================

@@ -1,0 +1,146 @@
+"""Data dumps of the reference: ``out_fmt = vtk`` (dump_vtk.c:28-327) and ``out_fmt = bin`` (dump_binary.c:30-266), with
+``out = cons`` or ``out = prim``.
+
+Both formats are single precision over the ACTIVE zones of one Grid.  A file is a header (text for vtk, a small binary
+record for bin) around *sections* of field data, zones ``[k][j][i]`` with i fastest:
+
+  vtk: ``density`` (n floats) | ``momentum`` / ``velocity`` (3n, the components of a zone next to each other) |
+       ``total_energy`` / ``pressure`` (n) | ``scalar[s]`` / ``specific_scalar[s]`` (n each); big-endian words
+  bin: NVAR = 5 + NSCALARS sections of n floats in ConsS / PrimS order; native (little-endian) words
+
+The writers take the sections from a callable, so the device path (``lib.Grid.dump_section``: the payload is made by the
+kernel of csrc/dump.hip and arrives in file order and byte order) and the host path (``payload_from_block``: the same
+arithmetic in numpy, for engines without a device and as the checker of the kernel) share every byte of header.
+"""
+from __future__ import annotations
+
+import os
+import struct
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+
+VTK, BIN = 1, 2                      # AA_DUMP_VTK / AA_DUMP_BIN of include/athena_amd.h
+FORMATS = {"vtk": VTK, "bin": BIN}
+TINY_NUMBER = 1.0e-20                # defs.h.in:160
+NUM_DIGIT = 4                        # the reference's num_digit
+
+
+def nsections(fmt: int, nscal: int) -> int:
+    return (3 if fmt == VTK else 5) + nscal
+
+
+def section_floats(fmt: int, section: int, nzones: int) -> int:
+    return 3 * nzones if (fmt == VTK and section == 1) else nzones
+
+
+def payload_from_block(U: np.ndarray, fmt: int, prim: bool, gamma: float, nscal: Optional[int] = None) -> List[np.ndarray]:
+    """The sections of a dump from a host block of ACTIVE zones ``[k][j][i][var]`` (d, M1, M2, M3, E[, s0]), each a flat
+    array in the file's dtype.  Primitive variables operation by operation as Cons1D_to_Prim1D (convert_var.c:389-421):
+    ``di = 1/d``, ``V = M*di``, ``P = MAX((E - 0.5*(M1^2 + M2^2 + M3^2)*di)*Gamma_1, TINY_NUMBER)`` -- the macro sends a
+    NaN to TINY_NUMBER -- and ``r = s*di``."""
+    fmt = FORMATS.get(fmt, fmt)
+    nscal = U.shape[-1] - 5 if nscal is None else nscal
+    dt = ">f4" if fmt == VTK else "<f4"
+    d, M1, M2, M3, E = (U[..., c] for c in range(5))
+    with np.errstate(all="ignore"):
+        if prim:
+            di = 1.0 / d
+            P = E - 0.5 * (M1 * M1 + M2 * M2 + M3 * M3) * di
+            P = P * (gamma - 1.0)
+            P = np.where(P > TINY_NUMBER, P, TINY_NUMBER)
+            v = [d, M1 * di, M2 * di, M3 * di, P] + [U[..., 5 + s] * di for s in range(nscal)]
+        else:
+            v = [d, M1, M2, M3, E] + [U[..., 5 + s] for s in range(nscal)]
+        if fmt == VTK:
+            v = [v[0], np.stack(v[1:4], axis=-1), v[4]] + v[5:]
+        return [np.ascontiguousarray(a).astype(dt).reshape(-1) for a in v]
+
+
+def fname(basename: str, level: int, domain: int, num: int, ext: str) -> str:
+    """ath_fname(plev, basename, plev, pdom, num_digit, num, NULL, ext) (ath_files.c:41-130), relative to the run directory."""
+    name = basename + (f"-lev{level}" if level > 0 else "") + (f"-dom{domain}" if domain > 0 else "")
+    name += ".%0*d.%s" % (NUM_DIGIT, num, ext)
+    return os.path.join(f"lev{level}", name) if level > 0 else name
+
+
+def vtk_titles(prim: bool, nscal: int) -> List[bytes]:
+    """The text in front of every section (dump_vtk.c:164-301): every title but the first begins with a newline."""
+    t = [b"SCALARS density float\nLOOKUP_TABLE default\n",
+         b"\nVECTORS velocity float\n" if prim else b"\nVECTORS momentum float\n",
+         (b"\nSCALARS pressure float\n" if prim else b"\nSCALARS total_energy float\n") + b"LOOKUP_TABLE default\n"]
+    for s in range(nscal):
+        t.append((b"\nSCALARS specific_scalar[%d] float\n" if prim else b"\nSCALARS scalar[%d] float\n") % s
+                 + b"LOOKUP_TABLE default\n")
+    return t
+
+
+def vtk_header(nx: Sequence[int], minx: Sequence[float], dx: Sequence[float], time: float, level: int, domain: int,
+               prim: bool) -> bytes:
+    """dump_vtk.c:121-160 (3-D Grids): DIMENSIONS counts the zone CORNERS, the ORIGIN / SPACING / CELL_DATA lines end in a blank."""
+    s = "# vtk DataFile Version 2.0\n"
+    s += "%s vars at time= %e, level= %i, domain= %i\n" % ("PRIMITIVE" if prim else "CONSERVED", time, level, domain)
+    s += "BINARY\nDATASET STRUCTURED_POINTS\n"
+    s += "DIMENSIONS %d %d %d\n" % (nx[0] + 1, nx[1] + 1, nx[2] + 1)
+    s += "ORIGIN %e %e %e \n" % (minx[0], minx[1], minx[2])
+    s += "SPACING %e %e %e \n" % (dx[0], dx[1], dx[2])
+    s += "CELL_DATA %d \n" % (nx[0] * nx[1] * nx[2])
+    return s.encode()
+
+
+def bin_header(nx: Sequence[int], minx: Sequence[float], dx: Sequence[float], time: float, dt: float, gamma: float,
+               nscal: int) -> bytes:
+    """dump_binary.c:111-191: coordsys = -1 (Cartesian), ndata[7] = zones, NVAR, NSCALARS, no self-gravity, no particles;
+    (float)Gamma_1 and 0 (adiabatic); (float)time, (float)dt; the zone centres along x1, x2, x3 (cc_pos.c:36-43) as floats."""
+    b = struct.pack("<i7i", -1, nx[0], nx[1], nx[2], 5 + nscal, nscal, 0, 0)
+    b += np.array([gamma - 1.0, 0.0], dtype="<f4").tobytes()
+    b += np.array([time, dt], dtype="<f4").tobytes()
+    for a in range(3):
+        x = minx[a] + (np.arange(nx[a], dtype=np.float64) + 0.5) * dx[a]
+        b += x.astype("<f4").tobytes()
+    return b
+
+
+def _raw(a) -> memoryview:
+    a = np.ascontiguousarray(a)
+    return memoryview(a).cast("B")
+
+
+def write_vtk(path: str, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, prim: bool, nscal: int,
+              level: int = 0, domain: int = 0) -> None:
+    """``section(i)`` returns section i of the vtk payload (big-endian words, see the module text), as an array or bytes."""
+    with open(path, "wb") as f:
+        f.write(vtk_header(nx, minx, dx, time, level, domain, prim))
+        for i, title in enumerate(vtk_titles(prim, nscal)):
+            f.write(title)
+            f.write(_raw(section(i)))
+
+
+def write_bin(path: str, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, dt: float, gamma: float,
+              prim: bool, nscal: int) -> None:
+    """``section(i)`` returns variable i of the bin payload (native words).  (`prim` does not show in the file: the reference's
+    header does not say which set it holds.)"""
+    with open(path, "wb") as f:
+        f.write(bin_header(nx, minx, dx, time, dt, gamma, nscal))
+        for i in range(5 + nscal):
+            f.write(_raw(section(i)))
+
+
+def write_dump(path: str, fmt, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, dt: float, gamma: float,
+               prim: bool, nscal: int, level: int = 0, domain: int = 0) -> None:
+    fmt = FORMATS.get(fmt, fmt)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    if fmt == VTK:
+        write_vtk(path, section, nx=nx, minx=minx, dx=dx, time=time, prim=prim, nscal=nscal, level=level, domain=domain)
+    elif fmt == BIN:
+        write_bin(path, section, nx=nx, minx=minx, dx=dx, time=time, dt=dt, gamma=gamma, prim=prim, nscal=nscal)
+    else:
+        raise ValueError(f"[write_dump]: format {fmt!r} (vtk or bin)")
+
+
+def write_dump_from_block(path: str, fmt, U: np.ndarray, *, prim: bool, gamma: float, nscal: int, **kw) -> None:
+    """A dump of a host block of active zones (the CPU engines' path)."""
+    pay = payload_from_block(U, fmt, prim, gamma, nscal)
+    write_dump(path, fmt, lambda i: pay[i], prim=prim, gamma=gamma, nscal=nscal, **kw)

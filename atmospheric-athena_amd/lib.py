@@ -119,6 +119,8 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_test_explog": (I, [I, dp, dp, dp]),
         "aa_test_xdiv": (I, [I, dp, dp, dp]),
         "aa_history": (I, [P, dp]),
+        "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),
+        "aa_dump_section": (I, [P, I, I, I, C.POINTER(C.c_float)]),
         "aa_profile_enable": (I, [P, I]), "aa_profile_reset": (I, [P]), "aa_profile_count": (I, [P]),
         "aa_profile_name": (C.c_char_p, [P, I]), "aa_profile_get": (I, [P, I, dp, llp]),
     }
@@ -361,6 +363,46 @@ class Grid:
         """Volume integrals of this Grid in .hst column order (dump_history.c:157-200)."""
         s = np.zeros(9); self._chk(self.L.aa_history(self._h, _dp(s))); return s
 
+    # ---- data dumps (dump_vtk.c / dump_binary.c) ----------------------------------------
+    def dump_sections(self, fmt) -> int:
+        from . import dumps
+        return int(self.L.aa_dump_sections(self._h, dumps.FORMATS.get(fmt, fmt)))
+
+    def dump_section(self, fmt, prim: bool, section: int, out: np.ndarray | None = None) -> np.ndarray:
+        """Section `section` of the vtk / bin payload of the ACTIVE zones, made on the device in file order and byte order
+        (csrc/dump.hip; fmt "vtk" | "bin").  The array holds the file's words: view it as ">f4" (vtk) or "<f4" (bin) for values."""
+        from . import dumps
+        fmt = dumps.FORMATS.get(fmt, fmt)
+        n = int(self.L.aa_dump_section_floats(self._h, fmt, section))
+        if n <= 0:
+            raise AthenaError(f"[dump_section]: no section {section} in format {fmt}")
+        if out is None:
+            out = np.empty(n, dtype=np.float32)
+        assert out.dtype == np.float32 and out.size == n and out.flags.c_contiguous
+        self._chk(self.L.aa_dump_section(self._h, fmt, 1 if prim else 0, section, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def write_dump(self, path: str, fmt, prim: bool, level: int | None = None, domain: int = 0,
+                   time: float | None = None, dt: float | None = None):
+        """dump_vtk / dump_binary of this Grid: the header from the Grid's geometry and MeshS time / dt (or the ones given:
+        a driver that keeps them itself), the sections from the device."""
+        from . import dumps
+        g = self.cfg; r = g.run
+        lev = g.level if level is None else level
+        dx = tuple(r.dx[d] / float(1 << g.level) for d in range(3))
+        if time is None or dt is None:
+            t_, dt_, _ = self.mesh_state()
+            time = t_ if time is None else time; dt = dt_ if dt is None else dt
+        buf = {}
+
+        def section(i):
+            n = int(self.L.aa_dump_section_floats(self._h, dumps.FORMATS.get(fmt, fmt), i))
+            if n not in buf:
+                buf[n] = np.empty(n, dtype=np.float32)
+            return self.dump_section(fmt, prim, i, buf[n])
+        dumps.write_dump(path, fmt, section, nx=g.Nx, minx=g.MinX, dx=dx, time=time, dt=dt, gamma=r.gamma, prim=prim,
+                         nscal=r.nscal, level=lev, domain=domain)
+
     # ---- measurement -------------------------------------------------------------------
     def profile_enable(self, on: bool = True): self.L.aa_profile_enable(self._h, 1 if on else 0)
     def profile_reset(self): self.L.aa_profile_reset(self._h)
@@ -475,6 +517,28 @@ class Mesh:
 
     def start(self):
         self._chk(self.L.aa_mesh_start(self._h)); return self
+
+    def domain_numbers(self):
+        """(level, domain) of every Grid in self.lev: Domains of a level are numbered in deck order (MeshS.Domain[nl][nd])."""
+        seen, out = {}, []
+        for g in self.lev:
+            l = g.cfg.level
+            out.append((l, seen.get(l, 0))); seen[l] = seen.get(l, 0) + 1
+        return out
+
+    def write_dump(self, rundir: str, basename: str, num: int, fmt, prim: bool, level: int = -1, domain: int = -1):
+        """dump_vtk / dump_binary over the Mesh: one file per Domain (level / domain = -1: all), named by ath_fname;
+        -> the relative paths written.  Every level carries the Mesh's time and dt."""
+        from . import dumps
+        ext = {dumps.VTK: "vtk", dumps.BIN: "bin"}[dumps.FORMATS.get(fmt, fmt)]
+        t, dt, n = self.state()
+        out = []
+        for g, (l, d) in zip(self.lev, self.domain_numbers()):
+            if (level == -1 or level == l) and (domain == -1 or domain == d):
+                rel = dumps.fname(basename, l, d, num, ext)
+                g.write_dump(os.path.join(rundir, rel), fmt, prim, level=l, domain=d, time=t, dt=dt)
+                out.append(rel)
+        return out
 
     def step(self):
         it = (C.c_int * len(self.lev))()

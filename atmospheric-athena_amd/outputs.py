@@ -1,0 +1,146 @@
+"""The ``<outputN>`` blocks of a deck: init_output (output.c:171-487) and data_output (:498-569) of the reference for the
+dump formats this package writes -- ``hst`` (history.py), ``rst`` (restart.py), ``vtk`` and ``bin`` (dumps.py), the last two
+with ``out = cons`` (the default) or ``out = prim``.
+
+Keys read per block: ``out_fmt``, ``out``, ``dt`` (required), ``time`` (default: the current time), ``num`` (default 0),
+``level`` / ``domain`` (default -1: all), ``id``, ``dat_fmt``; ``<job>maxout`` says how many blocks are looked at.  Everything
+else the reference knows -- single-variable outputs (``out = d``, ``P``, ``V1`` ... with slices), ``out_fmt = tab | ppm | pgm |
+pdf``, user outputs by ``name =`` -- is refused by ``from_par`` with the block and the value named: a run must not find out at
+its first dump.
+
+``data_output(target, flag)`` drives a *target*: anything with ``time`` and the three writers ``write_dump(out, self)``,
+``write_history(out, self)``, ``write_restart(out, self)`` (driver.Driver and driver.MeshRun).  File names are ath_fname's
+(dumps.fname); rank r of a multi-rank run writes under ``id<r>/`` with ``-id<r>`` in the base name for r > 0 (main.c:227-232,
+:785-850), every rank its own Grid.
+"""
+from __future__ import annotations
+
+import os
+import warnings
+from dataclasses import dataclass
+from typing import List, Optional
+
+from .athinput import ParError, ParTable
+
+MAXOUT_DEFAULT = 10
+DUMPS = ("vtk", "bin")
+
+
+@dataclass
+class Output:
+    """OutputS of the reference, the members the dumps use."""
+    n: int                      # the N of <outputN>
+    out_fmt: str
+    out: str                    # "cons" | "prim"
+    t: float                    # next output time
+    dt: float
+    num: int                    # next output number
+    level: int = -1
+    domain: int = -1
+    id: str = ""
+    dat_fmt: Optional[str] = None
+
+    @property
+    def prim(self) -> bool:
+        return self.out == "prim"
+
+
+class OutputSet:
+    def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int):
+        self.par, self.outs, self.rst = par, outs, rst
+        self.rank, self.nranks = rank, nranks
+        self.basename = par.gets("job", "problem_id")
+        self.dir = os.path.join(rundir, f"id{rank}") if nranks > 1 else rundir
+        self.written: List[str] = []          # relative to `dir`, in the order of writing
+
+    @classmethod
+    def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1) -> "OutputSet":
+        """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
+        r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries."""
+        if nranks > 1 and rank != 0:
+            par.blocks["job"]["problem_id"] = "%s-id%d" % (par.gets("job", "problem_id"), rank)
+        maxout = par.geti_def("job", "maxout", MAXOUT_DEFAULT)
+        outs: List[Output] = []
+        rst = None
+        for n in range(1, maxout + 1):
+            block = f"output{n}"
+            if not par.exist(block, "out_fmt") and not par.exist(block, "name"):
+                warnings.warn(f"[init_output]: neither {block}/out_fmt, nor {block}/name exist")      # output.c:195-199: not fatal
+                continue
+            if par.exist(block, "name"):
+                raise ParError(f"[init_output]: <{block}> name = {par.gets(block, 'name')}: user-defined outputs are not built")
+            fmt = par.gets(block, "out_fmt")
+            out = par.gets(block, "out") if par.exist(block, "out") else "cons"
+            if out not in ("cons", "prim"):
+                raise ParError(f"[init_output]: <{block}> out = {out} (out_fmt = {fmt}): single-variable outputs are not built; "
+                               "dumps take out = cons or out = prim")
+            ok = ("hst", "rst", "vtk", "bin") if out == "cons" else DUMPS
+            if fmt not in ok:
+                raise ParError(f"[init_output]: Unsupported dump mode for {block}/out_fmt={fmt} for out={out} "
+                               f"(built: {', '.join(ok)})")
+            o = Output(n=n, out_fmt=fmt, out=out,
+                       t=par.getd_def(block, "time", time), num=par.geti_def(block, "num", 0), dt=par.getd(block, "dt"),
+                       level=par.geti_def(block, "level", -1), domain=par.geti_def(block, "domain", -1),
+                       id=par.gets(block, "id") if par.exist(block, "id") else f"out{n}",
+                       dat_fmt=par.gets(block, "dat_fmt") if par.exist(block, "dat_fmt") else None)
+            par.blocks[block].setdefault("id", o.id)
+            par.blocks[block].setdefault("out", out)
+            if fmt == "rst":
+                rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
+            else:
+                outs.append(o)
+        return cls(par, outs, rst, rundir, rank, nranks)
+
+    def data_output(self, target, flag: int) -> None:
+        """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt
+        ONCE (output.c:509-512).  The restart dump goes first, after every block's next number and time have been written
+        back into the parameter table (:526-543), so that a restarted run continues the numbering."""
+        time = target.time
+        fire = []
+        for o in self.outs:
+            f = bool(flag)
+            if time >= o.t:
+                o.t += o.dt
+                f = True
+            fire.append(f)
+        r = self.rst
+        if r is not None:
+            f = bool(flag)
+            if time >= r.t:
+                r.t += r.dt
+                f = True
+            if f:
+                for o, fo in zip(self.outs, fire):
+                    b = self.par.blocks[f"output{o.n}"]
+                    b["num"] = "%d" % (o.num + 1 if fo else o.num)
+                    b["time"] = "%.15e" % o.t
+                b = self.par.blocks[f"output{r.n}"]
+                b["num"] = "%d" % (r.num + 1)
+                b["time"] = "%.15e" % r.t
+                target.write_restart(r, self)
+                r.num += 1
+        for o, fo in zip(self.outs, fire):
+            if fo:
+                if o.out_fmt == "hst":
+                    target.write_history(o, self)
+                else:
+                    target.write_dump(o, self)
+                o.num += 1
+
+    def path(self, rel: str) -> str:
+        """The place of a file named relative to this rank's run directory; remembers it in `written`."""
+        p = os.path.join(self.dir, rel)
+        os.makedirs(os.path.dirname(p) or ".", exist_ok=True)
+        self.written.append(rel)
+        return p
+
+
+def run(target, outputs: OutputSet, tlim: float, nlim: int = -1) -> None:
+    """main() of the reference around the loop: forced output after the start (main.c:501), data_output(0) at the top of every
+    pass (:524), forced output after the loop (:743).  `target`: start(), step(), time, nstep and the writers."""
+    target.start()
+    outputs.data_output(target, 1)
+    while target.time < tlim and (nlim < 0 or target.nstep < nlim):
+        outputs.data_output(target, 0)
+        target.step()
+    outputs.data_output(target, 1)

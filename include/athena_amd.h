@@ -251,6 +251,22 @@ int aa_test_explog(int n, const double *x, double *y_exp, double *y_log);  /* th
  *      caller's.                                                                               */
 int aa_history(aa_grid *g, double sums[9]);
 
+/* ---- dump_vtk.c:28-327 / dump_binary.c:30-266: the single-precision payload of a data dump, made on the device from the
+ *      ACTIVE zones and delivered in file order, one section at a time (zones [k][j][i], i fastest, no ghost zones):
+ *        AA_DUMP_VTK  0 density | 1 momentum or velocity, 3 floats per zone | 2 total energy or pressure | 3.. scalars;
+ *                     every word big-endian as the reference writes it (ath_bswap)
+ *        AA_DUMP_BIN  NVAR = 5 + NSCALARS sections in ConsS / PrimS order, native byte order
+ *      prim != 0: primitive variables exactly as Cons1D_to_Prim1D (convert_var.c:389-421; the same bits from the default and
+ *      the strict library).  The header text / binary header around the sections is the caller's (they hold no field data).
+ *      host_dst is any host memory of aa_dump_section_floats() floats: the library stages through a page-locked bounce
+ *      buffer of its own (two halves of AA_DUMP_CHUNK_FLOATS floats, default 2^23).  Like aa_download_cons the call uses the
+ *      face-state area (allowed between aa_integrate_begin and aa_integrate_3d_ctu) and changes no state.                 */
+#define AA_DUMP_VTK 1
+#define AA_DUMP_BIN 2
+int       aa_dump_sections(const aa_grid *g, int fmt);                        /* sections of a dump (0: unknown format) */
+long long aa_dump_section_floats(const aa_grid *g, int fmt, int section);     /* n or 3n; 0 past the last section       */
+int       aa_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
+
 /* ---- measurement: per-kernel accumulated device time (hipEvent pairs on the stream) */
 int         aa_profile_enable(aa_grid *g, int on);
 int         aa_profile_reset(aa_grid *g);
