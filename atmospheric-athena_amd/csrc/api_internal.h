@@ -124,6 +124,10 @@ int slabs_ion_run_phased(aa_grid *g, double limit, int *niter_out, double *dt_do
 int slabs_history(aa_grid *g, double *sums);
 int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away
+int dump_prepare(aa_grid *g);         // dump.hip: the bounce buffer, its stream and events, made on first use (shared with restart.hip)
+void dump_copy_out(float *dst, const float *src, size_t n);    // dump.hip: bounce buffer <-> the caller's memory on a few threads
+int slabs_rst_section(aa_grid *g, int section, double *host, int put);
+int rst_section_grid(aa_grid *g, int section, double *host, long long n, int put);   // restart.hip: the first n doubles of a section of one Grid
 void slabs_push_state(aa_grid *g);
 // evaluation of a StaticGravPot callback at zone centres and lower faces of a Grid (api.hip)
 void aa_eval_grav_tables(const aa_params &p, const double dx[3], int N1, int N2, int N3, aa_gravpot_fn fn, std::vector<double> t[4]);

@@ -102,7 +102,7 @@ static size_t dump_capacity(const aa_grid *g)
   return (cap + 3) & ~(size_t)3;
 }
 
-static int dump_prepare(aa_grid *g)
+int dump_prepare(aa_grid *g)
 {
   if (g->dump_host) return 0;
   const size_t cap = dump_capacity(g);
@@ -114,8 +114,8 @@ static int dump_prepare(aa_grid *g)
 }
 
 // bounce buffer -> the caller's memory (pageable as a rule): large pieces on a few threads, a single one does not reach the
-// rate of the link
-static void dump_copy_out(float *dst, const float *src, size_t n)
+// rate of the link (restart.hip uses it in both directions)
+void dump_copy_out(float *dst, const float *src, size_t n)
 {
   const size_t bytes = n*sizeof(float);
   if (bytes < ((size_t)4 << 20)) { memcpy(dst, src, bytes); return; }

@@ -1,0 +1,193 @@
+// restart.hip -- the payload of the reference's restart dumps (restart.c:463-983, read back by restart_grids :52-456) to and
+// from the resident state.
+//
+// A restart file holds, per Grid and per variable, exactly the ACTIVE zones [k][j][i] in double precision -- the SoA arrays
+// of DevGrid with the ghost shell stripped -- one labelled "section" after the other:
+//   DENSITY | 1-MOMENTUM | 2-MOMENTUM | 3-MOMENTUM | ENERGY | EDGEFLUX (ion radiation: (Nx1+1)(Nx2+1)(Nx3+1), dense) | SCALAR n
+// A section travels in pieces through the machinery of the data dumps (dump.hip): the idle face-state area as staging buffer,
+// the page-locked bounce buffer of two halves, the second stream and its events, the threaded host copy.
+//   get: a streaming kernel gathers a piece in file order into a staging slot, the copy of one piece overlaps the kernel and
+//        the host copy of its neighbours (as aa_dump_section);
+//   put: the inverse -- host -> bounce half -> staging slot -> a scatter kernel that writes ACTIVE zones only.
+// EDGEFLUX is dense on the device: the same pipeline without kernels and without the staging slots.
+// A piece is a range of the section's doubles, not a number of rows: with an odd Nx1 the two doubles of a thread may lie
+// in two rows, and a piece may begin and end inside one.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+#include "api_internal.h"
+
+using namespace aa;
+
+// doubles [first, first + n) of a section of variable array `src` (one field of DevGrid.U), first = row0*Nx1 + i0 with
+// row = k*Nx2 + j over the active zones; dst is 16-byte aligned.  Two consecutive doubles per thread, stored at once; every
+// load is unconditional (past the end of the piece: the last double again).
+__global__ void __launch_bounds__(256) k_rst_gather(DevGrid g, const Real *__restrict__ src, unsigned row0, unsigned i0, unsigned n,
+                                                    Real *__restrict__ dst)
+{
+  const unsigned o0 = 2u*(blockIdx.x*256u + threadIdx.x);
+  if (o0 >= n) return;
+  const unsigned nx1 = (unsigned)g.Nx1, nx2 = (unsigned)g.Nx2;
+  Real v[2];
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    const unsigned o = (o0 + q < n) ? o0 + q : n - 1u;
+    const unsigned t = i0 + o, r = t/nx1, i = t - r*nx1, row = row0 + r;
+    const unsigned k = row/nx2, j = row - k*nx2;
+    v[q] = src[(long)(k + AA_NGHOST_)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)];
+  }
+  if (o0 + 1u < n) *(double2*)(dst + o0) = make_double2(v[0], v[1]);
+  else dst[o0] = v[0];
+}
+
+// the inverse: doubles [first, first + n) of a section from `src` (16-byte aligned) into the active zones of `dst`
+__global__ void __launch_bounds__(256) k_rst_scatter(DevGrid g, Real *__restrict__ dst, unsigned row0, unsigned i0, unsigned n,
+                                                     const Real *__restrict__ src)
+{
+  const unsigned o0 = 2u*(blockIdx.x*256u + threadIdx.x);
+  if (o0 >= n) return;
+  const unsigned nx1 = (unsigned)g.Nx1, nx2 = (unsigned)g.Nx2;
+  Real v[2];
+  const bool pair = o0 + 1u < n;
+  if (pair) { const double2 w = *(const double2*)(src + o0); v[0] = w.x; v[1] = w.y; }
+  else v[0] = v[1] = src[o0];
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    if (q && !pair) break;
+    const unsigned t = i0 + o0 + q, r = t/nx1, i = t - r*nx1, row = row0 + r;
+    const unsigned k = row/nx2, j = row - k*nx2;
+    dst[(long)(k + AA_NGHOST_)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)] = v[q];
+  }
+}
+
+static int rst_nsections(const aa_grid *g) { return 5 + (g->p.ion ? 1 : 0) + g->p.nscal; }
+static bool rst_is_edgeflux(const aa_grid *g, int s) { return g->p.ion && s == 5; }
+// the field of DevGrid.U behind a section that is not EDGEFLUX
+static int rst_section_var(const aa_grid *g, int s) { return s < 5 ? s : s - (g->p.ion ? 1 : 0); }
+
+static long long rst_doubles(const aa_grid *g, int s)
+{
+  const int *nx = g->p.Nx;
+  if (rst_is_edgeflux(g, s)) return (long long)(nx[0] + 1)*(nx[1] + 1)*(nx[2] + 1);
+  return (long long)nx[0]*nx[1]*nx[2];
+}
+
+// one Grid on one device (the current one); `n` doubles of the section from its start (a slab's share of EDGEFLUX may leave
+// out the plane its upper neighbour owns)
+int rst_section_grid(aa_grid *g, int section, double *host, long long n, int put)
+{
+  { int rc = dump_prepare(g); if (rc) return rc; }
+  g->inner_swept = false;          // the face-state area is the staging buffer (see aa_integrate_begin in athena_amd.h)
+  const bool ef = rst_is_edgeflux(g, section);
+  if (ef && !put) { int rc = aa_edgeflux_ready(g); if (rc) return rc; }
+  const size_t per = g->dump_cap/2;                       // doubles per half: even, so that every piece starts 16-byte aligned
+  Real *field = ef ? g->d.edgeflux : g->d.U + (size_t)rst_section_var(g, section)*(size_t)g->d.nc;
+  Real *stage = g->d.LR, *pinned = (Real*)g->dump_host;
+  const unsigned nx1 = (unsigned)g->d.Nx1;
+  if (put) {
+    // whatever is queued on the Grid's stream may still read the state and the staging area
+    HIPCHK(hipEventRecord(g->dump_ev[0], g->st));
+    HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[0], 0));
+  }
+  long long prev_first = -1; size_t prev_n = 0; int c = 0;
+  for (long long first = 0; first < n; first += (long long)per, c++) {
+    const size_t np = (first + (long long)per <= n) ? per : (size_t)(n - first);
+    const int slot = c & 1;
+    Real *dev = ef ? field + first : stage + (size_t)slot*per, *pin = pinned + (size_t)slot*per;
+    const unsigned row0 = (unsigned)(first/nx1), i0 = (unsigned)(first - (long long)row0*nx1);
+    const unsigned blocks = (unsigned)((np + 511)/512);
+    if (!put) {
+      if (!ef) {
+        { Scope sc(g, "rst_gather");
+          hipLaunchKernelGGL(k_rst_gather, dim3(blocks), dim3(256), 0, g->st, (DevGrid)g->d, (const Real*)field, row0, i0, (unsigned)np, dev); }
+        HIPCHK(hipGetLastError());
+      }
+      HIPCHK(hipEventRecord(g->dump_ev[slot], g->st));
+      HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[slot], 0));
+      HIPCHK(hipMemcpyAsync(pin, dev, np*sizeof(Real), hipMemcpyDeviceToHost, g->dump_st));
+      HIPCHK(hipEventRecord(g->dump_ev[2 + slot], g->dump_st));
+      if (prev_first >= 0) {       // the piece before this one: hand it out while this one travels
+        HIPCHK(hipEventSynchronize(g->dump_ev[2 + (slot ^ 1)]));
+        dump_copy_out((float*)(host + prev_first), (const float*)(pinned + (size_t)(slot ^ 1)*per), 2*prev_n);
+      }
+    } else {
+      if (c >= 2) {                // this half's last piece has left the host, and its staging slot has been scattered
+        HIPCHK(hipEventSynchronize(g->dump_ev[2 + slot]));
+        if (!ef) HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[slot], 0));
+      }
+      dump_copy_out((float*)pin, (const float*)(host + first), 2*np);
+      HIPCHK(hipMemcpyAsync(dev, pin, np*sizeof(Real), hipMemcpyHostToDevice, g->dump_st));
+      HIPCHK(hipEventRecord(g->dump_ev[2 + slot], g->dump_st));
+      if (!ef) {
+        HIPCHK(hipStreamWaitEvent(g->st, g->dump_ev[2 + slot], 0));
+        { Scope sc(g, "rst_scatter");
+          hipLaunchKernelGGL(k_rst_scatter, dim3(blocks), dim3(256), 0, g->st, (DevGrid)g->d, field, row0, i0, (unsigned)np, (const Real*)dev); }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(g->dump_ev[slot], g->st));
+      }
+    }
+    prev_first = first; prev_n = np;
+  }
+  if (!put) {
+    if (prev_first >= 0) {
+      const int slot = (c - 1) & 1;
+      HIPCHK(hipEventSynchronize(g->dump_ev[2 + slot]));
+      dump_copy_out((float*)(host + prev_first), (const float*)(pinned + (size_t)slot*per), 2*prev_n);
+    }
+    return 0;
+  }
+  // every piece has landed before the call returns: the next user of the state or of the staging area finds them complete
+  HIPCHK(hipStreamSynchronize(g->dump_st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  g->cfl_ready = false; g->inner_swept = false; g->active_dirty = true;      // the device holds what no host block does
+  if (ef) g->ef_stale = false;
+  return 0;
+}
+
+extern "C" {
+
+int aa_rst_sections(const aa_grid *g) { return g ? rst_nsections(g) : 0; }
+
+int aa_rst_section_label(const aa_grid *g, int section, char *buf, int n)
+{
+  if (!g || !buf || n <= 0) return aa_fail(-1, "[aa_rst_section_label]: null argument");
+  if (section < 0 || section >= rst_nsections(g)) return aa_fail(-1, "[aa_rst_section_label]: section %d of %d", section, rst_nsections(g));
+  static const char *const lab[5] = {"DENSITY", "1-MOMENTUM", "2-MOMENTUM", "3-MOMENTUM", "ENERGY"};
+  if (section < 5) snprintf(buf, (size_t)n, "%s", lab[section]);
+  else if (rst_is_edgeflux(g, section)) snprintf(buf, (size_t)n, "EDGEFLUX");
+  else snprintf(buf, (size_t)n, "SCALAR %d", rst_section_var(g, section) - 5);
+  return 0;
+}
+
+long long aa_rst_section_doubles(const aa_grid *g, int section)
+{
+  if (!g || section < 0 || section >= rst_nsections(g)) return 0;
+  return rst_doubles(g, section);
+}
+
+int aa_rst_section_get(aa_grid *g, int section, double *host)
+{
+  if (!g || !host) return aa_fail(-1, "[aa_rst_section_get]: null argument");
+  if (section < 0 || section >= rst_nsections(g)) return aa_fail(-1, "[aa_rst_section_get]: section %d of %d", section, rst_nsections(g));
+  if (!g->slab.empty()) return slabs_rst_section(g, section, host, 0);
+  return rst_section_grid(g, section, host, rst_doubles(g, section), 0);
+}
+
+int aa_rst_section_put(aa_grid *g, int section, const double *host)
+{
+  if (!g || !host) return aa_fail(-1, "[aa_rst_section_put]: null argument");
+  if (section < 0 || section >= rst_nsections(g)) return aa_fail(-1, "[aa_rst_section_put]: section %d of %d", section, rst_nsections(g));
+  if (!g->slab.empty()) return slabs_rst_section(g, section, const_cast<double*>(host), 1);
+  return rst_section_grid(g, section, const_cast<double*>(host), rst_doubles(g, section), 1);
+}
+
+// main.c:398-451 of a restarted run: the ghost zones and the radiation boundary, and NOT new_dt -- the file's dt is the next step's
+int aa_resume(aa_grid *g)
+{
+  int rc;
+  if (!g) return aa_fail(-1, "[aa_resume]: null argument");
+  if ((rc = aa_bvals_mhd(g))) return rc;
+  return aa_bvals_ionrad(g);
+}
+
+}  // extern "C"

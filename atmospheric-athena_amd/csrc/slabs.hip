@@ -288,6 +288,26 @@ int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_d
   }
   return 0;
 }
+// a section of a restart dump (restart.hip): a slab's share of a section is a contiguous range of planes.  Of EDGEFLUX a slab
+// hands out the planes below its upper neighbour's first one (the last slab all of its Nx3 + 1), and takes all of its own
+// (as slabs_download_edgeflux / slabs_upload_edgeflux)
+int slabs_rst_section(aa_grid *g, int section, double *host, int put)
+{
+  DevGuard keep;
+  HALO_FLUSH(g);
+  SlabLink *L = g->link;
+  g->inner_swept = false;
+  const bool ef = g->p.ion && section == 5;
+  const size_t pl = ef ? (size_t)(g->p.Nx[0] + 1)*(g->p.Nx[1] + 1) : (size_t)g->p.Nx[0]*g->p.Nx[1];
+  for (int s = 0; s < L->n; s++) {
+    SLAB_DEV(L, s);
+    const int np = L->nk[s] + ((ef && (put || s == L->n - 1)) ? 1 : 0);
+    int rc = rst_section_grid(g->slab[s], section, host + (size_t)L->k0[s]*pl, (long long)np*(long long)pl, put);
+    if (rc) return rc;
+  }
+  if (put) { g->cfl_ready = false; g->active_dirty = true; if (ef) g->ef_stale = false; }
+  return 0;
+}
 int slabs_upload_edgeflux(aa_grid *g, const double *ef)
 {
   DevGuard keep;

@@ -644,6 +644,18 @@ int aa_mesh_start(aa_mesh *m)
   return aa_mesh_new_dt(m);
 }
 
+// main.c:398-451 of a restarted run: aa_mesh_start without new_dt -- the file's dt is the next step's
+int aa_mesh_resume(aa_mesh *m)
+{
+  int rc;
+  if ((rc = aa_mesh_restrict_correct(m))) return rc;
+  for (int l = 0; l < m->nl; l++) {
+    if ((rc = aa_bvals_mhd(m->lev[l]))) return rc;
+    if ((rc = aa_bvals_ionrad(m->lev[l]))) return rc;
+  }
+  return aa_mesh_prolongate(m);
+}
+
 // one pass of main.c:519-669 with STATIC_MESH_REFINEMENT; niter[l] = radiation sub-cycles of level l
 int aa_mesh_step(aa_mesh *m, int *niter)
 {

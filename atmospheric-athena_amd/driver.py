@@ -35,7 +35,8 @@ class HipEngine:
     """One slab on one MI355X, through include/athena_amd.h."""
 
     def __init__(self, grid: GridConfig, device: int = 0, strict: Optional[bool] = None, use_torch_stream: bool = True,
-                 nslab: int = 1):
+                 nslab: int = 1, initial: bool = True):
+        """initial = False: no problem generator, the state comes from a restart dump (lib.setup_problem)"""
         import torch
         from . import lib
         self.torch = torch
@@ -43,7 +44,7 @@ class HipEngine:
         torch.cuda.set_device(device)
         # nslab > 1: the library cuts this Grid into x3 slabs itself (csrc/slabs.hip; one stream per slab, so the
         # caller's stream is not handed over)
-        self.g = lib.setup_problem(grid, device, strict, nslab=nslab)
+        self.g = lib.setup_problem(grid, device, strict, nslab=nslab, initial=initial)
         if use_torch_stream and nslab == 1:
             # run the kernels on torch's current stream so that torch.distributed collectives and
             # torch.cuda.Event timing are ordered with them
@@ -112,6 +113,9 @@ class HipEngine:
     def has_radiation(self) -> bool: return self.g.has_radplane()      # main.c:546, as aa_step: the ion step runs iff nradplane > 0
     def step_local(self) -> int: return self.g.step()
     def start_local(self): self.g.start()
+    def resume_local(self): self.g.resume()
+    def write_rst_payload(self, f): self.g.write_rst_payload(f)
+    def read_rst_payload(self, f): self.g.read_rst_payload(f)
     def mesh_state(self): return self.g.mesh_state()
 
     # halo
@@ -143,14 +147,17 @@ class Driver:
     """main() of the reference for one process of an N-process run."""
 
     def __init__(self, run: RunConfig, engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0,
-                 strict: Optional[bool] = None, p2: int = 1):
-        """p2 > 1: an NGrid_x2 x NGrid_x3 = p2 x (nranks / p2) pencil decomposition (init_mesh.c:526-620) instead of x3 slabs"""
+                 strict: Optional[bool] = None, p2: int = 1, initial: bool = True):
+        """p2 > 1: an NGrid_x2 x NGrid_x3 = p2 x (nranks / p2) pencil decomposition (init_mesh.c:526-620) instead of x3 slabs;
+        initial = False: the product engine skips the problem generator (from_restart loads the state)"""
         self.run = run
         self.rank, self.nranks = rank, nranks
         if p2 < 1 or nranks % p2:
             raise ValueError(f"{nranks} ranks cannot be dealt {p2} along x2")
         self.grid = pencil(run, rank, p2, nranks // p2)
-        self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict)
+        self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict, initial=initial)
+        self.restarted = False    # from_restart: start() is the restarted run's, outputs.run skips the forced first output
+        self.par = None           # the parameter table this Driver was built from (from_restart)
         self.time, self.dt, self.nstep = 0.0, 0.0, 0
         self.niter_trace: List[int] = []
         self._hst = {}            # HistoryWriter per <outputN> block with out_fmt = hst
@@ -165,6 +172,38 @@ class Driver:
             self.torch, self.dist = torch, dist
             assert dist.is_initialized() and dist.get_world_size() == nranks and dist.get_rank() == rank
             self._sdev = getattr(self.eng, "scalar_device", torch.device("cpu"))
+
+    @classmethod
+    def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
+                     engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
+                     p2: int = 1) -> "Driver":
+        """``athena -r path [block/key=value ...]`` (main.c:168-173, :216-288; restart_grids, restart.c:52-456).  `path` is
+        rank 0's file: every rank takes the parameter table from it, with the overrides on top (an unknown key is an error;
+        time/nlim and time/tlim extend a run), and reads its own Grid from restart.rank_path(path, rank).  The problem
+        generator does not run; the hooks are registered as by problem_read_restart.  The Driver keeps the table as `.par`:
+        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block."""
+        from . import config, restart
+        head0 = restart.read_head(path)
+        par = head0["par"].cmdline(overrides)
+        run = config.from_par(par, problem)
+        if integrator not in ("ctu", "vl", "ctu-noh"):
+            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
+        run.integrator, run.order = integrator, order
+        d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
+        head = head0 if rank == 0 else restart.read_head(restart.rank_path(path, rank))
+        head["levels"] = restart.index_sections(head, [d.grid.Nx], run.nscal, run.ion)
+        if hasattr(d.eng, "read_rst_payload"):
+            with open(head["path"], "rb") as f:
+                f.seek(head["offset"])
+                d.eng.read_rst_payload(f)
+        elif hasattr(d.eng, "load_state"):
+            d.eng.load_state(*restart.read_state(head, 0, d.grid.Nx, run.nscal))
+        else:
+            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_payload or load_state)")
+        d.time, d.dt, d.nstep = head["time"], head["dt"], head["nstep"]
+        d.eng.set_mesh_state(d.time, d.dt, d.nstep)
+        d.restarted, d.par = True, par
+        return d
 
     # ---- collectives ------------------------------------------------------------------
     def _allreduce(self, vals, op):
@@ -223,7 +262,7 @@ class Driver:
             return
         w = self._hst.get(out.n)
         if w is None:
-            w = self._hst[out.n] = HistoryWriter(outputs.dir, outputs.basename, 0, 0, out.dat_fmt)
+            w = self._hst[out.n] = HistoryWriter(outputs.dir, outputs.basename, 0, 0, out.dat_fmt, num=out.num)
         self.dump_history(w)                      # (every rank takes part in the sum; rank 0 writes)
         rel = os.path.relpath(w.path, outputs.dir)
         if self.rank == 0 and rel not in outputs.written:
@@ -236,6 +275,13 @@ class Driver:
         par = outputs.par
         par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
         par.blocks["time"]["nstep"] = "%d" % self.nstep
+        if hasattr(self.eng, "write_rst_payload"):        # the sections come from the device in file order (csrc/restart.hip)
+            path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
+            with open(path, "wb") as f:
+                restart.write_header(f, restart.par_dump(par), self.nstep, self.time, self.dt)
+                self.eng.write_rst_payload(f)
+                restart.write_trailer(f)
+            return
         U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
         ef = None
         if self.run.ion:
@@ -436,6 +482,15 @@ class Driver:
 
     # ---- main.c ---------------------------------------------------------------------------------
     def start(self):                # main.c:412-451
+        if self.restarted:          # main.c:398-451 after restart_grids: the ghost zones, and NO new_dt -- the file's dt is the next step's
+            if not self.distributed and hasattr(self.eng, "resume_local"):
+                self.eng.set_mesh_state(self.time, self.dt, self.nstep)
+                self.eng.resume_local()
+                return
+            self.eng.set_mesh_state(self.time, self.dt, self.nstep)
+            self.bvals_mhd()
+            self.eng.bvals_ionrad()
+            return
         if not self.distributed and hasattr(self.eng, "start_local"):
             self.eng.start_local()
             self.time, self.dt, self.nstep = self.eng.mesh_state()
@@ -481,12 +536,42 @@ class MeshRun:
     def __init__(self, mesh, run: RunConfig):
         self.mesh, self.run = mesh, run
         self._hst = {}
+        self.restarted = False
+        self.par = None
+
+    @classmethod
+    def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
+                     device: int = 0, strict: Optional[bool] = None) -> "MeshRun":
+        """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770)."""
+        from . import config, lib, restart
+        head = restart.read_head(path)
+        par = head["par"].cmdline(overrides)
+        run = config.from_par(par, problem)
+        if integrator not in ("ctu", "vl", "ctu-noh"):
+            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
+        run.integrator, run.order = integrator, order
+        grids = config.levels(par, run)
+        head["levels"] = restart.index_sections(head, [g.Nx for g in grids], run.nscal, run.ion)
+        mesh = lib.Mesh(grids, device, strict, initial=False)
+        with open(path, "rb") as f:
+            f.seek(head["offset"])
+            for g in mesh.lev:
+                g.read_rst_payload(f)
+        mesh.set_state(head["time"], head["dt"], head["nstep"])
+        m = cls(mesh, run)
+        m.restarted, m.par = True, par
+        return m
 
     time = property(lambda s: s.mesh.time)
     dt = property(lambda s: s.mesh.dt)
     nstep = property(lambda s: s.mesh.nstep)
 
-    def start(self): self.mesh.start()
+    def start(self):
+        if self.restarted:
+            self.mesh.resume()
+        else:
+            self.mesh.start()
+
     def step(self): return self.mesh.step()
 
     def write_dump(self, out, outputs):
@@ -501,7 +586,7 @@ class MeshRun:
                 continue
             w = self._hst.get((out.n, l, d))
             if w is None:
-                w = self._hst[(out.n, l, d)] = HistoryWriter(outputs.dir, outputs.basename, l, d, out.dat_fmt)
+                w = self._hst[(out.n, l, d)] = HistoryWriter(outputs.dir, outputs.basename, l, d, out.dat_fmt, num=out.num)
             vol = 1.0
             for a in range(3):
                 vol *= g.cfg.Nx[a] * (self.run.dx[a] / float(1 << l))
@@ -513,15 +598,16 @@ class MeshRun:
     def write_restart(self, out, outputs):
         """one file for all levels (restart.c:531-770)"""
         from . import dumps, restart
-        ng = 4
         t, dt, n = self.mesh.state()
         par = outputs.par
         par.blocks.setdefault("time", {})["time"] = "%e" % t
         par.blocks["time"]["nstep"] = "%d" % n
-        levels = [(g.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal], g.download_edgeflux() if self.run.ion else None)
-                  for g in self.mesh.lev]
         path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
-        restart.write_rst_levels(path, restart.par_dump(par), n, t, dt, levels)
+        with open(path, "wb") as f:                       # the sections of every level from the device in file order
+            restart.write_header(f, restart.par_dump(par), n, t, dt)
+            for g in self.mesh.lev:
+                g.write_rst_payload(f)
+            restart.write_trailer(f)
 
     def data_output(self, outputs, flag: int): outputs.data_output(self, flag)
 

@@ -45,15 +45,16 @@ def format_row(values: Sequence[float], dat_fmt: Optional[str] = None) -> str:
 
 
 class HistoryWriter:
-    """dump_history(pM, pOut) for one Domain; appends like the reference (fopen "a", :353)."""
+    """dump_history(pM, pOut) for one Domain; appends like the reference (fopen "a", :353).  `num`: the <outputN> block's
+    number when the run begins -- the header goes out only with num == 0 (:353-361), so a resumed run adds rows and no header."""
 
     def __init__(self, rundir: str, basename: str, level: int = 0, domain: int = 0,
-                 dat_fmt: Optional[str] = None):
+                 dat_fmt: Optional[str] = None, num: int = 0):
         d = os.path.join(rundir, f"lev{level}") if level > 0 else rundir
         os.makedirs(d, exist_ok=True)
         name = basename + (f"-lev{level}" if level > 0 else "") + (f"-dom{domain}" if domain > 0 else "")
         self.path = os.path.join(d, name + ".hst")
-        self.level, self.domain, self.dat_fmt, self.num = level, domain, dat_fmt, 0
+        self.level, self.domain, self.dat_fmt, self.num = level, domain, dat_fmt, int(num)
 
     def dump(self, time: float, dt: float, sums: np.ndarray, volume: float, nscal: int):
         """sums: aa_history() of the Domain (already added over its Grids)."""

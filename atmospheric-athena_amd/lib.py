@@ -121,6 +121,9 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_history": (I, [P, dp]),
         "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),
         "aa_dump_section": (I, [P, I, I, I, C.POINTER(C.c_float)]),
+        "aa_rst_sections": (I, [P]), "aa_rst_section_label": (I, [P, I, C.c_char_p, I]), "aa_rst_section_doubles": (LL, [P, I]),
+        "aa_rst_section_get": (I, [P, I, dp]), "aa_rst_section_put": (I, [P, I, dp]),
+        "aa_resume": (I, [P]), "aa_mesh_resume": (I, [P]),
         "aa_profile_enable": (I, [P, I]), "aa_profile_reset": (I, [P]), "aa_profile_count": (I, [P]),
         "aa_profile_name": (C.c_char_p, [P, I]), "aa_profile_get": (I, [P, I, dp, llp]),
     }
@@ -286,6 +289,10 @@ class Grid:
     def apply_pinned_cells(self): self._chk(self.L.aa_apply_pinned_cells(self._h))
     def start(self): self._chk(self.L.aa_start(self._h))
 
+    def resume(self):
+        """The start sequence of a restarted run (main.c:398-451): bvals_mhd and bvals_ionrad, NO new_dt."""
+        self._chk(self.L.aa_resume(self._h))
+
     def ion_radtransfer_3d(self) -> int:
         n = C.c_int(); self._chk(self.L.aa_ion_radtransfer_3d(self._h, C.byref(n))); return n.value
 
@@ -403,6 +410,58 @@ class Grid:
         dumps.write_dump(path, fmt, section, nx=g.Nx, minx=g.MinX, dx=dx, time=time, dt=dt, gamma=r.gamma, prim=prim,
                          nscal=r.nscal, level=lev, domain=domain)
 
+    # ---- restart dumps (restart.c): the sections of this Grid to and from the device -----------
+    def rst_sections(self):
+        """[(label, doubles)] of this Grid's sections in file order (csrc/restart.hip)."""
+        out = []
+        buf = C.create_string_buffer(32)
+        for s in range(int(self.L.aa_rst_sections(self._h))):
+            self._chk(self.L.aa_rst_section_label(self._h, s, buf, len(buf)))
+            out.append((buf.value.decode(), int(self.L.aa_rst_section_doubles(self._h, s))))
+        return out
+
+    def rst_section(self, s: int, out: np.ndarray | None = None) -> np.ndarray:
+        """Section `s` of the restart payload: the ACTIVE zones [k][j][i] of one variable (or EdgeFlux) in double precision."""
+        n = int(self.L.aa_rst_section_doubles(self._h, s))
+        if n <= 0:
+            raise AthenaError(f"[rst_section]: no section {s}")
+        if out is None:
+            out = np.empty(n, dtype=np.float64)
+        assert out.dtype == np.float64 and out.size == n and out.flags.c_contiguous
+        self._chk(self.L.aa_rst_section_get(self._h, s, _dp(out)))
+        return out
+
+    def put_rst_section(self, s: int, arr: np.ndarray):
+        """The inverse of rst_section: writes the active zones on the device and no ghost zone."""
+        n = int(self.L.aa_rst_section_doubles(self._h, s))
+        if n <= 0:
+            raise AthenaError(f"[put_rst_section]: no section {s}")
+        assert arr.dtype == np.float64 and arr.size == n and arr.flags.c_contiguous
+        self._chk(self.L.aa_rst_section_put(self._h, s, _dp(arr)))
+
+    def _rst_buffer(self) -> np.ndarray:
+        n = max(n for _, n in self.rst_sections())
+        if getattr(self, "_rst_buf", None) is None or self._rst_buf.size < n:
+            self._rst_buf = np.empty(n, dtype=np.float64)
+        return self._rst_buf
+
+    def write_rst_payload(self, f):
+        """This Grid's labelled sections as dump_restart writes them (restart.c:531-770), one at a time through one host buffer."""
+        buf = self._rst_buffer()
+        for s, (label, n) in enumerate(self.rst_sections()):
+            f.write(b"\n" + label.encode() + b"\n")
+            f.write(memoryview(self.rst_section(s, buf[:n])).cast("B"))
+
+    def read_rst_payload(self, f):
+        """The inverse: `f` stands at this Grid's first label (restart_grids, restart.c:52-456)."""
+        from . import restart
+        buf = self._rst_buffer()
+        for s, (label, n) in enumerate(self.rst_sections()):
+            restart.expect_label(f, label)
+            if f.readinto(memoryview(buf[:n]).cast("B")) != 8 * n:
+                raise restart.RestartError(f"[restart_grids]: Expected {n} doubles of {label}, found the end of the file")
+            self.put_rst_section(s, buf[:n])
+
     # ---- measurement -------------------------------------------------------------------
     def profile_enable(self, on: bool = True): self.L.aa_profile_enable(self._h, 1 if on else 0)
     def profile_reset(self): self.L.aa_profile_reset(self._h)
@@ -416,14 +475,20 @@ class Grid:
         return out
 
 
-def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None, ion_path: int = 0, nslab: int = 1) -> Grid:
+def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None, ion_path: int = 0, nslab: int = 1,
+                  initial: bool = True) -> Grid:
     """problem(DomainS*) of the reference for the shipped decks: fill the host block with the
-    C problem generator, upload it, register the hooks (main.c:393)."""
+    C problem generator, upload it, register the hooks (main.c:393).  initial = False is problem_read_restart
+    (ioniz_sphere.c:191-239): the hooks only -- no host block is built, the state comes from a restart dump."""
     r = grid.run; pr = r.prob
     g = Grid(grid, device, strict, ion_path, nslab)
     H = host()
-    U = g.new_host_block()
-    if r.problem == "ifront":
+    U = g.new_host_block() if initial else None
+    if r.problem not in ("ifront", "ioniz_sphere", "blast", "shkset1d"):
+        raise AthenaError(f"unknown problem {r.problem}")
+    if not initial:
+        rc = 0
+    elif r.problem == "ifront":
         rc = H.aa_problem_ifront(C.byref(g.params), pr["n_H"], pr["cs"], _dp(U))
     elif r.problem == "ioniz_sphere":
         rc = H.aa_problem_ioniz_sphere(C.byref(g.params), pr["cs"], pr.get("rp", 1.2e10),
@@ -439,7 +504,8 @@ def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None,
         raise AthenaError(f"unknown problem {r.problem}")
     if rc != 0:
         raise AthenaError(f"problem generator {r.problem} rejected the configuration")
-    g.upload(U)
+    if initial:
+        g.upload(U)
     if r.problem == "ioniz_sphere":
         g.set_static_grav_pot(H.aa_planet_pot)                           # StaticGravPot = PlanetPot
         n = H.aa_ioniz_sphere_pinned(C.byref(g.params), None, None)
@@ -461,9 +527,10 @@ class Mesh:
     names follow the reference: RestrictCorrect, Prolongate (smr.c), new_dt, and the per-level
     ion_radtransfer_3d with its coarse -> fine EdgeFlux hand-off (ionrad_smr.c)."""
 
-    def __init__(self, grids, device: int = 0, strict: bool | None = None, links=None, ion_path: int = 0):
-        """links: config.LinkConfig list for one rank's stack of slabs (multi-GPU SMR); None = the whole Mesh."""
-        self.lev = [setup_problem(g, device, strict, ion_path) for g in grids]
+    def __init__(self, grids, device: int = 0, strict: bool | None = None, links=None, ion_path: int = 0, initial: bool = True):
+        """links: config.LinkConfig list for one rank's stack of slabs (multi-GPU SMR); None = the whole Mesh.
+        initial = False: the hooks only, the state of every level comes from a restart dump (setup_problem)."""
+        self.lev = [setup_problem(g, device, strict, ion_path, initial=initial) for g in grids]
         self.L = self.lev[0].L
         n = len(grids)
         hs = (C.c_void_p * n)(*[g._h for g in self.lev])
@@ -517,6 +584,16 @@ class Mesh:
 
     def start(self):
         self._chk(self.L.aa_mesh_start(self._h)); return self
+
+    def resume(self):
+        """aa_mesh_start without new_dt: the start sequence of a restarted run (main.c:398-451)"""
+        self._chk(self.L.aa_mesh_resume(self._h)); return self
+
+    def set_state(self, time: float, dt: float, nstep: int):
+        """MeshS time / dt / nstep, and every level's copy of them (as aa_mesh_new_dt leaves them)"""
+        self._chk(self.L.aa_mesh_set_state(self._h, time, dt, nstep))
+        for g in self.lev:
+            g.set_mesh_state(time, dt, nstep)
 
     def domain_numbers(self):
         """(level, domain) of every Grid in self.lev: Domains of a level are numbered in deck order (MeshS.Domain[nl][nd])."""

@@ -136,10 +136,12 @@ class OutputSet:
 
 
 def run(target, outputs: OutputSet, tlim: float, nlim: int = -1) -> None:
-    """main() of the reference around the loop: forced output after the start (main.c:501), data_output(0) at the top of every
-    pass (:524), forced output after the loop (:743).  `target`: start(), step(), time, nstep and the writers."""
+    """main() of the reference around the loop: forced output after the start (main.c:501; a restarted run -- a target with
+    ``restarted`` set -- skips it), data_output(0) at the top of every pass (:524), forced output after the loop (:743).
+    `target`: start(), step(), time, nstep and the writers."""
     target.start()
-    outputs.data_output(target, 1)
+    if not getattr(target, "restarted", False):
+        outputs.data_output(target, 1)
     while target.time < tlim and (nlim < 0 or target.nstep < nlim):
         outputs.data_output(target, 0)
         target.step()

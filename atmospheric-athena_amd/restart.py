@@ -158,3 +158,143 @@ def read_rst_levels(path: str, nxs: Sequence[Sequence[int]], nscal: int, ion: bo
         levels.append((U, ef))
     expect(b"USER_DATA")
     return dict(header=header, par=ParTable.from_text(header), nstep=nstep, time=time, dt=dt, levels=levels)
+
+
+# ---- continuing a run (main.c -r): a reader that does not slurp the file, and the writer's pieces ------------------------------
+
+class RestartError(ValueError):
+    """ath_error of restart_grids (restart.c:52-456)"""
+
+
+def section_table(nx: Sequence[int], nscal: int, ion: bool):
+    """[(label, doubles)] of one Grid's sections in file order"""
+    n = int(nx[0]) * int(nx[1]) * int(nx[2])
+    out = [(lab, n) for lab in _LABELS]
+    if ion:
+        out.append(("EDGEFLUX", (int(nx[0]) + 1) * (int(nx[1]) + 1) * (int(nx[2]) + 1)))
+    out += [(f"SCALAR {s}", n) for s in range(nscal)]
+    return out
+
+
+def expect_label(f, label: str, first: bool = False) -> None:
+    """The label the reference's reader insists on at this place of the file (restart.c:79-84 ...)"""
+    tag = (b"" if first else b"\n") + label.encode() + b"\n"
+    got = f.read(len(tag))
+    if got != tag:
+        raise RestartError(f"[restart_grids]: Expected {label}, found {got!r}")
+
+
+def write_header(f, par_text: str, nstep: int, time: float, dt: float) -> None:
+    """Everything in front of the first Grid's sections: the parameter dump, N_STEP, TIME, TIME_STEP"""
+    if not par_text.rstrip().endswith("<par_end>"):
+        par_text = par_text.rstrip("\n") + "\n<par_end>\n"
+    f.write(par_text.encode())
+    f.write(b"N_STEP\n" + struct.pack("<i", int(nstep)))
+    f.write(b"\nTIME\n" + struct.pack("<d", float(time)))
+    f.write(b"\nTIME_STEP\n" + struct.pack("<d", float(dt)))
+
+
+def write_trailer(f) -> None:
+    f.write(b"\nUSER_DATA\n")
+
+
+def read_head(path: str) -> Dict:
+    """The parameter dump (text, and parsed: comments and every block it holds), nstep / time / dt, and `offset`: where the
+    first Grid's first label begins.  Reads the head of the file only."""
+    import os
+    with open(path, "rb") as f:
+        buf = b""
+        while True:
+            end = buf.find(b"<par_end>")
+            if end >= 0:
+                nl = buf.find(b"\n", end)
+                if nl >= 0:
+                    break
+            more = f.read(1 << 16)
+            if not more:
+                raise RestartError("[restart_grids]: Expected <par_end>, found the end of the file")
+            buf += more
+        pos = nl + 1
+        header = buf[:pos].decode(errors="replace")
+        f.seek(pos)
+        expect_label(f, "N_STEP", first=True)
+        raw = f.read(4)
+        expect_label(f, "TIME"); raw += f.read(8)
+        expect_label(f, "TIME_STEP"); raw += f.read(8)
+        if len(raw) != 20:
+            raise RestartError("[restart_grids]: Expected TIME_STEP, found the end of the file")
+        nstep, time, dt = struct.unpack("<idd", raw)
+        offset = f.tell()
+    return dict(path=path, header=header, par=ParTable.from_text(header), nstep=nstep, time=time, dt=dt, offset=offset,
+                size=os.path.getsize(path))
+
+
+def index_sections(head: Dict, nxs: Sequence[Sequence[int]], nscal: int, ion: bool):
+    """[[(label, byte offset of the data, doubles), ...] per level, root first] of the file behind `head` for Grids of `nxs`
+    active zones.  Every label is looked at in its place and the total size must be the file's: a file of another mesh or another
+    number of ranks, a truncated one, or one with bytes after USER_DATA (none of the built problems writes any) is refused."""
+    levels = []
+    with open(head["path"], "rb") as f:
+        pos = head["offset"]
+        for nx in nxs:
+            secs = []
+            for label, n in section_table(nx, nscal, ion):
+                f.seek(pos)
+                expect_label(f, label)
+                pos = f.tell()
+                secs.append((label, pos, n))
+                pos += 8 * n
+            levels.append(secs)
+        f.seek(pos)
+        expect_label(f, "USER_DATA")
+        pos = f.tell()
+    if pos != head["size"]:
+        raise RestartError(f"[restart_grids]: Expected {pos} bytes, found {head['size']}")
+    return levels
+
+
+def scan_rst(path: str, nxs: Sequence[Sequence[int]], nscal: int, ion: bool) -> Dict:
+    """read_head + index_sections"""
+    head = read_head(path)
+    head["levels"] = index_sections(head, nxs, nscal, ion)
+    return head
+
+
+def read_section(path: str, offset: int, n: int) -> np.ndarray:
+    a = np.fromfile(path, dtype="<f8", count=n, offset=offset)
+    if a.size != n:
+        raise RestartError(f"[restart_grids]: Expected {n} doubles at byte {offset}, found {a.size}")
+    return a
+
+
+def read_state(head: Dict, level: int, nx: Sequence[int], nscal: int):
+    """(U_active [Nx3][Nx2][Nx1][5 + nscal], edgeflux or None) of one level of an indexed file: for engines that keep a host block"""
+    U = np.zeros((nx[2], nx[1], nx[0], 5 + nscal)); ef = None
+    for label, off, n in head["levels"][level]:
+        a = read_section(head["path"], off, n)
+        if label == "EDGEFLUX":
+            ef = a.reshape(nx[2] + 1, nx[1] + 1, nx[0] + 1)
+        else:
+            c = _LABELS.index(label) if label in _LABELS else 5 + int(label.split()[1])
+            U[..., c] = a.reshape(nx[2], nx[1], nx[0])
+    return U, ef
+
+
+def rank_path(path0: str, rank: int) -> str:
+    """The file rank r > 0 reads, from rank 0's path (main.c:265-288): ``-id<r>`` goes in front of ``.NNNN.rst``, in the same
+    directory; if that does not exist, ``../id<r>/`` -- where every rank of a run wrote its own."""
+    import os
+    if rank == 0:
+        return path0
+    d, name = os.path.split(path0)
+    parts = name.rsplit(".", 2)
+    if len(parts) != 3:
+        raise RestartError(f"[main]: restart file name {name} is not <basename>.NNNN.rst")
+    sib = f"{parts[0]}-id{rank}.{parts[1]}.{parts[2]}"
+    here = os.path.join(d, sib)
+    if os.path.exists(here):
+        return here
+    there = os.path.join(d, os.pardir, f"id{rank}", sib)
+    if os.path.exists(there):
+        return os.path.normpath(there)
+    raise RestartError(f"[main]: rank {rank} finds neither {here} nor {there}")

@@ -267,6 +267,24 @@ int       aa_dump_sections(const aa_grid *g, int fmt);                        /*
 long long aa_dump_section_floats(const aa_grid *g, int fmt, int section);     /* n or 3n; 0 past the last section       */
 int       aa_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 
+/* ---- restart.c:463-983 / restart_grids :52-456: the double-precision payload of a restart dump to and from the resident state,
+ *      one labelled section at a time, ACTIVE zones [k][j][i] only:
+ *        DENSITY | 1-MOMENTUM | 2-MOMENTUM | 3-MOMENTUM | ENERGY | EDGEFLUX (ion radiation; (Nx1+1)(Nx2+1)(Nx3+1)) | SCALAR n
+ *      `host` is any host memory of aa_rst_section_doubles() doubles; the data travels through the bounce buffer of the data
+ *      dumps (AA_DUMP_CHUNK_FLOATS: two floats per double).  get uses the face-state area like aa_dump_section and changes no
+ *      state.  put writes the active zones and NO ghost zone; afterwards the device holds what no host block does (the next
+ *      aa_download_ghost_zones moves the whole block) and new_dt's maxima are due again; EDGEFLUX counts as filled.  Composite
+ *      handles (aa_params.nslab > 1) take both calls.
+ *      aa_resume / aa_mesh_resume: the start sequence of a restarted run (main.c:398-451) -- aa_start / aa_mesh_start without
+ *      new_dt: the dt of the file (aa_set_mesh_state / aa_mesh_set_state) is the next step's.                              */
+int       aa_rst_sections(const aa_grid *g);
+int       aa_rst_section_label(const aa_grid *g, int section, char *buf, int n);
+long long aa_rst_section_doubles(const aa_grid *g, int section);          /* 0 past the last section */
+int       aa_rst_section_get(aa_grid *g, int section, double *host);
+int       aa_rst_section_put(aa_grid *g, int section, const double *host);
+int       aa_resume(aa_grid *g);
+int       aa_mesh_resume(aa_mesh *m);
+
 /* ---- measurement: per-kernel accumulated device time (hipEvent pairs on the stream) */
 int         aa_profile_enable(aa_grid *g, int on);
 int         aa_profile_reset(aa_grid *g);
