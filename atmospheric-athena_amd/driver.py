@@ -622,13 +622,15 @@ class MeshRun:
 class HipMeshEngine:
     """One rank's stack of x3 slabs (one per level present on the rank) on one MI355X."""
 
-    def __init__(self, cfg, device: int = 0, strict: Optional[bool] = None, use_torch_stream: bool = True):
+    def __init__(self, cfg, device: int = 0, strict: Optional[bool] = None, use_torch_stream: bool = True,
+                 initial: bool = True):
+        """initial = False: no problem generator, the state of every level comes from a restart dump (lib.Mesh)"""
         import torch
         from . import lib
         self.torch = torch
         self.cfg = cfg
         torch.cuda.set_device(device)
-        self.mesh = lib.Mesh(cfg.levels, device, strict, links=cfg.links)
+        self.mesh = lib.Mesh(cfg.levels, device, strict, links=cfg.links, initial=initial)
         if use_torch_stream:
             self.mesh.set_stream(torch.cuda.current_stream().cuda_stream)
         self.lev = self.mesh.lev
@@ -704,6 +706,16 @@ class HipMeshEngine:
     def flux_x3_apply(self, l, side, i0, j0, n1, n2, t): self.lev[l].flux_x3_apply(side, i0, j0, n1, n2, t.data_ptr())
 
     def download(self, l) -> np.ndarray: return self.lev[l].download()
+    def edgeflux(self, l) -> np.ndarray: return self.lev[l].download_edgeflux()
+    def history(self, l) -> np.ndarray: return self.lev[l].history()
+    def set_mesh_state(self, time, dt, nstep): self.mesh.set_state(time, dt, nstep)
+
+    def write_dump(self, rundir, basename, num, fmt, prim, level, domain, time, dt):
+        """dump_vtk / dump_binary of every slab of this rank's stack: the payloads come from the device (csrc/dump.hip)"""
+        return self.mesh.write_dump(rundir, basename, num, fmt, prim, level, domain, time=time, dt=dt)
+
+    def write_rst_payload(self, l, f): self.lev[l].write_rst_payload(f)
+    def read_rst_payload(self, l, f): self.lev[l].read_rst_payload(f)
     def sync(self): self.lev[0].sync()
     def close(self): self.mesh.close()
 
@@ -717,7 +729,8 @@ class MeshDriver:
     ionrad_3d.c in the reference)."""
 
     def __init__(self, par, run: RunConfig, engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0,
-                 strict: Optional[bool] = None, cuts=None):
+                 strict: Optional[bool] = None, cuts=None, initial: bool = True):
+        """initial = False: the product engine skips the problem generator (from_restart loads the state)"""
         from .config import mesh_slabs
         import torch
         import torch.distributed as dist
@@ -725,8 +738,12 @@ class MeshDriver:
         self.run, self.rank, self.nranks = run, rank, nranks
         from .config import levels as _levels
         self.cfg = mesh_slabs(par, run, rank, nranks, cuts)
-        self.level_nx1 = [g.Nx[0] for g in _levels(par, run)]     # zones along the rays of every level (x3 slabs keep them)
-        self.eng = engine_factory(self.cfg) if engine_factory else HipMeshEngine(self.cfg, device, strict)
+        self.domains = _levels(par, run)                  # the whole Domain of every level (history: its volume)
+        self.level_nx1 = [g.Nx[0] for g in self.domains]  # zones along the rays of every level (x3 slabs keep them)
+        self.eng = engine_factory(self.cfg) if engine_factory else HipMeshEngine(self.cfg, device, strict, initial=initial)
+        self.restarted = False    # from_restart: start() is the restarted run's, outputs.run skips the forced first output
+        self.par = None           # the parameter table this driver was built from (from_restart)
+        self._hst = {}            # HistoryWriter per (<outputN> block, level)
         self.NL = len(self.cfg.table[0])                  # levels of the Mesh
         self.nl = len(self.cfg.levels)                    # levels present on this rank
         self.time, self.dt, self.nstep = 0.0, 0.0, 0
@@ -742,12 +759,144 @@ class MeshDriver:
 
     def has(self, l: int) -> bool: return l < self.nl
 
+    @classmethod
+    def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
+                     engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
+                     cuts=None) -> "MeshDriver":
+        """``athena -r path [block/key=value ...]`` of the MPI + SMR build (main.c:168-173, :216-288; restart_grids,
+        restart.c:52-456).  `path` is rank 0's file: every rank takes the parameter table from it, with the overrides on top
+        (an unknown key is an error), and reads the Grids it holds, root first, from restart.rank_path(path, rank).  A file
+        written for other cuts or another number of ranks holds Grids of other sizes and is refused by the size check of
+        restart.index_sections.  The problem generator does not run.  The driver keeps the table as `.par`:
+        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block."""
+        from . import config, restart
+        head0 = restart.read_head(path)
+        par = head0["par"].cmdline(overrides)
+        run = config.from_par(par, problem)
+        if integrator not in ("ctu", "vl", "ctu-noh"):
+            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
+        run.integrator, run.order = integrator, order
+        d = cls(par, run, engine_factory, rank, nranks, device, strict, cuts, initial=False)
+        head = head0 if rank == 0 else restart.read_head(restart.rank_path(path, rank))
+        nxs = [g.Nx for g in d.cfg.levels]
+        head["levels"] = restart.index_sections(head, nxs, run.nscal, run.ion)
+        if hasattr(d.eng, "read_rst_payload"):
+            with open(head["path"], "rb") as f:
+                f.seek(head["offset"])
+                for l in range(d.nl):
+                    d.eng.read_rst_payload(l, f)
+        elif hasattr(d.eng, "load_state"):
+            for l in range(d.nl):
+                d.eng.load_state(l, *restart.read_state(head, l, nxs[l], run.nscal))
+        else:
+            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_payload or load_state)")
+        d.time, d.dt, d.nstep = head["time"], head["dt"], head["nstep"]
+        d.dtl = [d.dt] * d.NL
+        if hasattr(d.eng, "set_mesh_state"):
+            d.eng.set_mesh_state(d.time, d.dt, d.nstep)
+        for l in range(d.nl):
+            d.eng.set_level_state(l, d.time, d.dt, d.nstep)
+        d.restarted, d.par = True, par
+        return d
+
     def _allreduce(self, vals, op):
         if not self.distributed:
             return list(vals)
         t = self.torch.tensor(list(vals), dtype=self.torch.float64, device=self._sdev)
         self.dist.all_reduce(t, op=op)
         return t.tolist()
+
+    # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
+    def _fires(self, out, l: int) -> bool:
+        return out.level in (-1, l) and out.domain in (-1, 0)
+
+    def write_dump(self, out, outputs):
+        """dump_vtk / dump_binary under MPI + SMR: one file per level this rank holds zones of, under the rank's directory;
+        the header is the slab's own (its DIMENSIONS and ORIGIN, the level's spacing, the Mesh time)."""
+        from . import dumps
+        if hasattr(self.eng, "write_dump"):
+            for rel in self.eng.write_dump(outputs.dir, outputs.basename, out.num, out.out_fmt, out.prim, out.level, out.domain,
+                                           self.time, self.dt):
+                outputs.written.append(rel)
+            return
+        ng, r = 4, self.run
+        for l, g in enumerate(self.cfg.levels):   # an engine without a device: the same payload from its host blocks
+            if not self._fires(out, l):
+                continue
+            path = outputs.path(dumps.fname(outputs.basename, l, 0, out.num, out.out_fmt))
+            U = self.eng.download(l)[ng:-ng, ng:-ng, ng:-ng]
+            dumps.write_dump_from_block(path, out.out_fmt, U, prim=out.prim, gamma=r.gamma, nscal=r.nscal, nx=g.Nx,
+                                        minx=g.MinX, dx=tuple(r.dx[a] / float(1 << l) for a in range(3)), time=self.time,
+                                        dt=self.dt, level=l, domain=0)
+
+    def history(self) -> np.ndarray:
+        """dump_history.c:157-260 for every level: [NL][9] volume integrals, each level's added over the ranks that hold
+        zones of it (MPI_Reduce(SUM) :257 over the Domain's communicator; here ONE all-reduce for all levels, in which a
+        rank without the level takes part with zeros)."""
+        s = np.zeros((self.NL, 9))
+        for l in range(self.nl):
+            s[l] = self.eng.history(l)
+        if self.distributed:
+            s = np.array(self._allreduce(s.reshape(-1), self.dist.ReduceOp.SUM)).reshape(self.NL, 9)
+        return s
+
+    def write_history(self, out, outputs):
+        """One row per level.  The sums are divided by the volume of the whole Domain (:271-279); the lowest rank that holds
+        zones of a level writes its file, under rank 0's directory with its OWN problem_id in the name (:328-349)."""
+        from .history import HistoryWriter
+        s = self.history()                         # (every rank takes part in the sum)
+        id0 = os.path.join(os.path.dirname(outputs.dir), "id0") if outputs.nranks > 1 else outputs.dir
+        for l, g in enumerate(self.domains):
+            if not self._fires(out, l):
+                continue
+            writer = min(r for r in range(self.nranks) if self.cfg.table[r][l] is not None)
+            if writer != self.rank:
+                continue
+            w = self._hst.get((out.n, l))
+            if w is None:
+                w = self._hst[(out.n, l)] = HistoryWriter(id0, outputs.basename, l, 0, out.dat_fmt, num=out.num)
+            vol = 1.0
+            for a in range(3):
+                vol *= g.Nx[a] * (self.run.dx[a] / float(1 << l))
+            w.dump(self.time, self.dt, s[l], vol, self.run.nscal)
+            rel = os.path.relpath(w.path, outputs.dir)
+            if rel not in outputs.written:
+                outputs.written.append(rel)
+
+    def write_restart(self, out, outputs):
+        """dump_restart (restart.c:463-983): ONE file per rank -- the parameter table as it stands now, then the sections of
+        every Grid this rank holds, root first (:531-770)."""
+        from . import dumps, restart
+        ng = 4
+        par = outputs.par
+        par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
+        par.blocks["time"]["nstep"] = "%d" % self.nstep
+        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
+        with open(path, "wb") as f:
+            restart.write_header(f, restart.par_dump(par), self.nstep, self.time, self.dt)
+            for l in range(self.nl):
+                if hasattr(self.eng, "write_rst_payload"):    # the sections come from the device in file order (csrc/restart.hip)
+                    self.eng.write_rst_payload(l, f)
+                    continue
+                U = self.eng.download(l)[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
+                ef = None
+                if self.run.ion:
+                    if not hasattr(self.eng, "edgeflux"):
+                        raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
+                    ef = self.eng.edgeflux(l)
+                restart.write_grid_sections(f, U, ef)
+            restart.write_trailer(f)
+
+    def data_output(self, outputs, flag: int):
+        """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
+        outputs.data_output(self, flag)
+
+    def main(self, outputs):
+        """main.c:501-743 for this rank: start, forced output (not after a restart), the loop up to <time>tlim / nlim with
+        data_output(0) at the top of every pass, forced output.  Every rank calls it with its own
+        OutputSet.from_par(par, time, rundir, rank, nranks)."""
+        from . import outputs as _outputs
+        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
     def _p2p(self, sends, recvs):
         """sends: [(tensor, peer)], recvs: [(tensor, peer)]; gloo moves host tensors only."""
@@ -999,7 +1148,13 @@ class MeshDriver:
             if self.has(l):
                 self.eng.bvals_ionrad(l)
         self.eng.prolongate()
-        self.new_dt()
+        if self.restarted:          # main.c:398-451 after restart_grids: NO new_dt -- the file's dt is the next step's
+            for l in range(self.NL):
+                self.dtl[l] = self.dt
+                if self.has(l):
+                    self.eng.set_level_state(l, self.time, self.dt, self.nstep)
+        else:
+            self.new_dt()
         return self
 
     def step(self) -> List[int]:

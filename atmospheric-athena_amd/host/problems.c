@@ -90,6 +90,15 @@ int aa_problem_ioniz_sphere(const aa_params *p, double cs, double rp, double mp,
   return 0;
 }
 
+/* problem_read_restart (ioniz_sphere.c:191-239): the file-scope constants PlanetPot and Userwork_in_loop read, and no state --
+ * a run resumed from a restart dump never calls the problem generator. */
+int aa_problem_ioniz_sphere_restart(const aa_params *p, double cs, double rp, double mp, double np)
+{
+  if (p->nscal != 1) return -1;
+  sphere_setup(p, cs, rp, mp, np);
+  return 0;
+}
+
 /* StaticGravPot = PlanetPot (ioniz_sphere.c:316-330, non-shearing-box branch) */
 double aa_planet_pot(double x1, double x2, double x3)
 {

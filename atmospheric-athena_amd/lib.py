@@ -145,6 +145,7 @@ def host() -> C.CDLL:
         dp = C.POINTER(C.c_double); pp = C.POINTER(aa_params); D = C.c_double
         H.aa_problem_ifront.argtypes = [pp, D, D, dp]; H.aa_problem_ifront.restype = C.c_int
         H.aa_problem_ioniz_sphere.argtypes = [pp, D, D, D, D, dp]; H.aa_problem_ioniz_sphere.restype = C.c_int
+        H.aa_problem_ioniz_sphere_restart.argtypes = [pp, D, D, D, D]; H.aa_problem_ioniz_sphere_restart.restype = C.c_int
         H.aa_problem_blast.argtypes = [pp, D, D, D, D, D, dp]; H.aa_problem_blast.restype = C.c_int
         H.aa_problem_shkset1d.argtypes = [pp, dp, dp, C.c_int, dp]; H.aa_problem_shkset1d.restype = C.c_int
         H.aa_planet_pot.argtypes = [D, D, D]; H.aa_planet_pot.restype = D
@@ -488,6 +489,9 @@ def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None,
         raise AthenaError(f"unknown problem {r.problem}")
     if not initial:
         rc = 0
+        if r.problem == "ioniz_sphere":          # the constants behind PlanetPot and the pinned zones (a process that resumes never ran the generator)
+            rc = H.aa_problem_ioniz_sphere_restart(C.byref(g.params), pr["cs"], pr.get("rp", 1.2e10), pr.get("mp", 1.0e30),
+                                                   pr.get("np", 6.0e8))
     elif r.problem == "ifront":
         rc = H.aa_problem_ifront(C.byref(g.params), pr["n_H"], pr["cs"], _dp(U))
     elif r.problem == "ioniz_sphere":
@@ -603,12 +607,15 @@ class Mesh:
             out.append((l, seen.get(l, 0))); seen[l] = seen.get(l, 0) + 1
         return out
 
-    def write_dump(self, rundir: str, basename: str, num: int, fmt, prim: bool, level: int = -1, domain: int = -1):
+    def write_dump(self, rundir: str, basename: str, num: int, fmt, prim: bool, level: int = -1, domain: int = -1,
+                   time: float | None = None, dt: float | None = None):
         """dump_vtk / dump_binary over the Mesh: one file per Domain (level / domain = -1: all), named by ath_fname;
-        -> the relative paths written.  Every level carries the Mesh's time and dt."""
+        -> the relative paths written.  Every level carries the Mesh's time and dt (or the ones given: a driver that
+        keeps them itself, driver.MeshDriver)."""
         from . import dumps
         ext = {dumps.VTK: "vtk", dumps.BIN: "bin"}[dumps.FORMATS.get(fmt, fmt)]
-        t, dt, n = self.state()
+        t, dt_, n = self.state()
+        t = t if time is None else time; dt = dt_ if dt is None else dt
         out = []
         for g, (l, d) in zip(self.lev, self.domain_numbers()):
             if (level == -1 or level == l) and (domain == -1 or domain == d):

@@ -194,6 +194,20 @@ def write_header(f, par_text: str, nstep: int, time: float, dt: float) -> None:
     f.write(b"\nTIME_STEP\n" + struct.pack("<d", float(dt)))
 
 
+def write_grid_sections(f, U: np.ndarray, edgeflux: Optional[np.ndarray] = None) -> None:
+    """One Grid's labelled sections from a host block of ACTIVE zones [Nx3][Nx2][Nx1][nvar] (engines without a device); the
+    bytes lib.Grid.write_rst_payload writes for the same state."""
+    for c, lab in enumerate(_LABELS):
+        f.write(b"\n" + lab.encode() + b"\n")
+        f.write(np.ascontiguousarray(U[..., c], dtype="<f8").tobytes())
+    if edgeflux is not None:
+        f.write(b"\nEDGEFLUX\n")
+        f.write(np.ascontiguousarray(edgeflux, dtype="<f8").tobytes())
+    for n in range(U.shape[-1] - 5):
+        f.write(f"\nSCALAR {n}\n".encode())
+        f.write(np.ascontiguousarray(U[..., 5 + n], dtype="<f8").tobytes())
+
+
 def write_trailer(f) -> None:
     f.write(b"\nUSER_DATA\n")
 
