@@ -144,6 +144,129 @@ int rst_section_grid(aa_grid *g, int section, double *host, long long n, int put
   return 0;
 }
 
+// ---- boxes: a part [lo, lo + n) of a section, in the section's own index space (active zones; the (Nx+1)^3 face indices
+// for EDGEFLUX), to and from a contiguous host block [k][j][i] -- what a run resumed on other cuts reads from every source file
+// that meets its Grid, and what a dump written for other cuts takes out of the resident state.
+//
+// `base` is the field at the box's first element, sK / sJ the field's strides; doubles [row0*n1, row0*n1 + n) of the box with
+// row = k*n2 + j over the box's rows.  One thread per double, lanes along i: a box narrower than a wavefront (an x1 cut) packs
+// several rows into one wave, a wide one keeps 512-byte requests per row.  No arithmetic, addresses only.
+__global__ void __launch_bounds__(256) k_rst_box_gather(const Real *__restrict__ base, long sK, long sJ, unsigned n1, unsigned n2,
+                                                        unsigned row0, unsigned n, Real *__restrict__ dst)
+{
+  const unsigned o = blockIdx.x*256u + threadIdx.x;
+  if (o >= n) return;
+  const unsigned r = o/n1, i = o - r*n1, row = row0 + r;
+  const unsigned k = row/n2, j = row - k*n2;
+  dst[o] = base[(long)k*sK + (long)j*sJ + (long)i];
+}
+
+__global__ void __launch_bounds__(256) k_rst_box_scatter(Real *__restrict__ base, long sK, long sJ, unsigned n1, unsigned n2,
+                                                         unsigned row0, unsigned n, const Real *__restrict__ src)
+{
+  const unsigned o = blockIdx.x*256u + threadIdx.x;
+  if (o >= n) return;
+  const unsigned r = o/n1, i = o - r*n1, row = row0 + r;
+  const unsigned k = row/n2, j = row - k*n2;
+  base[(long)k*sK + (long)j*sJ + (long)i] = src[o];
+}
+
+// one Grid on one device (the current one).  Pieces of whole box rows through the two halves of the bounce buffer, as
+// rst_section_grid; EDGEFLUX too goes through the staging slots here (a box of it is not contiguous on the device).
+static int rst_box_grid(aa_grid *g, int section, const int lo[3], const int nb[3], double *host, int put)
+{
+  { int rc = dump_prepare(g); if (rc) return rc; }
+  g->inner_swept = false;          // the face-state area is the staging buffer (see aa_integrate_begin in athena_amd.h)
+  const bool ef = rst_is_edgeflux(g, section);
+  // (put as well: the entries outside the box stay what a reader would have found)
+  if (ef) { int rc = aa_edgeflux_ready(g); if (rc) return rc; }
+  Real *base; long sK, sJ;
+  if (ef) {
+    sJ = (long)g->d.Nx1 + 1; sK = sJ*((long)g->d.Nx2 + 1);
+    base = g->d.edgeflux + (long)lo[2]*sK + (long)lo[1]*sJ + (long)lo[0];
+  } else {
+    sJ = g->d.sJ; sK = g->d.sK;
+    base = g->d.U + (size_t)rst_section_var(g, section)*(size_t)g->d.nc
+         + (long)(lo[2] + AA_NGHOST_)*sK + (long)(lo[1] + AA_NGHOST_)*sJ + (long)(lo[0] + AA_NGHOST_);
+  }
+  const unsigned n1 = (unsigned)nb[0], n2 = (unsigned)nb[1];
+  const long long nrows = (long long)nb[1]*nb[2];
+  const size_t per = g->dump_cap/2;                       // doubles per half
+  const long long rows_per = (long long)(per/n1);
+  if (rows_per < 1) return aa_fail(-1, "[aa_rst_section_box]: a row of %u doubles does not fit the bounce buffer (%zu)", n1, per);
+  Real *stage = g->d.LR, *pinned = (Real*)g->dump_host;
+  if (put) {
+    // whatever is queued on the Grid's stream may still read the state and the staging area
+    HIPCHK(hipEventRecord(g->dump_ev[0], g->st));
+    HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[0], 0));
+  }
+  long long prev_first = -1; size_t prev_n = 0; int c = 0;
+  for (long long row0 = 0; row0 < nrows; row0 += rows_per, c++) {
+    const long long nr = (row0 + rows_per <= nrows) ? rows_per : nrows - row0;
+    const size_t np = (size_t)nr*n1;
+    const long long first = row0*(long long)n1;
+    const int slot = c & 1;
+    Real *dev = stage + (size_t)slot*per, *pin = pinned + (size_t)slot*per;
+    const unsigned blocks = (unsigned)((np + 255)/256);
+    if (!put) {
+      { Scope sc(g, "rst_box_gather");
+        hipLaunchKernelGGL(k_rst_box_gather, dim3(blocks), dim3(256), 0, g->st, (const Real*)base, sK, sJ, n1, n2, (unsigned)row0, (unsigned)np, dev); }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(g->dump_ev[slot], g->st));
+      HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[slot], 0));
+      HIPCHK(hipMemcpyAsync(pin, dev, np*sizeof(Real), hipMemcpyDeviceToHost, g->dump_st));
+      HIPCHK(hipEventRecord(g->dump_ev[2 + slot], g->dump_st));
+      if (prev_first >= 0) {       // the piece before this one: hand it out while this one travels
+        HIPCHK(hipEventSynchronize(g->dump_ev[2 + (slot ^ 1)]));
+        dump_copy_out((float*)(host + prev_first), (const float*)(pinned + (size_t)(slot ^ 1)*per), 2*prev_n);
+      }
+    } else {
+      if (c >= 2) {                // this half's last piece has left the host, and its staging slot has been scattered
+        HIPCHK(hipEventSynchronize(g->dump_ev[2 + slot]));
+        HIPCHK(hipStreamWaitEvent(g->dump_st, g->dump_ev[slot], 0));
+      }
+      dump_copy_out((float*)pin, (const float*)(host + first), 2*np);
+      HIPCHK(hipMemcpyAsync(dev, pin, np*sizeof(Real), hipMemcpyHostToDevice, g->dump_st));
+      HIPCHK(hipEventRecord(g->dump_ev[2 + slot], g->dump_st));
+      HIPCHK(hipStreamWaitEvent(g->st, g->dump_ev[2 + slot], 0));
+      { Scope sc(g, "rst_box_scatter");
+        hipLaunchKernelGGL(k_rst_box_scatter, dim3(blocks), dim3(256), 0, g->st, base, sK, sJ, n1, n2, (unsigned)row0, (unsigned)np, (const Real*)dev); }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(g->dump_ev[slot], g->st));
+    }
+    prev_first = first; prev_n = np;
+  }
+  if (!put) {
+    if (prev_first >= 0) {
+      const int slot = (c - 1) & 1;
+      HIPCHK(hipEventSynchronize(g->dump_ev[2 + slot]));
+      dump_copy_out((float*)(host + prev_first), (const float*)(pinned + (size_t)slot*per), 2*prev_n);
+    }
+    return 0;
+  }
+  // every piece has landed before the call returns: the next user of the state or of the staging area finds them complete
+  HIPCHK(hipStreamSynchronize(g->dump_st));
+  HIPCHK(hipStreamSynchronize(g->st));
+  g->cfl_ready = false; g->inner_swept = false; g->active_dirty = true;      // the device holds what no host block does
+  if (ef) g->ef_stale = false;
+  return 0;
+}
+
+static int rst_box_call(const char *who, aa_grid *g, int section, const int lo[3], const int n[3], double *host, int put)
+{
+  if (!g || !lo || !n || !host) return aa_fail(-1, "[%s]: null argument", who);
+  if (section < 0 || section >= rst_nsections(g)) return aa_fail(-1, "[%s]: section %d of %d", who, section, rst_nsections(g));
+  if (!g->slab.empty())
+    return aa_fail(-1, "[%s]: a Grid cut into slabs inside the library (aa_params.nslab > 1) takes whole sections only", who);
+  const int e = rst_is_edgeflux(g, section) ? 1 : 0;
+  for (int d = 0; d < 3; d++) {
+    const int dim = g->p.Nx[d] + e;
+    if (lo[d] < 0 || n[d] < 1 || lo[d] > dim - n[d])
+      return aa_fail(-1, "[%s]: box [%d, %d) along x%d is not inside the section's [0, %d)", who, lo[d], lo[d] + n[d], d + 1, dim);
+  }
+  return rst_box_grid(g, section, lo, n, host, put);
+}
+
 extern "C" {
 
 int aa_rst_sections(const aa_grid *g) { return g ? rst_nsections(g) : 0; }
@@ -180,6 +303,12 @@ int aa_rst_section_put(aa_grid *g, int section, const double *host)
   if (!g->slab.empty()) return slabs_rst_section(g, section, const_cast<double*>(host), 1);
   return rst_section_grid(g, section, const_cast<double*>(host), rst_doubles(g, section), 1);
 }
+
+int aa_rst_section_get_box(aa_grid *g, int section, const int lo[3], const int n[3], double *host)
+{ return rst_box_call("aa_rst_section_get_box", g, section, lo, n, host, 0); }
+
+int aa_rst_section_put_box(aa_grid *g, int section, const int lo[3], const int n[3], const double *host)
+{ return rst_box_call("aa_rst_section_put_box", g, section, lo, n, const_cast<double*>(host), 1); }
 
 // main.c:398-451 of a restarted run: the ghost zones and the radiation boundary, and NOT new_dt -- the file's dt is the next step's
 int aa_resume(aa_grid *g)

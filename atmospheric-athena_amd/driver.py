@@ -116,6 +116,8 @@ class HipEngine:
     def resume_local(self): self.g.resume()
     def write_rst_payload(self, f): self.g.write_rst_payload(f)
     def read_rst_payload(self, f): self.g.read_rst_payload(f)
+    def read_rst_boxes(self, sources, rootNx, lo, n): self.g.read_rst_boxes(sources, rootNx, lo, n)
+    def write_rst_box_payload(self, f, lo, n): self.g.write_rst_box_payload(f, lo, n)
     def mesh_state(self): return self.g.mesh_state()
 
     # halo
@@ -176,12 +178,18 @@ class Driver:
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
                      engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
-                     p2: int = 1) -> "Driver":
+                     p2: int = 1, regrid: bool = False) -> "Driver":
         """``athena -r path [block/key=value ...]`` (main.c:168-173, :216-288; restart_grids, restart.c:52-456).  `path` is
         rank 0's file: every rank takes the parameter table from it, with the overrides on top (an unknown key is an error;
         time/nlim and time/tlim extend a run), and reads its own Grid from restart.rank_path(path, rank).  The problem
         generator does not run; the hooks are registered as by problem_read_restart.  The Driver keeps the table as `.par`:
-        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block."""
+        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block.
+
+        regrid = True resumes on THIS Driver's decomposition (rank, nranks, p2) whatever cuts wrote the files -- the file's own
+        ``<domain1> NGrid_x1/2/3``, x1 cuts included: every rank reads, from every source file that meets its Grid, the part
+        that does (restart.scan_sources, restart.box_pieces); time, dt and nstep are rank 0's file's.  `.par` then names the new
+        cuts (NGrid_x1 = 1, NGrid_x2 = p2, NGrid_x3 = nranks / p2, no AutoWithNProc), so that a later dump describes itself.
+        Single-level meshes only."""
         from . import config, restart
         head0 = restart.read_head(path)
         par = head0["par"].cmdline(overrides)
@@ -189,6 +197,19 @@ class Driver:
         if integrator not in ("ctu", "vl", "ctu-noh"):
             raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
         run.integrator, run.order = integrator, order
+        if regrid:
+            sources = restart.scan_sources(path, run.rootNx, run.nscal, run.ion, head0)
+            d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
+            if hasattr(d.eng, "read_rst_boxes"):
+                d.eng.read_rst_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx)
+            elif hasattr(d.eng, "load_state"):
+                d.eng.load_state(*restart.read_state_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx, run.nscal))
+            else:
+                raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_boxes or load_state)")
+            d.time, d.dt, d.nstep = head0["time"], head0["dt"], head0["nstep"]
+            d.eng.set_mesh_state(d.time, d.dt, d.nstep)
+            d.restarted, d.par = True, restart.regrid_par(par, (1, p2, nranks // p2))
+            return d
         d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
         head = head0 if rank == 0 else restart.read_head(restart.rank_path(path, rank))
         head["levels"] = restart.index_sections(head, [d.grid.Nx], run.nscal, run.ion)
@@ -275,6 +296,8 @@ class Driver:
         par = outputs.par
         par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
         par.blocks["time"]["nstep"] = "%d" % self.nstep
+        if getattr(outputs, "rst_ngrid", None):
+            return self._write_restart_split(out, outputs)
         if hasattr(self.eng, "write_rst_payload"):        # the sections come from the device in file order (csrc/restart.hip)
             path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
             with open(path, "wb") as f:
@@ -290,6 +313,35 @@ class Driver:
             ef = self.eng.download_edgeflux()
         path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
         restart.write_rst(path, restart.par_dump(par), self.nstep, self.time, self.dt, U, ef)
+
+    def _write_restart_split(self, out, outputs):
+        """OutputSet(rst_ngrid=...): one file per Grid of restart.grid_boxes, ``id<r>/<base>[-id<r>].NNNN.rst`` as the ranks of a
+        run on those cuts would leave them -- each under a table with NGrid_x* set to the target and its own problem_id, each
+        with the box of every section (EDGEFLUX with its n + 1 faces)."""
+        from . import dumps, restart
+        ng = 4
+        if self.nranks > 1:
+            raise ValueError("[dump_restart]: rst_ngrid takes a one-rank run")
+        U = ef = None
+        if not hasattr(self.eng, "write_rst_box_payload"):
+            U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
+            if self.run.ion:
+                if not hasattr(self.eng, "download_edgeflux"):
+                    raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
+                ef = self.eng.download_edgeflux()
+        for r, lo, n in restart.grid_boxes(self.run.rootNx, outputs.rst_ngrid):
+            base = outputs.basename + ("-id%d" % r if r else "")
+            path = outputs.path(os.path.join("id%d" % r, dumps.fname(base, 0, 0, out.num, "rst")))
+            text = restart.par_dump(restart.regrid_par(outputs.par, outputs.rst_ngrid, r, outputs.basename))
+            with open(path, "wb") as f:
+                restart.write_header(f, text, self.nstep, self.time, self.dt)
+                if U is None:
+                    self.eng.write_rst_box_payload(f, lo, n)
+                else:
+                    k, j, i = (slice(lo[d], lo[d] + n[d]) for d in (2, 1, 0))
+                    k1, j1, i1 = (slice(lo[d], lo[d] + n[d] + 1) for d in (2, 1, 0))
+                    restart.write_grid_sections(f, U[k, j, i], None if ef is None else ef[k1, j1, i1])
+                restart.write_trailer(f)
 
     def data_output(self, outputs, flag: int):
         """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""

@@ -123,6 +123,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_dump_section": (I, [P, I, I, I, C.POINTER(C.c_float)]),
         "aa_rst_sections": (I, [P]), "aa_rst_section_label": (I, [P, I, C.c_char_p, I]), "aa_rst_section_doubles": (LL, [P, I]),
         "aa_rst_section_get": (I, [P, I, dp]), "aa_rst_section_put": (I, [P, I, dp]),
+        "aa_rst_section_get_box": (I, [P, I, ip, ip, dp]), "aa_rst_section_put_box": (I, [P, I, ip, ip, dp]),
         "aa_resume": (I, [P]), "aa_mesh_resume": (I, [P]),
         "aa_profile_enable": (I, [P, I]), "aa_profile_reset": (I, [P]), "aa_profile_count": (I, [P]),
         "aa_profile_name": (C.c_char_p, [P, I]), "aa_profile_get": (I, [P, I, dp, llp]),
@@ -462,6 +463,44 @@ class Grid:
             if f.readinto(memoryview(buf[:n]).cast("B")) != 8 * n:
                 raise restart.RestartError(f"[restart_grids]: Expected {n} doubles of {label}, found the end of the file")
             self.put_rst_section(s, buf[:n])
+
+    # ---- boxes of a section: resuming on, and writing for, another decomposition ------------------
+    def rst_get_box(self, s: int, lo, n, out: np.ndarray | None = None) -> np.ndarray:
+        """The part [lo, lo + n) of section `s`, (x1, x2, x3) in the section's own index space (active zones; the face indices
+        for EDGEFLUX): [n3][n2][n1] doubles, the slice of rst_section."""
+        lo3 = (C.c_int * 3)(*[int(v) for v in lo]); n3 = (C.c_int * 3)(*[int(v) for v in n])
+        cnt = max(0, int(n[0])) * max(0, int(n[1])) * max(0, int(n[2]))
+        if out is None:
+            out = np.empty(cnt, dtype=np.float64)
+        assert out.dtype == np.float64 and out.size == cnt and out.flags.c_contiguous
+        self._chk(self.L.aa_rst_section_get_box(self._h, s, lo3, n3, _dp(out)))
+        return out.reshape(max(0, int(n[2])), max(0, int(n[1])), max(0, int(n[0])))
+
+    def rst_put_box(self, s: int, lo, n, arr: np.ndarray):
+        """The inverse: writes the box and nothing outside it (no ghost zone)."""
+        lo3 = (C.c_int * 3)(*[int(v) for v in lo]); n3 = (C.c_int * 3)(*[int(v) for v in n])
+        cnt = max(0, int(n[0])) * max(0, int(n[1])) * max(0, int(n[2]))
+        assert arr.dtype == np.float64 and arr.size == cnt and arr.flags.c_contiguous
+        self._chk(self.L.aa_rst_section_put_box(self._h, s, lo3, n3, _dp(arr)))
+
+    def write_rst_box_payload(self, f, lo, n):
+        """The labelled sections of the Grid [lo, lo + n) of this Grid's active zones, as a rank that held just that Grid would
+        write them (EDGEFLUX with its n + 1 faces)."""
+        for s, (label, _cnt) in enumerate(self.rst_sections()):
+            e = 1 if label == "EDGEFLUX" else 0
+            f.write(b"\n" + label.encode() + b"\n")
+            f.write(memoryview(self.rst_get_box(s, lo, [int(v) + e for v in n])).cast("B"))
+
+    def read_rst_boxes(self, sources, rootNx, lo, n):
+        """This Grid = [lo, lo + n) of the root Domain from the files of restart.scan_sources: section by section, every source
+        file's part of it (restart.box_pieces) straight to the device -- never more than one such part in host memory."""
+        from . import restart
+        for s, (label, _cnt) in enumerate(self.rst_sections()):
+            e = 1 if label == "EDGEFLUX" else 0
+            for src, slo, dlo, ext in restart.box_pieces(sources, rootNx, lo, [int(v) + e for v in n], bool(e)):
+                if src["levels"][0][s][0] != label:
+                    raise restart.RestartError(f"[restart_grids]: Expected {label}, found {src['levels'][0][s][0]}")
+                self.rst_put_box(s, dlo, ext, restart.read_box(src, s, slo, ext))
 
     # ---- measurement -------------------------------------------------------------------
     def profile_enable(self, on: bool = True): self.L.aa_profile_enable(self._h, 1 if on else 0)

@@ -46,17 +46,27 @@ class Output:
 
 
 class OutputSet:
-    def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int):
+    def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int,
+                 rst_ngrid=None):
         self.par, self.outs, self.rst = par, outs, rst
+        self.rst_ngrid = tuple(int(v) for v in rst_ngrid) if rst_ngrid else None      # restart dumps cut for other Grids
         self.rank, self.nranks = rank, nranks
         self.basename = par.gets("job", "problem_id")
         self.dir = os.path.join(rundir, f"id{rank}") if nranks > 1 else rundir
         self.written: List[str] = []          # relative to `dir`, in the order of writing
 
     @classmethod
-    def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1) -> "OutputSet":
+    def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
+                 rst_ngrid=None) -> "OutputSet":
         """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
-        r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries."""
+        r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
+        rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
+        file per Grid under ``id<r>/`` (Driver.write_restart; x1 cuts are written and read, never run)."""
+        if rst_ngrid is not None:
+            if nranks > 1:
+                raise ValueError("[init_output]: rst_ngrid takes a one-rank run")
+            if len(tuple(rst_ngrid)) != 3 or min(int(v) for v in rst_ngrid) < 1:
+                raise ValueError(f"[init_output]: rst_ngrid = {rst_ngrid!r} (three counts >= 1)")
         if nranks > 1 and rank != 0:
             par.blocks["job"]["problem_id"] = "%s-id%d" % (par.gets("job", "problem_id"), rank)
         maxout = par.geti_def("job", "maxout", MAXOUT_DEFAULT)
@@ -89,7 +99,7 @@ class OutputSet:
                 rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
             else:
                 outs.append(o)
-        return cls(par, outs, rst, rundir, rank, nranks)
+        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid)
 
     def data_output(self, target, flag: int) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt

@@ -312,3 +312,132 @@ def rank_path(path0: str, rank: int) -> str:
     if os.path.exists(there):
         return os.path.normpath(there)
     raise RestartError(f"[main]: rank {rank} finds neither {here} nor {there}")
+
+
+# ---- resuming on another decomposition: the Grids of the run that wrote the files, and boxes out of them ------------------------
+
+def grid_boxes(Nx: Sequence[int], ngrid: Sequence[int]):
+    """[(rank, disp(3), nx(3))] of the Grids the reference cuts a root Domain of `Nx` zones into for `<domain1> NGrid_x1/2/3`
+    (init_mesh.c:575-653): Nx/NGrid zones per Grid, the WHOLE remainder of a direction on the first Grid of that direction
+    (:596-621), displacements accumulated (:625-653), rank ids with the x1 index fastest, then x2, then x3 (:585-591)."""
+    sizes, disps = [], []
+    for d in range(3):
+        n, g = int(Nx[d]), int(ngrid[d])
+        if g < 1:
+            raise RestartError(f"[init_mesh] Cannot enter NGrid_x{d + 1}={g} in domain1")
+        if g > 1 and n <= 1:
+            raise RestartError(f"[init_mesh]: domain1/NGrid_x{d + 1} = {g} and Nx{d + 1} = {n}")
+        q, r = divmod(n, g)
+        sz = [q + r] + [q] * (g - 1)
+        dp = [0]
+        for v in sz[:-1]:
+            dp.append(dp[-1] + v)
+        sizes.append(sz); disps.append(dp)
+    out = []
+    for n3 in range(int(ngrid[2])):
+        for m in range(int(ngrid[1])):
+            for l in range(int(ngrid[0])):
+                out.append((len(out), (disps[0][l], disps[1][m], disps[2][n3]), (sizes[0][l], sizes[1][m], sizes[2][n3])))
+    return out
+
+
+def par_ngrid(par: ParTable):
+    """`<domain1> NGrid_x1/2/3` of a parameter dump, default 1 (a run started with AutoWithNProc has them written into the
+    table, init_mesh.c:545-547)"""
+    return tuple(par.geti("domain1", f"NGrid_x{d}") if par.exist("domain1", f"NGrid_x{d}") else 1 for d in (1, 2, 3))
+
+
+def scan_sources(path0: str, rootNx: Sequence[int], nscal: int, ion: bool, head0: Optional[Dict] = None):
+    """The files of the run that wrote `path0` (rank 0's file), whatever its cuts: [head with `rank`, `disp`, `nx`, `ngrid` and the
+    indexed sections `levels`] in rank order.  Single-level meshes only; the number of files found through rank_path must be
+    the product of the file's own NGrid_x*, and every file must have exactly the size of its box."""
+    head0 = head0 or read_head(path0)
+    par = head0["par"]
+    nd = par.geti("job", "num_domains") if par.exist("job", "num_domains") else 1
+    if nd > 1:
+        raise RestartError(f"[restart_grids]: <job> num_domains = {nd}: a file of a refined mesh cannot be resumed on other cuts "
+                           "(regrid takes single-level meshes only)")
+    ngrid = par_ngrid(par)
+    boxes = grid_boxes(rootNx, ngrid)
+    out = []
+    for rank, disp, nx in boxes:
+        try:
+            p = rank_path(path0, rank)
+        except RestartError:
+            raise RestartError(f"[restart_grids]: Expected {len(boxes)} files for NGrid = {ngrid[0]} x {ngrid[1]} x {ngrid[2]}, "
+                               f"found {rank}") from None
+        head = head0 if rank == 0 else read_head(p)
+        head["levels"] = index_sections(head, [nx], nscal, ion)
+        head.update(rank=rank, disp=disp, nx=nx, ngrid=ngrid)
+        out.append(head)
+    try:
+        extra = rank_path(path0, len(boxes))
+    except RestartError:
+        extra = None
+    if extra is not None:
+        raise RestartError(f"[restart_grids]: Expected {len(boxes)} files for NGrid = {ngrid[0]} x {ngrid[1]} x {ngrid[2]}, "
+                           f"found {extra} as well")
+    return out
+
+
+def box_pieces(sources, rootNx: Sequence[int], lo: Sequence[int], n: Sequence[int], edgeflux: bool = False):
+    """The parts of the box [lo, lo + n) -- root Domain indices: zones, or faces for EDGEFLUX -- that every source file holds:
+    [(source, lo in the source's section, lo in the box, extent)].  Neighbouring Grids share one face index of EDGEFLUX: the
+    entry comes from the upper Grid (its index 0; along x1 that is the Grid the flux enters), and the last face of a direction
+    from the last Grid of that direction."""
+    out = []
+    for src in sources:
+        slo, dlo, ext = [], [], []
+        for d in range(3):
+            a = src["disp"][d]
+            b = a + src["nx"][d]
+            if edgeflux and b == int(rootNx[d]):
+                b += 1
+            x0, x1 = max(a, int(lo[d])), min(b, int(lo[d]) + int(n[d]))
+            if x1 <= x0:
+                break
+            slo.append(x0 - a); dlo.append(x0 - int(lo[d])); ext.append(x1 - x0)
+        else:
+            out.append((src, tuple(slo), tuple(dlo), tuple(ext)))
+    return out
+
+
+def read_box(src: Dict, s: int, slo: Sequence[int], ext: Sequence[int]) -> np.ndarray:
+    """[ext3][ext2][ext1] doubles of section `s` of an indexed source file, from `slo` in the section's own index space: only the
+    pages of the rows that meet the box are read."""
+    label, off, cnt = src["levels"][0][s]
+    e = 1 if label == "EDGEFLUX" else 0
+    nx = src["nx"]
+    m = np.memmap(src["path"], dtype="<f8", mode="r", offset=off, shape=(nx[2] + e, nx[1] + e, nx[0] + e))
+    a = np.ascontiguousarray(m[slo[2]:slo[2] + ext[2], slo[1]:slo[1] + ext[1], slo[0]:slo[0] + ext[0]], dtype=np.float64)
+    del m
+    return a
+
+
+def read_state_boxes(sources, rootNx: Sequence[int], lo: Sequence[int], n: Sequence[int], nscal: int):
+    """(U_active [n3][n2][n1][5 + nscal], edgeflux [n3+1][n2+1][n1+1] or None) of the Grid [lo, lo + n) of the root Domain,
+    joined from the files of `scan_sources`: for engines that keep a host block (load_state)."""
+    U = np.zeros((n[2], n[1], n[0], 5 + nscal)); ef = None
+    for s, (label, _off, _cnt) in enumerate(sources[0]["levels"][0]):
+        e = label == "EDGEFLUX"
+        if e:
+            ef = np.zeros((n[2] + 1, n[1] + 1, n[0] + 1)); dst = ef
+        else:
+            dst = U[..., _LABELS.index(label) if label in _LABELS else 5 + int(label.split()[1])]
+        for src, slo, dlo, ext in box_pieces(sources, rootNx, lo, [v + (1 if e else 0) for v in n], e):
+            dst[dlo[2]:dlo[2] + ext[2], dlo[1]:dlo[1] + ext[1], dlo[0]:dlo[0] + ext[0]] = read_box(src, s, slo, ext)
+    return U, ef
+
+
+def regrid_par(par: ParTable, ngrid: Sequence[int], rank: int = 0, basename: Optional[str] = None) -> ParTable:
+    """A copy of the table that describes a Grid of the cuts `ngrid`: NGrid_x* set, no AutoWithNProc, and for rank r > 0
+    ``<job> problem_id`` with ``-id<r>`` (main.c:227-232)."""
+    import copy
+    q = copy.deepcopy(par)
+    dom = q.blocks.setdefault("domain1", {})
+    dom.pop("AutoWithNProc", None)
+    for d in range(3):
+        dom[f"NGrid_x{d + 1}"] = "%d" % int(ngrid[d])
+    if basename is not None:
+        q.blocks["job"]["problem_id"] = basename + ("-id%d" % rank if rank else "")
+    return q

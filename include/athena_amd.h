@@ -282,6 +282,13 @@ int       aa_rst_section_label(const aa_grid *g, int section, char *buf, int n);
 long long aa_rst_section_doubles(const aa_grid *g, int section);          /* 0 past the last section */
 int       aa_rst_section_get(aa_grid *g, int section, double *host);
 int       aa_rst_section_put(aa_grid *g, int section, const double *host);
+/*      Boxes: the part [lo, lo + n) of a section, `lo` and `n` in the section's own index space (active zones; the (Nx+1)^3 face
+ *      indices for EDGEFLUX), `host` the box, contiguous [k][j][i].  Any sequence of put_box calls that tiles a section leaves
+ *      what one aa_rst_section_put of the joined data leaves; put_box writes nothing outside its box; get_box returns the
+ *      slice of aa_rst_section_get.  -1 for a box that is not wholly inside the section, and for composite handles
+ *      (aa_params.nslab > 1): those take whole sections only.                                                             */
+int       aa_rst_section_get_box(aa_grid *g, int section, const int lo[3], const int n[3], double *host);
+int       aa_rst_section_put_box(aa_grid *g, int section, const int lo[3], const int n[3], const double *host);
 int       aa_resume(aa_grid *g);
 int       aa_mesh_resume(aa_mesh *m);
 
