@@ -1215,6 +1215,21 @@ void orc_ion_rates(OrcSim *s, double *dt_chem, double *dt_therm)
   *dt_therm = compute_therm_rates(s);
 }
 
+/* the per-zone arrays the last orc_ion_rates left behind, over the active zones [k][j][i] (NULL: not wanted): ph_rate,
+ * nHdot (damped), edot, last_sign, sign_count.  Copies only: for tests that count which branches a state reaches. */
+void orc_ion_zone_rates(OrcSim *s, double *ph, double *nHdot, double *edot, int *last_sign, int *sign_count)
+{
+  int i, j, k; size_t n = 0;
+  for (k = s->ks; k <= s->ke; k++) for (j = s->js; j <= s->je; j++) for (i = s->is; i <= s->ie; i++, n++) {
+    size_t m = IDX(s,k,j,i);
+    if (ph) ph[n] = s->ph_rate[m];
+    if (nHdot) nHdot[n] = s->nHdot[m];
+    if (edot) edot[n] = s->edot[m];
+    if (last_sign) last_sign[n] = s->last_sign[m];
+    if (sign_count) sign_count[n] = s->sign_count[m];
+  }
+}
+
 void orc_ion_update(OrcSim *s, double dt)          /* ionization_update :565-588 + floors */
 {
   const OrcParams *p = &s->p; int i, j, k;

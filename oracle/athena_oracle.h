@@ -82,6 +82,7 @@ int    orc_step(OrcSim *s);             /* one pass of the main loop (main.c:519
 /* sub-phases of the ion step, for slab-decomposed drivers */
 void   orc_ion_begin(OrcSim *s);                                   /* ionrad_3d.c:896-905 */
 void   orc_ion_rates(OrcSim *s, double *dt_chem, double *dt_therm);/* :922-938            */
+void   orc_ion_zone_rates(OrcSim *s, double *ph, double *nHdot, double *edot, int *last_sign, int *sign_count); /* copies, active zones */
 void   orc_ion_update(OrcSim *s, double dt);                       /* :965-971            */
 long   orc_ion_check_range_count(OrcSim *s);                       /* :206-264            */
 double orc_ion_dt_hydro(OrcSim *s);                                /* :593-669            */

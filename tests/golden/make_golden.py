@@ -10,7 +10,7 @@ through oracle/_ref/libref_<cfg>.so to produce function-level known-answer vecto
 
 Fixtures are DATA (arrays + the scalar trace of each run); no reference text is stored.
 
-usage: python tests/golden/make_golden.py [whole] [shk] [dev] [kernels] [ppm] [smr] [hst] [ray] [cool] [vlppm] [noh]
+usage: python tests/golden/make_golden.py [whole] [shk] [dev] [kernels] [ppm] [smr] [hst] [ray] [cool] [vlppm] [noh] [ionmatrix]
 """
 import ctypes as C
 import os
@@ -93,12 +93,18 @@ def whole_runs():
     sphere = os.path.join(REF, "tst/massloss/athinput.ioniz_sphere_hires")
     blast = os.path.join(REF, "tst/3D-hydro/athinput.blast")
     # (name, cfg, deck, nx, nlim, extra reference-cmdline, nscal, ion, overrides for OUR decks)
-    for nx, nlims in (((16, 8, 8), (1, 3, 6)), ((8, 12, 16), (4,))):
+    # (16x5x4: 20 rays = MAXCELLCOUNT, so check_range cannot stop the sub-cycles: the step leaves by dt_hydro < dt_done, ionrad_3d.c:1003)
+    only = os.environ.get("GOLDEN_ONLY")               # (regenerate one ifront run: GOLDEN_ONLY=ifront_16x5x4_n1 python make_golden.py whole)
+    for nx, nlims in (((16, 8, 8), (1, 3, 6)), ((8, 12, 16), (4,)), ((16, 5, 4), (1,))):
         for nlim in nlims:
+            if only and only != f"ifront_{nx[0]}x{nx[1]}x{nx[2]}_n{nlim}":
+                continue
             f, l, it = run_reference("ifront", ifront, nx, nlim,
                                      ["job/maxout=3", "output3/out_fmt=rst", "output3/dt=1e300",
                                       "output1/dt=1e300", "output2/dt=1e300"], "ifront", 1, True)
             save(f"ifront_{nx[0]}x{nx[1]}x{nx[2]}_n{nlim}", f, l, it, nx, [])
+    if only:
+        return
     for nx, nlims in (((20, 20, 20), (1, 3)), ((24, 16, 12), (2,))):
         for nlim in nlims:
             f, l, it = run_reference("ioniz_sphere", sphere, nx, nlim,
@@ -137,6 +143,29 @@ def rayplane_runs():
                                  ["job/maxout=3", "output3/out_fmt=rst", "output3/dt=1e300", "output1/dt=1e300", "output2/dt=1e300",
                                   f"problem/raydir={d}"], "ifront", 1, True)
         save(f"rayplane_dir{-d}_{nx[0]}x{nx[1]}x{nx[2]}_n{nlim}", f, l, it, nx, [f"raydir={d}"])
+    shutil.rmtree(tmp)
+
+
+def ion_matrix_runs():
+    """The radiation sub-cycle's per-zone chemistry on a state designed to reach every branch of it (ionrad_3d.c:70-590): our own
+    problem file tests/fixtures/ion_matrix.c linked into the reference's ifront configuration, one step at 64x7x6 with the deck's
+    temperature ceiling and with the ceiling switched off (tceil = 0).  d_nlo travels as a <problem> key (tests/ionmatrix.py)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ionmatrix
+    import orc
+    deck0 = open(os.path.join(REF, "tst/ionradiation/athinput.ifront")).read()
+    tmp = tempfile.mkdtemp(prefix="golden_deck_")
+    deck = os.path.join(tmp, "athinput.ionmatrix")
+    nx = ionmatrix.NX
+    run = orc.make_sim("ifront", ionmatrix.overrides(nx)).grid.run
+    lo = ionmatrix.d_nlo(run, nx)
+    open(deck, "w").write(re.sub(r"(?m)^(nradplanes\s*=.*)$", r"\1\nd_nlo = %s" % repr(lo), deck0, count=1))
+    for name, tceil in (("ionmatrix", None), ("ionmatrix_tceil0", 0)):
+        over = [] if tceil is None else [f"ionradiation/tceil={tceil}"]
+        f, l, it = run_reference("ionmatrix", deck, nx, 1,
+                                 ["job/maxout=3", "output3/out_fmt=rst", "output3/dt=1e300", "output1/dt=1e300", "output2/dt=1e300"] + over,
+                                 "ifront", 1, True)
+        save(f"{name}_{nx[0]}x{nx[1]}x{nx[2]}_n1", f, l, it, nx, over)
     shutil.rmtree(tmp)
 
 
@@ -472,7 +501,9 @@ def kernel_vectors():
 if __name__ == "__main__":
     if not os.path.isdir(REF) or not os.path.isdir(REFBIN):
         sys.exit("needs /root/reference and oracle/_ref (make -C oracle ref)")
-    which = sys.argv[1:] or ["whole", "shk", "dev", "kernels", "ppm", "smr", "hst", "ray", "cool", "vlppm", "noh"]
+    which = sys.argv[1:] or ["whole", "shk", "dev", "kernels", "ppm", "smr", "hst", "ray", "cool", "vlppm", "noh", "ionmatrix"]
+    if "ionmatrix" in which:
+        ion_matrix_runs()
     if "cool" in which:
         cooling_runs()
     if "vlppm" in which:

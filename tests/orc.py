@@ -73,6 +73,8 @@ def lib():
         L.orc_step.restype = C.c_int; L.orc_step.argtypes = [P]
         L.orc_ion_rates.argtypes = [P, dp, dp]
         L.orc_ion_update.argtypes = [P, D]
+        ip = C.POINTER(C.c_int)
+        L.orc_ion_zone_rates.argtypes = [P, dp, dp, dp, ip, ip]; L.orc_ion_zone_rates.restype = None
         L.orc_ion_check_range_count.restype = C.c_long; L.orc_ion_check_range_count.argtypes = [P]
         L.orc_mesh_create.restype = P; L.orc_mesh_create.argtypes = [C.c_int, C.POINTER(OrcParams), C.POINTER(C.c_int)]
         L.orc_mesh_destroy.argtypes = [P]
@@ -195,6 +197,15 @@ class Sim:
         return a.value, b.value
 
     def ion_update(self, dt): self.L.orc_ion_update(self.h, dt)
+
+    def ion_zone_rates(self):
+        """-> (ph_rate, nHdot, edot, last_sign, sign_count) of the last ion_rates, copies over the active zones [k][j][i]"""
+        nx = self.grid.Nx; shp = (nx[2], nx[1], nx[0])
+        ph = np.zeros(shp); nHdot = np.zeros(shp); edot = np.zeros(shp)
+        ls = np.zeros(shp, dtype=np.intc); sc = np.zeros(shp, dtype=np.intc)
+        ip = C.POINTER(C.c_int)
+        self.L.orc_ion_zone_rates(self.h, _dp(ph), _dp(nHdot), _dp(edot), ls.ctypes.data_as(ip), sc.ctypes.data_as(ip))
+        return ph, nHdot, edot, ls, sc
 
     def cfl_max_v(self):
         v = np.zeros(3); self.L.orc_cfl_max_v(self.h, _dp(v)); return list(v)

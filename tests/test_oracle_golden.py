@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import ionmatrix
 import orc
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -78,6 +79,85 @@ def test_cooling_fixtures_differ_from_the_run_without():
     assert np.abs(a["U"][..., 4] / b["U"][..., 4] - 1).max() > 1e-2          # the cooling terms move the energy by per cent
 
 
+def _ionmatrix(name, g):
+    """The designed ion state (tests/ionmatrix.py) from our own problem file (tests/fixtures/ion_matrix.c) run by the reference:
+    every branch of the sub-cycle's per-zone chemistry (ionrad_3d.c:70-590), with the temperature ceiling and without."""
+    kv = dict(str(o).split("=") for o in g["overrides"])
+    s = ionmatrix.make_sim(tuple(int(n) for n in g["nx"]), kv.get("ionradiation/tceil"))
+    assert _same(s.active, g["U0"]), "initial condition"
+    s.start()
+    assert s.dt == float(g["dt0"])
+    niter = [s.step() for _ in range(int(g["nstep"]))]
+    assert niter == [int(x) for x in g["niter"]], "radiation sub-cycle counts"
+    assert s.time == float(g["time"]) and s.dt == float(g["dt"])
+    assert _same(s.active, g["U"])
+    assert _same(s.edgeflux, g["edgeflux"])
+
+
+def test_ion_matrix_fixtures_differ_where_the_ceiling_acts():
+    a = np.load(os.path.join(GOLD, "ionmatrix_64x7x6_n1.npz")); b = np.load(os.path.join(GOLD, "ionmatrix_tceil0_64x7x6_n1.npz"))
+    assert _same(a["U0"], b["U0"])
+    hot = ionmatrix.indices()[0] == 8                    # the 3e6 K zones
+    assert hot.sum() >= 32 and (a["U"][..., 4] != b["U"][..., 4])[hot].all()
+
+
+def test_ion_matrix_covers_every_branch():
+    """The census of the designed state, from the oracle's own arrays (orc_ion_zone_rates): the first rates pass puts at least 32
+    zones into every class of compute_chem_rates / compute_therm_rates, every class stays populated over the 12 sub-cycles the GPU
+    tests follow, and the entry takes every branch of the two floors in at least 32 zones.  Conditions, not measurements: a pattern
+    that misses one has to change."""
+    s = ionmatrix.make_sim()
+    run = s.grid.run
+    entry = ionmatrix.entry_census(s.active.copy(), run)
+    print("entry:", entry)
+    assert all(v >= 32 for v in entry.values()), entry
+    assert entry["T<tfloor"] == ionmatrix.floored_by_design()
+    s.bvals(); s.bvals_ionrad(); s.new_dt()
+    s.ion_begin()
+    seen = dict.fromkeys(ionmatrix.CLASSES, 0)
+    for n in range(ionmatrix.NSUB):
+        dt_chem, dt_therm = s.ion_rates()
+        c = ionmatrix.census(s)
+        if n == 0:
+            print("first rates pass:", c)
+            assert all(c[k] >= 32 for k in ionmatrix.CLASSES), c
+        assert all(c[k] > 0 for k in ionmatrix.CLASSES), (n, c)
+        for k in ionmatrix.CLASSES:
+            seen[k] += c[k]
+        s.ion_update(ionmatrix.subcycle_dt(dt_chem, dt_therm))
+    print(f"zone-sub-cycles over {ionmatrix.NSUB} sub-cycles:", seen)
+
+
+def test_ifront_with_20_rays_leaves_by_dt_hydro():
+    """ifront 16x5x4: 20 rays = MAXCELLCOUNT, so check_range never stops the sub-cycles (ionrad_3d.c:985): the one step of the golden
+    run takes its 109 sub-cycles and leaves by dt_hydro < dt_done (:1003) -- the data-dependent stop the one-kernel path learns of
+    one sweep late -- and the sign-flip damping (:360-363, sign_count > MAXSIGNCOUNT) acts on the way."""
+    g = np.load(os.path.join(GOLD, "ifront_16x5x4_n1.npz"))
+    s = orc.make_sim("ifront", [f"domain1/Nx{d + 1}={int(g['nx'][d])}" for d in range(3)])
+    s.start()
+    limit = s.dt
+    dt_done, niter, damped, exit_by = 0.0, 0, 0, None
+    s.ion_begin()
+    while exit_by is None:
+        dt_chem, dt_therm = s.ion_rates()
+        damped += int((s.ion_zone_rates()[4] > 4).sum())
+        dt = min(dt_therm, dt_chem)
+        done = dt_done + dt > limit
+        if done:
+            dt = limit - dt_done
+        s.ion_update(dt)
+        dt_done += dt; niter += 1
+        count = s.ion_check_range_count()
+        assert count <= 20
+        if done:
+            exit_by = "hydro_done"
+        elif s.ion_dt_hydro() < dt_done:
+            exit_by = "dt_hydro"
+    print(f"ifront 16x5x4: {niter} sub-cycles, exit by {exit_by}, {count} zones out of range, {damped} damped zone-sub-cycles")
+    assert exit_by == "dt_hydro" and niter == 109 == int(g["niter"][0])
+    assert damped > 0
+
+
 RUNS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*_n[0-9]*.npz")))
 
 
@@ -88,6 +168,8 @@ def test_whole_run_bitwise(name):
         return _rayplane(name, g)
     if name.startswith("coolpat"):
         return _coolpat(name, g)
+    if name.startswith("ionmatrix"):
+        return _ionmatrix(name, g)
     prob = name.rsplit("_", 2)[0]
     integrator = "ctu"
     order = 2

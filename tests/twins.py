@@ -78,3 +78,21 @@ def developed_sphere_32():
         worst = max(worst, float(np.nanmax(e)))
         nflip = max(nflip, int((e > 1e-9).any(axis=-1).sum()))
     return worst, nflip
+
+
+@functools.lru_cache(maxsize=None)
+def ion_matrix(tceil=None):
+    """-> ({quantity: largest relative spread}, most edge zones a twin took the other way) over the twins of the designed ion state
+    (tests/ionmatrix.py) driven through the same 12 sub-cycles with the base run's steps: E and s of every zone after each
+    update, EdgeFlux, the two time-step limits, dt_hydro.  An edge zone -- at the temperature floor to 1e-12, where `T < tfloor`
+    is decided in the last bit -- that takes the other branch counts with its distance from that branch's outcome."""
+    import ionmatrix
+    tr = ionmatrix.trace(tceil)
+    worst = dict.fromkeys(ionmatrix.QUANT, 0.0); nflip = 0
+    for seed in SEEDS:
+        p = ionmatrix.make_sim(tceil=tceil)
+        perturb(p.active, seed)
+        w, nf, _ = ionmatrix.follow(tr, ionmatrix.OracleFollower(p))
+        worst = {k: max(worst[k], w[k]) for k in worst}
+        nflip = max(nflip, nf)
+    return worst, nflip
