@@ -21,12 +21,15 @@ inside the C library (aa_step) with no Python between kernels.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional
 
 import numpy as np
 
+from . import config, dumps, restart
 from .config import pencil, GridConfig, RunConfig, slab
+from .history import HistoryWriter
 
 MAXCELLCOUNT = 20   # ionrad.h:38
 
@@ -145,7 +148,131 @@ class HipEngine:
     def close(self): self.g.close()
 
 
-class Driver:
+def _fires(out, level: int, domain: int = 0) -> bool:
+    """whether an <outputN> block asks for this Domain (level / domain = -1: all of them; output.c:509-560)"""
+    return out.level in (-1, level) and out.domain in (-1, domain)
+
+
+class _Runner:
+    """What Driver, MeshRun and MeshDriver share: the scalar collectives, continuing from a restart dump, and the output side that
+    outputs.OutputSet drives.  A runner has `run`, `time`, `dt`, `nstep`, `restarted`, `par` and the HistoryWriters `_hst`."""
+
+    def _init_collectives(self, rank: int, nranks: int):
+        # AA_FORCE_DISTRIBUTED=1 runs the Python-orchestrated loop (with its collectives) even on one
+        # rank: used to rehearse the N>1 code path on a single GPU
+        self.distributed = nranks > 1 or bool(os.environ.get("AA_FORCE_DISTRIBUTED"))
+        self._py_syncs = 0        # host round trips of collectives issued from here (bench: host_syncs_per_step)
+        if self.distributed:
+            import torch
+            import torch.distributed as dist
+            self.torch, self.dist = torch, dist
+            assert dist.is_initialized() and dist.get_world_size() == nranks and dist.get_rank() == rank
+            self._sdev = getattr(self.eng, "scalar_device", torch.device("cpu"))
+
+    def _allreduce(self, vals, op):
+        if not self.distributed:
+            return list(vals)
+        t = self.torch.tensor(list(vals), dtype=self.torch.float64, device=self._sdev)
+        self.dist.all_reduce(t, op=op)
+        self._py_syncs += 1
+        return t.tolist()
+
+    # ---- continuing a run (main.c -r) ------------------------------------------------------------------
+    @staticmethod
+    def _resume_head(path, overrides, problem, integrator, order):
+        """(head of rank 0's file, its parameter table with the overrides on top, the RunConfig built from that)"""
+        head0 = restart.read_head(path)
+        par = head0["par"].cmdline(overrides)
+        run = config.from_par(par, problem)
+        if integrator not in ("ctu", "vl", "ctu-noh"):
+            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
+        run.integrator, run.order = integrator, order
+        return head0, par, run
+
+    def _read_rank_file(self, head0, nxs, per_level: bool):
+        """This rank's file (restart.rank_path) into the engine: the sections of the Grids of `nxs` active zones, root first, by
+        read_rst_payload or, for an engine that keeps host blocks, load_state; per_level: both take the level first.
+        -> the file's head"""
+        run, eng = self.run, self.eng
+        head = head0 if self.rank == 0 else restart.read_head(restart.rank_path(head0["path"], self.rank))
+        head["levels"] = restart.index_sections(head, nxs, run.nscal, run.ion)
+        lev = (lambda l: (l,)) if per_level else (lambda l: ())
+        if hasattr(eng, "read_rst_payload"):
+            with open(head["path"], "rb") as f:
+                f.seek(head["offset"])
+                for l in range(len(nxs)):
+                    eng.read_rst_payload(*lev(l), f)
+        elif hasattr(eng, "load_state"):
+            for l, nx in enumerate(nxs):
+                eng.load_state(*lev(l), *restart.read_state(head, l, nx, run.nscal))
+        else:
+            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_payload or load_state)")
+        return head
+
+    def _resumed(self, head, par):
+        """time, dt and nstep of the file into the runner and its engine (_set_state); start() is then the restarted run's"""
+        self._set_state(head["time"], head["dt"], head["nstep"])
+        self.restarted, self.par = True, par
+
+    # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
+    @contextlib.contextmanager
+    def _rst_file(self, out, outputs, rel=None, table=None):
+        """dump_restart's file, open between header and trailer: the time and the step count go into the parameter table first
+        (restart.c:522-523), the table as it then stands -- or table(it) -- is the file's parameter dump.  rel: the path
+        under the rank's directory, by default ath_fname's."""
+        par = outputs.par
+        par.blocks.setdefault("time", {})["time"] = "%e" % self.time
+        par.blocks["time"]["nstep"] = "%d" % self.nstep
+        rel = rel or dumps.fname(outputs.basename, 0, 0, out.num, "rst")
+        with open(outputs.path(rel), "wb") as f:
+            restart.write_header(f, restart.par_dump(table(par) if table else par), self.nstep, self.time, self.dt)
+            yield f
+            restart.write_trailer(f)
+
+    def _host_state(self, *level):
+        """(U of the active zones, EdgeFlux or None) from the host block of an engine that has no write_rst_payload: what
+        restart.write_grid_sections takes.  level: none for Driver's engine, (l,) for MeshDriver's."""
+        ng = config.NGHOST
+        U = self.eng.download(*level)[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
+        ef = None
+        if self.run.ion:
+            edgeflux = getattr(self.eng, "edgeflux" if level else "download_edgeflux", None)
+            if edgeflux is None:
+                raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
+            ef = edgeflux(*level)
+        return U, ef
+
+    def _domain_volume(self, Nx, level: int) -> float:
+        """of a Domain of Nx zones of a refined mesh (Driver has its own: the root Domain's, from its edges)"""
+        vol = 1.0
+        for a in range(3):
+            vol *= Nx[a] * (self.run.dx[a] / float(1 << level))
+        return vol
+
+    def _history_row(self, key, rundir, level, domain, out, outputs, sums, vol):
+        """One row of the .hst file of a Domain of volume `vol` (dump_history.c:271-279, :328-361): `sums` are its volume
+        integrals, already added over its Grids; the writer is kept under `key` for the rows to come."""
+        w = self._hst.get(key)
+        if w is None:
+            w = self._hst[key] = HistoryWriter(rundir, outputs.basename, level, domain, out.dat_fmt, num=out.num)
+        w.dump(self.time, self.dt, sums, vol, self.run.nscal)
+        rel = os.path.relpath(w.path, outputs.dir)
+        if rel not in outputs.written:
+            outputs.written.append(rel)
+
+    def data_output(self, outputs, flag: int):
+        """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
+        outputs.data_output(self, flag)
+
+    def main(self, outputs):
+        """main.c:501-743: start, forced output (not after a restart), the loop up to <time>tlim / nlim with data_output(0) at
+        the top of every pass, forced output.  Every rank of a multi-rank run calls it with its own
+        OutputSet.from_par(par, time, rundir, rank, nranks) and writes its own Grids."""
+        from . import outputs as _outputs
+        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
+
+
+class Driver(_Runner):
     """main() of the reference for one process of an N-process run."""
 
     def __init__(self, run: RunConfig, engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0,
@@ -164,16 +291,7 @@ class Driver:
         self.niter_trace: List[int] = []
         self._hst = {}            # HistoryWriter per <outputN> block with out_fmt = hst
         self._halo = {}           # messages in flight per axis (2: x2, 3: x3): post .. finish
-        self._py_syncs = 0        # host round trips of collectives issued from here (bench: host_syncs_per_step)
-        # AA_FORCE_DISTRIBUTED=1 runs the Python-orchestrated loop (with its collectives) even on one
-        # rank: used to rehearse the N>1 code path on a single GPU
-        self.distributed = nranks > 1 or bool(os.environ.get("AA_FORCE_DISTRIBUTED"))
-        if self.distributed:
-            import torch
-            import torch.distributed as dist
-            self.torch, self.dist = torch, dist
-            assert dist.is_initialized() and dist.get_world_size() == nranks and dist.get_rank() == rank
-            self._sdev = getattr(self.eng, "scalar_device", torch.device("cpu"))
+        self._init_collectives(rank, nranks)
 
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
@@ -190,51 +308,26 @@ class Driver:
         that does (restart.scan_sources, restart.box_pieces); time, dt and nstep are rank 0's file's.  `.par` then names the new
         cuts (NGrid_x1 = 1, NGrid_x2 = p2, NGrid_x3 = nranks / p2, no AutoWithNProc), so that a later dump describes itself.
         Single-level meshes only."""
-        from . import config, restart
-        head0 = restart.read_head(path)
-        par = head0["par"].cmdline(overrides)
-        run = config.from_par(par, problem)
-        if integrator not in ("ctu", "vl", "ctu-noh"):
-            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
-        run.integrator, run.order = integrator, order
-        if regrid:
-            sources = restart.scan_sources(path, run.rootNx, run.nscal, run.ion, head0)
-            d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
-            if hasattr(d.eng, "read_rst_boxes"):
-                d.eng.read_rst_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx)
-            elif hasattr(d.eng, "load_state"):
-                d.eng.load_state(*restart.read_state_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx, run.nscal))
-            else:
-                raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_boxes or load_state)")
-            d.time, d.dt, d.nstep = head0["time"], head0["dt"], head0["nstep"]
-            d.eng.set_mesh_state(d.time, d.dt, d.nstep)
-            d.restarted, d.par = True, restart.regrid_par(par, (1, p2, nranks // p2))
-            return d
+        head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        sources = restart.scan_sources(path, run.rootNx, run.nscal, run.ion, head0) if regrid else None
         d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
-        head = head0 if rank == 0 else restart.read_head(restart.rank_path(path, rank))
-        head["levels"] = restart.index_sections(head, [d.grid.Nx], run.nscal, run.ion)
-        if hasattr(d.eng, "read_rst_payload"):
-            with open(head["path"], "rb") as f:
-                f.seek(head["offset"])
-                d.eng.read_rst_payload(f)
+        if not regrid:
+            d._resumed(d._read_rank_file(head0, [d.grid.Nx], per_level=False), par)
+            return d
+        if hasattr(d.eng, "read_rst_boxes"):
+            d.eng.read_rst_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx)
         elif hasattr(d.eng, "load_state"):
-            d.eng.load_state(*restart.read_state(head, 0, d.grid.Nx, run.nscal))
+            d.eng.load_state(*restart.read_state_boxes(sources, run.rootNx, d.grid.disp, d.grid.Nx, run.nscal))
         else:
-            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_payload or load_state)")
-        d.time, d.dt, d.nstep = head["time"], head["dt"], head["nstep"]
-        d.eng.set_mesh_state(d.time, d.dt, d.nstep)
-        d.restarted, d.par = True, par
+            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_boxes or load_state)")
+        d._resumed(head0, restart.regrid_par(par, (1, p2, nranks // p2)))
         return d
 
-    # ---- collectives ------------------------------------------------------------------
-    def _allreduce(self, vals, op):
-        if not self.distributed:
-            return list(vals)
-        t = self.torch.tensor(list(vals), dtype=self.torch.float64, device=self._sdev)
-        self.dist.all_reduce(t, op=op)
-        self._py_syncs += 1
-        return t.tolist()
+    def _set_state(self, time, dt, nstep):
+        self.time, self.dt, self.nstep = time, dt, nstep
+        self.eng.set_mesh_state(time, dt, nstep)
 
+    # ---- collectives ------------------------------------------------------------------
     def host_sync_count(self, reset: bool = False) -> int:
         """Times the host waited for the device to hand back scalars (library read-backs + collectives' .tolist())."""
         n = self._py_syncs + (self.eng.host_syncs(reset) if hasattr(self.eng, "host_syncs") else 0)
@@ -254,104 +347,69 @@ class Driver:
 
     def dump_history(self, writer):
         """One row of the .hst file (history.HistoryWriter); call it where main.c calls data_output."""
+        s = self.history()
+        if self.rank == 0:
+            writer.dump(self.time, self.dt, s, self._volume(), self.run.nscal)
+
+    def _volume(self) -> float:
+        """of the root Domain, from its edges: not always the double that Nx * dx gives (_Runner._domain_volume)"""
         vol = 1.0
         for d in range(3):
             vol *= self.run.xmax[d] - self.run.xmin[d]
-        s = self.history()
-        if self.rank == 0:
-            writer.dump(self.time, self.dt, s, vol, self.run.nscal)
+        return vol
 
     # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
     def write_dump(self, out, outputs):
         """dump_vtk / dump_binary of this rank's Grid (level 0, domain 0) for one <outputN> block."""
-        from . import dumps
-        if out.level not in (-1, 0) or out.domain not in (-1, 0):
+        if not _fires(out, 0):
             return
         g, r = self.grid, self.run
         path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, out.out_fmt))
         if hasattr(self.eng, "write_dump"):
             self.eng.write_dump(path, out.out_fmt, out.prim, self.time, self.dt)
         else:                                     # an engine without a device: the same payload from its host block
-            ng = 4
+            ng = config.NGHOST
             U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng]
             dumps.write_dump_from_block(path, out.out_fmt, U, prim=out.prim, gamma=r.gamma, nscal=r.nscal, nx=g.Nx,
                                         minx=g.MinX, dx=r.dx, time=self.time, dt=self.dt)
 
     def write_history(self, out, outputs):
-        from .history import HistoryWriter
-        if out.level not in (-1, 0) or out.domain not in (-1, 0):
+        if not _fires(out, 0):
             return
-        w = self._hst.get(out.n)
-        if w is None:
-            w = self._hst[out.n] = HistoryWriter(outputs.dir, outputs.basename, 0, 0, out.dat_fmt, num=out.num)
-        self.dump_history(w)                      # (every rank takes part in the sum; rank 0 writes)
-        rel = os.path.relpath(w.path, outputs.dir)
-        if self.rank == 0 and rel not in outputs.written:
-            outputs.written.append(rel)
+        s = self.history()                        # (every rank takes part in the sum; rank 0 writes)
+        if self.rank == 0:
+            self._history_row(out.n, outputs.dir, 0, 0, out, outputs, s, self._volume())
 
     def write_restart(self, out, outputs):
         """dump_restart (restart.c:463-983): this rank's Grid under the parameter table as it stands now."""
-        from . import dumps, restart
-        ng = 4
-        par = outputs.par
-        par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
-        par.blocks["time"]["nstep"] = "%d" % self.nstep
         if getattr(outputs, "rst_ngrid", None):
             return self._write_restart_split(out, outputs)
-        if hasattr(self.eng, "write_rst_payload"):        # the sections come from the device in file order (csrc/restart.hip)
-            path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
-            with open(path, "wb") as f:
-                restart.write_header(f, restart.par_dump(par), self.nstep, self.time, self.dt)
+        with self._rst_file(out, outputs) as f:
+            if hasattr(self.eng, "write_rst_payload"):    # the sections come from the device in file order (csrc/restart.hip)
                 self.eng.write_rst_payload(f)
-                restart.write_trailer(f)
-            return
-        U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
-        ef = None
-        if self.run.ion:
-            if not hasattr(self.eng, "download_edgeflux"):
-                raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
-            ef = self.eng.download_edgeflux()
-        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
-        restart.write_rst(path, restart.par_dump(par), self.nstep, self.time, self.dt, U, ef)
+            else:
+                restart.write_grid_sections(f, *self._host_state())
 
     def _write_restart_split(self, out, outputs):
         """OutputSet(rst_ngrid=...): one file per Grid of restart.grid_boxes, ``id<r>/<base>[-id<r>].NNNN.rst`` as the ranks of a
         run on those cuts would leave them -- each under a table with NGrid_x* set to the target and its own problem_id, each
         with the box of every section (EDGEFLUX with its n + 1 faces)."""
-        from . import dumps, restart
-        ng = 4
         if self.nranks > 1:
             raise ValueError("[dump_restart]: rst_ngrid takes a one-rank run")
         U = ef = None
         if not hasattr(self.eng, "write_rst_box_payload"):
-            U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
-            if self.run.ion:
-                if not hasattr(self.eng, "download_edgeflux"):
-                    raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
-                ef = self.eng.download_edgeflux()
+            U, ef = self._host_state()
         for r, lo, n in restart.grid_boxes(self.run.rootNx, outputs.rst_ngrid):
             base = outputs.basename + ("-id%d" % r if r else "")
-            path = outputs.path(os.path.join("id%d" % r, dumps.fname(base, 0, 0, out.num, "rst")))
-            text = restart.par_dump(restart.regrid_par(outputs.par, outputs.rst_ngrid, r, outputs.basename))
-            with open(path, "wb") as f:
-                restart.write_header(f, text, self.nstep, self.time, self.dt)
+            rel = os.path.join("id%d" % r, dumps.fname(base, 0, 0, out.num, "rst"))
+            with self._rst_file(out, outputs, rel,
+                                lambda par: restart.regrid_par(par, outputs.rst_ngrid, r, outputs.basename)) as f:
                 if U is None:
                     self.eng.write_rst_box_payload(f, lo, n)
                 else:
                     k, j, i = (slice(lo[d], lo[d] + n[d]) for d in (2, 1, 0))
                     k1, j1, i1 = (slice(lo[d], lo[d] + n[d] + 1) for d in (2, 1, 0))
                     restart.write_grid_sections(f, U[k, j, i], None if ef is None else ef[k1, j1, i1])
-                restart.write_trailer(f)
-
-    def data_output(self, outputs, flag: int):
-        """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
-        outputs.data_output(self, flag)
-
-    def main(self, outputs):
-        """(`run` is taken: the RunConfig of this Driver.)  main.c:501-743: start, forced output, the loop up to <time>tlim / nlim with data_output(0) at the top of every
-        pass, forced output.  Every rank of a multi-rank run calls it and writes its own Grid."""
-        from . import outputs as _outputs
-        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
     def exchange_x3(self):
         """bvals_mhd.c:423-493 for the x3 direction."""
@@ -580,7 +638,7 @@ class Driver:
         return niter
 
 
-class MeshRun:
+class MeshRun(_Runner):
     """main() of the reference built with STATIC_MESH_REFINEMENT for a lib.Mesh (all levels on one GPU; the loop itself is
     aa_mesh_step): what outputs.run / OutputSet.data_output need -- time, nstep, start, step and the three writers, which loop
     over the Domains like dump_vtk / dump_binary / dump_history / dump_restart do."""
@@ -595,24 +653,19 @@ class MeshRun:
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
                      device: int = 0, strict: Optional[bool] = None) -> "MeshRun":
         """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770)."""
-        from . import config, lib, restart
-        head = restart.read_head(path)
-        par = head["par"].cmdline(overrides)
-        run = config.from_par(par, problem)
-        if integrator not in ("ctu", "vl", "ctu-noh"):
-            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
-        run.integrator, run.order = integrator, order
+        from . import lib
+        head, par, run = cls._resume_head(path, overrides, problem, integrator, order)
         grids = config.levels(par, run)
         head["levels"] = restart.index_sections(head, [g.Nx for g in grids], run.nscal, run.ion)
-        mesh = lib.Mesh(grids, device, strict, initial=False)
+        m = cls(lib.Mesh(grids, device, strict, initial=False), run)
         with open(path, "rb") as f:
             f.seek(head["offset"])
-            for g in mesh.lev:
+            for g in m.mesh.lev:
                 g.read_rst_payload(f)
-        mesh.set_state(head["time"], head["dt"], head["nstep"])
-        m = cls(mesh, run)
-        m.restarted, m.par = True, par
+        m._resumed(head, par)
         return m
+
+    def _set_state(self, time, dt, nstep): self.mesh.set_state(time, dt, nstep)
 
     time = property(lambda s: s.mesh.time)
     dt = property(lambda s: s.mesh.dt)
@@ -631,41 +684,15 @@ class MeshRun:
             outputs.written.append(rel)
 
     def write_history(self, out, outputs):
-        from .history import HistoryWriter
-        t, dt, _ = self.mesh.state()
         for g, (l, d) in zip(self.mesh.lev, self.mesh.domain_numbers()):
-            if out.level not in (-1, l) or out.domain not in (-1, d):
-                continue
-            w = self._hst.get((out.n, l, d))
-            if w is None:
-                w = self._hst[(out.n, l, d)] = HistoryWriter(outputs.dir, outputs.basename, l, d, out.dat_fmt, num=out.num)
-            vol = 1.0
-            for a in range(3):
-                vol *= g.cfg.Nx[a] * (self.run.dx[a] / float(1 << l))
-            w.dump(t, dt, g.history(), vol, self.run.nscal)
-            rel = os.path.relpath(w.path, outputs.dir)
-            if rel not in outputs.written:
-                outputs.written.append(rel)
+            if _fires(out, l, d):
+                self._history_row((out.n, l, d), outputs.dir, l, d, out, outputs, g.history(), self._domain_volume(g.cfg.Nx, l))
 
     def write_restart(self, out, outputs):
-        """one file for all levels (restart.c:531-770)"""
-        from . import dumps, restart
-        t, dt, n = self.mesh.state()
-        par = outputs.par
-        par.blocks.setdefault("time", {})["time"] = "%e" % t
-        par.blocks["time"]["nstep"] = "%d" % n
-        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
-        with open(path, "wb") as f:                       # the sections of every level from the device in file order
-            restart.write_header(f, restart.par_dump(par), n, t, dt)
+        """one file for all levels (restart.c:531-770), the sections of every level from the device in file order"""
+        with self._rst_file(out, outputs) as f:
             for g in self.mesh.lev:
                 g.write_rst_payload(f)
-            restart.write_trailer(f)
-
-    def data_output(self, outputs, flag: int): outputs.data_output(self, flag)
-
-    def main(self, outputs):
-        from . import outputs as _outputs
-        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
 
 # ==================================================================================================
@@ -772,7 +799,7 @@ class HipMeshEngine:
     def close(self): self.mesh.close()
 
 
-class MeshDriver:
+class MeshDriver(_Runner):
     """main() of the reference built with STATIC_MESH_REFINEMENT (main.c:395-447, :519-669) for one
     process of an N-process run in which every level is cut into x3 slabs at the same root planes
     (config.mesh_slabs).  Inside a rank the level coupling is the local aa_mesh; across ranks go the
@@ -783,14 +810,9 @@ class MeshDriver:
     def __init__(self, par, run: RunConfig, engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0,
                  strict: Optional[bool] = None, cuts=None, initial: bool = True):
         """initial = False: the product engine skips the problem generator (from_restart loads the state)"""
-        from .config import mesh_slabs
-        import torch
-        import torch.distributed as dist
-        self.torch, self.dist = torch, dist
         self.run, self.rank, self.nranks = run, rank, nranks
-        from .config import levels as _levels
-        self.cfg = mesh_slabs(par, run, rank, nranks, cuts)
-        self.domains = _levels(par, run)                  # the whole Domain of every level (history: its volume)
+        self.cfg = config.mesh_slabs(par, run, rank, nranks, cuts)
+        self.domains = config.levels(par, run)            # the whole Domain of every level (history: its volume)
         self.level_nx1 = [g.Nx[0] for g in self.domains]  # zones along the rays of every level (x3 slabs keep them)
         self.eng = engine_factory(self.cfg) if engine_factory else HipMeshEngine(self.cfg, device, strict, initial=initial)
         self.restarted = False    # from_restart: start() is the restarted run's, outputs.run skips the forced first output
@@ -801,11 +823,7 @@ class MeshDriver:
         self.time, self.dt, self.nstep = 0.0, 0.0, 0
         self.dtl = [0.0] * self.NL                        # pGrid->dt of every level
         self.tcoarse = 0.0
-        # AA_FORCE_DISTRIBUTED=1: issue the collectives even on one rank (rehearsal of the N>1 path)
-        self.distributed = nranks > 1 or bool(os.environ.get("AA_FORCE_DISTRIBUTED"))
-        if self.distributed:
-            assert dist.is_initialized() and dist.get_world_size() == nranks and dist.get_rank() == rank
-        self._sdev = getattr(self.eng, "scalar_device", torch.device("cpu"))
+        self._init_collectives(rank, nranks)
         self.niter_trace: List[List[int]] = []
         self._fused_cache = {}
 
@@ -821,59 +839,31 @@ class MeshDriver:
         written for other cuts or another number of ranks holds Grids of other sizes and is refused by the size check of
         restart.index_sections.  The problem generator does not run.  The driver keeps the table as `.par`:
         OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block."""
-        from . import config, restart
-        head0 = restart.read_head(path)
-        par = head0["par"].cmdline(overrides)
-        run = config.from_par(par, problem)
-        if integrator not in ("ctu", "vl", "ctu-noh"):
-            raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
-        run.integrator, run.order = integrator, order
+        head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
         d = cls(par, run, engine_factory, rank, nranks, device, strict, cuts, initial=False)
-        head = head0 if rank == 0 else restart.read_head(restart.rank_path(path, rank))
-        nxs = [g.Nx for g in d.cfg.levels]
-        head["levels"] = restart.index_sections(head, nxs, run.nscal, run.ion)
-        if hasattr(d.eng, "read_rst_payload"):
-            with open(head["path"], "rb") as f:
-                f.seek(head["offset"])
-                for l in range(d.nl):
-                    d.eng.read_rst_payload(l, f)
-        elif hasattr(d.eng, "load_state"):
-            for l in range(d.nl):
-                d.eng.load_state(l, *restart.read_state(head, l, nxs[l], run.nscal))
-        else:
-            raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_payload or load_state)")
-        d.time, d.dt, d.nstep = head["time"], head["dt"], head["nstep"]
-        d.dtl = [d.dt] * d.NL
-        if hasattr(d.eng, "set_mesh_state"):
-            d.eng.set_mesh_state(d.time, d.dt, d.nstep)
-        for l in range(d.nl):
-            d.eng.set_level_state(l, d.time, d.dt, d.nstep)
-        d.restarted, d.par = True, par
+        d._resumed(d._read_rank_file(head0, [g.Nx for g in d.cfg.levels], per_level=True), par)
         return d
 
-    def _allreduce(self, vals, op):
-        if not self.distributed:
-            return list(vals)
-        t = self.torch.tensor(list(vals), dtype=self.torch.float64, device=self._sdev)
-        self.dist.all_reduce(t, op=op)
-        return t.tolist()
+    def _set_state(self, time, dt, nstep):
+        self.time, self.dt, self.nstep = time, dt, nstep
+        self.dtl = [dt] * self.NL
+        if hasattr(self.eng, "set_mesh_state"):
+            self.eng.set_mesh_state(time, dt, nstep)
+        for l in range(self.nl):
+            self.eng.set_level_state(l, time, dt, nstep)
 
     # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
-    def _fires(self, out, l: int) -> bool:
-        return out.level in (-1, l) and out.domain in (-1, 0)
-
     def write_dump(self, out, outputs):
         """dump_vtk / dump_binary under MPI + SMR: one file per level this rank holds zones of, under the rank's directory;
         the header is the slab's own (its DIMENSIONS and ORIGIN, the level's spacing, the Mesh time)."""
-        from . import dumps
         if hasattr(self.eng, "write_dump"):
             for rel in self.eng.write_dump(outputs.dir, outputs.basename, out.num, out.out_fmt, out.prim, out.level, out.domain,
                                            self.time, self.dt):
                 outputs.written.append(rel)
             return
-        ng, r = 4, self.run
+        ng, r = config.NGHOST, self.run
         for l, g in enumerate(self.cfg.levels):   # an engine without a device: the same payload from its host blocks
-            if not self._fires(out, l):
+            if not _fires(out, l):
                 continue
             path = outputs.path(dumps.fname(outputs.basename, l, 0, out.num, out.out_fmt))
             U = self.eng.download(l)[ng:-ng, ng:-ng, ng:-ng]
@@ -895,60 +885,21 @@ class MeshDriver:
     def write_history(self, out, outputs):
         """One row per level.  The sums are divided by the volume of the whole Domain (:271-279); the lowest rank that holds
         zones of a level writes its file, under rank 0's directory with its OWN problem_id in the name (:328-349)."""
-        from .history import HistoryWriter
         s = self.history()                         # (every rank takes part in the sum)
         id0 = os.path.join(os.path.dirname(outputs.dir), "id0") if outputs.nranks > 1 else outputs.dir
         for l, g in enumerate(self.domains):
-            if not self._fires(out, l):
-                continue
-            writer = min(r for r in range(self.nranks) if self.cfg.table[r][l] is not None)
-            if writer != self.rank:
-                continue
-            w = self._hst.get((out.n, l))
-            if w is None:
-                w = self._hst[(out.n, l)] = HistoryWriter(id0, outputs.basename, l, 0, out.dat_fmt, num=out.num)
-            vol = 1.0
-            for a in range(3):
-                vol *= g.Nx[a] * (self.run.dx[a] / float(1 << l))
-            w.dump(self.time, self.dt, s[l], vol, self.run.nscal)
-            rel = os.path.relpath(w.path, outputs.dir)
-            if rel not in outputs.written:
-                outputs.written.append(rel)
+            if _fires(out, l) and self.rank == min(r for r in range(self.nranks) if self.cfg.table[r][l] is not None):
+                self._history_row((out.n, l), id0, l, 0, out, outputs, s[l], self._domain_volume(g.Nx, l))
 
     def write_restart(self, out, outputs):
         """dump_restart (restart.c:463-983): ONE file per rank -- the parameter table as it stands now, then the sections of
         every Grid this rank holds, root first (:531-770)."""
-        from . import dumps, restart
-        ng = 4
-        par = outputs.par
-        par.blocks.setdefault("time", {})["time"] = "%e" % self.time        # restart.c:522-523
-        par.blocks["time"]["nstep"] = "%d" % self.nstep
-        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, "rst"))
-        with open(path, "wb") as f:
-            restart.write_header(f, restart.par_dump(par), self.nstep, self.time, self.dt)
+        with self._rst_file(out, outputs) as f:
             for l in range(self.nl):
                 if hasattr(self.eng, "write_rst_payload"):    # the sections come from the device in file order (csrc/restart.hip)
                     self.eng.write_rst_payload(l, f)
-                    continue
-                U = self.eng.download(l)[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
-                ef = None
-                if self.run.ion:
-                    if not hasattr(self.eng, "edgeflux"):
-                        raise RuntimeError("[dump_restart]: this engine cannot hand out GridS.EdgeFlux")
-                    ef = self.eng.edgeflux(l)
-                restart.write_grid_sections(f, U, ef)
-            restart.write_trailer(f)
-
-    def data_output(self, outputs, flag: int):
-        """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
-        outputs.data_output(self, flag)
-
-    def main(self, outputs):
-        """main.c:501-743 for this rank: start, forced output (not after a restart), the loop up to <time>tlim / nlim with
-        data_output(0) at the top of every pass, forced output.  Every rank calls it with its own
-        OutputSet.from_par(par, time, rundir, rank, nranks)."""
-        from . import outputs as _outputs
-        _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
+                else:
+                    restart.write_grid_sections(f, *self._host_state(l))
 
     def _p2p(self, sends, recvs):
         """sends: [(tensor, peer)], recvs: [(tensor, peer)]; gloo moves host tensors only."""

@@ -9,9 +9,12 @@ pdf``, user outputs by ``name =`` -- is refused by ``from_par`` with the block a
 its first dump.
 
 ``data_output(target, flag)`` drives a *target*: anything with ``time`` and the three writers ``write_dump(out, self)``,
-``write_history(out, self)``, ``write_restart(out, self)`` (driver.Driver and driver.MeshRun).  File names are ath_fname's
-(dumps.fname); rank r of a multi-rank run writes under ``id<r>/`` with ``-id<r>`` in the base name for r > 0 (main.c:227-232,
-:785-850), every rank its own Grid.
+``write_history(out, self)``, ``write_restart(out, self)``: driver.Driver (one Grid per rank), driver.MeshRun (every level of a
+refined mesh on one GPU) and driver.MeshDriver (a refined mesh over several ranks).  What the three have in common on this side --
+the restart file between header and trailer, the host-block state, the history row, the level / domain test, ``data_output``
+and ``main`` -- is written once in their base class driver._Runner.  File names are ath_fname's (dumps.fname); rank r of a
+multi-rank run writes under ``id<r>/`` with ``-id<r>`` in the base name for r > 0 (main.c:227-232, :785-850), every rank its own
+Grids; the history of a Domain goes out once, under rank 0's directory.
 """
 from __future__ import annotations
 

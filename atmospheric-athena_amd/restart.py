@@ -9,11 +9,28 @@ each over ACTIVE zones, [k][j][i]), with ion radiation ``\\nEDGEFLUX\\n`` ((Nx1+
 doubles), then ``\\nSCALAR n\\n`` per passive scalar; finally ``\\nUSER_DATA\\n`` followed by whatever
 the problem file writes (nothing for ifront / ioniz_sphere / blast).  With static mesh refinement
 the Grid blocks of all Domains follow each other, root first (the loop over levels of
-restart.c:531-770), under the one header: `write_rst_levels` / `read_rst_levels`.
+restart.c:531-770), under the one header.
 
-With these two functions a run of this package can be continued by the reference
-(``athena -r file.rst``) and vice versa, and the parity tests can start from a developed
-reference state instead of the initial condition.
+One writer: `write_header`, `write_grid_sections` per Grid (or the engine's own payload from the
+device, lib.Grid.write_rst_payload, between the same two), `write_trailer`.  `write_rst_levels` is
+those three on a file of its own, `write_rst` its one-level case.
+
+One reader, which never holds more than one section of the file: `read_head` (the parameter dump,
+nstep, time, dt), `index_sections` (every label looked at in its place, the total size checked
+against the file's) and `read_state` (one level's host block); `scan_rst` is the first two,
+`read_rst_levels` all three for every level, `read_rst` its one-level case.  A file that is not
+exactly the head, the sections of the Grids asked for and ``USER_DATA`` is refused with the
+reference's ``[restart_grids]: Expected LABEL`` (RestartError, a ValueError) -- a truncated file,
+one of another mesh, and also one with bytes after ``USER_DATA``: none of the built problems
+writes any, so there is nothing they could be read into.
+
+After that: the files of the other ranks of a run (`rank_path`), and resuming on another
+decomposition (`grid_boxes`, `scan_sources`, `box_pieces`, `read_box`, `read_state_boxes`,
+`regrid_par`).
+
+With this a run of this package can be continued by the reference (``athena -r file.rst``) and
+vice versa, and the parity tests can start from a developed reference state instead of the
+initial condition.
 """
 from __future__ import annotations
 
@@ -40,127 +57,56 @@ def par_dump(par: ParTable) -> str:
     return "\n".join(out) + "\n"
 
 
-def write_rst(path: str, par_text: str, nstep: int, time: float, dt: float, U: np.ndarray,
-              edgeflux: Optional[np.ndarray] = None) -> None:
-    """U: active zones [Nx3][Nx2][Nx1][nvar] (nvar = 5 or 6)."""
+# ---- the writer: header, one Grid's sections per Grid, trailer -----------------------------------------------------------------
+
+def _tag(label: str, first: bool = False) -> bytes:
+    """A label as it stands in the file: on a line of its own, the newline in front of it closing the data before it"""
+    return (b"" if first else b"\n") + label.encode() + b"\n"
+
+
+def write_header(f, par_text: str, nstep: int, time: float, dt: float) -> None:
+    """Everything in front of the first Grid's sections: the parameter dump, N_STEP, TIME, TIME_STEP"""
     if not par_text.rstrip().endswith("<par_end>"):
         par_text = par_text.rstrip("\n") + "\n<par_end>\n"
-    nvar = U.shape[-1]
-    with open(path, "wb") as f:
-        f.write(par_text.encode())
-        f.write(b"N_STEP\n" + struct.pack("<i", int(nstep)))
-        f.write(b"\nTIME\n" + struct.pack("<d", float(time)))
-        f.write(b"\nTIME_STEP\n" + struct.pack("<d", float(dt)))
-        for c, lab in enumerate(_LABELS):
-            f.write(b"\n" + lab.encode() + b"\n")
-            f.write(np.ascontiguousarray(U[..., c], dtype="<f8").tobytes())
-        if edgeflux is not None:
-            f.write(b"\nEDGEFLUX\n")
-            f.write(np.ascontiguousarray(edgeflux, dtype="<f8").tobytes())
-        for n in range(nvar - 5):
-            f.write(f"\nSCALAR {n}\n".encode())
-            f.write(np.ascontiguousarray(U[..., 5 + n], dtype="<f8").tobytes())
-        f.write(b"\nUSER_DATA\n")
+    f.write(par_text.encode())
+    f.write(_tag("N_STEP", first=True) + struct.pack("<i", int(nstep)))
+    f.write(_tag("TIME") + struct.pack("<d", float(time)))
+    f.write(_tag("TIME_STEP") + struct.pack("<d", float(dt)))
 
 
-def read_rst(path: str, nx: Sequence[int], nscal: int, ion: bool) -> Dict:
-    b = open(path, "rb").read()
-    end = b.index(b"<par_end>")
-    end = b.index(b"\n", end) + 1
-    header = b[:end].decode(errors="replace")
-    pos = end
-    if b[pos:pos + 7] != b"N_STEP\n":
-        raise ValueError("[restart_grids]: Expected N_STEP")
-    pos += 7
-    nstep = struct.unpack_from("<i", b, pos)[0]; pos += 4
+def write_grid_sections(f, U: np.ndarray, edgeflux: Optional[np.ndarray] = None) -> None:
+    """One Grid's labelled sections from a host block of ACTIVE zones [Nx3][Nx2][Nx1][nvar] (nvar = 5 + passive scalars; engines
+    without a device); the bytes lib.Grid.write_rst_payload writes for the same state."""
+    sections = [(lab, U[..., c]) for c, lab in enumerate(_LABELS)]
+    if edgeflux is not None:
+        sections.append(("EDGEFLUX", edgeflux))
+    sections += [(f"SCALAR {n}", U[..., 5 + n]) for n in range(U.shape[-1] - 5)]
+    for label, a in sections:
+        f.write(_tag(label))
+        f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
 
-    def expect(label: bytes):
-        nonlocal pos
-        tag = b"\n" + label + b"\n"
-        if b[pos:pos + len(tag)] != tag:
-            raise ValueError(f"[restart_grids]: Expected {label.decode()}, found {b[pos:pos + 24]!r}")
-        pos += len(tag)
 
-    expect(b"TIME"); time = struct.unpack_from("<d", b, pos)[0]; pos += 8
-    expect(b"TIME_STEP"); dt = struct.unpack_from("<d", b, pos)[0]; pos += 8
-    n = int(nx[0]) * int(nx[1]) * int(nx[2])
-    U = np.zeros((nx[2], nx[1], nx[0], 5 + nscal))
-    for c, lab in enumerate(_LABELS):
-        expect(lab.encode())
-        U[..., c] = np.frombuffer(b, dtype="<f8", count=n, offset=pos).reshape(nx[2], nx[1], nx[0]); pos += 8 * n
-    ef = None
-    if ion:
-        expect(b"EDGEFLUX")
-        ne = (nx[0] + 1) * (nx[1] + 1) * (nx[2] + 1)
-        ef = np.frombuffer(b, dtype="<f8", count=ne, offset=pos).reshape(nx[2] + 1, nx[1] + 1, nx[0] + 1).copy(); pos += 8 * ne
-    for s in range(nscal):
-        expect(f"SCALAR {s}".encode())
-        U[..., 5 + s] = np.frombuffer(b, dtype="<f8", count=n, offset=pos).reshape(nx[2], nx[1], nx[0]); pos += 8 * n
-    expect(b"USER_DATA")
-    return dict(header=header, par=ParTable.from_text(header), nstep=nstep, time=time, dt=dt, U=U, edgeflux=ef)
+def write_trailer(f) -> None:
+    f.write(_tag("USER_DATA"))
 
 
 def write_rst_levels(path: str, par_text: str, nstep: int, time: float, dt: float,
                      levels: Sequence[Sequence[Optional[np.ndarray]]]) -> None:
     """levels: [(U_active, edgeflux or None), ...] root first."""
-    if not par_text.rstrip().endswith("<par_end>"):
-        par_text = par_text.rstrip("\n") + "\n<par_end>\n"
     with open(path, "wb") as f:
-        f.write(par_text.encode())
-        f.write(b"N_STEP\n" + struct.pack("<i", int(nstep)))
-        f.write(b"\nTIME\n" + struct.pack("<d", float(time)))
-        f.write(b"\nTIME_STEP\n" + struct.pack("<d", float(dt)))
+        write_header(f, par_text, nstep, time, dt)
         for U, edgeflux in levels:
-            for c, lab in enumerate(_LABELS):
-                f.write(b"\n" + lab.encode() + b"\n")
-                f.write(np.ascontiguousarray(U[..., c], dtype="<f8").tobytes())
-            if edgeflux is not None:
-                f.write(b"\nEDGEFLUX\n")
-                f.write(np.ascontiguousarray(edgeflux, dtype="<f8").tobytes())
-            for n in range(U.shape[-1] - 5):
-                f.write(f"\nSCALAR {n}\n".encode())
-                f.write(np.ascontiguousarray(U[..., 5 + n], dtype="<f8").tobytes())
-        f.write(b"\nUSER_DATA\n")
+            write_grid_sections(f, U, edgeflux)
+        write_trailer(f)
 
 
-def read_rst_levels(path: str, nxs: Sequence[Sequence[int]], nscal: int, ion: bool) -> Dict:
-    """nxs: active zones (Nx1, Nx2, Nx3) of every level, root first."""
-    b = open(path, "rb").read()
-    end = b.index(b"<par_end>")
-    end = b.index(b"\n", end) + 1
-    header = b[:end].decode(errors="replace")
-    pos = end
-
-    def expect(label: bytes):
-        nonlocal pos
-        tag = (b"" if label == b"N_STEP" else b"\n") + label + b"\n"
-        if b[pos:pos + len(tag)] != tag:
-            raise ValueError(f"[restart_grids]: Expected {label.decode()}, found {b[pos:pos + 24]!r}")
-        pos += len(tag)
-
-    expect(b"N_STEP"); nstep = struct.unpack_from("<i", b, pos)[0]; pos += 4
-    expect(b"TIME"); time = struct.unpack_from("<d", b, pos)[0]; pos += 8
-    expect(b"TIME_STEP"); dt = struct.unpack_from("<d", b, pos)[0]; pos += 8
-    levels = []
-    for nx in nxs:
-        n = int(nx[0]) * int(nx[1]) * int(nx[2])
-        U = np.zeros((nx[2], nx[1], nx[0], 5 + nscal)); ef = None
-        for c, lab in enumerate(_LABELS):
-            expect(lab.encode())
-            U[..., c] = np.frombuffer(b, dtype="<f8", count=n, offset=pos).reshape(nx[2], nx[1], nx[0]); pos += 8 * n
-        if ion:
-            expect(b"EDGEFLUX")
-            ne = (nx[0] + 1) * (nx[1] + 1) * (nx[2] + 1)
-            ef = np.frombuffer(b, dtype="<f8", count=ne, offset=pos).reshape(nx[2] + 1, nx[1] + 1, nx[0] + 1).copy(); pos += 8 * ne
-        for sc in range(nscal):
-            expect(f"SCALAR {sc}".encode())
-            U[..., 5 + sc] = np.frombuffer(b, dtype="<f8", count=n, offset=pos).reshape(nx[2], nx[1], nx[0]); pos += 8 * n
-        levels.append((U, ef))
-    expect(b"USER_DATA")
-    return dict(header=header, par=ParTable.from_text(header), nstep=nstep, time=time, dt=dt, levels=levels)
+def write_rst(path: str, par_text: str, nstep: int, time: float, dt: float, U: np.ndarray,
+              edgeflux: Optional[np.ndarray] = None) -> None:
+    """U: active zones [Nx3][Nx2][Nx1][nvar] (nvar = 5 or 6)."""
+    write_rst_levels(path, par_text, nstep, time, dt, [(U, edgeflux)])
 
 
-# ---- continuing a run (main.c -r): a reader that does not slurp the file, and the writer's pieces ------------------------------
+# ---- the reader: the head, the index of the sections, one level's state; it does not slurp the file ---------------------------
 
 class RestartError(ValueError):
     """ath_error of restart_grids (restart.c:52-456)"""
@@ -178,38 +124,10 @@ def section_table(nx: Sequence[int], nscal: int, ion: bool):
 
 def expect_label(f, label: str, first: bool = False) -> None:
     """The label the reference's reader insists on at this place of the file (restart.c:79-84 ...)"""
-    tag = (b"" if first else b"\n") + label.encode() + b"\n"
+    tag = _tag(label, first)
     got = f.read(len(tag))
     if got != tag:
         raise RestartError(f"[restart_grids]: Expected {label}, found {got!r}")
-
-
-def write_header(f, par_text: str, nstep: int, time: float, dt: float) -> None:
-    """Everything in front of the first Grid's sections: the parameter dump, N_STEP, TIME, TIME_STEP"""
-    if not par_text.rstrip().endswith("<par_end>"):
-        par_text = par_text.rstrip("\n") + "\n<par_end>\n"
-    f.write(par_text.encode())
-    f.write(b"N_STEP\n" + struct.pack("<i", int(nstep)))
-    f.write(b"\nTIME\n" + struct.pack("<d", float(time)))
-    f.write(b"\nTIME_STEP\n" + struct.pack("<d", float(dt)))
-
-
-def write_grid_sections(f, U: np.ndarray, edgeflux: Optional[np.ndarray] = None) -> None:
-    """One Grid's labelled sections from a host block of ACTIVE zones [Nx3][Nx2][Nx1][nvar] (engines without a device); the
-    bytes lib.Grid.write_rst_payload writes for the same state."""
-    for c, lab in enumerate(_LABELS):
-        f.write(b"\n" + lab.encode() + b"\n")
-        f.write(np.ascontiguousarray(U[..., c], dtype="<f8").tobytes())
-    if edgeflux is not None:
-        f.write(b"\nEDGEFLUX\n")
-        f.write(np.ascontiguousarray(edgeflux, dtype="<f8").tobytes())
-    for n in range(U.shape[-1] - 5):
-        f.write(f"\nSCALAR {n}\n".encode())
-        f.write(np.ascontiguousarray(U[..., 5 + n], dtype="<f8").tobytes())
-
-
-def write_trailer(f) -> None:
-    f.write(b"\nUSER_DATA\n")
 
 
 def read_head(path: str) -> Dict:
@@ -292,6 +210,20 @@ def read_state(head: Dict, level: int, nx: Sequence[int], nscal: int):
             c = _LABELS.index(label) if label in _LABELS else 5 + int(label.split()[1])
             U[..., c] = a.reshape(nx[2], nx[1], nx[0])
     return U, ef
+
+
+def read_rst_levels(path: str, nxs: Sequence[Sequence[int]], nscal: int, ion: bool) -> Dict:
+    """The whole file on the host.  nxs: active zones (Nx1, Nx2, Nx3) of every level, root first."""
+    head = scan_rst(path, nxs, nscal, ion)
+    levels = [read_state(head, l, nx, nscal) for l, nx in enumerate(nxs)]
+    return dict(header=head["header"], par=head["par"], nstep=head["nstep"], time=head["time"], dt=head["dt"], levels=levels)
+
+
+def read_rst(path: str, nx: Sequence[int], nscal: int, ion: bool) -> Dict:
+    """read_rst_levels of a one-level file, the level unpacked into `U` and `edgeflux`"""
+    r = read_rst_levels(path, [nx], nscal, ion)
+    r["U"], r["edgeflux"] = r.pop("levels")[0]
+    return r
 
 
 def rank_path(path0: str, rank: int) -> str:

@@ -172,6 +172,28 @@ def test_restart_levels_round_trip(aa, tmp_path):
     assert np.array_equal(r1["levels"][0][0], levels[0][0])
 
 
+def test_restart_refuses_bytes_after_user_data(aa, tmp_path):
+    """One reader: a file with a byte after USER_DATA (none of the built problems writes any) is refused by read_rst,
+    read_rst_levels and scan_rst alike, with the size named; the same file without it is read by all three."""
+    R = aa.restart
+    rng = np.random.default_rng(7)
+    nx = (5, 4, 3)
+    U = rng.normal(size=(nx[2], nx[1], nx[0], 6)); ef = rng.normal(size=(nx[2] + 1, nx[1] + 1, nx[0] + 1))
+    par = aa.athinput.ParTable.from_text("<job>\nproblem_id = x\n")
+    p = str(tmp_path / "x.rst")
+    R.write_rst(p, R.par_dump(par), 2, 0.5, 0.25, U, ef)
+    readers = [lambda: R.read_rst(p, nx, 1, True), lambda: R.read_rst_levels(p, [nx], 1, True), lambda: R.scan_rst(p, [nx], 1, True)]
+    r = readers[0]()
+    assert np.array_equal(r["U"], U) and np.array_equal(r["edgeflux"], ef) and r["U"].flags.writeable and r["edgeflux"].flags.writeable
+    assert np.array_equal(readers[1]()["levels"][0][0], U) and readers[2]()["size"] == os.path.getsize(p)
+    with open(p, "ab") as f:
+        f.write(b"\0")
+    size = os.path.getsize(p)
+    for read in readers:
+        with pytest.raises(R.RestartError, match=r"\[restart_grids\]: Expected %d bytes, found %d" % (size - 1, size)):
+            read()
+
+
 def test_bench_helpers():
     """bench.py's host-side bookkeeping: every kernel stage the library can report has a byte figure and a phase, the
     dominant kernel is the argmax of total time, the MPI baseline splits ranks over x2 and x3 only."""
