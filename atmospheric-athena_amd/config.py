@@ -58,6 +58,9 @@ class RunConfig:
     # configure --with-order: 2 = piecewise linear (lr_states_plm.c, the default), 3 = piecewise parabolic
     # (lr_states_ppm.c); characteristic variables in both cases
     order: int = 2
+    # configure --enable-fofc (FIRST_ORDER_FLUX_CORRECTION): first-order flux correction of the van Leer integrator
+    # (integrate_3d_vl.c Steps 10 and 14); off by default
+    fofc: bool = False
 
     @property
     def dx(self) -> Tuple[float, float, float]:
@@ -117,11 +120,28 @@ def from_par(par: ParTable, problem: Optional[str] = None) -> RunConfig:
     return cfg
 
 
-def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu") -> RunConfig:
+def check_fofc(run: RunConfig, nranks: int = 1, mesh: bool = False) -> None:
+    """First-order flux correction is accepted where a reference build pins what it does: the van Leer integrator at second
+    order, one Grid on one device (FixCell's bounds are per Grid; there is no MPI or SMR reference with it)."""
+    if not run.fofc:
+        return
+    if run.integrator != "vl":
+        raise ParError(f"[config]: fofc needs the van Leer integrator (integrate_3d_vl.c only), not \"{run.integrator}\"")
+    if run.order != 2:
+        raise ParError("[config]: fofc with third-order reconstruction: no reference build pins it")
+    if mesh:
+        raise ParError("[config]: fofc on a refined or decomposed Mesh: FixCell's bounds are per Grid and no reference build pins it")
+    if nranks > 1:
+        raise ParError(f"[config]: fofc on {nranks} ranks: FixCell's bounds are per Grid and no MPI reference build pins it")
+
+
+def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu", fofc: bool = False) -> RunConfig:
     run = from_par(ParTable.from_file(path).cmdline(overrides), problem)
     if integrator not in ("ctu", "vl", "ctu-noh"):      # ctu-noh: CTU without --enable-h-correction (the reference's configure default)
         raise ParError(f"[integrate_init]: unknown integrator {integrator}")
     run.integrator = integrator
+    run.fofc = bool(fofc)
+    check_fofc(run)
     return run
 
 

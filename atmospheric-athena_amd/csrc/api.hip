@@ -6,6 +6,7 @@
 #include <math.h>
 #include <float.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -228,6 +229,7 @@ void aa_destroy(aa_grid *g)
   if (g->pin_val) hipFree(g->pin_val);
   if (g->pin_mask) hipFree(g->pin_mask);
   if (g->cfl_part) hipFree(g->cfl_part);
+  if (g->fofc_list) hipFree(g->fofc_list);
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);
@@ -390,6 +392,32 @@ int aa_set_cooling(aa_grid *g, int kind)
     g->bytes += (long long)g->d.nc*sizeof(Real);
   }
   g->cool = kind;
+  return 0;
+}
+
+// First-order flux correction of the van Leer integrator (the reference's --enable-fofc: integrate_3d_vl.c Step 10, a second-order
+// flux that came out NaN becomes the predictor flux of its face; Step 14 + FixCell, a zone the full update left with d < 0 or P < 0
+// takes the predictor fluxes instead, and so do its neighbours for the faces they share).  Off by default; with it off the step
+// launches what it always did.  Accepted where a reference build pins the behaviour, refused elsewhere.
+int aa_set_fofc(aa_grid *g, int on)
+{
+  if (!on) { if (g->slab.empty() && !g->link) { g->fofc = false; g->fofc_counts[0] = g->fofc_counts[1] = g->fofc_counts[2] = 0; } return 0; }
+  if (!g->slab.empty() || g->link) return fail(-1, "[aa_set_fofc]: not available on a Grid cut into slabs (FixCell's bounds are per Grid; no reference build pins a cut one)");
+  if (g->p.integrator != 1) return fail(-1, "[aa_set_fofc]: the CTU integrator has no first-order flux correction in the reference (integrate_3d_vl.c only)");
+  if (g->p.order == 3) return fail(-1, "[aa_set_fofc]: no reference build pins first-order flux correction with third-order reconstruction");
+  if (g->level > 0 || g->keep_flux) return fail(-1, "[aa_set_fofc]: not available on a level of a refined Mesh (FixCell would also have to replace the fluxes RestrictCorrect reads)");
+  if (!g->fofc_list) {
+    HIPCHK(hipMalloc(&g->fofc_list, (size_t)3*AA_FOFC_MAX*sizeof(long long)));
+    HIPCHK(hipMemsetAsync(g->fofc_list, 0, (size_t)3*AA_FOFC_MAX*sizeof(long long), g->st));
+    g->bytes += (long long)(3*AA_FOFC_MAX*sizeof(long long));
+  }
+  g->fofc = true;
+  return 0;
+}
+int aa_get_fofc(const aa_grid *g) { return g->fofc ? 1 : 0; }
+int aa_get_fofc_counts(const aa_grid *g, long long out[3])
+{
+  for (int n = 0; n < 3; n++) out[n] = g->fofc_counts[n];
   return 0;
 }
 
@@ -668,12 +696,66 @@ int aa_integrate_3d_ctu(aa_grid *g)
 }
 
 #undef HL
+// U^n of the first-order flux correction: the second face-state family, idle in the van Leer integrator (grid.h)
+static Real *fofc_un(const aa_grid *g) { return g->d.LR + 6*g->d.nc; }
+static int fofc_zero(aa_grid *g, int first_field_off, int nfields)
+{
+  HIPCHK(hipMemsetAsync((char*)g->sc + first_field_off, 0, (size_t)nfields*sizeof(int), g->st));
+  return 0;
+}
+static void vl_update(aa_grid *g)
+{
+  const HostGrid &d = g->d; const int ns = g->p.nscal;
+  if (g->fofc) launch_update_fofc(d, ns, d.LR, g->dt, g->grav, g->st, g->cfl_ready ? g->sc : nullptr, g->cfl_part, g->pin_mask, g->sc, g->fofc_list);
+  else launch_update(d, ns, d.LR, g->dt, g->grav, g->st, g->cfl_ready ? g->sc : nullptr, g->cfl_part, g->pin_mask);   // d^{n+1/2} = Uhalf.d
+}
+// What is left of Steps 10 and 14 once the update has run: the counts come back with the step's other scalars (one read-back;
+// zero candidates, the common case, launches nothing more).
+static int fofc_finish(aa_grid *g)
+{
+  const HostGrid &d = g->d; const int ns = g->p.nscal;
+  const size_t ubytes = (size_t)(5 + ns)*d.nc*sizeof(Real);
+  int rc = aa_fetch_scalars(g); if (rc) return rc;
+  long long nan = 0;
+  if (g->sc_host->fofc_nanseen) {
+    // Step 10, made up for: the reference tests every second-order flux as it is computed; here the update notices a NaN among
+    // the fluxes it reads (no pass over the flux arrays in the steps that have none: all of them, on every deck tried), and then
+    // U^n goes back, the fluxes are repaired over the reference's ranges and the update runs again.
+    HIPCHK(hipMemcpyAsync(d.U, fofc_un(g), ubytes, hipMemcpyDeviceToDevice, g->st));
+    for (int dir = 0; dir < 3; dir++) launch_fofc_nanfix(d, ns, dir, fofc_un(g), g->sc, g->st);
+    if ((rc = fofc_zero(g, offsetof(DevScalars, fofc_n), 2))) return rc;
+    if (g->cfl_ready) HIPCHK(hipMemsetAsync(g->sc->max_v, 0, 3*sizeof(unsigned long long), g->st));
+    vl_update(g);
+    if ((rc = aa_fetch_scalars(g))) return rc;
+    nan = g->sc_host->fofc_nan;
+  }
+  const int ncand = g->sc_host->fofc_n;
+  long long negd = 0, negP = 0;
+  if (ncand > AA_FOFC_MAX)
+    return fail(-4, "[aa_integrate_3d_vl]: first-order flux correction: %d zones with d < 0 in one step, more than the %d the fix handles", ncand, AA_FOFC_MAX);
+  if (ncand > 0) {
+    launch_fofc_fix(d, ns, fofc_un(g), g->dt, g->sc, g->fofc_list, g->st);
+    if ((rc = aa_fetch_scalars(g))) return rc;
+    if (g->sc_host->fofc_ovf)
+      return fail(-4, "[aa_integrate_3d_vl]: first-order flux correction: the zones changed ahead of the scan outgrew the list of %d", AA_FOFC_MAX);
+    negd = g->sc_host->fofc_negd; negP = g->sc_host->fofc_negP;
+    if (negd + negP > 0) g->cfl_ready = false;       // zones changed behind the update: its CFL maxima are stale, new_dt takes them with k_cfl
+  }
+  g->fofc_counts[0] = negd; g->fofc_counts[1] = negP; g->fofc_counts[2] = nan;
+  return 0;
+}
+
 int aa_integrate_3d_vl(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_integrate(g, 1);
   g->cfl_ready = false; g->active_dirty = true;
   // integrate_3d_vl.c:96-: donor-cell fluxes -> U^{n+1/2} -> PLM or PPM (no tracing) + Roe -> update
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
+  if (g->fofc) {      // Step 5d, restated: keep U^n (ghost zones included) instead of the predictor fluxes
+    // (outside the profiler's stages, like the fix: their cost is the difference profiles/fofc_rate.py measures on whole steps)
+    HIPCHK(hipMemcpyAsync(fofc_un(g), d.U, (size_t)(5 + ns)*d.nc*sizeof(Real), hipMemcpyDeviceToDevice, g->st));
+    int rc = fofc_zero(g, offsetof(DevScalars, fofc_n), 6); if (rc) return rc;
+  }
   // donor-cell fluxes + U^{n+1/2} in one marching kernel from 2^18 zones (512^3: 16.8 -> 9.7 ms; same at 80^3;
   // 10 % slower at 32^3); AA_VL_PREDICT forces either, the results are the same bit for bit
   if (g->vl_predict) { Scope s(g, "vl_predict"); launch_vl_predict(d, ns, dt, g->grav, g->st); }
@@ -696,9 +778,10 @@ int aa_integrate_3d_vl(aa_grid *g)
         if (hipMalloc(&g->cfl_part, (size_t)3*nb*sizeof(Real)) == hipSuccess) g->cfl_part_n = 3*nb; else g->cfl_ready = false; g->active_dirty = true;
       }
     }
-    launch_update(d, ns, d.LR, dt, g->grav, g->st, g->cfl_ready ? g->sc : nullptr, g->cfl_part, g->pin_mask);   // d^{n+1/2} = Uhalf.d
+    vl_update(g);
   }
   HIPCHK(hipGetLastError());
+  if (g->fofc) return fofc_finish(g);
   return 0;
 }
 

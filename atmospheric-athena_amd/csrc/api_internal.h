@@ -56,6 +56,9 @@ struct aa_grid {
   int ion_cur = 0; bool ion_pending = false;   // buffer of the last sweep that counts; a sweep launched but not yet relied upon
   aa::IonPart *ion_part = nullptr; aa::Real *ion_words = nullptr;   // per-block records of a pass; this Grid's folded words
   int host_syncs = 0;                  // stream synchronisations that return scalars to the host (bench: per step)
+  bool fofc = false;                   // aa_set_fofc: first-order flux correction of the van Leer integrator (integrate_3d_vl.c Steps 10, 14)
+  long long *fofc_list = nullptr;      //   ... candidates | sorted | pending, 3 x AA_FOFC_MAX zone indices (device)
+  long long fofc_counts[3] = {0, 0, 0};   //   ... of the last step: zones with d < 0, with P < 0, second-order fluxes replaced
   bool vl_predict = false;             // van Leer predictor as one kernel (k_vl_predict): 2^18 zones or more, or AA_VL_PREDICT
   bool keep_flux = false;              // a level of an aa_mesh: RestrictCorrect reads the second-pass fluxes ...
   aa::KeepPlanes keep = {0, {{0}}};        // ... on these face planes (own boundaries + the child's outline)

@@ -8,6 +8,7 @@
 //     U    : 6*nc   d, M1, M2, M3, E, s0                      (GridS.U, athena.h:290)
 //     LR   : 36*nc  [dir][L|R][var] face states, GLOBAL momentum frame
 //                                                            (Ul/Ur_x?Face, integrate_3d_ctu.c:61-63)
+//                   (van Leer integrator: [0][L] holds U^{n+1/2}; with aa_set_fofc [0][R] holds U^n, the rest is idle)
 //     F    : 18*nc  [dir][var] fluxes, global frame           (x?Flux, :64)
 //     eta  : 3*nc   H-correction wave-speed spread per face   (eta1..3, :74)
 //     dhalf: nc                                               (:71)
@@ -82,6 +83,10 @@ struct DevScalars {
   // 1 = k_ion_pick2 found that step to be the one (the closing update pass has nothing left to do), 2 = it was not (the
   // next pass starts again from e_init / s_init), 0 otherwise
   int spec_state, pad2;
+  // first-order flux correction of the van Leer integrator (aa_set_fofc; integrate_3d_vl.c Steps 10 and 14), per step:
+  // zones the update left with d < 0 (appended to the candidate list), whether a flux the update read was NaN, what the
+  // fix kernel counted while it replayed the reference's scan, the fluxes k_fofc_nanfix replaced, list overflow
+  int fofc_n, fofc_nanseen, fofc_negd, fofc_negP, fofc_nan, fofc_ovf;
 };
 
 // what one block of k_ion_pass contributes to the reductions of a sub-cycle (all doubles: the record is

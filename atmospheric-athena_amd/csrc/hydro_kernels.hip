@@ -1306,6 +1306,93 @@ k_update(DevGrid g, const Real *dhalf, Real dt, Order ord, Real *cfl_part, const
   }
 }
 
+#if !AA_COOLING
+// k_update of the van Leer integrator with the detection half of the first-order flux correction (aa_set_fofc) on board -- the
+// update itself is k_update's, line for line but for the cooling term the van Leer integrator does not have (a kernel of its own, so that k_update stays the code it was): a zone whose new
+// density is negative goes onto the candidate list of Step 14 (one ballot and one vector atomic per wavefront that has any; the
+// order of the list is whatever the atomics make it: k_fofc_fix sorts), and a NaN among the second-order fluxes the zone read
+// raises sc->fofc_nanseen (Step 10 is then made up for: api.hip fofc_finish).
+template <int NS, bool GRAV, bool CFL>
+__global__ void __launch_bounds__(256)
+k_update_fofc(DevGrid g, const Real *dhalf, Real dt, Order ord, Real *cfl_part, const unsigned char *pinmask, DevScalars *sc, long long *list)
+{
+  // CFL (the van Leer integrator's update; the CTU path has it in k_flux2_update): the zone's contribution to new_dt's maxima from the
+  // updated state while it is in registers; one zone per thread makes half a million blocks at 512^3, so a block leaves its three
+  // maxima in cfl_part[d][block] (k_cfl_fold turns them into the three words) instead of 1.5 M same-address atomics
+  __shared__ Real s_red[CFL ? 3 : 1][CFL ? 256 : 1];
+  Real cmx[3] = {0.0, 0.0, 0.0};
+  const int ni = g.ie - g.is + 1, nj = g.je - g.js + 1, nk = g.ke - g.ks + 1;
+  int i, j, k;
+  const bool ok = decode_zone(ord, ni, nj, nk, i, j, k);
+  bool bad = false, nanf = false;
+  long mbad = 0;
+  if (ok) {
+  i += g.is; j += g.js; k += g.ks;
+  const long m = (long)k*g.sK + (long)j*g.sJ + i;
+  constexpr int NV = 5 + NS;
+  Real u[6];
+#pragma unroll
+  for (int v = 0; v < NV; v++) u[v] = Uf(g, v)[m];
+  Real dtodx[3];
+#pragma unroll
+  for (int d = 0; d < 3; d++) dtodx[d] = dt/g.dx[d];
+  if (GRAV) {   // :2741-2782
+    const Real phic = Pf(g, 0)[m], dh = dhalf[m];
+#pragma unroll
+    for (int e = 0; e < 3; e++) {
+      const long se = stride_rt(g, e);
+      const Real phir = Pf(g, 1 + e)[m + se], phil = Pf(g, 1 + e)[m];
+      const Real *fd = Ff(g, e, 0);
+      u[1 + e] -= dtodx[e]*(phir - phil)*dh;
+      u[4] -= dtodx[e]*(fd[m]*(phic - phil) + fd[m + se]*(phir - phic));
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) {   // :2981-3050, x1 then x2 then x3
+    const long sd = stride_rt(g, d);
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const Real *f = Ff(g, d, v);
+      if (v < 5) { const Real fh = f[m + sd], fl = f[m]; nanf = nanf || (fh != fh) || (fl != fl); }      // (the scalar flux is not part of the reference's test)
+      u[v] -= dtodx[d]*(f[m + sd] - f[m]);
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < NV; v++) Uf(g, v)[m] = u[v];
+  if (CFL && !(pinmask && pinmask[m])) cfl_zone(u[0], u[1], u[2], u[3], u[4], g.Gamma, g.Gamma_1, cmx);
+  bad = u[0] < 0.0; mbad = m;
+  }
+  {
+    const int lane = __lane_id();
+    const unsigned long long b = __ballot(bad);
+    if (b) {
+      const int first = __ffsll((long long)b) - 1;
+      int base = 0;
+      if (lane == first) base = atomicAdd(&sc->fofc_n, __popcll(b));
+      base = __shfl(base, first);
+      const int pos = base + __popcll(b & ((1ULL << lane) - 1ULL));
+      if (bad && pos < AA_FOFC_MAX) list[pos] = mbad;          // (beyond the list only the count goes on: the caller fails the step)
+    }
+    const unsigned long long bn = __ballot(nanf);
+    if (bn && lane == __ffsll((long long)bn) - 1) atomicAdd(&sc->fofc_nanseen, 1);
+  }
+  if (CFL) {
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int d = 0; d < 3; d++) s_red[CFL ? d : 0][CFL ? t : 0] = cmx[d];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) s_red[CFL ? d : 0][CFL ? t : 0] = rmax(s_red[CFL ? d : 0][CFL ? t : 0], s_red[CFL ? d : 0][CFL ? t + w : 0]);
+      }
+      __syncthreads();
+    }
+    if (t < 3) cfl_part[(size_t)t*gridDim.x + blockIdx.x] = s_red[CFL ? t : 0][0];
+  }
+}
+#endif
+
 // the blocks' maxima of k_update<CFL> -> the three words of new_dt (MAX of non-negative doubles on their bit patterns: order-free)
 __global__ void __launch_bounds__(256)
 k_cfl_fold(const Real *part, int nb, DevScalars *sc)
@@ -1864,6 +1951,151 @@ k_vl_uhalf(DevGrid g, Real dt)
   for (int v = 0; v < NV; v++) LRf(g, 0, 0, v)[m] = u[v];
 }
 
+#if !AA_COOLING
+// ---- first-order flux correction (integrate_3d_vl.c, FIRST_ORDER_FLUX_CORRECTION) ---------------------------------------------
+// The reference keeps a copy of the predictor fluxes (Step 5d, 3 x nvar doubles per zone) for the few faces Steps 10 and 14 ever
+// look at.  Here they are recomputed for those faces from U^n (`un`, copied before the predictor: a third of that traffic, and
+// k_vl_predict never has its fluxes in HBM): the donor-cell flux of face m along D exactly as k_vl_flux1 forms it, sweep frame.
+template <int NS, int D>
+AA_DEV void fofc_pred_flux(const DevGrid &g, const Real *un, long m, Real f[6])
+{
+  const long s = stride<D>(g);
+  Real u[6], wl[6], wr[6], ul[6], ur[6];
+  load_sweep<D, NS>(un, g.nc, m - s, u); cons_to_prim<NS>(u, wl, g.Gamma_1);
+  load_sweep<D, NS>(un, g.nc, m, u);     cons_to_prim<NS>(u, wr, g.Gamma_1);
+  prim_to_cons<NS>(wl, ul, g.Gamma_1, g.rGamma_1);
+  prim_to_cons<NS>(wr, ur, g.Gamma_1, g.rGamma_1);
+  flux_roe<NS>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
+}
+// second-order minus predictor flux of face m along DP, sweep-frame components d, Mx, My, Mz, E; the second-order flux is taken
+// from the array of direction D2 (D2 != DP only where the reference does so: fofc_fix_cell)
+template <int NS, int D2, int DP>
+AA_DEV void fofc_flux_diff(const DevGrid &g, const Real *un, long m, Real fd[5])
+{
+  Real f2[6], fp[6];
+  load_sweep<D2, NS>(Ff(g, D2, 0), g.nc, m, f2);
+  fofc_pred_flux<NS, DP>(g, un, m, fp);
+#pragma unroll
+  for (int n = 0; n < 5; n++) fd[n] = f2[n] - fp[n];
+}
+// U[m] (+/-)= dtodx * fd, the momenta taking the sweep-frame components (c1, c2, c3) of fd
+AA_DEV void fofc_add(const DevGrid &g, long m, Real sign, Real dtodx, const Real fd[5], int c1, int c2, int c3)
+{
+  const int c[5] = {0, c1, c2, c3, 4};
+#pragma unroll
+  for (int v = 0; v < 5; v++) {
+    Real *u = Uf(g, v) + m;
+    if (sign > 0.0) *u += dtodx*(fd[c[v]]); else *u -= dtodx*(fd[c[v]]);
+  }
+}
+// FixCell (integrate_3d_vl.c:1995-2232), hydro: the zone trades the second-order fluxes of its six faces for the predictor
+// fluxes; so does each neighbour for the face it shares, if it lies strictly inside the Grid's index range in that direction
+// as the reference tests it (ix.i > is, ix.i < ie, ...: the periodic image of a zone across the boundary is NOT corrected, and
+// the run is no longer conservative there -- the reference's behaviour, kept).  Passive scalars are not corrected (no s[n]
+// lines in FixCell).  Two things in the reference's x3 lines look like slips and are reproduced because parity is the bar:
+//   * the flux difference of the UPPER x3 face is x2Flux[k+1] - x3FluxP[k+1] (:2014-2047): the x2 array, every field;
+//   * the x3 differences go to the momenta in the x2 rotation (M1 <- Mz, M2 <- Mx, M3 <- My; :2085-2090, :2139-2157), where
+//     Step 13c uses M1 <- My, M2 <- Mz, M3 <- Mx.
+template <int NS>
+AA_DEV void fofc_fix_cell(const DevGrid &g, const Real *un, Real dt, long m, int i, int j, int k)
+{
+  const Real dtodx1 = dt/g.dx[0], dtodx2 = dt/g.dx[1], dtodx3 = dt/g.dx[2];
+  Real x1_i[5], x1_ip1[5], x2_j[5], x2_jp1[5], x3_k[5], x3_kp1[5], c[5];
+  fofc_flux_diff<NS, 0, 0>(g, un, m, x1_i);
+  fofc_flux_diff<NS, 1, 1>(g, un, m, x2_j);
+  fofc_flux_diff<NS, 2, 2>(g, un, m, x3_k);
+  fofc_flux_diff<NS, 0, 0>(g, un, m + 1, x1_ip1);
+  fofc_flux_diff<NS, 1, 1>(g, un, m + g.sJ, x2_jp1);
+  fofc_flux_diff<NS, 1, 2>(g, un, m + g.sK, x3_kp1);       // x2Flux[k+1] - x3FluxP[k+1]: as the reference has it
+#pragma unroll
+  for (int n = 0; n < 5; n++) c[n] = x1_ip1[n] - x1_i[n];
+  fofc_add(g, m, 1.0, dtodx1, c, 1, 2, 3);
+#pragma unroll
+  for (int n = 0; n < 5; n++) c[n] = x2_jp1[n] - x2_j[n];
+  fofc_add(g, m, 1.0, dtodx2, c, 3, 1, 2);
+#pragma unroll
+  for (int n = 0; n < 5; n++) c[n] = x3_kp1[n] - x3_k[n];
+  fofc_add(g, m, 1.0, dtodx3, c, 3, 1, 2);
+  if (i > g.is) fofc_add(g, m - 1, 1.0, dtodx1, x1_i, 1, 2, 3);
+  if (i < g.ie) fofc_add(g, m + 1, -1.0, dtodx1, x1_ip1, 1, 2, 3);
+  if (j > g.js) fofc_add(g, m - g.sJ, 1.0, dtodx2, x2_j, 3, 1, 2);
+  if (j < g.je) fofc_add(g, m + g.sJ, -1.0, dtodx2, x2_jp1, 3, 1, 2);
+  if (k > g.ks) fofc_add(g, m - g.sK, 1.0, dtodx3, x3_k, 3, 1, 2);
+  if (k < g.ke) fofc_add(g, m + g.sK, -1.0, dtodx3, x3_kp1, 3, 1, 2);
+}
+// Step 14 (:1255-1279) is a sequential scan in k, j, i order: a fix changes the +i, +j, +k neighbours BEFORE the scan examines
+// them (they may turn bad, or good again) and the -i, -j, -k neighbours after it did (never looked at again), so fixing all
+// flagged zones at once is not the same thing.  The scan is replayed over the only zones it can flag: the candidates of the
+// update (d < 0 in a zone no fix touched is what the update saw) and the upper neighbours of the zones fixed so far, in
+// ascending zone index -- which is scan order.  One wavefront: the lanes sort the candidates (rank sort: they are distinct),
+// lane 0 walks.  buf: AA_FOFC_MAX candidates | sorted | pending upper neighbours (sorted, distinct).
+template <int NS>
+__global__ void __launch_bounds__(64)
+k_fofc_fix(DevGrid g, const Real *un, Real dt, DevScalars *sc, long long *buf)
+{
+  const long long *cand = buf;
+  long long *sorted = buf + AA_FOFC_MAX, *pend = buf + 2*AA_FOFC_MAX;
+  const int n = sc->fofc_n;               // (<= AA_FOFC_MAX: the host has looked)
+  for (int e = threadIdx.x; e < n; e += 64) {
+    const long long v = cand[e];
+    int r = 0;
+    for (int q = 0; q < n; q++) r += cand[q] < v;
+    sorted[r] = v;
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int negd = 0, negP = 0, ci = 0, pi = 0, pn = 0, ovf = 0;
+  while (ci < n || pi < pn) {
+    const long long a = ci < n ? sorted[ci] : 0x7fffffffffffffffLL, b = pi < pn ? pend[pi] : 0x7fffffffffffffffLL;
+    const long m = (long)(a < b ? a : b);
+    if (a == m) ci++;
+    if (b == m) pi++;
+    const int k = (int)(m / g.sK), j = (int)((m % g.sK) / g.sJ), i = (int)(m % g.sJ);
+    Real u[6], w[6];
+#pragma unroll
+    for (int v = 0; v < 5; v++) u[v] = Uf(g, v)[m];
+    u[5] = 0.0;
+    cons_to_prim<0>(u, w, g.Gamma_1);      // Cons_to_Prim of the CURRENT state (convert_var.c:104: Cons1D_to_Prim1D, which floors P)
+    bool flag = false;
+    if (w[0] < 0.0) { flag = true; negd++; }
+    if (w[4] < 0.0) { flag = true; negP++; }
+    if (!flag) continue;
+    fofc_fix_cell<NS>(g, un, dt, m, i, j, k);
+    const long up[3] = {i < g.ie ? m + 1 : -1L, j < g.je ? m + g.sJ : -1L, k < g.ke ? m + g.sK : -1L};   // ascending
+    for (int a3 = 0; a3 < 3; a3++) {
+      if (up[a3] < 0) continue;
+      int q = pn;
+      while (q > pi && pend[q - 1] > up[a3]) q--;
+      if (q > pi && pend[q - 1] == up[a3]) continue;
+      if (pn >= AA_FOFC_MAX) { ovf = 1; continue; }
+      for (int r = pn; r > q; r--) pend[r] = pend[r - 1];
+      pend[q] = up[a3]; pn++;
+    }
+  }
+  sc->fofc_negd = negd; sc->fofc_negP = negP; sc->fofc_ovf = ovf;
+}
+// Step 10 (:775-791, :825-841, :875-891): a second-order flux with a NaN in d, Mx, My, Mz or E becomes the predictor flux of its
+// face, all components (the scalar flux is part of the struct copy).  Faces as the reference loops: [s, e+1] along D, [s-1, e+1]
+// across (the sweeps fill at least that).
+template <int NS, int D>
+__global__ void __launch_bounds__(256)
+k_fofc_nanfix(DevGrid g, const Real *un, DevScalars *sc)
+{
+  const int ni = g.ie - g.is + 3 - (D == 0), nj = g.je - g.js + 3 - (D == 1), nk = g.ke - g.ks + 3 - (D == 2);
+  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
+  if (lin >= (long)ni*nj*nk) return;
+  const int i = g.is - (D != 0) + (int)(lin % ni), j = g.js - (D != 1) + (int)((lin / ni) % nj), k = g.ks - (D != 2) + (int)(lin / ((long)ni*nj));
+  const long m = (long)k*g.sK + (long)j*g.sJ + i;
+  Real f[6];
+  load_sweep<D, NS>(Ff(g, D, 0), g.nc, m, f);
+  if (f[0] == f[0] && f[1] == f[1] && f[2] == f[2] && f[3] == f[3] && f[4] == f[4]) return;
+  fofc_pred_flux<NS, D>(g, un, m, f);
+  store_sweep<D, NS>(Ff(g, D, 0), g.nc, m, f);
+  atomicAdd(&sc->fofc_nan, 1);
+}
+#endif
+
 // ---- physical boundary conditions: bvals_mhd.c reflect :959, outflow :1319, periodic :1637 ---
 // dir d, side 0/1; transverse extents: x1 -> active j,k; x2 -> all i, active k; x3 -> all i,j.
 // side < 0: both sides in one launch, blockIdx.y = side, (flag, flag1) = the two flags (0 = leave alone)
@@ -2408,6 +2640,44 @@ void launch_update(const HostGrid &g, int nscal, const Real *dhalf, Real dt, boo
   else       { if (grav) hipLaunchKernelGGL((k_update<0, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr);
                else      hipLaunchKernelGGL((k_update<0, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr); }
 }
+
+#if !AA_COOLING
+void launch_update_fofc(const HostGrid &g, int nscal, const Real *dhalf, Real dt, bool grav, hipStream_t st, DevScalars *sc_cfl,
+                        Real *cfl_part, const unsigned char *pinmask, DevScalars *sc, long long *list)
+{
+  const long n = (long)(g.ie - g.is + 1)*(g.je - g.js + 1)*(g.ke - g.ks + 1);
+  dim3 grid(nblk8(n, 256)), blk(256);
+  if (sc_cfl && cfl_part) {
+    if (nscal) { if (grav) hipLaunchKernelGGL((k_update_fofc<1, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list);
+                 else      hipLaunchKernelGGL((k_update_fofc<1, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list); }
+    else       { if (grav) hipLaunchKernelGGL((k_update_fofc<0, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list);
+                 else      hipLaunchKernelGGL((k_update_fofc<0, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list); }
+    unsigned nf = nblk(grid.x, 256*8); if (nf > 256) nf = 256;
+    hipLaunchKernelGGL(k_cfl_fold, dim3(nf), dim3(256), 0, st, cfl_part, (int)grid.x, sc_cfl);
+    return;
+  }
+  if (nscal) { if (grav) hipLaunchKernelGGL((k_update_fofc<1, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list);
+               else      hipLaunchKernelGGL((k_update_fofc<1, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list); }
+  else       { if (grav) hipLaunchKernelGGL((k_update_fofc<0, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list);
+               else      hipLaunchKernelGGL((k_update_fofc<0, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list); }
+}
+void launch_fofc_fix(const DevGrid &g, int nscal, const Real *un, Real dt, DevScalars *sc, long long *list, hipStream_t st)
+{
+  if (nscal) hipLaunchKernelGGL(k_fofc_fix<1>, dim3(1), dim3(64), 0, st, g, un, dt, sc, list);
+  else       hipLaunchKernelGGL(k_fofc_fix<0>, dim3(1), dim3(64), 0, st, g, un, dt, sc, list);
+}
+template <int NS>
+static void fofc_nanfix_impl(const DevGrid &g, int dir, const Real *un, DevScalars *sc, hipStream_t st)
+{
+  long n[3] = {g.ie - g.is + 3, g.je - g.js + 3, g.ke - g.ks + 3}; n[dir] -= 1;
+  dim3 grid(nblk(n[0]*n[1]*n[2], 256)), blk(256);
+  if (dir == 0) hipLaunchKernelGGL((k_fofc_nanfix<NS, 0>), grid, blk, 0, st, g, un, sc);
+  else if (dir == 1) hipLaunchKernelGGL((k_fofc_nanfix<NS, 1>), grid, blk, 0, st, g, un, sc);
+  else hipLaunchKernelGGL((k_fofc_nanfix<NS, 2>), grid, blk, 0, st, g, un, sc);
+}
+void launch_fofc_nanfix(const DevGrid &g, int nscal, int dir, const Real *un, DevScalars *sc, hipStream_t st)
+{ if (nscal) fofc_nanfix_impl<1>(g, dir, un, sc, st); else fofc_nanfix_impl<0>(g, dir, un, sc, st); }
+#endif
 
 void launch_bc(const DevGrid &g, int nscal, int dir, int side, int flag, hipStream_t st)
 {

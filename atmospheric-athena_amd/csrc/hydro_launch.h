@@ -25,6 +25,15 @@ void launch_vl_flux1(const DevGrid &g, int nscal, int dir, hipStream_t st);
 void launch_vl_uhalf(const DevGrid &g, int nscal, Real dt, bool grav, hipStream_t st);
 void launch_vl_predict(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st);   // vl_flux1 x3 + vl_uhalf fused
 void launch_vl_flux2(const HostGrid &g, int nscal, int dir, Real dt, hipStream_t st);
+// first-order flux correction (integrate_3d_vl.c Steps 10, 14 and FixCell; `un`: U^n, six fields nc apart, ghost zones included)
+#define AA_FOFC_MAX 4096      /* most zones with d < 0 one step can hand to the fix kernel (the call fails beyond) */
+// launch_update + per zone: d < 0 -> appended to list[0 .. AA_FOFC_MAX) (sc->fofc_n counts all of them), a NaN among the fluxes read -> sc->fofc_nanseen
+void launch_update_fofc(const HostGrid &g, int nscal, const Real *dhalf, Real dt, bool grav, hipStream_t st, DevScalars *sc_cfl,
+                        Real *cfl_part, const unsigned char *pinmask, DevScalars *sc, long long *list);
+// Step 14 over the candidates in scan order (one wave); list: 3*AA_FOFC_MAX words (candidates | sorted | zones a fix changed ahead of the scan)
+void launch_fofc_fix(const DevGrid &g, int nscal, const Real *un, Real dt, DevScalars *sc, long long *list, hipStream_t st);
+// Step 10 for the second-order fluxes of one direction, over the reference's face ranges; counts into sc->fofc_nan
+void launch_fofc_nanfix(const DevGrid &g, int nscal, int dir, const Real *un, DevScalars *sc, hipStream_t st);
 void launch_bc(const DevGrid &g, int nscal, int dir, int side, int flag, hipStream_t st);
 void launch_bc_dir(const DevGrid &g, int nscal, int dir, int flag_in, int flag_out, hipStream_t st);   // both sides, one launch
 void launch_bc_shell(const DevGrid &g, int nscal, const int flags[6], hipStream_t st);                 // all six sides, one launch (k_bc_shell)

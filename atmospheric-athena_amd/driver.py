@@ -145,6 +145,7 @@ class HipEngine:
         """dump_vtk / dump_binary of this slab: the payload comes from the device in file order (csrc/dump.hip)"""
         self.g.write_dump(path, fmt, prim, time=time, dt=dt)
 
+    def fofc_counts(self): return self.g.fofc_counts()
     def close(self): self.g.close()
 
 
@@ -283,6 +284,8 @@ class Driver(_Runner):
         self.rank, self.nranks = rank, nranks
         if p2 < 1 or nranks % p2:
             raise ValueError(f"{nranks} ranks cannot be dealt {p2} along x2")
+        config.check_fofc(run, nranks)      # (ParError: first-order flux correction is a single-Grid feature)
+        self.fofc_trace: List[Tuple[int, int, int]] = []    # run.fofc: (zones with d < 0, with P < 0, fluxes replaced) of every step
         self.grid = pencil(run, rank, p2, nranks // p2)
         self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict, initial=initial)
         self.restarted = False    # from_restart: start() is the restarted run's, outputs.run skips the forced first output
@@ -296,7 +299,7 @@ class Driver(_Runner):
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
                      engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
-                     p2: int = 1, regrid: bool = False) -> "Driver":
+                     p2: int = 1, regrid: bool = False, fofc: bool = False) -> "Driver":
         """``athena -r path [block/key=value ...]`` (main.c:168-173, :216-288; restart_grids, restart.c:52-456).  `path` is
         rank 0's file: every rank takes the parameter table from it, with the overrides on top (an unknown key is an error;
         time/nlim and time/tlim extend a run), and reads its own Grid from restart.rank_path(path, rank).  The problem
@@ -309,6 +312,7 @@ class Driver(_Runner):
         cuts (NGrid_x1 = 1, NGrid_x2 = p2, NGrid_x3 = nranks / p2, no AutoWithNProc), so that a later dump describes itself.
         Single-level meshes only."""
         head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        run.fofc = bool(fofc)      # (a build option of the reference like the integrator: not in the file; it carries no state between steps)
         sources = restart.scan_sources(path, run.rootNx, run.nscal, run.ion, head0) if regrid else None
         d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
         if not regrid:
@@ -590,6 +594,17 @@ class Driver(_Runner):
         e.set_mesh_state(self.time, self.dt, self.nstep)
         return niter
 
+    def _fofc_report(self):
+        """The two lines integrate_3d_vl.c prints when the first-order flux correction did something (:898-901, :1281-1282)."""
+        if not self.run.fofc or not hasattr(self.eng, "fofc_counts"):
+            return
+        negd, negP, nan = self.eng.fofc_counts()
+        self.fofc_trace.append((negd, negP, nan))
+        if nan != 0:
+            print("[Step10] %i second-order fluxes replaced" % nan)
+        if negd > 0 or negP > 0:
+            print("[Step14]: %i cells had d<0; %i cells had P<0" % (negd, negP))
+
     # ---- main.c ---------------------------------------------------------------------------------
     def start(self):                # main.c:412-451
         if self.restarted:          # main.c:398-451 after restart_grids: the ghost zones, and NO new_dt -- the file's dt is the next step's
@@ -613,6 +628,7 @@ class Driver(_Runner):
     def step(self) -> int:          # main.c:519-669
         if not self.distributed and hasattr(self.eng, "step_local"):
             niter = self.eng.step_local()
+            self._fofc_report()
             self.time, self.dt, self.nstep = self.eng.mesh_state()
             self.niter_trace.append(niter)
             return niter
@@ -626,6 +642,7 @@ class Driver(_Runner):
                 self.eng.integrate_begin()
             self.finish_x3()
         self.eng.integrate()
+        self._fofc_report()
         self.eng.userwork()
         self.nstep += 1
         self.time += self.dt
@@ -811,6 +828,7 @@ class MeshDriver(_Runner):
                  strict: Optional[bool] = None, cuts=None, initial: bool = True):
         """initial = False: the product engine skips the problem generator (from_restart loads the state)"""
         self.run, self.rank, self.nranks = run, rank, nranks
+        config.check_fofc(run, nranks, mesh=True)
         self.cfg = config.mesh_slabs(par, run, rank, nranks, cuts)
         self.domains = config.levels(par, run)            # the whole Domain of every level (history: its volume)
         self.level_nx1 = [g.Nx[0] for g in self.domains]  # zones along the rays of every level (x3 slabs keep them)

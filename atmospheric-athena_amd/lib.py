@@ -91,6 +91,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_get_mesh_state": (I, [P, dp, dp, ip]), "aa_set_mesh_state": (I, [P, D, D, I]),
         "aa_set_static_grav_pot": (I, [P, GRAVPOT]),
         "aa_set_cooling": (I, [P, I]),
+        "aa_set_fofc": (I, [P, I]), "aa_get_fofc": (I, [P]), "aa_get_fofc_counts": (I, [P, llp]),
         "aa_set_static_grav_tables": (I, [P, dp, dp, dp, dp]),
         "aa_set_pinned_cells": (I, [P, LL, llp, dp]), "aa_apply_pinned_cells": (I, [P]),
         "aa_add_radplane_3d": (I, [P, I, D]), "aa_has_radplane": (I, [P]),
@@ -275,6 +276,17 @@ class Grid:
     def set_cooling(self, kind: int = 1):
         """CoolingFunc = KoyInut (kind 1, AA_COOL_KOYINUT) or NULL (0); CTU integrator only."""
         self._chk(self.L.aa_set_cooling(self._h, int(kind)))
+
+    def set_fofc(self, on: bool = True):
+        """configure --enable-fofc: first-order flux correction of the van Leer integrator (integrate_3d_vl.c Steps 10, 14);
+        refused (AthenaError) for the CTU integrator, third order, levels of a Mesh and Grids cut into slabs."""
+        self._chk(self.L.aa_set_fofc(self._h, 1 if on else 0))
+
+    def fofc(self) -> bool: return bool(self.L.aa_get_fofc(self._h))
+
+    def fofc_counts(self):
+        """(zones that had d < 0, zones that had P < 0, second-order fluxes replaced) of the last integrate_3d_vl"""
+        c = (C.c_longlong * 3)(); self._chk(self.L.aa_get_fofc_counts(self._h, c)); return int(c[0]), int(c[1]), int(c[2])
 
     def integrate_3d_ctu(self): self._chk(self.L.aa_integrate_3d_ctu(self._h))
     def integrate_3d_vl(self): self._chk(self.L.aa_integrate_3d_vl(self._h))
@@ -522,6 +534,12 @@ def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None,
     (ioniz_sphere.c:191-239): the hooks only -- no host block is built, the state comes from a restart dump."""
     r = grid.run; pr = r.prob
     g = Grid(grid, device, strict, ion_path, nslab)
+    if getattr(r, "fofc", False):
+        try:
+            g.set_fofc(True)
+        except AthenaError:
+            g.close()
+            raise
     H = host()
     U = g.new_host_block() if initial else None
     if r.problem not in ("ifront", "ioniz_sphere", "blast", "shkset1d"):

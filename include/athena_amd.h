@@ -99,6 +99,16 @@ int aa_set_static_grav_tables(aa_grid *g, const double *phi_cc, const double *ph
 #define AA_COOL_NONE    0
 #define AA_COOL_KOYINUT 1
 int aa_set_cooling(aa_grid *g, int kind);
+/* configure --enable-fofc (FIRST_ORDER_FLUX_CORRECTION, integrate_3d_vl.c): a second-order flux that came out NaN is replaced by
+ * the predictor flux of its face (Step 10); after the full update a zone with d < 0 (or P < 0) is repaired with the predictor
+ * fluxes, and so are its neighbours across the faces they share (Step 14, FixCell) -- the reference's scan, in its order.  Off
+ * by default; with it off a step is what it was.  van Leer integrator, second order, one Grid on one device: refused for the CTU
+ * integrator, third-order reconstruction, the Grids of an aa_mesh and Grids cut into slabs (no reference build pins those).  More
+ * than 4096 zones with d < 0 in one step fail the step.  aa_get_fofc_counts: out[0..2] = zones that had d < 0, zones that had
+ * P < 0 (Cons_to_Prim floors P: stays 0), second-order fluxes replaced, of the last aa_integrate_3d_vl.                    */
+int aa_set_fofc(aa_grid *g, int on);
+int aa_get_fofc(const aa_grid *g);
+int aa_get_fofc_counts(const aa_grid *g, long long out[3]);
 /* Userwork_in_loop of prob/ioniz_sphere.c:255-306 re-imposes fixed values on a fixed set of
  * cells every step; the device-side equivalent is a list of pinned cells (linear index into
  * the [k][j][i] block incl. ghosts, nvar values each) applied after the integrator.          */
