@@ -63,6 +63,11 @@ class RunConfig:
     fofc: bool = False
 
     @property
+    def ndim(self) -> int:
+        """integrate.c:30: the directions of the root Domain with more than one zone (2: Nx3 = 1, the 2-D integrators)"""
+        return sum(1 for n in self.rootNx if n > 1)
+
+    @property
     def dx(self) -> Tuple[float, float, float]:
         return tuple((self.xmax[d] - self.xmin[d]) / float(self.rootNx[d]) for d in range(3))
 
@@ -92,17 +97,29 @@ def from_par(par: ParTable, problem: Optional[str] = None) -> RunConfig:
     ion, nscal = PROBLEMS[problem]
     blk = "domain1"
     Nx = tuple(par.geti(blk, f"Nx{d}") for d in (1, 2, 3))
-    if min(Nx) <= 1:
-        raise ParError("[config]: the MI355X path is 3-D only (Nx1,Nx2,Nx3 > 1)")
+    # integrate.c:30-84: three directions with more than one zone, or two with Nx3 = 1; 1-D Grids have no path here
+    if min(Nx) < 1:
+        raise ParError("[config]: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
+    dim = sum(1 for n in Nx if n > 1)
+    if dim == 2 and Nx[2] > 1:
+        raise ParError("[integrate_init]: 2D problem must have Nx1 and Nx2 > 1: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
+    if dim == 1 and Nx[0] <= 1:
+        raise ParError("[integrate_init]: 1D problem must have Nx1 > 1: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
+    if dim < 2:
+        raise ParError("[config]: 1-D Grids are not supported: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
+    if dim == 2 and ion:
+        raise ParError(f"[config]: problem \"{problem}\" needs ion radiation, and the reference has ionrad_3d only: not on a 2-D Grid (Nx3 = 1)")
+    if dim == 2 and nscal:
+        raise ParError("[config]: passive scalars on a 2-D Grid (Nx3 = 1): no reference target pins them")
     xmin = tuple(par.getd(blk, f"x{d}min") for d in (1, 2, 3))
     xmax = tuple(par.getd(blk, f"x{d}max") for d in (1, 2, 3))
     bc = tuple(par.geti_def(blk, k, 0) for k in
                ("bc_ix1", "bc_ox1", "bc_ix2", "bc_ox2", "bc_ix3", "bc_ox3"))
-    for b in bc:
+    for b in bc[:2 * dim]:                                               # (a direction with one zone has no boundary functions)
         if b not in (1, 2, 4):
             raise ParError(f"[bvals_init]: bc flag = {b} unknown")       # bvals_mhd.c:586
     cour_no = par.getd("time", "cour_no")
-    if cour_no > 0.5:                                                    # integrate.c:66-68
+    if dim == 3 and cour_no > 0.5:                                       # integrate.c:66-68 (2-D: check_2d, by integrator)
         raise ParError("<time>cour_no was set to %g: must be <= 0.5 with 3D integrator" % cour_no)
     cfg = RunConfig(problem=problem, rootNx=Nx, xmin=xmin, xmax=xmax, bc=bc, nscal=nscal, ion=ion,
                     gamma=par.getd("problem", "gamma"), cour_no=cour_no,
@@ -135,13 +152,45 @@ def check_fofc(run: RunConfig, nranks: int = 1, mesh: bool = False) -> None:
         raise ParError(f"[config]: fofc on {nranks} ranks: FixCell's bounds are per Grid and no MPI reference build pins it")
 
 
+def check_2d(run: RunConfig, nranks: int = 1, mesh: bool = False, nslab: int = 1) -> None:
+    """What a 2-D run (Nx3 = 1) may be: the CTU integrator at any cour_no, the van Leer integrator up to 0.5 (integrate.c:55-57),
+    second order, no first-order flux correction, one Grid on one device -- what the reference's 2-D targets pin."""
+    if run.ndim != 2:
+        return
+    if run.integrator == "vl" and run.cour_no > 0.5:
+        raise ParError("<time>cour_no=%e, must be <= 0.5 with 2D VL integrator" % run.cour_no)
+    if run.order != 2:
+        raise ParError("[config]: third-order reconstruction on a 2-D Grid (Nx3 = 1): no reference target pins it")
+    if run.fofc:
+        raise ParError("[config]: fofc on a 2-D Grid (Nx3 = 1): no reference target pins it")
+    if mesh:
+        raise ParError("[config]: static mesh refinement / MeshDriver on a 2-D Grid (Nx3 = 1) is not supported")
+    if nranks > 1:
+        raise ParError(f"[config]: a 2-D Grid (Nx3 = 1) on {nranks} ranks: it has no x3 to cut and x2 cuts are not supported")
+    if nslab > 1:
+        raise ParError(f"[config]: a 2-D Grid (Nx3 = 1) cannot be cut into {nslab} x3 slabs")
+
+
 def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu", fofc: bool = False) -> RunConfig:
-    run = from_par(ParTable.from_file(path).cmdline(overrides), problem)
+    deck = ParTable.from_file(path)
+    ndim_deck = sum(1 for d in (1, 2, 3) if deck.geti("domain1", f"Nx{d}") > 1)
+    par = deck.cmdline(overrides)
+    Nx = tuple(par.geti("domain1", f"Nx{d}") for d in (1, 2, 3))
+    # A deck is written for its number of dimensions (the x3 extent and boundary flags, cour_no -- 0.8 in the reference's 2-D
+    # decks, at most 0.5 in its 3-D ones --, the output blocks): overrides may resize it, not turn a 3-D deck into a 2-D run or
+    # back.  A 2-D run takes a deck with Nx3 = 1 (decks/athinput.blast2d, decks/athinput.shkset2d, or a reference deck of tst/2D-hydro).
+    ndim = sum(1 for n in Nx if n > 1)
+    if min(Nx) >= 1 and {ndim, ndim_deck} == {2, 3}:      # (every other shape: from_par, with the reference's messages)
+        raise ParError("[config]: the overrides turn a %d-D deck into a %d-D run (Nx1=%d, Nx2=%d, Nx3=%d): a 2-D run takes a deck "
+                       "written with Nx3 = 1 (decks/athinput.blast2d, decks/athinput.shkset2d), a 3-D run one with Nx3 > 1"
+                       % ((ndim_deck, ndim) + Nx))
+    run = from_par(par, problem)
     if integrator not in ("ctu", "vl", "ctu-noh"):      # ctu-noh: CTU without --enable-h-correction (the reference's configure default)
         raise ParError(f"[integrate_init]: unknown integrator {integrator}")
     run.integrator = integrator
     run.fofc = bool(fofc)
     check_fofc(run)
+    check_2d(run)
     return run
 
 
@@ -154,8 +203,9 @@ def split_cells(n: int, parts: int) -> List[int]:
 def slab(run: RunConfig, rank: int = 0, nranks: int = 1) -> GridConfig:
     if nranks < 1 or not (0 <= rank < nranks):
         raise ParError(f"[config]: bad rank {rank} of {nranks}")
+    check_2d(run, nranks)
     nx3 = split_cells(run.rootNx[2], nranks)
-    if min(nx3) < NGHOST:
+    if run.ndim == 3 and min(nx3) < NGHOST:
         raise ParError(f"[config]: x3 slabs thinner than nghost={NGHOST} ({run.rootNx[2]}/{nranks})")
     dx = run.dx
     disp3 = sum(nx3[:rank])
@@ -182,6 +232,7 @@ def pencil(run: RunConfig, rank: int, p2: int, p3: int) -> GridConfig:
     NGrid_x1 = 1); cells per Grid and the remainder rule as :583-620, MinX accumulated as init_grid.c:104-111."""
     if p2 < 1 or p3 < 1 or not (0 <= rank < p2 * p3):
         raise ParError(f"[config]: bad rank {rank} of {p2}x{p3}")
+    check_2d(run, p2 * p3)
     if p2 == 1:
         return slab(run, rank, p3)
     r2, r3 = rank % p2, rank // p2
@@ -222,6 +273,7 @@ def levels(par: ParTable, run: RunConfig) -> List[GridConfig]:
     are not on the root boundary get bc = 0 (bvals_mhd.c:193-361, ProlongateLater).  Domains of one level neither overlap nor
     touch (:398-418), so every Domain lies in ONE Domain of the level below."""
     nd = par.geti_def("job", "num_domains", 1)
+    check_2d(run, mesh=nd > 1)
     doms = sorted((par.geti(f"domain{n}", "level"), n) for n in range(1, nd + 1))
     levs = sorted({lev for lev, _ in doms})
     if levs != list(range(len(levs))) or sum(1 for lev, _ in doms if lev == 0) != 1:

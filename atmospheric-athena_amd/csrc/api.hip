@@ -69,10 +69,32 @@ const char *aa_last_error(void) { return g_err; }
 int aa_create(const aa_params *p, aa_grid **out)
 {
   if (!p || !out) return fail(-1, "[aa_create]: null argument");
-  for (int d = 0; d < 3; d++)
-    if (p->Nx[d] <= 1) return fail(-1, "[aa_create]: 3-D only, Nx%d=%d", d + 1, p->Nx[d]);
-  if (p->cour_no > 0.5)   // integrate.c:66-68
+  // integrate.c:30-84: the integrator follows the number of directions with more than one zone
+  int dim = 0;
+  for (int d = 0; d < 3; d++) {
+    if (p->Nx[d] < 1) return fail(-1, "[aa_create]: Nx%d=%d", d + 1, p->Nx[d]);
+    if (p->Nx[d] > 1) dim++;
+  }
+  if (dim == 2 && p->Nx[2] > 1)
+    return fail(-1, "[integrate_init]: 2D problem must have Nx1 and Nx2 > 1: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
+  if (dim == 1 && p->Nx[0] <= 1)
+    return fail(-1, "[integrate_init]: 1D problem must have Nx1 > 1: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
+  if (dim < 2) return fail(-1, "[aa_create]: 1-D Grids are not supported: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
+  const bool two_d = dim == 2;
+  if (!two_d && p->cour_no > 0.5)   // integrate.c:66-68
     return fail(-1, "<time>cour_no was set to %g: must be <= 0.5 with 3D integrator", p->cour_no);
+  if (two_d) {
+    if (p->integrator == 1 && p->cour_no > 0.5)   // integrate.c:55-57; integrate_2d_ctu has no such limit
+      return fail(-1, "<time>cour_no=%e, must be <= 0.5 with 2D VL integrator", p->cour_no);
+    // what no reference target pins on a 2-D Grid is refused
+    if (p->ion) return fail(-1, "[aa_create]: ion radiation on a 2-D Grid: the reference has ionrad_3d only");
+    if (p->nscal != 0) return fail(-1, "[aa_create]: passive scalars on a 2-D Grid: no reference target pins them (NSCALARS must be 0)");
+    if (p->order == 3) return fail(-1, "[aa_create]: third-order reconstruction on a 2-D Grid: no reference target pins it");
+    if (p->level != 0) return fail(-1, "[aa_create]: a 2-D Grid cannot be a level of a refined Mesh (level %d)", p->level);
+    int ns = p->nslab;
+    if (ns == 0) { const char *e = getenv("AA_NGPU"); if (e) ns = atoi(e); }
+    if (ns > 1) return fail(-1, "[aa_create]: a 2-D Grid cannot be cut into x3 slabs (nslab / AA_NGPU = %d)", ns);
+  }
   if (p->ion && p->nscal != 1) return fail(-1, "[aa_create]: ion radiation needs NSCALARS=1");
   if (p->nscal != 0 && p->nscal != 1) return fail(-1, "[aa_create]: NSCALARS must be 0 or 1");
   { // one Grid of the caller on several GPUs: aa_params.nslab, or AA_NGPU in the environment (drop-in executables)
@@ -111,6 +133,8 @@ int aa_create(const aa_params *p, aa_grid **out)
   d.N1 = d.Nx1 + 2*AA_NGHOST; d.N2 = d.Nx2 + 2*AA_NGHOST; d.N3 = d.Nx3 + 2*AA_NGHOST;
   d.is = d.js = d.ks = AA_NGHOST;
   d.ie = d.is + d.Nx1 - 1; d.je = d.js + d.Nx2 - 1; d.ke = d.ks + d.Nx3 - 1;
+  g->two_d = two_d;
+  if (two_d) { d.N3 = 1; d.ks = d.ke = 0; }      // init_grid.c:144-174: no ghost zones along a direction with one zone
   // rows padded to a multiple of 16 doubles and every field shifted by 12 doubles: the first active zone of
   // every row (i = 4) then sits on a 128-byte line, and so does every wavefront of the kernels that walk the
   // active zones 64 at a time (-2.9 % of a 512^3 step; AA_PITCH_ALIGN=0: dense rows)
@@ -141,6 +165,9 @@ int aa_create(const aa_params *p, aa_grid **out)
   const size_t nc = (size_t)d.nc;
   const size_t nef = (size_t)(d.Nx1 + 1)*(d.Nx2 + 1)*(d.Nx3 + 1);
   size_t n = nc*(6 + 36 + 18 + 5 + 1 + 4);       // eta: 3 + the two edge arrays of k_correct_all
+  // a 2-D Grid: U 5 | LR 2 x 2 x 5 | F 2 x 5 | eta 2 | edge (hydro2d_kernels.hip), nothing of the 3-D set
+  const size_t nedge2 = two_d ? (size_t)5*ntiles_2d(d)*d.N2 : 0;
+  if (two_d) n = nc*(5 + 20 + 10 + 2) + nedge2;
   // the one-kernel sub-cycle wants whole wavefronts along the rays; AA_ION_FUSED forces either path
   { const char *e = getenv("AA_ION_BEGIN_FUSED"); g->ion_begin_fused = e ? atoi(e) != 0 : true; }
   { const char *e = getenv("AA_ION_SPECULATE"); g->ion_spec_on = e ? atoi(e) != 0 : true; }
@@ -160,8 +187,11 @@ int aa_create(const aa_params *p, aa_grid **out)
   g->bytes = (long long)(n*sizeof(Real));
   hipMemset(g->pool, 0, n*sizeof(Real));
   Real *q = g->pool + (pitch_align ? 12 : 0);
+  if (two_d) { d.U = q; q += 5*nc; d.LR = q; q += 20*nc; d.F = q; q += 10*nc; d.eta = q; q += 2*nc; g->edge2d = q; q += nedge2; }
+  else {
   d.U = q; q += 6*nc; d.LR = q; q += 36*nc; d.F = q; q += 18*nc; d.eta = q; q += 5*nc; d.dhalf = q; q += nc;
   d.phi = q; q += 4*nc;
+  }
   if (p->order == 3) { d.slope = q; q += 18*nc; }
   if (p->ion) {
     d.ph_rate = q; q += nc; d.kin = q; q += nc; d.vmax = q; q += nc;
@@ -286,6 +316,15 @@ int aa_download_ghost_zones(aa_grid *g, double *U)
   const size_t row = (size_t)N1*nvar*sizeof(Real), plane = row*N2;
   launch_soa_to_aos(g->d, nvar, g->d.LR, g->st);
   const char *S = (const char*)g->d.LR; char *D = (char*)U;
+  if (g->two_d) {      // one plane: four rows at either end, four zones at either end of the rows in between
+    const size_t w2 = (size_t)ng*nvar*sizeof(Real), mid2 = (size_t)ng*row;
+    HIPCHK(hipMemcpyAsync(D, S, ng*row, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpyAsync(D + (size_t)(N2 - ng)*row, S + (size_t)(N2 - ng)*row, ng*row, hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpy2DAsync(D + mid2, row, S + mid2, row, w2, (size_t)(N2 - 2*ng), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipMemcpy2DAsync(D + mid2 + row - w2, row, S + mid2 + row - w2, row, w2, (size_t)(N2 - 2*ng), hipMemcpyDeviceToHost, g->st));
+    HIPCHK(hipStreamSynchronize(g->st));
+    return 0;
+  }
   // x3: the four planes at either end, whole
   HIPCHK(hipMemcpyAsync(D, S, ng*plane, hipMemcpyDeviceToHost, g->st));
   HIPCHK(hipMemcpyAsync(D + (size_t)(N3 - ng)*plane, S + (size_t)(N3 - ng)*plane, ng*plane, hipMemcpyDeviceToHost, g->st));
@@ -353,6 +392,7 @@ int aa_set_static_grav_tables(aa_grid *g, const double *pc, const double *p1, co
 {
   if (!g->slab.empty()) return slabs_set_grav_tables(g, pc, p1, p2, p3);
   if (!pc) { g->grav = false; return 0; }
+  if (g->two_d) return fail(-1, "[aa_set_static_grav_tables]: static gravity on a 2-D Grid: no reference run pins it (prob/ioniz_sphere.c:113 writes past a 2-D Grid)");
   // host tables are dense [N3][N2][N1]; device rows are sJ apart
   const double *src[4] = {pc, p1, p2, p3};
   for (int w = 0; w < 4; w++)
@@ -366,6 +406,7 @@ int aa_set_static_grav_tables(aa_grid *g, const double *pc, const double *p1, co
 int aa_set_static_grav_pot(aa_grid *g, aa_gravpot_fn fn)
 {
   if (!fn) return aa_set_static_grav_tables(g, nullptr, nullptr, nullptr, nullptr);
+  if (g->two_d) return fail(-1, "[aa_set_static_grav_pot]: static gravity on a 2-D Grid: no reference run pins it (prob/ioniz_sphere.c:113 writes past a 2-D Grid)");
   // (a Grid cut into slabs evaluates the callback at the positions of the caller's ONE Grid: the slabs then hold
   //  the very numbers the undivided Grid would)
   const int N1 = g->p.Nx[0] + 2*AA_NGHOST, N2 = g->p.Nx[1] + 2*AA_NGHOST, N3 = g->p.Nx[2] + 2*AA_NGHOST;
@@ -384,6 +425,7 @@ int aa_set_cooling(aa_grid *g, int kind)
 {
   if (kind != AA_COOL_NONE && kind != AA_COOL_KOYINUT) return fail(-1, "[aa_set_cooling]: kind=%d: only AA_COOL_NONE and AA_COOL_KOYINUT", kind);
   if (kind && g->p.integrator == 1) return fail(-1, "[aa_set_cooling]: the van Leer integrator has no cooling terms in the reference (integrate_3d_vl.c)");
+  if (kind && g->two_d) return fail(-1, "[aa_set_cooling]: cooling on a 2-D Grid: no reference target pins it");
   if (!g->slab.empty() || g->link) return slabs_set_cooling(g, kind);
   g->inner_swept = false;
   if (kind && !g->d.phalf) {
@@ -403,6 +445,7 @@ int aa_set_fofc(aa_grid *g, int on)
 {
   if (!on) { if (g->slab.empty() && !g->link) { g->fofc = false; g->fofc_counts[0] = g->fofc_counts[1] = g->fofc_counts[2] = 0; } return 0; }
   if (!g->slab.empty() || g->link) return fail(-1, "[aa_set_fofc]: not available on a Grid cut into slabs (FixCell's bounds are per Grid; no reference build pins a cut one)");
+  if (g->two_d) return fail(-1, "[aa_set_fofc]: first-order flux correction on a 2-D Grid: no reference target pins it (integrate_3d_vl.c only here)");
   if (g->p.integrator != 1) return fail(-1, "[aa_set_fofc]: the CTU integrator has no first-order flux correction in the reference (integrate_3d_vl.c only)");
   if (g->p.order == 3) return fail(-1, "[aa_set_fofc]: no reference build pins first-order flux correction with third-order reconstruction");
   if (g->level > 0 || g->keep_flux) return fail(-1, "[aa_set_fofc]: not available on a level of a refined Mesh (FixCell would also have to replace the fluxes RestrictCorrect reads)");
@@ -458,6 +501,7 @@ int aa_apply_pinned_cells(aa_grid *g)
 
 int aa_add_radplane_3d(aa_grid *g, int dir, double flux)
 {
+  if (g->two_d) return fail(-1, "[add_radplane_3d]: ion radiation on a 2-D Grid: the reference has ionrad_3d only");
   if (!g->p.ion) return fail(-1, "[add_radplane_3d]: ion radiation is off");
   // Rays along +x1 (dir = -1) and along +x2 (dir = -2).  The reference has no working behaviour for the others:
   // right-to-left rays (dir > 0) never enter the loop `for (i=s; i<=e; i+=lr)` with s > e (ionradplane_3d.c:275, :335,
@@ -480,6 +524,10 @@ int aa_bvals_mhd(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_bvals_mhd(g);
   Scope s(g, "bvals_mhd");
+  if (g->two_d) {      // bvals_mhd.c:170: x1 then x2, so the corners fill; a direction with one zone has no boundary functions
+    for (int d = 0; d < 2; d++) launch_bc_dir(g->d, g->p.nscal, d, g->p.bc[2*d], g->p.bc[2*d + 1], g->st);
+    return 0;
+  }
   if (g->d.cfg.bc_one) { launch_bc_shell(g->d, g->p.nscal, g->p.bc, g->st); return 0; }      // the three passes as one launch: same bits
   for (int d = 0; d < 3; d++)            // x1, x2, x3 so the corners fill (bvals_mhd.c:170)
     launch_bc_dir(g->d, g->p.nscal, d, g->p.bc[2*d], g->p.bc[2*d + 1], g->st);
@@ -490,6 +538,7 @@ int aa_bvals_mhd_side(aa_grid *g, int dir, int side)
 {
   if (dir < 0 || dir > 2 || side < 0 || side > 1) return fail(-1, "[aa_bvals_mhd_side]: dir=%d side=%d", dir, side);
   if (!g->slab.empty()) return slabs_bvals_mhd_side(g, dir, side);
+  if (g->two_d && dir == 2) return 0;      // (no ghost zones along x3)
   const int flag = g->p.bc[2*dir + side];
   if (flag) { Scope s(g, "bvals_mhd"); launch_bc(g->d, g->p.nscal, dir, side, flag, g->st); }
   return 0;
@@ -546,7 +595,8 @@ int aa_new_dt_local(aa_grid *g, double *dt_cfl)
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
   double max_dti = 0.0;                   // new_dt.c:159-166
-  for (int d = 0; d < 3; d++) { double v = bits_to_double(g->sc_host->max_v[d])/g->d.dx[d]; max_dti = (max_dti > v) ? max_dti : v; }
+  const int ndir = g->two_d ? 2 : 3;     // new_dt.c:156-161: only the directions with more than one zone
+  for (int d = 0; d < ndir; d++) { double v = bits_to_double(g->sc_host->max_v[d])/g->d.dx[d]; max_dti = (max_dti > v) ? max_dti : v; }
   *dt_cfl = g->p.cour_no/max_dti;
   return 0;
 }
@@ -560,6 +610,7 @@ int aa_cfl_max_v(aa_grid *g, double *v)      // new_dt.c:72-140 of this Grid: ma
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
   for (int d = 0; d < 3; d++) v[d] = bits_to_double(g->sc_host->max_v[d]);
+  if (g->two_d) v[2] = 0.0;              // new_dt.c:135: max_v3 only where Nx3 > 1
   return 0;
 }
 
@@ -608,6 +659,7 @@ static bool x3_fused(const aa_grid *g)      // default: always (round 3; until t
 static bool x1_fused(const aa_grid *g) { return g->correct_all && x3_fused(g) && HL(ca_x1_on_board)(); }
 int aa_integrate_begin(aa_grid *g)
 {
+  if (g->two_d) return 0;
   if (!g->slab.empty() || g->p.integrator != 0 || g->d.slope || !g->correct_all || !g->fused_update || g->inner_swept) return 0;
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
   const int nk = d.ke - d.ks + 1;
@@ -633,6 +685,7 @@ static void no_h_correction(aa_grid *g)
 int aa_integrate_3d_ctu(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_integrate(g, 0);
+  if (g->two_d) return fail(-1, "[aa_integrate_3d_ctu]: this is a 2-D Grid (Nx3 = 1): aa_integrate_2d_ctu");
   g->cfl_ready = false; g->active_dirty = true;
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
   if (g->inner_swept) {      // aa_integrate_begin did the planes ks .. ke: the two ghost planes either side remain
@@ -748,6 +801,7 @@ static int fofc_finish(aa_grid *g)
 int aa_integrate_3d_vl(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_integrate(g, 1);
+  if (g->two_d) return fail(-1, "[aa_integrate_3d_vl]: this is a 2-D Grid (Nx3 = 1): aa_integrate_2d_vl");
   g->cfl_ready = false; g->active_dirty = true;
   // integrate_3d_vl.c:96-: donor-cell fluxes -> U^{n+1/2} -> PLM or PPM (no tracing) + Roe -> update
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
@@ -1125,6 +1179,8 @@ int aa_step(aa_grid *g, int *niter_out)
   // (between the integrator and new_dt this loop only pins zones: the integrator may leave new_dt's maxima behind)
   const bool keep_opt = g->cfl_in_update;
   if (g->slab.empty() && g->cfl_step) g->cfl_in_update = true;      // (both builds since round 4: aa_cfl_in_update)
+  if (g->two_d) rc = (g->p.integrator == 1 ? aa_integrate_2d_vl(g) : aa_integrate_2d_ctu(g));     // integrate.c:49-58
+  else
   rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g));                    // :572-585
   g->cfl_in_update = keep_opt;
   if (rc) return rc;
@@ -1137,7 +1193,8 @@ int aa_step(aa_grid *g, int *niter_out)
 }
 
 // ---- x3 halo ------------------------------------------------------------------------------
-#define NO_SLABS(name) if (!g->slab.empty()) return fail(-1, "[" name "]: not available on a Grid cut into slabs")
+#define NO_SLABS(name) if (!g->slab.empty()) return fail(-1, "[" name "]: not available on a Grid cut into slabs"); \
+  if (g->two_d) return fail(-1, "[" name "]: not available on a 2-D Grid (one Grid, no halo exchange)")
 long long aa_halo_doubles(const aa_grid *g)      // (a Grid cut into slabs exchanges its halos itself: 0)
 { return g->slab.empty() ? (long long)g->d.N1*g->d.N2*AA_NGHOST*(5 + g->p.nscal) : 0LL; }
 int aa_pack_x3(aa_grid *g, int side, double *buf)

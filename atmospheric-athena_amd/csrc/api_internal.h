@@ -43,6 +43,8 @@ struct aa_grid {
   int cool = 0;                        // aa_set_cooling: 1 = KoyInut; the integrator then launches the kernels of namespace aa_cool
   int rad_dir = 0, nradplane = 0; aa::Real flux_i = 0;
   int level = 0;                       // DomainS.Level: > 0 only as a level of an aa_mesh
+  bool two_d = false;                  // Nx3 = 1: the 2-D integrators (hydro2d_kernels.hip); U 5 | LR 20 | F 10 | eta 2 | edge2d
+  aa::Real *edge2d = nullptr;          //   ... what the x1 tiles of the 2-D kernels hand each other (grid.h)
   bool fused_update = false;           // second-pass fluxes + update in one kernel (AA_FUSED_UPDATE=0 at aa_create: the unfused chain)
   int x3_fused_mode = -1;              // k_correct_all also does the x3 first pass: -1 by configuration (api.hip), AA_X3_FUSED=0/1 forces
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) k_dump_section(DevGrid g, int var, int pr
     const unsigned z = VEC ? o/3u : o, c = VEC ? o - 3u*z : 0u;
     const unsigned r = z/nx1, i = z - r*nx1, row = (unsigned)row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    const long m = (long)(k + AA_NGHOST_)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
+    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
     const unsigned b = __float_as_uint(dump_value(g, VEC ? 1 + (int)c : var, prim, m));
     w[q] = swap ? __builtin_bswap32(b) : b;
   }
@@ -95,7 +95,7 @@ void dump_release(aa_grid *g)
 static size_t dump_capacity(const aa_grid *g)
 {
   size_t cap = (size_t)g->dump_chunk;
-  const size_t room = (size_t)36*(size_t)g->d.nc;         // LR is 36*nc doubles = 72*nc floats: two slots of 36*nc
+  const size_t room = (size_t)(g->two_d ? 20 : 36)*(size_t)g->d.nc;   // LR is 36*nc doubles = 72*nc floats: two slots of 36*nc (a 2-D Grid: 20*nc)
   const size_t row = (size_t)3*(size_t)g->d.Nx1;
   if (cap > room) cap = room;
   if (cap < row) cap = row;

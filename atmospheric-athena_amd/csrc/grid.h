@@ -162,4 +162,13 @@ void launch_ion_reduce_pick(const HostGrid &g, const IonPart *part, Real *words,
 void launch_ion_finish(const DevGrid &g, int cur, hipStream_t st);
 void launch_test_explog(int n, const Real *x, Real *ye, Real *yl, hipStream_t st);   // n a multiple of 4
 
+// ---- launch wrappers (hydro2d_kernels.hip): a 2-D Grid (Nx3 = 1: N3 = 1, ks = ke = 0, no ghost zones along x3) -----------
+// `edge`: 5 x ntiles_2d x N2 doubles, what a lane at the end of an x1 tile needs from the tile beside it (filled by a side kernel)
+int  ntiles_2d(const DevGrid &g);
+void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, hipStream_t st);               // integrate_2d_ctu.c Steps 1, 2
+void launch_2d_ctu_correct(const DevGrid &g, Real dt, bool hcorr, hipStream_t st);             // Steps 5a, 6a, 9a (hcorr false: etas 0)
+void launch_2d_ctu_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st);   // Steps 9b-c, 12; sc: and new_dt's maxima
+void launch_2d_vl_predict(const DevGrid &g, Real dt, Real *edge, hipStream_t st);              // integrate_2d_vl.c Steps 1-5
+void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st);    // Steps 7-13
+
 }  // namespace aa

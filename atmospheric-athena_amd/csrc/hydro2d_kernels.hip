@@ -1,0 +1,382 @@
+// hydro2d_kernels.hip -- the hydro hot path of a 2-D Grid (Nx3 = 1; gfx950): integrate_2d_ctu.c and integrate_2d_vl.c of the
+// reference for HYDRO, ADIABATIC, CARTESIAN, second order, no gravity, no cooling, no passive scalar.  The per-cell and
+// per-face arithmetic is that of hydro_dev.h, unchanged; this file only restates the 2-D loop nests.
+//
+// Layout (api.hip aa_create): one plane [N2][sJ] per field, no ghost zones along x3 (ks = ke = 0), fields nc = sJ*N2 apart,
+//   U   5 fields  d, M1, M2, M3, E                               (global momentum frame)
+//   LR  20 fields [dir][L|R][d, Mx, My, Mz, E]                   (SWEEP frame: x1 (M1,M2,M3), x2 (M2,M3,M1); integrate_2d_ctu.c:1087-1097)
+//                 van Leer: fields 0 .. 4 hold U^{n+1/2} in the global frame
+//   F   10 fields [dir][d, Mx, My, Mz, E]                        first-pass fluxes, sweep frame (CTU only)
+//   eta 2 fields  eta1, eta2                                     (CTU only)
+//   edge 5 x ntx x N2 doubles: what lane 0 / lane 63 of an x1 tile needs from the neighbouring tile (see below)
+//
+// Kernel shape: a block is T2_R wavefronts, each 64 lanes along x1 on whole 128-byte lines (tiles start at i = is, which
+// aa_create puts on a line), one row of zones per wavefront.  Tiles do not overlap in x1: what a face needs of the zone
+// one lane down (its left state) or up (the flux of the upper face) comes by wavefront shuffle; across the tile's edge it
+// comes from the `edge` buffer, filled by a small side kernel with one thread per tile edge and row.  Along x2 the same
+// quantities travel through LDS between the block's wavefronts; one wavefront of the block is a halo row that only feeds
+// its neighbour.  Second-pass fluxes never reach HBM: k2d_step computes the fluxes of a zone's two lower faces, takes the
+// upper ones from its neighbours, updates the zone and folds new_dt's maxima.
+//
+// CTU: k2d_edge_wl, k2d_first, k2d_correct, k2d_edge<CTU2>, k2d_step<CTU2>   (3 launches + 2 side kernels)
+// VL : k2d_edge<VL1>, k2d_step<VL1>, k2d_edge<VL2>, k2d_step<VL2>            (2 launches + 2 side kernels)
+#include <hip/hip_runtime.h>
+#include "grid.h"
+#include "hydro_dev.h"
+
+namespace aa {
+
+#define T2_W 64
+#define T2_R 8            /* wavefronts (rows) per block, one of them the halo row */
+
+AA_DEV Real *U2(const DevGrid &g, int v) { return g.U + (long)v*g.nc; }
+AA_DEV Real *LR2(const DevGrid &g, int d, int side, int v) { return g.LR + (long)((d*2 + side)*5 + v)*g.nc; }
+AA_DEV Real *F2(const DevGrid &g, int d, int v) { return g.F + (long)(d*5 + v)*g.nc; }
+AA_DEV int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// a zone of a global-frame state (5 fields nc apart) in the sweep frame of direction D
+template <int D>
+AA_DEV void load_cons(const Real *b, long nc, long m, Real u[6])
+{
+  u[0] = b[m]; u[4] = b[4*nc + m]; u[5] = 0.0;
+  if (D == 0) { u[1] = b[nc + m];   u[2] = b[2*nc + m]; u[3] = b[3*nc + m]; }
+  else        { u[1] = b[2*nc + m]; u[2] = b[3*nc + m]; u[3] = b[nc + m]; }
+}
+AA_DEV void load5(const Real *b, long nc, long m, Real u[6])
+{
+#pragma unroll
+  for (int v = 0; v < 5; v++) u[v] = b[(long)v*nc + m];
+  u[5] = 0.0;
+}
+AA_DEV void store5(Real *b, long nc, long m, const Real u[6])
+{
+#pragma unroll
+  for (int v = 0; v < 5; v++) b[(long)v*nc + m] = u[v];
+}
+
+// PLM with characteristic tracing of the zone at m along D (lr_states_plm.c): Wl of its upper face, Wr of its lower face
+template <int D, bool TRACE>
+AA_DEV void recon_zone(const Real *src, const DevGrid &g, long m, Real dt, Real wl_next[6], Real wr_here[6])
+{
+  const long s = D == 0 ? 1L : g.sJ;
+  Real u[6], wm[6], w[6], wp[6];
+  load_cons<D>(src, g.nc, m - s, u); cons_to_prim<0>(u, wm, g.Gamma_1);
+  load_cons<D>(src, g.nc, m, u);     cons_to_prim<0>(u, w, g.Gamma_1);
+  load_cons<D>(src, g.nc, m + s, u); cons_to_prim<0>(u, wp, g.Gamma_1);
+  plm_cell<0, TRACE>(wm, w, wp, dt/g.dx[D], g.Gamma, wl_next, wr_here);
+}
+
+// first-pass flux of one face from its primitive L/R states (integrate_2d_ctu.c Step 1d / 2d: etah = 0)
+AA_DEV void face_first(const DevGrid &g, const Real wl[6], const Real wr[6], Real ul[6], Real ur[6], Real f[6])
+{
+  prim_to_cons<0>(wl, ul, g.Gamma_1, g.rGamma_1);
+  prim_to_cons<0>(wr, ur, g.Gamma_1, g.rGamma_1);
+  flux_roe<0>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
+}
+
+// ---- CTU, Steps 1 and 2 -------------------------------------------------------------------------------------------------
+// side kernel: the left state of the first x1 face of every tile but the first (the zone below it belongs to the tile before)
+__global__ void __launch_bounds__(64)
+k2d_edge_wl(DevGrid g, Real dt, Real *edge, int ntx)
+{
+  const int jl = g.js - 2, nj = g.je - g.js + 5;
+  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
+  if (lin >= (long)nj*(ntx - 1)) return;
+  const int j = jl + (int)(lin % nj), t = 1 + (int)(lin / nj);
+  const int i0 = g.is + 64*(t - 1);
+  if (i0 > g.ie + 2) return;
+  Real wl[6], wr[6];
+  recon_zone<0, true>(g.U, g, (long)j*g.sJ + i0 - 1, dt, wl, wr);
+  const long es = (long)ntx*g.N2;
+#pragma unroll
+  for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = wl[v];
+}
+
+// L/R states and first-pass fluxes of the lower x1 and x2 face of every zone of [is-2, ie+2] x [js-2, je+2]
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_first(DevGrid g, Real dt, const Real *edge)
+{
+  __shared__ Real sh[5][T2_R][T2_W];
+  const int lane = threadIdx.x, ty = threadIdx.y;
+  const int il = g.is - 2, iu = g.ie + 2, jl = g.js - 2, ju = g.je + 2;
+  const int i = g.is + 64*((int)blockIdx.x - 1) + lane;
+  const int j = jl + (T2_R - 1)*(int)blockIdx.y + ty - 1;           // ty = 0: the halo row below the block's zones
+  const int ic = clampi(i, il, iu), jc = clampi(j, jl, ju);         // (threads outside the range compute on a zone inside it and store nothing)
+  const bool in_i = i >= il && i <= iu, in_j = j >= jl && j <= ju;
+  const long m = (long)jc*g.sJ + ic;
+  Real wl[6], wr[6], wln[6], ul[6], ur[6], f[6];
+
+  recon_zone<1, true>(g.U, g, m, dt, wln, wr);
+#pragma unroll
+  for (int v = 0; v < 5; v++) sh[v][ty][lane] = wln[v];
+  Real wr2[6];
+#pragma unroll
+  for (int v = 0; v < 6; v++) wr2[v] = wr[v];
+
+  if (ty > 0) {          // (one row per wavefront: the branch is uniform)
+    recon_zone<0, true>(g.U, g, m, dt, wln, wr);
+#pragma unroll
+    for (int v = 0; v < 5; v++) wl[v] = __shfl_up(wln[v], 1);
+    wl[5] = 0.0;
+    if (lane == 0 && blockIdx.x >= 1) {
+      const long es = (long)gridDim.x*g.N2;
+#pragma unroll
+      for (int v = 0; v < 5; v++) wl[v] = edge[v*es + (long)blockIdx.x*g.N2 + jc];
+    }
+    face_first(g, wl, wr, ul, ur, f);
+    if (in_j && i >= il + 1 && i <= iu) {
+      store5(LR2(g, 0, 0, 0), g.nc, m, ul); store5(LR2(g, 0, 1, 0), g.nc, m, ur); store5(F2(g, 0, 0), g.nc, m, f);
+    }
+  }
+  __syncthreads();
+  if (ty > 0) {
+#pragma unroll
+    for (int v = 0; v < 5; v++) wl[v] = sh[v][ty - 1][lane];
+    wl[5] = 0.0;
+    face_first(g, wl, wr2, ul, ur, f);
+    if (in_i && j >= jl + 1 && j <= ju) {
+      store5(LR2(g, 1, 0, 0), g.nc, m, ul); store5(LR2(g, 1, 1, 0), g.nc, m, ur); store5(F2(g, 1, 0), g.nc, m, f);
+    }
+  }
+}
+
+// ---- CTU, Steps 5a, 6a and 9a: transverse flux gradients on the face states, then eta1 / eta2 ----------------------------
+// a -= h*(fp - fm) for the five fields, with the transverse flux's components permuted into this face's frame
+// (x1 faces take (d, Mz, Mx, My, E) of the x2 fluxes, x2 faces (d, My, Mz, Mx, E) of the x1 fluxes)
+template <int D>
+AA_DEV void correct_state(Real u[6], Real h, const Real fp[6], const Real fm[6])
+{
+  u[0] -= h*(fp[0] - fm[0]);
+  if (D == 0) { u[1] -= h*(fp[3] - fm[3]); u[2] -= h*(fp[1] - fm[1]); u[3] -= h*(fp[2] - fm[2]); }
+  else        { u[1] -= h*(fp[2] - fm[2]); u[2] -= h*(fp[3] - fm[3]); u[3] -= h*(fp[1] - fm[1]); }
+  u[4] -= h*(fp[4] - fm[4]);
+}
+__global__ void __launch_bounds__(256)
+k2d_correct(DevGrid g, Real dt, int hcorr)
+{
+  const int il = g.is - 2, iu = g.ie + 2, jl = g.js - 2, ju = g.je + 2;
+  const int i = g.is + 64*((int)blockIdx.x - 1) + (int)threadIdx.x;
+  const int j = jl + 1 + 4*(int)blockIdx.y + (int)threadIdx.y;
+  if (i < il + 1 || i > iu || j > ju) return;
+  const long m = (long)j*g.sJ + i;
+  const Real hdtodx1 = 0.5*(dt/g.dx[0]), hdtodx2 = 0.5*(dt/g.dx[1]);
+  Real ul[6], ur[6], fp[6], fm[6];
+  if (j <= ju - 1) {                                       // x1 face (j, i)
+    load5(LR2(g, 0, 0, 0), g.nc, m, ul); load5(LR2(g, 0, 1, 0), g.nc, m, ur);
+    load5(F2(g, 1, 0), g.nc, m + g.sJ - 1, fp); load5(F2(g, 1, 0), g.nc, m - 1, fm);
+    correct_state<0>(ul, hdtodx2, fp, fm);
+    load5(F2(g, 1, 0), g.nc, m + g.sJ, fp); load5(F2(g, 1, 0), g.nc, m, fm);
+    correct_state<0>(ur, hdtodx2, fp, fm);
+    store5(LR2(g, 0, 0, 0), g.nc, m, ul); store5(LR2(g, 0, 1, 0), g.nc, m, ur);
+    if (j >= g.js - 1 && j <= g.je + 1 && i >= g.is - 1 && i <= g.ie + 2) {
+      Real e = 0.0;
+      if (hcorr) {
+        const Real lambdar = lambda_face(ur, g.Gamma, g.Gamma_1, 1.0), lambdal = lambda_face(ul, g.Gamma, g.Gamma_1, -1.0);
+        e = 0.5*fabs(lambdar - lambdal);
+      }
+      g.eta[m] = e;
+    }
+  }
+  if (i <= iu - 1) {                                       // x2 face (j, i)
+    load5(LR2(g, 1, 0, 0), g.nc, m, ul); load5(LR2(g, 1, 1, 0), g.nc, m, ur);
+    load5(F2(g, 0, 0), g.nc, m - g.sJ + 1, fp); load5(F2(g, 0, 0), g.nc, m - g.sJ, fm);
+    correct_state<1>(ul, hdtodx1, fp, fm);
+    load5(F2(g, 0, 0), g.nc, m + 1, fp); load5(F2(g, 0, 0), g.nc, m, fm);
+    correct_state<1>(ur, hdtodx1, fp, fm);
+    store5(LR2(g, 1, 0, 0), g.nc, m, ul); store5(LR2(g, 1, 1, 0), g.nc, m, ur);
+    if (j >= g.js - 1 && j <= g.je + 2 && i >= g.is - 1 && i <= g.ie + 1) {
+      Real e = 0.0;
+      if (hcorr) {
+        const Real lambdar = lambda_face(ur, g.Gamma, g.Gamma_1, 1.0), lambdal = lambda_face(ul, g.Gamma, g.Gamma_1, -1.0);
+        e = 0.5*fabs(lambdar - lambdal);
+      }
+      g.eta[g.nc + m] = e;
+    }
+  }
+}
+
+// ---- the flux of the lower face of zone (j, i) along D, in the sweep frame, for the three fused update kernels -----------
+enum { M_CTU2 = 0, M_VL1 = 1, M_VL2 = 2 };
+template <int MODE, int D>
+AA_DEV void face_flux(const DevGrid &g, int i, int j, Real dt, Real f[6])
+{
+  const long m = (long)j*g.sJ + i;
+  const long s = D == 0 ? 1L : g.sJ;
+  Real ul[6], ur[6], wl[6], wr[6];
+  if (MODE == M_CTU2) {
+    // Steps 9b / 9c: the largest of the five etas around the face, in the reference's order (MAX as a ternary), then the flux
+    const Real *e1 = g.eta, *e2 = g.eta + g.nc;
+    Real etah;
+    if (D == 0) {
+      etah = rmax(e2[m - 1], e2[m]);
+      etah = rmax(etah, e2[m + g.sJ - 1]);
+      etah = rmax(etah, e2[m + g.sJ]);
+      etah = rmax(etah, e1[m]);
+    } else {
+      etah = rmax(e1[m - g.sJ], e1[m]);
+      etah = rmax(etah, e1[m - g.sJ + 1]);
+      etah = rmax(etah, e1[m + 1]);
+      etah = rmax(etah, e2[m]);
+    }
+    load5(LR2(g, D, 0, 0), g.nc, m, ul); load5(LR2(g, D, 1, 0), g.nc, m, ur);
+    cons_to_prim<0>(ul, wl, g.Gamma_1); cons_to_prim<0>(ur, wr, g.Gamma_1);
+    flux_roe<0>(ul, ur, wl, wr, etah, g.Gamma, g.Gamma_1, f);
+  } else if (MODE == M_VL1) {
+    // integrate_2d_vl.c Steps 1-2: donor cell, through the primitive variables and back as the reference does
+    Real u[6];
+    load_cons<D>(g.U, g.nc, m - s, u); cons_to_prim<0>(u, wl, g.Gamma_1);
+    load_cons<D>(g.U, g.nc, m, u);     cons_to_prim<0>(u, wr, g.Gamma_1);
+    face_first(g, wl, wr, ul, ur, f);
+  } else {
+    // Steps 7-10: PLM without tracing on U^{n+1/2} (LR fields 0 .. 4), then the flux
+    Real dump[6];
+    recon_zone<D, false>(g.LR, g, m - s, dt, wl, dump);
+    recon_zone<D, false>(g.LR, g, m, dt, dump, wr);
+    face_first(g, wl, wr, ul, ur, f);
+  }
+}
+template <int MODE> struct Range2 {
+  __host__ __device__ static int ext() { return MODE == M_VL1 ? 3 : 0; }      // zones updated: the active ones, or those 3 ghost zones out
+  __host__ __device__ static int toff() { return MODE == M_VL1 ? 1 : 0; }     // x1 tiles in front of the one that starts at is
+};
+
+// side kernel: the x1 flux of the face above the last lane of every x1 tile
+template <int MODE>
+__global__ void __launch_bounds__(64)
+k2d_edge(DevGrid g, Real dt, Real *edge, int ntx)
+{
+  const int X = Range2<MODE>::ext();
+  const int lo_j = g.js - X, nj = g.je - g.js + 1 + 2*X, hi_i = g.ie + X;
+  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
+  if (lin >= (long)nj*ntx) return;
+  const int j = lo_j + (int)(lin % nj), t = (int)(lin / nj);
+  const int i = g.is + 64*(t - Range2<MODE>::toff()) + 64;
+  if (i < g.is - X + 1 || i > hi_i + 1) return;
+  Real f[6];
+  face_flux<MODE, 0>(g, i, j, dt, f);
+  const long es = (long)ntx*g.N2;
+#pragma unroll
+  for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = f[v];
+}
+
+// new_dt.c:72-140 for one zone (the operands and their order as in the CFL kernel of the 3-D path; never contracted, so that
+// the maxima are the same bits whichever kernel visits the zone)
+AA_DEV void cfl_zone2(Real d, Real m1, Real m2, Real m3, Real e, Real Gamma, Real Gamma_1, Real mx[2])
+{
+#pragma clang fp contract(off)
+  const Real di = 1.0/d;
+  const Real v1 = m1*di, v2 = m2*di, v3 = m3*di;
+  const Real qsq = v1*v1 + v2*v2 + v3*v3;
+  const Real p = rmax(Gamma_1*(e - 0.5*d*qsq), AA_TINY);
+  const Real a = sqrt(Gamma*p*di);
+  mx[0] = rmax(mx[0], fabs(v1) + a); mx[1] = rmax(mx[1], fabs(v2) + a);
+}
+
+// fluxes of the two lower faces + update of the zone (+ new_dt's maxima): U^{n+1/2} of the van Leer predictor (M_VL1, c = dt/2dx,
+// written to LR), the full update of either integrator (c = dt/dx, U in place; x1 differences first, then x2: Steps 12a-b / 13)
+template <int MODE, bool CFL>
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
+{
+  __shared__ Real sh[5][T2_R][T2_W];
+  __shared__ Real red[2][T2_R];
+  const int X = Range2<MODE>::ext();
+  const int lane = threadIdx.x, ty = threadIdx.y;
+  const int lo_i = g.is - X, hi_i = g.ie + X, lo_j = g.js - X, hi_j = g.je + X;
+  const int i = g.is + 64*((int)blockIdx.x - Range2<MODE>::toff()) + lane;
+  const int j = lo_j + (T2_R - 1)*(int)blockIdx.y + ty;             // ty = T2_R - 1: the halo row above the block's zones
+  const int ic = clampi(i, lo_i, hi_i), jc = clampi(j, lo_j, hi_j);
+  Real f1[6], f2[6], f1p[6], f2p[6];
+
+  // x2 flux of the lower face: rows lo_j .. hi_j + 1
+  face_flux<MODE, 1>(g, ic, clampi(j, lo_j, hi_j + 1), dt, f2);
+#pragma unroll
+  for (int v = 0; v < 5; v++) sh[v][ty][lane] = f2[v];
+  const bool zone = ty < T2_R - 1 && i >= lo_i && i <= hi_i && j <= hi_j;
+  if (ty < T2_R - 1) {                                             // (uniform per wavefront)
+    face_flux<MODE, 0>(g, clampi(i, lo_i, hi_i + 1), jc, dt, f1);
+#pragma unroll
+    for (int v = 0; v < 5; v++) f1p[v] = __shfl_down(f1[v], 1);
+    if (lane == 63 && zone) {
+      const long es = (long)gridDim.x*g.N2;
+#pragma unroll
+      for (int v = 0; v < 5; v++) f1p[v] = edge[v*es + (long)blockIdx.x*g.N2 + j];
+    }
+  }
+  __syncthreads();
+  Real mx[2] = {0.0, 0.0};
+  if (zone) {
+#pragma unroll
+    for (int v = 0; v < 5; v++) f2p[v] = sh[v][ty + 1][lane];
+    const long m = (long)j*g.sJ + i;
+    Real u[5];
+#pragma unroll
+    for (int v = 0; v < 5; v++) u[v] = U2(g, v)[m];
+    u[0] -= c1*(f1p[0] - f1[0]);
+    u[1] -= c1*(f1p[1] - f1[1]);
+    u[2] -= c1*(f1p[2] - f1[2]);
+    u[3] -= c1*(f1p[3] - f1[3]);
+    u[4] -= c1*(f1p[4] - f1[4]);
+    u[0] -= c2*(f2p[0] - f2[0]);
+    u[1] -= c2*(f2p[3] - f2[3]);
+    u[2] -= c2*(f2p[1] - f2[1]);
+    u[3] -= c2*(f2p[2] - f2[2]);
+    u[4] -= c2*(f2p[4] - f2[4]);
+    Real *dst = MODE == M_VL1 ? g.LR : g.U;
+#pragma unroll
+    for (int v = 0; v < 5; v++) dst[(long)v*g.nc + m] = u[v];
+    if (CFL) cfl_zone2(u[0], u[1], u[2], u[3], u[4], g.Gamma, g.Gamma_1, mx);
+  }
+  if (CFL) {
+    // (a NaN maximum loses every comparison here and is dropped by the atomic, as in the CFL kernel of the 3-D path)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mx[0] = rmax(mx[0], __shfl_xor(mx[0], o)); mx[1] = rmax(mx[1], __shfl_xor(mx[1], o)); }
+    if (lane == 0) { red[0][ty] = mx[0]; red[1][ty] = mx[1]; }
+    __syncthreads();
+    if (ty == 0 && lane < 2) {
+      Real r = red[lane][0];
+      for (int q = 1; q < T2_R; q++) r = rmax(r, red[lane][q]);
+      if (r == r) atomicMax(&sc->max_v[lane], (unsigned long long)__double_as_longlong(r));
+    }
+  }
+}
+
+// ---- launch wrappers -----------------------------------------------------------------------------------------------------
+static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1)/b); }
+
+int ntiles_2d(const DevGrid &g) { return 2 + (g.Nx1 + 2)/64; }      // the most x1 tiles any of the kernels below launches
+
+void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
+{
+  const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);                     // tile -1 (is-64 .. is-1) and the tiles up to ie+2
+  const int nj = g.Nx2 + 4;
+  if (ntx > 1) hipLaunchKernelGGL(k2d_edge_wl, dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, dt, edge, ntx);
+  hipLaunchKernelGGL(k2d_first, dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, edge);
+}
+void launch_2d_ctu_correct(const DevGrid &g, Real dt, bool hcorr, hipStream_t st)
+{
+  const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
+  hipLaunchKernelGGL(k2d_correct, dim3(ntx, cdiv(g.Nx2 + 4, 4)), dim3(64, 4), 0, st, g, dt, hcorr ? 1 : 0);
+}
+template <int MODE, bool CFL>
+static void launch_step(const DevGrid &g, Real dt, Real c1, Real c2, Real *edge, DevScalars *sc, hipStream_t st)
+{
+  const int X = Range2<MODE>::ext();
+  const int ntx = Range2<MODE>::toff() + (int)cdiv(g.Nx1 + X, 64), nj = g.Nx2 + 2*X;
+  hipLaunchKernelGGL((k2d_edge<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
+  hipLaunchKernelGGL((k2d_step<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, c1, c2, edge, sc);
+}
+void launch_2d_ctu_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
+{
+  if (sc) launch_step<M_CTU2, true>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st);
+  else    launch_step<M_CTU2, false>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, nullptr, st);
+}
+void launch_2d_vl_predict(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
+{ launch_step<M_VL1, false>(g, dt, 0.5*(dt/g.dx[0]), 0.5*(dt/g.dx[1]), edge, nullptr, st); }
+void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
+{
+  if (sc) launch_step<M_VL2, true>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st);
+  else    launch_step<M_VL2, false>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, nullptr, st);
+}
+
+}  // namespace aa

@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) k_rst_gather(DevGrid g, const Real *__res
     const unsigned o = (o0 + q < n) ? o0 + q : n - 1u;
     const unsigned t = i0 + o, r = t/nx1, i = t - r*nx1, row = row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    v[q] = src[(long)(k + AA_NGHOST_)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)];
+    v[q] = src[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)];
   }
   if (o0 + 1u < n) *(double2*)(dst + o0) = make_double2(v[0], v[1]);
   else dst[o0] = v[0];
@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) k_rst_scatter(DevGrid g, Real *__restrict
     if (q && !pair) break;
     const unsigned t = i0 + o0 + q, r = t/nx1, i = t - r*nx1, row = row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    dst[(long)(k + AA_NGHOST_)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)] = v[q];
+    dst[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)] = v[q];
   }
 }
 
@@ -187,7 +187,7 @@ static int rst_box_grid(aa_grid *g, int section, const int lo[3], const int nb[3
   } else {
     sJ = g->d.sJ; sK = g->d.sK;
     base = g->d.U + (size_t)rst_section_var(g, section)*(size_t)g->d.nc
-         + (long)(lo[2] + AA_NGHOST_)*sK + (long)(lo[1] + AA_NGHOST_)*sJ + (long)(lo[0] + AA_NGHOST_);
+         + (long)(lo[2] + g->d.ks)*sK + (long)(lo[1] + AA_NGHOST_)*sJ + (long)(lo[0] + AA_NGHOST_);
   }
   const unsigned n1 = (unsigned)nb[0], n2 = (unsigned)nb[1];
   const long long nrows = (long long)nb[1]*nb[2];

@@ -332,6 +332,7 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels)
       mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: grids must come level by level from the root (grid %d)", l); return nullptr; }
     if (!g->slab.empty()) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is cut into slabs (aa_params.nslab / AA_NGPU): nested levels stay on one device", l); return nullptr; }
     if (g->p.device != levels[0]->p.device) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: all levels must live on one device"); return nullptr; }
+    if (g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is a 2-D Grid: static mesh refinement is 3-D only here", l); return nullptr; }
     if (g->fofc) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] has first-order flux correction on (aa_set_fofc): not available on the Grids of a Mesh", l); return nullptr; }
     m->lev[l] = g; m->box[l] = nullptr; m->par[l] = l;
     g->keep_flux = true;

@@ -149,6 +149,13 @@ class HipEngine:
     def close(self): self.g.close()
 
 
+def _active(U: np.ndarray) -> np.ndarray:
+    """the active zones of a host block [N3][N2][N1][nvar]; a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1)"""
+    ng = config.NGHOST
+    k = slice(ng, -ng) if U.shape[0] > 1 else slice(None)
+    return U[k, ng:-ng, ng:-ng]
+
+
 def _fires(out, level: int, domain: int = 0) -> bool:
     """whether an <outputN> block asks for this Domain (level / domain = -1: all of them; output.c:509-560)"""
     return out.level in (-1, level) and out.domain in (-1, domain)
@@ -188,6 +195,7 @@ class _Runner:
         if integrator not in ("ctu", "vl", "ctu-noh"):
             raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
         run.integrator, run.order = integrator, order
+        config.check_2d(run)
         return head0, par, run
 
     def _read_rank_file(self, head0, nxs, per_level: bool):
@@ -233,8 +241,7 @@ class _Runner:
     def _host_state(self, *level):
         """(U of the active zones, EdgeFlux or None) from the host block of an engine that has no write_rst_payload: what
         restart.write_grid_sections takes.  level: none for Driver's engine, (l,) for MeshDriver's."""
-        ng = config.NGHOST
-        U = self.eng.download(*level)[ng:-ng, ng:-ng, ng:-ng, :5 + self.run.nscal]
+        U = _active(self.eng.download(*level))[..., :5 + self.run.nscal]
         ef = None
         if self.run.ion:
             edgeflux = getattr(self.eng, "edgeflux" if level else "download_edgeflux", None)
@@ -285,6 +292,7 @@ class Driver(_Runner):
         if p2 < 1 or nranks % p2:
             raise ValueError(f"{nranks} ranks cannot be dealt {p2} along x2")
         config.check_fofc(run, nranks)      # (ParError: first-order flux correction is a single-Grid feature)
+        config.check_2d(run, nranks)      # (ParError: a 2-D run is one Grid on one rank)
         self.fofc_trace: List[Tuple[int, int, int]] = []    # run.fofc: (zones with d < 0, with P < 0, fluxes replaced) of every step
         self.grid = pencil(run, rank, p2, nranks // p2)
         self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict, initial=initial)
@@ -359,7 +367,8 @@ class Driver(_Runner):
         """of the root Domain, from its edges: not always the double that Nx * dx gives (_Runner._domain_volume)"""
         vol = 1.0
         for d in range(3):
-            vol *= self.run.xmax[d] - self.run.xmin[d]
+            if d == 0 or self.run.rootNx[d] > 1:      # dump_history.c:316-321: a direction with one zone does not count
+                vol *= self.run.xmax[d] - self.run.xmin[d]
         return vol
 
     # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
@@ -372,8 +381,7 @@ class Driver(_Runner):
         if hasattr(self.eng, "write_dump"):
             self.eng.write_dump(path, out.out_fmt, out.prim, self.time, self.dt)
         else:                                     # an engine without a device: the same payload from its host block
-            ng = config.NGHOST
-            U = self.eng.download()[ng:-ng, ng:-ng, ng:-ng]
+            U = _active(self.eng.download())
             dumps.write_dump_from_block(path, out.out_fmt, U, prim=out.prim, gamma=r.gamma, nscal=r.nscal, nx=g.Nx,
                                         minx=g.MinX, dx=r.dx, time=self.time, dt=self.dt)
 
@@ -829,6 +837,7 @@ class MeshDriver(_Runner):
         """initial = False: the product engine skips the problem generator (from_restart loads the state)"""
         self.run, self.rank, self.nranks = run, rank, nranks
         config.check_fofc(run, nranks, mesh=True)
+        config.check_2d(run, nranks, mesh=True)
         self.cfg = config.mesh_slabs(par, run, rank, nranks, cuts)
         self.domains = config.levels(par, run)            # the whole Domain of every level (history: its volume)
         self.level_nx1 = [g.Nx[0] for g in self.domains]  # zones along the rays of every level (x3 slabs keep them)

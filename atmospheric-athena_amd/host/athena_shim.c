@@ -290,6 +290,10 @@ static void ensure_grid(MeshS *pM)
 #endif
     p.integrator = use_vl() ? 1 : (no_h_correction() ? 2 : 0);
     p.order = recon_order();
+    /* the shim hands whole 3-D blocks to and fro (ncell below, the coherence copies): a 2-D Grid, which the library itself takes
+     * since it has the 2-D integrators, stays refused here */
+    if (p.Nx[0] <= 1 || p.Nx[1] <= 1 || p.Nx[2] <= 1)
+      ath_error("[athena_amd]: the drop-in shim is 3-D only: Nx1=%d, Nx2=%d, Nx3=%d\n", p.Nx[0], p.Nx[1], p.Nx[2]);
     CHK(aa_create(&p, &G[l]));
     ncell[l] = (size_t)(PG[l]->Nx[0] + 2*AA_NGHOST)*(PG[l]->Nx[1] + 2*AA_NGHOST)*(PG[l]->Nx[2] + 2*AA_NGHOST);
     host_newer[l] = 1; snap[l] = NULL;

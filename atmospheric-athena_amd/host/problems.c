@@ -18,6 +18,8 @@
 #define MAXR(a,b) (((a) > (b)) ? (a) : (b))
 #define MINR(a,b) (((a) < (b)) ? (a) : (b))
 #define SQR(x) ((x)*(x))
+/* ghost zones along x3: none on a 2-D Grid (Nx3 = 1: ks = ke = 0, init_grid.c:144-174) */
+#define NG3(p) ((p)->Nx[2] > 1 ? NG : 0)
 
 static void centre(const aa_params *p, int i, int j, int k, double x[3])   /* cc_pos.c:36-43 */
 {
@@ -25,7 +27,7 @@ static void centre(const aa_params *p, int i, int j, int k, double x[3])   /* cc
   for (d = 0; d < 3; d++) dx[d] = (p->xmax[d] - p->xmin[d])/(double)p->rootNx[d]/(double)(1 << p->level);   /* init_mesh.c:225,245 */
   x[0] = p->MinX[0] + ((double)(i - NG) + 0.5)*dx[0];
   x[1] = p->MinX[1] + ((double)(j - NG) + 0.5)*dx[1];
-  x[2] = p->MinX[2] + ((double)(k - NG) + 0.5)*dx[2];
+  x[2] = p->MinX[2] + ((double)(k - NG3(p)) + 0.5)*dx[2];
 }
 
 static double *cell(const aa_params *p, double *U, int i, int j, int k)
@@ -145,7 +147,7 @@ int aa_problem_blast(const aa_params *p, double radius, double pamb, double damb
   int i, j, k;
   if (p->nscal != 0) return -1;
 #pragma omp parallel for private(i, j)
-  for (k = NG; k < NG + p->Nx[2]; k++) for (j = NG; j < NG + p->Nx[1]; j++) for (i = NG; i < NG + p->Nx[0]; i++) {
+  for (k = NG3(p); k < NG3(p) + p->Nx[2]; k++) for (j = NG; j < NG + p->Nx[1]; j++) for (i = NG; i < NG + p->Nx[0]; i++) {
     double *u = cell(p, U, i, j, k), x[3], rad, P, d;
     centre(p, i, j, k, x);
     rad = sqrt(x[0]*x[0] + x[1]*x[1] + x[2]*x[2]);
@@ -161,7 +163,7 @@ int aa_problem_blast(const aa_params *p, double radius, double pamb, double damb
 int aa_problem_shkset1d(const aa_params *p, const double *wl, const double *wr, int shk_dir, double *U)
 {
   const double Gamma_1 = p->gamma - 1.0;
-  const int N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG, N3 = p->Nx[2] + 2*NG;
+  const int N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG, N3 = p->Nx[2] + 2*NG3(p);
   double c[2][5];
   int i, j, k, side;
   if (p->nscal != 0 || shk_dir < 1 || shk_dir > 3) return -1;

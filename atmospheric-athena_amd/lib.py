@@ -96,7 +96,8 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_set_pinned_cells": (I, [P, LL, llp, dp]), "aa_apply_pinned_cells": (I, [P]),
         "aa_add_radplane_3d": (I, [P, I, D]), "aa_has_radplane": (I, [P]),
         "aa_bvals_mhd": (I, [P]), "aa_bvals_mhd_side": (I, [P, I, I]), "aa_bvals_ionrad": (I, [P]), "aa_new_dt": (I, [P]),
-        "aa_integrate_3d_ctu": (I, [P]), "aa_integrate_begin": (I, [P]), "aa_cfl_in_update": (I, [P, I]), "aa_integrate_3d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
+        "aa_integrate_3d_ctu": (I, [P]), "aa_integrate_begin": (I, [P]), "aa_cfl_in_update": (I, [P, I]), "aa_integrate_3d_vl": (I, [P]),
+        "aa_integrate_2d_ctu": (I, [P]), "aa_integrate_2d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
         "aa_start": (I, [P]), "aa_step": (I, [P, ip]),
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
         "aa_ion_update": (I, [P, D, llp, dp]),
@@ -192,7 +193,9 @@ class Grid:
         self.L = load(strict)
         self.params = params_from_grid(grid, device, ion_path, nslab)
         self.nvar = 5 + grid.run.nscal
-        self.N = tuple(n + 2 * NGHOST for n in grid.Nx)          # (N1, N2, N3)
+        # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, init_grid.c:144-174)
+        self.N = tuple(n + 2 * NGHOST if n > 1 else 1 for n in grid.Nx)
+        self.ndim = sum(1 for n in grid.Nx if n > 1)
         h = C.c_void_p()
         self._h = None
         self._chk(self.L.aa_create(C.byref(self.params), C.byref(h)))
@@ -290,13 +293,18 @@ class Grid:
 
     def integrate_3d_ctu(self): self._chk(self.L.aa_integrate_3d_ctu(self._h))
     def integrate_3d_vl(self): self._chk(self.L.aa_integrate_3d_vl(self._h))
+    def integrate_2d_ctu(self): self._chk(self.L.aa_integrate_2d_ctu(self._h))
+    def integrate_2d_vl(self): self._chk(self.L.aa_integrate_2d_vl(self._h))
     def integrate_begin(self): self._chk(self.L.aa_integrate_begin(self._h))
     def ion_speculate(self, limit: float): self._chk(self.L.aa_ion_speculate(self._h, float(limit)))
     def cfl_in_update(self, on: bool = True): self._chk(self.L.aa_cfl_in_update(self._h, 1 if on else 0))
 
     def integrate(self):
         """(*Integrate)(pD): the function pointer integrate_init() selected (integrate.c:63-75)."""
-        if self.cfg.run.integrator == "vl":
+        vl = self.cfg.run.integrator == "vl"
+        if self.ndim == 2:                                      # integrate.c:49-58
+            self.integrate_2d_vl() if vl else self.integrate_2d_ctu()
+        elif vl:
             self.integrate_3d_vl()
         else:
             self.integrate_3d_ctu()

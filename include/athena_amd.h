@@ -24,7 +24,9 @@ enum { AA_NGHOST = 4 };                     /* defs.h.in:129-140 */
 enum { AA_BC_NONE = 0, AA_BC_REFLECT = 1, AA_BC_OUTFLOW = 2, AA_BC_PERIODIC = 4 }; /* bvals_mhd.c:560-586 */
 
 typedef struct aa_params {
-  int    Nx[3];            /* active zones of this Grid (all > 1: 3-D only)                     */
+  int    Nx[3];            /* active zones of this Grid: all > 1 (3-D), or Nx[2] == 1 with
+                              Nx[0], Nx[1] > 1 (2-D: no ghost zones along x3, host block
+                              U[1][Nx2+8][Nx1+8], init_grid.c:144-174); 1-D Grids are refused     */
   int    rootNx[3];        /* active zones of the root Domain                                   */
   double xmin[3], xmax[3]; /* root Domain extent; dx = (xmax-xmin)/rootNx (init_mesh.c:225)     */
   double MinX[3];          /* lower edge of this Grid (init_grid.c:104-111)                     */
@@ -128,6 +130,12 @@ int aa_bvals_ionrad(aa_grid *g);                    /* bvals_ionrad.c:63        
 int aa_new_dt(aa_grid *g);                          /* new_dt.c:32                                */
 int aa_integrate_3d_ctu(aa_grid *g);                /* integrate_3d_ctu.c:110, dt = Grid dt       */
 int aa_integrate_3d_vl(aa_grid *g);                 /* integrate_3d_vl.c:96 (NO_H_CORRECTION)     */
+/* A 2-D Grid (Nx[2] == 1; integrate.c:49-58 picks these by dimension, and so do aa_start / aa_step): HYDRO, ADIABATIC, second
+ * order, no gravity / cooling / scalars / ion radiation / fofc / Mesh / slabs (each refused with a message: no reference target pins
+ * them in 2-D).  cour_no may exceed 0.5 with the CTU integrator, not with van Leer (integrate.c:55-57).  The 3-D entry points
+ * return an error on a 2-D Grid and these on a 3-D one.                                                                        */
+int aa_integrate_2d_ctu(aa_grid *g);                /* integrate_2d_ctu.c (integrator 0: + H-correction, 2: without) */
+int aa_integrate_2d_vl(aa_grid *g);                 /* integrate_2d_vl.c (NO_H_CORRECTION)        */
 int aa_ion_radtransfer_3d(aa_grid *g, int *niter);  /* ionrad_3d.c:862; may shrink the Grid dt    */
 int aa_start(aa_grid *g);                           /* main.c:412-451: bvals, bvals_ionrad, new_dt */
 int aa_step(aa_grid *g, int *niter);                /* one pass of main.c:519-669                 */
