@@ -274,6 +274,27 @@ def levels(par: ParTable, run: RunConfig) -> List[GridConfig]:
     touch (:398-418), so every Domain lies in ONE Domain of the level below."""
     nd = par.geti_def("job", "num_domains", 1)
     check_2d(run, mesh=nd > 1)
+    return _levels(par, run, 3)
+
+
+def levels_2d(par: ParTable, run: RunConfig) -> List[GridConfig]:
+    """config.levels for a 2-D refined deck (root Nx3 = 1; the reference's tst/2D-hydro/athinput.blast has three levels): the
+    same Domains in the same order, nested by the rules of init_mesh.c:320-499 in x1 and x2.  Every child has Nx3 = 1
+    (init_mesh.c:300-305) and kDisp = 0 (:355-360 never reads it on a 2-D Mesh; a deck that sets it means something else).
+    One process, one device: lib.Mesh / driver.MeshRun; the reference's SMR builds are CTU with H-correction and van Leer."""
+    if run.ndim != 2:
+        raise ParError("[config]: levels_2d takes a 2-D run (Nx3 = 1); a 3-D refined deck goes through config.levels")
+    check_2d(run)
+    nd = par.geti_def("job", "num_domains", 1)
+    if nd > 1 and run.integrator == "ctu-noh":
+        raise ParError("[config]: static mesh refinement on a 2-D Grid with CTU without H-correction: no reference build pins it")
+    return _levels(par, run, 2)
+
+
+def _levels(par: ParTable, run: RunConfig, ndim: int) -> List[GridConfig]:
+    """ndim: the directions with more than one zone (3, or 2 with Nx3 = 1: the rules hold in those only, init_mesh.c:321, :363)"""
+    nd = par.geti_def("job", "num_domains", 1)
+    D = range(ndim)
     doms = sorted((par.geti(f"domain{n}", "level"), n) for n in range(1, nd + 1))
     levs = sorted({lev for lev, _ in doms})
     if levs != list(range(len(levs))) or sum(1 for lev, _ in doms if lev == 0) != 1:
@@ -285,24 +306,29 @@ def levels(par: ParTable, run: RunConfig) -> List[GridConfig]:
         irefine = 2 ** lev
         Nx = tuple(par.geti(blk, f"Nx{d}") for d in (1, 2, 3))
         disp = tuple(par.geti(blk, k) for k in ("iDisp", "jDisp", "kDisp"))
-        for d in range(3):
+        if ndim == 2:
+            if Nx[2] != 1 or min(Nx[:2]) <= 1:
+                raise ParError("[init_mesh]: in %s grid is %dD, but in root level it is 2D" % (blk, sum(1 for n in Nx if n > 1)))
+            if disp[2] != 0:
+                raise ParError(f"[init_mesh]: {blk}/kDisp = {disp[2]} on a 2-D Mesh (Nx3 = 1): must be 0")
+        for d in D:
             if Nx[d] % irefine:
                 raise ParError(f"[init_mesh]: {blk}/Nx{d + 1} = {Nx[d]} must be divisible by {irefine}")
             if disp[d] % irefine:
                 raise ParError(f"[init_mesh]: {blk}/Disp{d + 1} = {disp[d]} must be divisible by {irefine}")
         # init_mesh.c:398-418: Domains on the same level may neither overlap nor touch
         for g, (o, sz) in zip(out, ext):
-            if g.level == lev and all(disp[d] <= o[d] + sz[d] and o[d] <= disp[d] + Nx[d] for d in range(3)):
+            if g.level == lev and all(disp[d] <= o[d] + sz[d] and o[d] <= disp[d] + Nx[d] for d in D):
                 raise ParError(f"[init_mesh]: Domains at level {lev} overlap or touch ({blk})")
         # init_mesh.c:320-360, :448-470: inside ONE Domain of the level below; it may touch its edge only where that is the root boundary
         parent = None
         for g, (o, sz) in zip(out, ext):
-            if g.level == lev - 1 and all(disp[d] // 2 >= o[d] and (disp[d] + Nx[d]) // 2 <= o[d] + sz[d] for d in range(3)):
+            if g.level == lev - 1 and all(disp[d] // 2 >= o[d] and (disp[d] + Nx[d]) // 2 <= o[d] + sz[d] for d in D):
                 parent = (o, sz)
         if parent is None:
             raise ParError(f"[init_mesh]: {blk} is not inside the Domain of level {lev - 1}")
         pdisp, pNx = parent
-        for d in range(3):
+        for d in D:
             lo, hi = disp[d] // 2, (disp[d] + Nx[d]) // 2
             if (lo == pdisp[d] and disp[d] != 0) or \
                (hi == pdisp[d] + pNx[d] and (disp[d] + Nx[d]) // irefine != run.rootNx[d]):
@@ -313,7 +339,7 @@ def levels(par: ParTable, run: RunConfig) -> List[GridConfig]:
         dxl = tuple(run.dx[d] / float(irefine) for d in range(3))
         MinX = tuple(run.xmin[d] if disp[d] == 0 else run.xmin[d] + float(disp[d]) * dxl[d] for d in range(3))
         bc = list(run.bc)
-        for d in range(3):
+        for d in D:
             if disp[d] != 0:
                 bc[2 * d] = 0
             if (disp[d] + Nx[d]) // irefine != run.rootNx[d]:

@@ -90,7 +90,6 @@ int aa_create(const aa_params *p, aa_grid **out)
     if (p->ion) return fail(-1, "[aa_create]: ion radiation on a 2-D Grid: the reference has ionrad_3d only");
     if (p->nscal != 0) return fail(-1, "[aa_create]: passive scalars on a 2-D Grid: no reference target pins them (NSCALARS must be 0)");
     if (p->order == 3) return fail(-1, "[aa_create]: third-order reconstruction on a 2-D Grid: no reference target pins it");
-    if (p->level != 0) return fail(-1, "[aa_create]: a 2-D Grid cannot be a level of a refined Mesh (level %d)", p->level);
     int ns = p->nslab;
     if (ns == 0) { const char *e = getenv("AA_NGPU"); if (e) ns = atoi(e); }
     if (ns > 1) return fail(-1, "[aa_create]: a 2-D Grid cannot be cut into x3 slabs (nslab / AA_NGPU = %d)", ns);
@@ -159,6 +158,7 @@ int aa_create(const aa_params *p, aa_grid **out)
   for (int a = 0; a < 3; a++) {
     rootdx[a] = (p->xmax[a] - p->xmin[a])/(Real)(p->rootNx[a]);   // init_mesh.c:225
     d.dx[a] = rootdx[a]/(Real)(1 << p->level);                    // :245
+    if (two_d && a == 2) d.dx[a] = rootdx[a];                     // :331-337: a direction with one zone keeps the root's extent
   }
   d.Gamma = p->gamma; d.Gamma_1 = p->gamma - 1.0; d.rGamma_1 = 1.0/d.Gamma_1;
   // one pool: U 6 | LR 36 | F 18 | eta 3 | dhalf 1 | phi 4 | ion 5 + sign(1) | edgeflux

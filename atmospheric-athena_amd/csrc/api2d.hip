@@ -30,7 +30,9 @@ int aa_integrate_2d_ctu(aa_grid *g)
   { Scope s(g, "ctu2d_correct"); launch_2d_ctu_correct(d, dt, g->p.integrator == 0, g->st); }
   { Scope s(g, "ctu2d_flux2_update");
     cfl_arm_2d(g);
-    launch_2d_ctu_flux2_update(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->st); }
+    // (a level of a Mesh: the instantiation that also leaves the second-pass fluxes on the level-boundary lines in F)
+    if (g->keep_flux) launch_2d_ctu_flux2_update_keep(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->keep, g->st);
+    else launch_2d_ctu_flux2_update(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->st); }
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -44,7 +46,8 @@ int aa_integrate_2d_vl(aa_grid *g)
   { Scope s(g, "vl2d_predict"); launch_2d_vl_predict(d, dt, g->edge2d, g->st); }
   { Scope s(g, "vl2d_flux2_update");
     cfl_arm_2d(g);
-    launch_2d_vl_flux2_update(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->st); }
+    if (g->keep_flux) launch_2d_vl_flux2_update_keep(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->keep, g->st);
+    else launch_2d_vl_flux2_update(d, dt, g->edge2d, g->cfl_ready ? g->sc : nullptr, g->st); }
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -140,6 +140,13 @@ int aa_edgeflux_ready(aa_grid *g);    // fill GridS.EdgeFlux from the buffers of
 extern "C" int aa_download_cons_planes(aa_grid *g, int k_first, int nplanes, double *dst);
 extern "C" int aa_download_edgeflux_planes(aa_grid *g, int nplanes, double *dst);
 
+// hydro2d_kernels.hip: the update kernels of a 2-D Grid that is a level of a Mesh -- k2d_step<CTU2 | VL2> instantiated to also store the
+// second-pass fluxes of the faces on the lines of `kp` into F (global momentum order; smr.hip k2d_flux_correct reads them)
+namespace aa {
+void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
+void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
+}
+
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }
 static inline unsigned long long double_to_bits(double x) { unsigned long long b; memcpy(&b, &x, 8); return b; }
 extern "C" int aa_fetch_scalars(aa_grid *g);     // DevScalars device -> pinned host, synchronous

@@ -20,6 +20,8 @@
 //
 // CTU: k2d_edge_wl, k2d_first, k2d_correct, k2d_edge<CTU2>, k2d_step<CTU2>   (3 launches + 2 side kernels)
 // VL : k2d_edge<VL1>, k2d_step<VL1>, k2d_edge<VL2>, k2d_step<VL2>            (2 launches + 2 side kernels)
+// A level of a Mesh (csrc/smr.hip, aa_mesh_create_2d) takes k2d_step_keep<CTU2 | VL2> in place of k2d_step: the same body, which
+// also stores the second-pass fluxes of the faces on the level-boundary lines into F for the flux correction.
 #include <hip/hip_runtime.h>
 #include "grid.h"
 #include "hydro_dev.h"
@@ -274,9 +276,21 @@ AA_DEV void cfl_zone2(Real d, Real m1, Real m2, Real m3, Real e, Real Gamma, Rea
 
 // fluxes of the two lower faces + update of the zone (+ new_dt's maxima): U^{n+1/2} of the van Leer predictor (M_VL1, c = dt/2dx,
 // written to LR), the full update of either integrator (c = dt/dx, U in place; x1 differences first, then x2: Steps 12a-b / 13)
-template <int MODE, bool CFL>
-__global__ void __launch_bounds__(T2_W*T2_R)
-k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
+// KEEP (a level of a Mesh, csrc/smr.hip): the fluxes of the faces on the lines of `kp` -- the Grid's own boundary and the outline of
+// its children -- also go to the flux family F, in the GLOBAL momentum order of the reference's myFlx (integrate_2d_ctu.c:1722-1877:
+// x1 faces M1, M2, M3 = Mx, My, Mz; x2 faces Mz, Mx, My).  F is free here: k2d_correct has consumed the first-pass fluxes, and the
+// van Leer integrator never uses it.  Every face of [is, ie+1] x [js, je] (x1) and [is, ie] x [js, je+1] (x2) is computed by some
+// thread of this launch: the x1 face above a tile's last lane arrives from the tile-edge path and is stored by that lane, and the
+// rows the halo wavefront solves for the block above are stored by both (the same bits).
+AA_DEV bool on_kept_line(const KeepPlanes &kp, int d, int x)
+{
+  bool hit = false;
+#pragma unroll
+  for (int q = 0; q < 8; q++) hit = hit || kp.p[d][q] == x;
+  return hit;
+}
+template <int MODE, bool CFL, bool KEEP>
+AA_DEV void step_body(const DevGrid &g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc, const KeepPlanes *kp)
 {
   __shared__ Real sh[5][T2_R][T2_W];
   __shared__ Real red[2][T2_R];
@@ -292,6 +306,12 @@ k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
   face_flux<MODE, 1>(g, ic, clampi(j, lo_j, hi_j + 1), dt, f2);
 #pragma unroll
   for (int v = 0; v < 5; v++) sh[v][ty][lane] = f2[v];
+  if (KEEP) {
+    if (i >= lo_i && i <= hi_i && j <= hi_j + 1 && on_kept_line(*kp, 1, j)) {
+      const long m = (long)j*g.sJ + i;
+      F2(g, 1, 0)[m] = f2[0]; F2(g, 1, 1)[m] = f2[3]; F2(g, 1, 2)[m] = f2[1]; F2(g, 1, 3)[m] = f2[2]; F2(g, 1, 4)[m] = f2[4];
+    }
+  }
   const bool zone = ty < T2_R - 1 && i >= lo_i && i <= hi_i && j <= hi_j;
   if (ty < T2_R - 1) {                                             // (uniform per wavefront)
     face_flux<MODE, 0>(g, clampi(i, lo_i, hi_i + 1), jc, dt, f1);
@@ -301,6 +321,13 @@ k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
       const long es = (long)gridDim.x*g.N2;
 #pragma unroll
       for (int v = 0; v < 5; v++) f1p[v] = edge[v*es + (long)blockIdx.x*g.N2 + j];
+    }
+    if (KEEP) {
+      if (j <= hi_j) {
+        const long m = (long)j*g.sJ + i;
+        if (i >= lo_i && i <= hi_i + 1 && on_kept_line(*kp, 0, i)) store5(F2(g, 0, 0), g.nc, m, f1);
+        if (lane == 63 && zone && on_kept_line(*kp, 0, i + 1)) store5(F2(g, 0, 0), g.nc, m + 1, f1p);
+      }
     }
   }
   __syncthreads();
@@ -340,6 +367,14 @@ k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
     }
   }
 }
+template <int MODE, bool CFL>
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
+{ step_body<MODE, CFL, false>(g, dt, c1, c2, edge, sc, nullptr); }
+template <int MODE, bool CFL>
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_step_keep(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc, KeepPlanes kp)
+{ step_body<MODE, CFL, true>(g, dt, c1, c2, edge, sc, &kp); }
 
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1)/b); }
@@ -365,6 +400,24 @@ static void launch_step(const DevGrid &g, Real dt, Real c1, Real c2, Real *edge,
   const int ntx = Range2<MODE>::toff() + (int)cdiv(g.Nx1 + X, 64), nj = g.Nx2 + 2*X;
   hipLaunchKernelGGL((k2d_edge<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
   hipLaunchKernelGGL((k2d_step<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, c1, c2, edge, sc);
+}
+// the keeping form (KEEP above), for the levels of a Mesh; the side kernel is the same
+template <int MODE, bool CFL>
+static void launch_step_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{
+  const int ntx = (int)cdiv(g.Nx1, 64), nj = g.Nx2;
+  hipLaunchKernelGGL((k2d_edge<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_keep<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, kp);
+}
+void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{
+  if (sc) launch_step_keep<M_CTU2, true>(g, dt, edge, sc, kp, st);
+  else    launch_step_keep<M_CTU2, false>(g, dt, edge, nullptr, kp, st);
+}
+void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{
+  if (sc) launch_step_keep<M_VL2, true>(g, dt, edge, sc, kp, st);
+  else    launch_step_keep<M_VL2, false>(g, dt, edge, nullptr, kp, st);
 }
 void launch_2d_ctu_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
 {

@@ -15,6 +15,10 @@
 //
 // Summation orders follow the reference term by term, so the strict (-ffp-contract=off) build
 // reproduces the CPU results bit for bit.
+//
+// A Mesh of 2-D Grids (Nx3 = 1 on every level; aa_mesh_create_2d) runs the same host control flow on kernels of its own --
+// k2d_restrict, k2d_flux_correct, k2d_box_copy, k2d_prolong: the nDim == 2 branches of smr.c -- and the 2-D integrators, whose
+// update kernel leaves the fluxes of the level-boundary lines in F (hydro2d_kernels.hip k2d_step_keep; integrate_2d_ctu.c:1722-1877).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -240,6 +244,128 @@ k_flux_x3_apply(DevGrid c, int side, int i0, int j0, int n1, int n2, int nvar, R
     fld(c, c.U, v)[mc] -= q*(fld(c, c.F, 2*6 + v)[mf] - buf[(long)lin*6 + v]);
 }
 
+// ---- 2-D Grids (Nx3 = 1; aa_mesh_create_2d): one plane per field, five fields, the flux family F as [dir][5] with the kept
+// second-pass fluxes in the global momentum order (hydro2d_kernels.hip k2d_step_keep).  A block is S2_R wavefronts of 64 lanes
+// along x1; every kernel touches an outline or a ghost shell only, and none needs an atomic or LDS. ------------------------------
+#define S2_W 64
+#define S2_R 4
+
+// restriction: 2x2 fine zones -> one parent zone.  smr.c Step 3a on a 2-D Grid: the pair of the lower row, plus the pair of the
+// upper row, times 0.25 (the x3 pass is skipped: Nx[2] = 1)
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_restrict(DevGrid f, DevGrid c, Link L)
+{
+  const int a = (int)blockIdx.x*S2_W + (int)threadIdx.x, b = (int)blockIdx.y*S2_R + (int)threadIdx.y;
+  if (a >= L.n[0] || b >= L.n[1]) return;
+  const long mc = (long)(L.cs[1] + b)*c.sJ + (L.cs[0] + a);
+  const long mf = (long)(f.js + 2*b)*f.sJ + (f.is + 2*a);
+#pragma unroll
+  for (int v = 0; v < 5; v++) {
+    const Real *q = fld(f, f.U, v) + mf;
+    Real s = q[0] + q[1];
+    s += q[f.sJ] + q[f.sJ + 1];
+    s *= 0.25;
+    fld(c, c.U, v)[mc] = s;
+  }
+}
+
+// flux correction of the parent zones just outside the child (smr.c Step 2a); the child's flux through a parent face is the sum
+// of its two faces times 0.5 (Step 3c with nDim = 2).  One thread per parent face of a side; dim_arg < 0: the four sides in one
+// launch, side = blockIdx.y (they correct disjoint parent zones)
+__global__ void __launch_bounds__(S2_W)
+k2d_flux_correct(DevGrid f, DevGrid c, Link L, int dim_arg, Real dt)
+{
+  const int dim = (dim_arg >= 0) ? dim_arg : (int)blockIdx.y;
+  if (dim_arg < 0 && !L.corr[dim]) return;
+  const int d = dim >> 1, t = 1 - d;
+  const int a = (int)blockIdx.x*S2_W + (int)threadIdx.x;
+  if (a >= L.n[t]) return;
+  const long sc[2] = {1, c.sJ}, sf[2] = {1, f.sJ};
+  const int flo[2] = {f.is, f.js}, fhi[2] = {f.ie, f.je};
+  int ic[2]; ic[t] = L.cs[t] + a;
+  Real q;
+  if (dim & 1) { ic[d] = L.ce[d] + 1; q =  (dt/c.dx[d]); }
+  else         { ic[d] = L.cs[d] - 1; q = -(dt/c.dx[d]); }
+  const long mcell = ic[1]*sc[1] + ic[0];
+  ic[d] = (dim & 1) ? L.ce[d] + 1 : L.cs[d];
+  const long mface_c = ic[1]*sc[1] + ic[0];
+  int jf[2]; jf[t] = flo[t] + 2*a; jf[d] = (dim & 1) ? fhi[d] + 1 : flo[d];
+  const long mface_f = jf[1]*sf[1] + jf[0];
+#pragma unroll
+  for (int v = 0; v < 5; v++) {
+    const Real mine = fld(c, c.F, d*5 + v)[mface_c];
+    const Real *qf = fld(f, f.F, d*5 + v) + mface_f;
+    Real fine = qf[0] + qf[sf[t]];
+    fine *= 0.5;
+    fld(c, c.U, v)[mcell] -= q*(mine - fine);
+  }
+}
+
+// snapshot of the parent zones cs-3 .. ce+3 around the child in x1 and x2, taken when the parent "sends" (smr.c Step 1 of Prolongate)
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_box_copy(DevGrid c, Link L, Real *box)
+{
+  const int b0 = L.n[0] + 6, b1 = L.n[1] + 6;
+  const int i = (int)blockIdx.x*S2_W + (int)threadIdx.x, j = (int)blockIdx.y*S2_R + (int)threadIdx.y;
+  if (i >= b0 || j >= b1) return;
+  const long nb = (long)b0*b1;
+  const long m = (long)(L.cs[1] - 3 + j)*c.sJ + (L.cs[0] - 3 + i);
+#pragma unroll
+  for (int v = 0; v < 5; v++) box[(long)v*nb + (long)j*b0 + i] = fld(c, c.U, v)[m];
+}
+
+// one thread = one parent zone under 2x2 ghost zones of the child.  ProCon (smr.c:3068) on a 2-D Grid: the planes below and above
+// are copies of the plane itself (Step 3a, nDim == 2), so the x3 slope is mcd_slope of equal values = 0 and its term -0.25*0 adds
+// nothing; k = 0 only is stored.  The four sides dim < 2*nDim; dim_arg < 0: all in one launch, side = blockIdx.z
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_prolong(DevGrid f, Link L, const Real *box, int dim_arg)
+{
+  const int dim = (dim_arg >= 0) ? dim_arg : (int)blockIdx.z;
+  if (dim_arg < 0 && !L.prol[dim]) return;
+  const int lo[2] = {f.is, f.js}, hi[2] = {f.ie, f.je};
+  int ps[2], cnt[2];
+  for (int d = 0; d < 2; d++) { ps[d] = lo[d] - NG; cnt[d] = (hi[d] - lo[d] + 1 + 2*NG)/2; }
+  if (dim & 1) ps[dim >> 1] = hi[dim >> 1] + 1;
+  cnt[dim >> 1] = NG/2;
+  const int a = (int)blockIdx.x*S2_W + (int)threadIdx.x, b = (int)blockIdx.y*S2_R + (int)threadIdx.y;
+  if (a >= cnt[0] || b >= cnt[1]) return;
+  const int i = ps[0] + 2*a, j = ps[1] + 2*b;                                 // lower fine zone of the 2x2 block
+  const int b0 = L.n[0] + 6;
+  const long nb = (long)b0*(L.n[1] + 6), sb1 = b0;
+  // parent zone in box coordinates: fine lo-4 lies in parent cs-2 = box index 1
+  const long mb = (long)((j - (lo[1] - NG))/2 + 1)*sb1 + ((i - (lo[0] - NG))/2 + 1);
+  Real P[5][4];
+#pragma unroll
+  for (int v = 0; v < 4; v++) {
+    const Real *q = box + (long)v*nb + mb;
+    const Real uc = q[0];
+    const Real dq1 = mcd_slope(q[-1], uc, q[1]);
+    const Real dq2 = mcd_slope(q[-sb1], uc, q[sb1]);
+    for (int jj = 0; jj < 2; jj++) for (int ii = 0; ii < 2; ii++)
+      P[v][jj*2 + ii] = uc + (0.5*ii - 0.25)*dq1 + (0.5*jj - 0.25)*dq2;
+  }
+  {  // the internal energy, not E, is interpolated
+    const Real *qd = box + mb, *q1 = box + nb + mb, *q2 = box + 2*nb + mb, *q3 = box + 3*nb + mb, *qe = box + 4*nb + mb;
+#define EINT(o) (qe[o] - 0.5*(q1[o]*q1[o] + q2[o]*q2[o] + q3[o]*q3[o])/qd[o])
+    const Real Pi = EINT(0);
+    const Real dq1 = mcd_slope(EINT(-1), Pi, EINT(1));
+    const Real dq2 = mcd_slope(EINT(-sb1), Pi, EINT(sb1));
+#undef EINT
+    for (int jj = 0; jj < 2; jj++) for (int ii = 0; ii < 2; ii++) {
+      const int o = jj*2 + ii;
+      Real e = Pi + (0.5*ii - 0.25)*dq1 + (0.5*jj - 0.25)*dq2;
+      e += 0.5*(P[1][o]*P[1][o] + P[2][o]*P[2][o] + P[3][o]*P[3][o])/P[0][o];
+      P[4][o] = e;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < 5; v++) {
+    Real *u = fld(f, f.U, v);
+    for (int jj = 0; jj < 2; jj++) for (int ii = 0; ii < 2; ii++)
+      u[(long)(j + jj)*f.sJ + (i + ii)] = P[v][jj*2 + ii];
+  }
+}
+
 inline unsigned nblk(long n, int b) { return (unsigned)((n + b - 1)/b); }
 
 }  // namespace
@@ -261,6 +387,7 @@ struct aa_mesh {
   // integrates on side[l], forked from and joined to `st` by events (AA_MESH_OVERLAP=0: one after the other on `st`)
   hipStream_t side[AA_MAXLEV] = {nullptr}; hipEvent_t ev_fork = nullptr, ev_join[AA_MAXLEV] = {nullptr}; bool overlap = true;
   bool one_launch = true;          // the six sides of a flux correction / prolongation in one launch each
+  bool two_d = false;              // aa_mesh_create_2d: every level is a 2-D Grid (Nx3 = 1): the k2d_* kernels, the 2-D integrators
   double tcoarse = 0;              // ionrad_3d.c:44
   double time = 0, dt = 0; int nstep = 0;   // MeshS
 };
@@ -292,10 +419,14 @@ static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out)
   }
   for (int l = 0; l + 1 < m->nl; l++) {
     const Link &L = m->link[l];
-    const size_t nb = (size_t)(L.n[0] + 6)*(L.n[1] + 6)*(L.n[2] + 6)*6;
+    const size_t nb = m->two_d ? (size_t)(L.n[0] + 6)*(L.n[1] + 6)*5 : (size_t)(L.n[0] + 6)*(L.n[1] + 6)*(L.n[2] + 6)*6;
     if (hipMalloc(&m->box[l], nb*sizeof(Real)) != hipSuccess) { aa_mesh_destroy(m); return aa_fail(-2, "[aa_mesh_create]: hipMalloc box"); }
     (void)hipMemset(m->box[l], 0, nb*sizeof(Real));
   }
+  // a 2-D Grid's F holds first-pass fluxes of whatever it integrated before: RestrictCorrect of aa_mesh_start / _resume must read
+  // zeros on the kept lines (main.c:401: the reference's myFlx are still empty there, q*(0 - 0))
+  if (m->two_d)
+    for (int l = 0; l < m->nl; l++) (void)hipMemsetAsync(m->lev[l]->d.F, 0, (size_t)10*m->lev[l]->d.nc*sizeof(Real), m->st);
   // the face planes whose second-pass fluxes k_flux_correct / k_flux_x3_export / k_flux_x3_apply read:
   // a level's own boundary faces and the outline of its child
   for (int l = 0; l < m->nl; l++) {
@@ -320,11 +451,11 @@ static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out)
   return 0;
 }
 
-static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels)
+static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels, bool two_d = false)
 {
   if (!levels || nlevels < 1 || nlevels > AA_MAXLEV) { aa_fail(-1, "[aa_mesh_create]: bad arguments"); return nullptr; }
   aa_mesh *m = new aa_mesh();
-  m->nl = nlevels;
+  m->nl = nlevels; m->two_d = two_d;
   for (int l = 0; l < AA_MAXLEV; l++) { m->lev[l] = nullptr; m->box[l] = nullptr; }
   for (int l = 0; l < nlevels; l++) {
     aa_grid *g = levels[l];
@@ -332,7 +463,14 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels)
       mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: grids must come level by level from the root (grid %d)", l); return nullptr; }
     if (!g->slab.empty()) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is cut into slabs (aa_params.nslab / AA_NGPU): nested levels stay on one device", l); return nullptr; }
     if (g->p.device != levels[0]->p.device) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: all levels must live on one device"); return nullptr; }
-    if (g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is a 2-D Grid: static mesh refinement is 3-D only here", l); return nullptr; }
+    if (two_d) {      // aa_mesh_create_2d: what the reference's 2-D SMR targets (CTU + H-correction, van Leer) pin
+      if (!g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] is a 3-D Grid: aa_mesh_create", l); return nullptr; }
+      if (g->p.integrator != levels[0]->p.integrator) {
+        mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] has integrator %d, the root %d: the levels of a Mesh share one integrator", l, g->p.integrator, levels[0]->p.integrator); return nullptr; }
+      if (g->p.integrator == 2) {
+        mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] has integrator = 2 (CTU without H-correction): no reference build with static mesh refinement pins it", l); return nullptr; }
+    } else
+    if (g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is a 2-D Grid: aa_mesh_create_2d (this is the 3-D constructor)", l); return nullptr; }
     if (g->fofc) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] has first-order flux correction on (aa_set_fofc): not available on the Grids of a Mesh", l); return nullptr; }
     m->lev[l] = g; m->box[l] = nullptr; m->par[l] = l;
     g->keep_flux = true;
@@ -342,10 +480,11 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels)
 
 // init_grid.c (overlap tables) + SMR_init (smr.c:2931).  Takes over the levels' streams: all
 // levels run on one stream so that inter-level kernels are ordered without events.
-int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out)
+static int mesh_create_nested(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out, const bool two_d)
 {
+  const int nd = two_d ? 2 : 3;      // directions with more than one zone
   if (!disp || !out) return aa_fail(-1, "[aa_mesh_create]: bad arguments");
-  aa_mesh *m = mesh_alloc(nlevels, levels);
+  aa_mesh *m = mesh_alloc(nlevels, levels, two_d);
   if (!m) return -1;
   for (int c = 1; c < nlevels; c++) {
     const aa_grid *C = m->lev[c];
@@ -355,7 +494,7 @@ int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out
     for (int q = 0; q < c && pi < 0; q++) {
       const aa_grid *Q = m->lev[q];
       bool inside = (Q->level == C->level - 1);
-      for (int d = 0; d < 3 && inside; d++) {
+      for (int d = 0; d < nd && inside; d++) {
         const int dq = Q->level ? disp[3*q + d] : 0;
         if (dc[d]/2 < dq || (dc[d] + C->p.Nx[d])/2 > dq + Q->p.Nx[d]) inside = false;
       }
@@ -369,7 +508,11 @@ int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out
     const int lo[3] = {P->d.is, P->d.js, P->d.ks};
     const int irefine = 1 << C->level;
     const int dp[3] = {P->level ? disp[3*pi] : 0, P->level ? disp[3*pi + 1] : 0, P->level ? disp[3*pi + 2] : 0};
-    for (int d = 0; d < 3; d++) {
+    if (two_d) {      // one plane: nothing along x3 (Link: n = 1, cs = ce = 0, no side)
+      if (dc[2] != 0) { mesh_drop(m); return aa_fail(-1, "[aa_mesh_create_2d]: grid %d has kDisp = %d: a 2-D Domain (Nx3 = 1) has no x3 displacement", c, dc[2]); }
+      L.cs[2] = L.ce[2] = 0; L.n[2] = 1; L.cdisp[2] = 0; L.prol[4] = L.prol[5] = L.corr[4] = L.corr[5] = 0;
+    }
+    for (int d = 0; d < nd; d++) {
       const int a = dc[d]/2 - dp[d], b = (dc[d] + C->p.Nx[d])/2 - dp[d];
       if ((dc[d] & 1) || (C->p.Nx[d] & 1) || a < 0 || b > P->p.Nx[d]) {
         mesh_drop(m); return aa_fail(-1, "[aa_mesh_create]: grid %d is not nested in grid %d along x%d", c, pi, d + 1);
@@ -381,13 +524,17 @@ int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out
       if ((a == 0 && L.prol[2*d]) || (b == P->p.Nx[d] && L.prol[2*d + 1])) {
         mesh_drop(m); return aa_fail(-1, "[init_mesh] child Domain (grid %d) touches its parent in x%d", c, d + 1);
       }
+      // init_mesh.c:484-499: nor closer than nghost/2 parent zones to its edge (the prolongation stencil)
+      if (two_d && ((L.prol[2*d] && 2*a < NG) || (L.prol[2*d + 1] && 2*(P->p.Nx[d] - b) < NG))) {
+        mesh_drop(m); return aa_fail(-1, "[init_mesh] child Domain (grid %d) closer than nghost/2 to its parent in x%d", c, d + 1);
+      }
     }
     // init_mesh.c:398-418: Domains on the same level neither overlap nor touch
     for (int q = 1; q < c; q++) {
       const aa_grid *Q = m->lev[q];
       if (Q->level != C->level) continue;
       bool sep = false;
-      for (int d = 0; d < 3; d++) if (dc[d] > disp[3*q + d] + Q->p.Nx[d] || disp[3*q + d] > dc[d] + C->p.Nx[d]) sep = true;
+      for (int d = 0; d < nd; d++) if (dc[d] > disp[3*q + d] + Q->p.Nx[d] || disp[3*q + d] > dc[d] + C->p.Nx[d]) sep = true;
       if (!sep) { mesh_drop(m); return aa_fail(-1, "[init_mesh]: Domains at the same level overlap or touch (grids %d and %d)", q, c); }
     }
     // ionrad_smr.c:97-98 mixes a parent-local index with the child's root-relative Disp: with a displaced
@@ -405,6 +552,11 @@ int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out
   }
   return mesh_finish(m, levels, out);
 }
+int aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out)
+{ return mesh_create_nested(nlevels, levels, disp, out, false); }
+// the same contract for Grids that are all 2-D (Nx3 = 1): disp[3*l + 2] must be 0, the nesting rules hold in x1 and x2
+int aa_mesh_create_2d(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out)
+{ return mesh_create_nested(nlevels, levels, disp, out, true); }
 
 // One rank's stack of x3 slabs of a Mesh whose levels are all cut at the same planes (multi-GPU
 // SMR).  links[21*l..]: cs[3] (local parent index incl. ghosts), n[3], prol[6], corr[6], cdisp[3]
@@ -472,6 +624,18 @@ int aa_mesh_restrict_correct_pair(aa_mesh *m, int l)      // level l+1 -> level 
   const Link &L = m->link[l];
   const int nvar = 5 + P->p.nscal;
   Scope s(P, "smr_restrict_correct");
+  if (m->two_d) {
+    hipLaunchKernelGGL(k2d_restrict, dim3(nblk(L.n[0], S2_W), nblk(L.n[1], S2_R)), dim3(S2_W, S2_R), 0, m->st, C->d, P->d, L);
+    const int nmax = L.n[0] > L.n[1] ? L.n[0] : L.n[1];
+    const bool any = L.corr[0] || L.corr[1] || L.corr[2] || L.corr[3];
+    if (m->one_launch) {      // the four sides in ONE launch (AA_SMR_ONE_LAUNCH=0: one per side)
+      if (any) hipLaunchKernelGGL(k2d_flux_correct, dim3(nblk(nmax, S2_W), 4), dim3(S2_W), 0, m->st, C->d, P->d, L, -1, (Real)P->dt);
+    } else
+    for (int dim = 0; dim < 4; dim++)
+      if (L.corr[dim]) hipLaunchKernelGGL(k2d_flux_correct, dim3(nblk(L.n[1 - (dim >> 1)], S2_W)), dim3(S2_W), 0, m->st, C->d, P->d, L, dim, (Real)P->dt);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   hipLaunchKernelGGL(k_restrict, dim3(nblk((long)L.n[0]*L.n[1]*L.n[2], 256)), dim3(256), 0, m->st,
                      C->d, P->d, L, (1u << nvar) - 1u);
   if (m->one_launch) {      // the six sides in ONE launch (AA_SMR_ONE_LAUNCH=0: one per side)
@@ -503,6 +667,7 @@ int aa_mesh_restrict_correct(aa_mesh *m)
 // smr.c:85: E and s[0] only, after the radiation step
 int aa_mesh_ionrad_restrict_correct(aa_mesh *m)
 {
+  if (m->two_d) return aa_fail(-1, "[aa_mesh_ionrad_restrict_correct]: a Mesh of 2-D Grids has no ion radiation (the reference has ionrad_3d only)");
   for (int l = 0; l < m->nl; l++) m->lev[l]->active_dirty = true;
   for (int q = 0; q + 1 < m->nl; q++) {
     const int l = m->f2c[q];
@@ -523,6 +688,10 @@ int aa_mesh_prolongate(aa_mesh *m)
     for (int c = 0; c + 1 < m->nl; c++) {      // Step 1: hand the zones around every child over
       if (m->par[c] != l) continue;
       const Link &L = m->link[c];
+      if (m->two_d) {
+        hipLaunchKernelGGL(k2d_box_copy, dim3(nblk(L.n[0] + 6, S2_W), nblk(L.n[1] + 6, S2_R)), dim3(S2_W, S2_R), 0, m->st, m->lev[l]->d, L, m->box[c]);
+        continue;
+      }
       const long nb = (long)(L.n[0] + 6)*(L.n[1] + 6)*(L.n[2] + 6);
       hipLaunchKernelGGL(k_box_copy, dim3(nblk(nb, 256)), dim3(256), 0, m->st, m->lev[l]->d, L, m->box[c]);
     }
@@ -531,6 +700,18 @@ int aa_mesh_prolongate(aa_mesh *m)
       const Link &L = m->link[l - 1];
       const int nvar = 5 + C->p.nscal;
       Scope s(C, "smr_prolongate");
+      if (m->two_d) {      // the sides dim < 2*nDim (smr.c:2560); a side's region spans the other direction's ghost zones too
+        const int c0 = (C->p.Nx[0] + 2*NG)/2, c1 = (C->p.Nx[1] + 2*NG)/2;
+        const bool any = L.prol[0] || L.prol[1] || L.prol[2] || L.prol[3];
+        if (m->one_launch) {
+          if (any) hipLaunchKernelGGL(k2d_prolong, dim3(nblk(c0, S2_W), nblk(c1, S2_R), 4), dim3(S2_W, S2_R), 0, m->st, C->d, L, m->box[l - 1], -1);
+        } else
+        for (int dim = 0; dim < 4; dim++) {
+          if (!L.prol[dim]) continue;
+          const int n0 = (dim >> 1) == 0 ? NG/2 : c0, n1 = (dim >> 1) == 1 ? NG/2 : c1;
+          hipLaunchKernelGGL(k2d_prolong, dim3(nblk(n0, S2_W), nblk(n1, S2_R)), dim3(S2_W, S2_R), 0, m->st, C->d, L, m->box[l - 1], dim);
+        }
+      } else
       if (m->one_launch) {
         long nmax = 0;
         for (int dim = 0; dim < 6; dim++) {
@@ -557,17 +738,18 @@ int aa_mesh_prolongate(aa_mesh *m)
 int aa_mesh_new_dt(aa_mesh *m)
 {
   double cum[3] = {0.0, 0.0, 0.0}, max_dti = 0.0;
+  const int ndir = m->two_d ? 2 : 3;      // new_dt.c:126-161: max_v3 only where Nx3 > 1
   for (int l = 0; l < m->nl; l++) {
     aa_grid *g = m->lev[l];
     { Scope s(g, "new_dt");
       HIPCHK(hipMemsetAsync(g->sc->max_v, 0, 3*sizeof(unsigned long long), g->st));
       launch_cfl(g->d, g->sc, g->st); }
     int rc = aa_fetch_scalars(g); if (rc) return rc;
-    for (int d = 0; d < 3; d++) {
+    for (int d = 0; d < ndir; d++) {
       const double v = bits_to_double(g->sc_host->max_v[d]);
       cum[d] = (cum[d] > v) ? cum[d] : v;
     }
-    for (int d = 0; d < 3; d++) { const double q = cum[d]/g->d.dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
+    for (int d = 0; d < ndir; d++) { const double q = cum[d]/g->d.dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
   }
   const aa_params &p = m->lev[0]->p;
   const double dtc = p.cour_no/max_dti;
@@ -580,6 +762,7 @@ int aa_mesh_new_dt(aa_mesh *m)
 // ionrad_smr.c:345 + :34: the flux level l-1 left at the upstream face of level l, onto level l's rays
 int aa_mesh_ionflux_prolong(aa_mesh *m, int l)
 {
+  if (m->two_d) return aa_fail(-1, "[aa_mesh_ionflux_prolong]: a Mesh of 2-D Grids has no ion radiation (the reference has ionrad_3d only)");
   if (l < 1 || l >= m->nl) return aa_fail(-1, "[aa_mesh_ionflux_prolong]: level %d", l);
   const Link &L = m->link[l - 1];
   aa_grid *P = m->lev[m->par[l - 1]];
@@ -617,6 +800,7 @@ int aa_flux_x3_apply(aa_grid *parent, int side, int i0, int j0, int n1, int n2, 
 // publishes the time it covered; a refined level sub-cycles until it has covered exactly that
 int aa_mesh_ion_radtransfer(aa_mesh *m, int l, int *niter_out)
 {
+  if (m->two_d) return aa_fail(-1, "[aa_mesh_ion_radtransfer]: a Mesh of 2-D Grids has no ion radiation (the reference has ionrad_3d only)");
   aa_grid *g = m->lev[l];
   const bool finegrid = (g->level != 0);
   double dt_done = 0.0;
@@ -682,7 +866,8 @@ int aa_mesh_step(aa_mesh *m, int *niter)
   for (int l = 0; l < m->nl && !rc; l++) {                            // :572-585
     aa_grid *g = m->lev[l];
     if (fork && l > 0) g->st = m->side[l];
-    rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g));
+    if (m->two_d) rc = (g->p.integrator == 1 ? aa_integrate_2d_vl(g) : aa_integrate_2d_ctu(g));      // integrate.c:49-58
+    else rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g));
     g->st = m->st;
   }
   if (fork)

@@ -254,7 +254,8 @@ class _Runner:
         """of a Domain of Nx zones of a refined mesh (Driver has its own: the root Domain's, from its edges)"""
         vol = 1.0
         for a in range(3):
-            vol *= Nx[a] * (self.run.dx[a] / float(1 << level))
+            if a == 0 or Nx[a] > 1:               # dump_history.c:316-321: a direction with one zone (x3 of a 2-D Domain) does not count
+                vol *= Nx[a] * (self.run.dx[a] / float(1 << level))
         return vol
 
     def _history_row(self, key, rundir, level, domain, out, outputs, sums, vol):
@@ -680,7 +681,7 @@ class MeshRun(_Runner):
         """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770)."""
         from . import lib
         head, par, run = cls._resume_head(path, overrides, problem, integrator, order)
-        grids = config.levels(par, run)
+        grids = config.levels_2d(par, run) if run.ndim == 2 else config.levels(par, run)      # by the file's table: Nx3 = 1 is a 2-D Mesh
         head["levels"] = restart.index_sections(head, [g.Nx for g in grids], run.nscal, run.ion)
         m = cls(lib.Mesh(grids, device, strict, initial=False), run)
         with open(path, "rb") as f:

@@ -25,6 +25,7 @@ static void centre(const aa_params *p, int i, int j, int k, double x[3])   /* cc
 {
   double dx[3]; int d;
   for (d = 0; d < 3; d++) dx[d] = (p->xmax[d] - p->xmin[d])/(double)p->rootNx[d]/(double)(1 << p->level);   /* init_mesh.c:225,245 */
+  if (p->Nx[2] == 1) dx[2] = (p->xmax[2] - p->xmin[2])/(double)p->rootNx[2];   /* :331-337: a direction with one zone is not refined */
   x[0] = p->MinX[0] + ((double)(i - NG) + 0.5)*dx[0];
   x[1] = p->MinX[1] + ((double)(j - NG) + 0.5)*dx[1];
   x[2] = p->MinX[2] + ((double)(k - NG3(p)) + 0.5)*dx[2];

@@ -108,6 +108,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_halo_doubles_x2": (LL, [P]), "aa_pack_x2": (I, [P, I, P]), "aa_unpack_x2": (I, [P, I, P]),
         "aa_halo_doubles_dir": (LL, [P, I]), "aa_halo_get": (I, [P, I, I, dp]), "aa_halo_put": (I, [P, I, I, dp]), "aa_device_count": (I, []),
         "aa_mesh_create": (I, [I, C.POINTER(P), ip, C.POINTER(P)]), "aa_mesh_destroy": (None, [P]),
+        "aa_mesh_create_2d": (I, [I, C.POINTER(P), ip, C.POINTER(P)]),
         "aa_mesh_get_state": (I, [P, dp, dp, ip]), "aa_mesh_set_state": (I, [P, D, D, I]),
         "aa_mesh_set_stream": (I, [P, P]), "aa_mesh_restrict_correct_pair": (I, [P, I]),
         "aa_mesh_restrict_correct": (I, [P]), "aa_mesh_ionrad_restrict_correct": (I, [P]),
@@ -418,7 +419,8 @@ class Grid:
         from . import dumps
         g = self.cfg; r = g.run
         lev = g.level if level is None else level
-        dx = tuple(r.dx[d] / float(1 << g.level) for d in range(3))
+        # (init_mesh.c:331-337: a direction with one zone -- x3 of a 2-D Grid -- keeps the root's extent on every level)
+        dx = tuple(r.dx[d] / float(1 << g.level) if g.Nx[d] > 1 else r.dx[d] for d in range(3))
         if time is None or dt is None:
             t_, dt_, _ = self.mesh_state()
             time = t_ if time is None else time; dt = dt_ if dt is None else dt
@@ -607,7 +609,9 @@ class Mesh:
         self._h = None
         if links is None:
             disp = (C.c_int * (3 * n))(*[g.disp[d] if g.level else 0 for g in grids for d in range(3)])
-            self._chk(self.L.aa_mesh_create(n, hs, disp, C.byref(h)))
+            # (Grids with Nx3 = 1: the 2-D constructor -- nesting in x1 and x2, the 2-D integrators and coupling kernels)
+            create = self.L.aa_mesh_create_2d if all(g.Nx[2] == 1 for g in grids) else self.L.aa_mesh_create
+            self._chk(create(n, hs, disp, C.byref(h)))
         else:
             flat = [v for L_ in links for v in (*L_.cs, *L_.n, *L_.prol, *L_.corr, *L_.cdisp)]
             arr = (C.c_int * max(1, len(flat)))(*flat)

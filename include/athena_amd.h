@@ -219,6 +219,13 @@ int aa_device_count(void);                                               /* visi
 typedef struct aa_mesh aa_mesh;
 int  aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out); /* init_grid.c overlap
                                                           tables (:150-560) + SMR_init (smr.c:2931)  */
+/* The same contract for Grids that are all 2-D (Nx3 = 1; the reference's tst/2D-hydro/athinput.blast has three levels):
+ * disp[3*g+2] must be 0, and the nesting rules of init_mesh.c:320-499 hold in x1 and x2.  Every aa_mesh_* function below works
+ * on such a Mesh except the radiation ones, which return an error; aa_mesh_step runs aa_integrate_2d_ctu / _vl, and
+ * aa_mesh_new_dt carries max_v1 and max_v2 only.  cour_no up to the reference's 0.8 with CTU, <= 0.5 with van Leer.  Refused:
+ * a 3-D Grid among the levels (aa_mesh_create is the 3-D constructor, as this one refuses there), levels of mixed
+ * integrators, integrator = 2 (no reference build with --enable-smr and without H-correction), a Grid with fofc on.          */
+int  aa_mesh_create_2d(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out);
 void aa_mesh_destroy(aa_mesh *m);
 int  aa_mesh_get_state(const aa_mesh *m, double *time, double *dt, int *nstep);     /* MeshS          */
 int  aa_mesh_set_state(aa_mesh *m, double time, double dt, int nstep);
