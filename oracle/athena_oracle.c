@@ -44,6 +44,14 @@ typedef struct { Real d, Vx, Vy, Vz, P, r; } P1;      /* sweep frame, athena.h:1
 
 /* diagnostics: how often the Roe solver fell back to HLLE / returned an upwind flux */
 long orc_dbg_hlle = 0, orc_dbg_supersonic = 0;
+/* the branch census of the hydro step (tests/hydromatrix.py CLASSES, in this order): one slot per class and sweep direction.
+ * The integrators set orc_dbg_dir before each sweep; the function-level entry points count under direction 0. */
+enum { DBG_FL, DBG_FR, DBG_HLLE_D, DBG_HLLE_P, DBG_ETAH_WINS, DBG_ETAH_NOT, DBG_LIM_ZERO, DBG_LIM_2LIM1, DBG_LIM_LIM2,
+       DBG_CLAMP, DBG_TR_EV0, DBG_TR_VXP, DBG_TR_VXM, DBG_TR_EV4, DBG_PFLOOR, DBG_PPM_FLAT, DBG_PPM_STEEP, DBG_NCLASS };
+long orc_dbg_class[DBG_NCLASS][3];
+int orc_dbg_dir = 0;
+static int dbg_hpass = 0;     /* set while the second-pass (H-corrected) fluxes are solved: only those faces count for the etah classes */
+#define CNT(c) (orc_dbg_class[c][orc_dbg_dir]++)
 
 struct OrcSim {
   OrcParams p;
@@ -76,6 +84,7 @@ static P1 cons_to_prim(const C1 *u, Real Gamma_1, int nscal)
   w.d = u->d; w.Vx = u->Mx*di; w.Vy = u->My*di; w.Vz = u->Mz*di;
   w.P = u->E - 0.5*(SQR(u->Mx)+SQR(u->My)+SQR(u->Mz))*di;
   w.P *= Gamma_1;
+  if (!(w.P > TINY_NUMBER)) CNT(DBG_PFLOOR);
   w.P = MAXR(w.P, TINY_NUMBER);
   w.r = nscal ? u->s*di : 0.0;
   return w;
@@ -179,8 +188,8 @@ static void flux_roe(const C1 *Ul, const C1 *Ur, const P1 *Wl, const P1 *Wr, Rea
   Fl[5] = nscal ? Fl[0]*Wl->r : 0.0;
   Fr[5] = nscal ? Fr[0]*Wr->r : 0.0;
 
-  if (ev[0] >= 0.0) { orc_dbg_supersonic++; for (n = 0; n < 6; n++) F[n] = Fl[n]; return; }   /* :215-235 */
-  if (ev[4] <= 0.0) { orc_dbg_supersonic++; for (n = 0; n < 6; n++) F[n] = Fr[n]; return; }
+  if (ev[0] >= 0.0) { orc_dbg_supersonic++; CNT(DBG_FL); for (n = 0; n < 6; n++) F[n] = Fl[n]; return; }   /* :215-235 */
+  if (ev[4] <= 0.0) { orc_dbg_supersonic++; CNT(DBG_FR); for (n = 0; n < 6; n++) F[n] = Fr[n]; return; }
 
   /* left eigenvectors (rows), esystem_roe.c:183-214 */
   na = 0.5/asq;
@@ -220,9 +229,15 @@ static void flux_roe(const C1 *Ul, const C1 *Ur, const P1 *Wl, const P1 *Wr, Rea
       else { p_inter = u[4] - 0.5*(SQR(u[1])+SQR(u[2])+SQR(u[3]))/u[0]; if (p_inter < 0.0) hlle_flag = 2; }
     }
   }
-  if (hlle_flag) { orc_dbg_hlle++; flux_hlle(Ul, Ur, Wl, Wr, Gamma, Gamma_1, nscal, pF); return; }
+  if (hlle_flag) { orc_dbg_hlle++; CNT(hlle_flag == 1 ? DBG_HLLE_D : DBG_HLLE_P); flux_hlle(Ul, Ur, Wl, Wr, Gamma, Gamma_1, nscal, pF); return; }
 
   for (n = 0; n < NW; n++) coeff[n] = 0.5*MAXR(fabs(ev[n]), etah)*aa[n];   /* :291-312 */
+  if (dbg_hpass) {          /* faces on which etah wins the MAX for at least one wave / loses it for at least one */
+    int wins = 0, loses = 0;
+    for (n = 0; n < NW; n++) { if (etah > fabs(ev[n])) wins = 1; else loses = 1; }
+    if (wins) CNT(DBG_ETAH_WINS);
+    if (loses) CNT(DBG_ETAH_NOT);
+  }
   F[0] = 0.5*(Fl[0] + Fr[0]); F[0] -= coeff[0]; F[0] -= coeff[3]; F[0] -= coeff[4];
   F[1] = 0.5*(Fl[1] + Fr[1]); F[1] -= coeff[0]*(v1 - a); F[1] -= coeff[3]*v1; F[1] -= coeff[4]*(v1 + a);
   F[2] = 0.5*(Fl[2] + Fr[2]); F[2] -= coeff[0]*v2; F[2] -= coeff[1]; F[2] -= coeff[3]*v2; F[2] -= coeff[4]*v2;
@@ -279,7 +294,8 @@ static void lr_states_x(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl, P
         lim1 = MINR(fabs(dal[n]), fabs(dar[n]));
         lim2 = MINR(0.5*fabs(dac[n]), fabs(dag[n]));
         da[n] = ((dac[n] < 0.) ? -1. : 1.)*MINR(2.0*lim1, lim2);
-      }
+        CNT(2.0*lim1 < lim2 ? DBG_LIM_2LIM1 : DBG_LIM_LIM2);
+      } else CNT(DBG_LIM_ZERO);
     }
     dWm[0] = da[0]; dWm[0] += da[1]; dWm[0] += da[4];                   /* :192-202 */
     dWm[1] = da[0]*r10; dWm[1] += da[4]*r14;
@@ -292,12 +308,16 @@ static void lr_states_x(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl, P
       Wrv[n] = w[n] + 0.5*dWm[n]*1.0;
     }
     for (n = 0; n < nv; n++) {
+      Real unclamped = Wlv[n]; int acted;
       C = Wrv[n] + 1.0*Wlv[n];
       Wlv[n] = MAXR(MINR(w[n], wm[n]), Wlv[n]);
       Wlv[n] = MINR(MAXR(w[n], wm[n]), Wlv[n]);
+      acted = (Wlv[n] != unclamped);
       Wrv[n] = C - 1.0*Wlv[n];
+      unclamped = Wrv[n];
       Wrv[n] = MAXR(MINR(w[n], wp[n]), Wrv[n]);
       Wrv[n] = MINR(MAXR(w[n], wp[n]), Wrv[n]);
+      if (acted || Wrv[n] != unclamped) CNT(DBG_CLAMP);
       Wlv[n] = (C - Wrv[n])*1.0;
     }
     for (n = 0; n < nv; n++) dW[n] = Wrv[n] - Wlv[n];
@@ -315,12 +335,12 @@ static void lr_states_x(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl, P
 
     /* :322-339: waves with ev>=0 that do not reach the right interface */
     qx1 = 0.5*dtodx*ev4;
-    if (ev0 >= 0.0) {
+    if (ev0 >= 0.0) { CNT(DBG_TR_EV0);
       qx2 = 0.5*dtodx*ev0; qx = qx1 - qx2;
       qa = 0.0; qa += l01*qx*dW[1]; qa += l04*qx*dW[4];
       pWl[0] += qa; pWl[1] += qa*r10; pWl[4] += qa*asq;
     }
-    if (vx >= 0.0) {
+    if (vx >= 0.0) { CNT(DBG_TR_VXP);
       qx2 = 0.5*dtodx*vx; qx = qx1 - qx2;
       qa = 0.0; qa += 1.0*qx*dW[0]; qa += l14*qx*dW[4];  pWl[0] += qa;
       qa = 0.0; qa += 1.0*qx*dW[2];                      pWl[2] += qa;
@@ -330,13 +350,13 @@ static void lr_states_x(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl, P
     /* :341-358: waves with ev<=0 that do not reach the left interface */
     qx1 = -0.5*dtodx*ev0;
     /* n=0: qx = 0 adds exact zeros */
-    if (vx <= 0.0) {
+    if (vx <= 0.0) { CNT(DBG_TR_VXM);
       qx2 = -0.5*dtodx*vx; qx = -qx1 + qx2;
       qa = 0.0; qa += 1.0*qx*dW[0]; qa += l14*qx*dW[4];  pWr[0] += qa;
       qa = 0.0; qa += 1.0*qx*dW[2];                      pWr[2] += qa;
       qa = 0.0; qa += 1.0*qx*dW[3];                      pWr[3] += qa;
     }
-    if (ev4 <= 0.0) {
+    if (ev4 <= 0.0) { CNT(DBG_TR_EV4);
       qx2 = -0.5*dtodx*ev4; qx = -qx1 + qx2;
       qa = 0.0; qa += l41*qx*dW[1]; qa += l04*qx*dW[4];
       pWr[0] += qa; pWr[1] += qa*r14; pWr[4] += qa*asq;
@@ -385,7 +405,8 @@ static void limited_slopes(const P1 *W, int i, Real Gamma, int nscal, Real dWm[6
       lim1 = MINR(fabs(dal[n]), fabs(dar[n]));
       lim2 = MINR(0.5*fabs(dac[n]), fabs(dag[n]));
       da[n] = ((dac[n] < 0.) ? -1. : 1.)*MINR(2.0*lim1, lim2);
-    }
+      CNT(2.0*lim1 < lim2 ? DBG_LIM_2LIM1 : DBG_LIM_LIM2);
+    } else CNT(DBG_LIM_ZERO);
   }
   dWm[0] = da[0]; dWm[0] += da[1]; dWm[0] += da[4];
   dWm[1] = da[0]*r10; dWm[1] += da[4]*r14;
@@ -420,15 +441,17 @@ static void lr_states_ppm(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl,
       qa = (Wrv[n]-w[n])*(w[n]-Wlv[n]);
       qb = Wrv[n]-Wlv[n];
       qc = 6.0*(w[n] - 0.5*(Wlv[n]*(1.0-gamma_curv) + Wrv[n]*(1.0+gamma_curv)));
-      if (qa <= 0.0) { Wlv[n] = w[n]; Wrv[n] = w[n]; }
-      else if ((qb*qc) > (qb*qb)) Wlv[n] = (6.0*w[n] - Wrv[n]*(4.0+3.0*gamma_curv))/(2.0-3.0*gamma_curv);
-      else if ((qb*qc) < -(qb*qb)) Wrv[n] = (6.0*w[n] - Wlv[n]*(4.0-3.0*gamma_curv))/(2.0+3.0*gamma_curv);
+      if (qa <= 0.0) { CNT(DBG_PPM_FLAT); Wlv[n] = w[n]; Wrv[n] = w[n]; }
+      else if ((qb*qc) > (qb*qb)) { CNT(DBG_PPM_STEEP); Wlv[n] = (6.0*w[n] - Wrv[n]*(4.0+3.0*gamma_curv))/(2.0-3.0*gamma_curv); }
+      else if ((qb*qc) < -(qb*qb)) { CNT(DBG_PPM_STEEP); Wrv[n] = (6.0*w[n] - Wlv[n]*(4.0-3.0*gamma_curv))/(2.0+3.0*gamma_curv); }
     }
     for (n = 0; n < nv; n++) {
+      const Real l0 = Wlv[n], r0 = Wrv[n];
       Wlv[n] = MAXR(MINR(w[n],wm[n]),Wlv[n]);
       Wlv[n] = MINR(MAXR(w[n],wm[n]),Wlv[n]);
       Wrv[n] = MAXR(MINR(w[n],wp[n]),Wrv[n]);
       Wrv[n] = MINR(MAXR(w[n],wp[n]),Wrv[n]);
+      if (Wlv[n] != l0 || Wrv[n] != r0) CNT(DBG_CLAMP);
     }
     for (n = 0; n < nv; n++) {                                          /* Step 17 :451-455 */
       dW[n] = Wrv[n] - Wlv[n];
@@ -453,25 +476,25 @@ static void lr_states_ppm(const P1 *W, Real dt, Real dx, int il, int iu, P1 *Wl,
 #define TERML(m) (qb*(dW[m]-W6[m]) + qc*W6[m])
 #define TERMR(m) (qb*(dW[m]+W6[m]) + qc*W6[m])
     qx1 = 0.5*dtodx*ev4;
-    if (ev0 >= 0.0) {
+    if (ev0 >= 0.0) { CNT(DBG_TR_EV0);
       qx2 = 0.5*dtodx*ev0; qb = qx1 - qx2; qc = FOUR_3RDS*(SQR(qx1) - SQR(qx2));
       qa = 0.0; qa += l01*TERML(1); qa += l04*TERML(4);
       pWl[0] += qa; pWl[1] += qa*r10; pWl[4] += qa*asq;
     }
-    if (vx >= 0.0) {
+    if (vx >= 0.0) { CNT(DBG_TR_VXP);
       qx2 = 0.5*dtodx*vx; qb = qx1 - qx2; qc = FOUR_3RDS*(SQR(qx1) - SQR(qx2));
       qa = 0.0; qa += 1.0*TERML(0); qa += l14*TERML(4);  pWl[0] += qa;
       qa = 0.0; qa += 1.0*TERML(2);                      pWl[2] += qa;
       qa = 0.0; qa += 1.0*TERML(3);                      pWl[3] += qa;
     }
     qx1 = 0.5*dtodx*ev0;
-    if (vx <= 0.0) {
+    if (vx <= 0.0) { CNT(DBG_TR_VXM);
       qx2 = 0.5*dtodx*vx; qb = qx1 - qx2; qc = FOUR_3RDS*(SQR(qx1) - SQR(qx2));
       qa = 0.0; qa += 1.0*TERMR(0); qa += l14*TERMR(4);  pWr[0] += qa;
       qa = 0.0; qa += 1.0*TERMR(2);                      pWr[2] += qa;
       qa = 0.0; qa += 1.0*TERMR(3);                      pWr[3] += qa;
     }
-    if (ev4 <= 0.0) {
+    if (ev4 <= 0.0) { CNT(DBG_TR_EV4);
       qx2 = 0.5*dtodx*ev4; qb = qx1 - qx2; qc = FOUR_3RDS*(SQR(qx1) - SQR(qx2));
       qa = 0.0; qa += l41*TERMR(1); qa += l04*TERMR(4);
       pWr[0] += qa; pWr[1] += qa*r14; pWr[4] += qa*asq;
@@ -589,6 +612,7 @@ void orc_integrate(OrcSim *s)
   for (d = 0; d < 3; d++) {
     const int d1 = (d+1)%3, d2 = (d+2)%3;   /* the two transverse directions */
     int a, b, c, idx[3];
+    orc_dbg_dir = d;
     /* transverse loop extents: x1 sweep: k,j in [l,u]; x2 sweep: k in [kl,ku], i in [il,iu];
        x3 sweep: j,i in [l,u] -- i.e. always [l,u] in both transverse directions */
     for (a = l[d2]; a <= u[d2]; a++) for (b = l[d1]; b <= u[d1]; b++) {
@@ -732,6 +756,7 @@ void orc_integrate(OrcSim *s)
        (a > b ? a : b) is order-sensitive when an eta is NaN (negative face pressure) */
     const int d1 = (d == 0) ? 1 : 0, d2 = (d == 2) ? 1 : 2;
     int rl[3], ru[3];
+    orc_dbg_dir = d; dbg_hpass = (s->p.integrator == 0);
     for (e = 0; e < 3; e++) { rl[e] = (e == d) ? lo[e] : lo[e]-1; ru[e] = hi[e]+1; }
     for (k = rl[2]; k <= ru[2]; k++) for (j = rl[1]; j <= ru[1]; j++) for (i = rl[0]; i <= ru[0]; i++) {
       size_t m = IDX(s,k,j,i), ml = m - str[d];
@@ -752,6 +777,7 @@ void orc_integrate(OrcSim *s)
     }
   }
 
+  dbg_hpass = 0;
   /* === Step 11a: gravity source terms for the full step (:2741-2782) === */
   if (grav) {
     for (k = s->ks; k <= s->ke; k++) for (j = s->js; j <= s->je; j++) for (i = s->is; i <= s->ie; i++) {
@@ -786,6 +812,7 @@ void orc_integrate(OrcSim *s)
       for (n = 0; n < nv; n++) pu[n] -= dtodx[d]*(f1[n] - f0[n]);
     }
   }
+  orc_dbg_dir = 0;
   free(W); free(Wl); free(Wr);
 }
 
@@ -814,6 +841,7 @@ static void integrate_vl(OrcSim *s)
   for (d = 0; d < 3; d++) {
     const int d1 = (d+1)%3, d2 = (d+2)%3;
     int a, b, c, idx[3];
+    orc_dbg_dir = d;
     for (a = lo[d2]-NGHOST; a <= hi[d2]+NGHOST; a++) for (b = lo[d1]-NGHOST; b <= hi[d1]+NGHOST; b++) {
       size_t base;
       idx[d1] = b; idx[d2] = a; idx[d] = 0; base = IDX(s, idx[2], idx[1], idx[0]);
@@ -856,6 +884,7 @@ static void integrate_vl(OrcSim *s)
   for (d = 0; d < 3; d++) {
     const int d1 = (d+1)%3, d2 = (d+2)%3;
     int a, b, c, idx[3];
+    orc_dbg_dir = d;
     for (a = lo[d2]-1; a <= hi[d2]+1; a++) for (b = lo[d1]-1; b <= hi[d1]+1; b++) {
       size_t base;
       idx[d1] = b; idx[d2] = a; idx[d] = 0; base = IDX(s, idx[2], idx[1], idx[0]);
@@ -894,6 +923,7 @@ static void integrate_vl(OrcSim *s)
       const Real *f0 = (const Real*)&s->F[d][m], *f1 = (const Real*)&s->F[d][m + str[d]];
       for (n = 0; n < nv; n++) pu[n] -= dtodx[d]*(f1[n] - f0[n]);
     }
+  orc_dbg_dir = 0;
   free(W); free(Wl); free(Wr);
 }
 

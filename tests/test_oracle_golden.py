@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import hydromatrix
 import ionmatrix
 import orc
 
@@ -158,6 +159,136 @@ def test_ifront_with_20_rays_leaves_by_dt_hydro():
     assert damped > 0
 
 
+def _hydromatrix(name, g):
+    """The designed hydro state (tests/hydromatrix.py) from our own problem file (tests/fixtures/hydro_matrix.c) run by the reference:
+    every branch of the Roe solver, the reconstruction and the tracing.  3-D runs, one level or nested: the oracle reaches the
+    reference's state bit for bit, and its live counters of the Roe solver's four exits equal, step by step, the execution counts
+    gcov read from the reference's own run (cov_roe) -- the same faces are solved, the same branches taken.  2-D runs (the oracle
+    has no 2-D path): the fixture starts from the pattern and stays finite with positive density."""
+    cnt = hydromatrix.counters()
+    if "nlevels" in g.files:
+        _, integrator, case, cour, dvac, pvac = hydromatrix.SMR_CFG[str(g["tag"])]
+        assert (float(g["dvac"]), float(g["pvac"])) == (dvac, pvac)
+        gam = hydromatrix.gamma(case[0][2])
+        for l in range(int(g["nlevels"])):
+            U0 = hydromatrix.pattern(tuple(g["nxs"][l]), gam, int(g["levels"][l]), tuple(g["disp"][l]), dvac, pvac)
+            assert _same(U0[..., :5], g[f"U0_{l}"]), f"initial condition, level {l}"
+            assert np.isfinite(g[f"U_{l}"]).all() and (g[f"U_{l}"][..., 0] > 0).all() and (g[f"U0_{l}"][..., 0] > 0).all()
+        if case[0][2] == 1:
+            return
+        m = hydromatrix.make_mesh(str(g["tag"]))
+        m.start()
+        assert m.dt == float(g["dt0"])
+        for n in range(int(g["nstep"])):
+            cnt[...] = 0
+            m.step()
+            assert cnt[:4].sum(axis=1).tolist() == g["cov_roe"][n].tolist(), f"exits of the Roe solver in step {n + 1}"
+        assert m.time == float(g["time"]) and m.dt == float(g["dt"])
+        for l, s in enumerate(m.lev):
+            assert _same(s.active[..., :5], g[f"U_{l}"]), f"level {l}"
+        return
+    cfg, nx = str(g["cfg"]), tuple(int(n) for n in g["nx"])
+    dvac, pvac = hydromatrix.CFG[cfg][4:]
+    assert (float(g["dvac"]), float(g["pvac"])) == (dvac, pvac)
+    assert np.isfinite(g["U"]).all() and (g["U"][..., 0] > 0).all() and (g["U0"][..., 0] > 0).all()
+    if nx[2] == 1:
+        assert _same(hydromatrix.pattern(nx, hydromatrix.gamma(1), dvac=dvac, pvac=pvac)[..., :5], g["U0"]), "initial condition"
+        return
+    s = hydromatrix.make_sim(cfg, nx)
+    assert _same(s.active[..., :5], g["U0"]), "initial condition"
+    s.start()
+    assert s.dt == float(g["dt0"])
+    for n in range(int(g["nstep"])):
+        cnt[...] = 0
+        s.step()
+        assert cnt[:4].sum(axis=1).tolist() == g["cov_roe"][n].tolist(), f"exits of the Roe solver in step {n + 1}"
+    assert s.time == float(g["time"]) and s.dt == float(g["dt"])
+    assert _same(s.active[..., :5], g["U"])
+
+
+SMALL_GRID_MIN = 8
+HYDROMATRIX = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "hydromatrix_*.npz")))
+
+
+@pytest.mark.parametrize("name", HYDROMATRIX)
+def test_hydro_matrix_covers_every_branch(name):
+    """The census of the designed hydro state.  In every reference run every step reaches each class at least 32 times per sweep
+    direction: conditions on the fixtures, not measurements -- a pattern that misses one has to change.
+      3-D, one level   the oracle's counters (pinned to the reference bit for bit and, for the Roe solver's exits, count for count):
+      and nested       the two supersonic returns, HLLE by u0 <= 0 and by p_inter < 0, the limiter giving zero / 2 lim1 / lim2, the
+                       clamps acting, the four tracing branches (CTU), the parabola flattened and steepened (PPM), the pressure floor
+                       where the configuration asks for it, and on the second-pass (H-corrected) faces etah winning the MAX for at
+                       least one wave and losing it for at least one.  (A face on which etah wins NO wave cannot be had short of a
+                       supersonic return: etah >= the face's own eta = |(vr + cr) - (vl - cl)| / 2, about the sound speed, so the
+                       entropy wave |v| > etah means ev0 >= 0 or ev4 <= 0, roe.c:215-235.)
+      2-D and nested   the reference's own execution counts of the Roe solver's exits, step by step (cov_roe; line counts tell neither
+                       the sweep directions nor the limiter and tracing outcomes apart), and, per direction and class, the first-order
+                       Riemann problems of the stored first state classified by the oracle's solver.  24x20 has a fifth of the faces
+                       of 67x35 (960 against 4690) and two receding block edges of either strength per direction: there each HLLE class
+                       is asked for SMALL_GRID_MIN = 8 times per direction (32 scaled by the faces is 6.6), the returns 32 times.
+                       The 2-D van Leer fixtures hold >= 32 zones whose pressure is floored in the first state.
+    At least 5 % of the zones of the first state lie in supersonic blocks.  Every side of every child Domain holds an HLLE face, and
+    at least two sides of every child an upwind face (first-order Riemann problems of the root's last stored state across the outline)."""
+    g = np.load(os.path.join(GOLD, name + ".npz"))
+    nested = "nlevels" in g.files
+    nx = tuple(int(n) for n in (g["nxs"][0] if nested else g["nx"]))
+    gam = hydromatrix.gamma(nx[2])
+    ndir = 2 if nx[2] == 1 else 3
+    assert hydromatrix.supersonic_fraction(nx) >= 0.05
+    cov = g["cov_roe"]
+    print(name, "reference's exits of the Roe solver per step (Fl, Fr, HLLE u0, HLLE p):", cov.tolist())
+    assert cov.shape == (hydromatrix.NSTEP, 4) and (cov >= hydromatrix.MIN_COUNT).all(), cov
+    U0 = g["U0_0"] if nested else g["U0"]
+    first = [np.bincount(hydromatrix.face_classes(U0, ax, gam).ravel(), minlength=5)[1:] for ax in range(ndir)]
+    print(name, "first-order faces of the first state per direction (Fl, Fr, HLLE u0, HLLE p):", [f.tolist() for f in first])
+    if nested or ndir == 2:
+        hlle_min = SMALL_GRID_MIN if U0[..., 0].size < 1000 else hydromatrix.MIN_COUNT
+        assert all((f[:2] >= hydromatrix.MIN_COUNT).all() and (f[2:] >= hlle_min).all() for f in first), first
+    pvac = float(g["pvac"])
+    floored = hydromatrix.floored_zones(U0, gam)
+    print(name, "zones of the first state with a floored pressure:", floored)
+    assert (floored >= hydromatrix.MIN_COUNT) == (pvac < 0), (floored, pvac)
+    if nested:
+        # the reference's own 1-ulp twins of the run (recorded by the golden script): the van Leer run is held on the GPU to the 3-D
+        # van Leer twins, which flip no decision -- a bound that can only be borrowed for a run whose own twins flip none either
+        print(name, f"the reference's 1-ulp twins part by {float(g['ref_twin_spread']):.3e}, {int(g['ref_twin_nflip'])} zones beyond 1e-9")
+        if str(g["integrator"]) == "vl" and str(g["tag"]) not in hydromatrix.STRICT_ONLY:
+            assert float(g["ref_twin_spread"]) < 1e-12 and int(g["ref_twin_nflip"]) == 0
+        Ue = g["U_0"]
+        for l in range(1, int(g["nlevels"])):
+            sides_with_upwind = 0
+            f = 2 ** int(g["levels"][l])
+            lo = [int(g["disp"][l][d]) // f for d in range(3)]; hi = [lo[d] + int(g["nxs"][l][d]) // f for d in range(3)]
+            for ax in range(ndir):
+                cls = hydromatrix.face_classes(Ue, ax, gam)            # [k][j][i]: the face above zone i along ax
+                box = [slice(lo[d], hi[d]) for d in range(3)]
+                for side, at in (("lower", lo[ax] - 1), ("upper", hi[ax] - 1)):
+                    sl = list(box); sl[ax] = slice(at, at + 1)
+                    if ndir == 2:
+                        sl[2] = slice(0, 1)
+                    n = int((cls[sl[2], sl[1], sl[0]] >= 3).sum()); up = int(np.isin(cls[sl[2], sl[1], sl[0]], (1, 2)).sum())
+                    print(name, f"Grid {l}, {side} x{ax + 1} side: {n} HLLE faces, {up} upwind faces")
+                    assert n >= 1, (name, l, ax, side)
+                    sides_with_upwind += up >= 1
+            assert sides_with_upwind >= 2, (name, l, sides_with_upwind)
+        if ndir == 3:           # the oracle runs the nested 3-D case: its full census, all levels together
+            _, integrator, case, cour, dvac, pvac = hydromatrix.SMR_CFG[str(g["tag"])]
+            cnt = hydromatrix.census_mesh(str(g["tag"]))
+            table = {c: cnt[:, i, :].min(axis=0).tolist() for i, c in enumerate(hydromatrix.CLASSES)}
+            print(name, "fewest per step, by direction:", table)
+            for c in hydromatrix.required_for(integrator, 2, pvac):
+                assert min(table[c]) >= hydromatrix.MIN_COUNT, (name, c, table[c])
+        return
+    if ndir == 2:
+        return
+    cfg = str(g["cfg"])
+    cnt, _ = hydromatrix.census(cfg, nx)
+    table = {c: cnt[:, i, :].min(axis=0).tolist() for i, c in enumerate(hydromatrix.CLASSES)}
+    print(name, "fewest per step, by direction:", table)
+    for c in hydromatrix.required(cfg):
+        assert min(table[c]) >= hydromatrix.MIN_COUNT, (name, c, table[c])
+
+
 RUNS = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*_n[0-9]*.npz")))
 
 
@@ -170,6 +301,8 @@ def test_whole_run_bitwise(name):
         return _coolpat(name, g)
     if name.startswith("ionmatrix"):
         return _ionmatrix(name, g)
+    if name.startswith("hydromatrix"):
+        return _hydromatrix(name, g)
     prob = name.rsplit("_", 2)[0]
     integrator = "ctu"
     order = 2

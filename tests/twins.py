@@ -96,3 +96,34 @@ def ion_matrix(tceil=None):
         worst = {k: max(worst[k], w[k]) for k in worst}
         nflip = max(nflip, nf)
     return worst, nflip
+
+
+@functools.lru_cache(maxsize=None)
+def hydro_matrix(cfg, nx=None):
+    """-> (largest spread, largest number of zones beyond 1e-9, zones of the Grid) over the twins of the 3 steps of the designed hydro
+    state (tests/hydromatrix.py) in configuration `cfg` on the Grid `nx`.  nx = None: the larger of either figure over the two 3-D
+    Grids, the number of zones as a share of the Grid (-> (spread, share)) -- what the 2-D and the nested runs, which the oracle cannot
+    twin, are held to.  On this state a 1-ulp change moves Roe -> HLLE and upwind decisions by design, so the spread is what any
+    arithmetic that differs from the reference's in the last bit (fused multiply-adds) can be held to."""
+    import hydromatrix
+    if nx is None:
+        figs = [hydro_matrix(cfg, s) for s in hydromatrix.SHAPES_3D]
+        return max(f[0] for f in figs), max(f[1] / f[2] for f in figs)
+
+    def advance(seed):
+        s = hydromatrix.make_sim(cfg, nx)
+        if seed:
+            perturb(s.active[..., :5], seed)
+        s.start()
+        for _ in range(hydromatrix.NSTEP):
+            s.step()
+        return s.active[..., :5].copy()
+
+    base = advance(0)
+    worst, nflip = 0.0, 0
+    for seed in SEEDS:
+        e = spread(advance(seed), base)
+        assert np.isfinite(e).all(), (cfg, nx, seed, "a twin of the designed state ends in NaN: the contrast is too high")
+        worst = max(worst, float(e.max()))
+        nflip = max(nflip, int((e > 1e-9).any(axis=-1).sum()))
+    return worst, nflip, int(base[..., 0].size)
