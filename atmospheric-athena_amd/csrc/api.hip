@@ -1122,7 +1122,7 @@ static int ion_run_phased(aa_grid *g, bool fine, double limit, int *niter_out, d
 int aa_ion_run(aa_grid *g, int finegrid, double limit, int *niter_out, double *dt_done_out)
 {
   g->cfl_ready = false; g->active_dirty = true;
-  if (!g->slab.empty() && !g->ion_fused) return slabs_ion_run_phased(g, limit, niter_out, dt_done_out);
+  if (!g->slab.empty() && !g->ion_fused) return slabs_ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out);
   return g->ion_fused ? ion_run_fused(g, finegrid != 0, limit, niter_out, dt_done_out)
                       : ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out);
 }

@@ -99,7 +99,53 @@ struct Scope {
 };
 
 // ---- composite Grids (slabs.hip) -------------------------------------------------------------
+struct SlabLink {
+  int n = 0;
+  std::vector<int> k0, nk, dev;            // first active plane (0-based, global), planes, HIP device of every slab
+  std::vector<int> lo, hi;                 // neighbour slab below / above (-1: physical boundary)
+  std::vector<aa::Real*> send[2], recv[2];     // halo buffers on every slab's device
+  std::vector<hipEvent_t> packed, copied;  // slab's send buffers are full / slab has pulled its neighbours' buffers
+  std::vector<bool> copied_valid;
+  // The peer copies run on a stream of their own beside the slab's kernels, and the unpack is left to whoever reads
+  // the ghost planes next (halo_finish): the integrator first sweeps the planes that hold no neighbour data
+  // (aa_integrate_begin), the ion step and new_dt never read them.
+  std::vector<hipStream_t> xfer;
+  std::vector<hipEvent_t> unpacked;        // slab's recv buffers have been unpacked (free for the next copy)
+  std::vector<bool> unpacked_valid;
+  bool halo_due = false;                   // messages posted, ghost planes not yet written
+  aa::DevScalars *hsc = nullptr;               // pinned: n
+  std::vector<aa::Real*> dwords_all;           // device: n x AA_ION_WORDS on every slab
+  std::vector<hipEvent_t> wdone;           // slab's words of the pass just queued are complete
+  hipEvent_t gathered = nullptr;           // slab 0 holds every slab's words
+  // no peer access between two neighbouring devices (or AA_SLAB_NO_PEER=1): the halo goes device -> pinned host -> device
+  bool staged = false;
+  std::vector<aa::Real*> hstage[2];            // pinned: the slab's two send buffers on the host
+  std::vector<hipStream_t> xout;           // the slab's device -> host copies
+  std::vector<hipEvent_t> staged_ev;       // ... are complete
+  // the radiation sub-cycle's words: slab 0 <-> every slab.  Where peer access between device 0 and ANY slab's device is missing (checked at
+  // create time for every pair, not only neighbours), or the halo is staged anyway, the words go through pinned host memory instead: every
+  // slab copies its words into hwords[round & 1][s] behind its pass and, once all have, reads the whole set back -- no peer copy at all.
+  // Two rounds of buffers: a slab can be one pick ahead of another, never two (its next pass waits for everybody's words of this one).
+  bool words_staged = false;
+  aa::Real *hwords[2] = {nullptr, nullptr};    // pinned: n x AA_ION_WORDS each
+  unsigned wround = 0;
+  size_t halo = 0;
+  int home = 0;                            // the caller's current device when the handle was made
+  // a level of a cut Mesh (aa_create_cut): the root's cuts K_0 .. K_ntotal, and the first root slab that holds zones of this level
+  // (slab s of the handle lies over root slab s0 + s and lives on its device; slabs without zones of the level are absent)
+  std::vector<int> cuts;
+  int s0 = 0, ntotal = 0;
+  bool by_cuts = false;                    // made by aa_create_cut (aa_mesh_create takes such handles, and only such)
+  int kdisp = 0;                           // the level's x3 displacement, zones of the level
+};
+
+// every composite entry point leaves the caller's current HIP device as it found it
+struct DevGuard { int d = -1; DevGuard() { if (hipGetDevice(&d) != hipSuccess) d = -1; } ~DevGuard() { if (d >= 0) (void)hipSetDevice(d); } };
 int slabs_create(const aa_params *p, int nslab, aa_grid **out);
+int slabs_bvals_local(aa_grid *g);   // the boundary conditions of every slab without the exchange between them
+int slabs_halo_finish(aa_grid *g);    // the ghost planes of a posted x3 exchange are written (before anything reads them)
+int slabs_halo_exchange(aa_grid *g);  // the x3 exchange between the slabs alone (no boundary condition)
+int slabs_cfl_queue(aa_grid *g);      // new_dt's maxima of every slab on their way to link->hsc, no wait
 void slabs_destroy(aa_grid *g);
 int slabs_sync(aa_grid *g);
 long long slabs_device_bytes(const aa_grid *g);
@@ -125,7 +171,7 @@ int slabs_ion_pass(aa_grid *g, int update, int sweep);
 int slabs_ion_pick(aa_grid *g, int first, double limit);
 int slabs_fetch_scalars(aa_grid *g);
 int slabs_ion_finish(aa_grid *g);
-int slabs_ion_run_phased(aa_grid *g, double limit, int *niter_out, double *dt_done_out);
+int slabs_ion_run_phased(aa_grid *g, int fine, double limit, int *niter_out, double *dt_done_out);
 int slabs_history(aa_grid *g, double *sums);
 int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away

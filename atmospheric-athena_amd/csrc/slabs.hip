@@ -23,6 +23,8 @@
 //   * StaticGravPot is evaluated at the positions of the caller's undivided Grid, and the problem generator /
 //     Userwork hooks work on the caller's block, so an N-slab run reproduces the 1-slab run bit for bit.
 // Block decomposition as init_mesh.c:583-620: Nx3/N planes each, the remainder to the first slabs.
+// aa_create_cut makes the same kind of handle for ONE LEVEL of a refined Mesh cut at given root planes (mesh_cuts.h): its slabs lie
+// over the root's slabs, on their devices, and a slab without zones of the level is absent; aa_mesh_create (smr.hip) couples such levels.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -30,45 +32,10 @@
 #include <string.h>
 #include <vector>
 #include "api_internal.h"
+#include "mesh_cuts.h"
 
 using namespace aa;
 
-struct SlabLink {
-  int n = 0;
-  std::vector<int> k0, nk, dev;            // first active plane (0-based, global), planes, HIP device of every slab
-  std::vector<int> lo, hi;                 // neighbour slab below / above (-1: physical boundary)
-  std::vector<Real*> send[2], recv[2];     // halo buffers on every slab's device
-  std::vector<hipEvent_t> packed, copied;  // slab's send buffers are full / slab has pulled its neighbours' buffers
-  std::vector<bool> copied_valid;
-  // The peer copies run on a stream of their own beside the slab's kernels, and the unpack is left to whoever reads
-  // the ghost planes next (halo_finish): the integrator first sweeps the planes that hold no neighbour data
-  // (aa_integrate_begin), the ion step and new_dt never read them.
-  std::vector<hipStream_t> xfer;
-  std::vector<hipEvent_t> unpacked;        // slab's recv buffers have been unpacked (free for the next copy)
-  std::vector<bool> unpacked_valid;
-  bool halo_due = false;                   // messages posted, ghost planes not yet written
-  DevScalars *hsc = nullptr;               // pinned: n
-  std::vector<Real*> dwords_all;           // device: n x AA_ION_WORDS on every slab
-  std::vector<hipEvent_t> wdone;           // slab's words of the pass just queued are complete
-  hipEvent_t gathered = nullptr;           // slab 0 holds every slab's words
-  // no peer access between two neighbouring devices (or AA_SLAB_NO_PEER=1): the halo goes device -> pinned host -> device
-  bool staged = false;
-  std::vector<Real*> hstage[2];            // pinned: the slab's two send buffers on the host
-  std::vector<hipStream_t> xout;           // the slab's device -> host copies
-  std::vector<hipEvent_t> staged_ev;       // ... are complete
-  // the radiation sub-cycle's words: slab 0 <-> every slab.  Where peer access between device 0 and ANY slab's device is missing (checked at
-  // create time for every pair, not only neighbours), or the halo is staged anyway, the words go through pinned host memory instead: every
-  // slab copies its words into hwords[round & 1][s] behind its pass and, once all have, reads the whole set back -- no peer copy at all.
-  // Two rounds of buffers: a slab can be one pick ahead of another, never two (its next pass waits for everybody's words of this one).
-  bool words_staged = false;
-  Real *hwords[2] = {nullptr, nullptr};    // pinned: n x AA_ION_WORDS each
-  unsigned wround = 0;
-  size_t halo = 0;
-  int home = 0;                            // the caller's current device when the handle was made
-};
-
-// every composite entry point leaves the caller's current HIP device as it found it
-struct DevGuard { int d = -1; DevGuard() { if (hipGetDevice(&d) != hipSuccess) d = -1; } ~DevGuard() { if (d >= 0) (void)hipSetDevice(d); } };
 #define SLAB_DEV(L, s) HIPCHK(hipSetDevice((L)->dev[s]))
 static int halo_finish(aa_grid *g);          // the ghost planes of a posted exchange are written before anything reads them
 #define HALO_FLUSH(g) do { int rc_ = halo_finish(g); if (rc_) return rc_; } while (0)
@@ -76,38 +43,37 @@ static int halo_finish(aa_grid *g);          // the ghost planes of a posted exc
 void slabs_push_state(aa_grid *g)
 { for (aa_grid *c : g->slab) { c->time = g->time; c->dt = g->dt; c->nstep = g->nstep; } }
 
-int slabs_create(const aa_params *p, int nslab, aa_grid **out)
+// the pieces of ONE Grid of the caller: piece s holds the planes [k0[s], k0[s] + nk[s]) of it and lies over root slab s0 + s of
+// ntotal (whose device it shares); wrap: the first and the last piece are neighbours (a periodic root)
+static int slabs_create_pieces(const aa_params *p, const std::vector<int> &pk0, const std::vector<int> &pnk, int s0, int ntotal, bool wrap,
+                               aa_grid **out)
 {
-  if (nslab > 64) return aa_fail(-1, "[aa_create]: %d slabs", nslab);
-  if (p->level != 0) return aa_fail(-1, "[aa_create]: only the root level can be cut into slabs");
-  if (p->Nx[2]/nslab < AA_NGHOST) return aa_fail(-1, "[aa_create]: %d x3 planes cut into %d slabs leave fewer than nghost = %d planes each",
-                                                  p->Nx[2], nslab, AA_NGHOST);
+  const int nslab = (int)pk0.size();
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return aa_fail(-3, "[aa_create]: no HIP device visible -- this library has no CPU path");
   DevGuard keep;
   aa_grid *g = new aa_grid();
-  g->p = *p; g->p.nslab = nslab;
+  g->p = *p; g->p.nslab = ntotal;
   memset(&g->d, 0, sizeof g->d);
-  g->level = 0;
-  SlabLink *L = new SlabLink(); g->link = L; L->n = nslab; L->home = keep.d;
+  g->level = p->level;
+  SlabLink *L = new SlabLink(); g->link = L; L->n = nslab; L->home = keep.d; L->s0 = s0; L->ntotal = ntotal;
 #define CREATE_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { slabs_destroy(g); \
   return aa_fail(-2, "[aa_create] HIP error %s at %s:%d: %s", #x, __FILE__, __LINE__, hipGetErrorString(e_)); } } while (0)
   // devices: AA_SLAB_DEVICES="0,1,2,.." or round robin over the visible ones (one device: a rehearsal of the
   // multi-GPU path, every slab on it)
   std::vector<int> devs;
   if (const char *e = getenv("AA_SLAB_DEVICES")) { for (const char *q = e; *q; ) { devs.push_back(atoi(q)); while (*q && *q != ',') q++; if (*q) q++; } }
-  const bool periodic = (p->bc[4] == AA_BC_PERIODIC && p->bc[5] == AA_BC_PERIODIC);
-  const Real dx3 = (p->xmax[2] - p->xmin[2])/(Real)(p->rootNx[2]);
-  int k0 = 0; Real minx3 = p->MinX[2];
+  const Real dx3 = ((p->xmax[2] - p->xmin[2])/(Real)(p->rootNx[2]))/(Real)(1 << p->level);
+  Real minx3 = p->MinX[2] + (pk0[0] > 0 ? (Real)pk0[0]*dx3 : 0.0);
   for (int s = 0; s < nslab; s++) {
-    const int nk = p->Nx[2]/nslab + (s < p->Nx[2] % nslab ? 1 : 0);      // init_mesh.c:583-620
+    const int nk = pnk[s], k0 = pk0[s];
     aa_params ps = *p;
     ps.nslab = 1;
     ps.Nx[2] = nk; ps.MinX[2] = minx3;                                    // init_grid.c:104-111
-    ps.device = devs.empty() ? (p->device + s) % ndev : devs[s % devs.size()];
-    if (ps.device >= ndev) { slabs_destroy(g); return aa_fail(-1, "[aa_create]: slab %d wants HIP device %d of %d", s, ps.device, ndev); }
-    const int lo = (s > 0) ? s - 1 : (periodic ? nslab - 1 : -1), hi = (s < nslab - 1) ? s + 1 : (periodic ? 0 : -1);
+    ps.device = devs.empty() ? (p->device + s0 + s) % ndev : devs[(s0 + s) % devs.size()];
+    if (ps.device >= ndev || ps.device < 0) { slabs_destroy(g); return aa_fail(-1, "[aa_create]: slab %d wants HIP device %d of %d", s0 + s, ps.device, ndev); }
+    const int lo = (s > 0) ? s - 1 : (wrap ? nslab - 1 : -1), hi = (s < nslab - 1) ? s + 1 : (wrap ? 0 : -1);
     if (lo >= 0) ps.bc[4] = AA_BC_NONE;
     if (hi >= 0) ps.bc[5] = AA_BC_NONE;
     aa_grid *c = nullptr;
@@ -115,7 +81,7 @@ int slabs_create(const aa_params *p, int nslab, aa_grid **out)
     if (rc) { slabs_destroy(g); return rc; }
     g->slab.push_back(c);
     L->k0.push_back(k0); L->nk.push_back(nk); L->dev.push_back(ps.device); L->lo.push_back(lo); L->hi.push_back(hi);
-    k0 += nk; minx3 += (Real)nk*dx3;
+    minx3 += (Real)nk*dx3;
   }
   g->ion_fused = g->slab[0]->ion_fused;
   for (aa_grid *c : g->slab) if (c->ion_fused != g->ion_fused) { slabs_destroy(g); return aa_fail(-1, "[aa_create]: slabs disagree on the sub-cycle path"); }
@@ -147,7 +113,9 @@ int slabs_create(const aa_params *p, int nslab, aa_grid **out)
       }
   }
   // ... and between slab 0's device and EVERY slab's device for the sub-cycle's words (slab 0 pulls from all, all pull from slab 0)
-  { const char *e = getenv("AA_SLAB_WORDS_STAGED"); L->words_staged = L->staged || (e && atoi(e) != 0); }
+  { const char *e = getenv("AA_SLAB_WORDS_STAGED"); L->words_staged = L->staged || (e && atoi(e) != 0);
+    if (e && atoi(e) != 0 && !L->staged)
+      fprintf(stderr, "[athena_amd] AA_SLAB_WORDS_STAGED: the radiation sub-cycle's reduction words of the slabs travel through pinned host memory\n"); }
   for (int s = 1; s < nslab && !L->words_staged; s++) {
     if (L->dev[s] == L->dev[0]) continue;
     for (int dir = 0; dir < 2 && !L->words_staged; dir++) {
@@ -196,6 +164,62 @@ int slabs_create(const aa_params *p, int nslab, aa_grid **out)
 #undef CREATE_CHK
   for (aa_grid *c : g->slab) g->bytes += c->bytes;
   *out = g;
+  return 0;
+}
+
+int slabs_create(const aa_params *p, int nslab, aa_grid **out)
+{
+  if (nslab > 64) return aa_fail(-1, "[aa_create]: %d slabs", nslab);
+  if (p->level != 0) return aa_fail(-1, "[aa_create]: only the root level can be cut into slabs (the levels of a Mesh cut at the root's planes: aa_create_cut)");
+  if (p->Nx[2]/nslab < AA_NGHOST) return aa_fail(-1, "[aa_create]: %d x3 planes cut into %d slabs leave fewer than nghost = %d planes each",
+                                                  p->Nx[2], nslab, AA_NGHOST);
+  std::vector<int> cuts(nslab + 1), k0(nslab), nk(nslab);
+  mc_equal_cuts(p->Nx[2], nslab, cuts.data());                          // init_mesh.c:583-620
+  for (int s = 0; s < nslab; s++) { k0[s] = cuts[s]; nk[s] = cuts[s + 1] - cuts[s]; }
+  const bool periodic = (p->bc[4] == AA_BC_PERIODIC && p->bc[5] == AA_BC_PERIODIC);
+  int rc = slabs_create_pieces(p, k0, nk, 0, nslab, periodic, out);
+  if (rc == 0) (*out)->link->cuts = cuts;
+  return rc;
+}
+
+// One level of a Mesh whose levels are all cut at the root's x3 planes `cuts` (K_0 = 0 < .. < K_nslab = rootNx3; NULL: the equal
+// division above): p describes the caller's undivided Grid of the level, kdisp its x3 displacement in zones of the level.  Piece s
+// lies over the root planes [K_s, K_s+1) on the device of the root's slab s; a slab without zones of the level is absent.
+extern "C" int aa_create_cut(const aa_params *p, int kdisp, int nslab, const int *cuts_in, aa_grid **out)
+{
+  if (!p || !out) return aa_fail(-1, "[aa_create_cut]: null argument");
+  if (nslab < 1 || nslab > MC_MAXSLAB) return aa_fail(-1, "[aa_create_cut]: %d slabs (1 .. %d)", nslab, MC_MAXSLAB);
+  if (p->Nx[2] <= 1) return aa_fail(-1, "[aa_create_cut]: a 2-D Grid (Nx3 = 1) cannot be cut into x3 slabs");
+  if (p->level < 0 || p->level > 7) return aa_fail(-1, "[aa_create_cut]: level %d out of range", p->level);
+  if (p->level == 0 && kdisp != 0) return aa_fail(-1, "[aa_create_cut]: the root level has no displacement (kdisp = %d)", kdisp);
+  char msg[256] = "";
+  std::vector<int> cuts(nslab + 1);
+  if (cuts_in) for (int s = 0; s <= nslab; s++) cuts[s] = cuts_in[s];
+  else if (const char *e = getenv("AA_SLAB_CUTS")) {      // (drop-in executables: the planes by name, as AA_SLAB_DEVICES names the devices)
+    int n = 0;
+    for (const char *q = e; *q; ) { if (n <= nslab) cuts[n] = atoi(q); n++; while (*q && *q != ',') q++; if (*q) q++; }
+    if (n != nslab + 1) return aa_fail(-1, "[aa_create_cut]: AA_SLAB_CUTS names %d planes, %d slabs need %d", n, nslab, nslab + 1);
+  } else mc_equal_cuts(p->rootNx[2], nslab, cuts.data());
+  if (mc_check_cuts(p->rootNx[2], nslab, cuts.data(), msg, sizeof msg)) return aa_fail(-1, "[aa_create_cut]: %s", msg);
+  std::vector<int> k0, nk;
+  int s0 = -1;
+  for (int s = 0; s < nslab; s++) {
+    int a, b;
+    if (mc_span(p->level, p->Nx[2], kdisp, s, cuts.data(), &a, &b, msg, sizeof msg)) return aa_fail(-1, "[aa_create_cut]: %s", msg);
+    if (b <= a) continue;
+    if (s0 < 0) s0 = s;
+    k0.push_back(a - (p->level ? kdisp : 0)); nk.push_back(b - a);
+  }
+  if (s0 < 0) return aa_fail(-1, "[aa_create_cut]: level %d (kdisp %d, %d planes) lies outside the root Domain", p->level, kdisp, p->Nx[2]);
+  { int tot = 0; for (int n : nk) tot += n;
+    if (tot != p->Nx[2]) return aa_fail(-1, "[aa_create_cut]: level %d (kdisp %d, %d planes) is not inside the root Domain", p->level, kdisp, p->Nx[2]); }
+  const bool periodic = (p->bc[4] == AA_BC_PERIODIC && p->bc[5] == AA_BC_PERIODIC);
+  if (periodic && p->level > 0 && nk.size() > 1)
+    return aa_fail(-1, "[aa_create_cut]: level %d is periodic along x3: only a periodic ROOT wraps across the slabs", p->level);
+  int rc = slabs_create_pieces(p, k0, nk, s0, nslab, periodic && p->level == 0 && nk.size() > 1, out);
+  if (rc) return rc;
+  SlabLink *L = (*out)->link;
+  L->cuts = cuts; L->by_cuts = true; L->kdisp = p->level ? kdisp : 0;
   return 0;
 }
 
@@ -479,12 +503,20 @@ static int halo_post(aa_grid *g)
   return 0;
 }
 
-int slabs_bvals_mhd(aa_grid *g)
+int slabs_halo_finish(aa_grid *g) { return halo_finish(g); }
+int slabs_halo_exchange(aa_grid *g) { return halo_post(g); }
+
+int slabs_bvals_local(aa_grid *g)      // x1, x2, physical x3 of every slab; the exchange between the slabs is the caller's
 {
   DevGuard keep;
   SlabLink *L = g->link;
   HALO_FLUSH(g);
-  for (int s = 0; s < L->n; s++) { SLAB_DEV(L, s); int rc = aa_bvals_mhd(g->slab[s]); if (rc) return rc; }   // x1, x2, physical x3
+  for (int s = 0; s < L->n; s++) { SLAB_DEV(L, s); int rc = aa_bvals_mhd(g->slab[s]); if (rc) return rc; }
+  return 0;
+}
+int slabs_bvals_mhd(aa_grid *g)
+{
+  int rc = slabs_bvals_local(g); if (rc) return rc;
   return halo_post(g);          // after x1 and x2, all i and j incl. ghosts: the corners travel (bvals_mhd.c:170)
 }
 
@@ -506,7 +538,7 @@ int slabs_bvals_mhd_side(aa_grid *g, int dir, int side)
 }
 
 // ---- time step: new_dt.c:72-177 ----------------------------------------------------------------------
-static int cfl_all(aa_grid *g)
+int slabs_cfl_queue(aa_grid *g)
 {
   DevGuard keep;
   SlabLink *L = g->link;
@@ -518,6 +550,13 @@ static int cfl_all(aa_grid *g)
       launch_cfl(c->d, c->sc, c->st); }
     HIPCHK(hipMemcpyAsync(&L->hsc[s], c->sc, sizeof(DevScalars), hipMemcpyDeviceToHost, c->st));
   }
+  return 0;
+}
+static int cfl_all(aa_grid *g)
+{
+  DevGuard keep;
+  SlabLink *L = g->link;
+  { int rc = slabs_cfl_queue(g); if (rc) return rc; }
   for (int s = 0; s < L->n; s++) { SLAB_DEV(L, s); HIPCHK(hipStreamSynchronize(g->slab[s]->st)); }
   g->host_syncs++;
   return 0;
@@ -690,9 +729,9 @@ int slabs_ion_update(aa_grid *g, double dt, long long *cellcount, double *dt_hyd
   if (dt_hydro) *dt_hydro = h;
   return 0;
 }
-int slabs_ion_run_phased(aa_grid *g, double limit, int *niter_out, double *dt_done_out)
+int slabs_ion_run_phased(aa_grid *g, int fine, double limit, int *niter_out, double *dt_done_out)
 {
-  // ionrad_3d.c:862-1012, root level
+  // ionrad_3d.c:862-1012: the root level, or (fine) a refined level of a cut Mesh, which sub-cycles until it has covered `limit`
   double dt_chem, dt_therm, dt_hydro = 0, dt, dt_done = 0.0;
   long long cellcount = 0;
   int niter = 0, hydro_done = 0, rc;
@@ -704,6 +743,7 @@ int slabs_ion_run_phased(aa_grid *g, double limit, int *niter_out, double *dt_do
     if ((rc = slabs_ion_update(g, dt, &cellcount, &dt_hydro))) return rc;
     dt_done += dt;
     niter++;
+    if (fine) { if (hydro_done) { g->dt = dt_done; break; } continue; }
     if (cellcount > MAXCELLCOUNT) { g->dt = dt_done; break; }
     if (hydro_done) break;
     if (dt_hydro < dt_done) { g->dt = dt_done; break; }

@@ -19,11 +19,16 @@
 // A Mesh of 2-D Grids (Nx3 = 1 on every level; aa_mesh_create_2d) runs the same host control flow on kernels of its own --
 // k2d_restrict, k2d_flux_correct, k2d_box_copy, k2d_prolong: the nDim == 2 branches of smr.c -- and the 2-D integrators, whose
 // update kernel leaves the fluxes of the level-boundary lines in F (hydro2d_kernels.hip k2d_step_keep; integrate_2d_ctu.c:1722-1877).
+//
+// A Mesh whose levels are composite handles cut at the same root x3 planes (aa_create_cut) runs one such stack per device in ONE
+// process: the last part of this file (one local stack per slab + what crosses slabs; the cut arithmetic is mesh_cuts.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <vector>
 #include "api_internal.h"
+#include "mesh_cuts.h"
 
 using namespace aa;
 
@@ -368,7 +373,61 @@ k2d_prolong(DevGrid f, Link L, const Real *box, int dim_arg)
 
 inline unsigned nblk(long n, int b) { return (unsigned)((n + b - 1)/b); }
 
+// ---- a Mesh on in-library slabs: the x3 halo of ALL levels two neighbouring slabs share in one launch per slab.  What
+// k_pack_x3 / k_unpack_x3 (hydro_kernels.hip) do for one Grid -- four k-planes, all i and j, one lane per zone with i fastest, the
+// buffer of a level laid out [v][kk][j][i] -- for the levels in a row: level l's block starts nvar*first doubles into the buffer
+// (the same offset on both slabs: it depends on N1 x N2 of the coarser levels only).  side = blockIdx.y: 0 the lower neighbour,
+// 1 the upper one; the levels shared with a neighbour are a prefix of the slab's levels (nesting), nshare[side] of them. ----------
+struct HaloLev { Real *U; long sJ, sK, nc, first; int N1, N2, kp[2], ku[2]; };   // first: lanes before this level; kp / ku: first plane packed / unpacked per side
+struct HaloBatch { int nshare[2], nvar, pad; long total[2]; HaloLev lev[AA_MAXLEV]; };
+
+template <bool PACK>
+__global__ void __launch_bounds__(256)
+k_halo_levels(HaloBatch B, Real *buf0, Real *buf1)
+{
+  const int side = (int)blockIdx.y;
+  Real *buf = side ? buf1 : buf0;
+  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
+  if (!buf || lin >= B.total[side]) return;
+  int l = 0;
+  while (l + 1 < B.nshare[side] && lin >= B.lev[l + 1].first) l++;
+  const HaloLev &h = B.lev[l];
+  const long q = lin - h.first, plane = (long)h.N1*h.N2, ntot = plane*NG;
+  const int i = (int)(q % h.N1), j = (int)((q / h.N1) % h.N2), kk = (int)(q / plane);
+  const long m = (long)((PACK ? h.kp[side] : h.ku[side]) + kk)*h.sK + (long)j*h.sJ + i;
+  Real *b = buf + h.first*B.nvar + q;
+  for (int v = 0; v < B.nvar; v++) {
+    if (PACK) b[(long)v*ntot] = h.U[(long)v*h.nc + m];
+    else h.U[(long)v*h.nc + m] = b[(long)v*ntot];
+  }
+}
+
+// a flux correction that crosses a cut: the child's piece on slab src ends at the cut, the parent plane outside is on slab dst
+struct FluxMsg {
+  int l, side, src, dst, i0, j0, n1, n2;      // link l (level l+1 on level l); side of the child's boundary
+  Real *sbuf = nullptr, *rbuf = nullptr, *hbuf = nullptr;      // on src's device, on dst's device, pinned (staged route only)
+  hipEvent_t sent = nullptr, done = nullptr; bool done_valid = false;
+};
+
 }  // namespace
+
+// one local stack per slab (the aa_mesh_create_local machinery) plus what crosses slabs
+struct CutMesh {
+  int n = 0;                                  // slabs of the root
+  mc_mesh *mc = nullptr;                      // spans, links, corr_to / corr_in (mesh_cuts.h)
+  std::vector<aa_mesh*> local;                // local[s]: the pieces on slab s, root first
+  std::vector<int> dev;
+  bool staged = false;                        // no peer access between neighbours (or AA_SLAB_NO_PEER=1): through pinned host memory
+  bool batch = true;                          // AA_MESH_HALO_BATCH=0: the exchange of all levels as one exchange per level
+  std::vector<HaloBatch> hb;
+  std::vector<Real*> send[2], recv[2], hstage[2];
+  std::vector<hipEvent_t> packed, copied, unpacked, staged_ev;
+  std::vector<bool> copied_valid, unpacked_valid;
+  std::vector<hipStream_t> xfer, xout;
+  bool halo_due = false;
+  std::vector<FluxMsg> msgs;
+  long long counts[3] = {0, 0, 0};            // of the exchanges of all levels so far: pack + unpack launches, copies, exchanges
+};
 
 // Grids in the order of the reference's loops: level by level from the root, Domains of a level in deck order
 // (MeshS.Domain[nl][nd]).  Link L joins grid L+1 (the child) to grid par[L] (its parent); with one Domain per level par[L] = L.
@@ -390,24 +449,34 @@ struct aa_mesh {
   bool two_d = false;              // aa_mesh_create_2d: every level is a 2-D Grid (Nx3 = 1): the k2d_* kernels, the 2-D integrators
   double tcoarse = 0;              // ionrad_3d.c:44
   double time = 0, dt = 0; int nstep = 0;   // MeshS
+  CutMesh *cut = nullptr;          // the levels are composite handles cut at the same root planes (aa_create_cut): see the end of this file
 };
 
 extern "C" {
 
 void aa_mesh_destroy(aa_mesh *m);
+static int cut_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out);
+static void cut_destroy(aa_mesh *m);
+static int cut_restrict_correct_pair(aa_mesh *m, int l);
+static int cut_ionrad_restrict_correct(aa_mesh *m);
+static int cut_prolongate(aa_mesh *m);
+static int cut_new_dt(aa_mesh *m);
+static int cut_ionflux_prolong(aa_mesh *m, int l);
+static int cut_start(aa_mesh *m, bool with_dt);
+static int cut_step(aa_mesh *m, int *niter);
 // error paths of the create functions: the caller keeps its Grids as they were (mesh_alloc marked them as levels of a Mesh)
 static void mesh_drop(aa_mesh *m)
 {
   for (int l = 0; l < m->nl; l++) if (m->lev[l]) { m->lev[l]->keep_flux = false; m->lev[l]->keep = {0, {{0}}}; }
   delete m;
 }
-static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out)
+static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out, bool may_overlap = true)
 {
   hipError_t e = hipSetDevice(levels[0]->p.device);
   if (e == hipSuccess) e = hipStreamCreate(&m->st);
   if (e != hipSuccess) { mesh_drop(m); return aa_fail(-2, "[aa_mesh_create]: %s", hipGetErrorString(e)); }
   for (int l = 0; l < m->nl; l++) aa_set_stream(m->lev[l], (void*)m->st);
-  { const char *ev = getenv("AA_MESH_OVERLAP"); m->overlap = ev ? atoi(ev) != 0 : true; }
+  { const char *ev = getenv("AA_MESH_OVERLAP"); m->overlap = may_overlap && (ev ? atoi(ev) != 0 : true); }
   { const char *ev = getenv("AA_SMR_ONE_LAUNCH"); m->one_launch = ev ? atoi(ev) != 0 : true; }
   if (m->overlap && m->nl > 1) {
     e = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
@@ -461,7 +530,7 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels, bool two_d = false)
     aa_grid *g = levels[l];
     if (!g || (l == 0 ? g->level != 0 : (g->level < 1 || g->level < levels[l - 1]->level || g->level > levels[l - 1]->level + 1))) {
       mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: grids must come level by level from the root (grid %d)", l); return nullptr; }
-    if (!g->slab.empty()) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is cut into slabs (aa_params.nslab / AA_NGPU): nested levels stay on one device", l); return nullptr; }
+    if (!g->slab.empty()) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is cut into slabs: not available here (aa_mesh_create takes the levels of a Mesh cut at the root's planes, all made by aa_create_cut)", l); return nullptr; }
     if (g->p.device != levels[0]->p.device) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: all levels must live on one device"); return nullptr; }
     if (two_d) {      // aa_mesh_create_2d: what the reference's 2-D SMR targets (CTU + H-correction, van Leer) pin
       if (!g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] is a 3-D Grid: aa_mesh_create", l); return nullptr; }
@@ -484,6 +553,17 @@ static int mesh_create_nested(int nlevels, aa_grid **levels, const int *disp, aa
 {
   const int nd = two_d ? 2 : 3;      // directions with more than one zone
   if (!disp || !out) return aa_fail(-1, "[aa_mesh_create]: bad arguments");
+  if (levels && nlevels >= 1 && nlevels <= AA_MAXLEV) {      // composite handles: a Mesh on in-library slabs, or a refusal by name
+    int ncomp = 0;
+    for (int l = 0; l < nlevels; l++) if (levels[l] && levels[l]->link) ncomp++;
+    if (ncomp && two_d) return aa_fail(-1, "[aa_mesh_create_2d]: a Mesh of 2-D Grids cannot be cut into x3 slabs");
+    if (ncomp && ncomp != nlevels) {
+      int l = 0; while (levels[l] && (levels[l]->link != nullptr) == (levels[0]->link != nullptr)) l++;
+      return aa_fail(-1, "[aa_mesh_create]: levels[%d] is %s but levels[0] is %s: the levels of a Mesh are all plain Grids, or all cut at the same root planes (aa_create_cut)",
+                     l, levels[l]->link ? "cut into slabs" : "a plain Grid", levels[0]->link ? "cut into slabs" : "a plain Grid");
+    }
+    if (ncomp) return cut_create(nlevels, levels, disp, out);
+  }
   aa_mesh *m = mesh_alloc(nlevels, levels, two_d);
   if (!m) return -1;
   for (int c = 1; c < nlevels; c++) {
@@ -563,7 +643,14 @@ int aa_mesh_create_2d(int nlevels, aa_grid **levels, const int *disp, aa_mesh **
 // of level l+1 on level l.  A child slab may reach the edge of its parent slab; where the level
 // itself ends at that edge (prol=1, corr=0) the parent plane outside is corrected on the
 // neighbouring slab with aa_flux_x3_export / aa_flux_x3_apply.
+static int mesh_create_local(int nlevels, aa_grid **levels, const int *links, aa_mesh **out, bool may_overlap);
 int aa_mesh_create_local(int nlevels, aa_grid **levels, const int *links, aa_mesh **out)
+{
+  for (int l = 0; levels && l < nlevels && l < AA_MAXLEV; l++)
+    if (levels[l] && levels[l]->link) return aa_fail(-1, "[aa_mesh_create_local]: levels[%d] is cut into slabs: a rank's stack holds plain Grids (one process on several GPUs: aa_create_cut + aa_mesh_create)", l);
+  return mesh_create_local(nlevels, levels, links, out, true);
+}
+static int mesh_create_local(int nlevels, aa_grid **levels, const int *links, aa_mesh **out, bool may_overlap)
 {
   if ((nlevels > 1 && !links) || !out) return aa_fail(-1, "[aa_mesh_create_local]: bad arguments");
   aa_mesh *m = mesh_alloc(nlevels, levels);
@@ -583,12 +670,13 @@ int aa_mesh_create_local(int nlevels, aa_grid **levels, const int *links, aa_mes
     }
     for (int d = 0; d < 6; d++) { L.prol[d] = q[6 + d]; L.corr[d] = q[12 + d]; }
   }
-  return mesh_finish(m, levels, out);
+  return mesh_finish(m, levels, out, may_overlap);
 }
 
 void aa_mesh_destroy(aa_mesh *m)      // the levels stay alive and go back to the default stream
 {
   if (!m) return;
+  if (m->cut) { cut_destroy(m); return; }
   hipStreamSynchronize(m->st);
   for (int l = 0; l < m->nl; l++) {
     m->lev[l]->st = nullptr; m->lev[l]->own_stream = false; if (m->box[l]) hipFree(m->box[l]);
@@ -602,6 +690,7 @@ void aa_mesh_destroy(aa_mesh *m)      // the levels stay alive and go back to th
 
 int aa_mesh_set_stream(aa_mesh *m, void *hip_stream)   // run every level on a caller-owned stream
 {
+  if (m->cut) return aa_fail(-1, "[aa_mesh_set_stream]: a Mesh cut into slabs runs on its slabs' own streams");
   hipStreamSynchronize(m->st);
   if (m->own_stream) { hipStreamDestroy(m->st); m->own_stream = false; }
   m->st = (hipStream_t)hip_stream;
@@ -618,6 +707,7 @@ int aa_mesh_set_state(aa_mesh *m, double time, double dt, int nstep)
 // flux correction adds q*(0-0); here the flux arrays are zero-initialised, to the same effect.
 int aa_mesh_restrict_correct_pair(aa_mesh *m, int l)      // level l+1 -> level l
 {
+  if (m->cut) return cut_restrict_correct_pair(m, l);
   if (l >= 0 && l + 1 < m->nl) m->lev[m->par[l]]->active_dirty = true;
   if (l < 0 || l + 1 >= m->nl) return aa_fail(-1, "[aa_mesh_restrict_correct_pair]: pair %d", l);
   aa_grid *P = m->lev[m->par[l]], *C = m->lev[l + 1];       // link l: grid l+1 on its parent
@@ -668,6 +758,7 @@ int aa_mesh_restrict_correct(aa_mesh *m)
 int aa_mesh_ionrad_restrict_correct(aa_mesh *m)
 {
   if (m->two_d) return aa_fail(-1, "[aa_mesh_ionrad_restrict_correct]: a Mesh of 2-D Grids has no ion radiation (the reference has ionrad_3d only)");
+  if (m->cut) return cut_ionrad_restrict_correct(m);
   for (int l = 0; l < m->nl; l++) m->lev[l]->active_dirty = true;
   for (int q = 0; q + 1 < m->nl; q++) {
     const int l = m->f2c[q];
@@ -684,6 +775,7 @@ int aa_mesh_ionrad_restrict_correct(aa_mesh *m)
 // smr.c:2359
 int aa_mesh_prolongate(aa_mesh *m)
 {
+  if (m->cut) return cut_prolongate(m);
   for (int l = 0; l < m->nl; l++) {
     for (int c = 0; c + 1 < m->nl; c++) {      // Step 1: hand the zones around every child over
       if (m->par[c] != l) continue;
@@ -737,6 +829,7 @@ int aa_mesh_prolongate(aa_mesh *m)
 // new_dt.c:32 over all levels: max_v is carried from Grid to Grid (:33), one dt for the Mesh
 int aa_mesh_new_dt(aa_mesh *m)
 {
+  if (m->cut) return cut_new_dt(m);
   double cum[3] = {0.0, 0.0, 0.0}, max_dti = 0.0;
   const int ndir = m->two_d ? 2 : 3;      // new_dt.c:126-161: max_v3 only where Nx3 > 1
   for (int l = 0; l < m->nl; l++) {
@@ -764,6 +857,7 @@ int aa_mesh_ionflux_prolong(aa_mesh *m, int l)
 {
   if (m->two_d) return aa_fail(-1, "[aa_mesh_ionflux_prolong]: a Mesh of 2-D Grids has no ion radiation (the reference has ionrad_3d only)");
   if (l < 1 || l >= m->nl) return aa_fail(-1, "[aa_mesh_ionflux_prolong]: level %d", l);
+  if (m->cut) return cut_ionflux_prolong(m, l);
   const Link &L = m->link[l - 1];
   aa_grid *P = m->lev[m->par[l - 1]];
   { int rc = aa_edgeflux_ready(P); if (rc) return rc; }       // the parent's EdgeFlux of its last sweep
@@ -821,6 +915,7 @@ int aa_mesh_ion_radtransfer(aa_mesh *m, int l, int *niter_out)
 int aa_mesh_start(aa_mesh *m)
 {
   int rc;
+  if (m->cut) return cut_start(m, true);
   if ((rc = aa_mesh_restrict_correct(m))) return rc;
   for (int l = 0; l < m->nl; l++) {
     if ((rc = aa_bvals_mhd(m->lev[l]))) return rc;
@@ -834,6 +929,7 @@ int aa_mesh_start(aa_mesh *m)
 int aa_mesh_resume(aa_mesh *m)
 {
   int rc;
+  if (m->cut) return cut_start(m, false);
   if ((rc = aa_mesh_restrict_correct(m))) return rc;
   for (int l = 0; l < m->nl; l++) {
     if ((rc = aa_bvals_mhd(m->lev[l]))) return rc;
@@ -846,6 +942,7 @@ int aa_mesh_resume(aa_mesh *m)
 int aa_mesh_step(aa_mesh *m, int *niter)
 {
   int rc;
+  if (m->cut) return cut_step(m, niter);
   aa_grid *root = m->lev[0];
   if (root->p.ion && root->nradplane > 0) {                          // :546-562
     for (int l = 0; l < m->nl; l++) {
@@ -882,5 +979,423 @@ int aa_mesh_step(aa_mesh *m, int *niter)
   for (int l = 0; l < m->nl; l++) if ((rc = aa_bvals_mhd(m->lev[l]))) return rc;   // :635-644
   return aa_mesh_prolongate(m);                                       // :647
 }
+
+
+// ==== a Mesh on in-library slabs: one process, N devices =======================================================================
+// Every level is a composite handle of aa_create_cut, all cut at the same root planes: slab s of every level lives on the device
+// of the root's slab s, and the pieces on one device form a local stack (mesh_create_local with the links of mesh_cuts.h) on ONE
+// stream, so that the level coupling inside a device needs no events.  Restriction, the radiation hand-off and prolongation stay
+// inside a slab (prolongation reads the parent's ghost planes where a level starts exactly at a cut, so a posted halo is finished
+// first).  What crosses slabs: the x3 halo of every level, the flux correction of the parent plane that lies across a cut from
+// the child's boundary, and the scalar reductions.  The order is that of aa_mesh_step / aa_mesh_start above, with one difference
+// that keeps the cut run equal to the undivided one: the x3 exchange behind the radiation step is posted AFTER
+// ionradRestrictCorrect (the boundary conditions stay where they were), because a slab's ghost planes are its neighbour's ACTIVE
+// zones, which the restriction rewrites.  The levels integrate one after the other (no AA_MESH_OVERLAP on a cut Mesh).
+
+static aa_grid *cut_piece(aa_mesh *m, int l, int s)      // level l on root slab s (nullptr: no zones there)
+{
+  SlabLink *K = m->lev[l]->link;
+  const int si = s - K->s0;
+  return (si >= 0 && si < K->n) ? m->lev[l]->slab[si] : nullptr;
+}
+#define CUT_DEV(C, s) HIPCHK(hipSetDevice((C)->dev[s]))
+
+static void cut_destroy(aa_mesh *m)
+{
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  for (int s = 0; s < C->n; s++) {
+    if (s < (int)C->dev.size()) hipSetDevice(C->dev[s]);
+    if (s < (int)C->local.size() && C->local[s]) { hipStreamSynchronize(C->local[s]->st); }
+    if (s < (int)C->xfer.size() && C->xfer[s]) { hipStreamSynchronize(C->xfer[s]); hipStreamDestroy(C->xfer[s]); }
+    if (s < (int)C->xout.size() && C->xout[s]) { hipStreamSynchronize(C->xout[s]); hipStreamDestroy(C->xout[s]); }
+    for (int w = 0; w < 2; w++) {
+      if (s < (int)C->send[w].size() && C->send[w][s]) hipFree(C->send[w][s]);
+      if (s < (int)C->recv[w].size() && C->recv[w][s]) hipFree(C->recv[w][s]);
+      if (s < (int)C->hstage[w].size() && C->hstage[w][s]) hipHostFree(C->hstage[w][s]);
+    }
+    if (s < (int)C->packed.size() && C->packed[s]) hipEventDestroy(C->packed[s]);
+    if (s < (int)C->copied.size() && C->copied[s]) hipEventDestroy(C->copied[s]);
+    if (s < (int)C->unpacked.size() && C->unpacked[s]) hipEventDestroy(C->unpacked[s]);
+    if (s < (int)C->staged_ev.size() && C->staged_ev[s]) hipEventDestroy(C->staged_ev[s]);
+  }
+  for (FluxMsg &q : C->msgs) {
+    if (q.src < (int)C->dev.size()) { hipSetDevice(C->dev[q.src]); if (C->local[q.src]) hipStreamSynchronize(C->local[q.src]->st); }
+    if (q.dst < (int)C->dev.size()) { hipSetDevice(C->dev[q.dst]); if (C->local[q.dst]) hipStreamSynchronize(C->local[q.dst]->st); }
+    if (q.sbuf) { hipSetDevice(C->dev[q.src]); hipFree(q.sbuf); }
+    if (q.rbuf) { hipSetDevice(C->dev[q.dst]); hipFree(q.rbuf); }
+    if (q.hbuf) hipHostFree(q.hbuf);
+    if (q.sent) hipEventDestroy(q.sent);
+    if (q.done) hipEventDestroy(q.done);
+  }
+  for (int s = 0; s < (int)C->local.size(); s++) if (C->local[s]) { hipSetDevice(C->dev[s]); aa_mesh_destroy(C->local[s]); }
+  delete C->mc;
+  delete C;
+  delete m;
+}
+
+static int cut_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out)
+{
+  DevGuard keep;
+  SlabLink *R = levels[0]->link;
+  for (int l = 0; l < nlevels; l++) {
+    aa_grid *g = levels[l];
+    SlabLink *K = g->link;
+    if (!K->by_cuts) return aa_fail(-1, "[aa_mesh_create]: levels[%d] was cut by aa_create (aa_params.nslab / AA_NGPU): the levels of a cut Mesh come from aa_create_cut", l);
+    if (g->level != l) return aa_fail(-1, "[aa_mesh_create]: levels[%d] is on level %d: several Domains on a level are not cut across GPUs (one Domain per level on a cut Mesh)", l, g->level);
+    if (K->ntotal != R->ntotal || K->cuts != R->cuts) return aa_fail(-1, "[aa_mesh_create]: levels[%d] has different cuts than the root: all levels of a Mesh are cut at the same root planes", l);
+    for (int si = 0; si < K->n; si++)
+      if (K->dev[si] != R->dev[K->s0 + si]) return aa_fail(-1, "[aa_mesh_create]: slab %d of levels[%d] lives on HIP device %d, the root's on %d", K->s0 + si, l, K->dev[si], R->dev[K->s0 + si]);
+    if (l && K->kdisp != disp[3*l + 2]) return aa_fail(-1, "[aa_mesh_create]: levels[%d] was cut with kdisp = %d, the Mesh gives kDisp = %d", l, K->kdisp, disp[3*l + 2]);
+    if (g->keep_flux) return aa_fail(-1, "[aa_mesh_create]: levels[%d] already belongs to a Mesh", l);
+    if (g->p.integrator != levels[0]->p.integrator) return aa_fail(-1, "[aa_mesh_create]: levels[%d] has integrator %d, the root %d", l, g->p.integrator, levels[0]->p.integrator);
+  }
+  // the nesting rules of mesh_create_nested, on the undivided Domains
+  mc_level lev[AA_MAXLEV];
+  for (int l = 0; l < nlevels; l++) for (int d = 0; d < 3; d++) { lev[l].Nx[d] = levels[l]->p.Nx[d]; lev[l].disp[d] = l ? disp[3*l + d] : 0; }
+  for (int c = 1; c < nlevels; c++) {
+    const int irefine = 1 << c;
+    for (int d = 0; d < 3; d++) {
+      const int dc = lev[c].disp[d], nc = lev[c].Nx[d], dp = lev[c - 1].disp[d], np = lev[c - 1].Nx[d];
+      const int a = dc/2 - dp, b = (dc + nc)/2 - dp;
+      if ((dc & 1) || (nc & 1) || a < 0 || b > np) return aa_fail(-1, "[aa_mesh_create]: grid %d is not nested in grid %d along x%d", c, c - 1, d + 1);
+      const bool plo = (dc != 0), phi = ((dc + nc)/irefine != levels[c]->p.rootNx[d]);
+      if ((a == 0 && plo) || (b == np && phi)) return aa_fail(-1, "[init_mesh] child Domain (grid %d) touches its parent in x%d", c, d + 1);
+    }
+    if (levels[c - 1]->p.ion && (lev[c - 1].disp[1] || lev[c - 1].disp[2])) {
+      const char *e = getenv("AA_SMR_DEEP_RADIATION");
+      if (!(e && strcmp(e, "fixed") == 0))
+        return aa_fail(-1, "[aa_mesh_create]: radiation across a displaced parent (grid %d) is undefined in the reference "
+                           "(set AA_SMR_DEEP_RADIATION=fixed for the corrected hand-off)", c - 1);
+    }
+  }
+  aa_mesh *m = new aa_mesh();
+  CutMesh *C = new CutMesh();
+  m->cut = C; m->nl = nlevels; m->overlap = false; m->own_stream = false;
+  for (int l = 0; l < AA_MAXLEV; l++) { m->lev[l] = nullptr; m->box[l] = nullptr; }
+  for (int l = 0; l < nlevels; l++) { m->lev[l] = levels[l]; m->par[l] = l; for (int d = 0; d < 3; d++) m->disp[l][d] = lev[l].disp[d]; }
+  for (int l = 0; l + 1 < nlevels; l++) m->f2c[l] = nlevels - 2 - l;
+  C->n = R->ntotal; C->dev = R->dev; C->staged = R->staged;
+  C->mc = new mc_mesh();
+  char msg[256] = "";
+  const aa_params &p0 = levels[0]->p;
+  if (mc_build(C->mc, nlevels, lev, p0.rootNx, C->n, R->cuts.data(), p0.bc[4] == AA_BC_PERIODIC && p0.bc[5] == AA_BC_PERIODIC, msg, sizeof msg)) {
+    cut_destroy(m); return aa_fail(-1, "[aa_mesh_create]: %s", msg);
+  }
+  { const char *e = getenv("AA_MESH_HALO_BATCH"); C->batch = e ? atoi(e) != 0 : true; }
+  const int n = C->n, nvar = 5 + p0.nscal;
+#define CUT_CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cut_destroy(m); \
+  return aa_fail(-2, "[aa_mesh_create] HIP error %s at %s:%d: %s", #x, __FILE__, __LINE__, hipGetErrorString(e_)); } } while (0)
+  C->local.assign(n, nullptr);
+  for (int s = 0; s < n; s++) {
+    const mc_slab &S = C->mc->slab[s];
+    aa_grid *pieces[AA_MAXLEV]; int links[21*AA_MAXLEV];
+    for (int l = 0; l < S.nl; l++) {
+      pieces[l] = cut_piece(m, l, s);
+      SlabLink *K = levels[l]->link;
+      const int d3 = lev[l].disp[2];
+      if (!pieces[l] || K->k0[s - K->s0] != S.piece[l].k0 - d3 || K->nk[s - K->s0] != S.piece[l].k1 - S.piece[l].k0) {
+        cut_destroy(m); return aa_fail(-1, "[aa_mesh_create]: level %d on slab %d does not lie over the root's planes %d .. %d", l, s, R->cuts[s], R->cuts[s + 1]);
+      }
+    }
+    for (int l = 0; l + 1 < S.nl; l++) mc_link_ints(&S.link[l], links + 21*l);
+    CUT_CHK(hipSetDevice(C->dev[s]));
+    int rc = mesh_create_local(S.nl, pieces, links, &C->local[s], false);
+    if (rc) { C->local[s] = nullptr; cut_destroy(m); return rc; }
+  }
+  // the exchange of all levels in one launch per slab: buffers, events and streams as slabs.hip keeps them per Grid
+  C->hb.assign(n, HaloBatch());
+  C->packed.assign(n, nullptr); C->copied.assign(n, nullptr); C->unpacked.assign(n, nullptr); C->staged_ev.assign(n, nullptr);
+  C->copied_valid.assign(n, false); C->unpacked_valid.assign(n, false);
+  C->xfer.assign(n, nullptr); C->xout.assign(n, nullptr);
+  for (int w = 0; w < 2; w++) { C->send[w].assign(n, nullptr); C->recv[w].assign(n, nullptr); C->hstage[w].assign(n, nullptr); }
+  for (int s = 0; s < n; s++) {
+    const mc_slab &S = C->mc->slab[s];
+    HaloBatch &B = C->hb[s];
+    memset(&B, 0, sizeof B);
+    B.nvar = nvar;
+    long first = 0;
+    for (int l = 0; l < S.nl; l++) {
+      const aa_grid *g = cut_piece(m, l, s);
+      HaloLev &h = B.lev[l];
+      h.U = g->d.U; h.sJ = g->d.sJ; h.sK = g->d.sK; h.nc = g->d.nc; h.first = first; h.N1 = g->d.N1; h.N2 = g->d.N2;
+      h.kp[0] = g->d.ks; h.kp[1] = g->d.ke - NG + 1; h.ku[0] = g->d.ks - NG; h.ku[1] = g->d.ke + 1;
+      first += (long)g->d.N1*g->d.N2*NG;
+      if (S.piece[l].lo >= 0) { B.nshare[0] = l + 1; B.total[0] = first; }
+      if (S.piece[l].hi >= 0) { B.nshare[1] = l + 1; B.total[1] = first; }
+    }
+    CUT_CHK(hipSetDevice(C->dev[s]));
+    for (int w = 0; w < 2; w++) if (B.total[w] > 0) {
+      const size_t bytes = (size_t)B.total[w]*nvar*sizeof(Real);
+      CUT_CHK(hipMalloc(&C->send[w][s], bytes)); CUT_CHK(hipMalloc(&C->recv[w][s], bytes));
+      if (C->staged) CUT_CHK(hipHostMalloc(&C->hstage[w][s], bytes));
+    }
+    CUT_CHK(hipEventCreateWithFlags(&C->packed[s], hipEventDisableTiming));
+    CUT_CHK(hipEventCreateWithFlags(&C->copied[s], hipEventDisableTiming));
+    CUT_CHK(hipEventCreateWithFlags(&C->unpacked[s], hipEventDisableTiming));
+    CUT_CHK(hipStreamCreateWithFlags(&C->xfer[s], hipStreamNonBlocking));
+    if (C->staged) {
+      CUT_CHK(hipStreamCreateWithFlags(&C->xout[s], hipStreamNonBlocking));
+      CUT_CHK(hipEventCreateWithFlags(&C->staged_ev[s], hipEventDisableTiming));
+    }
+  }
+  // flux corrections that cross a cut (corr_in of the receiving slab names the sender)
+  for (int t = 0; t < n; t++) {
+    const mc_slab &S = C->mc->slab[t];
+    for (int q = 0; q < S.ncorr_in; q++) {
+      const mc_corr_in &ci = S.corr_in[q];
+      if (C->mc->slab[ci.src].link[ci.level].corr_to[ci.side] != t) { cut_destroy(m); return aa_fail(-1, "[aa_mesh_create]: flux correction tables disagree (level %d, slabs %d -> %d)", ci.level, ci.src, t); }
+      FluxMsg f;
+      f.l = ci.level; f.side = ci.side; f.src = ci.src; f.dst = t; f.i0 = ci.i0; f.j0 = ci.j0; f.n1 = ci.n1; f.n2 = ci.n2;
+      C->msgs.push_back(f);
+      FluxMsg &F = C->msgs.back();
+      const size_t bytes = (size_t)F.n1*F.n2*6*sizeof(Real);
+      CUT_CHK(hipSetDevice(C->dev[F.src]));
+      CUT_CHK(hipMalloc(&F.sbuf, bytes));
+      CUT_CHK(hipEventCreateWithFlags(&F.sent, hipEventDisableTiming));
+      CUT_CHK(hipSetDevice(C->dev[F.dst]));
+      CUT_CHK(hipMalloc(&F.rbuf, bytes));
+      CUT_CHK(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
+      if (C->staged) CUT_CHK(hipHostMalloc(&F.hbuf, bytes));
+    }
+  }
+#undef CUT_CHK
+  *out = m;
+  return 0;
+}
+
+static int cut_restrict_correct_pair(aa_mesh *m, int l)
+{
+  if (l < 0 || l + 1 >= m->nl) return aa_fail(-1, "[aa_mesh_restrict_correct_pair]: pair %d", l);
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  for (int s = 0; s < C->n; s++) {
+    if (C->mc->slab[s].nl <= l + 1) continue;
+    CUT_DEV(C, s);
+    int rc = aa_mesh_restrict_correct_pair(C->local[s], l); if (rc) return rc;
+  }
+  for (FluxMsg &F : C->msgs) {
+    if (F.l != l) continue;
+    const size_t bytes = (size_t)F.n1*F.n2*6*sizeof(Real);
+    aa_grid *ch = cut_piece(m, l + 1, F.src), *pa = cut_piece(m, l, F.dst);
+    hipStream_t ss = C->local[F.src]->st, ds = C->local[F.dst]->st;
+    CUT_DEV(C, F.src);
+    if (F.done_valid) HIPCHK(hipStreamWaitEvent(ss, F.done, 0));            // the previous message has left sbuf
+    hipLaunchKernelGGL(k_flux_x3_export, dim3(nblk((long)F.n1*F.n2, 256)), dim3(256), 0, ss, ch->d, F.side, F.sbuf);
+    if (C->staged) HIPCHK(hipMemcpyAsync(F.hbuf, F.sbuf, bytes, hipMemcpyDeviceToHost, ss));
+    HIPCHK(hipEventRecord(F.sent, ss));
+    CUT_DEV(C, F.dst);
+    HIPCHK(hipStreamWaitEvent(ds, F.sent, 0));
+    if (C->staged) HIPCHK(hipMemcpyAsync(F.rbuf, F.hbuf, bytes, hipMemcpyHostToDevice, ds));
+    else if (C->dev[F.src] == C->dev[F.dst]) HIPCHK(hipMemcpyAsync(F.rbuf, F.sbuf, bytes, hipMemcpyDeviceToDevice, ds));
+    else HIPCHK(hipMemcpyPeerAsync(F.rbuf, C->dev[F.dst], F.sbuf, C->dev[F.src], bytes, ds));
+    HIPCHK(hipEventRecord(F.done, ds)); F.done_valid = true;
+    pa->active_dirty = true;
+    hipLaunchKernelGGL(k_flux_x3_apply, dim3(nblk((long)F.n1*F.n2, 256)), dim3(256), 0, ds, pa->d, F.side, F.i0, F.j0, F.n1, F.n2,
+                       5 + pa->p.nscal, (Real)pa->dt, F.rbuf);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int cut_ionrad_restrict_correct(aa_mesh *m)
+{
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  for (int s = 0; s < C->n; s++) { CUT_DEV(C, s); int rc = aa_mesh_ionrad_restrict_correct(C->local[s]); if (rc) return rc; }
+  return 0;
+}
+
+static int cut_ionflux_prolong(aa_mesh *m, int l)
+{
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  for (int s = 0; s < C->n; s++) {
+    if (C->mc->slab[s].nl <= l) continue;
+    CUT_DEV(C, s);
+    int rc = aa_mesh_ionflux_prolong(C->local[s], l); if (rc) return rc;
+  }
+  return 0;
+}
+
+// the ghost planes of the exchange of all levels are written (MPI_Waitall + unpack of every level, one launch per slab)
+static int cut_halo_finish(aa_mesh *m)
+{
+  CutMesh *C = m->cut;
+  if (!C->halo_due) return 0;
+  C->halo_due = false;
+  DevGuard keep;
+  for (int r = 0; r < C->n; r++) {
+    const HaloBatch &B = C->hb[r];
+    if (B.total[0] == 0 && B.total[1] == 0) continue;
+    CUT_DEV(C, r);
+    hipStream_t st = C->local[r]->st;
+    HIPCHK(hipStreamWaitEvent(st, C->copied[r], 0));
+    const long tot = B.total[0] > B.total[1] ? B.total[0] : B.total[1];
+    hipLaunchKernelGGL(k_halo_levels<false>, dim3(nblk(tot, 256), 2), dim3(256), 0, st, B,
+                       B.total[0] ? C->recv[0][r] : (Real*)nullptr, B.total[1] ? C->recv[1][r] : (Real*)nullptr);
+    HIPCHK(hipEventRecord(C->unpacked[r], st));
+    C->unpacked_valid[r] = true;
+    C->counts[0]++;
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// bvals_mhd of every level (main.c:635-644, :412-440): the boundary conditions of every piece, then the x3 halo of all levels --
+// ONE pack launch per slab, ONE copy per neighbour, ONE unpack launch per slab (cut_halo_finish); with AA_MESH_HALO_BATCH=0 one
+// exchange per level through the levels' own buffers (slabs.hip)
+static int cut_exchange_all(aa_mesh *m, bool with_bc)
+{
+  CutMesh *C = m->cut;
+  int rc;
+  if ((rc = cut_halo_finish(m))) return rc;
+  for (int l = 0; l < m->nl; l++) {
+    if (with_bc) { if ((rc = slabs_bvals_local(m->lev[l]))) return rc; }
+    else if ((rc = slabs_halo_finish(m->lev[l]))) return rc;
+  }
+  if (!C->batch) {
+    for (int l = 0; l < m->nl; l++) if ((rc = slabs_halo_exchange(m->lev[l]))) return rc;
+    return 0;
+  }
+  DevGuard keep;
+  const int nvar = C->hb[0].nvar;
+  bool any = false;
+  for (int s = 0; s < C->n; s++) {
+    const HaloBatch &B = C->hb[s];
+    if (B.total[0] == 0 && B.total[1] == 0) continue;
+    any = true;
+    CUT_DEV(C, s);
+    hipStream_t st = C->local[s]->st;
+    const mc_piece &root = C->mc->slab[s].piece[0];
+    // my send buffers are free once both neighbours have pulled the previous exchange out of them
+    for (int o : {root.lo, root.hi}) if (o >= 0 && C->copied_valid[o]) HIPCHK(hipStreamWaitEvent(st, C->copied[o], 0));
+    const long tot = B.total[0] > B.total[1] ? B.total[0] : B.total[1];
+    hipLaunchKernelGGL(k_halo_levels<true>, dim3(nblk(tot, 256), 2), dim3(256), 0, st, B,
+                       B.total[0] ? C->send[0][s] : (Real*)nullptr, B.total[1] ? C->send[1][s] : (Real*)nullptr);
+    HIPCHK(hipEventRecord(C->packed[s], st));
+    C->counts[0]++;
+    if (C->staged) {
+      HIPCHK(hipStreamWaitEvent(C->xout[s], C->packed[s], 0));
+      for (int w = 0; w < 2; w++) if (B.total[w])
+        HIPCHK(hipMemcpyAsync(C->hstage[w][s], C->send[w][s], (size_t)B.total[w]*nvar*sizeof(Real), hipMemcpyDeviceToHost, C->xout[s]));
+      HIPCHK(hipEventRecord(C->staged_ev[s], C->xout[s]));
+    }
+  }
+  for (int r = 0; r < C->n; r++) {
+    const HaloBatch &B = C->hb[r];
+    if (B.total[0] == 0 && B.total[1] == 0) continue;
+    CUT_DEV(C, r);
+    hipStream_t x = C->xfer[r];
+    const mc_piece &root = C->mc->slab[r].piece[0];
+    if (C->unpacked_valid[r]) HIPCHK(hipStreamWaitEvent(x, C->unpacked[r], 0));     // my recv buffers are free
+    for (int w = 0; w < 2; w++) {
+      if (!B.total[w]) continue;
+      const int o = w ? root.hi : root.lo;      // my lower ghost planes are the lower neighbour's upper planes, and the other way round
+      const size_t bytes = (size_t)B.total[w]*nvar*sizeof(Real);
+      HIPCHK(hipStreamWaitEvent(x, C->staged ? C->staged_ev[o] : C->packed[o], 0));
+      if (C->staged) HIPCHK(hipMemcpyAsync(C->recv[w][r], C->hstage[1 - w][o], bytes, hipMemcpyHostToDevice, x));
+      else if (C->dev[r] == C->dev[o]) HIPCHK(hipMemcpyAsync(C->recv[w][r], C->send[1 - w][o], bytes, hipMemcpyDeviceToDevice, x));
+      else HIPCHK(hipMemcpyPeerAsync(C->recv[w][r], C->dev[r], C->send[1 - w][o], C->dev[o], bytes, x));
+      C->counts[1]++;
+    }
+    HIPCHK(hipEventRecord(C->copied[r], x));
+    C->copied_valid[r] = true;
+  }
+  C->halo_due = any;
+  C->counts[2]++;
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int cut_halo_flush(aa_mesh *m)      // every posted exchange, of all levels or of one, has written its ghost planes
+{
+  int rc = cut_halo_finish(m); if (rc) return rc;
+  for (int l = 0; l < m->nl; l++) if ((rc = slabs_halo_finish(m->lev[l]))) return rc;
+  return 0;
+}
+
+static int cut_prolongate(aa_mesh *m)
+{
+  int rc = cut_halo_flush(m); if (rc) return rc;      // k_box_copy reads the parent's ghost planes where a child starts at a cut
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  for (int s = 0; s < C->n; s++) { CUT_DEV(C, s); if ((rc = aa_mesh_prolongate(C->local[s]))) return rc; }
+  return 0;
+}
+
+// new_dt.c:32 over all levels: every piece leaves its maxima in pinned memory, ONE wait, then the host folds -- MAX over the
+// slabs of a level, carried from level to level as aa_mesh_new_dt does
+static int cut_new_dt(aa_mesh *m)
+{
+  DevGuard keep;
+  CutMesh *C = m->cut;
+  int rc;
+  for (int l = 0; l < m->nl; l++) if ((rc = slabs_cfl_queue(m->lev[l]))) return rc;
+  for (int s = 0; s < C->n; s++) { CUT_DEV(C, s); HIPCHK(hipStreamSynchronize(C->local[s]->st)); }
+  m->lev[0]->host_syncs++;
+  double cum[3] = {0.0, 0.0, 0.0}, max_dti = 0.0;
+  for (int l = 0; l < m->nl; l++) {
+    const SlabLink *K = m->lev[l]->link;
+    for (int d = 0; d < 3; d++)
+      for (int si = 0; si < K->n; si++) { const double v = bits_to_double(K->hsc[si].max_v[d]); cum[d] = (cum[d] > v) ? cum[d] : v; }
+    for (int d = 0; d < 3; d++) { const double q = cum[d]/m->lev[l]->slab[0]->d.dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
+  }
+  const aa_params &p = m->lev[0]->p;
+  const double dtc = p.cour_no/max_dti;
+  if (m->nstep == 0) m->dt = dtc; else m->dt = (2.0*m->dt < dtc) ? 2.0*m->dt : dtc;
+  if ((m->time < p.tlim) && ((p.tlim - m->time) < m->dt)) m->dt = p.tlim - m->time;
+  for (int l = 0; l < m->nl; l++) { m->lev[l]->dt = m->dt; slabs_push_state(m->lev[l]); }
+  return 0;
+}
+
+static int cut_start(aa_mesh *m, bool with_dt)      // aa_mesh_start / aa_mesh_resume
+{
+  int rc;
+  if ((rc = aa_mesh_restrict_correct(m))) return rc;
+  if ((rc = cut_exchange_all(m, true))) return rc;
+  for (int l = 0; l < m->nl; l++) if ((rc = aa_bvals_ionrad(m->lev[l]))) return rc;
+  if ((rc = cut_prolongate(m))) return rc;
+  return with_dt ? cut_new_dt(m) : 0;
+}
+
+static int cut_step(aa_mesh *m, int *niter)         // aa_mesh_step
+{
+  int rc;
+  aa_grid *root = m->lev[0];
+  if (root->p.ion && root->nradplane > 0) {
+    for (int l = 0; l < m->nl; l++) {
+      int n = 0;
+      m->lev[l]->time = m->time;
+      if ((rc = aa_mesh_ion_radtransfer(m, l, &n))) return rc;
+      if (niter) niter[l] = n;
+      if ((rc = slabs_bvals_local(m->lev[l]))) return rc;       // (the exchange follows the restriction: see the head of this part)
+    }
+    if ((rc = cut_ionrad_restrict_correct(m))) return rc;
+    if ((rc = cut_exchange_all(m, false))) return rc;
+  } else if (niter) for (int l = 0; l < m->nl; l++) niter[l] = 0;
+  if ((rc = cut_halo_flush(m))) return rc;
+  for (int l = 0; l < m->nl; l++) {
+    aa_grid *g = m->lev[l];
+    if ((rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g)))) return rc;
+  }
+  if ((rc = aa_mesh_restrict_correct(m))) return rc;
+  for (int l = 0; l < m->nl; l++)
+    if (m->lev[l]->npin > 0 && (rc = aa_apply_pinned_cells(m->lev[l]))) return rc;
+  m->nstep++; m->time += m->dt;
+  for (int l = 0; l < m->nl; l++) { m->lev[l]->time = m->time; m->lev[l]->nstep = m->nstep; }
+  if ((rc = cut_new_dt(m))) return rc;
+  if ((rc = cut_exchange_all(m, true))) return rc;
+  return cut_prolongate(m);
+}
+
+// launches (pack + unpack), copies and exchanges of the all-level x3 exchanges of a cut Mesh so far (zeros on any other Mesh, and
+// with AA_MESH_HALO_BATCH=0, where every level exchanges through its own Grid's kernels)
+int aa_mesh_halo_counts(const aa_mesh *m, long long out[3])
+{
+  for (int q = 0; q < 3; q++) out[q] = m->cut ? m->cut->counts[q] : 0;
+  return 0;
+}
+int aa_mesh_nslab(const aa_mesh *m) { return m->cut ? m->cut->n : 1; }
 
 }  // extern "C"

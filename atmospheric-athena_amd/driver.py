@@ -669,7 +669,13 @@ class MeshRun(_Runner):
     aa_mesh_step): what outputs.run / OutputSet.data_output need -- time, nstep, start, step and the three writers, which loop
     over the Domains like dump_vtk / dump_binary / dump_history / dump_restart do."""
 
-    def __init__(self, mesh, run: RunConfig):
+    def __init__(self, mesh, run: RunConfig, nslab: int = 1, cuts=None, device: int = 0, strict: Optional[bool] = None):
+        """mesh: a lib.Mesh, or the levels (config.levels) to build one from -- with nslab > 1 / cuts every level cut at the
+        same root x3 planes inside the library, one slab stack per GPU; the outputs go through the composite level handles
+        as they are (hst per level, bin / vtk under lev<l>/, one .rst with all levels)."""
+        if isinstance(mesh, (list, tuple)):
+            from . import lib
+            mesh = lib.Mesh(list(mesh), device, strict, nslab=nslab, cuts=cuts)
         self.mesh, self.run = mesh, run
         self._hst = {}
         self.restarted = False
@@ -677,13 +683,14 @@ class MeshRun(_Runner):
 
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
-                     device: int = 0, strict: Optional[bool] = None) -> "MeshRun":
-        """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770)."""
+                     device: int = 0, strict: Optional[bool] = None, nslab: int = 1, cuts=None) -> "MeshRun":
+        """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770).
+        nslab / cuts: resume on a Mesh cut into slabs inside the library, whatever wrote the file (lib.Mesh)."""
         from . import lib
         head, par, run = cls._resume_head(path, overrides, problem, integrator, order)
         grids = config.levels_2d(par, run) if run.ndim == 2 else config.levels(par, run)      # by the file's table: Nx3 = 1 is a 2-D Mesh
         head["levels"] = restart.index_sections(head, [g.Nx for g in grids], run.nscal, run.ion)
-        m = cls(lib.Mesh(grids, device, strict, initial=False), run)
+        m = cls(lib.Mesh(grids, device, strict, initial=False, nslab=nslab, cuts=cuts), run)
         with open(path, "rb") as f:
             f.seek(head["offset"])
             for g in m.mesh.lev:

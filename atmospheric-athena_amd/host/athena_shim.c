@@ -102,6 +102,7 @@ static double tcoarse_ = 0.0;       /* ionrad_3d.c:44 */
 static int host_newer[MAXLEV];      /* the host block of this level holds data the device has not seen */
 static int active_same[MAXLEV];     /* host and device agree on the ACTIVE zones of this level (only ghost zones may differ) */
 static int learn = 0, learned = 0, sync_every = 1;
+static int nslab_mesh = 1;      /* AA_NGPU with nested levels: slabs every level is cut into (aa_create_cut) */
 /* AA_COHERENCE=auto: the write set of Userwork_in_loop must repeat before it is trusted; the output schedule */
 static int automode = 0, gave_up = 0;
 /* auto, after the imprint is trusted: the copy of it that re-validation compares against, and when to look again */
@@ -294,6 +295,16 @@ static void ensure_grid(MeshS *pM)
      * since it has the 2-D integrators, stays refused here */
     if (p.Nx[0] <= 1 || p.Nx[1] <= 1 || p.Nx[2] <= 1)
       ath_error("[athena_amd]: the drop-in shim is 3-D only: Nx1=%d, Nx2=%d, Nx3=%d\n", p.Nx[0], p.Nx[1], p.Nx[2]);
+#if defined(AA_SMR) && !defined(AA_MPI)
+    /* AA_NGPU=N > 1 with nested levels: every Domain's Grid is cut at the same root x3 planes, one slab stack per GPU, inside the
+     * library (aa_create_cut; AA_SLAB_CUTS=0,..,Nx3 in the environment names the planes, else the root's equal division); aa_mesh_create below
+     * takes the composite handles as it takes plain ones */
+    env = getenv("AA_NGPU");
+    if (env && atoi(env) > 1 && pM->NLevels > 1) {
+      nslab_mesh = atoi(env);
+      CHK(aa_create_cut(&p, pD->Disp[2], nslab_mesh, NULL, &G[l]));      /* (NULL: the library reads AA_SLAB_CUTS itself) */
+    } else
+#endif
     CHK(aa_create(&p, &G[l]));
     ncell[l] = (size_t)(PG[l]->Nx[0] + 2*AA_NGHOST)*(PG[l]->Nx[1] + 2*AA_NGHOST)*(PG[l]->Nx[2] + 2*AA_NGHOST);
     host_newer[l] = 1; snap[l] = NULL;
@@ -306,6 +317,9 @@ static void ensure_grid(MeshS *pM)
     if (env && atoi(env) > 1 && pM->NLevels == 1)   /* the library cuts the Grid into x3 slabs, one per GPU (csrc/slabs.hip) */
       fprintf(stderr, "[athena_amd] Grid %dx%dx%d in %d slabs along x3 on HIP devices %d.., %.2f GB resident, coherence=%s\n",
               p.Nx[0], p.Nx[1], p.Nx[2], atoi(env), p.device, aa_device_bytes(G[l])/1e9, automode ? "auto" : (learn ? "learn" : "step"));
+    else if (nslab_mesh > 1)                        /* ... every level of the Mesh at the same root planes (aa_create_cut) */
+      fprintf(stderr, "[athena_amd] Grid %dx%dx%d (level %d) in %d slabs along x3 on HIP devices %d.., %.2f GB resident, coherence=%s\n",
+              p.Nx[0], p.Nx[1], p.Nx[2], l, nslab_mesh, p.device, aa_device_bytes(G[l])/1e9, automode ? "auto" : (learn ? "learn" : "step"));
     else
     fprintf(stderr, "[athena_amd] Grid %dx%dx%d (level %d) on HIP device %d, %.2f GB resident, coherence=%s\n",
             p.Nx[0], p.Nx[1], p.Nx[2], l, p.device, aa_device_bytes(G[l])/1e9, automode ? "auto" : (learn ? "learn" : "step"));

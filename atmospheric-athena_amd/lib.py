@@ -81,6 +81,8 @@ def load(strict: bool | None = None) -> C.CDLL:
     dp = C.POINTER(C.c_double); ip = C.POINTER(C.c_int); llp = C.POINTER(C.c_longlong)
     sig = {
         "aa_create": (I, [C.POINTER(aa_params), C.POINTER(P)]),
+        "aa_create_cut": (I, [C.POINTER(aa_params), I, I, ip, C.POINTER(P)]),
+        "aa_mesh_nslab": (I, [P]), "aa_mesh_halo_counts": (I, [P, llp]),
         "aa_destroy": (None, [P]),
         "aa_last_error": (C.c_char_p, []),
         "aa_set_stream": (I, [P, P]),
@@ -188,18 +190,24 @@ def params_from_grid(g: GridConfig, device: int = 0, ion_path: int = 0, nslab: i
 class Grid:
     """Device-resident Grid.  Method names follow the reference's call sites."""
 
-    def __init__(self, grid: GridConfig, device: int = 0, strict: bool | None = None, ion_path: int = 0, nslab: int = 1):
-        """nslab > 1: the Grid is cut into x3 slabs inside the library (aa_params.nslab), one per GPU."""
+    def __init__(self, grid: GridConfig, device: int = 0, strict: bool | None = None, ion_path: int = 0, nslab: int = 1, cuts=None):
+        """nslab > 1: the Grid is cut into x3 slabs inside the library (aa_params.nslab), one per GPU.
+        cuts (root planes K_0 = 0 .. K_nslab = rootNx3): the Grid is one level of a Mesh cut at those planes (aa_create_cut)."""
         self.cfg = grid
         self.L = load(strict)
-        self.params = params_from_grid(grid, device, ion_path, nslab)
+        self.params = params_from_grid(grid, device, ion_path, 1 if cuts is not None else nslab)
         self.nvar = 5 + grid.run.nscal
         # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, init_grid.c:144-174)
         self.N = tuple(n + 2 * NGHOST if n > 1 else 1 for n in grid.Nx)
         self.ndim = sum(1 for n in grid.Nx if n > 1)
         h = C.c_void_p()
         self._h = None
-        self._chk(self.L.aa_create(C.byref(self.params), C.byref(h)))
+        if cuts is not None:
+            cuts = [int(k) for k in cuts]
+            self._chk(self.L.aa_create_cut(C.byref(self.params), int(grid.disp[2]) if grid.level else 0, len(cuts) - 1,
+                                           (C.c_int * len(cuts))(*cuts), C.byref(h)))
+        else:
+            self._chk(self.L.aa_create(C.byref(self.params), C.byref(h)))
         self._h = h
         self._keep = []
 
@@ -538,12 +546,12 @@ class Grid:
 
 
 def setup_problem(grid: GridConfig, device: int = 0, strict: bool | None = None, ion_path: int = 0, nslab: int = 1,
-                  initial: bool = True) -> Grid:
+                  initial: bool = True, cuts=None) -> Grid:
     """problem(DomainS*) of the reference for the shipped decks: fill the host block with the
     C problem generator, upload it, register the hooks (main.c:393).  initial = False is problem_read_restart
     (ioniz_sphere.c:191-239): the hooks only -- no host block is built, the state comes from a restart dump."""
     r = grid.run; pr = r.prob
-    g = Grid(grid, device, strict, ion_path, nslab)
+    g = Grid(grid, device, strict, ion_path, nslab, cuts)
     if getattr(r, "fofc", False):
         try:
             g.set_fofc(True)
@@ -598,10 +606,29 @@ class Mesh:
     names follow the reference: RestrictCorrect, Prolongate (smr.c), new_dt, and the per-level
     ion_radtransfer_3d with its coarse -> fine EdgeFlux hand-off (ionrad_smr.c)."""
 
-    def __init__(self, grids, device: int = 0, strict: bool | None = None, links=None, ion_path: int = 0, initial: bool = True):
+    def __init__(self, grids, device: int = 0, strict: bool | None = None, links=None, ion_path: int = 0, initial: bool = True,
+                 nslab: int = 1, cuts=None):
         """links: config.LinkConfig list for one rank's stack of slabs (multi-GPU SMR); None = the whole Mesh.
-        initial = False: the hooks only, the state of every level comes from a restart dump (setup_problem)."""
-        self.lev = [setup_problem(g, device, strict, ion_path, initial=initial) for g in grids]
+        initial = False: the hooks only, the state of every level comes from a restart dump (setup_problem).
+        nslab > 1 (or cuts given): every level is cut at the same root x3 planes, one slab stack per GPU, inside the library
+        (aa_create_cut + aa_mesh_create); cuts = None: config.balanced_cuts(grids, nslab)."""
+        from . import config
+        if cuts is not None:
+            nslab = len(cuts) - 1
+        self.nslab = int(nslab)
+        self.cuts = None
+        if self.nslab > 1 or cuts is not None:
+            if links is not None:
+                raise AthenaError("[Mesh]: a rank's stack of slabs (links) is not cut again inside the library")
+            self.cuts = tuple(int(k) for k in (cuts if cuts is not None else config.balanced_cuts(list(grids), self.nslab)))
+        self.lev = []
+        try:
+            for g in grids:
+                self.lev.append(setup_problem(g, device, strict, ion_path, initial=initial, cuts=self.cuts))
+        except Exception:
+            for g in self.lev:
+                g.close()
+            raise
         self.L = self.lev[0].L
         n = len(grids)
         hs = (C.c_void_p * n)(*[g._h for g in self.lev])
@@ -692,6 +719,10 @@ class Mesh:
                 g.write_dump(os.path.join(rundir, rel), fmt, prim, level=l, domain=d, time=t, dt=dt)
                 out.append(rel)
         return out
+
+    def halo_counts(self):
+        """(pack + unpack launches, copies, exchanges) of the all-level x3 exchanges of a cut Mesh so far"""
+        c = (C.c_longlong * 3)(); self._chk(self.L.aa_mesh_halo_counts(self._h, c)); return int(c[0]), int(c[1]), int(c[2])
 
     def step(self):
         it = (C.c_int * len(self.lev))()

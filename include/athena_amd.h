@@ -65,9 +65,20 @@ typedef struct aa_grid aa_grid;
  *      ion_radtransfer_init_3d (ionrad_3d.c:739), ion_radtransfer_init (ionrad.c:64)      */
 /* aa_params.nslab > 1 (or AA_NGPU=N in the environment): the handle stands for the caller's ONE Grid cut into N x3 slabs, one
  * per HIP device (AA_SLAB_DEVICES=0,1,.. or p->device, +1, .. modulo the visible ones; csrc/slabs.hip).  Root level only
- * (aa_mesh_create refuses it), >= 4 planes per slab, <= 64 slabs; aa_pack_x3 / aa_unpack_x3 / aa_set_stream return an error
+ * (the levels of a Mesh on several devices come from aa_create_cut), >= 4 planes per slab, <= 64 slabs; aa_pack_x3 / aa_unpack_x3 / aa_set_stream return an error
  * on it and aa_halo_doubles 0 (the slabs exchange their halos themselves); the caller's current device is left unchanged. */
 int         aa_create(const aa_params *p, aa_grid **out);
+/* One level of a Mesh whose levels are ALL cut at the same root x3 planes, one slab stack per HIP device, in one process.  `p`
+ * describes the caller's undivided Grid of the level (its Nx, MinX, bc, level), kdisp is its <domainN> kDisp in zones of the
+ * level (0 for the root), cuts[0..nslab] the root planes K_0 = 0 < .. < K_nslab = rootNx3 (NULL: AA_SLAB_CUTS=0,..,Nx3 from the
+ * environment if set, else the equal division aa_create uses).  The handle is a composite like aa_create's: slab s holds the level's zones over the root planes [K_s, K_s+1) and lives
+ * on the device of the root's slab s (AA_SLAB_DEVICES, or p->device + s modulo the visible ones); a slab without zones of the
+ * level is absent.  Everything a composite handle forwards works on it, scattered and gathered by k-plane range; gravity and
+ * pinned-zone positions are those of the undivided Grid.  A piece thinner than nghost is an error that names the level, the slab
+ * and the cut; bc[4] / bc[5] become AA_BC_NONE on interior cuts; a periodic root wraps.  Refused: 2-D Grids, a refined level
+ * that is periodic along x3.  aa_mesh_create takes such handles (see there); plain aa_create keeps refusing level > 0 with
+ * nslab > 1.  The arithmetic is csrc/mesh_cuts.h (plain C, no device). */
+int         aa_create_cut(const aa_params *p, int kdisp, int nslab, const int *cuts, aa_grid **out);
 void        aa_destroy(aa_grid *g);   /* integrate_destruct_3d :3498 */
 const char *aa_last_error(void);
 int         aa_set_stream(aa_grid *g, void *hip_stream);   /* run on a caller-owned stream */
@@ -219,6 +230,19 @@ int aa_device_count(void);                                               /* visi
 typedef struct aa_mesh aa_mesh;
 int  aa_mesh_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out); /* init_grid.c overlap
                                                           tables (:150-560) + SMR_init (smr.c:2931)  */
+/* A Mesh on several devices in ONE process: all levels made by aa_create_cut on the same cuts and devices, one Domain per level.
+ * Inside there is one local stack per device (the aa_mesh_create_local machinery, all pieces of a device on one stream) plus
+ * what crosses slabs: the x3 halo of every level (peer copies ordered by events, or pinned host memory where peer access is
+ * refused or AA_SLAB_NO_PEER=1; where all levels exchange in a row -- the end of aa_mesh_step, aa_mesh_start -- ONE pack launch
+ * per slab, ONE copy per neighbour and ONE unpack launch per slab for all levels two slabs share; AA_MESH_HALO_BATCH=0: one
+ * exchange per level), the flux correction of a parent plane across a cut, new_dt's maxima (one wait per step) and the
+ * radiation sub-cycle's words per level.  Every aa_mesh_* function below works on it with the same signature, except
+ * aa_mesh_set_stream (an error, as aa_set_stream on a composite).  The levels integrate one after the other (AA_MESH_OVERLAP
+ * does not apply).  Refused by name: mixed plain / composite levels, composites of plain aa_create, different cuts or devices,
+ * several Domains on a level, 2-D Grids, fofc, aa_mesh_create_local on composites.                                            */
+int  aa_mesh_nslab(const aa_mesh *m);                                /* slabs of a cut Mesh (1: an undivided Mesh)    */
+int  aa_mesh_halo_counts(const aa_mesh *m, long long out[3]);       /* all-level x3 exchanges of a cut Mesh so far: pack +
+                                                          unpack launches, copies, exchanges                         */
 /* The same contract for Grids that are all 2-D (Nx3 = 1; the reference's tst/2D-hydro/athinput.blast has three levels):
  * disp[3*g+2] must be 0, and the nesting rules of init_mesh.c:320-499 hold in x1 and x2.  Every aa_mesh_* function below works
  * on such a Mesh except the radiation ones, which return an error; aa_mesh_step runs aa_integrate_2d_ctu / _vl, and
