@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <float.h>
+#include <limits.h>
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -62,6 +63,52 @@ void aa_eval_grav_tables(const aa_params &p, const double dx[3], int N1, int N2,
   for (auto &th : pool) th.join();
 }
 
+// Every launch choice of one Grid (grid.h LaunchCfg): read from the environment here, once per Grid, never again.  One line per
+// knob: its name, its default or the size from which the default is on, its range.  Returns fail()'s code for a value out of range.
+static int launch_cfg_read(const aa_params &p, LaunchCfg &c)
+{
+  auto env = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+  constexpr int UNSET = INT_MIN;                                                     // (no knob takes it as a value)
+  auto on = [](int v, bool dflt) { return v == UNSET ? dflt : v != 0; };             // an on / off knob: forced by any number, else by default
+  const long long zones = (long long)p.Nx[0]*p.Nx[1]*p.Nx[2], rays = (long long)p.Nx[1]*p.Nx[2];
+  // ---- launch geometry
+  c.strip = env("AA_STRIP", 64); c.xcd = env("AA_XCD", 1);
+  c.x1_flat = env("AA_X1_FLAT", 1); c.slopes_march = env("AA_SLOPES_MARCH", 1);
+  c.ca_kc = env("AA_CA_KC", 0); c.fu_kc = env("AA_FU_KC", 0);
+  c.ion_pass_cap = env("AA_ION_PASS_BLOCKS", 4096); if (c.ion_pass_cap < 1) c.ion_pass_cap = 1;
+  c.pitch_align = env("AA_PITCH_ALIGN", 1);
+  c.mailbox = env("AA_MAILBOX", 1); c.mailbox_spin_us = env("AA_MAILBOX_SPIN_US", 300);
+  c.bc_one = env("AA_BC_ONE", 1); c.fuse_pick = env("AA_ION_FUSE_PICK", 1); c.pin_one = env("AA_PIN_ONE", 1);
+  c.edge_overlap = env("AA_EDGE_OVERLAP", 0);
+  c.sw_chunk = env("AA_SW_CHUNK", 0); c.vp_kc = env("AA_VP_KC", 0);
+  if (c.sw_chunk < 0 || c.sw_chunk > 4096 || c.vp_kc < 0 || c.vp_kc > 4096)
+    return fail(-1, "[aa_create]: AA_SW_CHUNK=%d AA_VP_KC=%d: each must be 0 (by size) or 1..4096", c.sw_chunk, c.vp_kc);
+  // ---- which kernels carry a stage
+  // the one-kernel correct pass (with both first passes on board since round 4) wins from about 70^3 zones on, the tile kernels
+  // below (profiles/microbench/ca_threshold_r04.sh: 64^3 -11 %, 80^3 +20 %, 96^3 +21 %, 112^3 +21 %; until round 4 the
+  // limit was 2^21 zones): same results bit for bit, so the choice follows the size unless AA_CORRECT_ALL forces it
+  c.correct_all = on(env("AA_CORRECT_ALL", UNSET), zones >= 400000LL);
+  { const int v = env("AA_X3_FUSED", UNSET); c.x3_fused_mode = v == UNSET ? -1 : (v != 0); }      // (the potential arrives after aa_create: x3_fused below decides)
+  c.fused_update = on(env("AA_FUSED_UPDATE", UNSET), true);
+  c.cfl_step = on(env("AA_CFL_FUSED", UNSET), true);                 // aa_step: new_dt's maxima from the update kernel (=2: as 1, kept for the tests)
+  c.vl_predict = on(env("AA_VL_PREDICT", UNSET), zones >= (1LL << 18));
+  // rates inside the ray sweep: one block per 64 rays, so it needs many rays to fill the chip (512^2 rays:
+  // -2.9 ms per step; 80^2 rays: +6 %); same results either way
+  c.fused_rates = on(env("AA_FUSED_RATES", UNSET), rays >= (1LL << 17));
+  // the one-kernel sub-cycle wants whole wavefronts along the rays (rays of 48 zones or more: the 52^3 level of the reference's own deck
+  // takes 6 sub-cycles of 4 launches + a read-back the other way, 3 + a read-back this way -- there the launches count, not the 12 idle
+  // lanes of a wavefront; round 3: 64); AA_ION_FUSED forces either path
+  c.ion_fused = on(env("AA_ION_FUSED", UNSET), p.Nx[0] >= 48);
+  c.ion_begin_fused = on(env("AA_ION_BEGIN_FUSED", UNSET), true);
+  c.ion_spec_on = on(env("AA_ION_SPECULATE", UNSET), true);
+  // ---- not a launch choice of a kernel of the step, kept here all the same: floats per half of the dumps' bounce buffer
+  c.dump_chunk = env("AA_DUMP_CHUNK_FLOATS", 1 << 23); if (c.dump_chunk < 4) c.dump_chunk = 4; if (c.dump_chunk > (1 << 28)) c.dump_chunk = 1 << 28;
+  return 0;
+}
+// slabs asked for: aa_params.nslab, or AA_NGPU in the environment (drop-in executables)
+static int slabs_wanted(const aa_params *p)
+{ int ns = p->nslab; if (ns == 0) { const char *e = getenv("AA_NGPU"); if (e) ns = atoi(e); } return ns; }
+
 extern "C" {
 
 const char *aa_last_error(void) { return g_err; }
@@ -90,15 +137,13 @@ int aa_create(const aa_params *p, aa_grid **out)
     if (p->ion) return fail(-1, "[aa_create]: ion radiation on a 2-D Grid: the reference has ionrad_3d only");
     if (p->nscal != 0) return fail(-1, "[aa_create]: passive scalars on a 2-D Grid: no reference target pins them (NSCALARS must be 0)");
     if (p->order == 3) return fail(-1, "[aa_create]: third-order reconstruction on a 2-D Grid: no reference target pins it");
-    int ns = p->nslab;
-    if (ns == 0) { const char *e = getenv("AA_NGPU"); if (e) ns = atoi(e); }
+    const int ns = slabs_wanted(p);
     if (ns > 1) return fail(-1, "[aa_create]: a 2-D Grid cannot be cut into x3 slabs (nslab / AA_NGPU = %d)", ns);
   }
   if (p->ion && p->nscal != 1) return fail(-1, "[aa_create]: ion radiation needs NSCALARS=1");
   if (p->nscal != 0 && p->nscal != 1) return fail(-1, "[aa_create]: NSCALARS must be 0 or 1");
-  { // one Grid of the caller on several GPUs: aa_params.nslab, or AA_NGPU in the environment (drop-in executables)
-    int ns = p->nslab;
-    if (ns == 0) { const char *e = getenv("AA_NGPU"); if (e) ns = atoi(e); }
+  { // one Grid of the caller on several GPUs
+    const int ns = slabs_wanted(p);
     if (ns > 1) return slabs_create(p, ns, out);
   }
   int ndev = 0;
@@ -109,25 +154,7 @@ int aa_create(const aa_params *p, aa_grid **out)
   g->p = *p;
   HostGrid &d = g->d;
   d = HostGrid();
-  {   // the launch choices of this Grid (grid.h LaunchCfg): read here, once per Grid, never again
-    LaunchCfg &c = d.cfg;
-    auto env = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    c.strip = env("AA_STRIP", 64); c.xcd = env("AA_XCD", 1);
-    c.x1_flat = env("AA_X1_FLAT", 1); c.slopes_march = env("AA_SLOPES_MARCH", 1);
-    c.ca_kc = env("AA_CA_KC", 0); c.fu_kc = env("AA_FU_KC", 0);
-    c.ion_pass_cap = env("AA_ION_PASS_BLOCKS", 4096); if (c.ion_pass_cap < 1) c.ion_pass_cap = 1;
-    c.pitch_align = env("AA_PITCH_ALIGN", 1);
-    c.mailbox = env("AA_MAILBOX", 1); c.mailbox_spin_us = env("AA_MAILBOX_SPIN_US", 300);
-    c.bc_one = env("AA_BC_ONE", 1); c.fuse_pick = env("AA_ION_FUSE_PICK", 1); c.pin_one = env("AA_PIN_ONE", 1);
-    c.edge_overlap = env("AA_EDGE_OVERLAP", 0);
-    // (not a launch choice of a kernel of the step: kept with the Grid, not in LaunchCfg) floats per half of the dumps' bounce buffer
-    g->dump_chunk = env("AA_DUMP_CHUNK_FLOATS", 1 << 23); if (g->dump_chunk < 4) g->dump_chunk = 4; if (g->dump_chunk > (1 << 28)) g->dump_chunk = 1 << 28;
-    c.sw_chunk = env("AA_SW_CHUNK", 0); c.vp_kc = env("AA_VP_KC", 0);
-    if (c.sw_chunk < 0 || c.sw_chunk > 4096 || c.vp_kc < 0 || c.vp_kc > 4096) {
-      const int sw = c.sw_chunk, vp = c.vp_kc; delete g;
-      return fail(-1, "[aa_create]: AA_SW_CHUNK=%d AA_VP_KC=%d: each must be 0 (by size) or 1..4096", sw, vp);
-    }
-  }
+  if (int rc = launch_cfg_read(*p, d.cfg)) { delete g; return rc; }
   d.Nx1 = p->Nx[0]; d.Nx2 = p->Nx[1]; d.Nx3 = p->Nx[2];
   d.N1 = d.Nx1 + 2*AA_NGHOST; d.N2 = d.Nx2 + 2*AA_NGHOST; d.N3 = d.Nx3 + 2*AA_NGHOST;
   d.is = d.js = d.ks = AA_NGHOST;
@@ -141,19 +168,6 @@ int aa_create(const aa_params *p, aa_grid **out)
   d.sJ = pitch_align ? ((d.N1 + 15)/16)*16 : d.N1; d.sK = (long)d.sJ*d.N2; d.nc = d.sK*d.N3;
   if (p->level < 0 || p->level > 7) { delete g; return fail(-1, "[aa_create]: level %d out of range", p->level); }
   g->level = p->level;
-  // the one-kernel correct pass (with both first passes on board since round 4) wins from about 70^3 zones on, the tile kernels
-  // below (profiles/microbench/ca_threshold_r04.sh: 64^3 -11 %, 80^3 +20 %, 96^3 +21 %, 112^3 +21 %; until round 4 the
-  // limit was 2^21 zones): same results bit for bit, so the choice follows the size unless AA_CORRECT_ALL forces it
-  { const char *e = getenv("AA_CORRECT_ALL");
-    g->correct_all = e ? atoi(e) != 0 : ((long long)p->Nx[0]*p->Nx[1]*p->Nx[2] >= 400000LL); }
-  // (k_correct_all also does the x3 first pass: see x3_fused below)
-  { const char *e = getenv("AA_CFL_FUSED"); g->cfl_step = e ? atoi(e) != 0 : true; g->cfl_force = e && atoi(e) == 2; }     // aa_step: new_dt's maxima from the update kernel
-  { const char *e = getenv("AA_X3_FUSED"); g->x3_fused_mode = e ? (atoi(e) != 0) : -1; }    // (the potential arrives after aa_create)
-  // rates inside the ray sweep: one block per 64 rays, so it needs many rays to fill the chip (512^2 rays:
-  // -2.9 ms per step; 80^2 rays: +6 %); same results either way
-  { const char *e = getenv("AA_FUSED_RATES"); g->fused_rates = e ? atoi(e) != 0 : ((long long)p->Nx[1]*p->Nx[2] >= (1LL << 17)); }
-  { const char *e = getenv("AA_VL_PREDICT"); g->vl_predict = e ? atoi(e) != 0 : ((long long)p->Nx[0]*p->Nx[1]*p->Nx[2] >= (1LL << 18)); }
-  { const char *e = getenv("AA_FUSED_UPDATE"); g->fused_update = e ? atoi(e) != 0 : true; }
   Real rootdx[3];
   for (int a = 0; a < 3; a++) {
     rootdx[a] = (p->xmax[a] - p->xmin[a])/(Real)(p->rootNx[a]);   // init_mesh.c:225
@@ -168,13 +182,7 @@ int aa_create(const aa_params *p, aa_grid **out)
   // a 2-D Grid: U 5 | LR 2 x 2 x 5 | F 2 x 5 | eta 2 | edge (hydro2d_kernels.hip), nothing of the 3-D set
   const size_t nedge2 = two_d ? (size_t)5*ntiles_2d(d)*d.N2 : 0;
   if (two_d) n = nc*(5 + 20 + 10 + 2) + nedge2;
-  // the one-kernel sub-cycle wants whole wavefronts along the rays; AA_ION_FUSED forces either path
-  { const char *e = getenv("AA_ION_BEGIN_FUSED"); g->ion_begin_fused = e ? atoi(e) != 0 : true; }
-  { const char *e = getenv("AA_ION_SPECULATE"); g->ion_spec_on = e ? atoi(e) != 0 : true; }
-  { const char *e = getenv("AA_ION_FUSED");
-    // (rays of 48 zones or more: the 52^3 level of the reference's own deck takes 6 sub-cycles of 4 launches + a read-back the other
-    //  way, 3 + a read-back this way -- there the launches count, not the 12 idle lanes of a wavefront; round 3: 64)
-    g->ion_fused = p->ion && (p->ion_path ? p->ion_path == 1 : (e ? atoi(e) != 0 : p->Nx[0] >= 48)); }
+  g->ion_fused = p->ion && (p->ion_path ? p->ion_path == 1 : d.cfg.ion_fused);      // (the caller's choice goes before the knob and the size)
   const size_t nrays = (size_t)d.Nx2*d.Nx3;
   if (p->ion) n += nc*6 + nef;
   if (g->ion_fused) n += 2*nc + 2*nrays;
@@ -626,7 +634,7 @@ int aa_new_dt(aa_grid *g)
 // k_correct_all also does the x3 first pass (no k_sweep_march<2> launch, those fluxes never in HBM): -3.1 ms of a 512^3
 // blast step, -4.2 ms ifront, -4.4 / -2.0 ms third order without / with gravity.  Second order + passive scalar + gravity
 // (ioniz_sphere: 249 VGPRs at 2 waves per SIMD) was a draw in round 2 and left to the sweep kernel; with the hardware
-// min / max in the reconstruction (AA_FD_MINMAX: 12 % fewer instructions in this kernel) it is ahead there too --
+// min / max in the reconstruction (default build, hydro_dev.h: 12 % fewer instructions in this kernel) it is ahead there too --
 // 19.5 against 17.2 + 4.55 ms, hydro chain 45.5 -> 43.3 (round 3, same-box ABAB) -- and is the default everywhere.
 // Same bits either way.
 // aa_cfl_in_update: zero the maxima and let k_flux2_update fill them
@@ -646,7 +654,7 @@ int aa_cfl_in_update(aa_grid *g, int on)
 }
 
 static bool x3_fused(const aa_grid *g)      // default: always (round 3; until then not for second order + scalar + gravity)
-{ return g->x3_fused_mode >= 0 ? g->x3_fused_mode != 0 : true; }
+{ return g->d.cfg.x3_fused_mode >= 0 ? g->d.cfg.x3_fused_mode != 0 : true; }
 
 // The part of the step that needs none of the x3 neighbours' planes: the first-pass x1 and x2 sweeps of the k-planes
 // ks .. ke (a pencil along x1 or x2 lies in one plane).  A multi-GPU caller posts the x3 halo, calls this, waits for the
@@ -655,12 +663,12 @@ static bool x3_fused(const aa_grid *g)      // default: always (round 3; until t
 // does not apply: composite Grids, third order (the slope arrays come first), the unfused correct / update chains, VL.
 // the kernels of a run with a cooling function are the second compilation of hydro_kernels.hip (namespace aa_cool)
 #define HL(f) (g->cool ? aa_cool::f : aa::f)
-// ... and with it the x1 first pass (round 4: hydro_kernels.hip CA_X1F): no k_sweep_x1_flat launch before k_correct_all
-static bool x1_fused(const aa_grid *g) { return g->correct_all && x3_fused(g) && HL(ca_x1_on_board)(); }
+// ... and with it the x1 first pass (round 4: k_correct_all<X3F>): no k_sweep_x1_flat launch before k_correct_all
+static bool x1_fused(const aa_grid *g) { return g->d.cfg.correct_all && x3_fused(g); }
 int aa_integrate_begin(aa_grid *g)
 {
   if (g->two_d) return 0;
-  if (!g->slab.empty() || g->p.integrator != 0 || g->d.slope || !g->correct_all || !g->fused_update || g->inner_swept) return 0;
+  if (!g->slab.empty() || g->p.integrator != 0 || g->d.slope || !g->d.cfg.correct_all || !g->d.cfg.fused_update || g->inner_swept) return 0;
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
   const int nk = d.ke - d.ks + 1;
   { Scope s(g, "sweep_x2"); HL(launch_sweep)(d, ns, 1, dt, g->grav, g->st, 2, nk); }
@@ -724,8 +732,8 @@ int aa_integrate_3d_ctu(aa_grid *g)
   // x2 and x3 first, so that the x1 sweep can do its first pass and its correct pass in one go
   { Scope s(g, "sweep_x2"); HL(launch_sweep)(d, ns, 1, dt, g->grav, g->st, 0, -1); }
   if (edges_aside) HIPCHK(hipStreamWaitEvent(g->st, g->ev_join, 0));
-  if (!(g->correct_all && x3_fused(g))) { Scope s(g, "sweep_x3"); HL(launch_sweep)(d, ns, 2, dt, g->grav, g->st, 0, -1); }
-  if (g->correct_all) {
+  if (!(g->d.cfg.correct_all && x3_fused(g))) { Scope s(g, "sweep_x3"); HL(launch_sweep)(d, ns, 2, dt, g->grav, g->st, 0, -1); }
+  if (g->d.cfg.correct_all) {
     if (!x1_fused(g)) { Scope s(g, "sweep_x1"); HL(launch_sweep)(d, ns, 0, dt, g->grav, g->st, 0, -1); }
     { Scope s(g, "correct_all"); HL(launch_correct_all)(d, ns, dt, g->grav, x3_fused(g), g->st, edges_aside); }
   } else {
@@ -734,7 +742,7 @@ int aa_integrate_3d_ctu(aa_grid *g)
     { Scope s(g, "correct_x3"); HL(launch_correct)(d, ns, 2, dt, g->grav, g->st); }
   }
   no_h_correction(g);
-  if (g->fused_update) {
+  if (g->d.cfg.fused_update) {
     Scope s(g, "flux2_update");
     cfl_arm(g);
     HL(launch_flux2_update)(d, ns, dt, g->grav, g->keep_flux ? &g->keep : nullptr, g->st, g->cfl_ready ? g->sc : nullptr, g->pin_mask);
@@ -812,7 +820,7 @@ int aa_integrate_3d_vl(aa_grid *g)
   }
   // donor-cell fluxes + U^{n+1/2} in one marching kernel from 2^18 zones (512^3: 16.8 -> 9.7 ms; same at 80^3;
   // 10 % slower at 32^3); AA_VL_PREDICT forces either, the results are the same bit for bit
-  if (g->vl_predict) { Scope s(g, "vl_predict"); launch_vl_predict(d, ns, dt, g->grav, g->st); }
+  if (g->d.cfg.vl_predict) { Scope s(g, "vl_predict"); launch_vl_predict(d, ns, dt, g->grav, g->st); }
   else {
     { Scope s(g, "vl_flux1"); for (int dir = 0; dir < 3; dir++) launch_vl_flux1(d, ns, dir, g->st); }
     { Scope s(g, "vl_uhalf"); launch_vl_uhalf(d, ns, dt, g->grav, g->st); }
@@ -848,7 +856,7 @@ int aa_ion_begin(aa_grid *g)
     // (a sweep of the previous ion step that nobody asked for is dropped here: its buffers are about to be reused)
     g->ion_cur = 0; g->ion_pending = false; g->ef_stale = false;
     g->ion_spec_dt = -1.0; g->ion_spec_armed = false;
-    if (g->ion_begin_fused) { g->ion_begin_due = true; return 0; }       // rides on the first pass
+    if (g->d.cfg.ion_begin_fused) { g->ion_begin_due = true; return 0; }       // rides on the first pass
     Scope s(g, "ion_begin");
     launch_ion_begin16(g->d, g->ion, g->st);
     return 0;
@@ -874,12 +882,12 @@ int aa_ion_rates(aa_grid *g, double *dt_chem, double *dt_therm)
     const Real flux0 = g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1);
     // :264-271: a refined level starts every ray from the flux its parent left in EdgeFlux[..][..][0]
     if (g->rad_dir == -2) { Scope s(g, "ray_sweep"); launch_ray_sweep_x2(g->d, g->ion, g->flux_i, g->st); }
-    else if (g->fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
+    else if (g->d.cfg.fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
     else { Scope s(g, "ray_sweep"); launch_ray_sweep(g->d, g->ion, flux0, g->level > 0, g->st); }
   } else {
     HIPCHK(hipMemsetAsync(g->d.ph_rate, 0, (size_t)g->d.nc*sizeof(Real), g->st));
   }
-  if (!(g->fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
+  if (!(g->d.cfg.fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
   if (g->sc_host->neg_dt_chem) return fail(-4, "[compute_chem_rates]: negative dt_chem");   // ionrad_3d.c:389-391
   *dt_chem = bits_to_double(g->sc_host->dt_chem);
@@ -921,12 +929,12 @@ int aa_ion_subcycle(aa_grid *g, double dt_done, double limit, double *dt, int *l
   if (g->nradplane > 0) {
     const Real flux0 = g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1);     // ionradplane_3d.c:265
     if (g->rad_dir == -2) { Scope s(g, "ray_sweep"); launch_ray_sweep_x2(g->d, g->ion, g->flux_i, g->st); }
-    else if (g->fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
+    else if (g->d.cfg.fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
     else { Scope s(g, "ray_sweep"); launch_ray_sweep(g->d, g->ion, flux0, g->level > 0, g->st); }
   } else {
     HIPCHK(hipMemsetAsync(g->d.ph_rate, 0, (size_t)g->d.nc*sizeof(Real), g->st));
   }
-  if (!(g->fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
+  if (!(g->d.cfg.fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
   launch_ion_pick(g->sc, dt_done, limit, g->st);
   { Scope s(g, "ion_update"); launch_ion_update_sel(g->d, g->ion, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
@@ -984,7 +992,7 @@ int aa_ion_pass(aa_grid *g, int update, int sweep, double *dev_words)
 // ONE sub-cycle per step -- the closing update pass has nothing left to do (k_ion_pass).  Results are the same bit for bit.
 int aa_ion_speculate(aa_grid *g, double limit)
 {
-  if (!g->ion_fused || !g->ion_spec_on) return 0;
+  if (!g->ion_fused || !g->d.cfg.ion_spec_on) return 0;
   if (!g->slab.empty()) { for (aa_grid *c : g->slab) { c->ion_spec_dt = c->ion_begin_due ? limit : -1.0; c->ion_spec_limit = limit; } return 0; }
   g->ion_spec_dt = g->ion_begin_due ? limit : -1.0;      // (only the pass that also does the step's entry can speculate)
   g->ion_spec_limit = limit;
@@ -1178,7 +1186,7 @@ int aa_step(aa_grid *g, int *niter_out)
   }
   // (between the integrator and new_dt this loop only pins zones: the integrator may leave new_dt's maxima behind)
   const bool keep_opt = g->cfl_in_update;
-  if (g->slab.empty() && g->cfl_step) g->cfl_in_update = true;      // (both builds since round 4: aa_cfl_in_update)
+  if (g->slab.empty() && g->d.cfg.cfl_step) g->cfl_in_update = true;      // (both builds since round 4: aa_cfl_in_update)
   if (g->two_d) rc = (g->p.integrator == 1 ? aa_integrate_2d_vl(g) : aa_integrate_2d_ctu(g));     // integrate.c:49-58
   else
   rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g));                    // :572-585

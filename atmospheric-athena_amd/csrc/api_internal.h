@@ -32,12 +32,9 @@ struct aa_grid {
   double *cfl_part = nullptr; long cfl_part_n = 0;   // the blocks' CFL maxima of k_update<CFL> (van Leer integrator), 3 x update_blocks
   unsigned char *pin_mask = nullptr;   // 1 where a zone is pinned (k_flux2_update<CFL> leaves those to k_pinned_cfl)
   bool cfl_in_update = false;          // aa_cfl_in_update: the integrator also leaves new_dt's maxima behind
-  bool ion_spec_on = true;             // AA_ION_SPECULATE=0: the first pass of an ion step never applies an update
   double ion_spec_dt = -1.0, ion_spec_limit = 0.0;   // aa_ion_speculate: armed for the next first pass / what it was told
   bool ion_spec_armed = false;         //   ... the first pass has speculated: aa_ion_pick(first) settles it
-  bool cfl_force = false;              // AA_CFL_FUSED=2 (until round 4: the way to have it in the strict build too; now the same as 1)
-  bool cfl_step = true;                // aa_step does so by itself (AA_CFL_FUSED=0: k_cfl)
-  bool cfl_ready = false;              //   ... and has done so for the state as it is now
+  bool cfl_ready = false;              //   ... and has done so for the state as it is now (aa_step arms it by itself: LaunchCfg cfl_step)
   bool active_dirty = true;            // a call since the last full upload / download of U wrote ACTIVE zones on the device (aa_download_ghost_zones then moves the whole block)
   bool grav = false;
   int cool = 0;                        // aa_set_cooling: 1 = KoyInut; the integrator then launches the kernels of namespace aa_cool
@@ -45,14 +42,9 @@ struct aa_grid {
   int level = 0;                       // DomainS.Level: > 0 only as a level of an aa_mesh
   bool two_d = false;                  // Nx3 = 1: the 2-D integrators (hydro2d_kernels.hip); U 5 | LR 20 | F 10 | eta 2 | edge2d
   aa::Real *edge2d = nullptr;          //   ... what the x1 tiles of the 2-D kernels hand each other (grid.h)
-  bool fused_update = false;           // second-pass fluxes + update in one kernel (AA_FUSED_UPDATE=0 at aa_create: the unfused chain)
-  int x3_fused_mode = -1;              // k_correct_all also does the x3 first pass: -1 by configuration (api.hip), AA_X3_FUSED=0/1 forces
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke
   double inner_dt = 0.0;               //   ... with this dt
-  bool correct_all = false;            // the three correct passes in one kernel (k_correct_all): Grids of 4e5 zones or more (2^21 until round 4), or AA_CORRECT_ALL
-  bool fused_rates = false;            // rates evaluated inside the ray sweep (k_ray_sweep<true>): 2^17 rays or more, or AA_FUSED_RATES
-  bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): rays of 64 zones or more, or AA_ION_FUSED
-  bool ion_begin_fused = true;         // the entry of the ion step rides on its first pass (AA_ION_BEGIN_FUSED=0: k_ion_begin16 on its own)
+  bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): aa_params.ion_path, else LaunchCfg ion_fused; a sweep along x2 turns it off
   bool ion_begin_due = false;          // aa_ion_begin was called: the next first pass does the entry
   bool ef_stale = false;               // GridS.EdgeFlux has not been filled from the last sweep yet (done when somebody reads it)
   int ion_cur = 0; bool ion_pending = false;   // buffer of the last sweep that counts; a sweep launched but not yet relied upon
@@ -61,7 +53,6 @@ struct aa_grid {
   bool fofc = false;                   // aa_set_fofc: first-order flux correction of the van Leer integrator (integrate_3d_vl.c Steps 10, 14)
   long long *fofc_list = nullptr;      //   ... candidates | sorted | pending, 3 x AA_FOFC_MAX zone indices (device)
   long long fofc_counts[3] = {0, 0, 0};   //   ... of the last step: zones with d < 0, with P < 0, second-order fluxes replaced
-  bool vl_predict = false;             // van Leer predictor as one kernel (k_vl_predict): 2^18 zones or more, or AA_VL_PREDICT
   bool keep_flux = false;              // a level of an aa_mesh: RestrictCorrect reads the second-pass fluxes ...
   aa::KeepPlanes keep = {0, {{0}}};        // ... on these face planes (own boundaries + the child's outline)
   double time = 0, dt = 0; int nstep = 0;
@@ -72,7 +63,6 @@ struct aa_grid {
   struct SlabLink *link = nullptr;
   // data dumps (dump.hip): the page-locked bounce buffer (two halves of dump_cap floats), the stream of its copies, and the events
   // "piece staged" [0..1] / "piece on the host" [2..3] of either half; made by the first aa_dump_section
-  int dump_chunk = 1 << 23;            // AA_DUMP_CHUNK_FLOATS at aa_create: floats per half asked for (4 .. 2^28)
   float *dump_host = nullptr; size_t dump_cap = 0;
   hipStream_t dump_st = nullptr; hipEvent_t dump_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool prof = false;

@@ -94,7 +94,7 @@ void dump_release(aa_grid *g)
 // face-state area holds, at least one row of the vector section; a multiple of 4, so that both slots are 16-byte aligned
 static size_t dump_capacity(const aa_grid *g)
 {
-  size_t cap = (size_t)g->dump_chunk;
+  size_t cap = (size_t)g->d.cfg.dump_chunk;
   const size_t room = (size_t)(g->two_d ? 20 : 36)*(size_t)g->d.nc;   // LR is 36*nc doubles = 72*nc floats: two slots of 36*nc (a 2-D Grid: 20*nc)
   const size_t row = (size_t)3*(size_t)g->d.Nx1;
   if (cap > room) cap = room;

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace aa {
 
@@ -31,7 +32,7 @@ struct DevGrid {
   long sJ, sK, nc;                // strides of j and k (i stride is 1); doubles per field
   Real dx[3];
   Real Gamma, Gamma_1;
-  Real rGamma_1;                  // 1/(gamma-1), correctly rounded (host division): prim_to_cons' quotient in three instructions (hydro_dev.h, AA_XDIV)
+  Real rGamma_1;                  // 1/(gamma-1), correctly rounded (host division): prim_to_cons' quotient in three instructions (hydro_dev.h, x_div_r)
   Real *U, *LR, *F, *eta, *dhalf;
   Real *phalf;                    // P^{n+1/2}: only with a cooling function (aa_set_cooling), else null
   Real *phi;                      // null when StaticGravPot == NULL; [0]=centre, [1+d]=lower face d
@@ -96,11 +97,11 @@ struct IonPart { Real dt_chem, dt_therm, max_dti, cellcount, neg; };
 #define AA_ION_WORDS 8               /* doubles per rank in the sub-cycle's reduction (5 used) */
 #endif
 
-// Host-side launch choices of ONE Grid: read from the environment by aa_create and kept with the Grid, so that no later change of
-// the environment (a test's monkeypatch, a second Grid of another caller) can reach a Grid that already exists and no Grid depends
-// on what an earlier one found there.  Every choice changes the launch geometry only; the results are the same bit for bit in the
-// strict build (tests/test_gpu_layout_switches.py).
+// Host-side launch choices of ONE Grid: read from the environment by aa_create (api.hip launch_cfg_read: every name, default, range
+// and size threshold is there) and kept with the Grid, so that no later change of the environment (a test's monkeypatch, a second
+// Grid of another caller) can reach a Grid that already exists and no Grid depends on what an earlier one found there.
 struct LaunchCfg {
+  // ---- launch geometry: the results are the same bit for bit in the strict build (tests/test_gpu_layout_switches.py)
   int strip = 64, xcd = 1;   // AA_STRIP / AA_XCD: zone order of the unfused stencil kernels (k_flux2, k_update)
   int x1_flat = 1;           // AA_X1_FLAT=0: the x1 first-pass sweep with a block per piece of a row
   int slopes_march = 1;      // AA_SLOPES_MARCH=0: the PPM slope arrays along x2 / x3 one zone per thread
@@ -116,9 +117,36 @@ struct LaunchCfg {
   int edge_overlap = 0;      // AA_EDGE_OVERLAP=1: k_x1_edge_flux beside the x2 sweep on a side stream instead of in front of k_correct_all on the Grid's stream
   int pin_one = 1;           // AA_PIN_ONE=0: the pinned zones' share of new_dt's maxima by a kernel of its own behind k_pinned
   int fuse_pick = 1;         // AA_ION_FUSE_PICK=0: k_ion_reduce and k_ion_pick2 as two launches also where one rank reduces alone
+  // ---- which kernels carry a stage: by the Grid's size unless the knob forces it (the defaults here are those of a handle aa_create
+  //      did not fill: the composite handle of a Grid cut into slabs)
+  bool correct_all = false;  // AA_CORRECT_ALL: the three correct passes in one kernel (k_correct_all): Grids of 4e5 zones or more
+  int x3_fused_mode = -1;    // AA_X3_FUSED=0/1: whether k_correct_all also does the x3 (and x1) first pass; -1: by configuration (api.hip x3_fused)
+  bool fused_update = false; // AA_FUSED_UPDATE=0: second-pass fluxes and update as the unfused chain instead of k_flux2_update
+  bool cfl_step = true;      // AA_CFL_FUSED=0: aa_step takes new_dt's maxima from k_cfl instead of the update kernel
+  bool vl_predict = false;   // AA_VL_PREDICT: the van Leer predictor as one kernel (k_vl_predict): 2^18 zones or more
+  bool fused_rates = false;  // AA_FUSED_RATES: rates evaluated inside the ray sweep (k_ray_sweep<true>): 2^17 rays or more
+  bool ion_fused = false;    // AA_ION_FUSED: the one-kernel radiation sub-cycle (ion_pass.hip): rays of 48 zones or more (aa_params.ion_path goes first)
+  bool ion_begin_fused = true;  // AA_ION_BEGIN_FUSED=0: the entry of the ion step as k_ion_begin16 on its own instead of on the first pass
+  bool ion_spec_on = true;   // AA_ION_SPECULATE=0: the first pass of an ion step never applies an update
+  int dump_chunk = 1 << 23;  // AA_DUMP_CHUNK_FLOATS: floats per half of the dumps' bounce buffer (4 .. 2^28; dump.hip)
 };
 // the descriptor as the host keeps it: what the kernels get (DevGrid, passed by value: the launch slices it off) + the launch choices
 struct HostGrid : DevGrid { LaunchCfg cfg; };
+
+// ---- run-time value -> template argument (host side of the kernel files).  A launcher that picks a kernel instantiation by a
+// run-time int / bool hands a generic lambda to one of these; the lambda's parameter is a std::integral_constant, which converts to
+// a template argument, so that every launch is written once:
+//   with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { hipLaunchKernelGGL((k_vl_uhalf<NS, GRAV>), grid, blk, 0, st, g, dt); });
+// A helper instantiates its lambda for exactly the values it names, and nothing else: what is not dispatched stays a plain argument.
+template <int A, int B, class F> static inline void with_either(bool a, F &&f)
+{ if (a) f(std::integral_constant<int, A>{}); else f(std::integral_constant<int, B>{}); }
+template <class F> static inline void with_flag(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static inline void with_ns(int nscal, F &&f) { with_either<1, 0>(nscal != 0, f); }         // passive scalars: 1 or 0
+template <class F> static inline void with_ord(bool third, F &&f) { with_either<3, 2>(third, f); }            // reconstruction: g.slope set = third order
+template <class F> static inline void with_dir12(int dir, F &&f) { with_either<1, 2>(dir == 1, f); }          // the strided directions
+template <class F> static inline void with_dir(int dir, F &&f) { if (dir == 0) f(std::integral_constant<int, 0>{}); else with_dir12(dir, f); }
+template <class F> static inline void with_ns_grav(int nscal, bool grav, F &&f)
+{ with_ns(nscal, [&](auto NS) { with_flag(grav, [&](auto GRAV) { f(NS, GRAV); }); }); }
 
 // the scalars' way back to the host (api.hip aa_fetch_scalars): pinned, device-visible host memory that a one-wave kernel fills
 // and stamps with a sequence number the host polls for -- a read-back costs a ~5 us launch instead of a copy + a stream wait

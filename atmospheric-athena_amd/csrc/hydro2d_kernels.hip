@@ -410,26 +410,14 @@ static void launch_step_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *
   hipLaunchKernelGGL((k2d_step_keep<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, kp);
 }
 void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
-{
-  if (sc) launch_step_keep<M_CTU2, true>(g, dt, edge, sc, kp, st);
-  else    launch_step_keep<M_CTU2, false>(g, dt, edge, nullptr, kp, st);
-}
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep<M_CTU2, CFL>(g, dt, edge, sc, kp, st); }); }
 void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
-{
-  if (sc) launch_step_keep<M_VL2, true>(g, dt, edge, sc, kp, st);
-  else    launch_step_keep<M_VL2, false>(g, dt, edge, nullptr, kp, st);
-}
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep<M_VL2, CFL>(g, dt, edge, sc, kp, st); }); }
 void launch_2d_ctu_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
-{
-  if (sc) launch_step<M_CTU2, true>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st);
-  else    launch_step<M_CTU2, false>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, nullptr, st);
-}
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step<M_CTU2, CFL>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }
 void launch_2d_vl_predict(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
 { launch_step<M_VL1, false>(g, dt, 0.5*(dt/g.dx[0]), 0.5*(dt/g.dx[1]), edge, nullptr, st); }
 void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
-{
-  if (sc) launch_step<M_VL2, true>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st);
-  else    launch_step<M_VL2, false>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, nullptr, st);
-}
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step<M_VL2, CFL>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }
 
 }  // namespace aa

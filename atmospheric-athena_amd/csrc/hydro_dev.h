@@ -31,27 +31,17 @@ AA_DEV Real sqr(Real x) { return x*x; }
 #ifndef AA_FAST_DIV
 #define AA_FAST_DIV 0
 #endif
-#ifndef AA_FD_C2P
-#define AA_FD_C2P AA_FAST_DIV
-#endif
-#ifndef AA_FD_PLM
-#define AA_FD_PLM AA_FAST_DIV
-#endif
-// P/(gamma - 1) in prim_to_cons as a product with the (loop-invariant) reciprocal: two divisions less per face; x2 / x3
-// first passes -6 %, hydro chain 45.7 -> 45.1 ms (round 3, same-box ABAB at 512^3) -- and OFF: the conserved face states
-// feed the Riemann solver's Roe -> HLLE switch (see AA_FD_ROE below), and with the energy rounded differently the
-// 3-level blast of the drop-in test left the reference by 7.6e-7 in time after six steps (one flipped switch)
-#ifndef AA_FD_P2C
-#define AA_FD_P2C 0
-#endif
-// The Riemann solver keeps the reference's operations in every build: its switch to HLLE (negative density or pressure of
-// an intermediate state, roe.c:256-286) is the one DISCONTINUOUS decision of the hydro step, and symmetric flows sit
-// exactly on it -- with the reciprocal forms in flux_roe a 3-level blast differed from the reference by 2.6e-3 in 116
-// zones after two steps (one flipped switch; 5e-16 without them).  Reconstruction and the variable conversion are
-// continuous in their inputs: there a changed last bit stays a changed last bit.
-#ifndef AA_FD_ROE
-#define AA_FD_ROE 0
-#endif
+// The reciprocal forms serve the variable conversion to primitives, the reconstruction, the wave speeds of eta and the
+// reconstruction's MIN / MAX -- all continuous in their inputs: there a changed last bit stays a changed last bit.  Two places
+// keep the reference's operations in every build, and must:
+// * The Riemann solver.  Its switch to HLLE (negative density or pressure of an intermediate state, roe.c:256-286) is the one
+//   DISCONTINUOUS decision of the hydro step, and symmetric flows sit exactly on it -- with the reciprocal forms in flux_roe a
+//   3-level blast differed from the reference by 2.6e-3 in 116 zones after two steps (one flipped switch; 5e-16 without them;
+//   k_flux2_update, at its register limit, was also slower with them).
+// * P/(gamma - 1) in prim_to_cons.  As a product with the (loop-invariant) reciprocal it saved two divisions per face (x2 / x3
+//   first passes -6 %, hydro chain 45.7 -> 45.1 ms, round 3, same-box ABAB at 512^3), but the conserved face states feed that
+//   same Roe -> HLLE switch, and with the energy rounded differently the 3-level blast of the drop-in test left the reference
+//   by 7.6e-7 in time after six steps (one flipped switch).
 AA_DEV Real q_rcp(Real x)
 {
   Real r = __builtin_amdgcn_rcp(x);
@@ -68,14 +58,8 @@ AA_DEV Real q_rsqrt(Real x)
   r = fma(r, e, r);
   return r;
 }
-// a/b for a denominator that may leave the range in which the Newton steps are safe
-AA_DEV Real q_div_checked(Real a, Real b)
-{
-  const Real ab = fabs(b);
-  return (ab > 1.0e-280 && ab < 1.0e280) ? a*q_rcp(b) : a/b;
-}
 
-// ---- both builds (AA_XDIV): IEEE quotients and square roots without the range scaling of hipcc's expansions.  a/b compiles to
+// ---- both builds: IEEE quotients and square roots without the range scaling of hipcc's expansions.  a/b compiles to
 // v_div_scale x2, v_rcp, four Newton fmas, q = n r, rem = fma(-d, q, n), v_div_fmas, v_div_fixup (11 instructions); sqrt(x) to a
 // compare + select + v_ldexp in front of and v_ldexp + class test + 3 selects behind v_rsq and nine mul / fma (20).  The scaling
 // only acts on denormal / huge denominators, quotients near the ends of the range, numerators below 2^-969 and x < 2^-767; the
@@ -89,9 +73,6 @@ AA_DEV Real q_div_checked(Real a, Real b)
 // the IEEE quotient on every operand tested (tests/test_gpu_parity.py: 3e6 pairs over 400 decades, and every bitwise run of the strict
 // build), NOT a proven one: Markstein's theorem (1990) wants q = RN(a y) to be a faithful rounding of a/b as well, and a RN(1/b) can be
 // off by ~1.5 ulp, so a quotient within ~2^-51 ulp of a rounding boundary could come out one ulp apart -- no test can rule that out.
-#ifndef AA_XDIV
-#define AA_XDIV 1
-#endif
 AA_DEV Real x_rcp_ref(Real b)                    // the reciprocal hipcc's division refines (two Newton steps on v_rcp_f64)
 {
   Real r = __builtin_amdgcn_rcp(b);
@@ -105,17 +86,9 @@ AA_DEV Real x_div_r(Real a, Real b, Real r)      // a/b with r = x_rcp_ref(b) or
   const Real rem = fma(-b, q, a);
   return fma(rem, r, q);
 }
-template <bool XD = true> AA_DEV Real x_div(Real a, Real b)
+AA_DEV Real x_div(Real a, Real b) { return x_div_r(a, b, x_rcp_ref(b)); }
+AA_DEV Real x_sqrt(Real x)
 {
-#if AA_XDIV
-  if (XD) return x_div_r(a, b, x_rcp_ref(b));
-#endif
-  return a/b;
-}
-template <bool XD = true> AA_DEV Real x_sqrt(Real x)
-{
-#if AA_XDIV
-  if (!XD) return sqrt(x);
   const Real y = __builtin_amdgcn_rsq(x);
   Real g = x*y, h = y*0.5;
   const Real r = fma(-h, g, 0.5);
@@ -123,16 +96,13 @@ template <bool XD = true> AA_DEV Real x_sqrt(Real x)
   Real d = fma(-g, g, x); g = fma(d, h, g);
   d = fma(-g, g, x); g = fma(d, h, g);
   return g;
-#else
-  return sqrt(x);
-#endif
 }
 
 // convert_var.c:389 Cons1D_to_Prim1D
 template <int NS>
 AA_DEV void cons_to_prim(const Real u[6], Real w[6], Real Gamma_1)
 {
-#if AA_FD_C2P
+#if AA_FAST_DIV
   Real di = q_rcp(u[0]);
 #else
   Real di = 1.0/u[0];
@@ -150,13 +120,7 @@ template <int NS>
 AA_DEV void prim_to_cons(const Real w[6], Real u[6], Real Gamma_1, Real rG_1)
 {
   u[0] = w[0]; u[1] = w[0]*w[1]; u[2] = w[0]*w[2]; u[3] = w[0]*w[3];
-#if AA_XDIV
   u[4] = x_div_r(w[4], Gamma_1, rG_1) + 0.5*w[0]*(sqr(w[1]) + sqr(w[2]) + sqr(w[3]));
-#elif AA_FD_P2C
-  u[4] = w[4]*(1.0/Gamma_1) + 0.5*w[0]*(sqr(w[1]) + sqr(w[2]) + sqr(w[3]));      // (the quotient is loop-invariant: one division per thread)
-#else
-  u[4] = w[4]/Gamma_1 + 0.5*w[0]*(sqr(w[1]) + sqr(w[2]) + sqr(w[3]));
-#endif
   u[5] = NS ? w[5]*w[0] : 0.0;
 }
 
@@ -169,17 +133,14 @@ AA_DEV Real cfast(const Real u[6], Real Gamma, Real Gamma_1)
 }
 
 // The wave speeds the H-correction's eta is made of (integrate_3d_ctu.c:2300-2343): v - cfast of a face's left state,
-// v + cfast of its right state.  Default build (AA_FD_ETA): one reciprocal of the density serves the velocity, the pressure
+// v + cfast of its right state.  Default build: one reciprocal of the density serves the velocity, the pressure
 // and the sound speed, the square root comes from v_rsq_f64 -- 3 divisions + 1 square root (~60 instructions, most of them
 // quarter rate) become ~25.  eta enters the second-pass fluxes only through max(|lambda|, etah): continuous, no switch
 // hangs on its last bit.  A non-positive a^2 (negative face pressure beside the planet's density jump: the NaN etas the
 // reference produces there) takes the reference's own expression, so the NaN pattern is the reference's.
-#ifndef AA_FD_ETA
-#define AA_FD_ETA AA_FAST_DIV
-#endif
 AA_DEV Real lambda_face(const Real u[6], Real Gamma, Real Gamma_1, Real sign)
 {
-#if AA_FD_ETA
+#if AA_FAST_DIV
   const Real d = u[0];
   if (d > 1.0e-280 && d < 1.0e280) {
     const Real di = q_rcp(d);
@@ -192,19 +153,19 @@ AA_DEV Real lambda_face(const Real u[6], Real Gamma, Real Gamma_1, Real sign)
 }
 
 // rsolvers/hlle.c:62 (compiled into roe.c as flux_hlle, roe.c:339-341)
-template <int NS, bool XD = true>
+template <int NS>
 AA_DEV void flux_hlle(const Real ul[6], const Real ur[6], const Real wl[6], const Real wr[6],
                       Real Gamma, Real Gamma_1, Real f[6])
 {
   // (the same scaling-free forms as in flux_roe, whose values these are: one evaluation serves both)
-  Real sqrtdl = x_sqrt<XD>(wl[0]), sqrtdr = x_sqrt<XD>(wr[0]);
-  Real isdlpdr = x_div<XD>(1.0, sqrtdl + sqrtdr);
+  Real sqrtdl = x_sqrt(wl[0]), sqrtdr = x_sqrt(wr[0]);
+  Real isdlpdr = x_div(1.0, sqrtdl + sqrtdr);
   Real v1 = (sqrtdl*wl[1] + sqrtdr*wr[1])*isdlpdr;
   Real v2 = (sqrtdl*wl[2] + sqrtdr*wr[2])*isdlpdr;
   Real v3 = (sqrtdl*wl[3] + sqrtdr*wr[3])*isdlpdr;
-  Real h  = (x_div<XD>(ul[4] + wl[4] + 0.0, sqrtdl) + x_div<XD>(ur[4] + wr[4] + 0.0, sqrtdr))*isdlpdr;
+  Real h  = (x_div(ul[4] + wl[4] + 0.0, sqrtdl) + x_div(ur[4] + wr[4] + 0.0, sqrtdr))*isdlpdr;
   Real vsq = v1*v1 + v2*v2 + v3*v3;
-  Real a = x_sqrt<XD>(Gamma_1*rmax((h - 0.5*vsq), AA_TINY));
+  Real a = x_sqrt(Gamma_1*rmax((h - 0.5*vsq), AA_TINY));
   Real ev0 = v1 - a, ev4 = v1 + a;
 
   Real asq = Gamma*wl[4]/wl[0];
@@ -235,39 +196,22 @@ AA_DEV void flux_hlle(const Real ul[6], const Real ur[6], const Real wl[6], cons
 
 // rsolvers/roe.c:59 fluxes() with the H-correction etah and the HLLE fallback;
 // eigensystem rsolvers/esystem_roe.c:132
-// FAST: the reciprocal forms (AA_FD_ROE, off: see above; k_flux2_update, at its register limit, was also slower with them)
-// XD: the scaling-free quotients / square roots (AA_XDIV).  k_flux2_update, which is not bound by its instruction count, lost 4 %
-// with them while it was at its register limit (13.9 -> 14.4 ms at 512^3, three more registers spilled) and gains 2 % since its
-// carried x3 flux waits in LDS (FU_PARK, hydro_kernels.hip)
-template <int NS, bool FAST = (AA_FD_ROE != 0), bool XD = true>
+// The quotients / square roots are the scaling-free x_div / x_sqrt in every kernel.  k_flux2_update, which is not bound by its
+// instruction count, lost 4 % with them while it was at its register limit (13.9 -> 14.4 ms at 512^3, three more registers spilled)
+// and gains 2 % since its carried x3 flux waits in LDS (s_f3, hydro_kernels.hip)
+template <int NS>
 AA_DEV void flux_roe(const Real ul[6], const Real ur[6], const Real wl[6], const Real wr[6],
                      Real etah, Real Gamma, Real Gamma_1, Real f[6])
 {
-  Real sqrtdl, sqrtdr, isdlpdr, v1, v2, v3, h, vsq, asq, a, iasq = 0.0;
-  if (FAST) {
-  const Real isl = q_rsqrt(wl[0]), isr = q_rsqrt(wr[0]);
-    sqrtdl = wl[0]*isl; sqrtdr = wr[0]*isr;
-    isdlpdr = q_rcp(sqrtdl + sqrtdr);
-    v1 = (sqrtdl*wl[1] + sqrtdr*wr[1])*isdlpdr;
-    v2 = (sqrtdl*wl[2] + sqrtdr*wr[2])*isdlpdr;
-    v3 = (sqrtdl*wl[3] + sqrtdr*wr[3])*isdlpdr;
-    h  = ((ul[4] + wl[4] + 0.0)*isl + (ur[4] + wr[4] + 0.0)*isr)*isdlpdr;
-    vsq = v1*v1 + v2*v2 + v3*v3;
-    asq = Gamma_1*rmax((h - 0.5*vsq), AA_TINY);
-    const Real ia = q_rsqrt(asq);
-    iasq = ia*ia;
-    a = asq*ia;
-  } else {
-    sqrtdl = x_sqrt<XD>(wl[0]); sqrtdr = x_sqrt<XD>(wr[0]);
-    isdlpdr = x_div<XD>(1.0, sqrtdl + sqrtdr);
-    v1 = (sqrtdl*wl[1] + sqrtdr*wr[1])*isdlpdr;
-    v2 = (sqrtdl*wl[2] + sqrtdr*wr[2])*isdlpdr;
-    v3 = (sqrtdl*wl[3] + sqrtdr*wr[3])*isdlpdr;
-    h  = (x_div<XD>(ul[4] + wl[4] + 0.0, sqrtdl) + x_div<XD>(ur[4] + wr[4] + 0.0, sqrtdr))*isdlpdr;
-    vsq = v1*v1 + v2*v2 + v3*v3;
-    asq = Gamma_1*rmax((h - 0.5*vsq), AA_TINY);
-    a = x_sqrt<XD>(asq);
-  }
+  const Real sqrtdl = x_sqrt(wl[0]), sqrtdr = x_sqrt(wr[0]);
+  const Real isdlpdr = x_div(1.0, sqrtdl + sqrtdr);
+  const Real v1 = (sqrtdl*wl[1] + sqrtdr*wr[1])*isdlpdr;
+  const Real v2 = (sqrtdl*wl[2] + sqrtdr*wr[2])*isdlpdr;
+  const Real v3 = (sqrtdl*wl[3] + sqrtdr*wr[3])*isdlpdr;
+  const Real h  = (x_div(ul[4] + wl[4] + 0.0, sqrtdl) + x_div(ur[4] + wr[4] + 0.0, sqrtdr))*isdlpdr;
+  const Real vsq = v1*v1 + v2*v2 + v3*v3;
+  const Real asq = Gamma_1*rmax((h - 0.5*vsq), AA_TINY);
+  const Real a = x_sqrt(asq);
   Real ev0 = v1 - a, ev4 = v1 + a;
 
   Real Fl[6], Fr[6];
@@ -292,14 +236,14 @@ AA_DEV void flux_roe(const Real ul[6], const Real ur[6], const Real wl[6], const
     return;
   }
 
-  const Real rasq = (FAST || !XD || !AA_XDIV) ? 0.0 : x_rcp_ref(asq);      // one refined reciprocal for the two quotients by a^2
-  Real na = FAST ? 0.5*iasq : ((XD && AA_XDIV) ? x_div_r(0.5, asq, rasq) : 0.5/asq);
+  const Real rasq = x_rcp_ref(asq);      // one refined reciprocal for the two quotients by a^2
+  Real na = x_div_r(0.5, asq, rasq);
   Real l00 = na*(0.5*Gamma_1*vsq + v1*a);
   Real l01 = -na*(Gamma_1*v1 + a);
   Real l02 = -na*Gamma_1*v2;
   Real l03 = -na*Gamma_1*v3;
   Real l04 = na*Gamma_1;
-  Real qa = FAST ? Gamma_1*iasq : ((XD && AA_XDIV) ? x_div_r(Gamma_1, asq, rasq) : Gamma_1/asq);
+  Real qa = x_div_r(Gamma_1, asq, rasq);
   Real l30 = 1.0 - na*Gamma_1*vsq;
   Real l31 = qa*v1, l32 = qa*v2, l33 = qa*v3, l34 = -qa;
   Real l40 = na*(0.5*Gamma_1*vsq - v1*a);
@@ -321,7 +265,7 @@ AA_DEV void flux_roe(const Real ul[6], const Real ur[6], const Real wl[6], const
   if (v1 > ev0) {
     if (u0 <= 0.0) hlle = true;
     else {
-      Real p_inter = FAST ? u4 - q_div_checked(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0) : u4 - x_div<XD>(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0);
+      Real p_inter = u4 - x_div(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0);
       if (p_inter < 0.0) hlle = true;
     }
   }
@@ -332,12 +276,12 @@ AA_DEV void flux_roe(const Real ul[6], const Real ur[6], const Real wl[6], const
     if (ev4 > v1) {
       if (u0 <= 0.0) hlle = true;
       else {
-      Real p_inter = FAST ? u4 - q_div_checked(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0) : u4 - x_div<XD>(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0);
-      if (p_inter < 0.0) hlle = true;
-    }
+        Real p_inter = u4 - x_div(0.5*(sqr(u1) + sqr(u2) + sqr(u3)), u0);
+        if (p_inter < 0.0) hlle = true;
+      }
     }
   }
-  if (hlle) { flux_hlle<NS, XD>(ul, ur, wl, wr, Gamma, Gamma_1, f); return; }
+  if (hlle) { flux_hlle<NS>(ul, ur, wl, wr, Gamma, Gamma_1, f); return; }
 
   Real c0 = 0.5*rmax(fabs(ev0), etah)*aa_[0];
   Real c1 = 0.5*rmax(fabs(v1), etah)*aa_[1];
@@ -358,16 +302,13 @@ AA_DEV void flux_roe(const Real ul[6], const Real ur[6], const Real wl[6], const
 // wl_next = Wl[i+1] (left state of the upper interface) and wr_here = Wr[i] (right state of
 // the lower interface), PLM in characteristic variables + CTU characteristic tracing.
 // TRACE=false is the VL_INTEGRATOR branch (lr_states_plm.c:250-255).
-// AA_FD_MINMAX (default build): v_min_f64 / v_max_f64 for the 66 MIN / MAX of a reconstructed cell instead of the
+// Default build: v_min_f64 / v_max_f64 for the 66 MIN / MAX of a reconstructed cell instead of the
 // reference's compare-and-select macro (3 instructions each): -5 % of the first-pass sweeps, -3 % of k_correct_all
 // (round 3, same-box ABAB at 512^3: hydro chain 48.0 -> 46.7 ms).  Equal on finite operands up to the sign of a zero; a NaN
 // operand is dropped by the hardware min / max where the macro's result depends on the operand order -- the strict build
 // keeps the macro, and so does every MAX of the H-correction's eta chain in both builds (NaN etas are part of the
 // reference's behaviour beside the planet's density jump).
-#ifndef AA_FD_MINMAX
-#define AA_FD_MINMAX AA_FAST_DIV
-#endif
-#if AA_FD_MINMAX
+#if AA_FAST_DIV
 AA_DEV Real pmax(Real a, Real b) { return __builtin_fmax(a, b); }
 AA_DEV Real pmin(Real a, Real b) { return __builtin_fmin(a, b); }
 #else
@@ -380,7 +321,7 @@ AA_DEV void plm_cell(const Real wm[6], const Real w[6], const Real wp[6], Real d
 {
   constexpr int NV = 5 + NS;
   Real d = w[0], vx = w[1];
-#if AA_FD_PLM
+#if AA_FAST_DIV
   const Real id = q_rcp(d);
   Real asq = (Gamma*w[4])*id;
   const Real ia = q_rsqrt(asq), iasq = ia*ia;
@@ -399,7 +340,7 @@ AA_DEV void plm_cell(const Real wm[6], const Real w[6], const Real wp[6], Real d
 #pragma unroll
   for (int n = 0; n < NV; n++) {
     dWc[n] = wp[n] - wm[n]; dWl[n] = w[n] - wm[n]; dWr[n] = wp[n] - w[n];
-#if AA_FD_PLM
+#if AA_FAST_DIV
     // (where the product is positive the sum is a normal number: two operands small enough for a subnormal sum have
     //  a product that underflows to zero)
     dWg[n] = (dWl[n]*dWr[n] > 0.0) ? 2.0*dWl[n]*dWr[n]*q_rcp(dWl[n] + dWr[n]) : 0.0;
@@ -497,7 +438,7 @@ AA_DEV void limited_slopes(const Real wm[6], const Real w[6], const Real wp[6], 
 {
   constexpr int NV = 5 + NS;
   Real d = w[0];
-#if AA_FD_PLM      // (default build: the reciprocal forms of plm_cell)
+#if AA_FAST_DIV      // (default build: the reciprocal forms of plm_cell)
   const Real id = q_rcp(d);
   Real asq = (Gamma*w[4])*id;
   const Real ia = q_rsqrt(asq), iasq = ia*ia;
@@ -513,7 +454,7 @@ AA_DEV void limited_slopes(const Real wm[6], const Real w[6], const Real wp[6], 
 #pragma unroll
   for (int n = 0; n < NV; n++) {
     dWc[n] = wp[n] - wm[n]; dWl[n] = w[n] - wm[n]; dWr[n] = wp[n] - w[n];
-#if AA_FD_PLM
+#if AA_FAST_DIV
     dWg[n] = (dWl[n]*dWr[n] > 0.0) ? 2.0*dWl[n]*dWr[n]*q_rcp(dWl[n] + dWr[n]) : 0.0;
 #else
     dWg[n] = (dWl[n]*dWr[n] > 0.0) ? 2.0*dWl[n]*dWr[n]/(dWl[n] + dWr[n]) : 0.0;
@@ -556,7 +497,7 @@ AA_DEV void ppm_cell(const Real wm[6], const Real w[6], const Real wp[6], const 
   constexpr Real FOUR_3RDS = 1.333333333333333, TWO_3RDS = 0.6666666666666667;     // defs.h.in:158-159
   const Real gamma_curv = 0.0, qxx1 = 0.0, qxx2 = 0.0;
   Real d = w[0], vx = w[1];
-#if AA_FD_PLM      // (default build: the reciprocal forms of plm_cell; the sixths as products)
+#if AA_FAST_DIV      // (default build: the reciprocal forms of plm_cell; the sixths as products)
   const Real id = q_rcp(d);
   Real asq = (Gamma*w[4])*id;
   const Real ia = q_rsqrt(asq), iasq = ia*ia;

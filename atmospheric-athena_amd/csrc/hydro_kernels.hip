@@ -300,9 +300,6 @@ AA_DEV bool decode_zone(const Order o, int ni, int nj, int nk, int &i, int &j, i
 // ---- steps 2,3: x2 / x3 sweeps, register sliding window along the sweep direction ---------
 // One thread owns one (i, transverse) column and a chunk of `chunk` interfaces; lanes are
 // consecutive in i.  Cells reconstructed: l..u = s-2..e+2; interfaces l+1..u (:179-184).
-#ifndef SW_ALIGN
-#define SW_ALIGN 1
-#endif
 // (the pool puts zone i = 4 of every row on a 128-byte line when the pitch is a multiple of 16 doubles: api.hip)
 __host__ __device__ static inline int march_shift(const DevGrid &g) { return (g.sJ & 15) ? 0 : ((g.is - 2 + 12) & 15); }
 __host__ __device__ static inline int march_slots(const DevGrid &g)
@@ -315,14 +312,11 @@ __host__ __device__ static inline bool march_cell(const DevGrid &g, int q, int &
   i = g.is - 2 - sh + q;
   return q >= sh && i <= g.ie + 2;
 }
-// The limited slopes along x2 / x3 as a march (SLOPES_MARCH, the default): k_slopes reads and converts three cells per zone, two of them
+// The limited slopes along x2 / x3 as a march (the default; AA_SLOPES_MARCH=0: k_slopes): k_slopes reads and converts three cells per zone, two of them
 // in other rows, which at 512^3 come back from HBM for blocks on other XCDs; here a thread owns an (i, transverse) column and a
 // chunk of cells along D with the three-cell window in registers (every cell read and converted once, lanes on whole 128-byte
 // lines as in k_sweep_march).  ONE inlined instance of the conversion serves every cell, so the values do not depend on where
 // the chunks start.  Cells [s-3, e+3] along D, [s-2, e+2] across, as k_slopes.
-#ifndef SLOPES_MARCH
-#define SLOPES_MARCH 1
-#endif
 template <int NS, int D>
 __global__ void __launch_bounds__(64)
 k_slopes_march(DevGrid g, const Real *src, int chunk)
@@ -373,7 +367,6 @@ k_sweep_march(DevGrid g, const Real *src, Real dt, int chunk, int toff, int tcnt
   const int tlo = (D == 1 ? g.ks : g.js) - 2 + toff;
   const int nt  = tcnt;
   const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
-#if SW_ALIGN
   // lanes on whole 128-byte lines: a row of slots starts on the line that holds is-2 and is a whole number of lines long (a
   // wavefront's 64 lanes are four whole lines of one or two rows; the lanes off the ends of [is-2, ie+2] leave)
   const int nq = march_slots(g);
@@ -382,12 +375,6 @@ k_sweep_march(DevGrid g, const Real *src, Real dt, int chunk, int toff, int tcnt
   int i;
   const int t = tlo + (int)(lin / nq);
   if (!march_cell(g, q, i)) return;
-#else
-  const int ni = g.ie - g.is + 5;                              // i in [is-2, ie+2]
-  if (lin >= (long)ni*nt) return;
-  const int i = g.is - 2 + (int)(lin % ni);
-  const int t = tlo + (int)(lin / ni);
-#endif
   const int lo = (D == 1 ? g.js : g.ks), hi = (D == 1 ? g.je : g.ke);
   const int f0 = lo - 1 + blockIdx.y*chunk;                    // first interface of this chunk
   int f1 = f0 + chunk - 1; if (f1 > hi + 2) f1 = hi + 2;
@@ -494,10 +481,7 @@ k_sweep_tile(DevGrid g, const Real *src, Real dt)
 // ---- step 1: x1 sweep, neighbours through LDS ------------------------------------------
 // A block of B threads reconstructs B consecutive cells of one (j,k) row and solves the B-1
 // interfaces between them; blocks overlap by one cell.
-#ifndef SW_X1_FLAT
-#define SW_X1_FLAT 1
-#endif
-// The x1 sweep with the rows of a k-plane laid end to end (SW_X1_FLAT, the default): a plane's (je-js+5) rows of nc = ie-is+5
+// The x1 sweep with the rows of a k-plane laid end to end (the default; AA_X1_FLAT=0 at run time: k_sweep_x1): a plane's (je-js+5) rows of nc = ie-is+5
 // cells l..u are ONE line of slots, cut into blocks of B-1 faces wherever they fall, so that only the plane's last block has
 // idle lanes (a block per row piece left 576 lanes for 516 cells at 512^3, 128 for 68 at 64^3).  A row's first cell has no
 // face to solve and its lower neighbour is not the slot before it: the lanes at a row's (or the block's) ends fetch and convert
@@ -645,7 +629,7 @@ AA_DEV void load_prim3(const DevGrid &g, long m, Real w[6], Real &p0, Real &p1)
 #pragma unroll
   for (int v = 0; v < 5 + NS; v++) u[v] = Uf(g, v)[m];
   if (!NS) u[5] = 0.0;
-#if AA_FD_C2P
+#if AA_FAST_DIV
   const Real di = q_rcp(u[0]);          // as cons_to_prim: the same bits whichever kernel converts the zone
 #else
   const Real di = 1.0/u[0];
@@ -674,9 +658,6 @@ template <int D> AA_DEV void to_sweep(const Real wg[6], Real p, Real ws[6])
   ws[4] = p;
 }
 
-#ifndef AA_NT_ST
-#define AA_NT_ST 1
-#endif
 struct CellFlux {            // first-pass fluxes across one zone
   Real dF[3][6];             // F_e(upper face) - F_e(lower face), global frame
   Real gm[3], ge[3];         // gravity: q_e (phi_r - phi_l) d   and   q_e (F_lo (phi_c - phi_l) + F_hi (phi_r - phi_c))
@@ -743,9 +724,8 @@ AA_DEV void cell_finish(const DevGrid &g, long m, const Real q[3], const CellFlu
   }
   if (store) {
 #pragma unroll
-    for (int v = 0; v < NV; v++) {      // written here, read once by the next kernel: non-temporal (AA_NT_ST=0: plain stores)
-      if (AA_NT_ST) { __builtin_nontemporal_store(ul[v], LRf(g, D, 0, v) + m + sD); __builtin_nontemporal_store(ur[v], LRf(g, D, 1, v) + m); }
-      else { LRf(g, D, 0, v)[m + sD] = ul[v]; LRf(g, D, 1, v)[m] = ur[v]; }
+    for (int v = 0; v < NV; v++) {      // written here, read once by the next kernel: non-temporal
+      __builtin_nontemporal_store(ul[v], LRf(g, D, 0, v) + m + sD); __builtin_nontemporal_store(ur[v], LRf(g, D, 1, v) + m);
     }
   }
 #pragma unroll
@@ -762,18 +742,11 @@ AA_DEV void cell_states(const DevGrid &g, long m, Real dt, Real dtodx, const Rea
   cell_finish<NS, D, GRAV>(g, m, q, cf, wl, wr, store, lam_l, lam_r);
 }
 
-#ifndef CA_PARK
-#define CA_PARK 1
-#endif
-// CA_X1F: with the x3 first pass on board (X3F), k_correct_all also does the x1 FIRST pass: a zone's reconstruction along x1 is the
+// With the x3 first pass on board (X3F), k_correct_all also does the x1 FIRST pass: a zone's reconstruction along x1 is the
 // same for the first pass and for the correct pass, the right state of its upper face is one lane away, and the first-pass
 // fluxes it needs are those of its own two faces.  k_sweep_x1_flat is not launched and its fluxes never reach HBM; what a tile
 // of 64 zones cannot do alone, the flux of the face it shares with the next tile, comes from k_x1_edge_flux (1/64 of the faces),
 // which keeps its result where the x1 flux array was: [variable][edge][k][j].  Same arithmetic, same bits.
-#ifndef CA_X1F
-#define CA_X1F 1
-#endif
-bool ca_x1_on_board() { return CA_X1F != 0; }
 __host__ __device__ static inline int x1_edges(const DevGrid &g) { return (g.ie + 2 - (g.is - 16))/64; }   // edge b = 1 .. : face is-16+64b <= ie+2
 AA_DEV long x1_edge_index(const DevGrid &g, int nbe, int v, int b, int j, int k) { return (((long)v*nbe + (b - 1))*g.N3 + k)*g.N2 + j; }
 template <int NS, bool GRAV, int ORD>
@@ -805,26 +778,19 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
   __shared__ Real s_l[CA_TJ][64];
   // X3F: the x3 states of zone k+1 wait here while zone k is corrected (each thread its own slots, no barrier): 24
   // registers that the 6-variable gravity kernel does not have at 2 waves per SIMD (it spilled 16 to scratch)
-  // (CA_PARK3, with the x1 first pass on board: two sets of slots taken in turn, so that the states of zone k need no registers
+  // (with the x1 first pass on board: two sets of 12 slots taken in turn, so that the states of zone k need no registers
   //  between the iterations nor under the x1 Riemann problem: they are read where they are used)
-#ifndef CA_PARK3
-#define CA_PARK3 1
-#endif
-  constexpr bool PARK3 = X3F && (CA_X1F != 0) && (CA_PARK != 0) && (CA_PARK3 != 0);
-  __shared__ Real s_park[(X3F && CA_PARK) ? (PARK3 ? 24 : 12) : 1][CA_TJ][64];
+  __shared__ Real s_park[X3F ? 24 : 1][CA_TJ][64];
   // ... and in the 6-variable gravity kernel, which spilled three registers, the x1 / x2 frame pressures of planes k+1 and k+2 wait
-  // there too (each thread its own slots): no scratch, 18.53 -> 18.18 ms at 512^3 (same-box ABAB x 3; CA_PARK2=0: in registers)
-#ifndef CA_PARK2
-#define CA_PARK2 1
-#endif
-  constexpr bool PARK2 = (CA_PARK2 != 0) && X3F && NS && GRAV;
+  // there too (each thread its own slots): no scratch, 18.53 -> 18.18 ms at 512^3 (same-box ABAB x 3 against keeping them in registers)
+  constexpr bool PARK2 = X3F && NS && GRAV;
   __shared__ Real s_pp[PARK2 ? 4 : 1][CA_TJ][64];
   // The zones a tile needs from its neighbours (lane 0's lower / lane 63's upper x1 neighbour, row 0's lower / row CA_TJ-1's
   // upper x2 neighbour) are requested at the head of the iteration with everything else and wait here for their block: a load
   // issued inside a block would have to wait for the face-state stores of the block before it (loads and stores retire
   // through one counter).  s_h1: per wave, the 6 + 6 conserved variables of the two x1 neighbours, fetched by lanes 0..11.
   // X1F: and behind them the first-pass x1 fluxes of the tile's two edge faces (lanes 12..23)
-  constexpr bool X1F = X3F && (CA_X1F != 0);
+  constexpr bool X1F = X3F;      // the x1 first pass comes with the x3 one; the name marks what belongs to which
   __shared__ Real s_h1[CA_TJ][X1F ? 24 : 12];
   __shared__ Real s_h2[2][6][64];
   constexpr int NV = 5 + NS;
@@ -869,7 +835,7 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
   if (X3F) {
     load_prim3<NS>(g, (long)kbeg*g.sK + mcol, wn, pn0, pn1);
     load_prim3<NS>(g, (long)(kbeg + 1)*g.sK + mcol, wn2, pn20, pn21);
-    if (PARK2) { s_pp[0][row][lane] = pn0; s_pp[PARK2 ? 1 : 0][row][lane] = pn1; s_pp[PARK2 ? 2 : 0][row][lane] = pn20; s_pp[PARK2 ? 3 : 0][row][lane] = pn21; }
+    if constexpr (PARK2) { s_pp[0][row][lane] = pn0; s_pp[1][row][lane] = pn1; s_pp[2][row][lane] = pn20; s_pp[3][row][lane] = pn21; }
 #pragma unroll
     for (int v = 0; v < 6; v++) { f3[v] = 0.0; wl3[v] = 1.0; wr3[v] = 1.0; wc[v] = 1.0; }
   } else {
@@ -883,7 +849,7 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     long m = (long)k*g.sK + mcol;
     asm volatile("" : "+v"(m));                   // one index for all fields (see k_flux2_update)
     const bool full = (k >= k0);                  // block-uniform; the provider plane does x3 only
-    const int pk = (k & 1) ? 12 : 0;              // PARK3: the slots of zone k (those of zone k+1: 12 - pk)
+    const int pk = (k & 1) ? 12 : 0;              // X3F: the s_park slots of zone k (those of zone k+1: 12 - pk)
     const bool zone = (k >= kstart);              // block-uniform; X3F: the two planes before do the first pass only
     Real f3n[6], wlN[6], wrN[6];
 #pragma unroll
@@ -895,17 +861,11 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     Real mlo[3], mhi[3];
     Real hv1 = 0.0;
     // What the zone needs behind its x1 Riemann problem is requested in front of it where the registers allow: the wait would
-    // otherwise come behind it with nothing left to do.  CA_X1F_EARLY=1 (the default): the x2 first-pass fluxes -- k_correct_all 22.6 ->
-    // 20.2 ms at 512^3, three registers in scratch.  (The potentials and the x2 neighbour rows as well: tens of registers in scratch, a
-    // loss -- also with the potentials parked in LDS; profiles/r04_x1f_ab.txt.)  The scalar kernel without gravity (ifront) has no room
-    // at two waves per SIMD: CA_X1F_EARLY_NG, default 0.
-#ifndef CA_X1F_EARLY
-#define CA_X1F_EARLY 1
-#endif
-#ifndef CA_X1F_EARLY_NG
-#define CA_X1F_EARLY_NG 0
-#endif
-    constexpr bool EARLY_F = X1F && (((NS && !GRAV) ? CA_X1F_EARLY_NG : CA_X1F_EARLY) != 0);
+    // otherwise come behind it with nothing left to do.  So the x2 first-pass fluxes are: k_correct_all 22.6 -> 20.2 ms at 512^3, three
+    // registers in scratch.  (The potentials and the x2 neighbour rows as well: tens of registers in scratch, a loss -- also with the
+    // potentials parked in LDS; profiles/r04_x1f_ab.txt.)  The scalar kernel without gravity (ifront) has no room for it at two waves
+    // per SIMD and requests them where they are used.
+    constexpr bool EARLY_F = X1F && !(NS && !GRAV);
     Real hv2[6];
 #pragma unroll
     for (int v = 0; v < 6; v++) hv2[v] = 0.0;
@@ -927,28 +887,23 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     if (X3F) {
 #pragma unroll
       for (int n = 0; n < 6; n++) { wc[n] = wn[n]; wn[n] = wn2[n]; }
-      if (PARK2) { pc0 = s_pp[0][row][lane]; pc1 = s_pp[1][row][lane]; s_pp[0][row][lane] = s_pp[PARK2 ? 2 : 0][row][lane]; s_pp[PARK2 ? 1 : 0][row][lane] = s_pp[PARK2 ? 3 : 0][row][lane]; }
+      if constexpr (PARK2) { pc0 = s_pp[0][row][lane]; pc1 = s_pp[1][row][lane]; s_pp[0][row][lane] = s_pp[2][row][lane]; s_pp[1][row][lane] = s_pp[3][row][lane]; }
       else { pc0 = pn0; pc1 = pn1; pn0 = pn20; pn1 = pn21; }
       load_prim3<NS>(g, m + 2*g.sK, wn2, pn20, pn21);
-      if (PARK2) { s_pp[PARK2 ? 2 : 0][row][lane] = pn20; s_pp[PARK2 ? 3 : 0][row][lane] = pn21; }
+      if constexpr (PARK2) { s_pp[2][row][lane] = pn20; s_pp[3][row][lane] = pn21; }
       if (do3) {
         {   // (A) zone k+1 along x3
           Real wm[6], ws[6], wp[6];
           to_sweep<2>(wc, wc[4], wm); to_sweep<2>(wn, wn[4], ws); to_sweep<2>(wn2, wn2[4], wp);
           cell_recon<NS, 2, GRAV, ORD>(g, m + g.sK, dt, sr.dtodx[2], wm, ws, wp, wlN, wrN);
         }
-#if CA_PARK
-        if (PARK3) {      // (the states of zone k+1 go to their slots before (B): the left one is not needed in it)
+        // (the states of zone k+1 go to their slots before (B): the left one is not needed in it)
 #pragma unroll
-          for (int n = 0; n < NV; n++) { s_park[(PARK3 ? 12 - pk : 0) + n][row][lane] = wlN[n]; s_park[(PARK3 ? 12 - pk : 0) + 6 + n][row][lane] = wrN[n]; }
-        }
-#endif
+        for (int n = 0; n < NV; n++) { s_park[12 - pk + n][row][lane] = wlN[n]; s_park[12 - pk + 6 + n][row][lane] = wrN[n]; }
         if (k >= kstart - 1) {   // (B) first-pass flux of face k+1 (face_work<MODE_FLUX1>), sweep frame -> global variables
           Real ul[6], ur[6], f[6];
-          if (PARK3) {
 #pragma unroll
-            for (int n = 0; n < 6; n++) wl3[n] = (n < NV) ? s_park[(PARK3 ? pk : 0) + n][row][lane] : 0.0;
-          }
+          for (int n = 0; n < 6; n++) wl3[n] = (n < NV) ? s_park[pk + n][row][lane] : 0.0;
           prim_to_cons<NS>(wl3, ul, g.Gamma_1, g.rGamma_1);
           prim_to_cons<NS>(wrN, ur, g.Gamma_1, g.rGamma_1);
           flux_roe<NS>(ul, ur, wl3, wrN, 0.0, g.Gamma, g.Gamma_1, f);
@@ -956,12 +911,10 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
           for (int n = 0; n < NV; n++) f3n[gv<2>(n)] = f[n];
         }
       }
-#if CA_PARK
-      if (!PARK3 || !do3) {
+      if (!do3) {
 #pragma unroll
-        for (int n = 0; n < NV; n++) { s_park[(PARK3 ? 12 - pk : 0) + n][row][lane] = wlN[n]; s_park[(PARK3 ? 12 - pk : 0) + 6 + n][row][lane] = wrN[n]; }
+        for (int n = 0; n < NV; n++) { s_park[12 - pk + n][row][lane] = wlN[n]; s_park[12 - pk + 6 + n][row][lane] = wrN[n]; }
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     } else {
 #pragma unroll
@@ -979,7 +932,7 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
 #pragma unroll
     for (int v = 0; v < 6; v++) { wl1[v] = 1.0; wr1[v] = 1.0; }
     // X1F: what the zone needs behind its x1 Riemann problem (x2 first-pass fluxes, potentials, the x2 neighbour rows) is requested
-    // in front of it -- the wait would otherwise come after it with nothing left to do (CA_X1F_EARLY=0: requested where it is used)
+    // in front of it -- the wait would otherwise come after it with nothing left to do (EARLY_F; without it: requested where it is used)
     Real eb0[6], eb1[6];
 #pragma unroll
     for (int v = 0; v < 6; v++) { eb0[v] = 0.0; eb1[v] = 0.0; }
@@ -1082,9 +1035,9 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     }
     if (do3) {   // ---- x3 in front of x2 (and of x1 where the x1 first pass is not on board): what only this block needs (the plane below / the states zone k kept) is dead under the others ----
       Real ll, lr;
-      if (PARK3) {
+      if (X3F) {
 #pragma unroll
-        for (int n = 0; n < 6; n++) { wl3[n] = (n < NV) ? s_park[(PARK3 ? pk : 0) + n][row][lane] : 0.0; wr3[n] = (n < NV) ? s_park[(PARK3 ? pk : 0) + 6 + n][row][lane] : 0.0; }
+        for (int n = 0; n < 6; n++) { wl3[n] = (n < NV) ? s_park[pk + n][row][lane] : 0.0; wr3[n] = (n < NV) ? s_park[pk + 6 + n][row][lane] : 0.0; }
       }
       if (X3F) cell_finish<NS, 2, GRAV>(g, m, q, cf, wl3, wr3, full, ll, lr);
       else {
@@ -1167,14 +1120,7 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     if (X3F) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int n = 0; n < 6; n++) {
-#if CA_PARK
-        if (!PARK3) { wl3[n] = (n < NV) ? s_park[n][row][lane] : 0.0; wr3[n] = (n < NV) ? s_park[6 + n][row][lane] : 0.0; }
-#else
-        wl3[n] = wlN[n]; wr3[n] = wrN[n];
-#endif
-        f3[n] = f3n[n];
-      }
+      for (int n = 0; n < 6; n++) f3[n] = f3n[n];
     }
   }
 }
@@ -1454,10 +1400,7 @@ AA_DEV void face_solve(const DevGrid &g, const FaceIn &in, Real f[6])
   Real wl[6], wr[6];
   cons_to_prim<NS>(in.ul, wl, g.Gamma_1);
   cons_to_prim<NS>(in.ur, wr, g.Gamma_1);
-#ifndef FU_XD
-#define FU_XD 1
-#endif
-  flux_roe<NS, false, (FU_XD != 0)>(in.ul, in.ur, wl, wr, etah, g.Gamma, g.Gamma_1, f);      // (faster without the AA_FAST_DIV forms here; the AA_XDIV forms since the x3 flux is parked in LDS)
+  flux_roe<NS>(in.ul, in.ur, wl, wr, etah, g.Gamma, g.Gamma_1, f);      // (the scaling-free quotients pay here since the x3 flux is parked in LDS: k_flux2_update)
 }
 template <int NS, int D>
 AA_DEV void face_flux2(const DevGrid &g, long m, Real f[6])
@@ -1500,15 +1443,11 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
   //  next plane's writers off this plane's readers -- 8 wavefronts, a whole CU, wait at every barrier of this block)
   __shared__ Real s_f2[2][FU_TJ][6][64];
   __shared__ Real s_f1e[2][FU_TJ - 1][6], s_f1s[2][FU_TJ - 1][6];
-#ifndef FU_PARK
-#define FU_PARK 1
-#endif
   // The lower x3 flux of the zone -- live across the whole iteration in 12 registers -- waits in the thread's own LDS slots: the
   // 6-variable gravity kernel then holds 246 registers without scratch, and the scaling-free quotients / square roots of the
-  // solver (FU_XD), which cost it three spilled registers and 4 % before, pay: 13.77 -> 13.45 ms at 512^3 (same-box ABAB x 3;
-  // parked alone 13.70).  FU_PARK=0 / FU_XD=0: the round's earlier form.
-  constexpr bool FPARK = (FU_PARK != 0);
-  __shared__ Real s_f3[FPARK ? 6 : 1][FPARK ? FU_TJ : 1][64];
+  // solver (x_div, x_sqrt: hydro_dev.h), which cost it three spilled registers and 4 % before, pay: 13.77 -> 13.45 ms at 512^3
+  // (same-box ABAB x 3; parked alone 13.70).
+  __shared__ Real s_f3[6][FU_TJ][64];
   const int lane = threadIdx.x, row = threadIdx.y;
   // Tiles of 64 x (FU_TJ - 1) zones; the rows start on a 128-byte line (zone is) and do not overlap in x1: with a stride
   // of 63 zones every 512-byte row request touched a fifth line and 512 zones took 9 tiles (rocprofv3: 559 B/zone fetched
@@ -1551,10 +1490,8 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
     //  run-to-run difference of 1e-16 on the levels of a Mesh in the default build)
     if (KEEP && blockIdx.z == 0 && on_plane(kp, 2, k0)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, (long)k0*g.sK + mcol, f3lo);
   }
-  if (FPARK) {
 #pragma unroll
-    for (int n = 0; n < NV; n++) s_f3[FPARK ? n : 0][FPARK ? row : 0][lane] = f3lo[n];
-  }
+  for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3lo[n];
   // Software pipeline: the operands of the NEXT Riemann problem are requested before the current one is
   // solved (x2's during the x1 solve, x3's during x2's, the next zone's x1's during x3's), so that with two
   // wavefronts per SIMD the memory pipe is not idle while a wavefront computes.
@@ -1615,17 +1552,13 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // FU_EARLY=1 (the default): the potentials and d^{n+1/2} of the zone's update are requested in front of the x3 Riemann problem
+    // The potentials and d^{n+1/2} of the zone's update are requested in front of the x3 Riemann problem
     // instead of behind it (same-box, 512^3: 13.45 -> 13.15 ms; the conserved variables instead 13.26, both 14.57: four registers in
     // scratch -- profiles/r04_x1f_ab.txt item 7)
-#ifndef FU_EARLY
-#define FU_EARLY 1
-#endif
-    constexpr bool EP = GRAV && (FU_EARLY != 0);
     Real ep[7], edh = 0.0;
 #pragma unroll
     for (int v = 0; v < 7; v++) ep[v] = 0.0;
-    if (EP && cell) {
+    if (GRAV && cell) {
       ep[0] = Pf(g, 0)[m]; edh = dhalf[m];
       ep[1] = Pf(g, 1)[m + 1]; ep[2] = Pf(g, 1)[m]; ep[3] = Pf(g, 2)[m + g.sJ]; ep[4] = Pf(g, 2)[m]; ep[5] = Pf(g, 3)[m + g.sK]; ep[6] = Pf(g, 3)[m];
     }
@@ -1639,11 +1572,11 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
     if (cell) {
       if (KEEP && on_plane(kp, 2, k + 1)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, m + g.sK, f3);
 #pragma unroll
-      for (int n = 0; n < NV; n++) { if (FPARK) f3lo[n] = s_f3[FPARK ? n : 0][FPARK ? row : 0][lane]; d3[n] = f3[n] - f3lo[n]; }
+      for (int n = 0; n < NV; n++) { f3lo[n] = s_f3[n][row][lane]; d3[n] = f3[n] - f3lo[n]; }
       m3hi = f3[0];
       const Real m3lo = f3lo[0];
 #pragma unroll
-      for (int n = 0; n < NV; n++) { if (FPARK) s_f3[FPARK ? n : 0][FPARK ? row : 0][lane] = f3[n]; else f3lo[n] = f3[n]; }
+      for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3[n];
       Real u[6];
 #pragma unroll
       for (int v = 0; v < NV; v++) u[v] = Uf(g, v)[m];
@@ -1652,14 +1585,14 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
       unsigned char pinned = 0;
       if (CFL && pinmask) pinned = pinmask[m];
       if (GRAV) {   // :2741-2782, with the mass fluxes (sweep component 0) of the faces just solved
-        const Real phic = EP ? ep[0] : Pf(g, 0)[m], dh = EP ? edh : dhalf[m];
-        { const Real phir = EP ? ep[1] : Pf(g, 1)[m + 1], phil = EP ? ep[2] : Pf(g, 1)[m];
+        const Real phic = ep[0], dh = edh;
+        { const Real phir = ep[1], phil = ep[2];
           u[1] -= dtodx[0]*(phir - phil)*dh;
           u[4] -= dtodx[0]*(m1lo*(phic - phil) + m1hi*(phir - phic)); }
-        { const Real phir = EP ? ep[3] : Pf(g, 2)[m + g.sJ], phil = EP ? ep[4] : Pf(g, 2)[m];
+        { const Real phir = ep[3], phil = ep[4];
           u[2] -= dtodx[1]*(phir - phil)*dh;
           u[4] -= dtodx[1]*(m2lo*(phic - phil) + m2hi*(phir - phic)); }
-        { const Real phir = EP ? ep[5] : Pf(g, 3)[m + g.sK], phil = EP ? ep[6] : Pf(g, 3)[m];
+        { const Real phir = ep[5], phil = ep[6];
           u[3] -= dtodx[2]*(phir - phil)*dh;
           u[4] -= dtodx[2]*(m3lo*(phic - phil) + m3hi*(phir - phic)); }
       }
@@ -2387,7 +2320,6 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
   if (kcnt < 0) kcnt = nk_all - koff;
   if (kcnt <= 0) return;
   if (dir == 0) {
-#if SW_X1_FLAT
     const int flat = g.cfg.x1_flat;
     const long nc = g.ie - g.is + 5, nslots = nc*(g.je - g.js + 5);
     if (flat && nslots < (1L << 30)) {
@@ -2400,7 +2332,6 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
                          koff, (unsigned)nslots, (unsigned)rmul, rsh);
       return;
     }
-#endif
     const int nfaces = (g.ie - g.is + 1) + 3;          // interfaces l+1..u
     int nb = (nfaces + 254)/255;
     int B = (nfaces + nb - 1)/nb + 1;                  // B-1 interfaces per block
@@ -2416,10 +2347,9 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
     const int nfaces = (dir == 1 ? g.je - g.js : g.ke - g.ks) + 1 + 3;
     dim3 grid(nblk(ni*nt, 64), (nfaces + BT - 2)/(BT - 1)), blk(64, BT);
     const size_t lds = (size_t)(5 + NS)*(BT + 2)*64*sizeof(Real);
-    if (dir == 1) hipLaunchKernelGGL((k_sweep_tile<NS, 1, GRAV, MODE, BT, ORD>), grid, blk, lds, st, g, src, dt);
-    else          hipLaunchKernelGGL((k_sweep_tile<NS, 2, GRAV, MODE, BT, ORD>), grid, blk, lds, st, g, src, dt);
+    with_dir12(dir, [&](auto D) { hipLaunchKernelGGL((k_sweep_tile<NS, D, GRAV, MODE, BT, ORD>), grid, blk, lds, st, g, src, dt); });
   } else if constexpr (MODE == MODE_FLUX1 || MODE == MODE_VL) {
-    const long ni = SW_ALIGN ? march_slots(g) : g.ie - g.is + 5;
+    const long ni = march_slots(g);
     const long nt = (dir == 1 ? kcnt : g.je - g.js + 5);
     const int toff = (dir == 1 ? koff : 0);
     const int nfaces = (dir == 1 ? g.je - g.js : g.ke - g.ks) + 1 + 3;
@@ -2432,16 +2362,14 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
     int chunk = g.cfg.sw_chunk > 0 ? g.cfg.sw_chunk : SW_CHUNK;          // (AA_SW_CHUNK overrides)
     if (g.cfg.sw_chunk <= 0) while (chunk > 4 && (long)nblk(ni*nt, 64)*((nfaces + chunk - 1)/chunk) < 4096) chunk >>= 1;
     dim3 grid(nblk(ni*nt, 64), (nfaces + chunk - 1)/chunk);
-    if (dir == 1) hipLaunchKernelGGL((k_sweep_march<NS, 1, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt);
-    else          hipLaunchKernelGGL((k_sweep_march<NS, 2, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt);
+    with_dir12(dir, [&](auto D) { hipLaunchKernelGGL((k_sweep_march<NS, D, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt); });
   }
 }
 template <int NS, bool GRAV, int MODE>
 static void sweep_impl(const HostGrid &g, const Real *src, int dir, Real dt, hipStream_t st, int koff = 0, int kcnt = -1)
 {
   // third order: the slope arrays were filled from the state the sweep reconstructs (U; U^{n+1/2} for the van Leer corrector)
-  if (g.slope) sweep_impl_o<NS, GRAV, MODE, 3>(g, src, dir, dt, st, koff, kcnt);
-  else sweep_impl_o<NS, GRAV, MODE, 2>(g, src, dir, dt, st, koff, kcnt);
+  with_ord(g.slope != nullptr, [&](auto ORD) { sweep_impl_o<NS, GRAV, MODE, ORD>(g, src, dir, dt, st, koff, kcnt); });
 }
 template <int NS>
 static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *src)
@@ -2450,7 +2378,6 @@ static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *
   const int lo[3] = {g.is, g.js, g.ks}, hi[3] = {g.ie, g.je, g.ke};
   for (int d = 0; d < 3; d++) n *= hi[d] - lo[d] + 1 + (d == dir ? 6 : 4);
   dim3 grid(nblk(n, 256)), blk(256);
-#if SLOPES_MARCH
   const int march = g.cfg.slopes_march;
   if (march && dir != 0) {
     const long nq = march_slots(g), nt = (dir == 1 ? g.ke - g.ks : g.je - g.js) + 5;
@@ -2458,31 +2385,23 @@ static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *
     int chunk = g.cfg.sw_chunk > 0 ? g.cfg.sw_chunk : 32;                // (AA_SW_CHUNK overrides)
     if (g.cfg.sw_chunk <= 0) while (chunk > 4 && (long)nblk(nq*nt, 64)*((ncell + chunk - 1)/chunk) < 4096) chunk >>= 1;
     dim3 gm(nblk(nq*nt, 64), (ncell + chunk - 1)/chunk);
-    if (dir == 1) hipLaunchKernelGGL((k_slopes_march<NS, 1>), gm, dim3(64), 0, st, g, src, chunk);
-    else          hipLaunchKernelGGL((k_slopes_march<NS, 2>), gm, dim3(64), 0, st, g, src, chunk);
+    with_dir12(dir, [&](auto D) { hipLaunchKernelGGL((k_slopes_march<NS, D>), gm, dim3(64), 0, st, g, src, chunk); });
     return;
   }
-#endif
-  if (dir == 0) hipLaunchKernelGGL((k_slopes<NS, 0>), grid, blk, 0, st, g, src);
-  else if (dir == 1) hipLaunchKernelGGL((k_slopes<NS, 1>), grid, blk, 0, st, g, src);
-  else hipLaunchKernelGGL((k_slopes<NS, 2>), grid, blk, 0, st, g, src);
+  with_dir(dir, [&](auto D) { hipLaunchKernelGGL((k_slopes<NS, D>), grid, blk, 0, st, g, src); });
 }
-// the correct passes of all three directions in one kernel (after the three first passes)
 // the first-pass x1 fluxes of the faces between the tiles of k_correct_all (needs U only: the caller may run it beside the x2 sweep)
 template <int NS, bool GRAV>
 static void x1_edges_impl(const HostGrid &g, Real dt, hipStream_t st)
 {
-  if (!CA_X1F || x1_edges(g) <= 0) return;
+  if (x1_edges(g) <= 0) return;
   const int nj = g.je - g.js + 3, nk = g.ke - g.ks + 3;
   dim3 ge(nblk(nj, 64), nk, x1_edges(g));
-  if (g.slope) hipLaunchKernelGGL((k_x1_edge_flux<NS, GRAV, 3>), ge, dim3(64), 0, st, g, dt);
-  else         hipLaunchKernelGGL((k_x1_edge_flux<NS, GRAV, 2>), ge, dim3(64), 0, st, g, dt);
+  with_ord(g.slope != nullptr, [&](auto ORD) { hipLaunchKernelGGL((k_x1_edge_flux<NS, GRAV, ORD>), ge, dim3(64), 0, st, g, dt); });
 }
 void launch_x1_edges(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
-{
-  if (nscal) { if (grav) x1_edges_impl<1, true>(g, dt, st); else x1_edges_impl<1, false>(g, dt, st); }
-  else       { if (grav) x1_edges_impl<0, true>(g, dt, st); else x1_edges_impl<0, false>(g, dt, st); }
-}
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { x1_edges_impl<NS, GRAV>(g, dt, st); }); }
+// the correct passes of all three directions in one kernel (after the three first passes; x3f: after those of x2 and the tile-edge x1 fluxes)
 template <int NS, bool GRAV>
 static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t st, bool edges_done)
 {
@@ -2499,13 +2418,8 @@ static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t s
   dim3 grid(nblk(ni + 15, 64), nblk(nj, CA_TJ), (nk + kc - 1)/kc), blk(64, CA_TJ);
   if (x3f && !edges_done) x1_edges_impl<NS, GRAV>(g, dt, st);
   const StepRatios sr = step_ratios(g, dt);
-  if (x3f) {
-    if (g.slope) hipLaunchKernelGGL((k_correct_all<NS, GRAV, 3, true>), grid, blk, 0, st, g, dt, kc, sr);
-    else         hipLaunchKernelGGL((k_correct_all<NS, GRAV, 2, true>), grid, blk, 0, st, g, dt, kc, sr);
-  } else {
-    if (g.slope) hipLaunchKernelGGL((k_correct_all<NS, GRAV, 3, false>), grid, blk, 0, st, g, dt, kc, sr);
-    else         hipLaunchKernelGGL((k_correct_all<NS, GRAV, 2, false>), grid, blk, 0, st, g, dt, kc, sr);
-  }
+  with_flag(x3f, [&](auto X3F) { with_ord(g.slope != nullptr, [&](auto ORD) {
+    hipLaunchKernelGGL((k_correct_all<NS, GRAV, ORD, X3F>), grid, blk, 0, st, g, dt, kc, sr); }); });
   const long nb1 = (g.ie + 1 - (g.is - 16))/64, nb2 = (g.je + 1 - (g.js - 1))/CA_TJ;
   {
     const long c0 = nb1 > 0 ? nb1*nj*nk : 0, c1 = nb2 > 0 ? (long)ni*nb2*nk : 0;      // (a direction without inner tile edges returns at once)
@@ -2513,47 +2427,28 @@ static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t s
   }
 }
 void launch_correct_all(const HostGrid &g, int nscal, Real dt, bool grav, bool x3f, hipStream_t st, bool edges_done)
-{
-  if (nscal) { if (grav) correct_all_impl<1, true>(g, dt, x3f, st, edges_done); else correct_all_impl<1, false>(g, dt, x3f, st, edges_done); }
-  else       { if (grav) correct_all_impl<0, true>(g, dt, x3f, st, edges_done); else correct_all_impl<0, false>(g, dt, x3f, st, edges_done); }
-}
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { correct_all_impl<NS, GRAV>(g, dt, x3f, st, edges_done); }); }
 
 void launch_slopes(const HostGrid &g, int nscal, int dir, hipStream_t st, const Real *src)
-{ if (!src) src = g.U; if (nscal) slopes_impl<1>(g, dir, st, src); else slopes_impl<0>(g, dir, st, src); }
+{ if (!src) src = g.U; with_ns(nscal, [&](auto NS) { slopes_impl<NS>(g, dir, st, src); }); }
 
 void launch_sweep(const HostGrid &g, int nscal, int dir, Real dt, bool grav, hipStream_t st, int koff, int kcnt)
-{
-  if (nscal) { if (grav) sweep_impl<1, true, MODE_FLUX1>(g, g.U, dir, dt, st, koff, kcnt); else sweep_impl<1, false, MODE_FLUX1>(g, g.U, dir, dt, st, koff, kcnt); }
-  else       { if (grav) sweep_impl<0, true, MODE_FLUX1>(g, g.U, dir, dt, st, koff, kcnt); else sweep_impl<0, false, MODE_FLUX1>(g, g.U, dir, dt, st, koff, kcnt); }
-}
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { sweep_impl<NS, GRAV, MODE_FLUX1>(g, g.U, dir, dt, st, koff, kcnt); }); }
 // x1 first pass + x1 correct pass in one sweep (must run after the x2 and x3 first passes)
 void launch_sweep_correct_x1(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
-{
-  if (nscal) { if (grav) sweep_impl<1, true, MODE_BOTH>(g, g.U, 0, dt, st); else sweep_impl<1, false, MODE_BOTH>(g, g.U, 0, dt, st); }
-  else       { if (grav) sweep_impl<0, true, MODE_BOTH>(g, g.U, 0, dt, st); else sweep_impl<0, false, MODE_BOTH>(g, g.U, 0, dt, st); }
-}
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { sweep_impl<NS, GRAV, MODE_BOTH>(g, g.U, 0, dt, st); }); }
 // CTU steps 5-7, 8a, 9a for the faces of one direction (after all three first-pass sweeps)
 void launch_correct(const HostGrid &g, int nscal, int dir, Real dt, bool grav, hipStream_t st)
-{
-  if (nscal) { if (grav) sweep_impl<1, true, MODE_CORR>(g, g.U, dir, dt, st); else sweep_impl<1, false, MODE_CORR>(g, g.U, dir, dt, st); }
-  else       { if (grav) sweep_impl<0, true, MODE_CORR>(g, g.U, dir, dt, st); else sweep_impl<0, false, MODE_CORR>(g, g.U, dir, dt, st); }
-}
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { sweep_impl<NS, GRAV, MODE_CORR>(g, g.U, dir, dt, st); }); }
 // VL second-order fluxes: PLM without tracing on U^{n+1/2} (kept in LR[0][L]), etah = 0
 void launch_vl_flux2(const HostGrid &g, int nscal, int dir, Real dt, hipStream_t st)
-{
-  if (nscal) sweep_impl<1, false, MODE_VL>(g, g.LR, dir, dt, st); else sweep_impl<0, false, MODE_VL>(g, g.LR, dir, dt, st);
-}
-template <int NS>
-static void vl_flux1_impl(const DevGrid &g, int dir, hipStream_t st)
+{ with_ns(nscal, [&](auto NS) { sweep_impl<NS, false, MODE_VL>(g, g.LR, dir, dt, st); }); }      // (no gravity kick in the states: GRAV = false only)
+void launch_vl_flux1(const DevGrid &g, int nscal, int dir, hipStream_t st)
 {
   long n[3] = {g.N1, g.N2, g.N3}; n[dir] -= 1;
   dim3 grid(nblk(n[0]*n[1]*n[2], 256)), blk(256);
-  if (dir == 0) hipLaunchKernelGGL((k_vl_flux1<NS, 0>), grid, blk, 0, st, g);
-  else if (dir == 1) hipLaunchKernelGGL((k_vl_flux1<NS, 1>), grid, blk, 0, st, g);
-  else hipLaunchKernelGGL((k_vl_flux1<NS, 2>), grid, blk, 0, st, g);
+  with_ns(nscal, [&](auto NS) { with_dir(dir, [&](auto D) { hipLaunchKernelGGL((k_vl_flux1<NS, D>), grid, blk, 0, st, g); }); });
 }
-void launch_vl_flux1(const DevGrid &g, int nscal, int dir, hipStream_t st)
-{ if (nscal) vl_flux1_impl<1>(g, dir, st); else vl_flux1_impl<0>(g, dir, st); }
 // donor-cell fluxes + U^{n+1/2} in one kernel (what launch_vl_flux1 x3 + launch_vl_uhalf do)
 void launch_vl_predict(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
 {
@@ -2561,52 +2456,28 @@ void launch_vl_predict(const HostGrid &g, int nscal, Real dt, bool grav, hipStre
   int kc = g.cfg.vp_kc > 0 ? g.cfg.vp_kc : 32;                             // (AA_VP_KC overrides)
   if (g.cfg.vp_kc <= 0) while (kc > 4 && (long)nblk(ni, 63)*nblk(nj, VP_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
   dim3 grid(nblk(ni, 63), nblk(nj, VP_TJ - 1), (nk + kc - 1)/kc), blk(64, VP_TJ);
-  if (nscal) { if (grav) hipLaunchKernelGGL((k_vl_predict<1, true>), grid, blk, 0, st, g, dt, kc);
-               else      hipLaunchKernelGGL((k_vl_predict<1, false>), grid, blk, 0, st, g, dt, kc); }
-  else       { if (grav) hipLaunchKernelGGL((k_vl_predict<0, true>), grid, blk, 0, st, g, dt, kc);
-               else      hipLaunchKernelGGL((k_vl_predict<0, false>), grid, blk, 0, st, g, dt, kc); }
+  with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { hipLaunchKernelGGL((k_vl_predict<NS, GRAV>), grid, blk, 0, st, g, dt, kc); });
 }
 void launch_vl_uhalf(const DevGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
 {
   const long n = (long)(g.ie - g.is + 7)*(g.je - g.js + 7)*(g.ke - g.ks + 7);
   dim3 grid(nblk(n, 256)), blk(256);
-  if (nscal) { if (grav) hipLaunchKernelGGL((k_vl_uhalf<1, true>), grid, blk, 0, st, g, dt);
-               else      hipLaunchKernelGGL((k_vl_uhalf<1, false>), grid, blk, 0, st, g, dt); }
-  else       { if (grav) hipLaunchKernelGGL((k_vl_uhalf<0, true>), grid, blk, 0, st, g, dt);
-               else      hipLaunchKernelGGL((k_vl_uhalf<0, false>), grid, blk, 0, st, g, dt); }
+  with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { hipLaunchKernelGGL((k_vl_uhalf<NS, GRAV>), grid, blk, 0, st, g, dt); });
 }
 
-template <int NS>
-static void flux2_impl(const HostGrid &g, int dir, hipStream_t st)
+void launch_flux2(const HostGrid &g, int nscal, int dir, hipStream_t st)
 {
   const long n = (long)(g.ie - g.is + 1 + (dir == 0))*(g.je - g.js + 1 + (dir == 1))*(g.ke - g.ks + 1 + (dir == 2));
   dim3 grid(nblk8(n, 256)), blk(256);
-  if (dir == 0) hipLaunchKernelGGL((k_flux2<NS, 0>), grid, blk, 0, st, g, zone_order(g));
-  else if (dir == 1) hipLaunchKernelGGL((k_flux2<NS, 1>), grid, blk, 0, st, g, zone_order(g));
-  else hipLaunchKernelGGL((k_flux2<NS, 2>), grid, blk, 0, st, g, zone_order(g));
+  with_ns(nscal, [&](auto NS) { with_dir(dir, [&](auto D) { hipLaunchKernelGGL((k_flux2<NS, D>), grid, blk, 0, st, g, zone_order(g)); }); });
 }
-void launch_flux2(const HostGrid &g, int nscal, int dir, hipStream_t st)
-{ if (nscal) flux2_impl<1>(g, dir, st); else flux2_impl<0>(g, dir, st); }
 
-// fused second-pass fluxes + update (CTU); `keep`: the face planes whose fluxes are stored as well
-template <int NS, bool GRAV>
-static void launch_fu(const DevGrid &g, Real dt, int kc, dim3 grid, dim3 blk, const KeepPlanes *keep, DevScalars *sc, const unsigned char *pinmask,
-                      hipStream_t st)
-{
-  KeepPlanes none = {0, {{0}}};
-  if (sc) {
-    if (keep && keep->n) hipLaunchKernelGGL((k_flux2_update<NS, GRAV, true, true>), grid, blk, 0, st, g, g.dhalf, dt, kc, *keep, sc, pinmask, step_ratios(g, dt));
-    else                 hipLaunchKernelGGL((k_flux2_update<NS, GRAV, false, true>), grid, blk, 0, st, g, g.dhalf, dt, kc, none, sc, pinmask, step_ratios(g, dt));
-  } else {
-    if (keep && keep->n) hipLaunchKernelGGL((k_flux2_update<NS, GRAV, true, false>), grid, blk, 0, st, g, g.dhalf, dt, kc, *keep, sc, pinmask, step_ratios(g, dt));
-    else                 hipLaunchKernelGGL((k_flux2_update<NS, GRAV, false, false>), grid, blk, 0, st, g, g.dhalf, dt, kc, none, sc, pinmask, step_ratios(g, dt));
-  }
-}
 void launch_pinned_cfl(const DevGrid &g, long long n, const long long *idx, DevScalars *sc, hipStream_t st)
 { if (n > 0) { unsigned nb = nblk(n, 256*8); if (nb > 256) nb = 256; if (nb < 1) nb = 1;
                hipLaunchKernelGGL(k_pinned_cfl, dim3(nb), dim3(256), 0, st, g, n, idx, sc); } }
 void launch_pin_mask(const DevGrid &g, long long n, const long long *idx, unsigned char *mask, hipStream_t st)
 { if (n > 0) hipLaunchKernelGGL(k_pin_mask, dim3(nblk(n, 256)), dim3(256), 0, st, g, n, idx, mask); }
+// fused second-pass fluxes + update (CTU); `keep`: the face planes whose fluxes are stored as well; sc: and new_dt's maxima
 void launch_flux2_update(const HostGrid &g, int nscal, Real dt, bool grav, const KeepPlanes *keep, hipStream_t st, DevScalars *sc, const unsigned char *pinmask)
 {
   const int ni = g.ie - g.is + 1, nj = g.je - g.js + 1, nk = g.ke - g.ks + 1;
@@ -2614,31 +2485,31 @@ void launch_flux2_update(const HostGrid &g, int nscal, Real dt, bool grav, const
   int kc = kc_env > 0 ? kc_env : 32;
   if (kc_env <= 0) while (kc > 4 && (long)nblk(ni, 64)*nblk(nj, FU_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
   dim3 grid(nblk(ni, 64), nblk(nj, FU_TJ - 1), (nk + kc - 1)/kc), blk(64, FU_TJ);
-  if (nscal) { if (grav) launch_fu<1, true>(g, dt, kc, grid, blk, keep, sc, pinmask, st); else launch_fu<1, false>(g, dt, kc, grid, blk, keep, sc, pinmask, st); }
-  else       { if (grav) launch_fu<0, true>(g, dt, kc, grid, blk, keep, sc, pinmask, st); else launch_fu<0, false>(g, dt, kc, grid, blk, keep, sc, pinmask, st); }
+  const bool keeps = keep && keep->n;
+  const KeepPlanes kp = keeps ? *keep : KeepPlanes{0, {{0}}};
+  with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { with_flag(keeps, [&](auto KEEP) { with_flag(sc != nullptr, [&](auto CFL) {
+    hipLaunchKernelGGL((k_flux2_update<NS, GRAV, KEEP, CFL>), grid, blk, 0, st, g, g.dhalf, dt, kc, kp, sc, pinmask, step_ratios(g, dt)); }); }); });
 }
 
 long update_blocks(const DevGrid &g)
 { return (long)nblk8((long)(g.ie - g.is + 1)*(g.je - g.js + 1)*(g.ke - g.ks + 1), 256); }
+// the per-block maxima of an update with CFL -> sc (one launch behind it)
+static void cfl_fold(Real *cfl_part, unsigned nblocks, DevScalars *sc, hipStream_t st)
+{
+  unsigned nf = nblk(nblocks, 256*8); if (nf > 256) nf = 256;
+  hipLaunchKernelGGL(k_cfl_fold, dim3(nf), dim3(256), 0, st, cfl_part, (int)nblocks, sc);
+}
 // sc != nullptr: new_dt's maxima ride on the update (cfl_part: 3 * update_blocks(g) doubles of scratch; pinmask: zones left out)
 void launch_update(const HostGrid &g, int nscal, const Real *dhalf, Real dt, bool grav, hipStream_t st, DevScalars *sc, Real *cfl_part,
                    const unsigned char *pinmask)
 {
   const long n = (long)(g.ie - g.is + 1)*(g.je - g.js + 1)*(g.ke - g.ks + 1);
   dim3 grid(nblk8(n, 256)), blk(256);
-  if (sc && cfl_part) {
-    if (nscal) { if (grav) hipLaunchKernelGGL((k_update<1, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask);
-                 else      hipLaunchKernelGGL((k_update<1, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask); }
-    else       { if (grav) hipLaunchKernelGGL((k_update<0, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask);
-                 else      hipLaunchKernelGGL((k_update<0, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask); }
-    unsigned nf = nblk(grid.x, 256*8); if (nf > 256) nf = 256;
-    hipLaunchKernelGGL(k_cfl_fold, dim3(nf), dim3(256), 0, st, cfl_part, (int)grid.x, sc);
-    return;
-  }
-  if (nscal) { if (grav) hipLaunchKernelGGL((k_update<1, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr);
-               else      hipLaunchKernelGGL((k_update<1, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr); }
-  else       { if (grav) hipLaunchKernelGGL((k_update<0, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr);
-               else      hipLaunchKernelGGL((k_update<0, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr); }
+  const bool cfl = sc && cfl_part;
+  if (!cfl) { cfl_part = nullptr; pinmask = nullptr; }
+  with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { with_flag(cfl, [&](auto CFL) {
+    hipLaunchKernelGGL((k_update<NS, GRAV, CFL>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask); }); });
+  if (cfl) cfl_fold(cfl_part, grid.x, sc, st);
 }
 
 #if !AA_COOLING
@@ -2647,36 +2518,20 @@ void launch_update_fofc(const HostGrid &g, int nscal, const Real *dhalf, Real dt
 {
   const long n = (long)(g.ie - g.is + 1)*(g.je - g.js + 1)*(g.ke - g.ks + 1);
   dim3 grid(nblk8(n, 256)), blk(256);
-  if (sc_cfl && cfl_part) {
-    if (nscal) { if (grav) hipLaunchKernelGGL((k_update_fofc<1, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list);
-                 else      hipLaunchKernelGGL((k_update_fofc<1, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list); }
-    else       { if (grav) hipLaunchKernelGGL((k_update_fofc<0, true, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list);
-                 else      hipLaunchKernelGGL((k_update_fofc<0, false, true>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list); }
-    unsigned nf = nblk(grid.x, 256*8); if (nf > 256) nf = 256;
-    hipLaunchKernelGGL(k_cfl_fold, dim3(nf), dim3(256), 0, st, cfl_part, (int)grid.x, sc_cfl);
-    return;
-  }
-  if (nscal) { if (grav) hipLaunchKernelGGL((k_update_fofc<1, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list);
-               else      hipLaunchKernelGGL((k_update_fofc<1, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list); }
-  else       { if (grav) hipLaunchKernelGGL((k_update_fofc<0, true, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list);
-               else      hipLaunchKernelGGL((k_update_fofc<0, false, false>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), nullptr, nullptr, sc, list); }
+  const bool cfl = sc_cfl && cfl_part;
+  if (!cfl) { cfl_part = nullptr; pinmask = nullptr; }
+  with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { with_flag(cfl, [&](auto CFL) {
+    hipLaunchKernelGGL((k_update_fofc<NS, GRAV, CFL>), grid, blk, 0, st, g, dhalf, dt, zone_order(g), cfl_part, pinmask, sc, list); }); });
+  if (cfl) cfl_fold(cfl_part, grid.x, sc_cfl, st);
 }
 void launch_fofc_fix(const DevGrid &g, int nscal, const Real *un, Real dt, DevScalars *sc, long long *list, hipStream_t st)
-{
-  if (nscal) hipLaunchKernelGGL(k_fofc_fix<1>, dim3(1), dim3(64), 0, st, g, un, dt, sc, list);
-  else       hipLaunchKernelGGL(k_fofc_fix<0>, dim3(1), dim3(64), 0, st, g, un, dt, sc, list);
-}
-template <int NS>
-static void fofc_nanfix_impl(const DevGrid &g, int dir, const Real *un, DevScalars *sc, hipStream_t st)
+{ with_ns(nscal, [&](auto NS) { hipLaunchKernelGGL(k_fofc_fix<NS>, dim3(1), dim3(64), 0, st, g, un, dt, sc, list); }); }
+void launch_fofc_nanfix(const DevGrid &g, int nscal, int dir, const Real *un, DevScalars *sc, hipStream_t st)
 {
   long n[3] = {g.ie - g.is + 3, g.je - g.js + 3, g.ke - g.ks + 3}; n[dir] -= 1;
   dim3 grid(nblk(n[0]*n[1]*n[2], 256)), blk(256);
-  if (dir == 0) hipLaunchKernelGGL((k_fofc_nanfix<NS, 0>), grid, blk, 0, st, g, un, sc);
-  else if (dir == 1) hipLaunchKernelGGL((k_fofc_nanfix<NS, 1>), grid, blk, 0, st, g, un, sc);
-  else hipLaunchKernelGGL((k_fofc_nanfix<NS, 2>), grid, blk, 0, st, g, un, sc);
+  with_ns(nscal, [&](auto NS) { with_dir(dir, [&](auto D) { hipLaunchKernelGGL((k_fofc_nanfix<NS, D>), grid, blk, 0, st, g, un, sc); }); });
 }
-void launch_fofc_nanfix(const DevGrid &g, int nscal, int dir, const Real *un, DevScalars *sc, hipStream_t st)
-{ if (nscal) fofc_nanfix_impl<1>(g, dir, un, sc, st); else fofc_nanfix_impl<0>(g, dir, un, sc, st); }
 #endif
 
 void launch_bc(const DevGrid &g, int nscal, int dir, int side, int flag, hipStream_t st)
@@ -2740,21 +2595,18 @@ void launch_unpack_x2(const DevGrid &g, int nvar, int j0, const Real *buf, hipSt
 
 void launch_test_fluxes(int nscal, Real gamma, int n, const Real *Ul, const Real *Ur, const Real *eta, Real *F, hipStream_t st)
 {
-  if (nscal) hipLaunchKernelGGL((k_test_fluxes<1>), dim3(nblk(n, 128)), dim3(128), 0, st, gamma, n, Ul, Ur, eta, F);
-  else       hipLaunchKernelGGL((k_test_fluxes<0>), dim3(nblk(n, 128)), dim3(128), 0, st, gamma, n, Ul, Ur, eta, F);
+  with_ns(nscal, [&](auto NS) { hipLaunchKernelGGL((k_test_fluxes<NS>), dim3(nblk(n, 128)), dim3(128), 0, st, gamma, n, Ul, Ur, eta, F); });
 }
 void launch_test_lr_ppm(int nscal, Real gamma, int n, const Real *W, Real dt, Real dx, int il, int iu, Real *Wl, Real *Wr, hipStream_t st)
 {
   const int nc = iu - il + 3;
-  if (nscal) hipLaunchKernelGGL((k_test_lr_ppm<1>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr);
-  else       hipLaunchKernelGGL((k_test_lr_ppm<0>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr);
+  with_ns(nscal, [&](auto NS) { hipLaunchKernelGGL((k_test_lr_ppm<NS>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr); });
 }
 void launch_test_lr(int nscal, Real gamma, int n, const Real *W, Real dt, Real dx, int il, int iu, Real *Wl, Real *Wr, hipStream_t st)
 {
   (void)n;
   const int nc = iu - il + 3;
-  if (nscal) hipLaunchKernelGGL((k_test_lr<1>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr);
-  else       hipLaunchKernelGGL((k_test_lr<0>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr);
+  with_ns(nscal, [&](auto NS) { hipLaunchKernelGGL((k_test_lr<NS>), dim3(nblk(nc, 128)), dim3(128), 0, st, gamma, n, W, dt, dx, il, iu, Wl, Wr); });
 }
 
 }  // namespace aa / aa_cool

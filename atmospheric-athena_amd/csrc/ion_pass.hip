@@ -60,9 +60,6 @@ AA_DEV Real wave_incl_prod(Real v, int lane)
 // range).  The ion step is not bit-comparable with the CPU anyway (device exp/log); these stay at 1e-16.
 AA_DEV Real frcp(Real x)
 {
-#ifdef STUB_RCP
-  return x;
-#endif
   const Real ax = fabs(x);
   if (ax > 1.0e-280 && ax < 1.0e280) {
     Real r = __builtin_amdgcn_rcp(x);
@@ -77,9 +74,6 @@ AA_DEV Real frcp(Real x)
 // mass); for a temperature: every T below the floor -- zero, negative -- only ever selects the floor branches
 AA_DEV Real frcp_n(Real x)
 {
-#ifdef STUB_RCP
-  return x;
-#endif
   Real r = __builtin_amdgcn_rcp(x);
   Real e = fma(-x, r, 1.0); r = fma(e, r, r);
   e = fma(-x, r, 1.0); r = fma(e, r, r);
@@ -106,9 +100,6 @@ AA_DEV Real fsqrt_n(Real x)
 template <int N>
 AA_DEV void exp_n(const Real (&x)[N], Real (&y)[N], const Real *tE)
 {
-#ifdef STUB_EXP
-  for (int k = 0; k < N; k++) y[k] = x[k]; return;
-#endif
   Real kf[N], r[N], q[N];
 #pragma unroll
   for (int k = 0; k < N; k++) {
@@ -138,9 +129,6 @@ AA_DEV void exp_n(const Real (&x)[N], Real (&y)[N], const Real *tE)
 // (x just under a power of two: e ln2 and ln m cancel); NaN -> NaN.
 AA_DEV Real log_pos(Real x, const Real *tR, const Real *tL)
 {
-#ifdef STUB_LOG
-  return x;
-#endif
   const Real m = 2.0*__builtin_amdgcn_frexp_mant(x);
   const int e = __builtin_amdgcn_frexp_exp(x) - 1;
   int j = (int)((m - 1.0)*128.0);
@@ -277,18 +265,10 @@ AA_DEV Real zone_ph(Real fin, Real etau, Real n_H, Real inv_len)      // ionradp
 
 struct Ops { Real d, ke, E, s, fp, e0, x0, vm; unsigned short sg; };
 
-#ifndef AA_ION_PREFETCH
-#define AA_ION_PREFETCH 0            /* 1: next tile's operands in flight during this tile's arithmetic (17 more VGPRs) */
-#endif
-#ifndef AA_ION_PREFETCH_HALF
-#define AA_ION_PREFETCH_HALF 0       /* the same for the first / closing passes (which have the registers to spare) */
-#endif
-#ifndef AA_ION_PAR_LDS
-#define AA_ION_PAR_LDS 1
-#endif
 // waves per SIMD the register budget is cut for.  With OCML's exp / log and IEEE divisions the full pass needed 3 waves
 // plus a software prefetch of the next tile (157 VGPRs); with the table-driven exp / log it fits 4 waves without the
-// prefetch (127 VGPRs, no spills) and the fourth wave hides more latency than the prefetch did: 2.63 against 2.98 ms
+// prefetch (127 VGPRs, no spills) and the fourth wave hides more latency than the prefetch did: 2.63 against 2.98 ms.
+// So the next tile's operands are requested behind this tile's arithmetic, in every pass.
 #ifndef AA_ION_PASS_WAVES
 #define AA_ION_PASS_WAVES 4
 #endif
@@ -373,14 +353,8 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
     bool nhave = true;
     if (nt == ntile) { nt = 0; nray = ray + nwaves_u; nhave = nray < nrays_u; if (nhave) nrow = row_of(nray); }
     Ops no; long nm = 0; bool nin = false;
-    constexpr bool PF = (UPD && SWP) ? (AA_ION_PREFETCH != 0) : (AA_ION_PREFETCH_HALF != 0);
-    if (PF && nhave) load(nrow, nt, no, nm, nin);            // in flight during this tile's arithmetic
-#if AA_ION_PAR_LDS
 #define PAR_HERE(name) int name##_off = 0; asm volatile("" : "+v"(name##_off)); \
                        const IonPar &name = *(const IonPar*)((const char*)&s_par + name##_off)
-#else
-#define PAR_HERE(name) const IonPar &name = p_arg
-#endif
 
     if (sweep && t == 0) {                                    // ionradplane_3d.c:262-271: flux entering the ray
       Real f0 = flux0;
@@ -492,7 +466,7 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
       if (from_init || c.E != E0) Uq(g,4)[m] = c.E;
       if (from_init || c.s != s0) Uq(g,5)[m] = c.s;
     }
-    if (!PF && nhave) load(nrow, nt, no, nm, nin);
+    if (nhave) load(nrow, nt, no, nm, nin);
     ray = nray; t = nt; have = nhave; row = nrow; o = no; m = nm; in = nin;
   }
 

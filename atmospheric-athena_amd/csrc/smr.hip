@@ -547,6 +547,12 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels, bool two_d = false)
   return m;
 }
 
+// ionrad_smr.c:97-98 mixes a parent-local index with the child's root-relative Disp: with a displaced
+// parent (3+ levels) the reference writes out of bounds.  Refused by default; AA_SMR_DEEP_RADIATION=fixed
+// uses the index the formula evidently means (child origin - 2 x parent origin), a documented
+// departure from the reference for decks like its own 5-level one.
+static bool deep_radiation_fixed() { const char *e = getenv("AA_SMR_DEEP_RADIATION"); return e && strcmp(e, "fixed") == 0; }
+
 // init_grid.c (overlap tables) + SMR_init (smr.c:2931).  Takes over the levels' streams: all
 // levels run on one stream so that inter-level kernels are ordered without events.
 static int mesh_create_nested(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out, const bool two_d)
@@ -617,13 +623,8 @@ static int mesh_create_nested(int nlevels, aa_grid **levels, const int *disp, aa
       for (int d = 0; d < nd; d++) if (dc[d] > disp[3*q + d] + Q->p.Nx[d] || disp[3*q + d] > dc[d] + C->p.Nx[d]) sep = true;
       if (!sep) { mesh_drop(m); return aa_fail(-1, "[init_mesh]: Domains at the same level overlap or touch (grids %d and %d)", q, c); }
     }
-    // ionrad_smr.c:97-98 mixes a parent-local index with the child's root-relative Disp: with a displaced
-    // parent (3+ levels) the reference writes out of bounds.  Refused by default; AA_SMR_DEEP_RADIATION=fixed
-    // uses the index the formula evidently means (child origin - 2 x parent origin), a documented
-    // departure from the reference for decks like its own 5-level one.
-    if (P->p.ion && (dp[1] || dp[2])) {
-      const char *e = getenv("AA_SMR_DEEP_RADIATION");
-      if (!(e && strcmp(e, "fixed") == 0)) {
+    if (P->p.ion && (dp[1] || dp[2])) {      // (see deep_radiation_fixed)
+      if (!deep_radiation_fixed()) {
         mesh_drop(m); return aa_fail(-1, "[aa_mesh_create]: radiation across a displaced parent (grid %d) is undefined in the reference "
                                      "(set AA_SMR_DEEP_RADIATION=fixed for the corrected hand-off)", pi);
       }
@@ -1063,8 +1064,7 @@ static int cut_create(int nlevels, aa_grid **levels, const int *disp, aa_mesh **
       if ((a == 0 && plo) || (b == np && phi)) return aa_fail(-1, "[init_mesh] child Domain (grid %d) touches its parent in x%d", c, d + 1);
     }
     if (levels[c - 1]->p.ion && (lev[c - 1].disp[1] || lev[c - 1].disp[2])) {
-      const char *e = getenv("AA_SMR_DEEP_RADIATION");
-      if (!(e && strcmp(e, "fixed") == 0))
+      if (!deep_radiation_fixed())
         return aa_fail(-1, "[aa_mesh_create]: radiation across a displaced parent (grid %d) is undefined in the reference "
                            "(set AA_SMR_DEEP_RADIATION=fixed for the corrected hand-off)", c - 1);
     }
