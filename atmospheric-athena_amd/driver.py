@@ -223,6 +223,16 @@ class _Runner:
         self._set_state(head["time"], head["dt"], head["nstep"])
         self.restarted, self.par = True, par
 
+    @staticmethod
+    def _mesh_sources(head0, par, run):
+        """regrid = True of MeshRun / MeshDriver.from_restart: (the Domains of the file's table -- config.levels --, per Domain the
+        Grids of the run that wrote the files with the file each lies in -- restart.scan_mesh_sources)"""
+        if run.ndim == 2:
+            raise restart.RestartError("[restart_grids]: regrid is not built for a 2-D mesh (Nx3 = 1): its files are read on the "
+                                       "cuts that wrote them")
+        doms = config.levels(par, run)
+        return doms, restart.scan_mesh_sources(head0["path"], doms, run.nscal, run.ion, head0)
+
     # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
     @contextlib.contextmanager
     def _rst_file(self, out, outputs, rel=None, table=None):
@@ -237,6 +247,24 @@ class _Runner:
             restart.write_header(f, restart.par_dump(table(par) if table else par), self.nstep, self.time, self.dt)
             yield f
             restart.write_trailer(f)
+
+    def _write_restart_mesh_split(self, out, outputs, Nxs, box_payload):
+        """OutputSet(rst_mesh_ngrid=...): one file per rank of a run of the reference whose Domains (of `Nxs` zones, level by level)
+        are cut by those NGrid_x* -- ``id<r>/<base>[-id<r>].NNNN.rst`` holding, in Domain order, the sections of the Grids
+        restart.mesh_grid_boxes deals to rank r, under a table with NGrid_x* of every <domainN> set, no AutoWithNProc, and its
+        own problem_id.  box_payload(n, f, lo, nx) writes the sections of the box [lo, lo + nx) of Domain n."""
+        ngrids = outputs.rst_mesh_ngrid
+        if len(ngrids) != len(Nxs):
+            raise ValueError(f"[dump_restart]: rst_mesh_ngrid names {len(ngrids)} Domains, the mesh has {len(Nxs)}")
+        table = restart.mesh_grid_boxes(list(zip(Nxs, ngrids)), outputs.rst_mesh_nproc)
+        for r in range(outputs.rst_mesh_nproc):
+            base = outputs.basename + ("-id%d" % r if r else "")
+            rel = os.path.join("id%d" % r, dumps.fname(base, 0, 0, out.num, "rst"))
+            with self._rst_file(out, outputs, rel, lambda par: restart.regrid_mesh_par(par, ngrids, r, outputs.basename)) as f:
+                for n, boxes in enumerate(table):
+                    for rank, lo, nx in boxes:
+                        if rank == r:
+                            box_payload(n, f, lo, nx)
 
     def _host_state(self, *level):
         """(U of the active zones, EdgeFlux or None) from the host block of an engine that has no write_rst_payload: what
@@ -683,11 +711,32 @@ class MeshRun(_Runner):
 
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
-                     device: int = 0, strict: Optional[bool] = None, nslab: int = 1, cuts=None) -> "MeshRun":
+                     device: int = 0, strict: Optional[bool] = None, nslab: int = 1, cuts=None, regrid: bool = False) -> "MeshRun":
         """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770).
-        nslab / cuts: resume on a Mesh cut into slabs inside the library, whatever wrote the file (lib.Mesh)."""
+        nslab / cuts: resume on a Mesh cut into slabs inside the library, whatever wrote the file (lib.Mesh).
+
+        regrid = True takes the files of an MPI run of the reference, `path` being rank 0's, whatever cuts wrote them: every
+        <domainN> by its own NGrid_x1/2/3, x1 cuts included, the Grids dealt to the ranks as restart.mesh_grid_boxes states it,
+        several Domains on a level included.  Every level reads, section by section, every source Grid's piece straight to the
+        device (lib.Grid.read_rst_boxes); a level cut into slabs inside the library takes whole sections only, so one section
+        of one level at a time is joined on the host (lib.Grid.read_rst_joined).  `.par` then names the decomposition this
+        run is on (NGrid_x* = 1 in every <domainN>, no AutoWithNProc): its own dumps are read back without the keyword."""
         from . import lib
         head, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        if regrid:
+            grids, sources = cls._mesh_sources(head, par, run)
+            m = cls(lib.Mesh(grids, device, strict, initial=False, nslab=nslab, cuts=cuts), run)
+            try:
+                for g, cfg, src in zip(m.mesh.lev, grids, sources):
+                    if m.mesh.cuts is not None:
+                        g.read_rst_joined(src, cfg.Nx)
+                    else:
+                        g.read_rst_boxes(src, cfg.Nx, (0, 0, 0), cfg.Nx)
+            except Exception:
+                m.mesh.close()
+                raise
+            m._resumed(head, restart.regrid_mesh_par(par, [(1, 1, 1)] * len(grids)))
+            return m
         grids = config.levels_2d(par, run) if run.ndim == 2 else config.levels(par, run)      # by the file's table: Nx3 = 1 is a 2-D Mesh
         head["levels"] = restart.index_sections(head, [g.Nx for g in grids], run.nscal, run.ion)
         m = cls(lib.Mesh(grids, device, strict, initial=False, nslab=nslab, cuts=cuts), run)
@@ -723,6 +772,13 @@ class MeshRun(_Runner):
 
     def write_restart(self, out, outputs):
         """one file for all levels (restart.c:531-770), the sections of every level from the device in file order"""
+        if getattr(outputs, "rst_mesh_ngrid", None):
+            if getattr(self.mesh, "cuts", None) is not None:
+                raise ValueError("[dump_restart]: rst_mesh_ngrid on a Mesh cut into slabs inside the library: its level handles "
+                                 "hand out whole sections only")
+            lev = self.mesh.lev
+            return self._write_restart_mesh_split(out, outputs, [g.cfg.Nx for g in lev],
+                                                  lambda n, f, lo, nx: lev[n].write_rst_box_payload(f, lo, nx))
         with self._rst_file(out, outputs) as f:
             for g in self.mesh.lev:
                 g.write_rst_payload(f)
@@ -828,6 +884,8 @@ class HipMeshEngine:
 
     def write_rst_payload(self, l, f): self.lev[l].write_rst_payload(f)
     def read_rst_payload(self, l, f): self.lev[l].read_rst_payload(f)
+    def read_rst_boxes(self, l, sources, Nx, lo, n): self.lev[l].read_rst_boxes(sources, Nx, lo, n)
+    def write_rst_box_payload(self, l, f, lo, n): self.lev[l].write_rst_box_payload(f, lo, n)
     def sync(self): self.lev[0].sync()
     def close(self): self.mesh.close()
 
@@ -867,16 +925,36 @@ class MeshDriver(_Runner):
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
                      engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
-                     cuts=None) -> "MeshDriver":
+                     cuts=None, regrid: bool = False) -> "MeshDriver":
         """``athena -r path [block/key=value ...]`` of the MPI + SMR build (main.c:168-173, :216-288; restart_grids,
         restart.c:52-456).  `path` is rank 0's file: every rank takes the parameter table from it, with the overrides on top
         (an unknown key is an error), and reads the Grids it holds, root first, from restart.rank_path(path, rank).  A file
         written for other cuts or another number of ranks holds Grids of other sizes and is refused by the size check of
         restart.index_sections.  The problem generator does not run.  The driver keeps the table as `.par`:
-        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block."""
+        OutputSet.from_par(d.par, d.time, rundir, rank, nranks) continues the numbering of every <outputN> block.
+
+        regrid = True resumes on THIS driver's slabs (rank, nranks, cuts) whatever cuts wrote the files -- every <domainN> by its
+        own NGrid_x1/2/3, x1 cuts included, the Grids dealt to the ranks as restart.mesh_grid_boxes states it: every rank reads,
+        for each Grid of its slab stack, the box ``g.disp - domain.disp`` of that level's Domain from every source Grid that
+        meets it; time, dt and nstep are rank 0's file's.  `.par` then names the new decomposition (NGrid_x3 of a <domainN> =
+        the ranks that hold zones of it, no AutoWithNProc)."""
         head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        sources = cls._mesh_sources(head0, par, run)[1] if regrid else None
         d = cls(par, run, engine_factory, rank, nranks, device, strict, cuts, initial=False)
-        d._resumed(d._read_rank_file(head0, [g.Nx for g in d.cfg.levels], per_level=True), par)
+        if not regrid:
+            d._resumed(d._read_rank_file(head0, [g.Nx for g in d.cfg.levels], per_level=True), par)
+            return d
+        for l, g in enumerate(d.cfg.levels):
+            dom = d.domains[l]
+            lo = tuple(g.disp[a] - (dom.disp[a] if dom.level else 0) for a in range(3))
+            if hasattr(d.eng, "read_rst_boxes"):
+                d.eng.read_rst_boxes(l, sources[l], dom.Nx, lo, g.Nx)
+            elif hasattr(d.eng, "load_state"):
+                d.eng.load_state(l, *restart.read_state_boxes(sources[l], dom.Nx, lo, g.Nx, run.nscal))
+            else:
+                raise RuntimeError("[restart_grids]: this engine takes no state (read_rst_boxes or load_state)")
+        held = [sum(1 for r in range(nranks) if d.cfg.table[r][l] is not None) for l in range(d.NL)]
+        d._resumed(head0, restart.regrid_mesh_par(par, [(1, 1, n) for n in held]))
         return d
 
     def _set_state(self, time, dt, nstep):
@@ -929,12 +1007,33 @@ class MeshDriver(_Runner):
     def write_restart(self, out, outputs):
         """dump_restart (restart.c:463-983): ONE file per rank -- the parameter table as it stands now, then the sections of
         every Grid this rank holds, root first (:531-770)."""
+        if getattr(outputs, "rst_mesh_ngrid", None):
+            return self._write_restart_split(out, outputs)
         with self._rst_file(out, outputs) as f:
             for l in range(self.nl):
                 if hasattr(self.eng, "write_rst_payload"):    # the sections come from the device in file order (csrc/restart.hip)
                     self.eng.write_rst_payload(l, f)
                 else:
                     restart.write_grid_sections(f, *self._host_state(l))
+
+    def _write_restart_split(self, out, outputs):
+        """OutputSet(rst_mesh_ngrid=...) on one rank, whose slab stack is every whole Domain (_Runner._write_restart_mesh_split)"""
+        if self.nranks > 1:
+            raise ValueError("[dump_restart]: rst_mesh_ngrid takes a one-rank run")
+        if hasattr(self.eng, "write_rst_box_payload"):
+            def payload(l, f, lo, nx): self.eng.write_rst_box_payload(l, f, lo, nx)
+        else:
+            host = {}
+
+            def payload(l, f, lo, nx):
+                if l not in host:
+                    host.clear()                      # (one level's host block at a time)
+                    host[l] = self._host_state(l)
+                U, ef = host[l]
+                k, j, i = (slice(lo[a], lo[a] + nx[a]) for a in (2, 1, 0))
+                k1, j1, i1 = (slice(lo[a], lo[a] + nx[a] + 1) for a in (2, 1, 0))
+                restart.write_grid_sections(f, U[k, j, i], None if ef is None else ef[k1, j1, i1])
+        self._write_restart_mesh_split(out, outputs, [g.Nx for g in self.domains], payload)
 
     def _p2p(self, sends, recvs):
         """sends: [(tensor, peer)], recvs: [(tensor, peer)]; gloo moves host tensors only."""

@@ -521,16 +521,32 @@ class Grid:
             f.write(b"\n" + label.encode() + b"\n")
             f.write(memoryview(self.rst_get_box(s, lo, [int(v) + e for v in n])).cast("B"))
 
-    def read_rst_boxes(self, sources, rootNx, lo, n):
-        """This Grid = [lo, lo + n) of the root Domain from the files of restart.scan_sources: section by section, every source
-        file's part of it (restart.box_pieces) straight to the device -- never more than one such part in host memory."""
+    def read_rst_boxes(self, sources, Nx, lo, n):
+        """This Grid = [lo, lo + n) of a Domain of `Nx` zones from the files that hold it -- restart.scan_sources for the root
+        Domain of a single-level run, one Domain's list of restart.scan_mesh_sources for a refined mesh (lo relative to the
+        Domain): section by section, every source's part of it (restart.box_pieces) straight to the device -- never more than
+        one such part in host memory."""
         from . import restart
         for s, (label, _cnt) in enumerate(self.rst_sections()):
             e = 1 if label == "EDGEFLUX" else 0
-            for src, slo, dlo, ext in restart.box_pieces(sources, rootNx, lo, [int(v) + e for v in n], bool(e)):
-                if src["levels"][0][s][0] != label:
-                    raise restart.RestartError(f"[restart_grids]: Expected {label}, found {src['levels'][0][s][0]}")
+            for src, slo, dlo, ext in restart.box_pieces(sources, Nx, lo, [int(v) + e for v in n], bool(e)):
+                found = src["levels"][src.get("entry", 0)][s][0]
+                if found != label:
+                    raise restart.RestartError(f"[restart_grids]: Expected {label}, found {found}")
                 self.rst_put_box(s, dlo, ext, restart.read_box(src, s, slo, ext))
+
+    def read_rst_joined(self, sources, Nx):
+        """The same for a handle that takes whole sections only (a Grid cut into slabs inside the library): one section of this
+        Grid = the whole Domain at a time is joined on the host (restart.read_section_boxes) and goes in through put_rst_section."""
+        from . import restart
+        for s, (label, cnt) in enumerate(self.rst_sections()):
+            found = sources[0]["levels"][sources[0].get("entry", 0)][s][0]
+            if found != label:
+                raise restart.RestartError(f"[restart_grids]: Expected {label}, found {found}")
+            a = restart.read_section_boxes(sources, Nx, s).reshape(-1)
+            if a.size != cnt:
+                raise restart.RestartError(f"[restart_grids]: Expected {cnt} doubles of {label}, found {a.size}")
+            self.put_rst_section(s, a)
 
     # ---- measurement -------------------------------------------------------------------
     def profile_enable(self, on: bool = True): self.L.aa_profile_enable(self._h, 1 if on else 0)

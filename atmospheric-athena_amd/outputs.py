@@ -50,9 +50,15 @@ class Output:
 
 class OutputSet:
     def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int,
-                 rst_ngrid=None):
+                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None):
         self.par, self.outs, self.rst = par, outs, rst
         self.rst_ngrid = tuple(int(v) for v in rst_ngrid) if rst_ngrid else None      # restart dumps cut for other Grids
+        # ... of a refined mesh: NGrid of every Domain, level by level (restart.domain_blocks), and the ranks they are dealt to
+        self.rst_mesh_ngrid = [tuple(int(v) for v in g) for g in rst_mesh_ngrid] if rst_mesh_ngrid else None
+        self.rst_mesh_nproc = rst_mesh_nproc
+        if self.rst_mesh_ngrid and rst_mesh_nproc is None:
+            from . import restart
+            self.rst_mesh_nproc = restart.mesh_nproc(self.rst_mesh_ngrid)
         self.rank, self.nranks = rank, nranks
         self.basename = par.gets("job", "problem_id")
         self.dir = os.path.join(rundir, f"id{rank}") if nranks > 1 else rundir
@@ -60,16 +66,37 @@ class OutputSet:
 
     @classmethod
     def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
-                 rst_ngrid=None) -> "OutputSet":
+                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None) -> "OutputSet":
         """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
         r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
         rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
-        file per Grid under ``id<r>/`` (Driver.write_restart; x1 cuts are written and read, never run)."""
+        file per Grid under ``id<r>/`` (Driver.write_restart; x1 cuts are written and read, never run).
+        rst_mesh_ngrid = [(n1, n2, n3) for <domain1>, <domain2>, ...]: the same for a refined mesh on one process (MeshRun, or
+        MeshDriver on one rank): one file per RANK of the reference's MPI run on those cuts, each with the Grids the reference
+        deals to that rank (restart.mesh_grid_boxes).  rst_mesh_nproc: the number of those ranks; by default the smallest that
+        the rules allow (restart.mesh_nproc) -- a larger one leaves ranks without a Grid of the root."""
         if rst_ngrid is not None:
             if nranks > 1:
                 raise ValueError("[init_output]: rst_ngrid takes a one-rank run")
             if len(tuple(rst_ngrid)) != 3 or min(int(v) for v in rst_ngrid) < 1:
                 raise ValueError(f"[init_output]: rst_ngrid = {rst_ngrid!r} (three counts >= 1)")
+        if rst_mesh_ngrid is None and rst_mesh_nproc is not None:
+            raise ValueError("[init_output]: rst_mesh_nproc without rst_mesh_ngrid")
+        if rst_mesh_ngrid is not None:
+            from . import restart
+            if rst_ngrid is not None:
+                raise ValueError("[init_output]: rst_ngrid (a single-level run) and rst_mesh_ngrid (a refined mesh) together")
+            if nranks > 1:
+                raise ValueError("[init_output]: rst_mesh_ngrid takes a one-rank run")
+            if par.geti("domain1", "Nx3") == 1:
+                raise ValueError("[init_output]: rst_mesh_ngrid is not built for a 2-D mesh (Nx3 = 1)")
+            blocks = restart.domain_blocks(par)
+            given = [tuple(g) for g in rst_mesh_ngrid]
+            if len(given) != len(blocks) or any(len(g) != 3 or min(int(v) for v in g) < 1 for g in given):
+                raise ValueError(f"[init_output]: rst_mesh_ngrid = {rst_mesh_ngrid!r} (three counts >= 1 for each of the "
+                                 f"{len(blocks)} <domainN> blocks)")
+            rst_mesh_ngrid = [given[n - 1] for n in blocks]                # level by level, as the reference visits them
+            rst_mesh_nproc = restart.mesh_nproc(rst_mesh_ngrid, rst_mesh_nproc)      # (ValueError: Grids no such rank count divides)
         if nranks > 1 and rank != 0:
             par.blocks["job"]["problem_id"] = "%s-id%d" % (par.gets("job", "problem_id"), rank)
         maxout = par.geti_def("job", "maxout", MAXOUT_DEFAULT)
@@ -102,7 +129,7 @@ class OutputSet:
                 rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
             else:
                 outs.append(o)
-        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid)
+        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc)
 
     def data_output(self, target, flag: int) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt

@@ -26,7 +26,9 @@ writes any, so there is nothing they could be read into.
 
 After that: the files of the other ranks of a run (`rank_path`), and resuming on another
 decomposition (`grid_boxes`, `scan_sources`, `box_pieces`, `read_box`, `read_state_boxes`,
-`regrid_par`).
+`regrid_par`); for a refined mesh the same per Domain (`mesh_grid_boxes`, `scan_mesh_sources`,
+`regrid_mesh_par`): every Domain cut by its own NGrid_x*, the Grids dealt to the ranks in one
+running count.
 
 With this a run of this package can be continued by the reference (``athena -r file.rst``) and
 vice versa, and the parity tests can start from a developed reference state instead of the
@@ -288,7 +290,7 @@ def scan_sources(path0: str, rootNx: Sequence[int], nscal: int, ion: bool, head0
     nd = par.geti("job", "num_domains") if par.exist("job", "num_domains") else 1
     if nd > 1:
         raise RestartError(f"[restart_grids]: <job> num_domains = {nd}: a file of a refined mesh cannot be resumed on other cuts "
-                           "(regrid takes single-level meshes only)")
+                           "(regrid takes single-level meshes only; MeshRun / MeshDriver.from_restart(regrid=True) take it)")
     ngrid = par_ngrid(par)
     boxes = grid_boxes(rootNx, ngrid)
     out = []
@@ -312,18 +314,19 @@ def scan_sources(path0: str, rootNx: Sequence[int], nscal: int, ion: bool, head0
     return out
 
 
-def box_pieces(sources, rootNx: Sequence[int], lo: Sequence[int], n: Sequence[int], edgeflux: bool = False):
-    """The parts of the box [lo, lo + n) -- root Domain indices: zones, or faces for EDGEFLUX -- that every source file holds:
+def box_pieces(sources, Nx: Sequence[int], lo: Sequence[int], n: Sequence[int], edgeflux: bool = False):
+    """The parts of the box [lo, lo + n) -- indices of the Domain of `Nx` zones the sources cut (the root Domain, or one Domain of
+    scan_mesh_sources with its Domain-relative displacements): zones, or faces for EDGEFLUX -- that every source file holds:
     [(source, lo in the source's section, lo in the box, extent)].  Neighbouring Grids share one face index of EDGEFLUX: the
     entry comes from the upper Grid (its index 0; along x1 that is the Grid the flux enters), and the last face of a direction
-    from the last Grid of that direction."""
+    from the last Grid of that direction of the Domain."""
     out = []
     for src in sources:
         slo, dlo, ext = [], [], []
         for d in range(3):
             a = src["disp"][d]
             b = a + src["nx"][d]
-            if edgeflux and b == int(rootNx[d]):
+            if edgeflux and b == int(Nx[d]):
                 b += 1
             x0, x1 = max(a, int(lo[d])), min(b, int(lo[d]) + int(n[d]))
             if x1 <= x0:
@@ -335,9 +338,9 @@ def box_pieces(sources, rootNx: Sequence[int], lo: Sequence[int], n: Sequence[in
 
 
 def read_box(src: Dict, s: int, slo: Sequence[int], ext: Sequence[int]) -> np.ndarray:
-    """[ext3][ext2][ext1] doubles of section `s` of an indexed source file, from `slo` in the section's own index space: only the
-    pages of the rows that meet the box are read."""
-    label, off, cnt = src["levels"][0][s]
+    """[ext3][ext2][ext1] doubles of section `s` of the source's Grid (entry `src["entry"]` of its indexed file, 0 where a file
+    holds one Grid), from `slo` in the section's own index space: only the pages of the rows that meet the box are read."""
+    label, off, cnt = src["levels"][src.get("entry", 0)][s]
     e = 1 if label == "EDGEFLUX" else 0
     nx = src["nx"]
     m = np.memmap(src["path"], dtype="<f8", mode="r", offset=off, shape=(nx[2] + e, nx[1] + e, nx[0] + e))
@@ -346,17 +349,18 @@ def read_box(src: Dict, s: int, slo: Sequence[int], ext: Sequence[int]) -> np.nd
     return a
 
 
-def read_state_boxes(sources, rootNx: Sequence[int], lo: Sequence[int], n: Sequence[int], nscal: int):
-    """(U_active [n3][n2][n1][5 + nscal], edgeflux [n3+1][n2+1][n1+1] or None) of the Grid [lo, lo + n) of the root Domain,
-    joined from the files of `scan_sources`: for engines that keep a host block (load_state)."""
+def read_state_boxes(sources, Nx: Sequence[int], lo: Sequence[int], n: Sequence[int], nscal: int):
+    """(U_active [n3][n2][n1][5 + nscal], edgeflux [n3+1][n2+1][n1+1] or None) of the Grid [lo, lo + n) of the Domain of `Nx`
+    zones, joined from the files of `scan_sources` (the root Domain) or one Domain's list of `scan_mesh_sources`: for engines
+    that keep a host block (load_state)."""
     U = np.zeros((n[2], n[1], n[0], 5 + nscal)); ef = None
-    for s, (label, _off, _cnt) in enumerate(sources[0]["levels"][0]):
+    for s, (label, _off, _cnt) in enumerate(sources[0]["levels"][sources[0].get("entry", 0)]):
         e = label == "EDGEFLUX"
         if e:
             ef = np.zeros((n[2] + 1, n[1] + 1, n[0] + 1)); dst = ef
         else:
             dst = U[..., _LABELS.index(label) if label in _LABELS else 5 + int(label.split()[1])]
-        for src, slo, dlo, ext in box_pieces(sources, rootNx, lo, [v + (1 if e else 0) for v in n], e):
+        for src, slo, dlo, ext in box_pieces(sources, Nx, lo, [v + (1 if e else 0) for v in n], e):
             dst[dlo[2]:dlo[2] + ext[2], dlo[1]:dlo[1] + ext[1], dlo[0]:dlo[0] + ext[0]] = read_box(src, s, slo, ext)
     return U, ef
 
@@ -370,6 +374,112 @@ def regrid_par(par: ParTable, ngrid: Sequence[int], rank: int = 0, basename: Opt
     dom.pop("AutoWithNProc", None)
     for d in range(3):
         dom[f"NGrid_x{d + 1}"] = "%d" % int(ngrid[d])
+    if basename is not None:
+        q.blocks["job"]["problem_id"] = basename + ("-id%d" % rank if rank else "")
+    return q
+
+
+# ---- the same for a refined mesh: every Domain cut by its own NGrid_x*, the Grids dealt to the ranks in one running count --------
+
+def domain_blocks(par: ParTable):
+    """The N of every <domainN> in the order of the reference's loops: level by level, deck order inside a level (config.levels)"""
+    nd = par.geti("job", "num_domains") if par.exist("job", "num_domains") else 1
+    return [n for _lev, n in sorted(((par.geti(f"domain{n}", "level") if par.exist(f"domain{n}", "level") else 0), n)
+                                    for n in range(1, nd + 1))]
+
+
+def par_mesh_ngrid(par: ParTable):
+    """par_ngrid of every <domainN>, in the order of domain_blocks"""
+    return [tuple(par.geti(f"domain{n}", f"NGrid_x{d}") if par.exist(f"domain{n}", f"NGrid_x{d}") else 1 for d in (1, 2, 3))
+            for n in domain_blocks(par)]
+
+
+def mesh_nproc(ngrids, nproc: Optional[int] = None) -> int:
+    """The number of ranks a mesh whose Domains are cut by `ngrids` runs on: `nproc` checked against init_mesh.c:564-567 (no
+    Domain has more Grids than there are ranks) and :661 (the running count ends at 0: the ranks divide the number of Grids), or,
+    without it, the smallest count that passes both.  ValueError otherwise."""
+    cnt = [int(g[0]) * int(g[1]) * int(g[2]) for g in ngrids]
+    if not cnt or min(cnt) < 1:
+        raise ValueError(f"[init_mesh]: NGrid = {list(ngrids)!r} (three counts >= 1 per Domain)")
+    total, most = sum(cnt), max(cnt)
+    if nproc is None:
+        return next(p for p in range(most, total + 1) if total % p == 0)
+    if int(nproc) < most or total % int(nproc):
+        raise ValueError(f"[init_mesh]: {total} Grids, {most} of them in one Domain, cannot be dealt to {nproc} ranks")
+    return int(nproc)
+
+
+def mesh_grid_boxes(domains, nproc: int):
+    """Per Domain the [(rank, disp(3), nx(3))] of its Grids.  domains: [(Nx, NGrid)] level by level, deck order inside a level.
+    Every Domain is cut like the root (grid_boxes: Nx / NGrid zones, the whole remainder on the first Grid of a direction;
+    `disp` is relative to the Domain, the reference adds the Domain's own Disp, init_mesh.c:625-653); the Grids take consecutive
+    world ranks, x1 index fastest, and the count runs on from Domain to Domain, wrapping at `nproc` (:589-590).  It must end at
+    0 (:661), and no Domain may have more Grids than there are ranks (:564-567) -- so a rank holds at most one Grid per Domain,
+    and possibly none of the root."""
+    nproc = int(nproc)
+    out, nxt, total = [], 0, 0
+    for n, (Nx, ngrid) in enumerate(domains):
+        boxes = grid_boxes(Nx, ngrid)
+        if len(boxes) > nproc:
+            raise RestartError(f"[restart_grids]: Expected at least {len(boxes)} files for the NGrid = {ngrid[0]} x {ngrid[1]} x "
+                               f"{ngrid[2]} of Domain {n} (a Domain has no more Grids than there are ranks), found {nproc}")
+        out.append([((nxt + r) % nproc, disp, nx) for r, disp, nx in boxes])
+        nxt = (nxt + len(boxes)) % nproc
+        total += len(boxes)
+    if nxt != 0:
+        raise RestartError(f"[restart_grids]: Expected a number of files that divides the {total} Grids of the mesh, found {nproc}")
+    return out
+
+
+def scan_mesh_sources(path0: str, domains, nscal: int, ion: bool, head0: Optional[Dict] = None):
+    """scan_sources for a refined mesh.  domains: Nx of every Domain (or anything with `.Nx`: config.levels), level by level;
+    their cuts are the file's own ``<domainN> NGrid_x1/2/3``.  The number of ranks is the number of files found through
+    rank_path; every file is indexed for exactly the Grids its rank holds by mesh_grid_boxes, in Domain order (restart.c:531-770)
+    -- a file of another size, of other cuts or of another number of ranks is refused by index_sections.
+    -> per Domain [source]: the file's head with `levels` (the sections of every Grid in the file) and this Grid's `rank`,
+    `disp` (relative to the Domain), `nx`, `ngrid` and `entry`, its place in `levels`."""
+    head0 = head0 or read_head(path0)
+    ngrids = par_mesh_ngrid(head0["par"])
+    Nxs = [tuple(int(v) for v in getattr(d, "Nx", d)) for d in domains]
+    if len(ngrids) != len(Nxs):
+        raise RestartError(f"[restart_grids]: Expected {len(Nxs)} Domains, found <job> num_domains = {len(ngrids)}")
+    paths = [path0]
+    while True:
+        try:
+            paths.append(rank_path(path0, len(paths)))
+        except RestartError:
+            break
+    table = mesh_grid_boxes(list(zip(Nxs, ngrids)), len(paths))
+    out = [[] for _ in Nxs]
+    for rank, p in enumerate(paths):
+        head = head0 if rank == 0 else read_head(p)
+        mine = [(n, b) for n, boxes in enumerate(table) for b in boxes if b[0] == rank]
+        head["levels"] = index_sections(head, [b[2] for _n, b in mine], nscal, ion)
+        for entry, (n, (_r, disp, nx)) in enumerate(mine):
+            out[n].append(dict(head, rank=rank, disp=disp, nx=nx, ngrid=ngrids[n], entry=entry))
+    return out
+
+
+def read_section_boxes(sources, Nx: Sequence[int], s: int) -> np.ndarray:
+    """Section `s` of the whole Domain of `Nx` zones joined on the host from one Domain's sources: what a handle that takes whole
+    sections only (a Grid cut into slabs inside the library) is given."""
+    e = 1 if sources[0]["levels"][sources[0].get("entry", 0)][s][0] == "EDGEFLUX" else 0
+    dims = [int(v) + e for v in Nx]
+    a = np.zeros((dims[2], dims[1], dims[0]))
+    for src, slo, dlo, ext in box_pieces(sources, Nx, (0, 0, 0), dims, bool(e)):
+        a[dlo[2]:dlo[2] + ext[2], dlo[1]:dlo[1] + ext[1], dlo[0]:dlo[0] + ext[0]] = read_box(src, s, slo, ext)
+    return a
+
+
+def regrid_mesh_par(par: ParTable, ngrids, rank: int = 0, basename: Optional[str] = None) -> ParTable:
+    """regrid_par for every <domainN>: `ngrids` in the order of domain_blocks"""
+    import copy
+    q = copy.deepcopy(par)
+    for n, ngrid in zip(domain_blocks(q), ngrids):
+        dom = q.blocks.setdefault(f"domain{n}", {})
+        dom.pop("AutoWithNProc", None)
+        for d in range(3):
+            dom[f"NGrid_x{d + 1}"] = "%d" % int(ngrid[d])
     if basename is not None:
         q.blocks["job"]["problem_id"] = basename + ("-id%d" % rank if rank else "")
     return q
