@@ -866,20 +866,15 @@ int aa_ion_begin(aa_grid *g)
   return 0;
 }
 
-int aa_ion_rates(aa_grid *g, double *dt_chem, double *dt_therm)
+// ionradplane_3d.c:265: the hard-coded time ramp of the incident flux, evaluated once on the host (it is the same for
+// every ray of the root level)
+static Real ion_flux0(const aa_grid *g) { return g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1); }
+
+// ionrad_3d.c:922-938 of the two-kernel sub-cycle, queued: ph_rate_init, the ray sweep, the rates and their reductions
+static int ion_sweep_and_rates(aa_grid *g)
 {
-  if (!g->slab.empty()) return slabs_ion_rates(g, dt_chem, dt_therm);
-  if (g->ion_fused) return fail(-1, "[aa_ion_rates]: this Grid runs the one-kernel sub-cycle (aa_ion_pass / aa_ion_pick / aa_ion_fetch)");
-  {
-    DevScalars init; memset(&init, 0, sizeof init);
-    init.dt_chem = double_to_bits(DBL_MAX); init.dt_therm = double_to_bits(DBL_MAX);
-    *g->sc_host = init;
-    HIPCHK(hipMemcpyAsync(g->sc, g->sc_host, sizeof(DevScalars), hipMemcpyHostToDevice, g->st));
-  }
   if (g->nradplane > 0) {
-    // ionradplane_3d.c:265: the hard-coded time ramp of the incident flux, evaluated once on the
-    // host (it is the same for every ray of the root level)
-    const Real flux0 = g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1);
+    const Real flux0 = ion_flux0(g);
     // :264-271: a refined level starts every ray from the flux its parent left in EdgeFlux[..][..][0]
     if (g->rad_dir == -2) { Scope s(g, "ray_sweep"); launch_ray_sweep_x2(g->d, g->ion, g->flux_i, g->st); }
     else if (g->d.cfg.fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
@@ -888,7 +883,17 @@ int aa_ion_rates(aa_grid *g, double *dt_chem, double *dt_therm)
     HIPCHK(hipMemsetAsync(g->d.ph_rate, 0, (size_t)g->d.nc*sizeof(Real), g->st));
   }
   if (!(g->d.cfg.fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
-  int rc = fetch_scalars(g); if (rc) return rc;
+  return 0;
+}
+
+int aa_ion_rates(aa_grid *g, double *dt_chem, double *dt_therm)
+{
+  int rc;
+  if (!g->slab.empty()) return slabs_ion_rates(g, dt_chem, dt_therm);
+  if (g->ion_fused) return fail(-1, "[aa_ion_rates]: this Grid runs the one-kernel sub-cycle (aa_ion_pass / aa_ion_pick / aa_ion_fetch)");
+  if ((rc = aa_ion_arm(g))) return rc;
+  if ((rc = ion_sweep_and_rates(g))) return rc;
+  if ((rc = fetch_scalars(g))) return rc;
   if (g->sc_host->neg_dt_chem) return fail(-4, "[compute_chem_rates]: negative dt_chem");   // ionrad_3d.c:389-391
   *dt_chem = bits_to_double(g->sc_host->dt_chem);
   *dt_therm = bits_to_double(g->sc_host->dt_therm);
@@ -926,18 +931,11 @@ int aa_ion_subcycle(aa_grid *g, double dt_done, double limit, double *dt, int *l
   g->cfl_ready = false; g->active_dirty = true;
   if (!g->slab.empty()) return fail(-1, "[aa_ion_subcycle]: not available on a Grid cut into slabs (aa_ion_run / aa_ion_rates + aa_ion_update)");
   if (g->ion_fused) return fail(-1, "[aa_ion_subcycle]: this Grid runs the one-kernel sub-cycle");
-  if (g->nradplane > 0) {
-    const Real flux0 = g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1);     // ionradplane_3d.c:265
-    if (g->rad_dir == -2) { Scope s(g, "ray_sweep"); launch_ray_sweep_x2(g->d, g->ion, g->flux_i, g->st); }
-    else if (g->d.cfg.fused_rates) { Scope s(g, "ray_sweep_rates"); launch_ray_sweep_rates(g->d, g->ion, flux0, g->level > 0, g->sc, g->st); }
-    else { Scope s(g, "ray_sweep"); launch_ray_sweep(g->d, g->ion, flux0, g->level > 0, g->st); }
-  } else {
-    HIPCHK(hipMemsetAsync(g->d.ph_rate, 0, (size_t)g->d.nc*sizeof(Real), g->st));
-  }
-  if (!(g->d.cfg.fused_rates && g->nradplane > 0 && g->rad_dir == -1)) { Scope s(g, "ion_rates"); launch_ion_rates(g->d, g->ion, g->sc, g->st); }
+  int rc;
+  if ((rc = ion_sweep_and_rates(g))) return rc;
   launch_ion_pick(g->sc, dt_done, limit, g->st);
   { Scope s(g, "ion_update"); launch_ion_update_sel(g->d, g->ion, g->sc, g->st); }
-  int rc = fetch_scalars(g); if (rc) return rc;
+  if ((rc = fetch_scalars(g))) return rc;
   if (g->sc_host->neg_out) return fail(-4, "[compute_chem_rates]: negative dt_chem");   // ionrad_3d.c:389-391
   *dt = g->sc_host->dt_sel; *limit_hit = g->sc_host->limit_hit;
   *dt_chem = g->sc_host->dt_chem_out; *dt_therm = g->sc_host->dt_therm_out;
@@ -967,10 +965,9 @@ int aa_ion_pass(aa_grid *g, int update, int sweep, double *dev_words)
     if (!g->ion_pending) return fail(-1, "[aa_ion_pass]: update without a preceding sweep");
     g->ion_cur ^= 1; g->ion_pending = false;
   }
-  // ionradplane_3d.c:265: the hard-coded time ramp of the incident flux (the same for every ray of the root
-  // level); :264-271: a refined level starts every ray from the flux its parent left in EdgeFlux[..][..][0];
-  // no radiation plane: flux 0 (every zone's ph_rate stays 0, as after ph_rate_init)
-  const Real flux0 = (g->nradplane > 0) ? g->flux_i*(5.*(erf((g->time - 1.2e5)/8e4)+1)+0.1) : 0.0;
+  // :264-271: a refined level starts every ray from the flux its parent left in EdgeFlux[..][..][0]; no radiation plane:
+  // flux 0 (every zone's ph_rate stays 0, as after ph_rate_init)
+  const Real flux0 = (g->nradplane > 0) ? ion_flux0(g) : 0.0;
   const bool begin = g->ion_begin_due;
   if (begin && update) return fail(-1, "[aa_ion_pass]: the first pass of an ion step cannot apply an update");
   g->ion_begin_due = false;
@@ -1069,11 +1066,19 @@ static int ion_gather(const IonGather &G)
   const int rc = G.fn(G.ctx);
   return rc ? aa_fail(-5, "[ion_radtransfer_3d]: the driver's all-gather of the sub-cycle's words failed (%d)", rc) : 0;
 }
+// what a level's loop leaves behind: :983, :1000, :1009 pGrid->dt = dt_done where the loop says so
+static int ion_ran(aa_grid *g, const IonSubcycles &r, int *niter_out, double *dt_done_out)
+{
+  if (r.rc) return r.rc;
+  if (r.cut) g->dt = r.dt_done;
+  *niter_out = r.niter; *dt_done_out = r.dt_done;
+  return 0;
+}
+
+// the one-kernel sub-cycle: pass / gather / pick / fetch
 static int ion_run_fused(aa_grid *g, bool fine, double limit, int *niter_out, double *dt_done_out, const IonGather &G = IonGather())
 {
-  double dt, dt_chem = 0, dt_therm = 0, dt_hydro = 0, dt_done = 0.0;
-  long long cellcount = 0;
-  int hit, neg, niter = 0, rc;
+  int rc;
   const double *all = G.fn ? G.all : nullptr;
   const int nr = G.fn ? G.nranks : 1;
   // one rank: every pass of this loop is followed by its pick with nothing in between -- fold and pick in one launch
@@ -1084,55 +1089,55 @@ static int ion_run_fused(aa_grid *g, bool fine, double limit, int *niter_out, do
   if ((rc = aa_ion_pass(g, 0, 1, G.fn ? G.words : nullptr))) return rc;      // sweep(0) + rates(0)
   if ((rc = ion_gather(G))) return rc;
   if ((rc = aa_ion_pick(g, all, nr, 1, limit))) return rc;                   // -> dt_0 (stays on the device)
-  for (;;) {
+  const IonSubcycles r = ion_subcycles(fine, [&](double, double *dt, int *hit, long long *cellcount, double *dt_hydro) -> int {
     // update(n) with the step picked on the device, then -- unless that step was cut back to the limit -- sweep(n+1) and
     // rates(n+1), speculatively: whether the loop goes on is only known from this pass's own reductions
+    int rc, neg;
     if ((rc = aa_ion_pass(g, 1, 1, G.fn ? G.words : nullptr))) return rc;
     if ((rc = ion_gather(G))) return rc;
     if ((rc = aa_ion_pick(g, all, nr, 0, limit))) return rc;
-    if ((rc = aa_ion_fetch(g, &dt, &hit, &dt_chem, &dt_therm, &cellcount, &dt_hydro, &neg))) return rc;   // the one read-back
+    if ((rc = aa_ion_fetch(g, dt, hit, nullptr, nullptr, cellcount, dt_hydro, &neg))) return rc;   // the one read-back
     if (neg) return fail(-4, "[compute_chem_rates]: negative dt_chem");      // ionrad_3d.c:389-391 (of the rates behind dt)
-    dt_done += dt;
-    niter++;
-    if (!fine) {
-      if (cellcount > MAXCELLCOUNT) { g->dt = dt_done; break; }
-      if (hit) break;
-      if (dt_hydro < dt_done) { g->dt = dt_done; break; }
-    } else if (hit) { g->dt = dt_done; break; }
-  }
+    return 0;
+  });
+  if (r.rc) return r.rc;
   if ((rc = aa_ion_finish(g))) return rc;
-  *niter_out = niter; *dt_done_out = dt_done;
-  return 0;
+  return ion_ran(g, r, niter_out, dt_done_out);
 }
 
+// the two-kernel sub-cycle, the step picked on the device: ONE read-back per sub-cycle
 static int ion_run_phased(aa_grid *g, bool fine, double limit, int *niter_out, double *dt_done_out)
 {
-  double dt_chem, dt_therm, dt_hydro = 0, dt, dt_done = 0.0;
-  long long cellcount;
-  int niter = 0, rc;
+  int rc;
   if ((rc = aa_ion_begin(g))) return rc;
   if ((rc = aa_ion_arm(g))) return rc;
-  for (;;) {
-    int hit = 0;
-    if ((rc = aa_ion_subcycle(g, dt_done, limit, &dt, &hit, &dt_chem, &dt_therm, &cellcount, &dt_hydro))) return rc;
-    dt_done += dt;
-    niter++;
-    if (!fine) {
-      if (cellcount > MAXCELLCOUNT) { g->dt = dt_done; break; }
-      if (hit) break;
-      if (dt_hydro < dt_done) { g->dt = dt_done; break; }
-    } else if (hit) { g->dt = dt_done; break; }
-  }
-  *niter_out = niter; *dt_done_out = dt_done;
-  return 0;
+  return ion_ran(g, ion_subcycles(fine, [&](double dt_done, double *dt, int *hit, long long *cellcount, double *dt_hydro) -> int {
+    double dt_chem, dt_therm;
+    return aa_ion_subcycle(g, dt_done, limit, dt, hit, &dt_chem, &dt_therm, cellcount, dt_hydro);
+  }), niter_out, dt_done_out);
+}
+
+// the two-kernel sub-cycle on a Grid cut into slabs (short rays): rates and update reduce over the slabs on the host, which
+// picks the step in between -- two read-backs per slab and sub-cycle, as under MPI
+static int ion_run_host_picked(aa_grid *g, bool fine, double limit, int *niter_out, double *dt_done_out)
+{
+  int rc;
+  if ((rc = aa_ion_begin(g))) return rc;
+  return ion_ran(g, ion_subcycles(fine, [&](double dt_done, double *dt, int *hit, long long *cellcount, double *dt_hydro) -> int {
+    double dt_chem, dt_therm;
+    int rc;
+    if ((rc = aa_ion_rates(g, &dt_chem, &dt_therm))) return rc;
+    *dt = ion_pick_step(dt_chem, dt_therm, dt_done, limit, hit);
+    return aa_ion_update(g, *dt, cellcount, dt_hydro);
+  }), niter_out, dt_done_out);
 }
 
 int aa_ion_run(aa_grid *g, int finegrid, double limit, int *niter_out, double *dt_done_out)
 {
   g->cfl_ready = false; g->active_dirty = true;
-  if (!g->slab.empty() && !g->ion_fused) return slabs_ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out);
-  return g->ion_fused ? ion_run_fused(g, finegrid != 0, limit, niter_out, dt_done_out)
-                      : ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out);
+  if (g->ion_fused) return ion_run_fused(g, finegrid != 0, limit, niter_out, dt_done_out);
+  return g->slab.empty() ? ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out)
+                         : ion_run_host_picked(g, finegrid != 0, limit, niter_out, dt_done_out);
 }
 
 int aa_ion_radtransfer_3d(aa_grid *g, int *niter_out)
@@ -1140,8 +1145,7 @@ int aa_ion_radtransfer_3d(aa_grid *g, int *niter_out)
   // ionrad_3d.c:862-1047, root level
   int niter = 0, rc; double dt_done = 0.0;
   if ((rc = aa_ion_run(g, 0, g->dt, &niter, &dt_done))) return rc;
-  if (niter == g->p.maxiter) g->dt = dt_done;
-  if (g->dt < 0) return fail(-4, "[ion_radtransfer_3d]: dt = %e, dt_done = %e", g->dt, dt_done);
+  if ((rc = ion_root_close(g, niter, dt_done, nullptr))) return rc;
   if (niter_out) *niter_out = niter;
   return 0;
 }
@@ -1156,8 +1160,7 @@ int aa_ion_radtransfer_3d_gather(aa_grid *g, double *dev_words, const double *de
   IonGather G; G.words = dev_words; G.all = dev_words_all; G.nranks = nranks; G.fn = gather; G.ctx = ctx;
   int niter = 0, rc; double dt_done = 0.0;
   if ((rc = ion_run_fused(g, false, g->dt, &niter, &dt_done, G))) return rc;
-  if (niter == g->p.maxiter) g->dt = dt_done;
-  if (g->dt < 0) return fail(-4, "[ion_radtransfer_3d]: dt = %e, dt_done = %e", g->dt, dt_done);
+  if ((rc = ion_root_close(g, niter, dt_done, nullptr))) return rc;
   if (niter_out) *niter_out = niter;
   return 0;
 }

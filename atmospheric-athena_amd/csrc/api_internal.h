@@ -6,12 +6,11 @@
 #include <vector>
 #include "../../include/athena_amd.h"
 #include "grid.h"
+#include "ion_subcycle.h"
 
 int aa_fail(int code, const char *fmt, ...);   // records the message aa_last_error() returns
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
   return aa_fail(-2, "[athena_amd] HIP error %s at %s:%d: %s", #x, __FILE__, __LINE__, hipGetErrorString(e_)); } while (0)
-
-#define MAXCELLCOUNT 20   /* ionrad.h:38 */
 
 struct ProfEntry { std::string name; std::vector<hipEvent_t> ev; double total_ms = 0; long long launches = 0; };
 
@@ -161,7 +160,6 @@ int slabs_ion_pass(aa_grid *g, int update, int sweep);
 int slabs_ion_pick(aa_grid *g, int first, double limit);
 int slabs_fetch_scalars(aa_grid *g);
 int slabs_ion_finish(aa_grid *g);
-int slabs_ion_run_phased(aa_grid *g, int fine, double limit, int *niter_out, double *dt_done_out);
 int slabs_history(aa_grid *g, double *sums);
 int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away
@@ -186,11 +184,18 @@ void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevSc
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }
 static inline unsigned long long double_to_bits(double x) { unsigned long long b; memcpy(&b, &x, 8); return b; }
 extern "C" int aa_fetch_scalars(aa_grid *g);     // DevScalars device -> pinned host, synchronous
-// one radiation sub-cycle with the step chosen on the device (api.hip); used by the single-Grid and the
-// Mesh drivers (the multi-rank drivers need the reductions on the host and use aa_ion_rates/_update)
-// ionrad_3d.c:862-1047 for the Grid of one level (api.hip): root (finegrid 0, limit = its dt) or refined level
-// (limit = the time the root covered); *dt_done_out = the time the sub-cycles covered
+// ionrad_3d.c:862-1012 for the Grid of one level (api.hip; the loop itself is ion_subcycle.h): root (finegrid 0, limit = its
+// dt) or refined level (limit = the time the root covered); *dt_done_out = the time the sub-cycles covered
 extern "C" int aa_ion_run(aa_grid *g, int finegrid, double limit, int *niter_out, double *dt_done_out);
+// :1017-1029, :1044 the root level behind that loop (tcoarse: of a Mesh, else NULL)
+static inline int ion_root_close(aa_grid *g, int niter, double dt_done, double *tcoarse)
+{
+  if (ion_close_root(niter, g->p.maxiter, dt_done, &g->dt, tcoarse))
+    return aa_fail(-4, "[ion_radtransfer_3d]: dt = %e, dt_done = %e", g->dt, dt_done);
+  return 0;
+}
+// one radiation sub-cycle with the step chosen on the device (api.hip); the multi-rank drivers need the reductions on the
+// host and use aa_ion_rates / aa_ion_update
 extern "C" int aa_ion_arm(aa_grid *g);
 extern "C" int aa_ion_subcycle(aa_grid *g, double dt_done, double limit, double *dt, int *limit_hit, double *dt_chem,
                                double *dt_therm, long long *cellcount, double *dt_hydro);

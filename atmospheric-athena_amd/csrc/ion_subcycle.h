@@ -1,0 +1,65 @@
+/* ion_subcycle.h -- the control flow of the radiation sub-cycle loop, ionrad_3d.c:919-1047 (plain host C++, no device).
+ *
+ * The loop is the only data-dependent control flow of the time step: it decides how many sub-cycles run, whether the root's step
+ * is cut back to the time they covered, and what time the refined levels have to cover.  However a sub-cycle is issued -- one
+ * kernel or two, the step picked on the device or on the host, one Grid or a Grid cut into slabs -- the stop rules, their order
+ * and the bookkeeping are the ones written here, once:
+ *   ion_pick_step   :941-962   the step of a sub-cycle, cut back to what is left of the limit
+ *   ion_subcycles   :919-1012  the loop around a callable that performs one sub-cycle
+ *   ion_close_root  :1017-1029 and :1044, what the root level does behind its loop
+ * (driver.py holds the same three for the Python drivers; tests/test_ion_subcycles.py runs one table of cases through both.)
+ */
+#ifndef AA_ION_SUBCYCLE_H
+#define AA_ION_SUBCYCLE_H
+#include "../../include/athena_amd.h"      /* AA_MAXCELLCOUNT, ionrad.h:38: check_range (:982) ends the root's loop above that many cells */
+
+/* :945 dt = MIN(dt_therm, dt_chem); :950-962 cut back so that dt_done + dt does not pass `limit` (root: the hydro step pGrid->dt;
+ * refined level: tcoarse); *hit = hydro_done / coarsetime_done */
+static inline double ion_pick_step(double dt_chem, double dt_therm, double dt_done, double limit, int *hit)
+{
+  double dt = (dt_therm < dt_chem) ? dt_therm : dt_chem;
+  *hit = 0;
+  if (dt_done + dt > limit) { dt = limit - dt_done; *hit = 1; }
+  return dt;
+}
+
+struct IonSubcycles {
+  int rc;            /* what the callable returned when it failed (the loop ended there), else 0 */
+  int niter;         /* sub-cycles done */
+  double dt_done;    /* the time they covered */
+  bool cut;          /* the level's step becomes dt_done (:983, :1000, :1009) */
+};
+
+/* one(dt_done, &dt, &hit, &cellcount, &dt_hydro) -> rc performs one sub-cycle that starts at dt_done: the step it applied, whether
+ * that step was cut back to the limit, and the operands of the root's stop tests behind the update (a refined level ignores them).
+ * As in the reference nothing caps the count: maxiter is looked at behind the loop only (ion_close_root). */
+template <class One>
+static inline IonSubcycles ion_subcycles(bool fine, One &&one)
+{
+  IonSubcycles r = {0, 0, 0.0, false};
+  for (;;) {
+    double dt = 0.0, dt_hydro = 0.0;
+    long long cellcount = 0;
+    int hit = 0;
+    if ((r.rc = one(r.dt_done, &dt, &hit, &cellcount, &dt_hydro))) break;
+    r.dt_done += dt;                                                      /* :966-967 */
+    r.niter++;
+    if (!fine) {
+      if (cellcount > AA_MAXCELLCOUNT) { r.cut = true; break; }           /* :982-986 check_range */
+      if (hit) break;                                                     /* :989-992 the whole hydro step is covered */
+      if (dt_hydro < r.dt_done) { r.cut = true; break; }                  /* :997-1002 */
+    } else if (hit) { r.cut = true; break; }                              /* :1008-1012 tcoarse is covered */
+  }
+  return r;
+}
+
+/* The root level behind its loop: :1022-1025 niter == maxiter sets the step to what was done; :1028 tcoarse = dt_done (a Mesh;
+ * NULL without refinement); :1044 the sanity check -- nonzero if the step is negative. */
+static inline int ion_close_root(int niter, int maxiter, double dt_done, double *dt, double *tcoarse)
+{
+  if (niter == maxiter) *dt = dt_done;
+  if (tcoarse) *tcoarse = dt_done;
+  return (*dt < 0) ? -1 : 0;
+}
+
+#endif

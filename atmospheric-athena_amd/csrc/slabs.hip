@@ -628,6 +628,17 @@ int slabs_ion_pass(aa_grid *g, int update, int sweep)
   return 0;
 }
 
+// slab c picks the step from the gathered words its stream has just been given (k_ion_pick2); the first pick of an ion step
+// settles what aa_ion_speculate armed
+static int slab_pick(aa_grid *c, const Real *dwords_all, int n, int first, double limit)
+{
+  if (first && c->ion_spec_armed && limit != c->ion_spec_limit)
+    return aa_fail(-1, "[aa_ion_pick]: limit %.17g, but aa_ion_speculate was told %.17g", limit, c->ion_spec_limit);
+  launch_ion_pick2(dwords_all, n, c->sc, first, limit, c->st, first ? (c->ion_spec_armed ? 1 : 0) : 0);
+  if (!first) c->ion_spec_armed = false;
+  return 0;
+}
+
 // ionrad_3d.c:275,399,554,672 (the MPI_Allreduce calls) without the host: slab 0 pulls every slab's words (after ALL of
 // them are complete: by then every slab has also finished reading the previous set out of slab 0), every slab pulls the
 // gathered set back and picks the step itself.  The next pass of slab s is queued behind its own pick, i.e. behind the
@@ -644,12 +655,9 @@ int slabs_ion_pick(aa_grid *g, int first, double limit)
     for (int s = 0; s < L->n; s++) {
       SLAB_DEV(L, s);
       aa_grid *c = g->slab[s];
-      if (first && c->ion_spec_armed && limit != c->ion_spec_limit)
-        return aa_fail(-1, "[aa_ion_pick]: limit %.17g, but aa_ion_speculate was told %.17g", limit, c->ion_spec_limit);
       for (int t = 0; t < L->n; t++) if (t != s) HIPCHK(hipStreamWaitEvent(c->st, L->wdone[t], 0));
       HIPCHK(hipMemcpyAsync(L->dwords_all[s], hw, (size_t)L->n*wb, hipMemcpyHostToDevice, c->st));
-      launch_ion_pick2(L->dwords_all[s], L->n, c->sc, first, limit, c->st, first ? (c->ion_spec_armed ? 1 : 0) : 0);
-      if (!first) c->ion_spec_armed = false;
+      int rc = slab_pick(c, L->dwords_all[s], L->n, first, limit); if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -667,15 +675,12 @@ int slabs_ion_pick(aa_grid *g, int first, double limit)
   for (int s = 0; s < L->n; s++) {
     SLAB_DEV(L, s);
     aa_grid *c = g->slab[s];
-    if (first && c->ion_spec_armed && limit != c->ion_spec_limit)
-      return aa_fail(-1, "[aa_ion_pick]: limit %.17g, but aa_ion_speculate was told %.17g", limit, c->ion_spec_limit);
     if (s > 0) {
       HIPCHK(hipStreamWaitEvent(c->st, L->gathered, 0));
       if (L->dev[s] == L->dev[0]) HIPCHK(hipMemcpyAsync(L->dwords_all[s], L->dwords_all[0], (size_t)L->n*wb, hipMemcpyDeviceToDevice, c->st));
       else HIPCHK(hipMemcpyPeerAsync(L->dwords_all[s], L->dev[s], L->dwords_all[0], L->dev[0], (size_t)L->n*wb, c->st));
     }
-    launch_ion_pick2(L->dwords_all[s], L->n, c->sc, first, limit, c->st, first ? (c->ion_spec_armed ? 1 : 0) : 0);
-    if (!first) c->ion_spec_armed = false;
+    int rc = slab_pick(c, L->dwords_all[s], L->n, first, limit); if (rc) return rc;
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -727,28 +732,6 @@ int slabs_ion_update(aa_grid *g, double dt, long long *cellcount, double *dt_hyd
   }
   if (cellcount) *cellcount = n;
   if (dt_hydro) *dt_hydro = h;
-  return 0;
-}
-int slabs_ion_run_phased(aa_grid *g, int fine, double limit, int *niter_out, double *dt_done_out)
-{
-  // ionrad_3d.c:862-1012: the root level, or (fine) a refined level of a cut Mesh, which sub-cycles until it has covered `limit`
-  double dt_chem, dt_therm, dt_hydro = 0, dt, dt_done = 0.0;
-  long long cellcount = 0;
-  int niter = 0, hydro_done = 0, rc;
-  if ((rc = slabs_ion_begin(g))) return rc;
-  while (!hydro_done) {
-    if ((rc = slabs_ion_rates(g, &dt_chem, &dt_therm))) return rc;
-    dt = (dt_therm < dt_chem) ? dt_therm : dt_chem;
-    if (dt_done + dt > limit) { dt = limit - dt_done; hydro_done = 1; }
-    if ((rc = slabs_ion_update(g, dt, &cellcount, &dt_hydro))) return rc;
-    dt_done += dt;
-    niter++;
-    if (fine) { if (hydro_done) { g->dt = dt_done; break; } continue; }
-    if (cellcount > MAXCELLCOUNT) { g->dt = dt_done; break; }
-    if (hydro_done) break;
-    if (dt_hydro < dt_done) { g->dt = dt_done; break; }
-  }
-  *niter_out = niter; *dt_done_out = dt_done;
   return 0;
 }
 

@@ -903,10 +903,7 @@ int aa_mesh_ion_radtransfer(aa_mesh *m, int l, int *niter_out)
   if (finegrid) { if ((rc = aa_mesh_ionflux_prolong(m, l))) return rc; }
   else m->tcoarse = 0;
   if ((rc = aa_ion_run(g, finegrid ? 1 : 0, finegrid ? m->tcoarse : g->dt, &niter, &dt_done))) return rc;
-  if (!finegrid) {
-    if (niter == g->p.maxiter) g->dt = dt_done;
-    m->tcoarse = dt_done;
-  }
+  if (!finegrid && (rc = ion_root_close(g, niter, dt_done, &m->tcoarse))) return rc;
   m->dt = g->dt;                             // :1030 pMesh->dt = pGrid->dt
   if (niter_out) *niter_out = niter;
   return 0;

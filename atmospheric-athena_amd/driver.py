@@ -161,6 +161,54 @@ def _fires(out, level: int, domain: int = 0) -> bool:
     return out.level in (-1, level) and out.domain in (-1, domain)
 
 
+def pick_step(dt_chem, dt_therm, dt_done, limit):
+    """ionrad_3d.c:941-962: MIN(dt_therm, dt_chem), cut back so that dt_done + dt does not pass `limit` (root: the hydro step;
+    refined level: tcoarse) -> (dt, whether it was cut back: hydro_done / coarsetime_done)"""
+    dt = dt_therm if dt_therm < dt_chem else dt_chem
+    if dt_done + dt > limit:
+        return limit - dt_done, True
+    return dt, False
+
+
+def subcycles(one, fine):
+    """The radiation sub-cycle loop ionrad_3d.c:919-1012, however a sub-cycle is issued: one(dt_done) performs the sub-cycle that
+    starts at dt_done (with its collectives) and returns (the step it applied, whether that step was cut back to the limit, cells
+    out of range, dt_hydro).  The root ends on check_range, on the covered step, on dt_hydro -- in this order; a refined level
+    only when tcoarse is covered.  Nothing caps the count (maxiter: close_root).  -> (niter, dt_done, whether the level's dt
+    becomes dt_done).  csrc/ion_subcycle.h is the same loop for the library; tests/test_ion_subcycles.py scripts both."""
+    dt_done, niter = 0.0, 0
+    while True:
+        dt, hit, cellcount, dt_hydro = one(dt_done)
+        dt_done += dt                                   # :966-967
+        niter += 1
+        if fine:
+            if hit:                                     # :1008-1012
+                return niter, dt_done, True
+        elif cellcount > MAXCELLCOUNT:                  # :982-986 check_range
+            return niter, dt_done, True
+        elif hit:                                       # :989-992
+            return niter, dt_done, False
+        elif dt_hydro < dt_done:                        # :997-1002
+            return niter, dt_done, True
+
+
+def close_root(niter, maxiter, dt, dt_done):
+    """The root level behind its loop, ionrad_3d.c:1017-1029 and :1044 -> (the root's dt, tcoarse)"""
+    if niter == maxiter:
+        dt = dt_done
+    if dt < 0:
+        raise RuntimeError(f"[ion_radtransfer_3d]: dt = {dt}")
+    return dt, dt_done
+
+
+def _fetched(fetch):
+    """the read-back of a one-kernel sub-cycle (aa_ion_fetch) as subcycles() takes it"""
+    dt, hit, _dt_chem, _dt_therm, cellcount, dt_hydro, neg = fetch
+    if neg:
+        raise RuntimeError("[compute_chem_rates]: negative dt_chem")           # ionrad_3d.c:389-391
+    return dt, hit, cellcount, dt_hydro
+
+
 class _Runner:
     """What Driver, MeshRun and MeshDriver share: the scalar collectives, continuing from a restart dump, and the output side that
     outputs.OutputSet drives.  A runner has `run`, `time`, `dt`, `nstep`, `restarted`, `par` and the HistoryWriters `_hst`."""
@@ -561,33 +609,21 @@ class Driver(_Runner):
             niter = e.ion_radtransfer_gather(dist)
             self.dt = e.mesh_state()[1]
             return niter
-        dt_done, niter = 0.0, 0
+        limit = self.dt
         e.ion_begin()
         if hasattr(e, "ion_speculate"):
-            e.ion_speculate(self.dt)        # the first pass may already apply the first update with the whole step
+            e.ion_speculate(limit)          # the first pass may already apply the first update with the whole step
         e.ion_pass(False, True)
-        e.ion_pick(dist, True, self.dt)
-        while True:
+        e.ion_pick(dist, True, limit)
+
+        def one(dt_done):
             e.ion_pass(True, True)          # the pass skips its sweep by itself once the step was cut back to the limit
-            e.ion_pick(dist, False, self.dt)
-            dt, hit, dt_chem, dt_therm, cellcount, dt_hydro, neg = e.ion_fetch()       # the one read-back
-            if neg:
-                raise RuntimeError("[compute_chem_rates]: negative dt_chem")           # ionrad_3d.c:389-391
-            dt_done += dt
-            niter += 1
-            if cellcount > MAXCELLCOUNT:
-                self.dt = dt_done
-                break
-            if hit:
-                break
-            if dt_hydro < dt_done:
-                self.dt = dt_done
-                break
+            e.ion_pick(dist, False, limit)
+            return _fetched(e.ion_fetch())  # the one read-back
+
+        niter, dt_done, cut = subcycles(one, False)
         e.ion_finish()
-        if niter == self.run.maxiter:
-            self.dt = dt_done
-        if self.dt < 0:
-            raise RuntimeError(f"[ion_radtransfer_3d]: dt = {self.dt}")
+        self.dt, _ = close_root(niter, self.run.maxiter, dt_done if cut else limit, dt_done)
         e.set_mesh_state(self.time, self.dt, self.nstep)
         return niter
 
@@ -595,16 +631,14 @@ class Driver(_Runner):
         e = self.eng
         if getattr(e, "ion_fused", False):
             return self._ion_radtransfer_fused()
-        dt_done, niter, hydro_done = 0.0, 0, False
+        limit = self.dt
         e.ion_begin()
-        while not hydro_done:
+
+        def one(dt_done):
             dt_chem, dt_therm = e.ion_rates()
             if self.distributed:
                 dt_chem, dt_therm = self._allreduce((dt_chem, dt_therm), self.dist.ReduceOp.MIN)
-            dt = min(dt_therm, dt_chem)
-            if dt_done + dt > self.dt:
-                dt = self.dt - dt_done
-                hydro_done = True
+            dt, hit = pick_step(dt_chem, dt_therm, dt_done, limit)
             cellcount, dt_hydro = e.ion_update(dt)
             if self.distributed:
                 # one round: SUM of the count and MIN of dt_hydro (as MAX of its negative)
@@ -614,20 +648,10 @@ class Driver(_Runner):
                 w2 = self.dist.all_reduce(h, op=self.dist.ReduceOp.MIN, async_op=True)
                 w1.wait(); w2.wait()
                 cellcount, dt_hydro = int(t[0].item()), float(h[0].item())
-            dt_done += dt
-            niter += 1
-            if cellcount > MAXCELLCOUNT:
-                self.dt = dt_done
-                break
-            if hydro_done:
-                break
-            if dt_hydro < dt_done:
-                self.dt = dt_done
-                break
-        if niter == self.run.maxiter:
-            self.dt = dt_done
-        if self.dt < 0:
-            raise RuntimeError(f"[ion_radtransfer_3d]: dt = {self.dt}")
+            return dt, hit, cellcount, dt_hydro
+
+        niter, dt_done, cut = subcycles(one, False)
+        self.dt, _ = close_root(niter, self.run.maxiter, dt_done if cut else limit, dt_done)
         e.set_mesh_state(self.time, self.dt, self.nstep)
         return niter
 
@@ -1188,39 +1212,25 @@ class MeshDriver(_Runner):
                 mir["dt_done"] = mir["dt_done"] + mir["dt_sel"]
             else:
                 mir["dt_done"] = 0.0
-            dt = dt_therm if dt_therm < dt_chem else dt_chem
-            hit = False
-            if mir["dt_done"] + dt > limit:
-                dt = limit - mir["dt_done"]; hit = True
-            mir["dt_sel"], mir["hit"], mir["neg"] = dt, hit, neg
+            mir["dt_sel"], mir["hit"] = pick_step(dt_chem, dt_therm, mir["dt_done"], limit)
+            mir["neg"] = neg
             return out
 
         one_pass(False, True)
-        dt_done, niter = 0.0, 0
-        while True:
-            dt, hit, dt_chem, dt_therm, cellcount, dt_hydro, neg = one_pass(True, False)
-            if neg:
-                raise RuntimeError("[compute_chem_rates]: negative dt_chem")
-            dt_done += dt
-            niter += 1
-            if not fine:
-                if cellcount > MAXCELLCOUNT:
-                    self.dtl[0] = dt_done; break
-                if hit:
-                    break
-                if dt_hydro < dt_done:
-                    self.dtl[0] = dt_done; break
-            elif hit:
-                self.dtl[l] = dt_done; break
+        niter, dt_done, cut = subcycles(lambda dt_done: _fetched(one_pass(True, False)), fine)
         if has:
             e.ion_finish(l)
-        if not fine:
-            if niter == self.run.maxiter:
-                self.dtl[0] = dt_done
-            self.tcoarse = dt_done
-        self.dt = self.dtl[l]                                   # ionrad_3d.c:1030 pMesh->dt = pGrid->dt
-        if has:
-            e.set_level_state(l, self.time, self.dtl[l], self.nstep)
+        return self._ion_close(l, niter, dt_done, cut)
+
+    def _ion_close(self, l: int, niter: int, dt_done: float, cut: bool) -> int:
+        """what level l's sub-cycle loop leaves behind: its step, the root's closing (ionrad_3d.c:1017-1029, :1044), :1033"""
+        if cut:
+            self.dtl[l] = dt_done
+        if l == 0:
+            self.dtl[0], self.tcoarse = close_root(niter, self.run.maxiter, self.dtl[0], dt_done)
+        self.dt = self.dtl[l]                                   # ionrad_3d.c:1033 pMesh->dt = pGrid->dt
+        if self.has(l):
+            self.eng.set_level_state(l, self.time, self.dtl[l], self.nstep)
         return niter
 
     def ion_radtransfer(self, l: int) -> int:
@@ -1236,44 +1246,25 @@ class MeshDriver(_Runner):
                 e.ionflux_prolong(l)
         else:
             self.tcoarse = 0.0
+        limit = self.tcoarse if fine else self.dtl[0]
         if has:
             e.set_level_state(l, self.time, self.dtl[l], self.nstep)
             e.ion_begin(l)
-        dt_done, niter, hydro_done, coarse_done = 0.0, 0, False, False
-        while fine or not hydro_done:
+
+        def one(dt_done):
             dt_chem, dt_therm = e.ion_rates(l) if has else (INF, INF)
             if self.distributed:
                 dt_chem, dt_therm = self._allreduce((dt_chem, dt_therm), self.dist.ReduceOp.MIN)
-            dt = min(dt_therm, dt_chem)
-            if not fine:
-                if dt_done + dt > self.dtl[0]:
-                    dt = self.dtl[0] - dt_done; hydro_done = True
-            elif dt_done + dt > self.tcoarse:
-                dt = self.tcoarse - dt_done; coarse_done = True
+            dt, hit = pick_step(dt_chem, dt_therm, dt_done, limit)
             cellcount, dt_hydro = e.ion_update(l, dt) if has else (0, INF)
             if self.distributed and not fine:
                 t = self._allreduce((float(cellcount),), self.dist.ReduceOp.SUM)
                 h = self._allreduce((dt_hydro,), self.dist.ReduceOp.MIN)
                 cellcount, dt_hydro = int(t[0]), h[0]
-            dt_done += dt
-            niter += 1
-            if not fine:
-                if cellcount > MAXCELLCOUNT:
-                    self.dtl[0] = dt_done; break
-                if hydro_done:
-                    break
-                if dt_hydro < dt_done:
-                    self.dtl[0] = dt_done; break
-            elif coarse_done:
-                self.dtl[l] = dt_done; break
-        if not fine:
-            if niter == self.run.maxiter:
-                self.dtl[0] = dt_done
-            self.tcoarse = dt_done
-        self.dt = self.dtl[l]                                   # ionrad_3d.c:1030 pMesh->dt = pGrid->dt
-        if has:
-            e.set_level_state(l, self.time, self.dtl[l], self.nstep)
-        return niter
+            return dt, hit, cellcount, dt_hydro
+
+        niter, dt_done, cut = subcycles(one, fine)
+        return self._ion_close(l, niter, dt_done, cut)
 
     # ---- main.c ----------------------------------------------------------------------------------------
     def start(self):

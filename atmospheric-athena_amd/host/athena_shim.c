@@ -716,6 +716,44 @@ void ionradRestrictCorrect(MeshS *pM)                  /* main.c:561 */
 void ion_radtransfer_init_domain(MeshS *pM) { (void)pM; }
 
 #if AA_ION_RADPLANE
+#ifdef AA_MPI
+/* The sub-cycle loop ionrad_3d.c:919-1029, :1044 of a rank of an MPI run, around aa_ion_rates / aa_ion_update with the reference's own
+ * reductions in the Domain's communicator, made when the reference makes them: MIN of dt_chem / dt_therm behind the rates (:399,
+ * :554) on every level; on the root SUM of the cells out of range behind the update (check_range, :275) and -- only if the loop goes
+ * on -- MIN of dt_hydro (:672).  `limit`: the root's step, or tcoarse on a refined level, which sub-cycles until it has covered it.
+ * Returns the level's step; the root also leaves the time it covered in *tcoarse (NULL without refinement).  (This file is C: the
+ * library's own loop, csrc/ion_subcycle.h, is not for it.  Every rank decides from reduced values, so all ranks agree.) */
+static double ion_subcycles_mpi(aa_grid *g, MPI_Comm comm, int fine, double limit, double *tcoarse, int *niter_out)
+{
+  double dt_done = 0.0, hdt = limit; int niter = 0, stop = 0;
+  CHK(aa_ion_begin(g));
+  while (fine || !stop) {
+    double a[2], b[2], dts, dth, dth_all; long long cnt; long cl, cl_all;
+    CHK(aa_ion_rates(g, &a[0], &a[1]));
+    MPI_Allreduce(a, b, 2, MPI_DOUBLE, MPI_MIN, comm);
+    dts = (b[1] < b[0]) ? b[1] : b[0];
+    if (dt_done + dts > limit) { dts = limit - dt_done; stop = 1; }
+    CHK(aa_ion_update(g, dts, &cnt, &dth));
+    dt_done += dts; niter++;
+    if (!fine) {
+      cl = (long)cnt;
+      MPI_Allreduce(&cl, &cl_all, 1, MPI_LONG, MPI_SUM, comm);
+      if (cl_all > AA_MAXCELLCOUNT) { hdt = dt_done; break; }
+      if (stop) break;
+      MPI_Allreduce(&dth, &dth_all, 1, MPI_DOUBLE, MPI_MIN, comm);
+      if (dth_all < dt_done) { hdt = dt_done; break; }
+    } else if (stop) { hdt = dt_done; break; }
+  }
+  if (!fine) {
+    if (niter == (int)par_getd("ionradiation", "maxiter")) hdt = dt_done;
+    if (tcoarse) *tcoarse = dt_done;
+    if (hdt < 0) ath_error("[ion_radtransfer_3d]: dt = %e, dt_done = %e\n", hdt, dt_done);
+  }
+  *niter_out = niter;
+  return hdt;
+}
+#endif
+
 static void ion_radtransfer_3d_amd(DomainS *pD)
 {
   GridS *pG = pD->Grid; MeshS *pM = pD->Mesh; int niter = 0; double t, dt; int n; const int l = GI(pD);
@@ -723,39 +761,14 @@ static void ion_radtransfer_3d_amd(DomainS *pD)
   active_same[l] = 0;
 #ifdef AA_MPISMR
   {
-    /* ionrad_3d.c:862-1047 on the Grid this rank holds of level pD->Level, with the reference's own reductions in the Domain's
-     * communicator: MIN of dt_chem / dt_therm behind the rates (:399, :554) on every level; on the root also SUM of the cells out
-     * of range and MIN of dt_hydro behind the update (:275, :672).  A refined level takes its incoming flux from this rank's own
-     * parent Grid (ionrad_smr.c:34, :345: the rays run along x1, which is never cut) and sub-cycles to the time the root covered. */
+    /* ionrad_3d.c:862-1047 on the Grid this rank holds of level pD->Level.  A refined level takes its incoming flux from this rank's
+     * own parent Grid (ionrad_smr.c:34, :345: the rays run along x1, which is never cut) and sub-cycles to the time the root covered. */
     const int fine = (pD->Level != 0);
-    double dt_done = 0.0, hdt = pG->dt; int stop = 0;
+    double hdt;
     if (!HAVE(l)) return;
     if (fine) CHK(aa_mesh_ionflux_prolong(MM, LI[l])); else tcoarse_ = 0.0;
     CHK(aa_set_mesh_state(G[l], pM->time, pG->dt, pM->nstep));
-    CHK(aa_ion_begin(G[l]));
-    while (fine || !stop) {
-      double a[2], b[2], dts, dth, dth_all; long long cnt; long cl, cl_all;
-      CHK(aa_ion_rates(G[l], &a[0], &a[1]));
-      MPI_Allreduce(a, b, 2, MPI_DOUBLE, MPI_MIN, comm_lev[l]);
-      dts = (b[1] < b[0]) ? b[1] : b[0];
-      if (!fine) { if (dt_done + dts > hdt) { dts = hdt - dt_done; stop = 1; } }
-      else if (dt_done + dts > tcoarse_) { dts = tcoarse_ - dt_done; stop = 1; }
-      CHK(aa_ion_update(G[l], dts, &cnt, &dth));
-      dt_done += dts; niter++;
-      if (!fine) {
-        cl = (long)cnt;
-        MPI_Allreduce(&cl, &cl_all, 1, MPI_LONG, MPI_SUM, comm_lev[l]);
-        if (cl_all > 20) { hdt = dt_done; break; }                 /* MAXCELLCOUNT, ionrad.h:38 */
-        if (stop) break;
-        MPI_Allreduce(&dth, &dth_all, 1, MPI_DOUBLE, MPI_MIN, comm_lev[l]);
-        if (dth_all < dt_done) { hdt = dt_done; break; }
-      } else if (stop) { hdt = dt_done; break; }
-    }
-    if (!fine) {
-      if (niter == (int)par_getd("ionradiation", "maxiter")) hdt = dt_done;
-      tcoarse_ = dt_done;
-      if (hdt < 0) ath_error("[ion_radtransfer_3d]: dt = %e, dt_done = %e\n", hdt, dt_done);
-    }
+    hdt = ion_subcycles_mpi(G[l], comm_lev[l], fine, fine ? tcoarse_ : pG->dt, &tcoarse_, &niter);
     CHK(aa_set_mesh_state(G[l], pM->time, hdt, pM->nstep));
   }
 #elif defined(AA_SMR)
@@ -763,27 +776,7 @@ static void ion_radtransfer_3d_amd(DomainS *pD)
   CHK(aa_mesh_ion_radtransfer(MM, l, &niter));
 #elif defined(AA_MPI)
   if (nranks_dom > 1) {
-    /* ionrad_3d.c:862-1047 with the reference's own reductions: MIN of dt_chem / dt_therm behind the rates (:275, :399),
-     * SUM of the cells out of range and MIN of dt_hydro behind the update (:554, :672); MAXCELLCOUNT ionrad.h:38 */
-    double dt_done = 0.0, hdt = pG->dt; int hydro_done = 0;
-    CHK(aa_ion_begin(G[l]));
-    while (!hydro_done) {
-      double a[2], b[2], dts, dth, dth_all; long long cnt; long cl, cl_all;
-      CHK(aa_ion_rates(G[l], &a[0], &a[1]));
-      MPI_Allreduce(a, b, 2, MPI_DOUBLE, MPI_MIN, comm_dom);
-      dts = (b[1] < b[0]) ? b[1] : b[0];
-      if (dt_done + dts > hdt) { dts = hdt - dt_done; hydro_done = 1; }
-      CHK(aa_ion_update(G[l], dts, &cnt, &dth));
-      cl = (long)cnt;
-      MPI_Allreduce(&cl, &cl_all, 1, MPI_LONG, MPI_SUM, comm_dom);
-      MPI_Allreduce(&dth, &dth_all, 1, MPI_DOUBLE, MPI_MIN, comm_dom);
-      dt_done += dts; niter++;
-      if (cl_all > 20) { hdt = dt_done; break; }
-      if (hydro_done) break;
-      if (dth_all < dt_done) { hdt = dt_done; break; }
-    }
-    if (niter == (int)par_getd("ionradiation", "maxiter")) hdt = dt_done;
-    if (hdt < 0) ath_error("[ion_radtransfer_3d]: dt = %e, dt_done = %e\n", hdt, dt_done);
+    const double hdt = ion_subcycles_mpi(G[l], comm_dom, 0, pG->dt, NULL, &niter);
     CHK(aa_set_mesh_state(G[l], pM->time, hdt, pM->nstep));
   } else CHK(aa_ion_radtransfer_3d(G[l], &niter));
 #else

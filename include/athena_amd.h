@@ -164,6 +164,9 @@ int aa_integrate_begin(aa_grid *g);      /* (aa_upload_cons, aa_download_cons an
  * registers and new_dt reads it instead of sweeping the Grid again.  aa_step does this by itself.                     */
 int aa_cfl_in_update(aa_grid *g, int on);
 int aa_new_dt_local(aa_grid *g, double *dt_cfl);                /* new_dt.c:72-170 before Allreduce */
+/* ionrad.h:38 MAXCELLCOUNT: the root's sub-cycle loop ends (check_range, ionrad_3d.c:982) when more cells than this, summed
+ * over all ranks, have left their allowed range -- for a driver that runs the loop itself around aa_ion_rates / aa_ion_update */
+#define AA_MAXCELLCOUNT 20
 int aa_ion_begin(aa_grid *g);                                   /* ionrad_3d.c:896-905            */
 int aa_ion_rates(aa_grid *g, double *dt_chem, double *dt_therm);/* :922-938 before Allreduce      */
 int aa_ion_update(aa_grid *g, double dt, long long *cellcount, double *dt_hydro); /* :965-1002    */
