@@ -1342,6 +1342,56 @@ int aa_test_explog(int n, const double *x, double *ye, double *yl)
   return 0;
 }
 
+// the folds and step picks of the radiation sub-cycle (k_ion_reduce, k_ion_reduce_pick, k_ion_pick2 of ion_pass.hip; k_ion_pick of
+// ion_kernels.hip) over n records and the scalars of a previous call: see include/athena_amd.h for the layout of a row
+static void pick_row_to_scalars(const double *v, DevScalars *s)
+{
+  memset(s, 0, sizeof *s);
+  if (!v) return;
+  s->dt_sel = v[0]; s->limit_hit = (int)v[1]; s->dt_done = v[2]; s->dt_applied = v[3]; s->hit_applied = (int)v[4]; s->neg_applied = (int)v[5];
+  s->spec_state = (int)v[6]; s->dt_chem_out = v[7]; s->dt_therm_out = v[8]; s->neg_out = (int)v[9];
+  s->max_dti = double_to_bits(v[10]); s->cellcount = (unsigned long long)v[11];
+  s->dt_chem = double_to_bits(v[12]); s->dt_therm = double_to_bits(v[13]); s->neg_dt_chem = (int)v[14];
+}
+static void pick_scalars_to_row(const DevScalars &s, double *v)
+{
+  v[0] = s.dt_sel; v[1] = s.limit_hit; v[2] = s.dt_done; v[3] = s.dt_applied; v[4] = s.hit_applied; v[5] = s.neg_applied;
+  v[6] = s.spec_state; v[7] = s.dt_chem_out; v[8] = s.dt_therm_out; v[9] = s.neg_out;
+  v[10] = bits_to_double(s.max_dti); v[11] = (double)s.cellcount;
+  v[12] = bits_to_double(s.dt_chem); v[13] = bits_to_double(s.dt_therm); v[14] = s.neg_dt_chem; v[15] = 0.0;
+}
+int aa_test_ion_pick(int n, const double *rec, int first, double limit, int spec_armed, const double *prev, double *words, double *out)
+{
+  if (n < 1 || n > (1 << 20)) return fail(-1, "[aa_test_ion_pick]: n = %d", n);
+  static_assert(sizeof(IonPart) == 5*sizeof(Real), "a record is five doubles");
+  const size_t nrec = (size_t)n*sizeof(IonPart), nw = 2*AA_ION_WORDS*sizeof(Real);
+  char *d = nullptr;
+  HIPCHK(hipMalloc(&d, nrec + nw + 3*sizeof(DevScalars)));
+  IonPart *part = (IonPart*)d;
+  Real *w = (Real*)(d + nrec);
+  DevScalars *sc = (DevScalars*)(d + nrec + nw);
+  DevScalars h[3];
+  pick_row_to_scalars(prev, &h[0]); h[1] = h[0]; h[2] = h[0];
+  HIPCHK(hipMemcpy(part, rec, nrec, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(w, 0xff, nw));            // (NaNs: a word a fold does not write shows)
+  HIPCHK(hipMemcpy(sc, h, 2*sizeof(DevScalars), hipMemcpyHostToDevice));
+  launch_test_ion_reduce(part, n, w, 0);
+  launch_test_ion_reduce_pick(part, n, w + AA_ION_WORDS, sc, first, limit, spec_armed, 0);
+  launch_ion_pick2(w, 1, sc + 1, first, limit, 0, spec_armed);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(words, w, nw, hipMemcpyDeviceToHost));
+  // the two-kernel form keeps its reductions in the scalars (k_ion_rates' atomics): here the fold of the records
+  h[2].dt_chem = double_to_bits(words[0]); h[2].dt_therm = double_to_bits(words[1]); h[2].max_dti = double_to_bits(words[2]);
+  h[2].cellcount = (unsigned long long)words[3]; h[2].neg_dt_chem = words[4] != 0.0;
+  HIPCHK(hipMemcpy(sc + 2, &h[2], sizeof(DevScalars), hipMemcpyHostToDevice));
+  launch_ion_pick(sc + 2, first ? 0.0 : h[0].dt_done + h[0].dt_sel, limit, 0);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(h, sc, 3*sizeof(DevScalars), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 3; k++) pick_scalars_to_row(h[k], out + (size_t)k*AA_TEST_PICK_SCALARS);
+  hipFree(d);
+  return 0;
+}
+
 // ---- history sums (dump_history.c:157-200) ---------------------------------------------------
 int aa_history(aa_grid *g, double *sums)
 {

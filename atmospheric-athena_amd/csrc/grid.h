@@ -189,6 +189,9 @@ void launch_ion_reduce_pick(const HostGrid &g, const IonPart *part, Real *words,
                             Mailbox *mb_dev = nullptr, unsigned long long seq = 0);      // mb_dev: also publish the scalars (stamp seq)
 void launch_ion_finish(const DevGrid &g, int cur, hipStream_t st);
 void launch_test_explog(int n, const Real *x, Real *ye, Real *yl, hipStream_t st);   // n a multiple of 4
+// function-level test of the folds: k_ion_reduce / k_ion_reduce_pick (no mailbox) over n records the caller wrote
+void launch_test_ion_reduce(const IonPart *part, int n, Real *words, hipStream_t st);
+void launch_test_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int first, Real dt_limit, int spec_armed, hipStream_t st);
 
 // ---- launch wrappers (hydro2d_kernels.hip): a 2-D Grid (Nx3 = 1: N3 = 1, ks = ke = 0, no ghost zones along x3) -----------
 // `edge`: 5 x ntiles_2d x N2 doubles, what a lane at the end of an x1 tile needs from the tile beside it (filled by a side kernel)

@@ -650,6 +650,12 @@ __global__ void k_test_explog(int n, const Real *x, Real *ye, Real *yl)
 }
 void launch_test_explog(int n, const Real *x, Real *ye, Real *yl, hipStream_t st)
 { hipLaunchKernelGGL(k_test_explog, dim3((n/4 + 255)/256), dim3(256), 0, st, n, x, ye, yl); }
+// function-level test of the folds (tests/test_gpu_ion_subcycles.py): the production kernels as they stand, over n records the
+// caller wrote instead of the ion_pass_blocks() records of a pass
+void launch_test_ion_reduce(const IonPart *part, int n, Real *words, hipStream_t st)
+{ hipLaunchKernelGGL(k_ion_reduce, dim3(1), dim3(256), 0, st, part, n, words); }
+void launch_test_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int first, Real dt_limit, int spec_armed, hipStream_t st)
+{ hipLaunchKernelGGL(k_ion_reduce_pick, dim3(1), dim3(256), 0, st, part, n, words, sc, first, dt_limit, spec_armed, (Mailbox*)nullptr, 0ULL); }
 
 // =============================================================================================
 static inline unsigned nblk(long n, int b) { return (unsigned)((n + b - 1)/b); }

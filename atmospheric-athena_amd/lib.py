@@ -38,6 +38,7 @@ class aa_params(C.Structure):
 
 
 ION_WORDS = 8     # AA_ION_WORDS of include/athena_amd.h
+TEST_PICK_SCALARS = 16     # AA_TEST_PICK_SCALARS: a row of aa_test_ion_pick's `prev` / `out`
 
 GRAVPOT = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double)
 GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p)      # aa_gather_fn of include/athena_amd.h
@@ -122,6 +123,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_test_lr_states": (I, [I, D, I, dp, D, D, I, I, dp, dp]),
         "aa_test_lr_states_ppm": (I, [I, D, I, dp, D, D, I, I, dp, dp]),
         "aa_test_explog": (I, [I, dp, dp, dp]),
+        "aa_test_ion_pick": (I, [I, dp, I, D, I, dp, dp, dp]),
         "aa_test_xdiv": (I, [I, dp, dp, dp]),
         "aa_history": (I, [P, dp]),
         "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),

@@ -296,6 +296,15 @@ int aa_test_xdiv(int n, const double *a, const double *b, double *out);  /* csrc
                                                                             sqrt, x_div_r(a, b, 1/b) */
 int aa_test_explog(int n, const double *x, double *y_exp, double *y_log);  /* the exp / ln of csrc/ion_pass.hip
                                                                              (n a multiple of 4): exp(x), ln|x|  */
+/* The folds and step picks of the radiation sub-cycle on scratch memory (tests/test_gpu_ion_subcycles.py): rec[n][5] = n records
+ * (dt_chem, dt_therm, max_dti, cellcount, neg) as the blocks of a pass leave them; prev[AA_TEST_PICK_SCALARS] = the scalars the
+ * picks find (those a previous call returned; NULL: all 0).  Launches k_ion_reduce -> words[0][8]; k_ion_reduce_pick (no mailbox)
+ * -> words[1][8], out[0][]; k_ion_pick2 on words[0] (one rank) -> out[1][]; k_ion_pick, its reductions set to words[0] and handed
+ * dt_done = first ? 0 : prev's dt_done + dt_sel -> out[2][].  A row of out / prev: dt_sel, limit_hit, dt_done, dt_applied,
+ * hit_applied, neg_applied, spec_state, dt_chem_out, dt_therm_out, neg_out, then the reductions as the pick leaves them: max_dti,
+ * cellcount, dt_chem, dt_therm (the doubles whose bits the words hold), neg_dt_chem, 0. */
+#define AA_TEST_PICK_SCALARS 16
+int aa_test_ion_pick(int n, const double *rec, int first, double limit, int spec_armed, const double *prev, double *words, double *out);
 
 /* ---- dump_history.c:157-200: volume integrals over the active zones of this Grid, in the column
  *      order of the .hst file: mass, total E, x1/x2/x3 Mom., x1/x2/x3-KE, scalar 0 (0 if NSCALARS=0).

@@ -8,6 +8,10 @@
 
 extern "C" int probe_maxcellcount(void) { return AA_MAXCELLCOUNT; }
 
+/* ion_pick_step alone: what the device's picks are held to (tests/test_gpu_ion_subcycles.py) */
+extern "C" double probe_ion_pick_step(double dt_chem, double dt_therm, double dt_done, double limit, int *hit)
+{ return ion_pick_step(dt_chem, dt_therm, dt_done, limit, hit); }
+
 extern "C" int probe_ion_subcycles(int fine, double limit, int maxiter, double dt_in, double tcoarse_in, int n, const double *rows,
                                    int *niter, double *dt_out, double *tcoarse_out, double *steps, int *rc_close)
 {

@@ -8,6 +8,8 @@ The same scripts drive
     the way test_distributed_gloo.OracleFusedEngine does), and
   * csrc/ion_subcycle.h -- the loop, the step pick and the root closing of the C library -- through
     fixtures/ion_subcycle_probe.cpp, built with the host compiler (no device).
+words_script states a case as the reduction words of the one-kernel sub-cycle's passes: tests/test_gpu_ion_subcycles.py writes
+them to the device and drives the real kernels with them; here they are checked on their own and through the emulated pick.
 
 Not scripted for MeshDriver: a root step that is negative on entry (the last case).  The reference's sanity check :1044 is the
 root's on a refined Mesh too; the case runs on Driver and on the header."""
@@ -68,6 +70,79 @@ CASES = [
     ("negative_dt", False, -1.0, 100, [(1.0, 1.0, 0, INF)], None, None, None, None, r"\[ion_radtransfer_3d\]: dt = "),
 ]
 FINE_DT = 3.0
+BIG = 1.7976931348623157e308              # DBL_MAX: the neutral element of the two MIN reductions
+
+
+# ---- the same cases as the reduction words of the one-kernel sub-cycle (tests/test_gpu_ion_subcycles.py writes them to the device)
+def max_dti_for(dt_hydro, cour_no):
+    """The device carries max_dti, the host forms dt_hydro = cour_no/max_dti: the max_dti of a scripted dt_hydro.  INF is 0 (no
+    zone moves), 0.0 is inf (the division gives 0), else the smallest max_dti whose quotient does not pass dt_hydro: the quotient
+    is dt_hydro where a double gives it, and the largest double the division can give below it otherwise."""
+    import numpy as np
+    if dt_hydro == INF:
+        return 0.0
+    if dt_hydro == 0.0:
+        return INF
+    c, m = np.float64(cour_no), np.float64(cour_no) / np.float64(dt_hydro)
+    while c / m > dt_hydro:
+        m = np.nextafter(m, np.float64(INF))
+    while c / np.nextafter(m, np.float64(0.0)) <= dt_hydro:
+        m = np.nextafter(m, np.float64(0.0))
+    return float(m)
+
+
+def words_script(case, cour_no):
+    """A case as the words of its passes, 8 doubles each: dt_chem, dt_therm, max_dti, cellcount, neg, 0, 0, 0.  Pass n carries the
+    rates of sub-cycle n and the update operands of sub-cycle n-1 (the mapping of Fused.ion_pass): pass 0 has no update behind it,
+    the pass behind the script's last sub-cycle has no rates (its sweep is the speculative one), and a step that was cut back to
+    the limit leaves the rates of its pass untaken -- all of these come as the neutral elements DBL_MAX / 0."""
+    limit, subs = case[2], case[4]
+    rows, dt_done, cut = [], 0.0, False
+    for n in range(len(subs) + 1):
+        dt_chem = dt_therm = BIG
+        max_dti = cellcount = neg = 0.0
+        if n > 0:
+            cellcount, max_dti = float(subs[n - 1][2]), max_dti_for(subs[n - 1][3], cour_no)
+        if n < len(subs) and not cut:
+            dt_chem, dt_therm, neg = subs[n][0], subs[n][1], float(len(subs[n]) > 4)
+            dt = dt_therm if dt_therm < dt_chem else dt_chem               # :945, :951: the step this pass's rates lead to
+            cut = dt_done + dt > limit
+            dt_done += (limit - dt_done) if cut else dt
+        rows.append((dt_chem, dt_therm, max_dti, cellcount, neg, 0.0, 0.0, 0.0))
+    return rows
+
+
+def deal_ranks(row):
+    """One pass's words dealt over three ranks so that every fold of k_ion_pick2 matters: the minimum dt_chem on the last rank,
+    the minimum dt_therm on the first, the maximum max_dti on the middle one, the cell count in thirds (21 = 7+7+7, 20 = 7+7+6),
+    the negative flag on one rank only; DBL_MAX / 0 on the others -> 3 x 8 doubles"""
+    dt_chem, dt_therm, max_dti, cellcount, neg = row[:5]
+    c = int(cellcount)
+    third = [c // 3 + (1 if r < c % 3 else 0) for r in range(3)]
+    return [(BIG, dt_therm, 0.0, float(third[0]), 0.0, 0.0, 0.0, 0.0),
+            (BIG, BIG, max_dti, float(third[1]), neg, 0.0, 0.0, 0.0),
+            (dt_chem, BIG, 0.0, float(third[2]), 0.0, 0.0, 0.0, 0.0)]
+
+
+def pick_quadruples():
+    """every (dt_chem, dt_therm, dt_done, limit) a pick meets in the table, with the step and the dt_done of the sub-cycle before
+    it (0, 0 in front of the first: dt_done = prev_done + prev_step is the loop's own sum) -> (case, n, quadruple, prev_done, prev_step)"""
+    out = []
+    for c in CASES:
+        limit, subs = c[2], c[4]
+        prev_done, prev_step = 0.0, 0.0
+        for n, s in enumerate(subs):
+            dt_done = prev_done + prev_step
+            out.append((c[0], n, (s[0], s[1], dt_done, limit), prev_done, prev_step))
+            dt = s[1] if s[1] < s[0] else s[0]
+            prev_done, prev_step = dt_done, (limit - dt_done if dt_done + dt > limit else dt)
+    return out
+
+
+def fold_ranks(rows):
+    """k_ion_pick2's fold over the ranks' words, in plain Python: MIN, MIN, MAX, SUM, OR"""
+    return (min(r[0] for r in rows), min(r[1] for r in rows), max(r[2] for r in rows), float(sum(r[3] for r in rows)),
+            float(any(r[4] != 0.0 for r in rows)), 0.0, 0.0, 0.0)
 
 
 # ---- scripted engines -------------------------------------------------------------------------------------------------
@@ -144,7 +219,7 @@ def mesh_engine(base, subs):
         def ion_update(self, l, dt): return base.ion_update(self, dt)
         def set_level_state(self, l, time, dt, nstep): self.state = (time, dt, nstep)
         def ionflux_prolong(self, l): self.prolonged = l
-        if base is Fused:
+        if issubclass(base, Fused):
             def ion_is_fused(self, l): return True
             def ion_pass(self, l, update, sweep): base.ion_pass(self, update, sweep)
             def ion_gather(self, dist): assert dist is None
@@ -194,6 +269,10 @@ def outcome(call, raises):
 @pytest.mark.parametrize("case,engine", combos(mesh=False))
 def test_driver(decks, case, engine):
     """Driver.ion_radtransfer (two-kernel form) and Driver._ion_radtransfer_fused (it dispatches on the engine's ion_fused)"""
+    check_driver(decks, case, engine)
+
+
+def check_driver(decks, case, engine):
     name, fine, limit, maxiter, subs, niter, steps, dt, dt_done, raises = case
     driver, run1, _, _ = decks
     run = copy.copy(run1); run.maxiter = maxiter
@@ -204,11 +283,16 @@ def test_driver(decks, case, engine):
         assert (got, d.eng.steps, d.dt) == (niter, steps, dt)
         assert d.eng.state == (d.time, dt, d.nstep)
         assert engine is Phased or d.eng.finished
+    return d
 
 
 @pytest.mark.parametrize("case,engine", combos(mesh=True))
 def test_mesh_driver(decks, case, engine):
     """MeshDriver.ion_radtransfer and MeshDriver._ion_radtransfer_fused, on the root level and on a refined one"""
+    check_mesh_driver(decks, case, engine)
+
+
+def check_mesh_driver(decks, case, engine):
     name, fine, limit, maxiter, subs, niter, steps, dt, dt_done, raises = case
     driver, _, par2, run2 = decks
     run = copy.copy(run2); run.maxiter = maxiter
@@ -228,6 +312,7 @@ def test_mesh_driver(decks, case, engine):
         else:
             assert (d.tcoarse, d.dtl[1]) == (dt_done, limit)
         assert engine is Phased or d.eng.finished
+    return d
 
 
 # ---- the C library's header -------------------------------------------------------------------------------------------
@@ -241,6 +326,8 @@ def probe(tmp_path_factory):
     L.probe_ion_subcycles.restype = C.c_int
     L.probe_ion_subcycles.argtypes = [C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip, dp, dp, dp, ip]
     L.probe_maxcellcount.restype = C.c_int
+    L.probe_ion_pick_step.restype = C.c_double
+    L.probe_ion_pick_step.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, ip]
     return L
 
 
@@ -269,3 +356,111 @@ def test_header(probe, case):
 
 def test_header_maxcellcount(probe, decks):
     assert probe.probe_maxcellcount() == decks[0].MAXCELLCOUNT == 20          # ionrad.h:38
+
+
+# ---- the cases as reduction words -------------------------------------------------------------------------------------
+COURS = [0.5, 0.4]          # what the runs on the device use (1.0 is max_dti = 0.5), and the deck's own
+
+
+@pytest.mark.parametrize("cour_no", COURS)
+def test_words_script_encodings(cour_no):
+    """words_script states dt_hydro as max_dti: with numpy's float64 division cour_no/max_dti is INF, 0 or the scripted value --
+    or, where no double gives it, the largest quotient below -- and compares with dt_done as the case needs"""
+    import numpy as np
+    c = np.float64(cour_no)
+    seen = set()
+    for case in CASES:
+        subs, steps = case[4], case[6]
+        rows = words_script(case, cour_no)
+        assert len(rows) == len(subs) + 1 and all(len(r) == 8 and r[5:] == (0.0, 0.0, 0.0) for r in rows)
+        assert rows[0][2:5] == (0.0, 0.0, float(len(subs[0]) > 4)) and rows[-1][:2] == (BIG, BIG)
+        dt_done = 0.0
+        for n, s in enumerate(subs):
+            m = np.float64(rows[n + 1][2])
+            with np.errstate(divide="ignore"):
+                q = c / m
+            if s[3] == INF:
+                assert m == 0.0 and q == INF
+            elif s[3] == 0.0:
+                assert q == 0.0
+            else:
+                assert q <= s[3] and c / np.nextafter(m, np.float64(0.0)) > s[3]        # the largest quotient that does not pass it
+                seen.add((s[3], float(q)))
+            assert rows[n + 1][3] == s[2]
+            if steps is not None and n < len(steps):
+                dt_done += steps[n]
+                assert (q < dt_done) == (s[3] < dt_done), (case[0], n)
+    if cour_no == 0.5:
+        # "equal goes on, one bit below stops": 1.0 is exact; no quotient of 0.5 is the double below 2.0, the next one down is taken
+        assert seen == {(1.0, 1.0), (BELOW2, H("0x1.ffffffffffffep+0"))}
+
+
+def test_deal_ranks_folds_back():
+    for case in CASES:
+        for row in words_script(case, 0.5):
+            dealt = deal_ranks(row)
+            assert fold_ranks(dealt) == row
+            # every fold matters: no rank alone, and no two ranks, give the row (unless the row is neutral in that word)
+            assert dealt[2][0] == row[0] and dealt[0][1] == row[1] and dealt[1][2] == row[2] and dealt[1][4] == row[4]
+            assert dealt[0][0] == dealt[1][0] == BIG and dealt[1][1] == dealt[2][1] == BIG and dealt[0][2] == dealt[2][2] == 0.0
+    assert [r[3] for r in deal_ranks((1.0, 1.0, 0.0, 21.0, 0.0))] == [7.0, 7.0, 7.0]
+    assert [r[3] for r in deal_ranks((1.0, 1.0, 0.0, 20.0, 0.0))] == [7.0, 7.0, 6.0]
+
+
+def test_pick_quadruples_follow_the_table(probe):
+    """the quadruples walk the cases with the steps the table states, and the header's ion_pick_step gives those steps on them"""
+    quads = pick_quadruples()
+    assert len(quads) == sum(len(c[4]) for c in CASES)
+    for c in CASES:
+        mine = [q for q in quads if q[0] == c[0]]
+        assert [q[2][2] for q in mine][0] == 0.0 and all(q[2][2] == q[3] + q[4] for q in mine)
+        if c[6] is not None:
+            assert [q[4] for q in mine[1:]] == c[6][:-1]
+            for q, step in zip(mine, c[6]):
+                hit = C.c_int(-1)
+                assert probe.probe_ion_pick_step(*q[2], C.byref(hit)) == step and hit.value in (0, 1)
+
+
+class Worded(Fused):
+    """Fused fed from words_script: its pass takes the pass's row instead of reading the sub-cycles (the update still books the
+    step it applied); dt_hydro is the host's quotient cour_no/max_dti"""
+
+    def __init__(self, case, cour_no):
+        super().__init__(case[4])
+        self.rows, self.cour_no, self.k = words_script(case, cour_no), cour_no, 0
+
+    def ion_begin(self): self.n = self.k = 0
+
+    def ion_pass(self, update, sweep):
+        import numpy as np
+        if update:
+            self.steps.append(self.sc["dt_sel"]); self.n += 1
+        r = self.rows[self.k]; self.k += 1
+        with np.errstate(divide="ignore"):
+            self.words = (r[0], r[1], float(np.float64(self.cour_no) / np.float64(r[2])), int(r[3]), r[4] != 0.0)
+
+
+def worded(case, cour_no):
+    """Worded as an engine class that is built from the sub-cycles, as Phased and Fused are"""
+    class W(Worded):
+        def __init__(self, subs): Worded.__init__(self, case, cour_no)
+    return W
+
+
+def worded_combos(mesh):
+    return [pytest.param(c, cour, id=f"{c[0]}-{cour}") for c in CASES for cour in COURS
+            if not ((c[1] and not mesh) or (c[0] == "negative_dt" and mesh))]
+
+
+@pytest.mark.parametrize("case,cour_no", worded_combos(mesh=False))
+def test_words_script_driver(decks, case, cour_no):
+    """the words give the table's outcomes through the emulated pick of Fused and Driver's loop: the script is right before it
+    reaches a device"""
+    d = check_driver(decks, case, worded(case, cour_no))
+    assert case[9] is not None or d.eng.k == case[5] + 1              # niter + 1 passes, the script did not run out
+
+
+@pytest.mark.parametrize("case,cour_no", worded_combos(mesh=True))
+def test_words_script_mesh_driver(decks, case, cour_no):
+    d = check_mesh_driver(decks, case, worded(case, cour_no))
+    assert case[9] is not None or d.eng.k == case[5] + 1
