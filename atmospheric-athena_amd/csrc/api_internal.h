@@ -64,6 +64,10 @@ struct aa_grid {
   // "piece staged" [0..1] / "piece on the host" [2..3] of either half; made by the first aa_dump_section
   float *dump_host = nullptr; size_t dump_cap = 0;
   hipStream_t dump_st = nullptr; hipEvent_t dump_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // ... and the snapshot slots of aa_dump_snapshot_begin: a whole payload in device memory (NOT the face-state area) and its page-locked
+  // twin, `cap` floats each, made on first use; held: between begin and release; staged / done: "payload made" on st, "on the host" on dump_st
+  struct DumpSlot { float *dev = nullptr, *host = nullptr; size_t cap = 0; bool held = false; int fmt = 0; hipEvent_t staged = nullptr, done = nullptr; };
+  DumpSlot snap[AA_DUMP_SLOTS];
   bool prof = false;
   std::vector<ProfEntry> pe;
   std::vector<hipEvent_t> ev_pool;     // events of drained scopes, reused (a small Grid's step is ~25 scopes: creating 50 events per step showed)

@@ -145,6 +145,10 @@ class HipEngine:
         """dump_vtk / dump_binary of this slab: the payload comes from the device in file order (csrc/dump.hip)"""
         self.g.write_dump(path, fmt, prim, time=time, dt=dt)
 
+    def dump_source(self):
+        """what takes the snapshots of an overlapped dump (outputs.OutputSet.overlapped_dump): this slab's Grid"""
+        return self.g
+
     def fofc_counts(self): return self.g.fofc_counts()
     def close(self): self.g.close()
 
@@ -454,7 +458,12 @@ class Driver(_Runner):
         if not _fires(out, 0):
             return
         g, r = self.grid, self.run
-        path = outputs.path(dumps.fname(outputs.basename, 0, 0, out.num, out.out_fmt))
+        rel = dumps.fname(outputs.basename, 0, 0, out.num, out.out_fmt)
+        if getattr(outputs, "overlap", False):    # snapshot now, copy and file write beside the next steps -- where the engine has a device
+            src = self.eng.dump_source() if hasattr(self.eng, "dump_source") else None
+            if outputs.overlapped_dump(src, rel, out.out_fmt, out.prim, time=self.time, dt=self.dt):
+                return
+        path = outputs.path(rel)
         if hasattr(self.eng, "write_dump"):
             self.eng.write_dump(path, out.out_fmt, out.prim, self.time, self.dt)
         else:                                     # an engine without a device: the same payload from its host block
@@ -786,6 +795,14 @@ class MeshRun(_Runner):
     def step(self): return self.mesh.step()
 
     def write_dump(self, out, outputs):
+        if getattr(outputs, "overlap", False):    # every level's Grid with its own snapshot slots; a level without the route writes now
+            t, dt = self.time, self.dt
+            for g, (l, d) in zip(self.mesh.lev, self.mesh.domain_numbers()):
+                if _fires(out, l, d):
+                    rel = dumps.fname(outputs.basename, l, d, out.num, out.out_fmt)
+                    if not outputs.overlapped_dump(g, rel, out.out_fmt, out.prim, level=l, domain=d, time=t, dt=dt):
+                        g.write_dump(outputs.path(rel), out.out_fmt, out.prim, level=l, domain=d, time=t, dt=dt)
+            return
         for rel in self.mesh.write_dump(outputs.dir, outputs.basename, out.num, out.out_fmt, out.prim, out.level, out.domain):
             outputs.written.append(rel)
 
@@ -993,6 +1010,8 @@ class MeshDriver(_Runner):
     def write_dump(self, out, outputs):
         """dump_vtk / dump_binary under MPI + SMR: one file per level this rank holds zones of, under the rank's directory;
         the header is the slab's own (its DIMENSIONS and ORIGIN, the level's spacing, the Mesh time)."""
+        if getattr(outputs, "overlap", False):
+            outputs.overlap_fallback("MeshDriver", "overlapped dumps are not built for a refined mesh over several ranks (MeshDriver)")
         if hasattr(self.eng, "write_dump"):
             for rel in self.eng.write_dump(outputs.dir, outputs.basename, out.num, out.out_fmt, out.prim, out.level, out.domain,
                                            self.time, self.dt):

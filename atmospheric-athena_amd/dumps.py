@@ -14,8 +14,10 @@ arithmetic in numpy, for engines without a device and as the checker of the kern
 """
 from __future__ import annotations
 
+import collections
 import os
 import struct
+import threading
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -107,24 +109,40 @@ def _raw(a) -> memoryview:
     return memoryview(a).cast("B")
 
 
+def dump_head(fmt, *, nx, minx, dx, time: float, dt: float, gamma: float, prim: bool, nscal: int, level: int = 0,
+              domain: int = 0):
+    """-> (header bytes, [the bytes in front of section i]) of a dump file: everything in it that is not field data.  vtk: the
+    text header and the title lines of every section; bin: the binary header, nothing between the sections.  (`prim` does not
+    show in a bin file: the reference's header does not say which set it holds.)"""
+    fmt = FORMATS.get(fmt, fmt)
+    if fmt == VTK:
+        return vtk_header(nx, minx, dx, time, level, domain, prim), vtk_titles(prim, nscal)
+    if fmt == BIN:
+        return bin_header(nx, minx, dx, time, dt, gamma, nscal), [b""] * (5 + nscal)
+    raise ValueError(f"[write_dump]: format {fmt!r} (vtk or bin)")
+
+
+def write_sections(path: str, header: bytes, titles: Sequence[bytes], section: Callable[[int], np.ndarray]) -> None:
+    """header | title 0 | section(0) | title 1 | section(1) ...: the one place that lays a dump file out"""
+    with open(path, "wb") as f:
+        f.write(header)
+        for i, title in enumerate(titles):
+            if title:
+                f.write(title)
+            f.write(_raw(section(i)))
+
+
 def write_vtk(path: str, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, prim: bool, nscal: int,
               level: int = 0, domain: int = 0) -> None:
     """``section(i)`` returns section i of the vtk payload (big-endian words, see the module text), as an array or bytes."""
-    with open(path, "wb") as f:
-        f.write(vtk_header(nx, minx, dx, time, level, domain, prim))
-        for i, title in enumerate(vtk_titles(prim, nscal)):
-            f.write(title)
-            f.write(_raw(section(i)))
+    write_sections(path, vtk_header(nx, minx, dx, time, level, domain, prim), vtk_titles(prim, nscal), section)
 
 
 def write_bin(path: str, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, dt: float, gamma: float,
               prim: bool, nscal: int) -> None:
     """``section(i)`` returns variable i of the bin payload (native words).  (`prim` does not show in the file: the reference's
     header does not say which set it holds.)"""
-    with open(path, "wb") as f:
-        f.write(bin_header(nx, minx, dx, time, dt, gamma, nscal))
-        for i in range(5 + nscal):
-            f.write(_raw(section(i)))
+    write_sections(path, bin_header(nx, minx, dx, time, dt, gamma, nscal), [b""] * (5 + nscal), section)
 
 
 def write_dump(path: str, fmt, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, dt: float, gamma: float,
@@ -145,3 +163,101 @@ def write_dump_from_block(path: str, fmt, U: np.ndarray, *, prim: bool, gamma: f
     """A dump of a host block of active zones (the CPU engines' path)."""
     pay = payload_from_block(U, fmt, prim, gamma, nscal)
     write_dump(path, fmt, lambda i: pay[i], prim=prim, gamma=gamma, nscal=nscal, **kw)
+
+
+class OverlapWriter:
+    """Writes dump files on ONE background thread while the run goes on.  Pure Python: the worker touches nothing but the
+    arrays of a job (page-locked host memory that a device copy has filled and finished with) and files -- it never calls the
+    library, HIP or torch.  Whatever has to happen on the driving thread when a file is complete (giving the snapshot's slot
+    back) is the job's ``on_done``, which `poll`, `wait` and `finish` run on THEIR caller's thread.
+
+    A job is (path, header bytes, section titles, section arrays, on_done).  The worker writes ``path + ".part"`` and renames it
+    onto `path` when the file is complete: a file under its final name is always whole.  Jobs are written in the order of
+    `submit`, so of two jobs for the same path the later one stays.  An exception of the worker is kept (the first one, until it
+    has been raised; the job's on_done still runs, the jobs behind it are tried all the same), and the next `poll` / `wait` or
+    `finish` re-raises it in the driving thread."""
+
+    def __init__(self):
+        self._cv = threading.Condition()
+        self._jobs = collections.deque()     # submitted, not yet taken by the worker
+        self._done = collections.deque()     # (ticket, on_done) of finished jobs whose on_done has not run yet
+        self._submitted = 0                  # tickets handed out / jobs the worker is through with
+        self._completed = 0
+        self._error = None
+        self._thread = None
+        self._stop = False
+
+    def submit(self, path: str, header: bytes, titles: Sequence[bytes], sections: Sequence[np.ndarray], on_done=None) -> int:
+        """-> the job's ticket (for `wait`)"""
+        with self._cv:
+            self._submitted += 1
+            self._jobs.append((self._submitted, path, header, list(titles), list(sections), on_done))
+            if self._thread is None:
+                self._stop = False
+                self._thread = threading.Thread(target=self._work, name="dump-writer", daemon=True)
+                self._thread.start()
+            self._cv.notify_all()
+            return self._submitted
+
+    def _work(self):
+        while True:
+            with self._cv:
+                while not self._jobs and not self._stop:
+                    self._cv.wait()
+                if not self._jobs:
+                    return
+                ticket, path, header, titles, sections, on_done = self._jobs.popleft()
+            err = None
+            try:
+                write_sections(path + ".part", header, titles, lambda i: sections[i])
+                os.replace(path + ".part", path)
+            except BaseException as e:           # kept for the driving thread
+                err = e
+            del sections
+            with self._cv:
+                if err is not None and self._error is None:
+                    self._error = err
+                self._completed = ticket
+                self._done.append((ticket, on_done))
+                self._cv.notify_all()
+
+    def _settle(self):
+        """on the caller's thread: the on_done of every finished job, then the worker's exception if there is one"""
+        while True:
+            with self._cv:
+                if not self._done:
+                    break
+                _ticket, on_done = self._done.popleft()
+            if on_done is not None:
+                on_done()
+        with self._cv:
+            err, self._error = self._error, None
+        if err is not None:
+            raise err
+
+    @property
+    def pending(self) -> int:
+        """jobs submitted and not yet written"""
+        with self._cv:
+            return self._submitted - self._completed
+
+    def poll(self) -> None:
+        """never blocks"""
+        self._settle()
+
+    def wait(self, ticket: int) -> None:
+        """blocks until the worker is through with the job of this ticket"""
+        with self._cv:
+            while self._completed < ticket:
+                self._cv.wait()
+        self._settle()
+
+    def finish(self) -> None:
+        """every job written, the worker joined; may be called again (and `submit` starts a new worker)"""
+        with self._cv:
+            th, self._thread = self._thread, None
+            self._stop = True
+            self._cv.notify_all()
+        if th is not None:
+            th.join()
+        self._settle()

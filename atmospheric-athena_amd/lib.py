@@ -128,6 +128,9 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_history": (I, [P, dp]),
         "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),
         "aa_dump_section": (I, [P, I, I, I, C.POINTER(C.c_float)]),
+        "aa_dump_snapshot_bytes": (LL, [P, I]), "aa_dump_snapshot_begin": (I, [P, I, I, I, LL]),
+        "aa_dump_snapshot_ready": (I, [P, I]), "aa_dump_snapshot_wait": (I, [P, I]),
+        "aa_dump_snapshot_section": (C.c_void_p, [P, I, I, llp]), "aa_dump_snapshot_release": (I, [P, I]),
         "aa_rst_sections": (I, [P]), "aa_rst_section_label": (I, [P, I, C.c_char_p, I]), "aa_rst_section_doubles": (LL, [P, I]),
         "aa_rst_section_get": (I, [P, I, dp]), "aa_rst_section_put": (I, [P, I, dp]),
         "aa_rst_section_get_box": (I, [P, I, ip, ip, dp]), "aa_rst_section_put_box": (I, [P, I, ip, ip, dp]),
@@ -189,6 +192,54 @@ def params_from_grid(g: GridConfig, device: int = 0, ion_path: int = 0, nslab: i
     return p
 
 
+class Snapshot:
+    """One slot of a Grid's dump snapshots between aa_dump_snapshot_begin and _release (Grid.dump_snapshot makes it).  Every
+    method calls HIP and belongs to the thread that drives the run; the arrays of `section` are plain page-locked host memory,
+    which any thread may read until `release`."""
+
+    def __init__(self, grid: "Grid", slot: int, fmt: int, prim: bool):
+        self._g, self.slot, self.fmt, self.prim = grid, slot, fmt, prim
+        self.nsections = int(grid.L.aa_dump_sections(grid._h, fmt))
+
+    def _grid(self) -> "Grid":
+        if self._g is None:
+            raise AthenaError("[Snapshot]: released, or its Grid is closed")
+        return self._g
+
+    def ready(self) -> bool:
+        """whether the payload is on the host: one event query, never blocks"""
+        g = self._grid()
+        rc = g.L.aa_dump_snapshot_ready(g._h, self.slot)
+        if rc < 0:
+            g._chk(rc)
+        return rc == 1
+
+    def wait(self) -> "Snapshot":
+        g = self._grid(); g._chk(g.L.aa_dump_snapshot_wait(g._h, self.slot)); return self
+
+    def section(self, i: int) -> np.ndarray:
+        """section i of the payload: a view of the page-locked buffer, no copy (float32 holding the file's words, as
+        Grid.dump_section returns them); valid until release"""
+        g = self._grid()
+        n = C.c_longlong()
+        p = g.L.aa_dump_snapshot_section(g._h, self.slot, int(i), C.byref(n))
+        if not p:
+            raise AthenaError(g.L.aa_last_error().decode() or "[aa_dump_snapshot_section]")
+        a = np.ctypeslib.as_array((C.c_float * n.value).from_address(p))
+        a.flags.writeable = False
+        return a
+
+    def sections(self) -> list:
+        return [self.section(i) for i in range(self.nsections)]
+
+    def release(self) -> None:
+        """frees the slot (waits first if the copy is still in flight); the arrays of `section` are dead afterwards"""
+        g, self._g = self._g, None
+        if g is not None and g._h is not None:
+            g._snaps[self.slot] = None
+            g._chk(g.L.aa_dump_snapshot_release(g._h, self.slot))
+
+
 class Grid:
     """Device-resident Grid.  Method names follow the reference's call sites."""
 
@@ -199,6 +250,7 @@ class Grid:
         self.L = load(strict)
         self.params = params_from_grid(grid, device, ion_path, 1 if cuts is not None else nslab)
         self.nvar = 5 + grid.run.nscal
+        self._composite = cuts is not None or nslab > 1
         # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, init_grid.c:144-174)
         self.N = tuple(n + 2 * NGHOST if n > 1 else 1 for n in grid.Nx)
         self.ndim = sum(1 for n in grid.Nx if n > 1)
@@ -219,6 +271,9 @@ class Grid:
 
     def close(self):
         if self._h is not None:
+            for s in getattr(self, "_snaps", ()):      # (aa_destroy waits for a snapshot in flight; its memory goes with the Grid)
+                if s is not None:
+                    s._g = None
             self.L.aa_destroy(self._h); self._h = None
 
     def __del__(self):
@@ -427,13 +482,6 @@ class Grid:
         """dump_vtk / dump_binary of this Grid: the header from the Grid's geometry and MeshS time / dt (or the ones given:
         a driver that keeps them itself), the sections from the device."""
         from . import dumps
-        g = self.cfg; r = g.run
-        lev = g.level if level is None else level
-        # (init_mesh.c:331-337: a direction with one zone -- x3 of a 2-D Grid -- keeps the root's extent on every level)
-        dx = tuple(r.dx[d] / float(1 << g.level) if g.Nx[d] > 1 else r.dx[d] for d in range(3))
-        if time is None or dt is None:
-            t_, dt_, _ = self.mesh_state()
-            time = t_ if time is None else time; dt = dt_ if dt is None else dt
         buf = {}
 
         def section(i):
@@ -441,8 +489,46 @@ class Grid:
             if n not in buf:
                 buf[n] = np.empty(n, dtype=np.float32)
             return self.dump_section(fmt, prim, i, buf[n])
-        dumps.write_dump(path, fmt, section, nx=g.Nx, minx=g.MinX, dx=dx, time=time, dt=dt, gamma=r.gamma, prim=prim,
-                         nscal=r.nscal, level=lev, domain=domain)
+        dumps.write_dump(path, fmt, section, **self.dump_geometry(prim, level, domain, time, dt))
+
+    def dump_geometry(self, prim: bool, level: int | None = None, domain: int = 0, time: float | None = None,
+                      dt: float | None = None) -> dict:
+        """what the header of a dump of this Grid says (the keywords of dumps.write_dump / dumps.dump_head)"""
+        g = self.cfg; r = g.run
+        lev = g.level if level is None else level
+        # (init_mesh.c:331-337: a direction with one zone -- x3 of a 2-D Grid -- keeps the root's extent on every level)
+        dx = tuple(r.dx[d] / float(1 << g.level) if g.Nx[d] > 1 else r.dx[d] for d in range(3))
+        if time is None or dt is None:
+            t_, dt_, _ = self.mesh_state()
+            time = t_ if time is None else time; dt = dt_ if dt is None else dt
+        return dict(nx=g.Nx, minx=g.MinX, dx=dx, time=time, dt=dt, gamma=r.gamma, prim=prim, nscal=r.nscal, level=lev, domain=domain)
+
+    # ---- the same payload beside the run: one kernel, one copy, two slots (csrc/dump.hip aa_dump_snapshot_*) -----------------
+    DUMP_SLOTS = 2                       # AA_DUMP_SLOTS
+
+    @property
+    def composite(self) -> bool:
+        """a Grid cut into slabs inside the library: one handle for several devices (no snapshots: dump_section is the path)"""
+        return bool(getattr(self, "_composite", False))
+
+    def dump_snapshot_bytes(self, fmt) -> int:
+        from . import dumps
+        return int(self.L.aa_dump_snapshot_bytes(self._h, dumps.FORMATS.get(fmt, fmt)))
+
+    def dump_snapshot(self, fmt, prim: bool, max_bytes: int = 8 << 30) -> "Snapshot":
+        """The whole payload of a dump of the state as it is now, on its way to page-locked host memory while the run goes on:
+        the kernel is queued behind what the step launched, the copy runs beside what comes next, nothing waits.  Takes the
+        first free slot of the two; with both held the library refuses (AthenaError) -- release one.  Call this, and every
+        method of the Snapshot, from the thread that drives the run; another thread may read the arrays `section` returns."""
+        from . import dumps
+        fmt = dumps.FORMATS.get(fmt, fmt)
+        if not hasattr(self, "_snaps"):
+            self._snaps = [None] * self.DUMP_SLOTS      # the Snapshots that hold this Grid's slots
+        free =[i for i, s in enumerate(self._snaps) if s is None]
+        slot = free[0] if free else 0                 # (none free: the library names the refusal)
+        self._chk(self.L.aa_dump_snapshot_begin(self._h, slot, fmt, 1 if prim else 0, int(max_bytes)))
+        s = self._snaps[slot] = Snapshot(self, slot, fmt, prim)
+        return s
 
     # ---- restart dumps (restart.c): the sections of this Grid to and from the device -----------
     def rst_sections(self):

@@ -15,9 +15,15 @@ the restart file between header and trailer, the host-block state, the history r
 and ``main`` -- is written once in their base class driver._Runner.  File names are ath_fname's (dumps.fname); rank r of a
 multi-rank run writes under ``id<r>/`` with ``-id<r>`` in the base name for r > 0 (main.c:227-232, :785-850), every rank its own
 Grids; the history of a Domain goes out once, under rank 0's directory.
+
+``OutputSet(..., overlap=True)`` writes the ``vtk`` / ``bin`` dumps of targets that have the route beside the run
+(``overlapped_dump``: a device snapshot taken when the block fires, its copy to page-locked memory next to the following steps,
+the file written by the thread of dumps.OverlapWriter); the files and ``written`` are those of the synchronous run.  One rule:
+only the thread that drives the run calls the library -- ``poll`` and ``finish`` belong to it.
 """
 from __future__ import annotations
 
+import collections
 import os
 import warnings
 from dataclasses import dataclass
@@ -50,8 +56,16 @@ class Output:
 
 class OutputSet:
     def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int,
-                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None):
+                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False, overlap_max_bytes: int = 8 << 30):
+        """overlap = True: vtk / bin dumps of targets that have the route (see `overlapped_dump`) are written beside the run;
+        overlap_max_bytes: the largest payload that may take it (each Grid that dumps keeps two device buffers and two
+        page-locked buffers of its payload's size)."""
         self.par, self.outs, self.rst = par, outs, rst
+        self.overlap, self.overlap_max_bytes = bool(overlap), int(overlap_max_bytes)
+        self._writer = None                   # dumps.OverlapWriter, made by the first overlapped dump
+        self._pending = collections.deque()   # snapshots taken whose payload is still on its way: jobs in the order of `written`
+        self._inflight = []                   # jobs the writer has, their slots not yet given back
+        self._warned = set()                  # fall-backs to the synchronous path already told
         self.rst_ngrid = tuple(int(v) for v in rst_ngrid) if rst_ngrid else None      # restart dumps cut for other Grids
         # ... of a refined mesh: NGrid of every Domain, level by level (restart.domain_blocks), and the ranks they are dealt to
         self.rst_mesh_ngrid = [tuple(int(v) for v in g) for g in rst_mesh_ngrid] if rst_mesh_ngrid else None
@@ -66,7 +80,8 @@ class OutputSet:
 
     @classmethod
     def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
-                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None) -> "OutputSet":
+                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False,
+                 overlap_max_bytes: int = 8 << 30) -> "OutputSet":
         """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
         r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
         rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
@@ -129,12 +144,14 @@ class OutputSet:
                 rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
             else:
                 outs.append(o)
-        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc)
+        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes)
 
     def data_output(self, target, flag: int) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt
         ONCE (output.c:509-512).  The restart dump goes first, after every block's next number and time have been written
-        back into the parameter table (:526-543), so that a restarted run continues the numbering."""
+        back into the parameter table (:526-543), so that a restarted run continues the numbering.  With overlapped dumps it
+        begins with a `poll`: the payloads that have arrived go to the writer, the files that are complete give their slots back."""
+        self.poll()
         time = target.time
         fire = []
         for o in self.outs:
@@ -175,14 +192,111 @@ class OutputSet:
         return p
 
 
+    # ---- overlapped vtk / bin dumps: device snapshot, background write (dumps.OverlapWriter) -----------------------------------
+    def overlap_fallback(self, kind: str, reason: str) -> None:
+        """a dump of a run with overlap = True takes the synchronous path: said once per kind of reason"""
+        if kind not in self._warned:
+            self._warned.add(kind)
+            warnings.warn(f"[data_output]: overlap = True, but {reason}: these dumps are written synchronously (the same files)")
+
+    def overlapped_dump(self, source, rel: str, fmt, prim: bool, level=None, domain: int = 0, time=None, dt=None) -> bool:
+        """The overlapped route of a target's write_dump for the dump `rel` (relative to this rank's directory) of `source`:
+        something with ``dump_snapshot(fmt, prim, max_bytes)`` -> a snapshot (``ready()``, ``wait()``, ``sections()``,
+        ``release()``), ``dump_snapshot_bytes(fmt)``, ``dump_geometry(prim, level, domain, time, dt)``, ``DUMP_SLOTS`` and
+        ``composite`` -- lib.Grid.  -> False when the route does not exist here (overlap off; no such source; a Grid cut into slabs;
+        a payload beyond overlap_max_bytes): the caller then writes synchronously, and the first such case of a kind has warned.
+
+        Else the snapshot is queued NOW, behind what the last step launched -- the file will hold this instant's state -- and
+        `rel` enters `written` now, as the synchronous run would have it; the header is made now too, from the time and dt of now.
+        Nothing waits: the copy to the host runs beside the next step, `poll` (every data_output begins with one) hands payloads
+        that have arrived to the writer thread and gives the slots of finished files back.  Every HIP call stays on this thread.
+
+        A source has DUMP_SLOTS (two) slots.  When all are held -- the dumps come faster than copy and file write take -- this
+        call WAITS for the source's oldest file to be complete: the synchronous cost reappears, one dump late."""
+        if not self.overlap:
+            return False
+        if source is None or not hasattr(source, "dump_snapshot"):
+            self.overlap_fallback("engine", "this engine keeps no state on a device")
+            return False
+        if getattr(source, "composite", False):
+            self.overlap_fallback("slabs", "a Grid cut into slabs inside the library takes no snapshot (aa_dump_section is the path there)")
+            return False
+        nbytes = int(source.dump_snapshot_bytes(fmt))
+        if nbytes > self.overlap_max_bytes:
+            self.overlap_fallback("max_bytes", f"a payload of {nbytes} bytes is beyond overlap_max_bytes = {self.overlap_max_bytes}")
+            return False
+        from . import dumps
+        slots = int(getattr(source, "DUMP_SLOTS", 2))
+        while sum(1 for j in list(self._pending) + self._inflight if j["source"] is source) >= slots:
+            self._wait_oldest(source)
+        snap = source.dump_snapshot(fmt, prim, self.overlap_max_bytes)
+        try:
+            header, titles = dumps.dump_head(fmt, **source.dump_geometry(prim, level, domain, time, dt))
+            path = self.path(rel)
+        except BaseException:
+            snap.release()
+            raise
+        self._pending.append({"source": source, "snap": snap, "path": path, "header": header, "titles": titles, "ticket": None})
+        return True
+
+    def _submit(self, job) -> None:
+        from . import dumps
+        if self._writer is None:
+            self._writer = dumps.OverlapWriter()
+        self._inflight.append(job)
+
+        def on_done(job=job):                     # (run by poll / wait / finish on the driving thread: release calls HIP)
+            self._inflight.remove(job)
+            job["snap"].release()
+        job["ticket"] = self._writer.submit(job["path"], job["header"], job["titles"], job["snap"].sections(), on_done)
+
+    def _wait_oldest(self, source) -> None:
+        """blocks until the oldest job of `source` is on disk and its slot free (files are written in the order of `written`:
+        everything taken before it goes to the writer first)"""
+        held = [j for j in self._inflight if j["source"] is source]
+        if not held:
+            while self._pending:
+                j = self._pending.popleft()
+                j["snap"].wait()
+                self._submit(j)
+                if j["source"] is source:
+                    held = [j]
+                    break
+        self._writer.wait(held[0]["ticket"])
+
+    def poll(self) -> None:
+        """Never blocks: one event query per pending snapshot (oldest first, up to the first that is still in flight); hands the
+        ones on the host to the writer, releases the slots of the files that are complete, re-raises what the writer met."""
+        while self._pending and self._pending[0]["snap"].ready():
+            self._submit(self._pending.popleft())
+        if self._writer is not None:
+            self._writer.poll()
+
+    def finish(self) -> None:
+        """Waits for the snapshots still in flight, hands them to the writer, joins it and re-raises what it met: afterwards every
+        file in `written` is on disk and every slot free.  May be called again."""
+        try:
+            while self._pending:
+                j = self._pending[0]
+                j["snap"].wait()
+                self._submit(self._pending.popleft())
+        finally:
+            if self._writer is not None:
+                self._writer.finish()
+
+
 def run(target, outputs: OutputSet, tlim: float, nlim: int = -1) -> None:
     """main() of the reference around the loop: forced output after the start (main.c:501; a restarted run -- a target with
     ``restarted`` set -- skips it), data_output(0) at the top of every pass (:524), forced output after the loop (:743).
     `target`: start(), step(), time, nstep and the writers."""
-    target.start()
-    if not getattr(target, "restarted", False):
+    try:
+        target.start()
+        if not getattr(target, "restarted", False):
+            outputs.data_output(target, 1)
+        while target.time < tlim and (nlim < 0 or target.nstep < nlim):
+            outputs.data_output(target, 0)
+            target.step()
         outputs.data_output(target, 1)
-    while target.time < tlim and (nlim < 0 or target.nstep < nlim):
-        outputs.data_output(target, 0)
-        target.step()
-    outputs.data_output(target, 1)
+    finally:
+        if hasattr(outputs, "finish"):            # overlapped dumps: every file on disk when main returns
+            outputs.finish()

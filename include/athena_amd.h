@@ -328,6 +328,32 @@ int       aa_dump_sections(const aa_grid *g, int fmt);                        /*
 long long aa_dump_section_floats(const aa_grid *g, int fmt, int section);     /* n or 3n; 0 past the last section       */
 int       aa_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 
+/* ---- the same payload without stopping the run: ONE kernel makes every section of a dump from the state as it is when the call is
+ *      queued (behind everything the step launched) into a snapshot buffer in device memory -- not the face-state area -- and one
+ *      copy on the stream of the dumps brings it into page-locked host memory while the Grid's stream goes on with the next step.
+ *      A Grid has AA_DUMP_SLOTS snapshot slots, each a device buffer and a page-locked buffer of aa_dump_snapshot_bytes() (made on
+ *      the slot's first use, sized for either format, kept until aa_destroy): two snapshots may be in flight or in the hands of a
+ *      writer at a time.
+ *        begin    queues kernel and copy and returns without waiting (allocation on first use apart).  It leaves the face-state
+ *                 area and the sweeps of aa_integrate_begin alone: a step between begin and ready is the step it would have been.
+ *                 max_bytes: the caller's cap on the payload (a larger one is refused).
+ *        ready    1: the payload is on the host, 0: in flight, < 0: error; never blocks.   wait: blocks until it is.
+ *        section  section s of the payload in the page-locked buffer, *nfloats = aa_dump_section_floats() (sections start 16-byte
+ *                 aligned, the words are those of aa_dump_section bit for bit); NULL before the payload is on the host.  The
+ *                 pointer holds until release.
+ *        release  waits if the copy is still in flight and frees the slot for the next begin.
+ *      ONE threading rule: every one of these calls -- like the rest of this header -- comes from the thread that drives the run.
+ *      Another thread may READ the memory `section` returned (and write it to a file) between ready and release, nothing else.
+ *      Composite handles (aa_params.nslab > 1) refuse begin: aa_dump_section is the path there.  aa_destroy with a snapshot in
+ *      flight waits for it.                                                                                                       */
+#define AA_DUMP_SLOTS 2
+long long    aa_dump_snapshot_bytes(const aa_grid *g, int fmt);                 /* of the payload with its padding (0: unknown format) */
+int          aa_dump_snapshot_begin(aa_grid *g, int slot, int fmt, int prim, long long max_bytes);
+int          aa_dump_snapshot_ready(aa_grid *g, int slot);
+int          aa_dump_snapshot_wait(aa_grid *g, int slot);
+const float *aa_dump_snapshot_section(aa_grid *g, int slot, int section, long long *nfloats);
+int          aa_dump_snapshot_release(aa_grid *g, int slot);
+
 /* ---- restart.c:463-983 / restart_grids :52-456: the double-precision payload of a restart dump to and from the resident state,
  *      one labelled section at a time, ACTIVE zones [k][j][i] only:
  *        DENSITY | 1-MOMENTUM | 2-MOMENTUM | 3-MOMENTUM | ENERGY | EDGEFLUX (ion radiation; (Nx1+1)(Nx2+1)(Nx3+1)) | SCALAR n

@@ -5,7 +5,17 @@ box, alternating A B A B; medians.  Then the wall time of one complete `vtk prim
 
   python profiles/dump_rate.py [--sizes 256 512] [--reps 3] [--file-size 512] [--out profiles/out/dump_rate.json]
 
-Bytes alone: B moves 4*NVAR*N^3 against 8*NVAR*(N+8)^3, a factor 2*(1+8/N)^3 (2.19 at 256^3, 2.10 at 512^3)."""
+Bytes alone: B moves 4*NVAR*N^3 against 8*NVAR*(N+8)^3, a factor 2*(1+8/N)^3 (2.19 at 256^3, 2.10 at 512^3).
+
+  python profiles/dump_rate.py --overlap [--sizes 256 512] [--run-steps 24] [--every 24 2] [--rounds 3] [--variants none sync overlap]
+
+measures what a `vtk prim` dump costs the RUN: S steps with no dump, with a synchronous dump every K steps, with an overlapped one
+(OutputSet(overlap=True): device snapshot, background write) -- one process, the variants alternating, medians over the rounds.
+stall per dump = (wall - wall without dumps) / dumps, the wall being the loop's; what finish() then takes (the last file still being
+written, once per run) is reported beside it.  A K runs max(--run-steps, 3 K) steps.
+Also: the step time while a copy or a write is in flight against the step time with none; k_dump_payload (profile scope
+dump_snapshot) against the dump_section scopes of one synchronous dump; the rate of the page-locked copy.  --variants none sync
+is what a checkout without the overlapped route can run: the yardstick for the synchronous figures."""
 import argparse
 import importlib
 import json
@@ -21,8 +31,120 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def overlap_main(a):
+    aa = importlib.import_module("atmospheric-athena_amd")
+    lib = importlib.import_module("atmospheric-athena_amd.lib")
+    O = importlib.import_module("atmospheric-athena_amd.outputs")
+    athinput = importlib.import_module("atmospheric-athena_amd.athinput")
+    import torch
+    res = {"box": torch.cuda.get_device_name(0), "host": os.uname().nodename, "variants": a.variants, "sizes": {}}
+    for n in a.sizes:
+        run = aa.config.load(os.path.join(ROOT, "atmospheric-athena_amd", "decks", "athinput.ioniz_sphere"),
+                             [f"domain1/Nx{d}={n}" for d in (1, 2, 3)], "ioniz_sphere")
+        g = lib.setup_problem(aa.config.slab(run), 0, False)
+        g.host_initial = None
+        g.start()
+        for _ in range(a.steps):
+            g.step()
+        g.sync()
+        d = tempfile.mkdtemp(prefix="dump_rate_", dir=a.tmp)
+        r = {"zones": n ** 3, "run_steps": a.run_steps, "every": {}}
+
+        def one(variant, every):
+            """-> (wall of the loop, seconds finish() then took, dumps, [(step seconds, something in flight at its start)])"""
+            nsteps = max(a.run_steps, 3 * every)
+            par = athinput.ParTable.from_text("<job>\nproblem_id = rate\n")
+            outs = O.OutputSet(par, [], None, d, 0, 1, **({"overlap": True} if variant == "overlap" else {}))
+            steps, dumps = [], 0
+            g.sync()
+            t0 = time.perf_counter()
+            for s in range(nsteps):
+                if variant == "overlap":
+                    outs.poll()
+                if variant != "none" and s % every == 0:
+                    rel = "rate.%04d.vtk" % (dumps % 2)                 # (two names: the disk holds two files, not every dump of the run)
+                    if variant == "sync":
+                        g.write_dump(outs.path(rel), "vtk", True)
+                    else:
+                        assert outs.overlapped_dump(g, rel, "vtk", True)
+                    dumps += 1
+                busy = variant == "overlap" and bool(outs._pending or outs._inflight)
+                t1 = time.perf_counter(); g.step(); steps.append((time.perf_counter() - t1, busy))
+            g.sync()
+            wall = time.perf_counter() - t0
+            if variant == "overlap":
+                outs.finish()
+            tail = time.perf_counter() - t0 - wall
+            for rel in set(outs.written):
+                os.remove(os.path.join(d, rel))
+            return wall, tail, dumps, steps
+
+        for every in a.every:
+            walls = {v: [] for v in a.variants}; busy, idle, tails, ndumps = [], [], [], 0
+            for _ in range(a.rounds):
+                for v in a.variants:
+                    wall, tail, nd, steps = one(v, every)
+                    walls[v].append(wall)
+                    if v == "overlap":
+                        busy += [t for t, b in steps if b]
+                        tails.append(tail)
+                    if v == "none":
+                        idle += [t for t, b in steps]
+                    ndumps = max(ndumps, nd)
+            e = {"dumps": ndumps, "steps": max(a.run_steps, 3 * every), "wall_s": walls, "wall_median_s": {v: statistics.median(w) for v, w in walls.items()}}
+            if "none" in walls:
+                e["step_plain_median_s"] = statistics.median(idle)
+                e["step_plain_min_max_s"] = [min(idle), max(idle)]
+                for v in walls:
+                    if v != "none":
+                        e[f"stall_per_dump_{v}_s"] = (e["wall_median_s"][v] - e["wall_median_s"]["none"]) / ndumps
+            if tails:
+                e["finish_tail_s"] = tails                   # once per run, behind the loop: the last file(s) still being written
+            if busy:
+                e["step_in_flight_median_s"] = statistics.median(busy)
+                e["steps_in_flight"] = len(busy)
+            r["every"][str(every)] = e
+            print(json.dumps({str(n): {str(every): e}}), flush=True)
+        # the kernels: one synchronous dump against one snapshot, by the library's event scopes
+        g.profile_enable(True); g.profile_reset()
+        reps = 5
+        for _ in range(reps):
+            for s in range(g.dump_sections("vtk")):
+                g.dump_section("vtk", True, s)
+        g.sync()
+        prof = g.profile()
+        r["dump_section_scopes_ms_per_dump"] = prof["dump_section"][0] / reps
+        r["dump_section_launches_per_dump"] = prof["dump_section"][1] / reps
+        if "overlap" in a.variants:
+            nbytes = g.dump_snapshot_bytes("vtk")
+            T = []
+            for _ in range(reps):
+                g.sync()
+                t0 = time.perf_counter(); sn = g.dump_snapshot("vtk", True); sn.wait(); T.append(time.perf_counter() - t0); sn.release()
+            g.sync()
+            ms = g.profile()["dump_snapshot"][0] / reps
+            r["dump_snapshot_ms"] = ms
+            r["dump_snapshot_bytes_per_zone"] = 8 * g.nvar + 4 * g.nvar
+            r["dump_snapshot_GBps"] = (8 * g.nvar + 4 * g.nvar) * n ** 3 / (ms * 1e-3) / 1e9
+            r["snapshot_payload_bytes"] = nbytes
+            r["begin_to_ready_s"] = T
+            r["pinned_copy_GBps"] = nbytes / (statistics.median(T) - ms * 1e-3) / 1e9
+        g.profile_enable(False)
+        os.rmdir(d)
+        res["sizes"][str(n)] = r
+        print(json.dumps({str(n): r}), flush=True)
+        g.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--overlap", action="store_true", help="what a dump costs the run: none / synchronous / overlapped (see the module text)")
+    ap.add_argument("--run-steps", type=int, default=24)
+    ap.add_argument("--every", type=int, nargs="+", default=[24, 2], help="a dump every K steps (one K per measurement)")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--variants", nargs="+", default=["none", "sync", "overlap"], choices=["none", "sync", "overlap"])
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--steps", type=int, default=2)
@@ -30,6 +152,8 @@ def main():
     ap.add_argument("--tmp", default=None, help="directory for that file (default: the system's temporary directory)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "out", "dump_rate.json"))
     a = ap.parse_args()
+    if a.overlap:
+        return overlap_main(a)
     aa = importlib.import_module("atmospheric-athena_amd")
     lib = importlib.import_module("atmospheric-athena_amd.lib")
     import torch
