@@ -68,6 +68,10 @@ struct aa_grid {
   // twin, `cap` floats each, made on first use; held: between begin and release; staged / done: "payload made" on st, "on the host" on dump_st
   struct DumpSlot { float *dev = nullptr, *host = nullptr; size_t cap = 0; bool held = false; int fmt = 0; hipEvent_t staged = nullptr, done = nullptr; };
   DumpSlot snap[AA_DUMP_SLOTS];
+  // ... and the slot of aa_rst_snapshot_begin (restart.hip): the whole restart payload, `cap` doubles on either side, made on first use;
+  // staged: "payload made and EdgeFlux copied" on st, done: "on the host" on dump_st
+  struct RstSlot { aa::Real *dev = nullptr, *host = nullptr; size_t cap = 0; bool held = false; hipEvent_t staged = nullptr, done = nullptr; };
+  RstSlot rst_snap[AA_RST_SLOTS];
   bool prof = false;
   std::vector<ProfEntry> pe;
   std::vector<hipEvent_t> ev_pool;     // events of drained scopes, reused (a small Grid's step is ~25 scopes: creating 50 events per step showed)
@@ -168,6 +172,8 @@ int slabs_history(aa_grid *g, double *sums);
 int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
 void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away
 int dump_prepare(aa_grid *g);         // dump.hip: the bounce buffer, its stream and events, made on first use (shared with restart.hip)
+int dump_stream(aa_grid *g);          // dump.hip: the stream of the dumps' copies alone, made on first use (the snapshots need no bounce buffer)
+void rst_snapshot_free(aa_grid *g);   // restart.hip: the restart snapshot's buffers and events (dump_release, behind the wait for dump_st)
 void dump_copy_out(float *dst, const float *src, size_t n);    // dump.hip: bounce buffer <-> the caller's memory on a few threads
 int slabs_rst_section(aa_grid *g, int section, double *host, int put);
 int rst_section_grid(aa_grid *g, int section, double *host, long long n, int put);   // restart.hip: the first n doubles of a section of one Grid

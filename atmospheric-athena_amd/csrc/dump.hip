@@ -186,6 +186,7 @@ static void dump_section_shape(int fmt, int section, int *var, int *ncomp)
 void dump_release(aa_grid *g)
 {
   if (g->dump_st) hipStreamSynchronize(g->dump_st);        // a snapshot in flight: its copy lands before its buffers go
+  rst_snapshot_free(g);
   for (aa_grid::DumpSlot &s : g->snap) {
     if (s.dev) hipFree(s.dev);
     if (s.host) hipHostFree(s.host);
@@ -212,7 +213,7 @@ static size_t dump_capacity(const aa_grid *g)
 }
 
 // the stream of the dumps' copies (the snapshots need it without the bounce buffer)
-static int dump_stream(aa_grid *g)
+int dump_stream(aa_grid *g)
 {
   if (!g->dump_st) HIPCHK(hipStreamCreateWithFlags(&g->dump_st, hipStreamNonBlocking));
   return 0;

@@ -60,6 +60,51 @@ __global__ void __launch_bounds__(256) k_rst_scatter(DevGrid g, Real *__restrict
   }
 }
 
+// ---- the whole payload in one pass (aa_rst_snapshot_begin) ------------------------------------------------------------------
+// where the sections of a Grid begin in a snapshot buffer, in doubles: file order, every section 16-byte aligned
+__host__ __device__ static inline unsigned long long rst_pad2(unsigned long long x) { return (x + 1ull) & ~1ull; }
+
+// two consecutive doubles of a section at once (p 16-byte aligned).  Non-temporal: nothing on the device reads the snapshot back
+// but the copy engine; measured against plain stores in DESIGN.md section 8
+__device__ __forceinline__ void rst_store2(Real *p, Real a, Real b)
+{
+  typedef double rst_v2d __attribute__((ext_vector_type(2)));
+  rst_v2d v = {a, b};
+  __builtin_nontemporal_store(v, (rst_v2d*)p);
+}
+
+// Every section of the n active zones that is not EDGEFLUX -- d, M1, M2, M3, E at f*S, scalar s at scal0 + s*S doubles -- to the
+// snapshot buffer dst.  Thread t owns the doubles o = 2t, 2t + 1 of the flat index o = (k*Nx2 + j)*Nx1 + i (a row may end between
+// them: odd Nx1): it computes either zone's address once, loads every field of both (unconditionally: past the end the last zone
+// again) and stores one 16-byte pair per section; only the thread that holds the end of a Grid with odd n stores one word.
+// Zone indices fit 32 bits (the caller refuses the rest), section offsets are 64 bits.  No LDS, no scratch.
+template <int NS>
+__global__ void __launch_bounds__(256) k_rst_payload(DevGrid g, unsigned n, unsigned long long S, unsigned long long scal0,
+                                                     Real *__restrict__ dst)
+{
+  const unsigned long long t = (unsigned long long)blockIdx.x*256ull + threadIdx.x;
+  if (2ull*t >= (unsigned long long)n) return;
+  const unsigned o0 = 2u*(unsigned)t;
+  const unsigned nx1 = (unsigned)g.Nx1, nx2 = (unsigned)g.Nx2;
+  Real v[2][5 + NS];
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    const unsigned o = (o0 + q < n) ? o0 + q : n - 1u;      // (n <= 2^32 - 2: no wrap)
+    const unsigned r = o/nx1, i = o - r*nx1;
+    const unsigned k = r/nx2, j = r - k*nx2;
+    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
+#pragma unroll
+    for (int f = 0; f < 5 + NS; f++) v[q][f] = g.U[(long)f*g.nc + m];
+  }
+  const bool pair = o0 + 1u < n;
+#pragma unroll
+  for (int f = 0; f < 5 + NS; f++) {
+    Real *s = dst + (f < 5 ? (unsigned long long)f*S : scal0 + (unsigned long long)(f - 5)*S) + o0;
+    if (pair) rst_store2(s, v[0][f], v[1][f]);
+    else s[0] = v[0][f];
+  }
+}
+
 static int rst_nsections(const aa_grid *g) { return 5 + (g->p.ion ? 1 : 0) + g->p.nscal; }
 static bool rst_is_edgeflux(const aa_grid *g, int s) { return g->p.ion && s == 5; }
 // the field of DevGrid.U behind a section that is not EDGEFLUX
@@ -70,6 +115,26 @@ static long long rst_doubles(const aa_grid *g, int s)
   const int *nx = g->p.Nx;
   if (rst_is_edgeflux(g, s)) return (long long)(nx[0] + 1)*(nx[1] + 1)*(nx[2] + 1);
   return (long long)nx[0]*nx[1]*nx[2];
+}
+
+// where section s begins in a snapshot buffer, in doubles (s = rst_nsections: where the payload ends): the sections one after the
+// other in file order, each start rounded up to 2 doubles
+static unsigned long long rst_snapshot_offset(const aa_grid *g, int s)
+{
+  unsigned long long off = 0;
+  for (int q = 0; q < s; q++) off += rst_pad2((unsigned long long)rst_doubles(g, q));
+  return off;
+}
+
+void rst_snapshot_free(aa_grid *g)
+{
+  for (aa_grid::RstSlot &s : g->rst_snap) {
+    if (s.dev) hipFree(s.dev);
+    if (s.host) hipHostFree(s.host);
+    if (s.staged) hipEventDestroy(s.staged);
+    if (s.done) hipEventDestroy(s.done);
+    s = aa_grid::RstSlot();
+  }
 }
 
 // one Grid on one device (the current one); `n` doubles of the section from its start (a slab's share of EDGEFLUX may leave
@@ -309,6 +374,115 @@ int aa_rst_section_get_box(aa_grid *g, int section, const int lo[3], const int n
 
 int aa_rst_section_put_box(aa_grid *g, int section, const int lo[3], const int n[3], const double *host)
 { return rst_box_call("aa_rst_section_put_box", g, section, lo, n, const_cast<double*>(host), 1); }
+
+// ---- snapshots: the whole payload made by one kernel and one device copy, brought to the host beside the run (see athena_amd.h).
+// The route of aa_dump_snapshot_* (dump.hip) on the same stream of copies; one slot, in doubles.
+long long aa_rst_snapshot_bytes(const aa_grid *g)
+{
+  if (!g) return 0;
+  return (long long)(rst_snapshot_offset(g, rst_nsections(g))*sizeof(Real));      // (where a section past the last would begin)
+}
+
+#define RST_SLOT(fn) \
+  if (!g) return aa_fail(-1, "[" fn "]: null argument"); \
+  if (slot < 0 || slot >= AA_RST_SLOTS) return aa_fail(-1, "[" fn "]: slot %d of %d", slot, AA_RST_SLOTS); \
+  aa_grid::RstSlot &s = g->rst_snap[slot]
+
+int aa_rst_snapshot_begin(aa_grid *g, int slot, long long max_bytes)
+{
+  RST_SLOT("aa_rst_snapshot_begin");
+  if (g->link || !g->slab.empty())
+    return aa_fail(-1, "[aa_rst_snapshot_begin]: a Grid cut into slabs takes no snapshot: the synchronous aa_rst_section_get is the path there");
+  if (s.held) return aa_fail(-1, "[aa_rst_snapshot_begin]: slot %d is still held (aa_rst_snapshot_release frees it)", slot);
+  const unsigned long long n = (unsigned long long)rst_doubles(g, 0);
+  if (n > 0xfffffffdull) return aa_fail(-1, "[aa_rst_snapshot_begin]: %llu zones (the kernel indexes zones with 32 bits)", n);
+  const long long bytes = aa_rst_snapshot_bytes(g);
+  if (bytes > max_bytes)
+    return aa_fail(-1, "[aa_rst_snapshot_begin]: a payload of %lld bytes, max_bytes = %lld", bytes, max_bytes);
+  { int rc = dump_stream(g); if (rc) return rc; }
+  if (!s.dev) {                    // first use; kept until aa_destroy
+    const size_t cap = (size_t)bytes/sizeof(Real);
+    Real *dev = nullptr, *host = nullptr;
+    HIPCHK(hipMalloc((void**)&dev, cap*sizeof(Real)));
+    if (hipHostMalloc((void**)&host, cap*sizeof(Real)) != hipSuccess) {
+      (void)hipGetLastError(); hipFree(dev);
+      return aa_fail(-2, "[aa_rst_snapshot_begin]: %zu bytes of page-locked memory", cap*sizeof(Real));
+    }
+    // (the padding words between sections are never written by the kernel: defined once, so that the copy moves no stale memory)
+    if (hipMemset(dev, 0, cap*sizeof(Real)) != hipSuccess) { (void)hipGetLastError(); hipFree(dev); hipHostFree(host); return aa_fail(-2, "[aa_rst_snapshot_begin]: hipMemset"); }
+    s.dev = dev; s.host = host; s.cap = cap;
+    g->bytes += (long long)(cap*sizeof(Real));
+    HIPCHK(hipEventCreateWithFlags(&s.staged, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  }
+  // EdgeFlux first: the one-kernel sub-cycle fills it on demand (exactly as aa_rst_section_get asks for it)
+  if (g->p.ion) { int rc = aa_edgeflux_ready(g); if (rc) return rc; }
+  {
+    Scope sc(g, "rst_snapshot");
+    const unsigned blocks = (unsigned)((n + 511ull)/512ull);
+    const unsigned long long S = rst_pad2(n), scal0 = rst_snapshot_offset(g, 5 + (g->p.ion ? 1 : 0));
+    with_ns(g->p.nscal, [&](auto NS) {
+      hipLaunchKernelGGL((k_rst_payload<NS>), dim3(blocks), dim3(256), 0, g->st, (DevGrid)g->d, (unsigned)n, S, scal0, s.dev);
+    });
+  }
+  HIPCHK(hipGetLastError());
+  if (g->p.ion) {                  // dense on the device: one copy into its place in file order
+    Scope sc(g, "rst_snapshot_ef");
+    HIPCHK(hipMemcpyAsync(s.dev + rst_snapshot_offset(g, 5), g->d.edgeflux, (size_t)rst_doubles(g, 5)*sizeof(Real),
+                          hipMemcpyDeviceToDevice, g->st));
+  }
+  HIPCHK(hipEventRecord(s.staged, g->st));
+  HIPCHK(hipStreamWaitEvent(g->dump_st, s.staged, 0));
+  HIPCHK(hipMemcpyAsync(s.host, s.dev, (size_t)bytes, hipMemcpyDeviceToHost, g->dump_st));
+  HIPCHK(hipEventRecord(s.done, g->dump_st));
+  s.held = true;
+  return 0;
+}
+
+int aa_rst_snapshot_ready(aa_grid *g, int slot)
+{
+  RST_SLOT("aa_rst_snapshot_ready");
+  if (!s.held) return aa_fail(-1, "[aa_rst_snapshot_ready]: slot %d holds no snapshot", slot);
+  const hipError_t e = hipEventQuery(s.done);
+  if (e == hipSuccess) return 1;
+  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+  return aa_fail(-2, "[aa_rst_snapshot_ready]: HIP error %s", hipGetErrorString(e));
+}
+
+int aa_rst_snapshot_wait(aa_grid *g, int slot)
+{
+  RST_SLOT("aa_rst_snapshot_wait");
+  if (!s.held) return aa_fail(-1, "[aa_rst_snapshot_wait]: slot %d holds no snapshot", slot);
+  HIPCHK(hipEventSynchronize(s.done));
+  return 0;
+}
+
+const double *aa_rst_snapshot_section(aa_grid *g, int slot, int section, long long *ndoubles)
+{
+  if (!g || !ndoubles) { aa_fail(-1, "[aa_rst_snapshot_section]: null argument"); return nullptr; }
+  if (slot < 0 || slot >= AA_RST_SLOTS) { aa_fail(-1, "[aa_rst_snapshot_section]: slot %d of %d", slot, AA_RST_SLOTS); return nullptr; }
+  const aa_grid::RstSlot &s = g->rst_snap[slot];
+  if (!s.held) { aa_fail(-1, "[aa_rst_snapshot_section]: slot %d holds no snapshot", slot); return nullptr; }
+  if (section < 0 || section >= rst_nsections(g)) {
+    aa_fail(-1, "[aa_rst_snapshot_section]: section %d of %d", section, rst_nsections(g)); return nullptr;
+  }
+  if (hipEventQuery(s.done) != hipSuccess) {
+    (void)hipGetLastError();
+    aa_fail(-1, "[aa_rst_snapshot_section]: the payload of slot %d is not on the host yet (aa_rst_snapshot_ready / _wait)", slot);
+    return nullptr;
+  }
+  *ndoubles = rst_doubles(g, section);
+  return s.host + rst_snapshot_offset(g, section);
+}
+
+int aa_rst_snapshot_release(aa_grid *g, int slot)
+{
+  RST_SLOT("aa_rst_snapshot_release");
+  if (!s.held) return 0;
+  HIPCHK(hipEventSynchronize(s.done));
+  s.held = false;
+  return 0;
+}
 
 // main.c:398-451 of a restarted run: the ghost zones and the radiation boundary, and NOT new_dt -- the file's dt is the next step's
 int aa_resume(aa_grid *g)

@@ -146,7 +146,7 @@ class HipEngine:
         self.g.write_dump(path, fmt, prim, time=time, dt=dt)
 
     def dump_source(self):
-        """what takes the snapshots of an overlapped dump (outputs.OutputSet.overlapped_dump): this slab's Grid"""
+        """what takes the snapshots of an overlapped dump (outputs.OutputSet.overlapped_dump / overlapped_restart): this slab's Grid"""
         return self.g
 
     def fofc_counts(self): return self.g.fofc_counts()
@@ -481,7 +481,15 @@ class Driver(_Runner):
     def write_restart(self, out, outputs):
         """dump_restart (restart.c:463-983): this rank's Grid under the parameter table as it stands now."""
         if getattr(outputs, "rst_ngrid", None):
+            if getattr(outputs, "overlap_rst", False):
+                outputs.overlap_fallback("rst_ngrid", "restart dumps cut for other Grids (rst_ngrid) take the boxes of "
+                                         "aa_rst_section_get_box", "overlap_rst")
             return self._write_restart_split(out, outputs)
+        if getattr(outputs, "overlap_rst", False):    # snapshot now, copy and file write beside the next steps -- where the engine has a device
+            src = self.eng.dump_source() if hasattr(self.eng, "dump_source") else None
+            rel = dumps.fname(outputs.basename, 0, 0, out.num, "rst")
+            if outputs.overlapped_restart([src], rel, self.nstep, self.time, self.dt):
+                return
         with self._rst_file(out, outputs) as f:
             if hasattr(self.eng, "write_rst_payload"):    # the sections come from the device in file order (csrc/restart.hip)
                 self.eng.write_rst_payload(f)
@@ -814,12 +822,19 @@ class MeshRun(_Runner):
     def write_restart(self, out, outputs):
         """one file for all levels (restart.c:531-770), the sections of every level from the device in file order"""
         if getattr(outputs, "rst_mesh_ngrid", None):
+            if getattr(outputs, "overlap_rst", False):
+                outputs.overlap_fallback("rst_ngrid", "restart dumps cut for other Grids (rst_mesh_ngrid) take the boxes of "
+                                         "aa_rst_section_get_box", "overlap_rst")
             if getattr(self.mesh, "cuts", None) is not None:
                 raise ValueError("[dump_restart]: rst_mesh_ngrid on a Mesh cut into slabs inside the library: its level handles "
                                  "hand out whole sections only")
             lev = self.mesh.lev
             return self._write_restart_mesh_split(out, outputs, [g.cfg.Nx for g in lev],
                                                   lambda n, f, lo, nx: lev[n].write_rst_box_payload(f, lo, nx))
+        if getattr(outputs, "overlap_rst", False):    # one job with the snapshot of every level, root first
+            rel = dumps.fname(outputs.basename, 0, 0, out.num, "rst")
+            if outputs.overlapped_restart(list(self.mesh.lev), rel, self.nstep, self.time, self.dt):
+                return
         with self._rst_file(out, outputs) as f:
             for g in self.mesh.lev:
                 g.write_rst_payload(f)
@@ -1050,6 +1065,9 @@ class MeshDriver(_Runner):
     def write_restart(self, out, outputs):
         """dump_restart (restart.c:463-983): ONE file per rank -- the parameter table as it stands now, then the sections of
         every Grid this rank holds, root first (:531-770)."""
+        if getattr(outputs, "overlap_rst", False):
+            outputs.overlap_fallback("MeshDriver", "overlapped restart dumps are not built for a refined mesh over several ranks "
+                                     "(MeshDriver)", "overlap_rst")
         if getattr(outputs, "rst_mesh_ngrid", None):
             return self._write_restart_split(out, outputs)
         with self._rst_file(out, outputs) as f:

@@ -122,14 +122,17 @@ def dump_head(fmt, *, nx, minx, dx, time: float, dt: float, gamma: float, prim: 
     raise ValueError(f"[write_dump]: format {fmt!r} (vtk or bin)")
 
 
-def write_sections(path: str, header: bytes, titles: Sequence[bytes], section: Callable[[int], np.ndarray]) -> None:
-    """header | title 0 | section(0) | title 1 | section(1) ...: the one place that lays a dump file out"""
+def write_sections(path: str, header: bytes, titles: Sequence[bytes], section: Callable[[int], np.ndarray],
+                   trailer: bytes = b"") -> None:
+    """header | title 0 | section(0) | title 1 | section(1) ... | trailer: the one place that lays a dump file out"""
     with open(path, "wb") as f:
         f.write(header)
         for i, title in enumerate(titles):
             if title:
                 f.write(title)
             f.write(_raw(section(i)))
+        if trailer:
+            f.write(trailer)
 
 
 def write_vtk(path: str, section: Callable[[int], np.ndarray], *, nx, minx, dx, time: float, prim: bool, nscal: int,
@@ -171,7 +174,8 @@ class OverlapWriter:
     library, HIP or torch.  Whatever has to happen on the driving thread when a file is complete (giving the snapshot's slot
     back) is the job's ``on_done``, which `poll`, `wait` and `finish` run on THEIR caller's thread.
 
-    A job is (path, header bytes, section titles, section arrays, on_done).  The worker writes ``path + ".part"`` and renames it
+    A job is (path, header bytes, section titles, section arrays, on_done[, trailer bytes: what stands behind the last section --
+    a restart dump's USER_DATA label]).  The worker writes ``path + ".part"`` and renames it
     onto `path` when the file is complete: a file under its final name is always whole.  Jobs are written in the order of
     `submit`, so of two jobs for the same path the later one stays.  An exception of the worker is kept (the first one, until it
     has been raised; the job's on_done still runs, the jobs behind it are tried all the same), and the next `poll` / `wait` or
@@ -187,11 +191,12 @@ class OverlapWriter:
         self._thread = None
         self._stop = False
 
-    def submit(self, path: str, header: bytes, titles: Sequence[bytes], sections: Sequence[np.ndarray], on_done=None) -> int:
+    def submit(self, path: str, header: bytes, titles: Sequence[bytes], sections: Sequence[np.ndarray], on_done=None,
+               trailer: bytes = b"") -> int:
         """-> the job's ticket (for `wait`)"""
         with self._cv:
             self._submitted += 1
-            self._jobs.append((self._submitted, path, header, list(titles), list(sections), on_done))
+            self._jobs.append((self._submitted, path, header, list(titles), list(sections), on_done, bytes(trailer)))
             if self._thread is None:
                 self._stop = False
                 self._thread = threading.Thread(target=self._work, name="dump-writer", daemon=True)
@@ -206,10 +211,10 @@ class OverlapWriter:
                     self._cv.wait()
                 if not self._jobs:
                     return
-                ticket, path, header, titles, sections, on_done = self._jobs.popleft()
+                ticket, path, header, titles, sections, on_done, trailer = self._jobs.popleft()
             err = None
             try:
-                write_sections(path + ".part", header, titles, lambda i: sections[i])
+                write_sections(path + ".part", header, titles, lambda i: sections[i], trailer)
                 os.replace(path + ".part", path)
             except BaseException as e:           # kept for the driving thread
                 err = e

@@ -134,6 +134,9 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_rst_sections": (I, [P]), "aa_rst_section_label": (I, [P, I, C.c_char_p, I]), "aa_rst_section_doubles": (LL, [P, I]),
         "aa_rst_section_get": (I, [P, I, dp]), "aa_rst_section_put": (I, [P, I, dp]),
         "aa_rst_section_get_box": (I, [P, I, ip, ip, dp]), "aa_rst_section_put_box": (I, [P, I, ip, ip, dp]),
+        "aa_rst_snapshot_bytes": (LL, [P]), "aa_rst_snapshot_begin": (I, [P, I, LL]),
+        "aa_rst_snapshot_ready": (I, [P, I]), "aa_rst_snapshot_wait": (I, [P, I]),
+        "aa_rst_snapshot_section": (C.c_void_p, [P, I, I, llp]), "aa_rst_snapshot_release": (I, [P, I]),
         "aa_resume": (I, [P]), "aa_mesh_resume": (I, [P]),
         "aa_profile_enable": (I, [P, I]), "aa_profile_reset": (I, [P]), "aa_profile_count": (I, [P]),
         "aa_profile_name": (C.c_char_p, [P, I]), "aa_profile_get": (I, [P, I, dp, llp]),
@@ -240,6 +243,58 @@ class Snapshot:
             g._chk(g.L.aa_dump_snapshot_release(g._h, self.slot))
 
 
+class RstSnapshot:
+    """The slot of a Grid's restart snapshot between aa_rst_snapshot_begin and _release (Grid.rst_snapshot makes it): the
+    double-precision payload of a restart dump.  The threading rule is Snapshot's: every method from the thread that drives the
+    run; the arrays of `sections` are plain page-locked host memory, which any thread may read until `release`."""
+
+    RST_SLOTS = 1                        # AA_RST_SLOTS
+
+    def __init__(self, grid: "Grid", slot: int):
+        self._g, self.slot = grid, slot
+        self.labels = [label for label, _ in grid.rst_sections()]
+        self.nsections = len(self.labels)
+
+    def _grid(self) -> "Grid":
+        if self._g is None:
+            raise AthenaError("[RstSnapshot]: released, or its Grid is closed")
+        return self._g
+
+    def ready(self) -> bool:
+        """whether the payload is on the host: one event query, never blocks"""
+        g = self._grid()
+        rc = g.L.aa_rst_snapshot_ready(g._h, self.slot)
+        if rc < 0:
+            g._chk(rc)
+        return rc == 1
+
+    def wait(self) -> "RstSnapshot":
+        g = self._grid(); g._chk(g.L.aa_rst_snapshot_wait(g._h, self.slot)); return self
+
+    def section(self, i: int) -> np.ndarray:
+        """section i of the payload: a float64 view of the page-locked buffer, no copy (what Grid.rst_section returns, bit for
+        bit); valid until release"""
+        g = self._grid()
+        n = C.c_longlong()
+        p = g.L.aa_rst_snapshot_section(g._h, self.slot, int(i), C.byref(n))
+        if not p:
+            raise AthenaError(g.L.aa_last_error().decode() or "[aa_rst_snapshot_section]")
+        a = np.ctypeslib.as_array((C.c_double * n.value).from_address(p))
+        a.flags.writeable = False
+        return a
+
+    def sections(self) -> list:
+        """[(label, float64 array over the page-locked buffer)] in file order"""
+        return [(label, self.section(i)) for i, label in enumerate(self.labels)]
+
+    def release(self) -> None:
+        """frees the slot (waits first if the copy is still in flight); the arrays of `sections` are dead afterwards"""
+        g, self._g = self._g, None
+        if g is not None and g._h is not None:
+            g._rst_snaps[self.slot] = None
+            g._chk(g.L.aa_rst_snapshot_release(g._h, self.slot))
+
+
 class Grid:
     """Device-resident Grid.  Method names follow the reference's call sites."""
 
@@ -271,7 +326,8 @@ class Grid:
 
     def close(self):
         if self._h is not None:
-            for s in getattr(self, "_snaps", ()):      # (aa_destroy waits for a snapshot in flight; its memory goes with the Grid)
+            # (aa_destroy waits for a snapshot in flight; its memory goes with the Grid)
+            for s in list(getattr(self, "_snaps", ())) + list(getattr(self, "_rst_snaps", ())):
                 if s is not None:
                     s._g = None
             self.L.aa_destroy(self._h); self._h = None
@@ -551,6 +607,26 @@ class Grid:
         self._chk(self.L.aa_rst_section_get(self._h, s, _dp(out)))
         return out
 
+    # ---- the restart payload beside the run: one kernel, one copy, ONE slot (csrc/restart.hip aa_rst_snapshot_*) ---------------
+    RST_SLOTS = 1                        # AA_RST_SLOTS
+
+    def rst_snapshot_bytes(self) -> int:
+        """of the restart payload with its padding: what the slot's device buffer and its page-locked twin each take"""
+        return int(self.L.aa_rst_snapshot_bytes(self._h))
+
+    def rst_snapshot(self, max_bytes: int = 8 << 30) -> "RstSnapshot":
+        """The restart payload of the state as it is now -- every section of rst_sections() -- on its way to page-locked host
+        memory while the run goes on (k_rst_payload and the EdgeFlux copy queued behind what the step launched, one copy beside
+        what comes next, nothing waits; the face-state area and the sweeps of integrate_begin are left alone).  One slot: while
+        it is held the library refuses (AthenaError) -- release it.  The threading rule is dump_snapshot's."""
+        if not hasattr(self, "_rst_snaps"):
+            self._rst_snaps = [None] * self.RST_SLOTS      # the RstSnapshots that hold this Grid's slots
+        free = [i for i, s in enumerate(self._rst_snaps) if s is None]
+        slot = free[0] if free else 0                    # (none free: the library names the refusal)
+        self._chk(self.L.aa_rst_snapshot_begin(self._h, slot, int(max_bytes)))
+        s = self._rst_snaps[slot] = RstSnapshot(self, slot)
+        return s
+
     def put_rst_section(self, s: int, arr: np.ndarray):
         """The inverse of rst_section: writes the active zones on the device and no ghost zone."""
         n = int(self.L.aa_rst_section_doubles(self._h, s))
@@ -798,6 +874,12 @@ class Mesh:
         self._chk(self.L.aa_mesh_set_state(self._h, time, dt, nstep))
         for g in self.lev:
             g.set_mesh_state(time, dt, nstep)
+
+    # ---- restart snapshots, per level (lib.Grid.rst_snapshot of self.lev[l]; driver.MeshRun hands outputs.overlapped_restart the levels)
+    RST_SLOTS = RstSnapshot.RST_SLOTS
+
+    def rst_snapshot_bytes(self, l: int) -> int: return self.lev[l].rst_snapshot_bytes()
+    def rst_snapshot(self, l: int, max_bytes: int = 8 << 30) -> "RstSnapshot": return self.lev[l].rst_snapshot(max_bytes)
 
     def domain_numbers(self):
         """(level, domain) of every Grid in self.lev: Domains of a level are numbered in deck order (MeshS.Domain[nl][nd])."""

@@ -19,11 +19,14 @@ Grids; the history of a Domain goes out once, under rank 0's directory.
 ``OutputSet(..., overlap=True)`` writes the ``vtk`` / ``bin`` dumps of targets that have the route beside the run
 (``overlapped_dump``: a device snapshot taken when the block fires, its copy to page-locked memory next to the following steps,
 the file written by the thread of dumps.OverlapWriter); the files and ``written`` are those of the synchronous run.  One rule:
-only the thread that drives the run calls the library -- ``poll`` and ``finish`` belong to it.
+only the thread that drives the run calls the library -- ``poll`` and ``finish`` belong to it.  ``overlap_rst=True`` -- a switch
+of its own -- does the same for the restart dump (``overlapped_restart``: the double-precision payload of every Grid from ONE
+snapshot slot per Grid, the file behind the vtk / bin files already queued).
 """
 from __future__ import annotations
 
 import collections
+import io
 import os
 import warnings
 from dataclasses import dataclass
@@ -56,12 +59,15 @@ class Output:
 
 class OutputSet:
     def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int,
-                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False, overlap_max_bytes: int = 8 << 30):
+                 rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False, overlap_max_bytes: int = 8 << 30,
+                 overlap_rst: bool = False):
         """overlap = True: vtk / bin dumps of targets that have the route (see `overlapped_dump`) are written beside the run;
         overlap_max_bytes: the largest payload that may take it (each Grid that dumps keeps two device buffers and two
-        page-locked buffers of its payload's size)."""
+        page-locked buffers of its payload's size).  overlap_rst = True, independent of `overlap`: the restart dump too (see
+        `overlapped_restart`; one device buffer and one page-locked buffer of the restart payload per Grid, under the same cap)."""
         self.par, self.outs, self.rst = par, outs, rst
         self.overlap, self.overlap_max_bytes = bool(overlap), int(overlap_max_bytes)
+        self.overlap_rst = bool(overlap_rst)
         self._writer = None                   # dumps.OverlapWriter, made by the first overlapped dump
         self._pending = collections.deque()   # snapshots taken whose payload is still on its way: jobs in the order of `written`
         self._inflight = []                   # jobs the writer has, their slots not yet given back
@@ -81,7 +87,7 @@ class OutputSet:
     @classmethod
     def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
                  rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False,
-                 overlap_max_bytes: int = 8 << 30) -> "OutputSet":
+                 overlap_max_bytes: int = 8 << 30, overlap_rst: bool = False) -> "OutputSet":
         """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
         r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
         rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
@@ -144,7 +150,8 @@ class OutputSet:
                 rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
             else:
                 outs.append(o)
-        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes)
+        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes,
+                   overlap_rst)
 
     def data_output(self, target, flag: int) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt
@@ -193,11 +200,12 @@ class OutputSet:
 
 
     # ---- overlapped vtk / bin dumps: device snapshot, background write (dumps.OverlapWriter) -----------------------------------
-    def overlap_fallback(self, kind: str, reason: str) -> None:
-        """a dump of a run with overlap = True takes the synchronous path: said once per kind of reason"""
-        if kind not in self._warned:
-            self._warned.add(kind)
-            warnings.warn(f"[data_output]: overlap = True, but {reason}: these dumps are written synchronously (the same files)")
+    def overlap_fallback(self, kind: str, reason: str, switch: str = "overlap") -> None:
+        """a dump of a run with overlap = True (or overlap_rst = True: `switch`) takes the synchronous path: said once per kind
+        of reason and switch"""
+        if (switch, kind) not in self._warned:
+            self._warned.add((switch, kind))
+            warnings.warn(f"[data_output]: {switch} = True, but {reason}: these dumps are written synchronously (the same files)")
 
     def overlapped_dump(self, source, rel: str, fmt, prim: bool, level=None, domain: int = 0, time=None, dt=None) -> bool:
         """The overlapped route of a target's write_dump for the dump `rel` (relative to this rank's directory) of `source`:
@@ -227,8 +235,8 @@ class OutputSet:
             return False
         from . import dumps
         slots = int(getattr(source, "DUMP_SLOTS", 2))
-        while sum(1 for j in list(self._pending) + self._inflight if j["source"] is source) >= slots:
-            self._wait_oldest(source)
+        while self._held(source, "dump") >= slots:
+            self._wait_oldest(source, "dump")
         snap = source.dump_snapshot(fmt, prim, self.overlap_max_bytes)
         try:
             header, titles = dumps.dump_head(fmt, **source.dump_geometry(prim, level, domain, time, dt))
@@ -236,8 +244,68 @@ class OutputSet:
         except BaseException:
             snap.release()
             raise
-        self._pending.append({"source": source, "snap": snap, "path": path, "header": header, "titles": titles, "ticket": None})
+        self._pending.append({"kind": "dump", "sources": (source,), "snaps": [snap], "path": path, "header": header,
+                              "titles": titles, "trailer": b"", "ticket": None})
         return True
+
+    def overlapped_restart(self, sources, rel: str, nstep: int, time: float, dt: float) -> bool:
+        """The overlapped route of a target's write_restart for the file `rel` holding the Grids `sources`, root first: each
+        something with ``rst_snapshot(max_bytes)`` -> a snapshot (``ready()``, ``wait()``, ``sections()`` -> [(label, float64
+        array)], ``release()``), ``rst_snapshot_bytes()``, ``RST_SLOTS`` and ``composite`` -- lib.Grid.  -> False when the route
+        does not exist here (overlap_rst off; no such source; a Grid cut into slabs; a payload beyond overlap_max_bytes): the
+        caller then writes synchronously, and the first such case of a kind has warned.
+
+        Else everything dump_restart does in front of the payload happens NOW, on this thread: the time and the step count go
+        into the parameter table (restart.c:522-523), the table is serialised with N_STEP / TIME / TIME_STEP into the file's
+        header bytes -- the next data_output changes the table again --, `rel` enters `written`, and every source's snapshot is
+        queued behind what the last step launched.  ONE job holds the snapshots of all sources; it is ready when all are, and it
+        stands behind the vtk / bin jobs already pending: files reach the writer in the order of `written`.  The trailer is
+        restart.write_trailer's.
+
+        A source has RST_SLOTS (one) slot.  While it is held -- the restart dumps come faster than copy and file write take --
+        this call WAITS for that source's oldest restart file to be complete."""
+        if not self.overlap_rst:
+            return False
+        sources = list(sources) if sources is not None else []
+        if not sources or any(s is None or not hasattr(s, "rst_snapshot") for s in sources):
+            self.overlap_fallback("engine", "this engine keeps no state on a device", "overlap_rst")
+            return False
+        if any(getattr(s, "composite", False) for s in sources):
+            self.overlap_fallback("slabs", "a Grid cut into slabs inside the library takes no snapshot (aa_rst_section_get is the "
+                                  "path there)", "overlap_rst")
+            return False
+        nbytes = max(int(s.rst_snapshot_bytes()) for s in sources)
+        if nbytes > self.overlap_max_bytes:
+            self.overlap_fallback("max_bytes", f"a restart payload of {nbytes} bytes is beyond overlap_max_bytes = "
+                                  f"{self.overlap_max_bytes}", "overlap_rst")
+            return False
+        from . import restart
+        for s in sources:
+            while self._held(s, "rst") >= int(getattr(s, "RST_SLOTS", 1)):
+                self._wait_oldest(s, "rst")
+        par = self.par
+        par.blocks.setdefault("time", {})["time"] = "%e" % time
+        par.blocks["time"]["nstep"] = "%d" % nstep
+        head, tail = io.BytesIO(), io.BytesIO()
+        restart.write_header(head, restart.par_dump(par), nstep, time, dt)
+        restart.write_trailer(tail)
+        snaps = []
+        try:
+            for s in sources:
+                snaps.append(s.rst_snapshot(self.overlap_max_bytes))
+            path = self.path(rel)
+        except BaseException:
+            for sn in snaps:
+                sn.release()
+            raise
+        self._pending.append({"kind": "rst", "sources": tuple(sources), "snaps": snaps, "path": path, "header": head.getvalue(),
+                              "titles": None, "trailer": tail.getvalue(), "ticket": None})
+        return True
+
+    def _held(self, source, kind: str) -> int:
+        """slots of `source` that jobs of this kind hold: snapshots on their way and files the writer has"""
+        return sum(1 for j in list(self._pending) + self._inflight
+                   if j["kind"] == kind and any(s is source for s in j["sources"]))
 
     def _submit(self, job) -> None:
         from . import dumps
@@ -247,19 +315,28 @@ class OutputSet:
 
         def on_done(job=job):                     # (run by poll / wait / finish on the driving thread: release calls HIP)
             self._inflight.remove(job)
-            job["snap"].release()
-        job["ticket"] = self._writer.submit(job["path"], job["header"], job["titles"], job["snap"].sections(), on_done)
+            for sn in job["snaps"]:
+                sn.release()
+        if job["kind"] == "rst":                  # every Grid's labelled sections, root first (restart.write_grid_sections' bytes)
+            from . import restart
+            pairs = [p for sn in job["snaps"] for p in sn.sections()]
+            titles, sections = [restart._tag(label) for label, _ in pairs], [a for _, a in pairs]
+        else:
+            titles, sections = job["titles"], job["snaps"][0].sections()
+        job["ticket"] = self._writer.submit(job["path"], job["header"], titles, sections, on_done, job["trailer"])
 
-    def _wait_oldest(self, source) -> None:
-        """blocks until the oldest job of `source` is on disk and its slot free (files are written in the order of `written`:
-        everything taken before it goes to the writer first)"""
-        held = [j for j in self._inflight if j["source"] is source]
+    def _wait_oldest(self, source, kind: str) -> None:
+        """blocks until the oldest job of this kind of `source` is on disk and its slot free (files are written in the order of
+        `written`: everything taken before it goes to the writer first)"""
+        def mine(j): return j["kind"] == kind and any(s is source for s in j["sources"])
+        held = [j for j in self._inflight if mine(j)]
         if not held:
             while self._pending:
                 j = self._pending.popleft()
-                j["snap"].wait()
+                for sn in j["snaps"]:
+                    sn.wait()
                 self._submit(j)
-                if j["source"] is source:
+                if mine(j):
                     held = [j]
                     break
         self._writer.wait(held[0]["ticket"])
@@ -267,7 +344,7 @@ class OutputSet:
     def poll(self) -> None:
         """Never blocks: one event query per pending snapshot (oldest first, up to the first that is still in flight); hands the
         ones on the host to the writer, releases the slots of the files that are complete, re-raises what the writer met."""
-        while self._pending and self._pending[0]["snap"].ready():
+        while self._pending and all(sn.ready() for sn in self._pending[0]["snaps"]):
             self._submit(self._pending.popleft())
         if self._writer is not None:
             self._writer.poll()
@@ -277,8 +354,8 @@ class OutputSet:
         file in `written` is on disk and every slot free.  May be called again."""
         try:
             while self._pending:
-                j = self._pending[0]
-                j["snap"].wait()
+                for sn in self._pending[0]["snaps"]:
+                    sn.wait()
                 self._submit(self._pending.popleft())
         finally:
             if self._writer is not None:

@@ -379,6 +379,34 @@ int       aa_rst_section_put_box(aa_grid *g, int section, const int lo[3], const
 int       aa_resume(aa_grid *g);
 int       aa_mesh_resume(aa_mesh *m);
 
+/* ---- the restart payload without stopping the run -- the route of aa_dump_snapshot_* above, in double precision: ONE kernel makes
+ *      every section but EDGEFLUX from the state as it is when the call is queued (behind everything the step launched), one copy on
+ *      the Grid's stream puts EDGEFLUX beside them (filled first where the one-kernel sub-cycle left that to the reader, as
+ *      aa_rst_section_get does), both into a snapshot buffer in device memory -- not the face-state area --, and one copy on the
+ *      stream of the dumps brings the whole payload into page-locked host memory while the Grid's stream goes on with the next step.
+ *      A Grid has AA_RST_SLOTS = 1 slot: a device buffer and a page-locked buffer of aa_rst_snapshot_bytes(), made on first use and
+ *      kept until aa_destroy (restart blocks fire rarely; at 512^3 with scalar and EdgeFlux the payload is 7.52 GB on either side).
+ *        begin    queues kernel and copies and returns without waiting (allocation on first use apart).  It leaves the face-state
+ *                 area, the sweeps of aa_integrate_begin, new_dt's maxima and the host block's bookkeeping alone: a step between
+ *                 begin and ready is the step it would have been.  max_bytes: the caller's cap on the payload (a larger one is
+ *                 refused before the slot is taken); a held slot is refused too.  Profile scopes: rst_snapshot (the kernel),
+ *                 rst_snapshot_ef (the EDGEFLUX copy).
+ *        ready    1: the payload is on the host, 0: in flight, < 0: error; never blocks.   wait: blocks until it is.
+ *        section  section s (those of aa_rst_sections / aa_rst_section_label) in the page-locked buffer, *ndoubles =
+ *                 aa_rst_section_doubles(); sections start 16-byte aligned, the doubles are those of aa_rst_section_get bit for
+ *                 bit; NULL before the payload is on the host.  The pointer holds until release.
+ *        release  waits if the copy is still in flight and frees the slot for the next begin.
+ *      The threading rule is that of the dump snapshots: every call from the thread that drives the run; another thread may READ the
+ *      memory `section` returned between ready and release, nothing else.  Composite handles (aa_params.nslab > 1) refuse begin:
+ *      aa_rst_section_get is the path there.  aa_destroy with a snapshot in flight waits for it.                              */
+#define AA_RST_SLOTS 1
+long long     aa_rst_snapshot_bytes(const aa_grid *g);                /* payload with its padding */
+int           aa_rst_snapshot_begin(aa_grid *g, int slot, long long max_bytes);
+int           aa_rst_snapshot_ready(aa_grid *g, int slot);
+int           aa_rst_snapshot_wait(aa_grid *g, int slot);
+const double *aa_rst_snapshot_section(aa_grid *g, int slot, int section, long long *ndoubles);  /* NULL before the payload is on the host */
+int           aa_rst_snapshot_release(aa_grid *g, int slot);
+
 /* ---- measurement: per-kernel accumulated device time (hipEvent pairs on the stream) */
 int         aa_profile_enable(aa_grid *g, int on);
 int         aa_profile_reset(aa_grid *g);
