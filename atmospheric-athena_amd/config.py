@@ -31,7 +31,7 @@ PROBLEMS = {
     "ifront": (True, 1),
     "ioniz_sphere": (True, 1),
     "blast": (False, 0),
-    "shkset1d": (False, 0),      # tst/1D-hydro/athinput.sod run as a slab of a 3-D box
+    "shkset1d": (False, 0),      # tst/1D-hydro/athinput.sod: on a 1-D Grid (decks/athinput.sod1d), or as a slab of a 2-D / 3-D box
 }
 
 
@@ -64,7 +64,8 @@ class RunConfig:
 
     @property
     def ndim(self) -> int:
-        """integrate.c:30: the directions of the root Domain with more than one zone (2: Nx3 = 1, the 2-D integrators)"""
+        """integrate.c:30: the directions of the root Domain with more than one zone (2: Nx3 = 1, the 2-D integrators; 1: Nx2 = Nx3 = 1,
+        the 1-D ones)"""
         return sum(1 for n in self.rootNx if n > 1)
 
     @property
@@ -97,7 +98,7 @@ def from_par(par: ParTable, problem: Optional[str] = None) -> RunConfig:
     ion, nscal = PROBLEMS[problem]
     blk = "domain1"
     Nx = tuple(par.geti(blk, f"Nx{d}") for d in (1, 2, 3))
-    # integrate.c:30-84: three directions with more than one zone, or two with Nx3 = 1; 1-D Grids have no path here
+    # integrate.c:30-84: three directions with more than one zone, two with Nx3 = 1, or one with Nx2 = Nx3 = 1
     if min(Nx) < 1:
         raise ParError("[config]: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
     dim = sum(1 for n in Nx if n > 1)
@@ -105,12 +106,13 @@ def from_par(par: ParTable, problem: Optional[str] = None) -> RunConfig:
         raise ParError("[integrate_init]: 2D problem must have Nx1 and Nx2 > 1: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
     if dim == 1 and Nx[0] <= 1:
         raise ParError("[integrate_init]: 1D problem must have Nx1 > 1: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
-    if dim < 2:
-        raise ParError("[config]: 1-D Grids are not supported: Nx1=%d, Nx2=%d, Nx3=%d" % Nx)
-    if dim == 2 and ion:
-        raise ParError(f"[config]: problem \"{problem}\" needs ion radiation, and the reference has ionrad_3d only: not on a 2-D Grid (Nx3 = 1)")
-    if dim == 2 and nscal:
-        raise ParError("[config]: passive scalars on a 2-D Grid (Nx3 = 1): no reference target pins them")
+    if dim == 0:
+        # (integrate.c:30-88 has no text for it: no case of its switch, and neither message behind it, takes dim = 0)
+        raise ParError("[config]: a Domain of a single zone (Nx1=%d, Nx2=%d, Nx3=%d): no integrator takes it; a 1-D run has Nx1 > 1" % Nx)
+    if dim < 3 and ion:
+        raise ParError(f"[config]: problem \"{problem}\" needs ion radiation, and the reference has ionrad_3d only: not on a {dim}-D Grid")
+    if dim < 3 and nscal:
+        raise ParError(f"[config]: passive scalars on a {dim}-D Grid: no reference target pins them")
     xmin = tuple(par.getd(blk, f"x{d}min") for d in (1, 2, 3))
     xmax = tuple(par.getd(blk, f"x{d}max") for d in (1, 2, 3))
     bc = tuple(par.geti_def(blk, k, 0) for k in
@@ -119,7 +121,7 @@ def from_par(par: ParTable, problem: Optional[str] = None) -> RunConfig:
         if b not in (1, 2, 4):
             raise ParError(f"[bvals_init]: bc flag = {b} unknown")       # bvals_mhd.c:586
     cour_no = par.getd("time", "cour_no")
-    if dim == 3 and cour_no > 0.5:                                       # integrate.c:66-68 (2-D: check_2d, by integrator)
+    if dim == 3 and cour_no > 0.5:                                       # integrate.c:66-68 (2-D: check_2d, 1-D: check_1d, by integrator)
         raise ParError("<time>cour_no was set to %g: must be <= 0.5 with 3D integrator" % cour_no)
     cfg = RunConfig(problem=problem, rootNx=Nx, xmin=xmin, xmax=xmax, bc=bc, nscal=nscal, ion=ion,
                     gamma=par.getd("problem", "gamma"), cour_no=cour_no,
@@ -171,18 +173,48 @@ def check_2d(run: RunConfig, nranks: int = 1, mesh: bool = False, nslab: int = 1
         raise ParError(f"[config]: a 2-D Grid (Nx3 = 1) cannot be cut into {nslab} x3 slabs")
 
 
+PROBLEMS_1D = ("blast", "shkset1d")
+
+
+def check_1d(run: RunConfig, nranks: int = 1, mesh: bool = False, nslab: int = 1) -> None:
+    """What a 1-D run (Nx2 = Nx3 = 1) may be: the CTU integrator at any cour_no (integrate.c:38-39), the van Leer integrator up to
+    0.5 (:41-44), second or third order, no first-order flux correction, one Grid on one device, a problem whose generator
+    fills a 1-D block, the shock along x1 -- what the reference's 1-D targets pin."""
+    if run.ndim != 1:
+        return
+    if run.integrator == "vl" and run.cour_no > 0.5:
+        raise ParError("<time>cour_no=%e, must be <= 0.5 with 1D VL integrator" % run.cour_no)
+    if run.rootNx[0] < NGHOST:      # (bvals_mhd.c's boundary functions then read ghost zones, in an order the kernels do not keep)
+        raise ParError("[config]: a 1-D Grid (Nx2 = Nx3 = 1) of %d zones: fewer than the %d ghost zones of a side is not supported" % (run.rootNx[0], NGHOST))
+    if run.fofc:
+        raise ParError("[config]: fofc on a 1-D Grid (Nx2 = Nx3 = 1): no reference target pins it")
+    if run.problem not in PROBLEMS_1D:
+        raise ParError(f"[config]: problem \"{run.problem}\" on a 1-D Grid (Nx2 = Nx3 = 1): have {sorted(PROBLEMS_1D)}")
+    if run.problem == "shkset1d" and int(run.prob.get("shk_dir", 1)) != 1:
+        raise ParError("[config]: shk_dir = %d on a 1-D Grid (Nx2 = Nx3 = 1): the shock runs along x1" % int(run.prob["shk_dir"]))
+    if mesh:
+        raise ParError("[config]: static mesh refinement / MeshDriver on a 1-D Grid (Nx2 = Nx3 = 1) is not supported")
+    if nranks > 1:
+        raise ParError(f"[config]: a 1-D Grid (Nx2 = Nx3 = 1) on {nranks} ranks: it has no x3 to cut and x1 cuts are not supported")
+    if nslab > 1:
+        raise ParError(f"[config]: a 1-D Grid (Nx2 = Nx3 = 1) cannot be cut into {nslab} x3 slabs")
+
+
 def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu", fofc: bool = False) -> RunConfig:
     deck = ParTable.from_file(path)
     ndim_deck = sum(1 for d in (1, 2, 3) if deck.geti("domain1", f"Nx{d}") > 1)
     par = deck.cmdline(overrides)
     Nx = tuple(par.geti("domain1", f"Nx{d}") for d in (1, 2, 3))
     # A deck is written for its number of dimensions (the x3 extent and boundary flags, cour_no -- 0.8 in the reference's 2-D
-    # decks, at most 0.5 in its 3-D ones --, the output blocks): overrides may resize it, not turn a 3-D deck into a 2-D run or
-    # back.  A 2-D run takes a deck with Nx3 = 1 (decks/athinput.blast2d, decks/athinput.shkset2d, or a reference deck of tst/2D-hydro).
+    # decks, at most 0.5 in its 3-D ones --, the output blocks): overrides may resize it, not turn a deck of one dimension into a
+    # run of another.  A 2-D run takes a deck with Nx3 = 1 (decks/athinput.blast2d, decks/athinput.shkset2d, or a reference deck of
+    # tst/2D-hydro), a 1-D run one with Nx2 = Nx3 = 1 (decks/athinput.sod1d, decks/athinput.blast1d, or one of tst/1D-hydro).
     ndim = sum(1 for n in Nx if n > 1)
-    if min(Nx) >= 1 and {ndim, ndim_deck} == {2, 3}:      # (every other shape: from_par, with the reference's messages)
-        raise ParError("[config]: the overrides turn a %d-D deck into a %d-D run (Nx1=%d, Nx2=%d, Nx3=%d): a 2-D run takes a deck "
-                       "written with Nx3 = 1 (decks/athinput.blast2d, decks/athinput.shkset2d), a 3-D run one with Nx3 > 1"
+    # (every other shape: from_par, with the reference's messages -- a single direction must be x1, two must be x1 and x2)
+    if min(Nx) >= 1 and ndim != ndim_deck and ndim >= 1 and ndim_deck >= 1 and (ndim != 1 or Nx[0] > 1) and (ndim != 2 or Nx[2] == 1):
+        raise ParError("[config]: the overrides turn a %d-D deck into a %d-D run (Nx1=%d, Nx2=%d, Nx3=%d): a 1-D run takes a deck "
+                       "written with Nx2 = Nx3 = 1 (decks/athinput.sod1d, decks/athinput.blast1d), a 2-D run one with Nx3 = 1 "
+                       "(decks/athinput.blast2d, decks/athinput.shkset2d), a 3-D run one with Nx3 > 1"
                        % ((ndim_deck, ndim) + Nx))
     run = from_par(par, problem)
     if integrator not in ("ctu", "vl", "ctu-noh"):      # ctu-noh: CTU without --enable-h-correction (the reference's configure default)
@@ -191,6 +223,7 @@ def load(path: str, overrides=None, problem: Optional[str] = None, integrator: s
     run.fofc = bool(fofc)
     check_fofc(run)
     check_2d(run)
+    check_1d(run)
     return run
 
 
@@ -204,6 +237,7 @@ def slab(run: RunConfig, rank: int = 0, nranks: int = 1) -> GridConfig:
     if nranks < 1 or not (0 <= rank < nranks):
         raise ParError(f"[config]: bad rank {rank} of {nranks}")
     check_2d(run, nranks)
+    check_1d(run, nranks)
     nx3 = split_cells(run.rootNx[2], nranks)
     if run.ndim == 3 and min(nx3) < NGHOST:
         raise ParError(f"[config]: x3 slabs thinner than nghost={NGHOST} ({run.rootNx[2]}/{nranks})")
@@ -233,6 +267,7 @@ def pencil(run: RunConfig, rank: int, p2: int, p3: int) -> GridConfig:
     if p2 < 1 or p3 < 1 or not (0 <= rank < p2 * p3):
         raise ParError(f"[config]: bad rank {rank} of {p2}x{p3}")
     check_2d(run, p2 * p3)
+    check_1d(run, p2 * p3)
     if p2 == 1:
         return slab(run, rank, p3)
     r2, r3 = rank % p2, rank // p2
@@ -274,6 +309,7 @@ def levels(par: ParTable, run: RunConfig) -> List[GridConfig]:
     touch (:398-418), so every Domain lies in ONE Domain of the level below."""
     nd = par.geti_def("job", "num_domains", 1)
     check_2d(run, mesh=nd > 1)
+    check_1d(run, mesh=nd > 1)
     return _levels(par, run, 3)
 
 

@@ -126,9 +126,30 @@ int aa_create(const aa_params *p, aa_grid **out)
     return fail(-1, "[integrate_init]: 2D problem must have Nx1 and Nx2 > 1: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
   if (dim == 1 && p->Nx[0] <= 1)
     return fail(-1, "[integrate_init]: 1D problem must have Nx1 > 1: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
-  if (dim < 2) return fail(-1, "[aa_create]: 1-D Grids are not supported: Nx1=%d, Nx2=%d, Nx3=%d", p->Nx[0], p->Nx[1], p->Nx[2]);
-  const bool two_d = dim == 2;
-  if (!two_d && p->cour_no > 0.5)   // integrate.c:66-68
+  // (integrate.c:30-88 has no text for dim = 0: no case of its switch, and neither message behind it, takes it)
+  if (dim == 0) return fail(-1, "[aa_create]: a Grid of a single zone (Nx1=%d, Nx2=%d, Nx3=%d): no integrator takes it; a 1-D Grid has Nx1 > 1", p->Nx[0], p->Nx[1], p->Nx[2]);
+  const bool two_d = dim == 2, one_d = dim == 1;
+  if (one_d) {
+    // integrate.c:30 counts the ROOT Domain's directions: a row of a 2-D or 3-D Domain would take that Domain's integrator, and
+    // the library does not cut Domains along x2 (nor 2-D ones at all)
+    if (p->rootNx[1] != 1 || p->rootNx[2] != 1)
+      return fail(-1, "[aa_create]: Nx2 = Nx3 = 1 in a root Domain of %d x %d x %d zones: a 1-D Grid takes a 1-D root Domain",
+                  p->rootNx[0], p->rootNx[1], p->rootNx[2]);
+    // bvals_mhd.c fills the ghost zones of a side one after the other, and one side after the other; with fewer active zones
+    // than ghost zones a boundary function reads ghost zones, and the order decides what it finds.  k_bc and k1d_run fill the
+    // eight ghost zones at once, which is the same thing only where every source is an active zone
+    if (p->Nx[0] < AA_NGHOST)
+      return fail(-1, "[aa_create]: a 1-D Grid of %d zones: fewer than the %d ghost zones of a side is not supported", p->Nx[0], AA_NGHOST);
+    if (p->integrator == 1 && p->cour_no > 0.5)   // integrate.c:41-44; integrate_1d_ctu has no such limit (:38-39)
+      return fail(-1, "<time>cour_no=%e, must be <= 0.5 with 1D VL integrator", p->cour_no);
+    // what no reference target pins on a 1-D Grid is refused
+    if (p->ion) return fail(-1, "[aa_create]: ion radiation on a 1-D Grid: the reference has ionrad_3d only");
+    if (p->nscal != 0) return fail(-1, "[aa_create]: passive scalars on a 1-D Grid: no reference target pins them (NSCALARS must be 0)");
+    if (p->level != 0) return fail(-1, "[aa_create]: a refined level (level %d) as a 1-D Grid: static mesh refinement is not available in 1-D", p->level);
+    const int ns = slabs_wanted(p);
+    if (ns > 1) return fail(-1, "[aa_create]: a 1-D Grid cannot be cut into x3 slabs (nslab / AA_NGPU = %d)", ns);
+  }
+  if (!two_d && !one_d && p->cour_no > 0.5)   // integrate.c:66-68
     return fail(-1, "<time>cour_no was set to %g: must be <= 0.5 with 3D integrator", p->cour_no);
   if (two_d) {
     if (p->integrator == 1 && p->cour_no > 0.5)   // integrate.c:55-57; integrate_2d_ctu has no such limit
@@ -159,8 +180,14 @@ int aa_create(const aa_params *p, aa_grid **out)
   d.N1 = d.Nx1 + 2*AA_NGHOST; d.N2 = d.Nx2 + 2*AA_NGHOST; d.N3 = d.Nx3 + 2*AA_NGHOST;
   d.is = d.js = d.ks = AA_NGHOST;
   d.ie = d.is + d.Nx1 - 1; d.je = d.js + d.Nx2 - 1; d.ke = d.ks + d.Nx3 - 1;
-  g->two_d = two_d;
-  if (two_d) { d.N3 = 1; d.ks = d.ke = 0; }      // init_grid.c:144-174: no ghost zones along a direction with one zone
+  g->two_d = two_d; g->one_d = one_d;
+  if (two_d || one_d) { d.N3 = 1; d.ks = d.ke = 0; }      // init_grid.c:144-174: no ghost zones along a direction with one zone
+  if (one_d) {
+    d.N2 = 1; d.js = d.je = 0;
+    // AA_1D_RESIDENT=0: aa_run_1d steps one launch at a time (k1d_step) instead of many steps in one launch (k1d_run); same bits
+    const char *e = getenv("AA_1D_RESIDENT");
+    g->resident_1d = e ? atoi(e) != 0 : true;
+  }
   // rows padded to a multiple of 16 doubles and every field shifted by 12 doubles: the first active zone of
   // every row (i = 4) then sits on a 128-byte line, and so does every wavefront of the kernels that walk the
   // active zones 64 at a time (-2.9 % of a 512^3 step; AA_PITCH_ALIGN=0: dense rows)
@@ -172,7 +199,7 @@ int aa_create(const aa_params *p, aa_grid **out)
   for (int a = 0; a < 3; a++) {
     rootdx[a] = (p->xmax[a] - p->xmin[a])/(Real)(p->rootNx[a]);   // init_mesh.c:225
     d.dx[a] = rootdx[a]/(Real)(1 << p->level);                    // :245
-    if (two_d && a == 2) d.dx[a] = rootdx[a];                     // :331-337: a direction with one zone keeps the root's extent
+    if ((two_d && a == 2) || (one_d && a >= 1)) d.dx[a] = rootdx[a];                     // :331-337: a direction with one zone keeps the root's extent
   }
   d.Gamma = p->gamma; d.Gamma_1 = p->gamma - 1.0; d.rGamma_1 = 1.0/d.Gamma_1;
   // one pool: U 6 | LR 36 | F 18 | eta 3 | dhalf 1 | phi 4 | ion 5 + sign(1) | edgeflux
@@ -182,12 +209,14 @@ int aa_create(const aa_params *p, aa_grid **out)
   // a 2-D Grid: U 5 | LR 2 x 2 x 5 | F 2 x 5 | eta 2 | edge (hydro2d_kernels.hip), nothing of the 3-D set
   const size_t nedge2 = two_d ? (size_t)5*ntiles_2d(d)*d.N2 : 0;
   if (two_d) n = nc*(5 + 20 + 10 + 2) + nedge2;
+  // a 1-D Grid: U 5 | the second U buffer 5 (hydro1d_kernels.hip; k1d_step writes it, then the two change places), nothing else
+  if (one_d) n = nc*(5 + 5);
   g->ion_fused = p->ion && (p->ion_path ? p->ion_path == 1 : d.cfg.ion_fused);      // (the caller's choice goes before the knob and the size)
   const size_t nrays = (size_t)d.Nx2*d.Nx3;
   if (p->ion) n += nc*6 + nef;
   if (g->ion_fused) n += 2*nc + 2*nrays;
   if (p->order != 0 && p->order != 2 && p->order != 3) { delete g; return fail(-1, "[aa_create]: order %d (2: PLM, 3: PPM)", p->order); }
-  if (p->order == 3) n += nc*18;
+  if (p->order == 3 && !one_d) n += nc*18;      // (the 1-D kernels keep the slopes in LDS)
   g->pool_doubles = n;
   n += 16;
   hipError_t e = hipMalloc(&g->pool, n*sizeof(Real));
@@ -195,12 +224,13 @@ int aa_create(const aa_params *p, aa_grid **out)
   g->bytes = (long long)(n*sizeof(Real));
   hipMemset(g->pool, 0, n*sizeof(Real));
   Real *q = g->pool + (pitch_align ? 12 : 0);
-  if (two_d) { d.U = q; q += 5*nc; d.LR = q; q += 20*nc; d.F = q; q += 10*nc; d.eta = q; q += 2*nc; g->edge2d = q; q += nedge2; }
+  if (one_d) { d.U = q; q += 5*nc; d.LR = q; q += 5*nc; }
+  else if (two_d) { d.U = q; q += 5*nc; d.LR = q; q += 20*nc; d.F = q; q += 10*nc; d.eta = q; q += 2*nc; g->edge2d = q; q += nedge2; }
   else {
   d.U = q; q += 6*nc; d.LR = q; q += 36*nc; d.F = q; q += 18*nc; d.eta = q; q += 5*nc; d.dhalf = q; q += nc;
   d.phi = q; q += 4*nc;
   }
-  if (p->order == 3) { d.slope = q; q += 18*nc; }
+  if (p->order == 3 && !one_d) { d.slope = q; q += 18*nc; }
   if (p->ion) {
     d.ph_rate = q; q += nc; d.kin = q; q += nc; d.vmax = q; q += nc;
     d.e_init = q; q += nc; d.x_init = q; q += nc;
@@ -245,6 +275,14 @@ int aa_create(const aa_params *p, aa_grid **out)
   // (every word of these is written before it is read; zeroed all the same, so that no run ever depends on what a freed
   //  allocation of an earlier Grid left behind)
   (void)hipMemset(g->sc, 0, sizeof(DevScalars));
+  if (one_d) {
+    if (hipHostMalloc(&g->run1d, sizeof(Run1D), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&g->run1d_dev, g->run1d, 0) != hipSuccess) {
+      if (g->run1d) hipHostFree(g->run1d);
+      hipFree(g->pool); hipFree(g->sc); hipHostFree(g->mb); delete g; return fail(-2, "[aa_create]: scalar buffers");
+    }
+    memset(g->run1d, 0, sizeof(Run1D));
+  }
   if (g->ion_part) (void)hipMemset(g->ion_part, 0, (size_t)ion_pass_blocks(d)*sizeof(IonPart));
   if (g->ion_words) (void)hipMemset(g->ion_words, 0, AA_ION_WORDS*sizeof(Real));
   hipStreamCreate(&g->st); g->own_stream = true;
@@ -268,6 +306,7 @@ void aa_destroy(aa_grid *g)
   if (g->pin_mask) hipFree(g->pin_mask);
   if (g->cfl_part) hipFree(g->cfl_part);
   if (g->fofc_list) hipFree(g->fofc_list);
+  if (g->run1d) hipHostFree(g->run1d);
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);
@@ -318,7 +357,7 @@ int aa_download_ghost_zones(aa_grid *g, double *U)
   if (!g->slab.empty()) return slabs_download_cons(g, U);
   // the caller says its active zones are current; the library knows whether any call since the last full transfer wrote active zones
   // (the integrators, the ion step, pinned zones, restriction / flux correction): then the whole block travels
-  if (g->active_dirty) return aa_download_cons(g, U);
+  if (g->active_dirty || g->one_d) return aa_download_cons(g, U);      // (a 1-D block is one row: it travels whole)
   g->inner_swept = false;
   const int nvar = 5 + g->p.nscal, N1 = g->d.N1, N2 = g->d.N2, N3 = g->d.N3, ng = AA_NGHOST;
   const size_t row = (size_t)N1*nvar*sizeof(Real), plane = row*N2;
@@ -400,6 +439,7 @@ int aa_set_static_grav_tables(aa_grid *g, const double *pc, const double *p1, co
 {
   if (!g->slab.empty()) return slabs_set_grav_tables(g, pc, p1, p2, p3);
   if (!pc) { g->grav = false; return 0; }
+  if (g->one_d) return fail(-1, "[aa_set_static_grav_tables]: static gravity on a 1-D Grid: no reference run pins it");
   if (g->two_d) return fail(-1, "[aa_set_static_grav_tables]: static gravity on a 2-D Grid: no reference run pins it (prob/ioniz_sphere.c:113 writes past a 2-D Grid)");
   // host tables are dense [N3][N2][N1]; device rows are sJ apart
   const double *src[4] = {pc, p1, p2, p3};
@@ -414,6 +454,7 @@ int aa_set_static_grav_tables(aa_grid *g, const double *pc, const double *p1, co
 int aa_set_static_grav_pot(aa_grid *g, aa_gravpot_fn fn)
 {
   if (!fn) return aa_set_static_grav_tables(g, nullptr, nullptr, nullptr, nullptr);
+  if (g->one_d) return fail(-1, "[aa_set_static_grav_pot]: static gravity on a 1-D Grid: no reference run pins it");
   if (g->two_d) return fail(-1, "[aa_set_static_grav_pot]: static gravity on a 2-D Grid: no reference run pins it (prob/ioniz_sphere.c:113 writes past a 2-D Grid)");
   // (a Grid cut into slabs evaluates the callback at the positions of the caller's ONE Grid: the slabs then hold
   //  the very numbers the undivided Grid would)
@@ -433,6 +474,7 @@ int aa_set_cooling(aa_grid *g, int kind)
 {
   if (kind != AA_COOL_NONE && kind != AA_COOL_KOYINUT) return fail(-1, "[aa_set_cooling]: kind=%d: only AA_COOL_NONE and AA_COOL_KOYINUT", kind);
   if (kind && g->p.integrator == 1) return fail(-1, "[aa_set_cooling]: the van Leer integrator has no cooling terms in the reference (integrate_3d_vl.c)");
+  if (kind && g->one_d) return fail(-1, "[aa_set_cooling]: cooling on a 1-D Grid: no reference target pins it");
   if (kind && g->two_d) return fail(-1, "[aa_set_cooling]: cooling on a 2-D Grid: no reference target pins it");
   if (!g->slab.empty() || g->link) return slabs_set_cooling(g, kind);
   g->inner_swept = false;
@@ -453,6 +495,7 @@ int aa_set_fofc(aa_grid *g, int on)
 {
   if (!on) { if (g->slab.empty() && !g->link) { g->fofc = false; g->fofc_counts[0] = g->fofc_counts[1] = g->fofc_counts[2] = 0; } return 0; }
   if (!g->slab.empty() || g->link) return fail(-1, "[aa_set_fofc]: not available on a Grid cut into slabs (FixCell's bounds are per Grid; no reference build pins a cut one)");
+  if (g->one_d) return fail(-1, "[aa_set_fofc]: first-order flux correction on a 1-D Grid: no reference target pins it (integrate_3d_vl.c only here)");
   if (g->two_d) return fail(-1, "[aa_set_fofc]: first-order flux correction on a 2-D Grid: no reference target pins it (integrate_3d_vl.c only here)");
   if (g->p.integrator != 1) return fail(-1, "[aa_set_fofc]: the CTU integrator has no first-order flux correction in the reference (integrate_3d_vl.c only)");
   if (g->p.order == 3) return fail(-1, "[aa_set_fofc]: no reference build pins first-order flux correction with third-order reconstruction");
@@ -509,6 +552,7 @@ int aa_apply_pinned_cells(aa_grid *g)
 
 int aa_add_radplane_3d(aa_grid *g, int dir, double flux)
 {
+  if (g->one_d) return fail(-1, "[add_radplane_3d]: ion radiation on a 1-D Grid: the reference has ionrad_3d only");
   if (g->two_d) return fail(-1, "[add_radplane_3d]: ion radiation on a 2-D Grid: the reference has ionrad_3d only");
   if (!g->p.ion) return fail(-1, "[add_radplane_3d]: ion radiation is off");
   // Rays along +x1 (dir = -1) and along +x2 (dir = -2).  The reference has no working behaviour for the others:
@@ -532,6 +576,10 @@ int aa_bvals_mhd(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_bvals_mhd(g);
   Scope s(g, "bvals_mhd");
+  if (g->one_d) {      // bvals_mhd.c:187-193, :542: the x1 pass only
+    launch_bc_dir(g->d, 0, 0, g->p.bc[0], g->p.bc[1], g->st);
+    return 0;
+  }
   if (g->two_d) {      // bvals_mhd.c:170: x1 then x2, so the corners fill; a direction with one zone has no boundary functions
     for (int d = 0; d < 2; d++) launch_bc_dir(g->d, g->p.nscal, d, g->p.bc[2*d], g->p.bc[2*d + 1], g->st);
     return 0;
@@ -546,7 +594,7 @@ int aa_bvals_mhd_side(aa_grid *g, int dir, int side)
 {
   if (dir < 0 || dir > 2 || side < 0 || side > 1) return fail(-1, "[aa_bvals_mhd_side]: dir=%d side=%d", dir, side);
   if (!g->slab.empty()) return slabs_bvals_mhd_side(g, dir, side);
-  if (g->two_d && dir == 2) return 0;      // (no ghost zones along x3)
+  if ((g->two_d && dir == 2) || (g->one_d && dir >= 1)) return 0;      // (no ghost zones along a direction with one zone)
   const int flag = g->p.bc[2*dir + side];
   if (flag) { Scope s(g, "bvals_mhd"); launch_bc(g->d, g->p.nscal, dir, side, flag, g->st); }
   return 0;
@@ -603,7 +651,7 @@ int aa_new_dt_local(aa_grid *g, double *dt_cfl)
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
   double max_dti = 0.0;                   // new_dt.c:159-166
-  const int ndir = g->two_d ? 2 : 3;     // new_dt.c:156-161: only the directions with more than one zone
+  const int ndir = g->one_d ? 1 : g->two_d ? 2 : 3;     // new_dt.c:156-161: only the directions with more than one zone
   for (int d = 0; d < ndir; d++) { double v = bits_to_double(g->sc_host->max_v[d])/g->d.dx[d]; max_dti = (max_dti > v) ? max_dti : v; }
   *dt_cfl = g->p.cour_no/max_dti;
   return 0;
@@ -618,7 +666,8 @@ int aa_cfl_max_v(aa_grid *g, double *v)      // new_dt.c:72-140 of this Grid: ma
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
   for (int d = 0; d < 3; d++) v[d] = bits_to_double(g->sc_host->max_v[d]);
-  if (g->two_d) v[2] = 0.0;              // new_dt.c:135: max_v3 only where Nx3 > 1
+  if (g->two_d || g->one_d) v[2] = 0.0;  // new_dt.c:135: max_v3 only where Nx3 > 1
+  if (g->one_d) v[1] = 0.0;              // :128: max_v2 only where Nx2 > 1
   return 0;
 }
 
@@ -667,7 +716,7 @@ static bool x3_fused(const aa_grid *g)      // default: always (round 3; until t
 static bool x1_fused(const aa_grid *g) { return g->d.cfg.correct_all && x3_fused(g); }
 int aa_integrate_begin(aa_grid *g)
 {
-  if (g->two_d) return 0;
+  if (g->two_d || g->one_d) return 0;
   if (!g->slab.empty() || g->p.integrator != 0 || g->d.slope || !g->d.cfg.correct_all || !g->d.cfg.fused_update || g->inner_swept) return 0;
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
   const int nk = d.ke - d.ks + 1;
@@ -693,6 +742,7 @@ static void no_h_correction(aa_grid *g)
 int aa_integrate_3d_ctu(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_integrate(g, 0);
+  if (g->one_d) return fail(-1, "[aa_integrate_3d_ctu]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_integrate_1d_ctu");
   if (g->two_d) return fail(-1, "[aa_integrate_3d_ctu]: this is a 2-D Grid (Nx3 = 1): aa_integrate_2d_ctu");
   g->cfl_ready = false; g->active_dirty = true;
   const HostGrid &d = g->d; const int ns = g->p.nscal; const Real dt = g->dt;
@@ -809,6 +859,7 @@ static int fofc_finish(aa_grid *g)
 int aa_integrate_3d_vl(aa_grid *g)
 {
   if (!g->slab.empty()) return slabs_integrate(g, 1);
+  if (g->one_d) return fail(-1, "[aa_integrate_3d_vl]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_integrate_1d_vl");
   if (g->two_d) return fail(-1, "[aa_integrate_3d_vl]: this is a 2-D Grid (Nx3 = 1): aa_integrate_2d_vl");
   g->cfl_ready = false; g->active_dirty = true;
   // integrate_3d_vl.c:96-: donor-cell fluxes -> U^{n+1/2} -> PLM or PPM (no tracing) + Roe -> update
@@ -1190,7 +1241,8 @@ int aa_step(aa_grid *g, int *niter_out)
   // (between the integrator and new_dt this loop only pins zones: the integrator may leave new_dt's maxima behind)
   const bool keep_opt = g->cfl_in_update;
   if (g->slab.empty() && g->d.cfg.cfl_step) g->cfl_in_update = true;      // (both builds since round 4: aa_cfl_in_update)
-  if (g->two_d) rc = (g->p.integrator == 1 ? aa_integrate_2d_vl(g) : aa_integrate_2d_ctu(g));     // integrate.c:49-58
+  if (g->one_d) rc = (g->p.integrator == 1 ? aa_integrate_1d_vl(g) : aa_integrate_1d_ctu(g));     // integrate.c:36-47
+  else if (g->two_d) rc = (g->p.integrator == 1 ? aa_integrate_2d_vl(g) : aa_integrate_2d_ctu(g));     // integrate.c:49-58
   else
   rc = (g->p.integrator == 1 ? aa_integrate_3d_vl(g) : aa_integrate_3d_ctu(g));                    // :572-585
   g->cfl_in_update = keep_opt;
@@ -1205,6 +1257,7 @@ int aa_step(aa_grid *g, int *niter_out)
 
 // ---- x3 halo ------------------------------------------------------------------------------
 #define NO_SLABS(name) if (!g->slab.empty()) return fail(-1, "[" name "]: not available on a Grid cut into slabs"); \
+  if (g->one_d) return fail(-1, "[" name "]: not available on a 1-D Grid (one Grid, no halo exchange)"); \
   if (g->two_d) return fail(-1, "[" name "]: not available on a 2-D Grid (one Grid, no halo exchange)")
 long long aa_halo_doubles(const aa_grid *g)      // (a Grid cut into slabs exchanges its halos itself: 0)
 { return g->slab.empty() ? (long long)g->d.N1*g->d.N2*AA_NGHOST*(5 + g->p.nscal) : 0LL; }

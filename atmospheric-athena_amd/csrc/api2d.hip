@@ -21,6 +21,7 @@ static void cfl_arm_2d(aa_grid *g)
 int aa_integrate_2d_ctu(aa_grid *g)
 {
   if (!g) return aa_fail(-1, "[aa_integrate_2d_ctu]: null argument");
+  if (g->one_d) return aa_fail(-1, "[aa_integrate_2d_ctu]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_integrate_1d_ctu");
   if (!g->two_d) return aa_fail(-1, "[aa_integrate_2d_ctu]: this is a 3-D Grid: aa_integrate_3d_ctu");
   if (g->p.integrator == 1) return aa_fail(-1, "[aa_integrate_2d_ctu]: this Grid was created for the van Leer integrator");
   g->cfl_ready = false; g->active_dirty = true;
@@ -39,6 +40,7 @@ int aa_integrate_2d_ctu(aa_grid *g)
 int aa_integrate_2d_vl(aa_grid *g)
 {
   if (!g) return aa_fail(-1, "[aa_integrate_2d_vl]: null argument");
+  if (g->one_d) return aa_fail(-1, "[aa_integrate_2d_vl]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_integrate_1d_vl");
   if (!g->two_d) return aa_fail(-1, "[aa_integrate_2d_vl]: this is a 3-D Grid: aa_integrate_3d_vl");
   if (g->p.integrator != 1) return aa_fail(-1, "[aa_integrate_2d_vl]: this Grid was created for the CTU integrator (its cour_no was checked for that one)");
   g->cfl_ready = false; g->active_dirty = true;

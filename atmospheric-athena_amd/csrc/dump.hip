@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) k_dump_section(DevGrid g, int var, int pr
     const unsigned z = VEC ? o/3u : o, c = VEC ? o - 3u*z : 0u;
     const unsigned r = z/nx1, i = z - r*nx1, row = (unsigned)row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
+    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + (unsigned)g.js)*g.sJ + (long)(i + AA_NGHOST_);
     const unsigned b = __float_as_uint(dump_value(g, VEC ? 1 + (int)c : var, prim, m));
     w[q] = swap ? __builtin_bswap32(b) : b;
   }
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(256) k_dump_payload(DevGrid g, int prim, unsig
     const unsigned z = (z0 + q < n) ? z0 + q : n - 1u;      // (n <= 2^32 - 4: no wrap)
     const unsigned r = z/nx1, i = z - r*nx1;
     const unsigned k = r/nx2, j = r - k*nx2;
-    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
+    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + (unsigned)g.js)*g.sJ + (long)(i + AA_NGHOST_);
     dump_zone<NS>(g, prim, m, VTK ? 1u : 0u, w[q]);
   }
   unsigned *out = (unsigned*)dst;
@@ -205,7 +205,7 @@ void dump_release(aa_grid *g)
 static size_t dump_capacity(const aa_grid *g)
 {
   size_t cap = (size_t)g->d.cfg.dump_chunk;
-  const size_t room = (size_t)(g->two_d ? 20 : 36)*(size_t)g->d.nc;   // LR is 36*nc doubles = 72*nc floats: two slots of 36*nc (a 2-D Grid: 20*nc)
+  const size_t room = (size_t)(g->one_d ? 5 : g->two_d ? 20 : 36)*(size_t)g->d.nc;   // LR is 36*nc doubles = 72*nc floats: two slots of 36*nc (a 2-D Grid: 20*nc, a 1-D Grid: 5*nc)
   const size_t row = (size_t)3*(size_t)g->d.Nx1;
   if (cap > room) cap = room;
   if (cap < row) cap = row;
@@ -336,6 +336,7 @@ int aa_dump_snapshot_begin(aa_grid *g, int slot, int fmt, int prim, long long ma
   if (fmt != AA_DUMP_VTK && fmt != AA_DUMP_BIN) return aa_fail(-1, "[aa_dump_snapshot_begin]: format %d (AA_DUMP_VTK or AA_DUMP_BIN)", fmt);
   if (g->link || !g->slab.empty())
     return aa_fail(-1, "[aa_dump_snapshot_begin]: a Grid cut into slabs takes no snapshot: the synchronous aa_dump_section is the path there");
+  if (g->one_d) return aa_fail(-1, "[aa_dump_snapshot_begin]: a 1-D Grid takes no snapshot: the synchronous aa_dump_section is the path there");
   if (s.held) return aa_fail(-1, "[aa_dump_snapshot_begin]: slot %d is still held (aa_dump_snapshot_release frees it)", slot);
   const unsigned long long n = (unsigned long long)g->p.Nx[0]*g->p.Nx[1]*g->p.Nx[2];
   if (n > 0xfffffffbull) return aa_fail(-1, "[aa_dump_snapshot_begin]: %llu zones (the kernel indexes zones with 32 bits)", n);

@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) k_rst_gather(DevGrid g, const Real *__res
     const unsigned o = (o0 + q < n) ? o0 + q : n - 1u;
     const unsigned t = i0 + o, r = t/nx1, i = t - r*nx1, row = row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    v[q] = src[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)];
+    v[q] = src[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + (unsigned)g.js)*g.sJ + (long)(i + AA_NGHOST_)];
   }
   if (o0 + 1u < n) *(double2*)(dst + o0) = make_double2(v[0], v[1]);
   else dst[o0] = v[0];
@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) k_rst_scatter(DevGrid g, Real *__restrict
     if (q && !pair) break;
     const unsigned t = i0 + o0 + q, r = t/nx1, i = t - r*nx1, row = row0 + r;
     const unsigned k = row/nx2, j = row - k*nx2;
-    dst[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_)] = v[q];
+    dst[(long)(k + (unsigned)g.ks)*g.sK + (long)(j + (unsigned)g.js)*g.sJ + (long)(i + AA_NGHOST_)] = v[q];
   }
 }
 
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) k_rst_payload(DevGrid g, unsigned n, unsi
     const unsigned o = (o0 + q < n) ? o0 + q : n - 1u;      // (n <= 2^32 - 2: no wrap)
     const unsigned r = o/nx1, i = o - r*nx1;
     const unsigned k = r/nx2, j = r - k*nx2;
-    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + AA_NGHOST_)*g.sJ + (long)(i + AA_NGHOST_);
+    const long m = (long)(k + (unsigned)g.ks)*g.sK + (long)(j + (unsigned)g.js)*g.sJ + (long)(i + AA_NGHOST_);
 #pragma unroll
     for (int f = 0; f < 5 + NS; f++) v[q][f] = g.U[(long)f*g.nc + m];
   }
@@ -252,7 +252,7 @@ static int rst_box_grid(aa_grid *g, int section, const int lo[3], const int nb[3
   } else {
     sJ = g->d.sJ; sK = g->d.sK;
     base = g->d.U + (size_t)rst_section_var(g, section)*(size_t)g->d.nc
-         + (long)(lo[2] + g->d.ks)*sK + (long)(lo[1] + AA_NGHOST_)*sJ + (long)(lo[0] + AA_NGHOST_);
+         + (long)(lo[2] + g->d.ks)*sK + (long)(lo[1] + g->d.js)*sJ + (long)(lo[0] + AA_NGHOST_);
   }
   const unsigned n1 = (unsigned)nb[0], n2 = (unsigned)nb[1];
   const long long nrows = (long long)nb[1]*nb[2];
@@ -393,6 +393,7 @@ int aa_rst_snapshot_begin(aa_grid *g, int slot, long long max_bytes)
   RST_SLOT("aa_rst_snapshot_begin");
   if (g->link || !g->slab.empty())
     return aa_fail(-1, "[aa_rst_snapshot_begin]: a Grid cut into slabs takes no snapshot: the synchronous aa_rst_section_get is the path there");
+  if (g->one_d) return aa_fail(-1, "[aa_rst_snapshot_begin]: a 1-D Grid takes no snapshot: the synchronous aa_rst_section_get is the path there");
   if (s.held) return aa_fail(-1, "[aa_rst_snapshot_begin]: slot %d is still held (aa_rst_snapshot_release frees it)", slot);
   const unsigned long long n = (unsigned long long)rst_doubles(g, 0);
   if (n > 0xfffffffdull) return aa_fail(-1, "[aa_rst_snapshot_begin]: %llu zones (the kernel indexes zones with 32 bits)", n);

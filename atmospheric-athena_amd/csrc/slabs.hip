@@ -189,6 +189,7 @@ extern "C" int aa_create_cut(const aa_params *p, int kdisp, int nslab, const int
 {
   if (!p || !out) return aa_fail(-1, "[aa_create_cut]: null argument");
   if (nslab < 1 || nslab > MC_MAXSLAB) return aa_fail(-1, "[aa_create_cut]: %d slabs (1 .. %d)", nslab, MC_MAXSLAB);
+  if (p->Nx[1] <= 1 && p->Nx[2] <= 1) return aa_fail(-1, "[aa_create_cut]: a 1-D Grid (Nx2 = Nx3 = 1) cannot be cut into x3 slabs");
   if (p->Nx[2] <= 1) return aa_fail(-1, "[aa_create_cut]: a 2-D Grid (Nx3 = 1) cannot be cut into x3 slabs");
   if (p->level < 0 || p->level > 7) return aa_fail(-1, "[aa_create_cut]: level %d out of range", p->level);
   if (p->level == 0 && kdisp != 0) return aa_fail(-1, "[aa_create_cut]: the root level has no displacement (kdisp = %d)", kdisp);

@@ -532,6 +532,7 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels, bool two_d = false)
       mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: grids must come level by level from the root (grid %d)", l); return nullptr; }
     if (!g->slab.empty()) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is cut into slabs: not available here (aa_mesh_create takes the levels of a Mesh cut at the root's planes, all made by aa_create_cut)", l); return nullptr; }
     if (g->p.device != levels[0]->p.device) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: all levels must live on one device"); return nullptr; }
+    if (g->one_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is a 1-D Grid: static mesh refinement is not available in 1-D", l); return nullptr; }
     if (two_d) {      // aa_mesh_create_2d: what the reference's 2-D SMR targets (CTU + H-correction, van Leer) pin
       if (!g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] is a 3-D Grid: aa_mesh_create", l); return nullptr; }
       if (g->p.integrator != levels[0]->p.integrator) {

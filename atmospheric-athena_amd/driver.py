@@ -115,6 +115,13 @@ class HipEngine:
     def set_mesh_state(self, time, dt, nstep): self.g.set_mesh_state(time, dt, nstep)
     def has_radiation(self) -> bool: return self.g.has_radplane()      # main.c:546, as aa_step: the ion step runs iff nradplane > 0
     def step_local(self) -> int: return self.g.step()
+
+    def can_batch(self) -> bool:
+        """a 1-D Grid aa_run_1d takes (it fits the resident kernel and has no pinned zones): run_local takes whole stretches of the
+        main loop in one launch; every other Grid steps one launch at a time"""
+        return self.g.can_run_until()
+
+    def run_local(self, t_stop: float, tlim: float, nstep_stop) -> int: return self.g.run_until(t_stop, tlim, nstep_stop)
     def start_local(self): self.g.start()
     def resume_local(self): self.g.resume()
     def write_rst_payload(self, f): self.g.write_rst_payload(f)
@@ -154,10 +161,12 @@ class HipEngine:
 
 
 def _active(U: np.ndarray) -> np.ndarray:
-    """the active zones of a host block [N3][N2][N1][nvar]; a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1)"""
+    """the active zones of a host block [N3][N2][N1][nvar]; a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, a
+    1-D Grid: N2 = N3 = 1)"""
     ng = config.NGHOST
     k = slice(ng, -ng) if U.shape[0] > 1 else slice(None)
-    return U[k, ng:-ng, ng:-ng]
+    j = slice(ng, -ng) if U.shape[1] > 1 else slice(None)
+    return U[k, j, ng:-ng]
 
 
 def _fires(out, level: int, domain: int = 0) -> bool:
@@ -248,6 +257,7 @@ class _Runner:
             raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
         run.integrator, run.order = integrator, order
         config.check_2d(run)
+        config.check_1d(run)
         return head0, par, run
 
     def _read_rank_file(self, head0, nxs, per_level: bool):
@@ -374,6 +384,7 @@ class Driver(_Runner):
             raise ValueError(f"{nranks} ranks cannot be dealt {p2} along x2")
         config.check_fofc(run, nranks)      # (ParError: first-order flux correction is a single-Grid feature)
         config.check_2d(run, nranks)      # (ParError: a 2-D run is one Grid on one rank)
+        config.check_1d(run, nranks)      # (... and so is a 1-D run)
         self.fofc_trace: List[Tuple[int, int, int]] = []    # run.fofc: (zones with d < 0, with P < 0, fluxes replaced) of every step
         self.grid = pencil(run, rank, p2, nranks // p2)
         self.eng = engine_factory(self.grid) if engine_factory else HipEngine(self.grid, device, strict, initial=initial)
@@ -401,6 +412,8 @@ class Driver(_Runner):
         cuts (NGrid_x1 = 1, NGrid_x2 = p2, NGrid_x3 = nranks / p2, no AutoWithNProc), so that a later dump describes itself.
         Single-level meshes only."""
         head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        if regrid and run.ndim == 1:
+            raise restart.RestartError("[restart_grids]: regrid is not built for a 1-D Grid (Nx2 = Nx3 = 1): it is one Grid on one rank")
         run.fofc = bool(fofc)      # (a build option of the reference like the integrator: not in the file; it carries no state between steps)
         sources = restart.scan_sources(path, run.rootNx, run.nscal, run.ion, head0) if regrid else None
         d = cls(run, engine_factory, rank, nranks, device, strict, p2, initial=False)
@@ -703,6 +716,19 @@ class Driver(_Runner):
         self.eng.bvals_ionrad()
         self.new_dt()
 
+    def may_batch(self) -> bool:
+        """whether advance() may take several steps in one call (outputs.run asks): one rank, a 1-D Grid the resident kernel holds"""
+        return not self.distributed and hasattr(self.eng, "can_batch") and self.eng.can_batch()
+
+    def advance(self, t_stop: float, nstep_stop=None) -> int:
+        """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit), in one launch
+        (aa_run_1d; the same bits as that many step() calls).  -> the steps taken"""
+        far = self.nstep + (1 << 20)              # (aa_run_1d covers 2^20 steps per call at the most; the caller's loop goes on)
+        n = self.eng.run_local(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
+        self.time, self.dt, self.nstep = self.eng.mesh_state()
+        self.niter_trace.extend([0] * n)
+        return n
+
     def step(self) -> int:          # main.c:519-669
         if not self.distributed and hasattr(self.eng, "step_local"):
             niter = self.eng.step_local()
@@ -742,6 +768,7 @@ class MeshRun(_Runner):
         """mesh: a lib.Mesh, or the levels (config.levels) to build one from -- with nslab > 1 / cuts every level cut at the
         same root x3 planes inside the library, one slab stack per GPU; the outputs go through the composite level handles
         as they are (hst per level, bin / vtk under lev<l>/, one .rst with all levels)."""
+        config.check_1d(run, mesh=True)      # (ParError: a 1-D run has no Mesh)
         if isinstance(mesh, (list, tuple)):
             from . import lib
             mesh = lib.Mesh(list(mesh), device, strict, nslab=nslab, cuts=cuts)
@@ -960,6 +987,7 @@ class MeshDriver(_Runner):
         self.run, self.rank, self.nranks = run, rank, nranks
         config.check_fofc(run, nranks, mesh=True)
         config.check_2d(run, nranks, mesh=True)
+        config.check_1d(run, nranks, mesh=True)
         self.cfg = config.mesh_slabs(par, run, rank, nranks, cuts)
         self.domains = config.levels(par, run)            # the whole Domain of every level (history: its volume)
         self.level_nx1 = [g.Nx[0] for g in self.domains]  # zones along the rays of every level (x3 slabs keep them)

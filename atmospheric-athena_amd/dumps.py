@@ -79,12 +79,12 @@ def vtk_titles(prim: bool, nscal: int) -> List[bytes]:
 
 def vtk_header(nx: Sequence[int], minx: Sequence[float], dx: Sequence[float], time: float, level: int, domain: int,
                prim: bool) -> bytes:
-    """dump_vtk.c:121-160: DIMENSIONS counts the zone CORNERS (1 along x3 on a 2-D Grid, :147-149), the ORIGIN / SPACING /
-    CELL_DATA lines end in a blank."""
+    """dump_vtk.c:121-160: DIMENSIONS counts the zone CORNERS (1 along x3 on a 2-D Grid, 1 along x2 and x3 on a 1-D Grid, :146-152),
+    the ORIGIN / SPACING / CELL_DATA lines end in a blank."""
     s = "# vtk DataFile Version 2.0\n"
     s += "%s vars at time= %e, level= %i, domain= %i\n" % ("PRIMITIVE" if prim else "CONSERVED", time, level, domain)
     s += "BINARY\nDATASET STRUCTURED_POINTS\n"
-    s += "DIMENSIONS %d %d %d\n" % (nx[0] + 1, nx[1] + 1, nx[2] + 1 if nx[2] > 1 else 1)
+    s += "DIMENSIONS %d %d %d\n" % (nx[0] + 1, nx[1] + 1 if nx[1] > 1 else 1, nx[2] + 1 if nx[2] > 1 and nx[1] > 1 else 1)
     s += "ORIGIN %e %e %e \n" % (minx[0], minx[1], minx[2])
     s += "SPACING %e %e %e \n" % (dx[0], dx[1], dx[2])
     s += "CELL_DATA %d \n" % (nx[0] * nx[1] * nx[2])

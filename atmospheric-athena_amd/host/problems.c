@@ -18,22 +18,25 @@
 #define MAXR(a,b) (((a) > (b)) ? (a) : (b))
 #define MINR(a,b) (((a) < (b)) ? (a) : (b))
 #define SQR(x) ((x)*(x))
-/* ghost zones along x3: none on a 2-D Grid (Nx3 = 1: ks = ke = 0, init_grid.c:144-174) */
+/* ghost zones along x3: none on a 2-D Grid (Nx3 = 1: ks = ke = 0, init_grid.c:144-174); along x2: none on a 1-D Grid (Nx2 = 1:
+ * js = je = 0), whose host block is U[1][1][Nx1 + 8] */
 #define NG3(p) ((p)->Nx[2] > 1 ? NG : 0)
+#define NG2(p) ((p)->Nx[1] > 1 ? NG : 0)
 
 static void centre(const aa_params *p, int i, int j, int k, double x[3])   /* cc_pos.c:36-43 */
 {
   double dx[3]; int d;
   for (d = 0; d < 3; d++) dx[d] = (p->xmax[d] - p->xmin[d])/(double)p->rootNx[d]/(double)(1 << p->level);   /* init_mesh.c:225,245 */
   if (p->Nx[2] == 1) dx[2] = (p->xmax[2] - p->xmin[2])/(double)p->rootNx[2];   /* :331-337: a direction with one zone is not refined */
+  if (p->Nx[1] == 1) dx[1] = (p->xmax[1] - p->xmin[1])/(double)p->rootNx[1];
   x[0] = p->MinX[0] + ((double)(i - NG) + 0.5)*dx[0];
-  x[1] = p->MinX[1] + ((double)(j - NG) + 0.5)*dx[1];
+  x[1] = p->MinX[1] + ((double)(j - NG2(p)) + 0.5)*dx[1];
   x[2] = p->MinX[2] + ((double)(k - NG3(p)) + 0.5)*dx[2];
 }
 
 static double *cell(const aa_params *p, double *U, int i, int j, int k)
 {
-  const int nvar = 5 + p->nscal, N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG;
+  const int nvar = 5 + p->nscal, N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG2(p);
   return U + (((size_t)k*N2 + j)*N1 + i)*nvar;
 }
 
@@ -148,7 +151,7 @@ int aa_problem_blast(const aa_params *p, double radius, double pamb, double damb
   int i, j, k;
   if (p->nscal != 0) return -1;
 #pragma omp parallel for private(i, j)
-  for (k = NG3(p); k < NG3(p) + p->Nx[2]; k++) for (j = NG; j < NG + p->Nx[1]; j++) for (i = NG; i < NG + p->Nx[0]; i++) {
+  for (k = NG3(p); k < NG3(p) + p->Nx[2]; k++) for (j = NG2(p); j < NG2(p) + p->Nx[1]; j++) for (i = NG; i < NG + p->Nx[0]; i++) {
     double *u = cell(p, U, i, j, k), x[3], rad, P, d;
     centre(p, i, j, k, x);
     rad = sqrt(x[0]*x[0] + x[1]*x[1] + x[2]*x[2]);
@@ -164,7 +167,7 @@ int aa_problem_blast(const aa_params *p, double radius, double pamb, double damb
 int aa_problem_shkset1d(const aa_params *p, const double *wl, const double *wr, int shk_dir, double *U)
 {
   const double Gamma_1 = p->gamma - 1.0;
-  const int N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG, N3 = p->Nx[2] + 2*NG3(p);
+  const int N1 = p->Nx[0] + 2*NG, N2 = p->Nx[1] + 2*NG2(p), N3 = p->Nx[2] + 2*NG3(p);
   double c[2][5];
   int i, j, k, side;
   if (p->nscal != 0 || shk_dir < 1 || shk_dir > 3) return -1;

@@ -101,6 +101,8 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_bvals_mhd": (I, [P]), "aa_bvals_mhd_side": (I, [P, I, I]), "aa_bvals_ionrad": (I, [P]), "aa_new_dt": (I, [P]),
         "aa_integrate_3d_ctu": (I, [P]), "aa_integrate_begin": (I, [P]), "aa_cfl_in_update": (I, [P, I]), "aa_integrate_3d_vl": (I, [P]),
         "aa_integrate_2d_ctu": (I, [P]), "aa_integrate_2d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
+        "aa_integrate_1d_ctu": (I, [P]), "aa_integrate_1d_vl": (I, [P]), "aa_run_1d": (I, [P, D, D, I, ip]),
+        "aa_run_1d_cap": (I, []), "aa_step_1d_block": (I, []),
         "aa_start": (I, [P]), "aa_step": (I, [P, ip]),
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
         "aa_ion_update": (I, [P, D, llp, dp]),
@@ -306,9 +308,10 @@ class Grid:
         self.params = params_from_grid(grid, device, ion_path, 1 if cuts is not None else nslab)
         self.nvar = 5 + grid.run.nscal
         self._composite = cuts is not None or nslab > 1
-        # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, init_grid.c:144-174)
+        # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, a 1-D Grid: N2 = N3 = 1; init_grid.c:144-174)
         self.N = tuple(n + 2 * NGHOST if n > 1 else 1 for n in grid.Nx)
         self.ndim = sum(1 for n in grid.Nx if n > 1)
+        self.npin = 0                           # zones pinned by set_pinned_cells (aa_run_1d takes none)
         h = C.c_void_p()
         self._h = None
         if cuts is not None:
@@ -390,6 +393,7 @@ class Grid:
         index = np.ascontiguousarray(index, dtype=np.int64); values = np.ascontiguousarray(values, dtype=np.float64)
         self._chk(self.L.aa_set_pinned_cells(self._h, len(index),
                                              index.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(values)))
+        self.npin = len(index)
 
     def add_radplane_3d(self, dir: int, flux: float): self._chk(self.L.aa_add_radplane_3d(self._h, dir, flux))
     def has_radplane(self) -> bool: return bool(self.L.aa_has_radplane(self._h))
@@ -417,6 +421,8 @@ class Grid:
     def integrate_3d_vl(self): self._chk(self.L.aa_integrate_3d_vl(self._h))
     def integrate_2d_ctu(self): self._chk(self.L.aa_integrate_2d_ctu(self._h))
     def integrate_2d_vl(self): self._chk(self.L.aa_integrate_2d_vl(self._h))
+    def integrate_1d_ctu(self): self._chk(self.L.aa_integrate_1d_ctu(self._h))
+    def integrate_1d_vl(self): self._chk(self.L.aa_integrate_1d_vl(self._h))
     def integrate_begin(self): self._chk(self.L.aa_integrate_begin(self._h))
     def ion_speculate(self, limit: float): self._chk(self.L.aa_ion_speculate(self._h, float(limit)))
     def cfl_in_update(self, on: bool = True): self._chk(self.L.aa_cfl_in_update(self._h, 1 if on else 0))
@@ -424,7 +430,9 @@ class Grid:
     def integrate(self):
         """(*Integrate)(pD): the function pointer integrate_init() selected (integrate.c:63-75)."""
         vl = self.cfg.run.integrator == "vl"
-        if self.ndim == 2:                                      # integrate.c:49-58
+        if self.ndim == 1:                                      # integrate.c:36-47
+            self.integrate_1d_vl() if vl else self.integrate_1d_ctu()
+        elif self.ndim == 2:                                    # :49-58
             self.integrate_2d_vl() if vl else self.integrate_2d_ctu()
         elif vl:
             self.integrate_3d_vl()
@@ -442,6 +450,24 @@ class Grid:
 
     def step(self) -> int:
         n = C.c_int(); self._chk(self.L.aa_step(self._h, C.byref(n))); return n.value
+
+    def run_cap(self) -> int:
+        """most active zones of a 1-D Grid that run_until keeps resident in one workgroup (aa_run_1d_cap)"""
+        return int(self.L.aa_run_1d_cap())
+
+    def can_run_until(self) -> bool:
+        """whether run_until takes this Grid: 1-D, up to run_cap() active zones, no pinned zones -- the refusals of aa_run_1d"""
+        return self.ndim == 1 and self.cfg.Nx[0] <= self.run_cap() and self.npin == 0
+
+    def run_until(self, t_stop: float, tlim: float | None = None, nstep_stop: int | None = None) -> int:
+        """Whole passes of the main loop on a 1-D Grid in ONE launch (aa_run_1d): until time >= t_stop, nstep == nstep_stop or
+        dt <= 0; new_dt clips at tlim (default: the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps
+        taken.  AthenaError on a Grid that is not 1-D, is above run_cap() zones or has pinned zones (can_run_until)."""
+        n = C.c_int()
+        tlim = self.cfg.run.tlim if tlim is None else tlim
+        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
+        self._chk(self.L.aa_run_1d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
+        return n.value
 
     # ---- phases ----------------------------------------------------------------------
     def new_dt_local(self) -> float:

@@ -101,6 +101,8 @@ class OutputSet:
                 raise ValueError("[init_output]: rst_ngrid takes a one-rank run")
             if len(tuple(rst_ngrid)) != 3 or min(int(v) for v in rst_ngrid) < 1:
                 raise ValueError(f"[init_output]: rst_ngrid = {rst_ngrid!r} (three counts >= 1)")
+            if par.geti("domain1", "Nx2") == 1 and par.geti("domain1", "Nx3") == 1:
+                raise ValueError("[init_output]: rst_ngrid is not built for a 1-D Grid (Nx2 = Nx3 = 1): it is one Grid on one rank")
         if rst_mesh_ngrid is None and rst_mesh_nproc is not None:
             raise ValueError("[init_output]: rst_mesh_nproc without rst_mesh_ngrid")
         if rst_mesh_ngrid is not None:
@@ -110,7 +112,7 @@ class OutputSet:
             if nranks > 1:
                 raise ValueError("[init_output]: rst_mesh_ngrid takes a one-rank run")
             if par.geti("domain1", "Nx3") == 1:
-                raise ValueError("[init_output]: rst_mesh_ngrid is not built for a 2-D mesh (Nx3 = 1)")
+                raise ValueError("[init_output]: rst_mesh_ngrid is not built for a 2-D mesh (Nx3 = 1), nor for a 1-D run")
             blocks = restart.domain_blocks(par)
             given = [tuple(g) for g in rst_mesh_ngrid]
             if len(given) != len(blocks) or any(len(g) != 3 or min(int(v) for v in g) < 1 for g in given):
@@ -229,6 +231,9 @@ class OutputSet:
         if getattr(source, "composite", False):
             self.overlap_fallback("slabs", "a Grid cut into slabs inside the library takes no snapshot (aa_dump_section is the path there)")
             return False
+        if getattr(source, "ndim", 3) == 1:
+            self.overlap_fallback("1-D", "a 1-D Grid takes no snapshot (its dumps are a few kilobytes)")
+            return False
         nbytes = int(source.dump_snapshot_bytes(fmt))
         if nbytes > self.overlap_max_bytes:
             self.overlap_fallback("max_bytes", f"a payload of {nbytes} bytes is beyond overlap_max_bytes = {self.overlap_max_bytes}")
@@ -273,6 +278,9 @@ class OutputSet:
         if any(getattr(s, "composite", False) for s in sources):
             self.overlap_fallback("slabs", "a Grid cut into slabs inside the library takes no snapshot (aa_rst_section_get is the "
                                   "path there)", "overlap_rst")
+            return False
+        if any(getattr(s, "ndim", 3) == 1 for s in sources):
+            self.overlap_fallback("1-D", "a 1-D Grid takes no snapshot (its dumps are a few kilobytes)", "overlap_rst")
             return False
         nbytes = max(int(s.rst_snapshot_bytes()) for s in sources)
         if nbytes > self.overlap_max_bytes:
@@ -365,14 +373,23 @@ class OutputSet:
 def run(target, outputs: OutputSet, tlim: float, nlim: int = -1) -> None:
     """main() of the reference around the loop: forced output after the start (main.c:501; a restarted run -- a target with
     ``restarted`` set -- skips it), data_output(0) at the top of every pass (:524), forced output after the loop (:743).
-    `target`: start(), step(), time, nstep and the writers."""
+    `target`: start(), step(), time, nstep and the writers.  A target that also has ``advance(t_stop, nstep_stop)`` and whose
+    ``may_batch()`` says so (driver.Driver on a 1-D Grid) takes every stretch between two output times in ONE call: up to the
+    earliest next time of any block, or tlim.  data_output(0) writes nothing between those times, so the files are the same."""
+    batch = hasattr(target, "advance") and hasattr(target, "may_batch")
     try:
         target.start()
         if not getattr(target, "restarted", False):
             outputs.data_output(target, 1)
         while target.time < tlim and (nlim < 0 or target.nstep < nlim):
             outputs.data_output(target, 0)
-            target.step()
+            done = 0
+            if batch and target.may_batch():      # (asked on every pass: zones pinned since the last one end the batching)
+                t_stop = min([tlim] + [o.t for o in outputs.outs] + ([outputs.rst.t] if outputs.rst is not None else []))
+                if t_stop > target.time:          # (a block whose next time has already passed fires again on the next pass)
+                    done = target.advance(t_stop, nlim if nlim >= 0 else None)
+            if done == 0:                         # ... and a dt that is not positive (or NaN) ends advance() with no step taken:
+                target.step()                     # the single step goes on as the reference does (time = NaN ends the loop)
         outputs.data_output(target, 1)
     finally:
         if hasattr(outputs, "finish"):            # overlapped dumps: every file on disk when main returns

@@ -26,7 +26,8 @@ enum { AA_BC_NONE = 0, AA_BC_REFLECT = 1, AA_BC_OUTFLOW = 2, AA_BC_PERIODIC = 4 
 typedef struct aa_params {
   int    Nx[3];            /* active zones of this Grid: all > 1 (3-D), or Nx[2] == 1 with
                               Nx[0], Nx[1] > 1 (2-D: no ghost zones along x3, host block
-                              U[1][Nx2+8][Nx1+8], init_grid.c:144-174); 1-D Grids are refused     */
+                              U[1][Nx2+8][Nx1+8], init_grid.c:144-174), or Nx[1] == Nx[2] == 1 in a
+                              1-D root Domain (1-D: host block U[1][1][Nx1+8])                   */
   int    rootNx[3];        /* active zones of the root Domain                                   */
   double xmin[3], xmax[3]; /* root Domain extent; dx = (xmax-xmin)/rootNx (init_mesh.c:225)     */
   double MinX[3];          /* lower edge of this Grid (init_grid.c:104-111)                     */
@@ -147,6 +148,22 @@ int aa_integrate_3d_vl(aa_grid *g);                 /* integrate_3d_vl.c:96 (NO_
  * return an error on a 2-D Grid and these on a 3-D one.                                                                        */
 int aa_integrate_2d_ctu(aa_grid *g);                /* integrate_2d_ctu.c (integrator 0: + H-correction, 2: without) */
 int aa_integrate_2d_vl(aa_grid *g);                 /* integrate_2d_vl.c (NO_H_CORRECTION)        */
+/* A 1-D Grid (Nx[1] == Nx[2] == 1 and rootNx[1] == rootNx[2] == 1; integrate.c:36-47): HYDRO, ADIABATIC, second or third order,
+ * no gravity / cooling / scalars / ion radiation / fofc / Mesh / slabs (each refused with a message that says 1-D).  cour_no has
+ * no limit with the CTU integrator and must be <= 0.5 with van Leer (integrate.c:41-44).  Integrators 0 and 2 are the same code:
+ * integrate_1d_ctu.c has no H-correction.  A one-row cut of a 2-D or 3-D root Domain is refused, and so is Nx[0] < 4.                                */
+int aa_integrate_1d_ctu(aa_grid *g);                /* integrate_1d_ctu.c                         */
+int aa_integrate_1d_vl(aa_grid *g);                 /* integrate_1d_vl.c                          */
+/* Many steps of a 1-D Grid in ONE launch (csrc/hydro1d_kernels.hip k1d_run): whole passes of main.c:519-669 -- integrate, nstep++,
+ * time += dt, bvals_mhd, new_dt with the clip at `tlim` (new_dt.c:183-185) -- until time >= t_stop, nstep == nstep_stop (the
+ * Grid's absolute step count; at most 2^20 steps ahead) or dt <= 0.  The Grid must have been started (aa_start / aa_resume).  The
+ * same bits as that many aa_step calls.  *nsteps_done: steps taken.  An error on a Grid that is not 1-D, has more than
+ * aa_run_1d_cap() active zones (one workgroup's LDS), or has pinned zones.  AA_1D_RESIDENT=0 in the environment at aa_create:
+ * the same call steps one launch at a time.                                                                                   */
+int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+int aa_run_1d_cap(void);                            /* most active zones aa_run_1d keeps resident */
+int aa_step_1d_block(void);                         /* TEST HOOK: active zones per block of the per-step kernel (the fixtures'
+                                                       sizes sit either side of it); nothing in the product calls it */
 int aa_ion_radtransfer_3d(aa_grid *g, int *niter);  /* ionrad_3d.c:862; may shrink the Grid dt    */
 int aa_start(aa_grid *g);                           /* main.c:412-451: bvals, bvals_ionrad, new_dt */
 int aa_step(aa_grid *g, int *niter);                /* one pass of main.c:519-669                 */
