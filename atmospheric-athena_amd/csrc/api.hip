@@ -182,6 +182,12 @@ int aa_create(const aa_params *p, aa_grid **out)
   d.ie = d.is + d.Nx1 - 1; d.je = d.js + d.Nx2 - 1; d.ke = d.ks + d.Nx3 - 1;
   g->two_d = two_d; g->one_d = one_d;
   if (two_d || one_d) { d.N3 = 1; d.ks = d.ke = 0; }      // init_grid.c:144-174: no ghost zones along a direction with one zone
+  if (two_d) {
+    // AA_2D_BATCH: steps aa_run_2d queues between two reads of the device clock (1 .. 1024); 0: it loops over aa_step; same bits
+    const char *e = getenv("AA_2D_BATCH");
+    g->batch_2d = e ? atoi(e) : AA_2D_BATCH_DEFAULT;
+    if (g->batch_2d < 0 || g->batch_2d > 1024) { const int v = g->batch_2d; delete g; return fail(-1, "[aa_create]: AA_2D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
+  }
   if (one_d) {
     d.N2 = 1; d.js = d.je = 0;
     // AA_1D_RESIDENT=0: aa_run_1d steps one launch at a time (k1d_step) instead of many steps in one launch (k1d_run); same bits
@@ -307,6 +313,8 @@ void aa_destroy(aa_grid *g)
   if (g->cfl_part) hipFree(g->cfl_part);
   if (g->fofc_list) hipFree(g->fofc_list);
   if (g->run1d) hipHostFree(g->run1d);
+  if (g->run2d) hipHostFree(g->run2d);
+  if (g->run2d_dev) hipFree(g->run2d_dev);
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);

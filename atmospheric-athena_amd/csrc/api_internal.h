@@ -7,6 +7,7 @@
 #include "../../include/athena_amd.h"
 #include "grid.h"
 #include "hydro1d_launch.h"
+#include "hydro2d_launch.h"
 #include "ion_subcycle.h"
 
 int aa_fail(int code, const char *fmt, ...);   // records the message aa_last_error() returns
@@ -45,6 +46,9 @@ struct aa_grid {
   bool one_d = false;                  // Nx2 = Nx3 = 1 in a 1-D root Domain: the 1-D integrators (hydro1d_kernels.hip); U 5 | LR 5 (the second U buffer)
   bool resident_1d = true;             //   ... AA_1D_RESIDENT=0 (read by aa_create): aa_run_1d steps one launch at a time instead of keeping the Grid in one workgroup's LDS (k1d_run)
   aa::Run1D *run1d = nullptr, *run1d_dev = nullptr;   //   ... time, dt, nstep of aa_run_1d: pinned, device-visible host memory and its device address
+  int batch_2d = 0;                    // a 2-D Grid: steps aa_run_2d queues between two reads of the clock (AA_2D_BATCH, read by aa_create; 0: it loops over aa_step)
+  aa::Run2D *run2d_dev = nullptr;      //   ... the clock in device memory and its page-locked mirror (hydro2d_launch.h), made by the first aa_run_2d
+  aa::Run2DMirror *run2d = nullptr, *run2d_map = nullptr;   //   ... (run2d_map: the mirror's device address)
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke
   double inner_dt = 0.0;               //   ... with this dt
   bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): aa_params.ion_path, else LaunchCfg ion_fused; a sweep along x2 turns it off

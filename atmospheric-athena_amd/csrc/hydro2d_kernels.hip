@@ -22,9 +22,14 @@
 // VL : k2d_edge<VL1>, k2d_step<VL1>, k2d_edge<VL2>, k2d_step<VL2>            (2 launches + 2 side kernels)
 // A level of a Mesh (csrc/smr.hip, aa_mesh_create_2d) takes k2d_step_keep<CTU2 | VL2> in place of k2d_step: the same body, which
 // also stores the second-pass fluxes of the faces on the level-boundary lines into F for the flux correction.
+//
+// aa_run_2d (csrc/api2d.hip) queues many steps without the host in between: every kernel above has a second entry point, *_dc, with
+// the same body, which takes dt from the device clock (hydro2d_launch.h Run2D) instead of a kernel argument and returns at once when
+// the clock has stopped; k2d_advance, one wavefront behind the update kernel, does new_dt and the loop's bookkeeping on the device.
 #include <hip/hip_runtime.h>
 #include "grid.h"
 #include "hydro_dev.h"
+#include "hydro2d_launch.h"
 
 namespace aa {
 
@@ -78,8 +83,7 @@ AA_DEV void face_first(const DevGrid &g, const Real wl[6], const Real wr[6], Rea
 
 // ---- CTU, Steps 1 and 2 -------------------------------------------------------------------------------------------------
 // side kernel: the left state of the first x1 face of every tile but the first (the zone below it belongs to the tile before)
-__global__ void __launch_bounds__(64)
-k2d_edge_wl(DevGrid g, Real dt, Real *edge, int ntx)
+AA_DEV void edge_wl_body(const DevGrid &g, Real dt, Real *edge, int ntx)
 {
   const int jl = g.js - 2, nj = g.je - g.js + 5;
   const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
@@ -94,9 +98,12 @@ k2d_edge_wl(DevGrid g, Real dt, Real *edge, int ntx)
   for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = wl[v];
 }
 
+__global__ void __launch_bounds__(64)
+k2d_edge_wl(DevGrid g, Real dt, Real *edge, int ntx)
+{ edge_wl_body(g, dt, edge, ntx); }
+
 // L/R states and first-pass fluxes of the lower x1 and x2 face of every zone of [is-2, ie+2] x [js-2, je+2]
-__global__ void __launch_bounds__(T2_W*T2_R)
-k2d_first(DevGrid g, Real dt, const Real *edge)
+AA_DEV void first_body(const DevGrid &g, Real dt, const Real *edge)
 {
   __shared__ Real sh[5][T2_R][T2_W];
   const int lane = threadIdx.x, ty = threadIdx.y;
@@ -142,6 +149,10 @@ k2d_first(DevGrid g, Real dt, const Real *edge)
   }
 }
 
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_first(DevGrid g, Real dt, const Real *edge)
+{ first_body(g, dt, edge); }
+
 // ---- CTU, Steps 5a, 6a and 9a: transverse flux gradients on the face states, then eta1 / eta2 ----------------------------
 // a -= h*(fp - fm) for the five fields, with the transverse flux's components permuted into this face's frame
 // (x1 faces take (d, Mz, Mx, My, E) of the x2 fluxes, x2 faces (d, My, Mz, Mx, E) of the x1 fluxes)
@@ -153,8 +164,7 @@ AA_DEV void correct_state(Real u[6], Real h, const Real fp[6], const Real fm[6])
   else        { u[1] -= h*(fp[2] - fm[2]); u[2] -= h*(fp[3] - fm[3]); u[3] -= h*(fp[1] - fm[1]); }
   u[4] -= h*(fp[4] - fm[4]);
 }
-__global__ void __launch_bounds__(256)
-k2d_correct(DevGrid g, Real dt, int hcorr)
+AA_DEV void correct_body(const DevGrid &g, Real dt, int hcorr)
 {
   const int il = g.is - 2, iu = g.ie + 2, jl = g.js - 2, ju = g.je + 2;
   const int i = g.is + 64*((int)blockIdx.x - 1) + (int)threadIdx.x;
@@ -196,6 +206,10 @@ k2d_correct(DevGrid g, Real dt, int hcorr)
     }
   }
 }
+
+__global__ void __launch_bounds__(256)
+k2d_correct(DevGrid g, Real dt, int hcorr)
+{ correct_body(g, dt, hcorr); }
 
 // ---- the flux of the lower face of zone (j, i) along D, in the sweep frame, for the three fused update kernels -----------
 enum { M_CTU2 = 0, M_VL1 = 1, M_VL2 = 2 };
@@ -244,8 +258,7 @@ template <int MODE> struct Range2 {
 
 // side kernel: the x1 flux of the face above the last lane of every x1 tile
 template <int MODE>
-__global__ void __launch_bounds__(64)
-k2d_edge(DevGrid g, Real dt, Real *edge, int ntx)
+AA_DEV void edge_body(const DevGrid &g, Real dt, Real *edge, int ntx)
 {
   const int X = Range2<MODE>::ext();
   const int lo_j = g.js - X, nj = g.je - g.js + 1 + 2*X, hi_i = g.ie + X;
@@ -260,6 +273,11 @@ k2d_edge(DevGrid g, Real dt, Real *edge, int ntx)
 #pragma unroll
   for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = f[v];
 }
+
+template <int MODE>
+__global__ void __launch_bounds__(64)
+k2d_edge(DevGrid g, Real dt, Real *edge, int ntx)
+{ edge_body<MODE>(g, dt, edge, ntx); }
 
 // new_dt.c:72-140 for one zone (the operands and their order as in the CFL kernel of the 3-D path; never contracted, so that
 // the maxima are the same bits whichever kernel visits the zone)
@@ -376,6 +394,80 @@ __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step_keep(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc, KeepPlanes kp)
 { step_body<MODE, CFL, true>(g, dt, c1, c2, edge, sc, &kp); }
 
+// ---- the device clock (aa_run_2d; hydro2d_launch.h Run2D) ------------------------------------------------------------------
+// dt/dx and dt/2dx of the update kernels as the launch wrappers below evaluate them on the host for the kernels that take dt as an
+// argument: one IEEE division, one multiplication by 0.5, never contracted with anything around them -- so c1 and c2 are the same
+// bits.  (Every other use of dt -- recon_zone, correct_body -- is evaluated on the device in either form, by the same code.)
+AA_DEV Real dt_over_dx(Real dt, Real dx)
+{
+#pragma clang fp contract(off)
+  return dt/dx;
+}
+AA_DEV Real half_dt_over_dx(Real dt, Real dx)
+{
+#pragma clang fp contract(off)
+  const Real q = dt/dx;
+  return 0.5*q;
+}
+// The *_dc entry points: `live` and dt in one uniform load at the top (the clock is written by k2d_advance / k2d_seed, kernels in
+// front of this one on the same stream, and by nobody while this one runs); a step queued behind the stop returns here, before
+// any store and before any barrier (the whole grid takes the same branch).
+__global__ void __launch_bounds__(64)
+k2d_edge_wl_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
+{ if (!rc->live) return; edge_wl_body(g, rc->dt, edge, ntx); }
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_first_dc(DevGrid g, const Run2D *rc, const Real *edge)
+{ if (!rc->live) return; first_body(g, rc->dt, edge); }
+__global__ void __launch_bounds__(256)
+k2d_correct_dc(DevGrid g, const Run2D *rc, int hcorr)
+{ if (!rc->live) return; correct_body(g, rc->dt, hcorr); }
+template <int MODE>
+__global__ void __launch_bounds__(64)
+k2d_edge_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
+{ if (!rc->live) return; edge_body<MODE>(g, rc->dt, edge, ntx); }
+template <int MODE, bool CFL>
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_step_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc)
+{
+  if (!rc->live) return;
+  const Real dt = rc->dt;
+  const Real c1 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[0]) : dt_over_dx(dt, g.dx[0]);
+  const Real c2 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[1]) : dt_over_dx(dt, g.dx[1]);
+  step_body<MODE, CFL, false>(g, dt, c1, c2, edge, sc, nullptr);
+}
+
+// the clock of a call: what aa_run_2d knows on the host, and the maxima zeroed for the first step's update kernel
+__global__ void __launch_bounds__(64)
+k2d_seed(Run2D *rc, Run2D v, DevScalars *sc)
+{
+  if (threadIdx.x != 0) return;
+  *rc = v;
+  sc->max_v[0] = 0ULL; sc->max_v[1] = 0ULL; sc->max_v[2] = 0ULL;
+}
+// One wavefront behind the update kernel of every step: what aa_step does on the host behind the integrator (main.c:618-629;
+// api.hip aa_step, aa_new_dt_local with ndir = 2, aa_new_dt), with the same operations in the same order, none contracted.  The
+// boundary pass that follows takes no dt.  Launch rule (as k1d_run states it for itself): a plain launch in stream order; nothing
+// here waits for another workgroup or spins on memory, so the launch ends whatever the data are.
+__global__ void __launch_bounds__(64)
+k2d_advance(Run2D *rc, DevScalars *sc, Real dx0, Real dx1, Run2DMirror *out)
+{
+#pragma clang fp contract(off)
+  if (threadIdx.x != 0 || !rc->live) return;
+  const int nstep = rc->nstep + 1;
+  const Real time = rc->time + rc->dt;
+  Real max_dti = 0.0;                                             // new_dt.c:159-166
+  { const Real v = __longlong_as_double((long long)sc->max_v[0])/dx0; max_dti = (max_dti > v) ? max_dti : v; }
+  { const Real v = __longlong_as_double((long long)sc->max_v[1])/dx1; max_dti = (max_dti > v) ? max_dti : v; }
+  const Real dt_cfl = rc->cour_no/max_dti;
+  Real dt = rc->dt;
+  if (nstep == 0) dt = dt_cfl; else dt = (2.0*dt < dt_cfl) ? 2.0*dt : dt_cfl;                  // :169-173
+  if ((time < rc->tlim) && ((rc->tlim - time) < dt)) dt = rc->tlim - time;                     // :183-185
+  sc->max_v[0] = 0ULL; sc->max_v[1] = 0ULL; sc->max_v[2] = 0ULL;                               // for the next step's update kernel
+  const int live = (time >= rc->t_stop || nstep == rc->nstep_stop || !(dt > 0.0)) ? 0 : 1;     // (a NaN dt stops too)
+  rc->time = time; rc->dt = dt; rc->nstep = nstep; rc->live = live;
+  out->time = time; out->dt = dt; out->nstep = nstep; out->live = live;
+}
+
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1)/b); }
 
@@ -419,5 +511,37 @@ void launch_2d_vl_predict(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
 { launch_step<M_VL1, false>(g, dt, 0.5*(dt/g.dx[0]), 0.5*(dt/g.dx[1]), edge, nullptr, st); }
 void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
 { with_flag(sc != nullptr, [&](auto CFL) { launch_step<M_VL2, CFL>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }
+
+// ---- the same chains on the device clock (aa_run_2d): the launch geometry of the wrappers above, dt from `rc` -------------------
+void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st)
+{
+  const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
+  const int nj = g.Nx2 + 4;
+  if (ntx > 1) hipLaunchKernelGGL(k2d_edge_wl_dc, dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, rc, edge, ntx);
+  hipLaunchKernelGGL(k2d_first_dc, dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge);
+}
+void launch_2d_ctu_correct_dc(const DevGrid &g, const Run2D *rc, bool hcorr, hipStream_t st)
+{
+  const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
+  hipLaunchKernelGGL(k2d_correct_dc, dim3(ntx, cdiv(g.Nx2 + 4, 4)), dim3(64, 4), 0, st, g, rc, hcorr ? 1 : 0);
+}
+template <int MODE, bool CFL>
+static void launch_step_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
+{
+  const int X = Range2<MODE>::ext();
+  const int ntx = Range2<MODE>::toff() + (int)cdiv(g.Nx1 + X, 64), nj = g.Nx2 + 2*X;
+  hipLaunchKernelGGL((k2d_edge_dc<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_dc<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc);
+}
+void launch_2d_ctu_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
+{ launch_step_dc<M_CTU2, true>(g, rc, edge, sc, st); }
+void launch_2d_vl_predict_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st)
+{ launch_step_dc<M_VL1, false>(g, rc, edge, nullptr, st); }
+void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
+{ launch_step_dc<M_VL2, true>(g, rc, edge, sc, st); }
+void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st)
+{ hipLaunchKernelGGL(k2d_seed, dim3(1), dim3(64), 0, st, rc, v, sc); }
+void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, Run2DMirror *out, hipStream_t st)
+{ hipLaunchKernelGGL(k2d_advance, dim3(1), dim3(64), 0, st, rc, sc, g.dx[0], g.dx[1], out); }
 
 }  // namespace aa

@@ -118,10 +118,16 @@ class HipEngine:
 
     def can_batch(self) -> bool:
         """a 1-D Grid aa_run_1d takes (it fits the resident kernel and has no pinned zones): run_local takes whole stretches of the
-        main loop in one launch; every other Grid steps one launch at a time"""
+        main loop in one launch; or a 2-D Grid aa_run_2d takes (no pinned zones, not a level of a Mesh) unless AA_2D_BATCH=0:
+        run_local queues AA_2D_BATCH steps per read-back; every other Grid steps one at a time"""
+        if self.g.ndim == 2:
+            return self.g.run_2d_batch() != 0 and self.g.can_run_2d()
         return self.g.can_run_until()
 
-    def run_local(self, t_stop: float, tlim: float, nstep_stop) -> int: return self.g.run_until(t_stop, tlim, nstep_stop)
+    def run_local(self, t_stop: float, tlim: float, nstep_stop) -> int:
+        if self.g.ndim == 2:
+            return self.g.run_2d(t_stop, tlim, nstep_stop)
+        return self.g.run_until(t_stop, tlim, nstep_stop)
     def start_local(self): self.g.start()
     def resume_local(self): self.g.resume()
     def write_rst_payload(self, f): self.g.write_rst_payload(f)
@@ -717,13 +723,15 @@ class Driver(_Runner):
         self.new_dt()
 
     def may_batch(self) -> bool:
-        """whether advance() may take several steps in one call (outputs.run asks): one rank, a 1-D Grid the resident kernel holds"""
+        """whether advance() may take several steps in one call (outputs.run asks): one rank, and a 1-D Grid the resident kernel
+        holds (aa_run_1d) or a 2-D Grid whose steps queue with the time step picked on the device (aa_run_2d)"""
         return not self.distributed and hasattr(self.eng, "can_batch") and self.eng.can_batch()
 
     def advance(self, t_stop: float, nstep_stop=None) -> int:
         """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit), in one launch
-        (aa_run_1d; the same bits as that many step() calls).  -> the steps taken"""
-        far = self.nstep + (1 << 20)              # (aa_run_1d covers 2^20 steps per call at the most; the caller's loop goes on)
+        (aa_run_1d) or as queued steps with one read-back per batch (aa_run_2d); the same bits as that many step() calls.
+        -> the steps taken"""
+        far = self.nstep + (1 << 20)              # (aa_run_1d / aa_run_2d cover 2^20 steps per call at the most; the caller's loop goes on)
         n = self.eng.run_local(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
         self.time, self.dt, self.nstep = self.eng.mesh_state()
         self.niter_trace.extend([0] * n)

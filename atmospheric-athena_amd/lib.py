@@ -102,6 +102,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_integrate_3d_ctu": (I, [P]), "aa_integrate_begin": (I, [P]), "aa_cfl_in_update": (I, [P, I]), "aa_integrate_3d_vl": (I, [P]),
         "aa_integrate_2d_ctu": (I, [P]), "aa_integrate_2d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
         "aa_integrate_1d_ctu": (I, [P]), "aa_integrate_1d_vl": (I, [P]), "aa_run_1d": (I, [P, D, D, I, ip]),
+        "aa_run_2d": (I, [P, D, D, I, ip]), "aa_run_2d_batch": (I, [P]),
         "aa_run_1d_cap": (I, []), "aa_step_1d_block": (I, []),
         "aa_start": (I, [P]), "aa_step": (I, [P, ip]),
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
@@ -311,7 +312,8 @@ class Grid:
         # (N1, N2, N3); a direction with one zone has no ghost zones (a 2-D Grid: N3 = 1, a 1-D Grid: N2 = N3 = 1; init_grid.c:144-174)
         self.N = tuple(n + 2 * NGHOST if n > 1 else 1 for n in grid.Nx)
         self.ndim = sum(1 for n in grid.Nx if n > 1)
-        self.npin = 0                           # zones pinned by set_pinned_cells (aa_run_1d takes none)
+        self.npin = 0                           # zones pinned by set_pinned_cells (aa_run_1d / aa_run_2d take none)
+        self.in_mesh = False                    # a level of a Mesh (Mesh sets it): aa_run_2d refuses those
         h = C.c_void_p()
         self._h = None
         if cuts is not None:
@@ -467,6 +469,25 @@ class Grid:
         tlim = self.cfg.run.tlim if tlim is None else tlim
         stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
         self._chk(self.L.aa_run_1d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
+        return n.value
+
+    def run_2d_batch(self) -> int:
+        """steps run_2d queues per read-back on this Grid (AA_2D_BATCH when the Grid was made; 0: it steps one at a time)"""
+        return int(self.L.aa_run_2d_batch(self._h))
+
+    def can_run_2d(self) -> bool:
+        """whether run_2d takes this Grid: 2-D, no pinned zones, not a level of a Mesh -- the refusals of aa_run_2d"""
+        return self.ndim == 2 and self.npin == 0 and not self.in_mesh and self.cfg.level == 0
+
+    def run_2d(self, t_stop: float, tlim: float | None = None, nstep_stop: int | None = None) -> int:
+        """Whole passes of the main loop on a 2-D Grid with the time step picked on the device (aa_run_2d): AA_2D_BATCH steps are
+        queued per read-back instead of one; until time >= t_stop, nstep == nstep_stop or dt <= 0; new_dt clips at tlim (default:
+        the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the same bits as that many step()
+        calls.  AthenaError on a Grid that is not 2-D, has pinned zones or is a level of a Mesh (can_run_2d)."""
+        n = C.c_int()
+        tlim = self.cfg.run.tlim if tlim is None else tlim
+        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
+        self._chk(self.L.aa_run_2d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
         return n.value
 
     # ---- phases ----------------------------------------------------------------------
@@ -850,6 +871,8 @@ class Mesh:
             arr = (C.c_int * max(1, len(flat)))(*flat)
             self._chk(self.L.aa_mesh_create_local(n, hs, arr, C.byref(h)))
         self._h = h
+        for g in self.lev:
+            g.in_mesh = True                    # (the levels step together: Grid.can_run_2d says no)
 
     def _chk(self, rc: int):
         if rc != 0:
@@ -858,6 +881,8 @@ class Mesh:
     def close(self):
         if self._h is not None:
             self.L.aa_mesh_destroy(self._h); self._h = None
+            for g in self.lev:
+                g.in_mesh = False
         for g in self.lev:
             g.close()
 

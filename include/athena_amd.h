@@ -161,6 +161,14 @@ int aa_integrate_1d_vl(aa_grid *g);                 /* integrate_1d_vl.c        
  * aa_run_1d_cap() active zones (one workgroup's LDS), or has pinned zones.  AA_1D_RESIDENT=0 in the environment at aa_create:
  * the same call steps one launch at a time.                                                                                   */
 int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+/* Many steps of a 2-D Grid per host visit (csrc/hydro2d_kernels.hip k2d_advance): the same loop and the same stop rules as aa_run_1d,
+ * with the time step picked on the device -- AA_2D_BATCH steps (environment at aa_create; default 32) are queued as plain launches,
+ * then the host reads time / dt / nstep / "stopped" ONCE and queues again while the run is live; steps queued behind the stop store
+ * nothing.  The same bits as that many aa_step calls.  An error on a Grid that is not 2-D, has pinned zones or is a level of an
+ * aa_mesh, for tlim other than the Grid's, and for nstep_stop outside nstep .. nstep + 2^20.  AA_2D_BATCH=0: the same call steps
+ * one aa_step at a time.                                                                                                        */
+int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+int aa_run_2d_batch(const aa_grid *g);              /* steps queued per read-back on this Grid (0: one aa_step at a time; not 2-D: 0) */
 int aa_run_1d_cap(void);                            /* most active zones aa_run_1d keeps resident */
 int aa_step_1d_block(void);                         /* TEST HOOK: active zones per block of the per-step kernel (the fixtures'
                                                        sizes sit either side of it); nothing in the product calls it */
