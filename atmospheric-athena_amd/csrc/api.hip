@@ -281,14 +281,6 @@ int aa_create(const aa_params *p, aa_grid **out)
   // (every word of these is written before it is read; zeroed all the same, so that no run ever depends on what a freed
   //  allocation of an earlier Grid left behind)
   (void)hipMemset(g->sc, 0, sizeof(DevScalars));
-  if (one_d) {
-    if (hipHostMalloc(&g->run1d, sizeof(Run1D), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&g->run1d_dev, g->run1d, 0) != hipSuccess) {
-      if (g->run1d) hipHostFree(g->run1d);
-      hipFree(g->pool); hipFree(g->sc); hipHostFree(g->mb); delete g; return fail(-2, "[aa_create]: scalar buffers");
-    }
-    memset(g->run1d, 0, sizeof(Run1D));
-  }
   if (g->ion_part) (void)hipMemset(g->ion_part, 0, (size_t)ion_pass_blocks(d)*sizeof(IonPart));
   if (g->ion_words) (void)hipMemset(g->ion_words, 0, AA_ION_WORDS*sizeof(Real));
   hipStreamCreate(&g->st); g->own_stream = true;
@@ -312,9 +304,7 @@ void aa_destroy(aa_grid *g)
   if (g->pin_mask) hipFree(g->pin_mask);
   if (g->cfl_part) hipFree(g->cfl_part);
   if (g->fofc_list) hipFree(g->fofc_list);
-  if (g->run1d) hipHostFree(g->run1d);
-  if (g->run2d) hipHostFree(g->run2d);
-  if (g->run2d_dev) hipFree(g->run2d_dev);
+  if (g->clock) { hipHostFree(g->clock); hipFree(g->run2d_dev); }      // (run.hip run_buffers; run2d_dev: null on a 1-D Grid)
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);
@@ -658,10 +648,9 @@ int aa_new_dt_local(aa_grid *g, double *dt_cfl)
     HIPCHK(hipMemsetAsync(g->sc->max_v, 0, 3*sizeof(unsigned long long), g->st));
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
-  double max_dti = 0.0;                   // new_dt.c:159-166
   const int ndir = g->one_d ? 1 : g->two_d ? 2 : 3;     // new_dt.c:156-161: only the directions with more than one zone
-  for (int d = 0; d < ndir; d++) { double v = bits_to_double(g->sc_host->max_v[d])/g->d.dx[d]; max_dti = (max_dti > v) ? max_dti : v; }
-  *dt_cfl = g->p.cour_no/max_dti;
+  double v[3]; max_v_of(*g->sc_host, v);
+  *dt_cfl = dt_courant(g->p.cour_no, dt_fold(0.0, v, g->d.dx, ndir));
   return 0;
 }
 
@@ -673,7 +662,7 @@ int aa_cfl_max_v(aa_grid *g, double *v)      // new_dt.c:72-140 of this Grid: ma
     HIPCHK(hipMemsetAsync(g->sc->max_v, 0, 3*sizeof(unsigned long long), g->st));
     launch_cfl(g->d, g->sc, g->st); }
   int rc = fetch_scalars(g); if (rc) return rc;
-  for (int d = 0; d < 3; d++) v[d] = bits_to_double(g->sc_host->max_v[d]);
+  max_v_of(*g->sc_host, v);
   if (g->two_d || g->one_d) v[2] = 0.0;  // new_dt.c:135: max_v3 only where Nx3 > 1
   if (g->one_d) v[1] = 0.0;              // :128: max_v2 only where Nx2 > 1
   return 0;
@@ -682,8 +671,7 @@ int aa_cfl_max_v(aa_grid *g, double *v)      // new_dt.c:72-140 of this Grid: ma
 int aa_new_dt(aa_grid *g)
 {
   double dtc; int rc = aa_new_dt_local(g, &dtc); if (rc) return rc;
-  if (g->nstep == 0) g->dt = dtc; else g->dt = (2.0*g->dt < dtc) ? 2.0*g->dt : dtc;       // new_dt.c:169-173
-  if ((g->time < g->p.tlim) && ((g->p.tlim - g->time) < g->dt)) g->dt = g->p.tlim - g->time;   // :183-185
+  g->dt = dt_pick(g->nstep, g->dt, dtc, g->time, g->p.tlim);       // new_dt.c:167-185
   if (!g->slab.empty()) slabs_push_state(g);
   return 0;
 }

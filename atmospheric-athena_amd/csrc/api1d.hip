@@ -1,4 +1,4 @@
-// api1d.hip -- the C-ABI of a 1-D Grid's integrators (include/athena_amd.h: aa_integrate_1d_ctu, aa_integrate_1d_vl, aa_run_1d):
+// api1d.hip -- the C-ABI of a 1-D Grid's integrators (include/athena_amd.h: aa_integrate_1d_ctu, aa_integrate_1d_vl; aa_run_1d is run.hip):
 // the kernels of csrc/hydro1d_kernels.hip.  Everything else a 1-D Grid needs (creation, transfers, bvals_mhd, new_dt, aa_start /
 // aa_step) is the code of api.hip, which branches on aa_grid::one_d where a 1-D Grid differs.  (The stage names below are not in
 // bench.py's table of bytes per stage: the benchmark has no 1-D workload; profiles/rate_1d.py measures whole runs.)
@@ -11,7 +11,6 @@ using namespace aa;
 
 extern "C" {
 
-int aa_run_1d_cap(void) { return run1d_cap(); }
 int aa_step_1d_block(void) { return step1d_block(); }
 
 // one launch: k1d_step reads U and writes the second buffer, which is U from here on (hydro1d_kernels.hip, header)
@@ -40,36 +39,6 @@ int aa_integrate_1d_vl(aa_grid *g)
   if (!g->one_d) return aa_fail(-1, "[aa_integrate_1d_vl]: this is a %s Grid: aa_integrate_%s_vl", g->two_d ? "2-D" : "3-D", g->two_d ? "2d" : "3d");
   if (g->p.integrator != 1) return aa_fail(-1, "[aa_integrate_1d_vl]: this Grid was created for the CTU integrator (its cour_no was checked for that one)");
   return integrate_1d(g, true);
-}
-
-// main.c:519-669 until time >= t_stop, nstep == nstep_stop or dt <= 0: in one launch (k1d_run), or step by step (AA_1D_RESIDENT=0)
-int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
-{
-  if (!g) return aa_fail(-1, "[aa_run_1d]: null argument");
-  if (!g->one_d) return aa_fail(-1, "[aa_run_1d]: this is a %s Grid: only a 1-D Grid runs many steps per launch", g->two_d ? "2-D" : "3-D");
-  if (g->d.Nx1 > run1d_cap())
-    return aa_fail(-1, "[aa_run_1d]: a 1-D Grid of %d zones is above the %d the resident kernel keeps in one workgroup's LDS: aa_step", g->d.Nx1, run1d_cap());
-  if (g->npin > 0) return aa_fail(-1, "[aa_run_1d]: a 1-D Grid with pinned zones steps one launch at a time: aa_step");
-  const long long span = (long long)nstep_stop - g->nstep;
-  if (span < 0 || span > (1LL << 20))
-    return aa_fail(-1, "[aa_run_1d]: nstep_stop=%d from nstep=%d: a call covers 0 .. 2^20 steps", nstep_stop, g->nstep);
-  if (tlim != g->p.tlim) return aa_fail(-1, "[aa_run_1d]: tlim=%.17g, but the Grid was created with %.17g (new_dt clips at that one)", tlim, g->p.tlim);
-  const int nstep0 = g->nstep;
-  if (!g->resident_1d) {
-    while (g->time < t_stop && g->nstep != nstep_stop && g->dt > 0.0) { int rc = aa_step(g, nullptr); if (rc) return rc; }
-    if (nsteps_done) *nsteps_done = g->nstep - nstep0;
-    return 0;
-  }
-  g->cfl_ready = false; g->active_dirty = true;
-  g->run1d->time = g->time; g->run1d->dt = g->dt; g->run1d->nstep = g->nstep;
-  { Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
-    launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->run1d_dev, g->st); }
-  HIPCHK(hipGetLastError());
-  g->host_syncs++;
-  HIPCHK(hipStreamSynchronize(g->st));
-  g->time = g->run1d->time; g->dt = g->run1d->dt; g->nstep = g->run1d->nstep;
-  if (nsteps_done) *nsteps_done = g->nstep - nstep0;
-  return 0;
 }
 
 }  // extern "C"

@@ -45,10 +45,9 @@ struct aa_grid {
   aa::Real *edge2d = nullptr;          //   ... what the x1 tiles of the 2-D kernels hand each other (grid.h)
   bool one_d = false;                  // Nx2 = Nx3 = 1 in a 1-D root Domain: the 1-D integrators (hydro1d_kernels.hip); U 5 | LR 5 (the second U buffer)
   bool resident_1d = true;             //   ... AA_1D_RESIDENT=0 (read by aa_create): aa_run_1d steps one launch at a time instead of keeping the Grid in one workgroup's LDS (k1d_run)
-  aa::Run1D *run1d = nullptr, *run1d_dev = nullptr;   //   ... time, dt, nstep of aa_run_1d: pinned, device-visible host memory and its device address
   int batch_2d = 0;                    // a 2-D Grid: steps aa_run_2d queues between two reads of the clock (AA_2D_BATCH, read by aa_create; 0: it loops over aa_step)
-  aa::Run2D *run2d_dev = nullptr;      //   ... the clock in device memory and its page-locked mirror (hydro2d_launch.h), made by the first aa_run_2d
-  aa::Run2DMirror *run2d = nullptr, *run2d_map = nullptr;   //   ... (run2d_map: the mirror's device address)
+  RunClock *clock = nullptr, *clock_dev = nullptr;   // time, dt, nstep, live of aa_run_1d / aa_run_2d (time_step.h): pinned, device-visible host memory and its device address ...
+  aa::Run2D *run2d_dev = nullptr;      //   ... and the 2-D call's clock in device memory (hydro2d_launch.h); made by the first run call that reaches the device (run.hip)
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke
   double inner_dt = 0.0;               //   ... with this dt
   bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): aa_params.ion_path, else LaunchCfg ion_fused; a sweep along x2 turns it off
@@ -201,6 +200,8 @@ void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevSc
 
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }
 static inline unsigned long long double_to_bits(double x) { unsigned long long b; memcpy(&b, &x, 8); return b; }
+// new_dt's maxima as the kernels left them, for time_step.h
+static inline void max_v_of(const aa::DevScalars &s, double *v) { for (int d = 0; d < 3; d++) v[d] = bits_to_double(s.max_v[d]); }
 extern "C" int aa_fetch_scalars(aa_grid *g);     // DevScalars device -> pinned host, synchronous
 // ionrad_3d.c:862-1012 for the Grid of one level (api.hip; the loop itself is ion_subcycle.h): root (finegrid 0, limit = its
 // dt) or refined level (limit = the time the root covered); *dt_done_out = the time the sub-cycles covered

@@ -262,7 +262,7 @@ AA_DEV void bc_x1_lds(Real *sU, int ld, int is, int ie, int bc_in, int bc_out)
 
 template <bool VL, int ORD>
 __global__ void __launch_bounds__(R1_NT)
-k1d_run(DevGrid g, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, int nstep_stop, Run1D *rs)
+k1d_run(DevGrid g, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, int nstep_stop, RunClock *rs)
 {
   __shared__ Real sU[5*R1_LD], sA[5*R1_LD], sB[5*R1_LD];
   __shared__ Real red[R1_NT/64];
@@ -276,7 +276,7 @@ k1d_run(DevGrid g, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, 
   Real time = rs->time, dt = rs->dt;
   int nstep = rs->nstep;
   __syncthreads();
-  while (time < t_stop && nstep != nstep_stop && dt > 0.0) {
+  while (run_live(time, t_stop, nstep, nstep_stop, dt)) {
     Real mx = step_core<VL, ORD, R1_NT, R1_K>(sU, sA, sB, R1_LD, n, dt, g.dx[0], g.Gamma, g.Gamma_1, g.rGamma_1);   // main.c:572-585
     nstep++; time += dt;                                            // :618-626
     mx = wave_max(mx);
@@ -286,17 +286,14 @@ k1d_run(DevGrid g, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, 
     Real vmax = red[0];
 #pragma unroll
     for (int q = 1; q < R1_NT/64; q++) vmax = rmax(vmax, red[q]);
-    const Real max_dti = rmax(0.0, vmax/g.dx[0]);                   // new_dt.c:156-157
-    const Real dtc = cour_no/max_dti;
-    dt = (nstep == 0) ? dtc : rmin(2.0*dt, dtc);                    // :167-171
-    if ((time < tlim) && ((tlim - time) < dt)) dt = tlim - time;    // :183-185
+    dt = dt_pick(nstep, dt, dt_courant(cour_no, dt_fold(0.0, &vmax, g.dx, 1)), time, tlim);   // new_dt.c:156-185 (time_step.h)
     __syncthreads();                                                // (the ghost zones are written; red is free again)
   }
   for (int c = tid; c < n; c += R1_NT) {
 #pragma unroll
     for (int v = 0; v < 5; v++) g.U[(long)v*g.nc + c] = sU[v*R1_LD + c];
   }
-  if (tid == 0) { rs->time = time; rs->dt = dt; rs->nstep = nstep; }
+  if (tid == 0) { rs->time = time; rs->dt = dt; rs->nstep = nstep; rs->live = 0; }   // (live: not read here; the loop has ended)
 }
 
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
@@ -309,7 +306,7 @@ void launch_1d_step(const DevGrid &g, bool vl, bool third, Real dt, Real *Unew, 
   with_flag(vl, [&](auto VL) { with_ord(third, [&](auto ORD) {
     hipLaunchKernelGGL((k1d_step<VL, ORD>), dim3(nb), dim3(S1_NT), 0, st, g, dt, Unew, sc); }); });
 }
-void launch_1d_run(const DevGrid &g, bool vl, bool third, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, int nstep_stop, Run1D *rs, hipStream_t st)
+void launch_1d_run(const DevGrid &g, bool vl, bool third, int bc_in, int bc_out, Real cour_no, Real t_stop, Real tlim, int nstep_stop, RunClock *rs, hipStream_t st)
 {
   with_flag(vl, [&](auto VL) { with_ord(third, [&](auto ORD) {
     hipLaunchKernelGGL((k1d_run<VL, ORD>), dim3(1), dim3(R1_NT), 0, st, g, bc_in, bc_out, cour_no, t_stop, tlim, nstep_stop, rs); }); });

@@ -414,23 +414,23 @@ AA_DEV Real half_dt_over_dx(Real dt, Real dx)
 // any store and before any barrier (the whole grid takes the same branch).
 __global__ void __launch_bounds__(64)
 k2d_edge_wl_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
-{ if (!rc->live) return; edge_wl_body(g, rc->dt, edge, ntx); }
+{ if (!rc->c.live) return; edge_wl_body(g, rc->c.dt, edge, ntx); }
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_first_dc(DevGrid g, const Run2D *rc, const Real *edge)
-{ if (!rc->live) return; first_body(g, rc->dt, edge); }
+{ if (!rc->c.live) return; first_body(g, rc->c.dt, edge); }
 __global__ void __launch_bounds__(256)
 k2d_correct_dc(DevGrid g, const Run2D *rc, int hcorr)
-{ if (!rc->live) return; correct_body(g, rc->dt, hcorr); }
+{ if (!rc->c.live) return; correct_body(g, rc->c.dt, hcorr); }
 template <int MODE>
 __global__ void __launch_bounds__(64)
 k2d_edge_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
-{ if (!rc->live) return; edge_body<MODE>(g, rc->dt, edge, ntx); }
+{ if (!rc->c.live) return; edge_body<MODE>(g, rc->c.dt, edge, ntx); }
 template <int MODE, bool CFL>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc)
 {
-  if (!rc->live) return;
-  const Real dt = rc->dt;
+  if (!rc->c.live) return;
+  const Real dt = rc->c.dt;
   const Real c1 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[0]) : dt_over_dx(dt, g.dx[0]);
   const Real c2 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[1]) : dt_over_dx(dt, g.dx[1]);
   step_body<MODE, CFL, false>(g, dt, c1, c2, edge, sc, nullptr);
@@ -449,23 +449,16 @@ k2d_seed(Run2D *rc, Run2D v, DevScalars *sc)
 // boundary pass that follows takes no dt.  Launch rule (as k1d_run states it for itself): a plain launch in stream order; nothing
 // here waits for another workgroup or spins on memory, so the launch ends whatever the data are.
 __global__ void __launch_bounds__(64)
-k2d_advance(Run2D *rc, DevScalars *sc, Real dx0, Real dx1, Run2DMirror *out)
+k2d_advance(Run2D *rc, DevScalars *sc, Real dx0, Real dx1, RunClock *out)
 {
-#pragma clang fp contract(off)
-  if (threadIdx.x != 0 || !rc->live) return;
-  const int nstep = rc->nstep + 1;
-  const Real time = rc->time + rc->dt;
-  Real max_dti = 0.0;                                             // new_dt.c:159-166
-  { const Real v = __longlong_as_double((long long)sc->max_v[0])/dx0; max_dti = (max_dti > v) ? max_dti : v; }
-  { const Real v = __longlong_as_double((long long)sc->max_v[1])/dx1; max_dti = (max_dti > v) ? max_dti : v; }
-  const Real dt_cfl = rc->cour_no/max_dti;
-  Real dt = rc->dt;
-  if (nstep == 0) dt = dt_cfl; else dt = (2.0*dt < dt_cfl) ? 2.0*dt : dt_cfl;                  // :169-173
-  if ((time < rc->tlim) && ((rc->tlim - time) < dt)) dt = rc->tlim - time;                     // :183-185
+  if (threadIdx.x != 0 || !rc->c.live) return;
+  RunClock c = rc->c;
+  c.nstep++; c.time += c.dt;
+  const Real max_v[2] = {__longlong_as_double((long long)sc->max_v[0]), __longlong_as_double((long long)sc->max_v[1])}, dx[2] = {dx0, dx1};
+  c.dt = dt_pick(c.nstep, c.dt, dt_courant(rc->cour_no, dt_fold(0.0, max_v, dx, 2)), c.time, rc->tlim);   // new_dt.c:156-185 (time_step.h)
   sc->max_v[0] = 0ULL; sc->max_v[1] = 0ULL; sc->max_v[2] = 0ULL;                               // for the next step's update kernel
-  const int live = (time >= rc->t_stop || nstep == rc->nstep_stop || !(dt > 0.0)) ? 0 : 1;     // (a NaN dt stops too)
-  rc->time = time; rc->dt = dt; rc->nstep = nstep; rc->live = live;
-  out->time = time; out->dt = dt; out->nstep = nstep; out->live = live;
+  c.live = run_live(c.time, rc->t_stop, c.nstep, rc->nstep_stop, c.dt);                        // (a NaN dt stops too)
+  rc->c = c; *out = c;
 }
 
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
@@ -541,7 +534,7 @@ void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge,
 { launch_step_dc<M_VL2, true>(g, rc, edge, sc, st); }
 void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st)
 { hipLaunchKernelGGL(k2d_seed, dim3(1), dim3(64), 0, st, rc, v, sc); }
-void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, Run2DMirror *out, hipStream_t st)
+void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st)
 { hipLaunchKernelGGL(k2d_advance, dim3(1), dim3(64), 0, st, rc, sc, g.dx[0], g.dx[1], out); }
 
 }  // namespace aa

@@ -3,6 +3,7 @@
 // (aa_step on a 2-D Grid) are declared there.
 #pragma once
 #include "grid.h"
+#include "time_step.h"
 
 // steps aa_run_2d queues between two reads of the clock where AA_2D_BATCH is not set (0: one aa_step at a time); DESIGN section 8
 // has the measurement it comes from
@@ -10,17 +11,15 @@
 
 namespace aa {
 
-// MeshS.time / dt / nstep of a 2-D Grid while aa_run_2d has steps queued, in DEVICE memory: every kernel of a queued step reads
-// `dt` and `live` (one 16-byte uniform load), k2d_advance behind the step's update kernel writes the next ones.  live = 0: the
+// The clock (time_step.h RunClock) of a 2-D Grid while aa_run_2d has steps queued, with the call's limits, in DEVICE memory: every
+// kernel of a queued step reads `dt` and `live` (one 16-byte uniform load), k2d_advance behind the step's update kernel writes the
+// next ones -- and a copy of the clock into the page-locked RunClock the host reads ONCE per batch of queued steps.  live = 0: the
 // call's stop rule has fired; what is queued behind it returns without a store.
 struct Run2D {
-  Real dt; int live, nstep;
-  Real time;
+  RunClock c;
   Real t_stop, tlim, cour_no;       // of the call: main.c's loop condition, new_dt.c's clip and CourNo
   int nstep_stop, pad;
 };
-// ... and what the host reads ONCE per batch of queued steps: page-locked, device-visible host memory k2d_advance also writes
-struct Run2DMirror { Real time, dt; int nstep, live; };
 
 void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st);               // the clock of a call; new_dt's maxima zeroed
 void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st);                     // as launch_2d_ctu_first ...
@@ -29,6 +28,6 @@ void launch_2d_ctu_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge
 void launch_2d_vl_predict_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st);
 void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st);
 // nstep++, time += dt, new_dt with the clip at tlim, the maxima zeroed again, the stop rule; `out`: the host's mirror
-void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, Run2DMirror *out, hipStream_t st);
+void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st);
 
 }  // namespace aa

@@ -1,0 +1,114 @@
+// run.hip -- the C-ABI of the run calls (include/athena_amd.h: aa_run_1d, aa_run_2d): main.c:519-669 until time >= t_stop,
+// nstep == nstep_stop or dt <= 0 with the loop's clock on the device -- a 1-D Grid in ONE launch (hydro1d_kernels.hip k1d_run), a 2-D
+// Grid as AA_2D_BATCH queued steps per read of the clock (hydro2d_kernels.hip k2d_advance) -- or, with the knob of either at 0, step
+// by step.  One body behind both names: the refusals, the fallback and the seed / synchronise / read-back frame are written once.
+// The rule of the step and the loop condition are those of time_step.h, on the host and in the two kernels.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include "api_internal.h"
+
+using namespace aa;
+
+// The clock of a run call: ONE page-locked, device-visible RunClock per Grid -- k1d_run reads and writes it in place; k2d_advance
+// copies the clock it keeps in device memory (Run2D, 2-D Grids only) into it for the host's one read per batch.  Made by the first
+// call that reaches the device; aa_destroy frees them.
+static int run_buffers(aa_grid *g, const char *who)
+{
+  if (g->clock) return 0;
+  RunClock *h = nullptr, *hd = nullptr; Run2D *d = nullptr;
+  if (hipHostMalloc(&h, sizeof(RunClock), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || (g->two_d && hipMalloc(&d, sizeof(Run2D)) != hipSuccess)) {
+    if (h) hipHostFree(h);
+    (void)hipGetLastError();
+    return aa_fail(-2, "[%s]: clock buffers", who);
+  }
+  memset(h, 0, sizeof(RunClock));
+  g->clock = h; g->clock_dev = hd; g->run2d_dev = d;
+  return 0;
+}
+
+// one step of the queue: the integrator's chain with new_dt's maxima on board, k2d_advance, bvals_mhd (main.c:572-644 without
+// Userwork_in_loop: a Grid with pinned zones is refused).  The stage names are those of aa_integrate_2d_* / aa_bvals_mhd.
+static void queue_step_2d(aa_grid *g)
+{
+  const HostGrid &d = g->d; const Run2D *rc = g->run2d_dev;
+  if (g->p.integrator == 1) {
+    { Scope s(g, "vl2d_predict"); launch_2d_vl_predict_dc(d, rc, g->edge2d, g->st); }
+    { Scope s(g, "vl2d_flux2_update"); launch_2d_vl_flux2_update_dc(d, rc, g->edge2d, g->sc, g->st); }
+  } else {
+    { Scope s(g, "ctu2d_first"); launch_2d_ctu_first_dc(d, rc, g->edge2d, g->st); }
+    { Scope s(g, "ctu2d_correct"); launch_2d_ctu_correct_dc(d, rc, g->p.integrator == 0, g->st); }
+    { Scope s(g, "ctu2d_flux2_update"); launch_2d_ctu_flux2_update_dc(d, rc, g->edge2d, g->sc, g->st); }
+  }
+  { Scope s(g, "run2d_advance"); launch_2d_advance(d, g->run2d_dev, g->sc, g->clock_dev, g->st); }
+  // The boundary kernels (k_bc) take no dt and are not predicated.  With four or more zones per direction every ghost zone is a
+  // copy of an ACTIVE zone (x1 pass) or of a row whose x1 ghost zones that pass has just filled (x2 pass), so behind a stopped
+  // step -- U untouched -- they write again what is there: idempotent.  (Grids with fewer zones step one at a time, below.)
+  { Scope s(g, "bvals_mhd");
+    for (int a = 0; a < 2; a++) launch_bc_dir(d, g->p.nscal, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
+}
+
+// `who`: the entry's name for its messages; ndim: the Grids it takes
+static int run_to_time(aa_grid *g, const char *who, int ndim, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{
+  if (!g) return aa_fail(-1, "[%s]: null argument", who);
+  if (ndim == 1) {
+    if (!g->one_d) return aa_fail(-1, "[%s]: this is a %s Grid: only a 1-D Grid runs many steps per launch", who, g->two_d ? "2-D" : "3-D");
+    // (before the knob is looked at: AA_1D_RESIDENT=0 does not lift it)
+    if (g->d.Nx1 > run1d_cap())
+      return aa_fail(-1, "[%s]: a 1-D Grid of %d zones is above the %d the resident kernel keeps in one workgroup's LDS: aa_step", who, g->d.Nx1, run1d_cap());
+  } else {
+    if (g->one_d) return aa_fail(-1, "[%s]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_run_1d", who);
+    if (!g->two_d) return aa_fail(-1, "[%s]: this is a 3-D Grid: only 1-D and 2-D Grids run many steps per host visit", who);
+  }
+  if (g->npin > 0) return aa_fail(-1, "[%s]: a %d-D Grid with pinned zones steps one at a time: aa_step", who, ndim);
+  if (g->keep_flux || g->level > 0)      // (2-D only: a 1-D Grid is never a level of a Mesh)
+    return aa_fail(-1, "[%s]: this Grid is a level of a Mesh (level %d): the levels step together, aa_mesh_step", who, g->level);
+  const long long span = (long long)nstep_stop - g->nstep;
+  if (span < 0 || span > (1LL << 20))
+    return aa_fail(-1, "[%s]: nstep_stop=%d from nstep=%d: a call covers 0 .. 2^20 steps", who, nstep_stop, g->nstep);
+  if (tlim != g->p.tlim) return aa_fail(-1, "[%s]: tlim=%.17g, but the Grid was created with %.17g (new_dt clips at that one)", who, tlim, g->p.tlim);
+  const int nstep0 = g->nstep;
+  // step by step: either knob at 0, or fewer zones than ghost zones along a direction of a 2-D Grid (a boundary kernel reads ghost
+  // zones there, see queue_step_2d)
+  if (ndim == 1 ? !g->resident_1d : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST)) {
+    while (run_live(g->time, t_stop, g->nstep, nstep_stop, g->dt)) { int rc = aa_step(g, nullptr); if (rc) return rc; }
+    if (nsteps_done) *nsteps_done = g->nstep - nstep0;
+    return 0;
+  }
+  if (nsteps_done) *nsteps_done = 0;
+  if (!run_live(g->time, t_stop, g->nstep, nstep_stop, g->dt)) return 0;      // nothing launched, nothing read back
+  if (int rc = run_buffers(g, who)) return rc;
+  g->cfl_ready = false; g->active_dirty = true;
+  const RunClock seed = {g->dt, 1, g->nstep, g->time};
+  if (ndim == 1) *g->clock = seed;
+  else {
+    const Run2D v = {seed, t_stop, tlim, g->p.cour_no, nstep_stop, 0};
+    launch_2d_seed(g->run2d_dev, v, g->sc, g->st);
+  }
+  // Every launch ends whatever the data are, so the queue drains.  1-D: the one launch runs to the stop and leaves live = 0.  2-D: a
+  // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call).
+  do {
+    if (ndim == 1) {
+      Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
+      launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->clock_dev, g->st);
+    } else for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
+    HIPCHK(hipGetLastError());
+    g->host_syncs++;
+    HIPCHK(hipStreamSynchronize(g->st));
+  } while (g->clock->live);
+  g->time = g->clock->time; g->dt = g->clock->dt; g->nstep = g->clock->nstep;
+  if (nsteps_done) *nsteps_done = g->nstep - nstep0;
+  return 0;
+}
+
+extern "C" {
+
+int aa_run_1d_cap(void) { return run1d_cap(); }
+int aa_run_2d_batch(const aa_grid *g) { return g && g->two_d ? g->batch_2d : 0; }
+int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{ return run_to_time(g, "aa_run_1d", 1, t_stop, tlim, nstep_stop, nsteps_done); }
+int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{ return run_to_time(g, "aa_run_2d", 2, t_stop, tlim, nstep_stop, nsteps_done); }
+
+}  // extern "C"

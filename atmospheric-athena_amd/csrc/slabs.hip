@@ -577,9 +577,8 @@ int slabs_new_dt_local(aa_grid *g, double *dt_cfl)
   int rc = cfl_all(g); if (rc) return rc;
   double dt = DBL_MAX;
   for (int s = 0; s < g->link->n; s++) {
-    double max_dti = 0.0;
-    for (int d = 0; d < 3; d++) { const double v = bits_to_double(g->link->hsc[s].max_v[d])/g->slab[s]->d.dx[d]; max_dti = (max_dti > v) ? max_dti : v; }
-    const double q = g->p.cour_no/max_dti;
+    double v[3]; max_v_of(g->link->hsc[s], v);
+    const double q = dt_courant(g->p.cour_no, dt_fold(0.0, v, g->slab[s]->d.dx, 3));
     dt = (q < dt) ? q : dt;
   }
   *dt_cfl = dt;

@@ -828,6 +828,12 @@ int aa_mesh_prolongate(aa_mesh *m)
   return 0;
 }
 
+// new_dt.c:167-185 of the Mesh, from the max_dti folded over its levels (time_step.h)
+static void mesh_pick_dt(aa_mesh *m, double max_dti)
+{
+  const aa_params &p = m->lev[0]->p;
+  m->dt = dt_pick(m->nstep, m->dt, dt_courant(p.cour_no, max_dti), m->time, p.tlim);
+}
 // new_dt.c:32 over all levels: max_v is carried from Grid to Grid (:33), one dt for the Mesh
 int aa_mesh_new_dt(aa_mesh *m)
 {
@@ -840,16 +846,10 @@ int aa_mesh_new_dt(aa_mesh *m)
       HIPCHK(hipMemsetAsync(g->sc->max_v, 0, 3*sizeof(unsigned long long), g->st));
       launch_cfl(g->d, g->sc, g->st); }
     int rc = aa_fetch_scalars(g); if (rc) return rc;
-    for (int d = 0; d < ndir; d++) {
-      const double v = bits_to_double(g->sc_host->max_v[d]);
-      cum[d] = (cum[d] > v) ? cum[d] : v;
-    }
-    for (int d = 0; d < ndir; d++) { const double q = cum[d]/g->d.dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
+    double v[3]; max_v_of(*g->sc_host, v);
+    max_dti = dt_fold_level(max_dti, cum, v, g->d.dx, ndir);
   }
-  const aa_params &p = m->lev[0]->p;
-  const double dtc = p.cour_no/max_dti;
-  if (m->nstep == 0) m->dt = dtc; else m->dt = (2.0*m->dt < dtc) ? 2.0*m->dt : dtc;
-  if ((m->time < p.tlim) && ((p.tlim - m->time) < m->dt)) m->dt = p.tlim - m->time;
+  mesh_pick_dt(m, max_dti);
   for (int l = 0; l < m->nl; l++) m->lev[l]->dt = m->dt;
   return 0;
 }
@@ -1335,14 +1335,10 @@ static int cut_new_dt(aa_mesh *m)
   double cum[3] = {0.0, 0.0, 0.0}, max_dti = 0.0;
   for (int l = 0; l < m->nl; l++) {
     const SlabLink *K = m->lev[l]->link;
-    for (int d = 0; d < 3; d++)
-      for (int si = 0; si < K->n; si++) { const double v = bits_to_double(K->hsc[si].max_v[d]); cum[d] = (cum[d] > v) ? cum[d] : v; }
-    for (int d = 0; d < 3; d++) { const double q = cum[d]/m->lev[l]->slab[0]->d.dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
+    for (int si = 0; si < K->n; si++) { double v[3]; max_v_of(K->hsc[si], v); dt_carry(cum, v, 3); }
+    max_dti = dt_fold(max_dti, cum, m->lev[l]->slab[0]->d.dx, 3);
   }
-  const aa_params &p = m->lev[0]->p;
-  const double dtc = p.cour_no/max_dti;
-  if (m->nstep == 0) m->dt = dtc; else m->dt = (2.0*m->dt < dtc) ? 2.0*m->dt : dtc;
-  if ((m->time < p.tlim) && ((p.tlim - m->time) < m->dt)) m->dt = p.tlim - m->time;
+  mesh_pick_dt(m, max_dti);
   for (int l = 0; l < m->nl; l++) { m->lev[l]->dt = m->dt; slabs_push_state(m->lev[l]); }
   return 0;
 }

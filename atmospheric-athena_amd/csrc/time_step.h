@@ -1,0 +1,87 @@
+/* time_step.h -- the time-step rule of new_dt.c:156-185 and the loop condition of main.c:519, once, for host and device
+ * (C99 and C++, no HIP include; the drop-in shim, the C library, k1d_run and k2d_advance all call these).
+ *
+ * However the maxima of |v| + a reach the caller -- one Grid, slabs, the levels of a Mesh, MPI ranks, a kernel that keeps the
+ * clock on the device -- the operations, their order and their comparison forms are the ones written here:
+ *   dt_fold        :156-161  max_dti = MAX(max_dti, max_v_d/dx_d) over the directions with more than one zone
+ *   dt_carry       :33, :53  max_v1..3 are zeroed once, in front of the loop over Grids: a level's maxima include the coarser ones'
+ *   dt_fold_level            the two of a level: carry, then fold
+ *   dt_courant     :168      CourNo/max_dti (max_dti = 0: +inf)
+ *   dt_grow        :167-171  nstep == 0 ? dt_cfl : MIN(2.0*dt, dt_cfl), MIN(a,b) = (a < b) ? a : b (defs.h.in:146): a NaN dt_cfl
+ *                            gives NaN.  With MPI this half stands before the MPI_Allreduce(MIN) of :177 ...
+ *   dt_clip        :183-185  ... and this half, the clip at tlim, behind it
+ *   dt_pick        :167-185  the two composed
+ *   run_live       main.c:519 as the run calls use it: time < t_stop && nstep != nstep_stop && dt > 0.0 (a NaN dt stops)
+ * No operation is contracted with another (the pragma inside every body: a file-scope one would reach the including file).
+ * (driver.py holds pick_dt / fold_levels for the Python drivers; tests/test_time_step.py runs one table of cases through both;
+ * oracle/athena_oracle.c keeps its own text: it is what the library is tested against.)
+ */
+#ifndef AA_TIME_STEP_H
+#define AA_TIME_STEP_H
+
+#ifdef __HIPCC__
+#define TS_FN static inline __host__ __device__
+#else
+#define TS_FN static inline
+#endif
+#ifdef __clang__
+#define TS_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define TS_NO_CONTRACT
+#endif
+
+/* MeshS.time / dt / nstep while a run call (aa_run_1d, aa_run_2d) has the main loop on the device, and whether the loop goes on.
+ * dt and live lead: every kernel of a queued 2-D step reads the two in one 16-byte uniform load (hydro2d_launch.h Run2D). */
+typedef struct RunClock { double dt; int live, nstep; double time; } RunClock;
+
+TS_FN double dt_fold(double max_dti, const double *max_v, const double *dx, int ndir)
+{
+  TS_NO_CONTRACT
+  int d;
+  for (d = 0; d < ndir; d++) { const double q = max_v[d]/dx[d]; max_dti = (max_dti > q) ? max_dti : q; }
+  return max_dti;
+}
+
+TS_FN void dt_carry(double *cum, const double *max_v, int ndir)
+{
+  int d;
+  for (d = 0; d < ndir; d++) cum[d] = (cum[d] > max_v[d]) ? cum[d] : max_v[d];
+}
+
+TS_FN double dt_fold_level(double max_dti, double *cum, const double *max_v, const double *dx, int ndir)
+{
+  dt_carry(cum, max_v, ndir);
+  return dt_fold(max_dti, cum, dx, ndir);
+}
+
+TS_FN double dt_courant(double cour_no, double max_dti)
+{
+  TS_NO_CONTRACT
+  return cour_no/max_dti;
+}
+
+TS_FN double dt_grow(int nstep, double dt, double dt_cfl)
+{
+  TS_NO_CONTRACT
+  if (nstep == 0) return dt_cfl;
+  return (2.0*dt < dt_cfl) ? 2.0*dt : dt_cfl;
+}
+
+TS_FN double dt_clip(double dt, double time, double tlim)
+{
+  TS_NO_CONTRACT
+  if ((time < tlim) && ((tlim - time) < dt)) dt = tlim - time;
+  return dt;
+}
+
+TS_FN double dt_pick(int nstep, double dt, double dt_cfl, double time, double tlim)
+{
+  return dt_clip(dt_grow(nstep, dt, dt_cfl), time, tlim);
+}
+
+TS_FN int run_live(double time, double t_stop, int nstep, int nstep_stop, double dt)
+{
+  return time < t_stop && nstep != nstep_stop && dt > 0.0;
+}
+
+#endif

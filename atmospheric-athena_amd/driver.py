@@ -220,6 +220,31 @@ def close_root(niter, maxiter, dt, dt_done):
     return dt, dt_done
 
 
+def fold_levels(v, dx, ndir=3):
+    """new_dt.c:33 and :156-161 over the levels of a Mesh: v holds max(|v_d| + a) per level and direction (3 per level), dx the zone
+    sizes per level.  The maxima are carried from level to level (max_v1..3 are zeroed once, in front of the loop over Grids), and
+    every level folds (carried maximum)/dx_d into max_dti over its first ndir directions -> max_dti.  One level: new_dt of a Grid.
+    csrc/time_step.h is the same rule for the library, the kernels and the shim; tests/test_time_step.py scripts both."""
+    cum, max_dti = [0.0, 0.0, 0.0], 0.0
+    for l in range(len(dx)):
+        for d in range(ndir):
+            cum[d] = cum[d] if cum[d] > v[3 * l + d] else v[3 * l + d]
+        for d in range(ndir):
+            q = cum[d] / dx[l][d]
+            max_dti = max_dti if max_dti > q else q
+    return max_dti
+
+
+def pick_dt(nstep, dt, dt_cfl, time, tlim):
+    """new_dt.c:167-185: the CFL step, at most twice the last one (not on step 0) -- MIN(a,b) = (a < b) ? a : b (defs.h.in:146), so a
+    NaN dt_cfl gives NaN, where min() would return 2*dt -- then cut back so that the loop ends at tlim exactly"""
+    if nstep != 0:
+        dt_cfl = 2.0 * dt if 2.0 * dt < dt_cfl else dt_cfl
+    if time < tlim and (tlim - time) < dt_cfl:
+        dt_cfl = tlim - time
+    return dt_cfl
+
+
 def _fetched(fetch):
     """the read-back of a one-kernel sub-cycle (aa_ion_fetch) as subcycles() takes it"""
     dt, hit, _dt_chem, _dt_therm, cellcount, dt_hydro, neg = fetch
@@ -629,9 +654,7 @@ class Driver(_Runner):
 
     def new_dt(self):               # new_dt.c:169-185
         dtc = self._min(self.eng.new_dt_local())[0] if self.distributed else self.eng.new_dt_local()
-        self.dt = dtc if self.nstep == 0 else min(2.0 * self.dt, dtc)
-        if self.time < self.run.tlim and (self.run.tlim - self.time) < self.dt:
-            self.dt = self.run.tlim - self.time
+        self.dt = pick_dt(self.nstep, self.dt, dtc, self.time, self.run.tlim)
         self.eng.set_mesh_state(self.time, self.dt, self.nstep)
 
     def _ion_radtransfer_fused(self) -> int:
@@ -1207,17 +1230,8 @@ class MeshDriver(_Runner):
             v += self.eng.cfl_max_v(l) if self.has(l) else [0.0, 0.0, 0.0]
         if self.distributed:
             v = self._allreduce(v, self.dist.ReduceOp.MAX)
-        cum, max_dti = [0.0, 0.0, 0.0], 0.0
-        for l in range(self.NL):
-            for d in range(3):
-                cum[d] = cum[d] if cum[d] > v[3 * l + d] else v[3 * l + d]
-            for d in range(3):
-                q = cum[d] / (self.run.dx[d] / float(1 << l))
-                max_dti = max_dti if max_dti > q else q
-        dtc = self.run.cour_no / max_dti
-        self.dt = dtc if self.nstep == 0 else min(2.0 * self.dt, dtc)
-        if self.time < self.run.tlim and (self.run.tlim - self.time) < self.dt:
-            self.dt = self.run.tlim - self.time
+        max_dti = fold_levels(v, [[x / float(1 << l) for x in self.run.dx] for l in range(self.NL)])
+        self.dt = pick_dt(self.nstep, self.dt, self.run.cour_no / max_dti, self.time, self.run.tlim)
         for l in range(self.NL):
             self.dtl[l] = self.dt
             if self.has(l):

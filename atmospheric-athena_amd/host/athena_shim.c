@@ -58,6 +58,7 @@
 #include <string.h>
 #include "../../include/athena_compat.h"
 #include "../../include/athena_amd.h"
+#include "../csrc/time_step.h"
 
 /* provided by the driver this shim is linked into (globals.h:14-25, prototypes.h:118,178-184) */
 extern Real CourNo, Gamma, Gamma_1;
@@ -646,15 +647,13 @@ void new_dt(MeshS *pM)
     for (l = 0; l < NL; l++) {
       if (!HAVE(l)) continue;
       CHK(aa_cfl_max_v(G[l], v));
-      { const double dxl[3] = {PG[l]->dx1, PG[l]->dx2, PG[l]->dx3}; int d_;
-        for (d_ = 0; d_ < 3; d_++) { cum[d_] = (cum[d_] > v[d_]) ? cum[d_] : v[d_]; }
-        for (d_ = 0; d_ < 3; d_++) { const double q_ = cum[d_]/dxl[d_]; max_dti = (max_dti > q_) ? max_dti : q_; } }
+      { const double dxl[3] = {PG[l]->dx1, PG[l]->dx2, PG[l]->dx3};
+        max_dti = dt_fold_level(max_dti, cum, v, dxl, 3); }
     }
-    mine = CourNo/max_dti;
-    mine = (pM->nstep == 0) ? mine : ((2.0*pM->dt < mine) ? 2.0*pM->dt : mine);       /* :169-173 before the reduction (:177) */
+    mine = dt_grow(pM->nstep, pM->dt, dt_courant(CourNo, max_dti));                       /* :167-171 before the reduction (:177) */
     MPI_Allreduce(&mine, &all, 1, MPI_DOUBLE, MPI_MIN, MPI_COMM_WORLD);
-    dt = all; t = pM->time; n = pM->nstep;
-    { const double tlim = par_getd("time", "tlim"); if (t < tlim && (tlim - t) < dt) dt = tlim - t; }
+    t = pM->time; n = pM->nstep;
+    dt = dt_clip(all, t, par_getd("time", "tlim"));                                   /* :183-185 */
     for (l = 0; l < NL; l++) if (HAVE(l)) CHK(aa_set_mesh_state(G[l], t, dt, n));
   }
 #elif defined(AA_SMR)
@@ -665,9 +664,8 @@ void new_dt(MeshS *pM)
   { double mine, all;                                /* new_dt.c:159-185 with the MIN over the Grids of the Domain (:177) */
     CHK(aa_new_dt_local(G[0], &mine));
     MPI_Allreduce(&mine, &all, 1, MPI_DOUBLE, MPI_MIN, MPI_COMM_WORLD);
-    dt = (pM->nstep == 0) ? all : ((2.0*pM->dt < all) ? 2.0*pM->dt : all);
     t = pM->time; n = pM->nstep;
-    { const double tlim = par_getd("time", "tlim"); if (t < tlim && (tlim - t) < dt) dt = tlim - t; }
+    dt = dt_pick(n, pM->dt, all, t, par_getd("time", "tlim"));
     CHK(aa_set_mesh_state(G[0], t, dt, n)); }
 #else
   CHK(aa_new_dt(G[0]));

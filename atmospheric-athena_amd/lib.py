@@ -453,6 +453,14 @@ class Grid:
     def step(self) -> int:
         n = C.c_int(); self._chk(self.L.aa_step(self._h, C.byref(n))); return n.value
 
+    def _run(self, call, t_stop, tlim, nstep_stop) -> int:
+        """the arguments of aa_run_1d / aa_run_2d: tlim None is the deck's, nstep_stop None is 2^20 steps ahead -> the steps taken"""
+        n = C.c_int()
+        tlim = self.cfg.run.tlim if tlim is None else tlim
+        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
+        self._chk(call(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
+        return n.value
+
     def run_cap(self) -> int:
         """most active zones of a 1-D Grid that run_until keeps resident in one workgroup (aa_run_1d_cap)"""
         return int(self.L.aa_run_1d_cap())
@@ -465,11 +473,7 @@ class Grid:
         """Whole passes of the main loop on a 1-D Grid in ONE launch (aa_run_1d): until time >= t_stop, nstep == nstep_stop or
         dt <= 0; new_dt clips at tlim (default: the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps
         taken.  AthenaError on a Grid that is not 1-D, is above run_cap() zones or has pinned zones (can_run_until)."""
-        n = C.c_int()
-        tlim = self.cfg.run.tlim if tlim is None else tlim
-        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
-        self._chk(self.L.aa_run_1d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
-        return n.value
+        return self._run(self.L.aa_run_1d, t_stop, tlim, nstep_stop)
 
     def run_2d_batch(self) -> int:
         """steps run_2d queues per read-back on this Grid (AA_2D_BATCH when the Grid was made; 0: it steps one at a time)"""
@@ -484,11 +488,7 @@ class Grid:
         queued per read-back instead of one; until time >= t_stop, nstep == nstep_stop or dt <= 0; new_dt clips at tlim (default:
         the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the same bits as that many step()
         calls.  AthenaError on a Grid that is not 2-D, has pinned zones or is a level of a Mesh (can_run_2d)."""
-        n = C.c_int()
-        tlim = self.cfg.run.tlim if tlim is None else tlim
-        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
-        self._chk(self.L.aa_run_2d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
-        return n.value
+        return self._run(self.L.aa_run_2d, t_stop, tlim, nstep_stop)
 
     # ---- phases ----------------------------------------------------------------------
     def new_dt_local(self) -> float:

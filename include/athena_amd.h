@@ -159,7 +159,9 @@ int aa_integrate_1d_vl(aa_grid *g);                 /* integrate_1d_vl.c        
  * Grid's absolute step count; at most 2^20 steps ahead) or dt <= 0.  The Grid must have been started (aa_start / aa_resume).  The
  * same bits as that many aa_step calls.  *nsteps_done: steps taken.  An error on a Grid that is not 1-D, has more than
  * aa_run_1d_cap() active zones (one workgroup's LDS), or has pinned zones.  AA_1D_RESIDENT=0 in the environment at aa_create:
- * the same call steps one launch at a time.                                                                                   */
+ * the same call steps one launch at a time.  aa_run_1d and aa_run_2d are one body (csrc/run.hip) with the rule of csrc/time_step.h;
+ * the first of them that reaches the device makes the Grid's clock (one page-locked time / dt / nstep / "live" record for both,
+ * and the 2-D call's copy in device memory); a Grid that never calls them allocates none.                                     */
 int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 /* Many steps of a 2-D Grid per host visit (csrc/hydro2d_kernels.hip k2d_advance): the same loop and the same stop rules as aa_run_1d,
  * with the time step picked on the device -- AA_2D_BATCH steps (environment at aa_create; default 32) are queued as plain launches,

@@ -140,6 +140,8 @@ def test_the_knob_and_the_call_are_documented():
     assert "int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);" in hdr
     for doc in ("INTEGRATION.md", "DESIGN.md", "README.md"):
         assert "AA_2D_BATCH" in open(os.path.join(root, doc)).read(), doc
-    # the sources bench.py fingerprints know nothing of the 2-D clock
-    for f in ("grid.h", "hydro_kernels.hip", "hydro_dev.h"):
-        assert "Run2D" not in open(os.path.join(root, "atmospheric-athena_amd", "csrc", f)).read(), f
+    # the sources bench.py fingerprints know nothing of the device clocks and of the header that holds their rule
+    for f in ("grid.h", "hydro_kernels.hip", "hydro_dev.h", "ion_kernels.hip", "ion_pass.hip", "ion_dev.h"):
+        text = open(os.path.join(root, "atmospheric-athena_amd", "csrc", f)).read()
+        for word in ("Run2D", "RunClock", "time_step.h"):
+            assert word not in text, (f, word)
