@@ -101,6 +101,11 @@ static int launch_cfg_read(const aa_params &p, LaunchCfg &c)
   c.ion_fused = on(env("AA_ION_FUSED", UNSET), p.Nx[0] >= 48);
   c.ion_begin_fused = on(env("AA_ION_BEGIN_FUSED", UNSET), true);
   c.ion_spec_on = on(env("AA_ION_SPECULATE", UNSET), true);
+  // the speculating first pass without the entry's dense saves (k_ion_pass<LEAN>): auto = behind a step whose speculation stood
+  // after one sub-cycle (the stationary regime); same results bit for bit either way
+  { const char *e = getenv("AA_ION_LEAN");
+    c.ion_lean = (!e || !strcmp(e, "auto")) ? -1 : (!strcmp(e, "0") ? 0 : (!strcmp(e, "1") ? 1 : 2));
+    if (c.ion_lean == 2) return fail(-1, "[aa_create]: AA_ION_LEAN=%s: must be auto, 0 or 1", e); }
   // ---- not a launch choice of a kernel of the step, kept here all the same: floats per half of the dumps' bounce buffer
   c.dump_chunk = env("AA_DUMP_CHUNK_FLOATS", 1 << 23); if (c.dump_chunk < 4) c.dump_chunk = 4; if (c.dump_chunk > (1 << 28)) c.dump_chunk = 1 << 28;
   return 0;
@@ -220,7 +225,8 @@ int aa_create(const aa_params *p, aa_grid **out)
   g->ion_fused = p->ion && (p->ion_path ? p->ion_path == 1 : d.cfg.ion_fused);      // (the caller's choice goes before the knob and the size)
   const size_t nrays = (size_t)d.Nx2*d.Nx3;
   if (p->ion) n += nc*6 + nef;
-  if (g->ion_fused) n += 2*nc + 2*nrays;
+  const size_t nlean = nrays*(size_t)((d.Nx1 + 63)/64);      // one ballot word per ray and 64-zone tile (k_ion_pass<LEAN>)
+  if (g->ion_fused) n += 2*nc + 2*nrays + nlean;
   if (p->order != 0 && p->order != 2 && p->order != 3) { delete g; return fail(-1, "[aa_create]: order %d (2: PLM, 3: PPM)", p->order); }
   if (p->order == 3 && !one_d) n += nc*18;      // (the 1-D kernels keep the slopes in LDS)
   g->pool_doubles = n;
@@ -243,7 +249,7 @@ int aa_create(const aa_params *p, aa_grid **out)
     d.sign = (int2*)q; q += nc; d.edgeflux = q; q += nef;
     d.sg16 = (unsigned short*)d.sign;                  // the fused path keeps its 2-byte sign words in the same storage
     d.fin[0] = d.ph_rate; d.fin[1] = d.ph_rate;
-    if (g->ion_fused) { d.fin[1] = q; q += nc; d.s_init = q; q += nc; d.raylast = q; q += 2*nrays; }
+    if (g->ion_fused) { d.fin[1] = q; q += nc; d.s_init = q; q += nc; d.raylast = q; q += 2*nrays; d.lean_mask = (unsigned long long*)q; q += nlean; }
     IonPar &ip = g->ion;
     ip.sigma_ph = p->sigma_ph; ip.m_H = p->m_H; ip.mu = p->mu; ip.e_gamma = p->e_gamma; ip.alpha_C = p->alpha_C;
     ip.k_B = p->k_B; ip.time_unit = p->time_unit;
@@ -273,7 +279,8 @@ int aa_create(const aa_params *p, aa_grid **out)
   g->sc_host = &g->mb->s;
   if (hipHostGetDevicePointer((void**)&g->mb_dev, g->mb, 0) != hipSuccess) { (void)hipGetLastError(); g->mb_dev = nullptr; d.cfg.mailbox = 0; }
   if (g->ion_fused) {
-    if (hipMalloc(&g->ion_part, (size_t)ion_pass_blocks(d)*sizeof(IonPart)) != hipSuccess ||
+    // (records of a pass | a second set nobody folds: k_ion_pass<LEAN>'s way back)
+    if (hipMalloc(&g->ion_part, (size_t)2*ion_pass_blocks(d)*sizeof(IonPart)) != hipSuccess ||
         hipMalloc(&g->ion_words, AA_ION_WORDS*sizeof(Real)) != hipSuccess) {
       hipFree(g->pool); hipFree(g->sc); hipHostFree(g->mb); delete g; return fail(-2, "[aa_create]: ion reduction buffers");
     }
@@ -281,7 +288,7 @@ int aa_create(const aa_params *p, aa_grid **out)
   // (every word of these is written before it is read; zeroed all the same, so that no run ever depends on what a freed
   //  allocation of an earlier Grid left behind)
   (void)hipMemset(g->sc, 0, sizeof(DevScalars));
-  if (g->ion_part) (void)hipMemset(g->ion_part, 0, (size_t)ion_pass_blocks(d)*sizeof(IonPart));
+  if (g->ion_part) (void)hipMemset(g->ion_part, 0, (size_t)2*ion_pass_blocks(d)*sizeof(IonPart));
   if (g->ion_words) (void)hipMemset(g->ion_words, 0, AA_ION_WORDS*sizeof(Real));
   hipStreamCreate(&g->st); g->own_stream = true;
   *out = g;
@@ -329,6 +336,7 @@ int aa_upload_cons(aa_grid *g, const double *U)
 {
   g->cfl_ready = false; g->active_dirty = false;      // (host and device agree on the active zones from here on)
   g->inner_swept = false;          // the state changes under a pending aa_integrate_begin: its sweeps are redone
+  ion_lean_forget(g);
   if (!g->slab.empty()) return slabs_upload_cons(g, U);
   const int nvar = 5 + g->p.nscal; const size_t n = (size_t)g->d.N1*g->d.N2*g->d.N3*nvar;
   HIPCHK(hipMemcpyAsync(g->d.LR, U, n*sizeof(Real), hipMemcpyHostToDevice, g->st));
@@ -903,6 +911,7 @@ int aa_ion_begin(aa_grid *g)
     // (a sweep of the previous ion step that nobody asked for is dropped here: its buffers are about to be reused)
     g->ion_cur = 0; g->ion_pending = false; g->ef_stale = false;
     g->ion_spec_dt = -1.0; g->ion_spec_armed = false;
+    g->ion_step_spec = g->ion_step_lean = false; g->ion_step_updates = 0;
     if (g->d.cfg.ion_begin_fused) { g->ion_begin_due = true; return 0; }       // rides on the first pass
     Scope s(g, "ion_begin");
     launch_ion_begin16(g->d, g->ion, g->st);
@@ -1022,9 +1031,18 @@ int aa_ion_pass(aa_grid *g, int update, int sweep, double *dev_words)
   const Real spec_dt = (begin && g->ion_spec_dt >= 0.0) ? g->ion_spec_dt : -1.0;
   if (!update) g->ion_spec_armed = spec_dt >= 0.0;
   g->ion_spec_dt = -1.0;
+  // which form a speculating first pass takes (LaunchCfg ion_lean) ...
+  const bool lean = spec_dt >= 0.0 && (g->d.cfg.ion_lean == 1 || (g->d.cfg.ion_lean < 0 && g->ion_lean_next));
+  if (!update && begin) { g->ion_step_spec = spec_dt >= 0.0; g->ion_step_lean = lean; if (spec_dt >= 0.0) g->ion_lean_n[lean ? 1 : 0]++; }
+  if (update) g->ion_step_updates++;
+  // ... and the lean form's way back, in front of the first updating pass (ion_spec_armed: until the pick behind it): one launch that
+  // leaves at once unless the pick refuted the speculation (spec_state 2); it sweeps into the buffer the first pass filled (ion_cur
+  // has just moved on) and counts with the updating pass's stage
+  const bool redo = update && g->ion_spec_armed && g->ion_step_lean;
   { Scope s(g, update ? (sweep ? "ion_pass" : "ion_pass_last") : (begin ? "ion_pass_begin" : "ion_pass_first"));
+    if (redo) launch_ion_lean_redo(g->d, g->ion, flux0, g->level > 0 && g->nradplane > 0, g->sc, g->ion_cur ^ 1, g->ion_part + ion_pass_blocks(g->d), g->st);
     launch_ion_pass(g->d, g->ion, update != 0, sweep != 0, begin, flux0, g->level > 0 && g->nradplane > 0, g->sc, g->ion_cur,
-                    g->ion_part, dev_words ? dev_words : g->ion_words, g->st, spec_dt, !g->ion_fuse_pick); }
+                    g->ion_part, dev_words ? dev_words : g->ion_words, g->st, spec_dt, !g->ion_fuse_pick, lean); }
   if (sweep) g->ion_pending = true;
   HIPCHK(hipGetLastError());
   return 0;
@@ -1091,7 +1109,22 @@ int aa_ion_finish(aa_grid *g)
   if (!g->ion_fused) return 0;
   if (!g->slab.empty()) return slabs_ion_finish(g);
   g->ion_pending = false;
+  g->ion_lean_next = g->ion_step_spec && g->ion_step_updates == 1;      // (a guess at the next step's regime, not a condition of anything)
   g->ef_stale = true;
+  return 0;
+}
+// speculating first passes queued so far in the dense and in the lean form, and lean ones that were refuted and redone densely
+// (counted on the device: this call waits for the stream); a Grid cut into slabs: slab 0's, every slab counts the same
+int aa_ion_lean_counts(aa_grid *g, long long *n)
+{
+  if (!g->ion_fused) { n[0] = n[1] = n[2] = 0; return 0; }
+  aa_grid *c = g->slab.empty() ? g : g->slab[0];
+  DevGuard keep;
+  HIPCHK(hipSetDevice(c->p.device));
+  DevScalars s;
+  HIPCHK(hipStreamSynchronize(c->st));
+  HIPCHK(hipMemcpy(&s, c->sc, sizeof(DevScalars), hipMemcpyDeviceToHost));
+  n[0] = c->ion_lean_n[0]; n[1] = c->ion_lean_n[1]; n[2] = s.lean_redone;
   return 0;
 }
 } // extern "C"

@@ -35,6 +35,11 @@ struct aa_grid {
   bool cfl_in_update = false;          // aa_cfl_in_update: the integrator also leaves new_dt's maxima behind
   double ion_spec_dt = -1.0, ion_spec_limit = 0.0;   // aa_ion_speculate: armed for the next first pass / what it was told
   bool ion_spec_armed = false;         //   ... the first pass has speculated: aa_ion_pick(first) settles it
+  // the lean form of the speculating first pass (k_ion_pass<LEAN>; LaunchCfg ion_lean): what this ion step is doing ...
+  bool ion_step_spec = false, ion_step_lean = false;   // its first pass speculated / did so in the lean form
+  int ion_step_updates = 0;            // updating passes queued since aa_ion_begin = sub-cycles
+  bool ion_lean_next = false;          // ... and what aa_ion_finish made of it: the step speculated and took ONE sub-cycle, so the next one is lean under `auto`
+  long long ion_lean_n[2] = {0, 0};    // speculating first passes queued so far: dense, lean (aa_ion_lean_counts)
   bool cfl_ready = false;              //   ... and has done so for the state as it is now (aa_step arms it by itself: LaunchCfg cfl_step)
   bool active_dirty = true;            // a call since the last full upload / download of U wrote ACTIVE zones on the device (aa_download_ghost_zones then moves the whole block)
   bool grav = false;
@@ -198,6 +203,8 @@ void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevS
 void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
 }
 
+// new state from outside (an upload, a restart section): the next ion step's speculating entry is the dense one
+static inline void ion_lean_forget(aa_grid *g) { g->ion_lean_next = false; for (aa_grid *c : g->slab) c->ion_lean_next = false; }
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }
 static inline unsigned long long double_to_bits(double x) { unsigned long long b; memcpy(&b, &x, 8); return b; }
 // new_dt's maxima as the kernels left them, for time_step.h

@@ -83,7 +83,8 @@ struct DevScalars {
   // the first pass of an ion step may already have applied the update with the whole step (k_ion_pass<BEG>, spec_dt):
   // 1 = k_ion_pick2 found that step to be the one (the closing update pass has nothing left to do), 2 = it was not (the
   // next pass starts again from e_init / s_init), 0 otherwise
-  int spec_state, pad2;
+  int spec_state;
+  int lean_redone;                   // lean first passes that were refuted and redone densely (k_ion_pass<LEAN>; counted, never read on the device)
   // first-order flux correction of the van Leer integrator (aa_set_fofc; integrate_3d_vl.c Steps 10 and 14), per step:
   // zones the update left with d < 0 (appended to the candidate list), whether a flux the update read was NaN, what the
   // fix kernel counted while it replayed the reference's scan, the fluxes k_fofc_nanfix replaced, list overflow
@@ -128,10 +129,12 @@ struct LaunchCfg {
   bool ion_fused = false;    // AA_ION_FUSED: the one-kernel radiation sub-cycle (ion_pass.hip): rays of 48 zones or more (aa_params.ion_path goes first)
   bool ion_begin_fused = true;  // AA_ION_BEGIN_FUSED=0: the entry of the ion step as k_ion_begin16 on its own instead of on the first pass
   bool ion_spec_on = true;   // AA_ION_SPECULATE=0: the first pass of an ion step never applies an update
+  int ion_lean = -1;         // AA_ION_LEAN: the speculating first pass without the entry's dense saves (k_ion_pass<LEAN>): auto (-1): behind a step
+                             //   whose speculation stood after one sub-cycle; 0: never; 1: every speculating step
   int dump_chunk = 1 << 23;  // AA_DUMP_CHUNK_FLOATS: floats per half of the dumps' bounce buffer (4 .. 2^28; dump.hip)
 };
 // the descriptor as the host keeps it: what the kernels get (DevGrid, passed by value: the launch slices it off) + the launch choices
-struct HostGrid : DevGrid { LaunchCfg cfg; };
+struct HostGrid : DevGrid { LaunchCfg cfg; unsigned long long *lean_mask = nullptr; };     // lean_mask: k_ion_pass<LEAN>, Nx2*Nx3*ceil(Nx1/64) words
 
 // ---- run-time value -> template argument (host side of the kernel files).  A launcher that picks a kernel instantiation by a
 // run-time int / bool hands a generic lambda to one of these; the lambda's parameter is a std::integral_constant, which converts to
@@ -182,7 +185,8 @@ void launch_ion_begin16(const DevGrid &g, const IonPar &p, hipStream_t st);
 // [entry of the ion step: floors, save_energy_and_x, if `begin`;] update(n-1) with sc->dt_sel, then sweep(n) + rates(n)
 // into buffer cur^1; folds the records into `words`
 void launch_ion_pass(const HostGrid &g, const IonPar &p, bool update, bool sweep, bool begin, Real flux0, bool from_edgeflux,
-                     const DevScalars *sc, int cur, IonPart *part, Real *words, hipStream_t st, Real spec_dt = -1.0, bool reduce = true);
+                     const DevScalars *sc, int cur, IonPart *part, Real *words, hipStream_t st, Real spec_dt = -1.0, bool reduce = true, bool lean = false);
+void launch_ion_lean_redo(const HostGrid &g, const IonPar &p, Real flux0, bool from_edgeflux, const DevScalars *sc, int cur, IonPart *scratch, hipStream_t st);
 void launch_ion_pick2(const Real *words, int nranks, DevScalars *sc, int first, Real dt_limit, hipStream_t st, int spec_armed = 0);
 // one rank: the fold of the pass's records (k_ion_reduce) and the pick in ONE launch; launch_ion_pass(..., reduce = false) goes before it
 void launch_ion_reduce_pick(const HostGrid &g, const IonPart *part, Real *words, DevScalars *sc, int first, Real dt_limit, hipStream_t st, int spec_armed,

@@ -263,7 +263,7 @@ AA_DEV void zone_rates(const Cell &c, const IonQ &iq, const Therm &th, Real ph, 
 AA_DEV Real zone_ph(Real fin, Real etau, Real n_H, Real inv_len)      // ionradplane_3d.c:296; 0 behind the cut-off
 { return (fin == 0.0) ? 0.0 : fin * (1.0 - etau) * frcp_n(n_H) * inv_len; }
 
-struct Ops { Real d, ke, E, s, fp, e0, x0, vm; unsigned short sg; };
+struct Ops { Real d, ke, E, s, fp, e0, x0, vm; unsigned short sg; bool saved; };      // saved: LEAN's second use alone
 
 // waves per SIMD the register budget is cut for.  With OCML's exp / log and IEEE divisions the full pass needed 3 waves
 // plus a software prefetch of the next tile (157 VGPRs); with the table-driven exp / log it fits 4 waves without the
@@ -277,10 +277,23 @@ struct Ops { Real d, ke, E, s, fp, e0, x0, vm; unsigned short sg; };
 #endif
 // BEG: the first pass of an ion step also does the step's entry -- floors, save_energy_and_x, the frozen kinetic
 // energy and max|v| (ionrad_3d.c:896-905; k_ion_begin16's arithmetic, bit for bit) -- on the zones it reads anyway
-template <bool UPD, bool SWP, bool BEG>
+// LEAN (an instantiation of its own beside the BEG one, whose instructions stay what they were): the speculating entry for a step that is expected
+// to be confirmed, as the one before it was.  Every dense store of the entry -- e_init, x_init, kin, vmax, s_init, the sign word --
+// is read by an updating pass of the SAME ion step only, and in a confirmed step none runs: 40 B/zone written for nothing.  The
+// lean pass stores none of them.  Where it overwrites U's E or s it first puts the values U held (as loaded, before the floors)
+// into the zone's e_init / s_init slots, and lane 0 stores the tile's ballot of "this lane overwrote U" (lmask, one 64-bit word
+// per ray and tile): it saves exactly what it destroys.
+//   The same instantiation with spec_dt < 0 is the way back for a lean speculation that was refuted: queued once in front of
+// the first updating pass, it leaves at once unless spec_state == 2, takes E and s from the saved slots where the tile's bit is
+// set, and then IS the non-speculating entry -- same source, same operands -- with every dense store, s_init among them, and
+// U's E and s put back to the floored entry values.  The updating pass behind it (spec_state still 2: from e_init / s_init)
+// finds what the dense form would have left.  Its block records go to a slot nobody folds: the pick has been made from the same numbers.
+template <bool UPD, bool SWP, bool BEG, bool LEAN = false>
 __global__ void __launch_bounds__(256, (UPD && SWP) ? AA_ION_PASS_WAVES : AA_ION_PASS_WAVES_HALF)
-k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScalars *sc, int cur, IonPart *part, int only_if_hit, Real spec_dt)
+k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScalars *sc, int cur, IonPart *part, int only_if_hit, Real spec_dt,
+           unsigned long long *lmask)
 {
+  static_assert(!LEAN || (BEG && SWP && !UPD), "the lean form is a first pass");
   // an updating pass is launched in both forms -- with and without the sweep of a further sub-cycle -- and the one
   // that does not match what the device picked (sc->limit_hit; the host has not read it yet) leaves at once
   if (UPD && only_if_hit >= 0 && (sc->limit_hit != 0) != (only_if_hit != 0)) return;
@@ -293,6 +306,11 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
   // k_ion_pick2 books; if not (2), the next pass starts from the state the entry saved (e_init, s_init) and writes
   // every zone back.  One pass per step instead of two where the radiation is quiet.
   const bool spec = BEG && spec_dt >= 0.0;
+  const bool redo = LEAN && !spec;              // the refuted lean speculation's way back (wave-uniform, as spec is)
+  if (LEAN && redo) {
+    if (sc->spec_state != 2) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) const_cast<DevScalars*>(sc)->lean_redone++;      // (aa_ion_lean_counts; nothing on the device reads it)
+  }
   const int spec_state = UPD ? sc->spec_state : 0;
   if (UPD && !SWP && spec_state == 1) return;
   const bool from_init = UPD && spec_state == 2;
@@ -325,18 +343,22 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
     const unsigned kk = ray_ / (unsigned)g.Nx2, jj = ray_ - kk*(unsigned)g.Nx2;
     return (long)(g.ks + (int)kk)*g.sK + (long)(g.js + (int)jj)*g.sJ + g.is;
   };
-  auto load = [&](long row_, int t_, Ops &o, long &m_, bool &in_) {
+  auto load = [&](unsigned ray_, long row_, int t_, Ops &o, long &m_, bool &in_) {
     const int ii = 64*t_ + lane;
     in_ = (ii < g.Nx1);
     m_ = row_ + ii;
     // lanes past the end of the row take part in the shuffles with harmless operands
-    o.d = 1.0; o.ke = 0.0; o.E = 1.0; o.s = 1.0; o.fp = 0.0; o.e0 = 1.0; o.x0 = 0.5; o.vm = 0.0; o.sg = 1;
+    o.d = 1.0; o.ke = 0.0; o.E = 1.0; o.s = 1.0; o.fp = 0.0; o.e0 = 1.0; o.x0 = 0.5; o.vm = 0.0; o.sg = 1; o.saved = false;
     if (in_) {
       o.d = Uq(g,0)[m_]; o.E = Uq(g,4)[m_]; o.s = Uq(g,5)[m_];
       if (BEG) { o.fp = Uq(g,1)[m_]; o.e0 = Uq(g,2)[m_]; o.x0 = Uq(g,3)[m_]; }      // the momenta, in the slots UPD would use
       else { o.ke = g.kin[m_]; o.sg = g.sg16[m_]; }
       if (UPD) { o.fp = fprev[m_]; o.e0 = g.e_init[m_]; o.x0 = g.x_init[m_]; o.vm = g.vmax[m_]; }
       if (from_init) { o.E = o.e0; o.s = g.s_init[m_]; }      // (U holds the update that turned out too long)
+      if (LEAN && redo) {                                     // (... and here only where the lean pass said so)
+        o.saved = (lmask[(long)ray_*ntile + t_] >> lane) & 1ull;
+        if (o.saved) { o.E = g.e_init[m_]; o.s = g.s_init[m_]; }
+      }
     }
   };
 
@@ -345,7 +367,7 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
   int t = 0;
   bool have = ray < nrays_u;
   Ops o; long m = 0, row = 0; bool in = false;
-  if (have) { row = row_of(ray); load(row, 0, o, m, in); }
+  if (have) { row = row_of(ray); load(ray, row, 0, o, m, in); }
   Real carry = 0.0, cut = 0.0;
   bool dead = false;
   while (have) {
@@ -378,11 +400,14 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
       if (floored) qb = ion_q(c, p, g.Gamma_1);
       if (in) {
         if (!spec) {
-          if (c.E != E0) Uq(g,4)[m] = c.E;
-          if (c.s != s0) Uq(g,5)[m] = c.s;
-        } else g.s_init[m] = c.s;
-        g.e_init[m] = c.E; g.x_init[m] = qb.x; g.kin[m] = c.ke;
-        g.vmax[m] = rmax(rmax(fabs(M1*die), fabs(M2*die)), fabs(M3*die));
+          if ((LEAN && o.saved) || c.E != E0) Uq(g,4)[m] = c.E;
+          if ((LEAN && o.saved) || c.s != s0) Uq(g,5)[m] = c.s;
+          if (LEAN) g.s_init[m] = c.s;
+        } else if (!LEAN) g.s_init[m] = c.s;
+        if (!LEAN || !spec) {
+          g.e_init[m] = c.E; g.x_init[m] = qb.x; g.kin[m] = c.ke;
+          g.vmax[m] = rmax(rmax(fabs(M1*die), fabs(M2*die)), fabs(M3*die));
+        }
       }
       e_here = c.E; x_here = qb.x; vm_here = rmax(rmax(fabs(M1*die), fabs(M2*die)), fabs(M3*die));
       sg = make_int2(0, 0); sg_new = true;
@@ -438,13 +463,14 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
         dt_chem_min = rmin(dt_chem_min, dtc);
         dt_therm_min = rmin(dt_therm_min, dtt);
         fnext[m] = fin;
-        if (sg_new || sg.x != sg0.x || sg.y != sg0.y) g.sg16[m] = sg_pack(sg);
+        if (!(LEAN && spec) && (sg_new || sg.x != sg0.x || sg.y != sg0.y)) g.sg16[m] = sg_pack(sg);
       }
       if (BEG && spec) {        // the update of the first sub-cycle with the whole step, as the UPD branch above would do it next pass
         const Real e0 = e_here, x0 = x_here, vm = vm_here;    // = e_init, x_init, vmax of this zone (BEG keeps the momenta in o.fp, o.e0, o.x0)
         zone_update(c, q, th, ph, sg.y, spec_dt, p);
         q = zone_q(c, di, p, g.Gamma_1);
         if (zone_floors(c, q, p, g.Gamma_1)) q = zone_q(c, di, p, g.Gamma_1);
+        bool wrote = false;
         if (in) {
           if (out_of_range(c, q, ph, e0, x0, p)) cnt++;
           const Real pp = rmax(g.Gamma_1*(c.E - c.ke), AA_TINY);
@@ -456,8 +482,16 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
             t3 = rmax(rmax((v1 + a)*p.inv_dx[0], (v2 + a)*p.inv_dx[1]), (v3 + a)*p.inv_dx[2]);
           }
           if (t3 == t3) dti = rmax(dti, t3);
+          if (LEAN) {
+            wrote = (c.E != E0) || (c.s != s0);
+            if (wrote) { g.e_init[m] = E0; g.s_init[m] = s0; }
+          }
           if (c.E != E0) Uq(g,4)[m] = c.E;
           if (c.s != s0) Uq(g,5)[m] = c.s;
+        }
+        if (LEAN) {
+          const unsigned long long w = __ballot(wrote);
+          if (lane == 0) lmask[(long)ray*ntile + t] = w;
         }
       }
       if (t == ntile - 1 && lane == 0) g.raylast[(long)(cur ^ 1)*nrays + ray] = dead ? 0.0 : carry;   // :308
@@ -466,7 +500,7 @@ k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScal
       if (from_init || c.E != E0) Uq(g,4)[m] = c.E;
       if (from_init || c.s != s0) Uq(g,5)[m] = c.s;
     }
-    if (nhave) load(nrow, nt, no, nm, nin);
+    if (nhave) load(nray, nrow, nt, no, nm, nin);
     ray = nray; t = nt; have = nhave; row = nrow; o = no; m = nm; in = nin;
   }
 
@@ -674,19 +708,25 @@ void launch_ion_reduce_pick(const HostGrid &g, const IonPart *part, Real *words,
                             Mailbox *mb_dev, unsigned long long seq)
 { hipLaunchKernelGGL(k_ion_reduce_pick, dim3(1), dim3(256), 0, st, part, ion_pass_blocks(g), words, sc, first, dt_limit, spec_armed, mb_dev, seq); }
 void launch_ion_pass(const HostGrid &g, const IonPar &p, bool update, bool sweep, bool begin, Real flux0, bool from_edgeflux,
-                     const DevScalars *sc, int cur, IonPart *part, Real *words, hipStream_t st, Real spec_dt, bool reduce)
+                     const DevScalars *sc, int cur, IonPart *part, Real *words, hipStream_t st, Real spec_dt, bool reduce, bool lean)
 {
   const int nb = ion_pass_blocks(g);
   const dim3 grid(nb), blk(256);
   const int fe = from_edgeflux ? 1 : 0;
   if (update && sweep) {
-    hipLaunchKernelGGL((k_ion_pass<true, true, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 0, -1.0);
-    hipLaunchKernelGGL((k_ion_pass<true, false, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 1, -1.0);
+    hipLaunchKernelGGL((k_ion_pass<true, true, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 0, -1.0, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL((k_ion_pass<true, false, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 1, -1.0, (unsigned long long*)nullptr);
   }
-  else if (sweep && begin) hipLaunchKernelGGL((k_ion_pass<false, true, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, spec_dt);
-  else if (sweep)      hipLaunchKernelGGL((k_ion_pass<false, true, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, -1.0);
-  else                 hipLaunchKernelGGL((k_ion_pass<true, false, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, -1.0);
+  else if (sweep && begin && lean) hipLaunchKernelGGL((k_ion_pass<false, true, true, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, spec_dt, g.lean_mask);
+  else if (sweep && begin) hipLaunchKernelGGL((k_ion_pass<false, true, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, spec_dt, (unsigned long long*)nullptr);
+  else if (sweep)      hipLaunchKernelGGL((k_ion_pass<false, true, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, -1.0, (unsigned long long*)nullptr);
+  else                 hipLaunchKernelGGL((k_ion_pass<true, false, false>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, -1, -1.0, (unsigned long long*)nullptr);
   if (reduce) hipLaunchKernelGGL(k_ion_reduce, dim3(1), dim3(256), 0, st, part, nb, words);
+}
+// the way back of a lean first pass (k_ion_pass<LEAN>, spec_dt < 0): the same sweep into the same buffer, records into `scratch`
+void launch_ion_lean_redo(const HostGrid &g, const IonPar &p, Real flux0, bool from_edgeflux, const DevScalars *sc, int cur, IonPart *scratch, hipStream_t st)
+{
+  hipLaunchKernelGGL((k_ion_pass<false, true, true, true>), dim3(ion_pass_blocks(g)), dim3(256), 0, st, g, p, flux0, from_edgeflux ? 1 : 0, sc, cur, scratch, -1, -1.0, g.lean_mask);
 }
 void launch_ion_pick2(const Real *words, int nranks, DevScalars *sc, int first, Real dt_limit, hipStream_t st, int spec_armed)
 { hipLaunchKernelGGL(k_ion_pick2, dim3(1), dim3(1), 0, st, words, nranks, sc, first, dt_limit, spec_armed); }

@@ -365,6 +365,7 @@ int aa_rst_section_put(aa_grid *g, int section, const double *host)
 {
   if (!g || !host) return aa_fail(-1, "[aa_rst_section_put]: null argument");
   if (section < 0 || section >= rst_nsections(g)) return aa_fail(-1, "[aa_rst_section_put]: section %d of %d", section, rst_nsections(g));
+  ion_lean_forget(g);
   if (!g->slab.empty()) return slabs_rst_section(g, section, const_cast<double*>(host), 1);
   return rst_section_grid(g, section, const_cast<double*>(host), rst_doubles(g, section), 1);
 }
@@ -373,7 +374,7 @@ int aa_rst_section_get_box(aa_grid *g, int section, const int lo[3], const int n
 { return rst_box_call("aa_rst_section_get_box", g, section, lo, n, host, 0); }
 
 int aa_rst_section_put_box(aa_grid *g, int section, const int lo[3], const int n[3], const double *host)
-{ return rst_box_call("aa_rst_section_put_box", g, section, lo, n, const_cast<double*>(host), 1); }
+{ if (g) ion_lean_forget(g); return rst_box_call("aa_rst_section_put_box", g, section, lo, n, const_cast<double*>(host), 1); }
 
 // ---- snapshots: the whole payload made by one kernel and one device copy, brought to the host beside the run (see athena_amd.h).
 // The route of aa_dump_snapshot_* (dump.hip) on the same stream of copies; one slot, in doubles.

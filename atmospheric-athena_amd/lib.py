@@ -108,7 +108,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
         "aa_ion_update": (I, [P, D, llp, dp]),
         "aa_ion_is_fused": (I, [P]), "aa_ion_speculate": (I, [P, D]), "aa_ion_pass": (I, [P, I, I, P]), "aa_ion_pick": (I, [P, P, I, I, D]),
-        "aa_ion_fetch": (I, [P, dp, ip, dp, dp, llp, dp, ip]), "aa_ion_finish": (I, [P]),
+        "aa_ion_fetch": (I, [P, dp, ip, dp, dp, llp, dp, ip]), "aa_ion_finish": (I, [P]), "aa_ion_lean_counts": (I, [P, llp]),
         "aa_ion_radtransfer_3d_gather": (I, [P, P, P, I, GATHER, P, ip]), "aa_host_syncs": (I, [P, I]),
         "aa_halo_doubles": (LL, [P]), "aa_pack_x3": (I, [P, I, P]), "aa_unpack_x3": (I, [P, I, P]),
         "aa_halo_doubles_x2": (LL, [P]), "aa_pack_x2": (I, [P, I, P]), "aa_unpack_x2": (I, [P, I, P]),
@@ -144,7 +144,10 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_profile_enable": (I, [P, I]), "aa_profile_reset": (I, [P]), "aa_profile_count": (I, [P]),
         "aa_profile_name": (C.c_char_p, [P, I]), "aa_profile_get": (I, [P, I, dp, llp]),
     }
+    variant = name not in ("libathena_amd_strict.so", "libathena_amd.so")
     for name_, (res, args) in sig.items():
+        if variant and not hasattr(L, name_):
+            continue                   # (an A/B build of older sources lacks what was added since)
         f = getattr(L, name_)          # AttributeError here = header and library disagree
         f.restype = res; f.argtypes = args
     L._sig = sig
@@ -521,6 +524,12 @@ class Grid:
         return dt.value, bool(hit.value), a.value, b.value, n.value, h.value, bool(neg.value)
 
     def ion_finish(self): self._chk(self.L.aa_ion_finish(self._h))
+
+    def ion_lean_counts(self):
+        """(dense, lean, redone): speculating first passes in either form, and lean ones that were refuted (AA_ION_LEAN)."""
+        n = (C.c_longlong * 3)()
+        self._chk(self.L.aa_ion_lean_counts(self._h, n))
+        return tuple(int(v) for v in n)
 
     def ion_radtransfer_3d_gather(self, dev_words: int, dev_words_all: int, nranks: int, gather) -> int:
         """ion_radtransfer_3d of one rank of a multi-rank run in ONE call: `gather()` is the driver's all-gather of the

@@ -222,6 +222,9 @@ int aa_ion_pick(aa_grid *g, const double *dev_words_all, int nranks, int first, 
 int aa_ion_fetch(aa_grid *g, double *dt, int *limit_hit, double *dt_chem, double *dt_therm, long long *cellcount,
                  double *dt_hydro, int *neg_dt_chem);
 int aa_ion_finish(aa_grid *g);
+/* The speculating first pass has two forms (AA_ION_LEAN; same results bit for bit): n[0], n[1] = first passes queued so far in the dense
+ * and in the lean form, n[2] = lean ones the pick refuted, which were then redone densely.  Waits for the Grid's stream.            */
+int aa_ion_lean_counts(aa_grid *g, long long *n);
 /* ion_radtransfer_3d (ionrad_3d.c:862-1047, root level) of a rank of a multi-rank run in ONE call: the loop above with the
  * driver's collective as a callback.  `gather(ctx)` must all-gather this rank's AA_ION_WORDS doubles at dev_words into
  * dev_words_all (nranks x AA_ION_WORDS, DEVICE memory) on the Grid's stream and return 0; it is called once per pass, between
