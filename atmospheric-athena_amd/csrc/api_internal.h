@@ -203,6 +203,26 @@ void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevS
 void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
 }
 
+// run.hip: the frame the run calls share -- aa_run_1d / aa_run_2d for a Grid, aa_mesh_run_2d (smr.hip) for a Mesh of 2-D Grids: the
+// refusals of span and tlim, the loop over single steps (stepwise), else begin -> { batch, synchronise `st`, read the clock } while it
+// is live -> the host's time / dt / nstep from the clock -> end.
+struct RunOps {
+  const char *who, *owner;             // the entry's name for its messages; "Grid" / "root": whose tlim new_dt clips at
+  void *self;
+  double *time, *dt; int *nstep;       // the host's MeshS
+  double tlim;
+  bool stepwise;
+  int (*step)(void *self);             // one aa_step / aa_mesh_step
+  int (*begin)(void *self, const RunClock &seed, double t_stop, double tlim, int nstep_stop, RunClock **clock);   // the clock buffers, the call's clock; *clock: the page-locked one the host reads
+  int (*batch)(void *self, double t_stop, double tlim, int nstep_stop);   // the launches between two reads of the clock
+  void (*end)(void *self);             // (may be null) the host's clock has been set
+  hipStream_t st; int *host_syncs;
+};
+int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+// run.hip: the integrator's chain of a 2-D Grid on the device clock `rc`, on g->st (a level of a Mesh: the flux-keeping update kernel;
+// sc == nullptr: without new_dt's maxima)
+void queue_chain_2d(aa_grid *g, const aa::Run2D *rc, aa::DevScalars *sc);
+
 // new state from outside (an upload, a restart section): the next ion step's speculating entry is the dense one
 static inline void ion_lean_forget(aa_grid *g) { g->ion_lean_next = false; for (aa_grid *c : g->slab) c->ion_lean_next = false; }
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }

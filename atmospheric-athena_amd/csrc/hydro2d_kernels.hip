@@ -461,6 +461,48 @@ k2d_advance(Run2D *rc, DevScalars *sc, Real dx0, Real dx1, RunClock *out)
   rc->c = c; *out = c;
 }
 
+// ---- the Grids of a 2-D Mesh on one clock (aa_mesh_run_2d, csrc/smr.hip) ----------------------------------------------------------
+// k2d_step_keep behind the clock load: KeepPlanes stays a by-value argument, c1 and c2 are the bits launch_step_keep forms on the host
+template <int MODE, bool CFL>
+__global__ void __launch_bounds__(T2_W*T2_R)
+k2d_step_keep_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc, KeepPlanes kp)
+{
+  if (!rc->c.live) return;
+  const Real dt = rc->c.dt;
+  step_body<MODE, CFL, true>(g, dt, dt_over_dx(dt, g.dx[0]), dt_over_dx(dt, g.dx[1]), edge, sc, &kp);
+}
+// the clock of a call, and new_dt's maxima of every Grid zeroed for the first step (lane l: Grid l)
+__global__ void __launch_bounds__(64)
+k2d_mesh_seed(Run2D *rc, Run2D v, MeshClockTab tab)
+{
+  const int l = threadIdx.x;
+  if (l == 0) *rc = v;
+  if (l < tab.n) { DevScalars *sc = tab.sc[l]; sc->max_v[0] = 0ULL; sc->max_v[1] = 0ULL; sc->max_v[2] = 0ULL; }
+}
+// One wavefront behind the level coupling of every queued step: what aa_mesh_step does on the host between RestrictCorrect and
+// bvals_mhd (main.c:618-629; smr.hip aa_mesh_step, aa_mesh_new_dt) -- the arithmetic is time_step.h run_advance_levels, the
+// maxima are those the update kernels (Grids without children) and k_cfl (Grids with children) left in every Grid's DevScalars.
+// Lane l reads and zeroes the maxima of Grid l, lane 0 does the rest.  `stepped` tells the kernels queued behind this one whether
+// the step in front of it was taken (k2d_box_copy_dc).  Launch rule as k2d_advance: a plain launch in stream order, no waiting.
+__global__ void __launch_bounds__(64)
+k2d_mesh_advance(Run2D *rc, MeshClockTab tab, RunClock *out)
+{
+  __shared__ Real mv[2*AA_2D_MESH_GRIDS], dx[2*AA_2D_MESH_GRIDS];
+  const int l = threadIdx.x, live = rc->c.live;
+  if (!live) { if (l == 0) rc->stepped = 0; return; }        // (uniform: the whole wavefront returns)
+  if (l < tab.n) {
+    DevScalars *sc = tab.sc[l];
+    mv[2*l] = __longlong_as_double((long long)sc->max_v[0]); mv[2*l + 1] = __longlong_as_double((long long)sc->max_v[1]);
+    sc->max_v[0] = 0ULL; sc->max_v[1] = 0ULL; sc->max_v[2] = 0ULL;                              // for the next step
+    dx[2*l] = tab.dx[2*l]; dx[2*l + 1] = tab.dx[2*l + 1];
+  }
+  __syncthreads();
+  if (l != 0) return;
+  RunClock c = rc->c;
+  run_advance_levels(&c, rc->t_stop, rc->tlim, rc->cour_no, rc->nstep_stop, tab.n, 2, mv, dx);
+  rc->c = c; rc->stepped = 1; *out = c;
+}
+
 // ---- launch wrappers -----------------------------------------------------------------------------------------------------
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1)/b); }
 
@@ -536,5 +578,22 @@ void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st)
 { hipLaunchKernelGGL(k2d_seed, dim3(1), dim3(64), 0, st, rc, v, sc); }
 void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st)
 { hipLaunchKernelGGL(k2d_advance, dim3(1), dim3(64), 0, st, rc, sc, g.dx[0], g.dx[1], out); }
+
+// ---- the Grids of a 2-D Mesh on one clock (aa_mesh_run_2d): launch_step_keep's geometry, dt from `rc` ----------------------------
+template <int MODE, bool CFL>
+static void launch_step_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{
+  const int ntx = (int)cdiv(g.Nx1, 64), nj = g.Nx2;
+  hipLaunchKernelGGL((k2d_edge_dc<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_keep_dc<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc, kp);
+}
+void launch_2d_ctu_flux2_update_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep_dc<M_CTU2, CFL>(g, rc, edge, sc, kp, st); }); }
+void launch_2d_vl_flux2_update_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{ with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep_dc<M_VL2, CFL>(g, rc, edge, sc, kp, st); }); }
+void launch_2d_mesh_seed(Run2D *rc, const Run2D &v, const MeshClockTab &tab, hipStream_t st)
+{ hipLaunchKernelGGL(k2d_mesh_seed, dim3(1), dim3(64), 0, st, rc, v, tab); }
+void launch_2d_mesh_advance(Run2D *rc, const MeshClockTab &tab, RunClock *out, hipStream_t st)
+{ hipLaunchKernelGGL(k2d_mesh_advance, dim3(1), dim3(64), 0, st, rc, tab, out); }
 
 }  // namespace aa

@@ -8,6 +8,10 @@
 // steps aa_run_2d queues between two reads of the clock where AA_2D_BATCH is not set (0: one aa_step at a time); DESIGN section 8
 // has the measurement it comes from
 #define AA_2D_BATCH_DEFAULT 32
+// ... and steps aa_mesh_run_2d queues for the Grids of a 2-D Mesh (0: one aa_mesh_step at a time); section 8 has its own measurement
+#define AA_2D_MESH_BATCH_DEFAULT 8
+// Grids of a Mesh the argument table of k2d_mesh_advance / k2d_mesh_seed holds; a Mesh with more steps one aa_mesh_step at a time
+#define AA_2D_MESH_GRIDS 16
 
 namespace aa {
 
@@ -18,8 +22,12 @@ namespace aa {
 struct Run2D {
   RunClock c;
   Real t_stop, tlim, cour_no;       // of the call: main.c's loop condition, new_dt.c's clip and CourNo
-  int nstep_stop, pad;
+  int nstep_stop;
+  int stepped;                      // aa_mesh_run_2d only: the step this advance kernel stands behind was taken (`live` before it ran)
 };
+
+// the Grids of a Mesh as k2d_mesh_seed / k2d_mesh_advance see them: new_dt's maxima and the zone sizes, in the Mesh's order
+struct MeshClockTab { int n, pad; DevScalars *sc[AA_2D_MESH_GRIDS]; Real dx[2*AA_2D_MESH_GRIDS]; };
 
 void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st);               // the clock of a call; new_dt's maxima zeroed
 void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st);                     // as launch_2d_ctu_first ...
@@ -29,5 +37,12 @@ void launch_2d_vl_predict_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipS
 void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st);
 // nstep++, time += dt, new_dt with the clip at tlim, the maxima zeroed again, the stop rule; `out`: the host's mirror
 void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st);
+// the Grids of a 2-D Mesh on ONE clock (aa_mesh_run_2d): the flux-keeping update kernels (sc == nullptr: without new_dt's maxima, for
+// a Grid that restriction and flux correction rewrite behind it), the clock of a call with every Grid's maxima zeroed, and
+// aa_mesh_step's nstep++ / time += dt / aa_mesh_new_dt over the Grids of `tab` (time_step.h run_advance_levels)
+void launch_2d_ctu_flux2_update_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
+void launch_2d_vl_flux2_update_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
+void launch_2d_mesh_seed(Run2D *rc, const Run2D &v, const MeshClockTab &tab, hipStream_t st);
+void launch_2d_mesh_advance(Run2D *rc, const MeshClockTab &tab, RunClock *out, hipStream_t st);
 
 }  // namespace aa

@@ -1,7 +1,8 @@
 // run.hip -- the C-ABI of the run calls (include/athena_amd.h: aa_run_1d, aa_run_2d): main.c:519-669 until time >= t_stop,
 // nstep == nstep_stop or dt <= 0 with the loop's clock on the device -- a 1-D Grid in ONE launch (hydro1d_kernels.hip k1d_run), a 2-D
 // Grid as AA_2D_BATCH queued steps per read of the clock (hydro2d_kernels.hip k2d_advance) -- or, with the knob of either at 0, step
-// by step.  One body behind both names: the refusals, the fallback and the seed / synchronise / read-back frame are written once.
+// by step.  One body behind both names: the refusals, the fallback and the seed / synchronise / read-back frame are written once
+// (run_frame, which aa_mesh_run_2d of smr.hip shares for the Grids of a 2-D Mesh on one clock).
 // The rule of the step and the loop condition are those of time_step.h, on the host and in the two kernels.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -27,25 +28,97 @@ static int run_buffers(aa_grid *g, const char *who)
   return 0;
 }
 
+// The integrator's chain of a 2-D Grid on the clock `rc`, on g->st.  The stage names are those of aa_integrate_2d_*.  A stand-alone
+// Grid (aa_run_2d: its own clock, new_dt's maxima always on board) and a level of a Mesh (aa_mesh_run_2d in smr.hip: the Mesh's one
+// clock, the update kernel in its flux-keeping form, sc == nullptr where the level's maxima are taken later) share it.
+void queue_chain_2d(aa_grid *g, const Run2D *rc, DevScalars *sc)
+{
+  const HostGrid &d = g->d;
+  if (g->p.integrator == 1) {
+    { Scope s(g, "vl2d_predict"); launch_2d_vl_predict_dc(d, rc, g->edge2d, g->st); }
+    { Scope s(g, "vl2d_flux2_update");
+      if (g->keep_flux) launch_2d_vl_flux2_update_keep_dc(d, rc, g->edge2d, sc, g->keep, g->st);
+      else launch_2d_vl_flux2_update_dc(d, rc, g->edge2d, sc, g->st); }
+  } else {
+    { Scope s(g, "ctu2d_first"); launch_2d_ctu_first_dc(d, rc, g->edge2d, g->st); }
+    { Scope s(g, "ctu2d_correct"); launch_2d_ctu_correct_dc(d, rc, g->p.integrator == 0, g->st); }
+    { Scope s(g, "ctu2d_flux2_update");
+      if (g->keep_flux) launch_2d_ctu_flux2_update_keep_dc(d, rc, g->edge2d, sc, g->keep, g->st);
+      else launch_2d_ctu_flux2_update_dc(d, rc, g->edge2d, sc, g->st); }
+  }
+}
+
 // one step of the queue: the integrator's chain with new_dt's maxima on board, k2d_advance, bvals_mhd (main.c:572-644 without
 // Userwork_in_loop: a Grid with pinned zones is refused).  The stage names are those of aa_integrate_2d_* / aa_bvals_mhd.
 static void queue_step_2d(aa_grid *g)
 {
-  const HostGrid &d = g->d; const Run2D *rc = g->run2d_dev;
-  if (g->p.integrator == 1) {
-    { Scope s(g, "vl2d_predict"); launch_2d_vl_predict_dc(d, rc, g->edge2d, g->st); }
-    { Scope s(g, "vl2d_flux2_update"); launch_2d_vl_flux2_update_dc(d, rc, g->edge2d, g->sc, g->st); }
-  } else {
-    { Scope s(g, "ctu2d_first"); launch_2d_ctu_first_dc(d, rc, g->edge2d, g->st); }
-    { Scope s(g, "ctu2d_correct"); launch_2d_ctu_correct_dc(d, rc, g->p.integrator == 0, g->st); }
-    { Scope s(g, "ctu2d_flux2_update"); launch_2d_ctu_flux2_update_dc(d, rc, g->edge2d, g->sc, g->st); }
-  }
+  const HostGrid &d = g->d;
+  queue_chain_2d(g, g->run2d_dev, g->sc);
   { Scope s(g, "run2d_advance"); launch_2d_advance(d, g->run2d_dev, g->sc, g->clock_dev, g->st); }
   // The boundary kernels (k_bc) take no dt and are not predicated.  With four or more zones per direction every ghost zone is a
   // copy of an ACTIVE zone (x1 pass) or of a row whose x1 ghost zones that pass has just filled (x2 pass), so behind a stopped
   // step -- U untouched -- they write again what is there: idempotent.  (Grids with fewer zones step one at a time, below.)
   { Scope s(g, "bvals_mhd");
     for (int a = 0; a < 2; a++) launch_bc_dir(d, g->p.nscal, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
+}
+
+// ---- the frame of every run call (api_internal.h RunOps): the span and tlim refusals, the loop over single steps, and the seed /
+// queue / synchronise / read the clock loop.  aa_run_1d and aa_run_2d come here through run_to_time, aa_mesh_run_2d from smr.hip.
+int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{
+  const char *who = o.who;
+  const long long span = (long long)nstep_stop - *o.nstep;
+  if (span < 0 || span > (1LL << 20))
+    return aa_fail(-1, "[%s]: nstep_stop=%d from nstep=%d: a call covers 0 .. 2^20 steps", who, nstep_stop, *o.nstep);
+  if (tlim != o.tlim) return aa_fail(-1, "[%s]: tlim=%.17g, but the %s was created with %.17g (new_dt clips at that one)", who, tlim, o.owner, o.tlim);
+  const int nstep0 = *o.nstep;
+  if (o.stepwise) {
+    while (run_live(*o.time, t_stop, *o.nstep, nstep_stop, *o.dt)) { int rc = o.step(o.self); if (rc) return rc; }
+    if (nsteps_done) *nsteps_done = *o.nstep - nstep0;
+    return 0;
+  }
+  if (nsteps_done) *nsteps_done = 0;
+  if (!run_live(*o.time, t_stop, *o.nstep, nstep_stop, *o.dt)) return 0;      // nothing launched, nothing read back
+  RunClock *clock = nullptr;
+  const RunClock seed = {*o.dt, 1, *o.nstep, *o.time};
+  if (int rc = o.begin(o.self, seed, t_stop, tlim, nstep_stop, &clock)) return rc;
+  // Every launch ends whatever the data are, so the queue drains.  1-D: the one launch runs to the stop and leaves live = 0.  2-D: a
+  // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call).
+  do {
+    if (int rc = o.batch(o.self, t_stop, tlim, nstep_stop)) return rc;
+    HIPCHK(hipGetLastError());
+    (*o.host_syncs)++;
+    HIPCHK(hipStreamSynchronize(o.st));
+  } while (clock->live);
+  *o.time = clock->time; *o.dt = clock->dt; *o.nstep = clock->nstep;
+  if (o.end) o.end(o.self);
+  if (nsteps_done) *nsteps_done = *o.nstep - nstep0;
+  return 0;
+}
+
+// a Grid behind that frame
+static int grid_step(void *self) { return aa_step((aa_grid*)self, nullptr); }
+static int grid_begin(void *self, const RunClock &seed, double t_stop, double tlim, int nstep_stop, RunClock **clock)
+{
+  aa_grid *g = (aa_grid*)self;
+  if (int rc = run_buffers(g, g->one_d ? "aa_run_1d" : "aa_run_2d")) return rc;
+  g->cfl_ready = false; g->active_dirty = true;
+  if (g->one_d) *g->clock = seed;
+  else {
+    const Run2D v = {seed, t_stop, tlim, g->p.cour_no, nstep_stop, 0};
+    launch_2d_seed(g->run2d_dev, v, g->sc, g->st);
+  }
+  *clock = g->clock;
+  return 0;
+}
+static int grid_batch(void *self, double t_stop, double tlim, int nstep_stop)
+{
+  aa_grid *g = (aa_grid*)self;
+  if (g->one_d) {
+    Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
+    launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->clock_dev, g->st);
+  } else for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
+  return 0;
 }
 
 // `who`: the entry's name for its messages; ndim: the Grids it takes
@@ -64,42 +137,13 @@ static int run_to_time(aa_grid *g, const char *who, int ndim, double t_stop, dou
   if (g->npin > 0) return aa_fail(-1, "[%s]: a %d-D Grid with pinned zones steps one at a time: aa_step", who, ndim);
   if (g->keep_flux || g->level > 0)      // (2-D only: a 1-D Grid is never a level of a Mesh)
     return aa_fail(-1, "[%s]: this Grid is a level of a Mesh (level %d): the levels step together, aa_mesh_step", who, g->level);
-  const long long span = (long long)nstep_stop - g->nstep;
-  if (span < 0 || span > (1LL << 20))
-    return aa_fail(-1, "[%s]: nstep_stop=%d from nstep=%d: a call covers 0 .. 2^20 steps", who, nstep_stop, g->nstep);
-  if (tlim != g->p.tlim) return aa_fail(-1, "[%s]: tlim=%.17g, but the Grid was created with %.17g (new_dt clips at that one)", who, tlim, g->p.tlim);
-  const int nstep0 = g->nstep;
   // step by step: either knob at 0, or fewer zones than ghost zones along a direction of a 2-D Grid (a boundary kernel reads ghost
   // zones there, see queue_step_2d)
-  if (ndim == 1 ? !g->resident_1d : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST)) {
-    while (run_live(g->time, t_stop, g->nstep, nstep_stop, g->dt)) { int rc = aa_step(g, nullptr); if (rc) return rc; }
-    if (nsteps_done) *nsteps_done = g->nstep - nstep0;
-    return 0;
-  }
-  if (nsteps_done) *nsteps_done = 0;
-  if (!run_live(g->time, t_stop, g->nstep, nstep_stop, g->dt)) return 0;      // nothing launched, nothing read back
-  if (int rc = run_buffers(g, who)) return rc;
-  g->cfl_ready = false; g->active_dirty = true;
-  const RunClock seed = {g->dt, 1, g->nstep, g->time};
-  if (ndim == 1) *g->clock = seed;
-  else {
-    const Run2D v = {seed, t_stop, tlim, g->p.cour_no, nstep_stop, 0};
-    launch_2d_seed(g->run2d_dev, v, g->sc, g->st);
-  }
-  // Every launch ends whatever the data are, so the queue drains.  1-D: the one launch runs to the stop and leaves live = 0.  2-D: a
-  // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call).
-  do {
-    if (ndim == 1) {
-      Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
-      launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->clock_dev, g->st);
-    } else for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
-    HIPCHK(hipGetLastError());
-    g->host_syncs++;
-    HIPCHK(hipStreamSynchronize(g->st));
-  } while (g->clock->live);
-  g->time = g->clock->time; g->dt = g->clock->dt; g->nstep = g->clock->nstep;
-  if (nsteps_done) *nsteps_done = g->nstep - nstep0;
-  return 0;
+  RunOps o;
+  o.who = who; o.owner = "Grid"; o.self = g; o.time = &g->time; o.dt = &g->dt; o.nstep = &g->nstep; o.tlim = g->p.tlim;
+  o.stepwise = ndim == 1 ? !g->resident_1d : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST);
+  o.step = grid_step; o.begin = grid_begin; o.batch = grid_batch; o.end = nullptr; o.st = g->st; o.host_syncs = &g->host_syncs;
+  return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }
 
 extern "C" {

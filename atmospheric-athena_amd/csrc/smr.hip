@@ -257,8 +257,7 @@ k_flux_x3_apply(DevGrid c, int side, int i0, int j0, int n1, int n2, int nvar, R
 
 // restriction: 2x2 fine zones -> one parent zone.  smr.c Step 3a on a 2-D Grid: the pair of the lower row, plus the pair of the
 // upper row, times 0.25 (the x3 pass is skipped: Nx[2] = 1)
-__global__ void __launch_bounds__(S2_W*S2_R)
-k2d_restrict(DevGrid f, DevGrid c, Link L)
+__device__ __forceinline__ void restrict2_body(const DevGrid &f, const DevGrid &c, const Link &L)
 {
   const int a = (int)blockIdx.x*S2_W + (int)threadIdx.x, b = (int)blockIdx.y*S2_R + (int)threadIdx.y;
   if (a >= L.n[0] || b >= L.n[1]) return;
@@ -273,12 +272,14 @@ k2d_restrict(DevGrid f, DevGrid c, Link L)
     fld(c, c.U, v)[mc] = s;
   }
 }
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_restrict(DevGrid f, DevGrid c, Link L)
+{ restrict2_body(f, c, L); }
 
 // flux correction of the parent zones just outside the child (smr.c Step 2a); the child's flux through a parent face is the sum
 // of its two faces times 0.5 (Step 3c with nDim = 2).  One thread per parent face of a side; dim_arg < 0: the four sides in one
 // launch, side = blockIdx.y (they correct disjoint parent zones)
-__global__ void __launch_bounds__(S2_W)
-k2d_flux_correct(DevGrid f, DevGrid c, Link L, int dim_arg, Real dt)
+__device__ __forceinline__ void flux_correct2_body(const DevGrid &f, const DevGrid &c, const Link &L, int dim_arg, Real dt)
 {
   const int dim = (dim_arg >= 0) ? dim_arg : (int)blockIdx.y;
   if (dim_arg < 0 && !L.corr[dim]) return;
@@ -305,10 +306,12 @@ k2d_flux_correct(DevGrid f, DevGrid c, Link L, int dim_arg, Real dt)
     fld(c, c.U, v)[mcell] -= q*(mine - fine);
   }
 }
+__global__ void __launch_bounds__(S2_W)
+k2d_flux_correct(DevGrid f, DevGrid c, Link L, int dim_arg, Real dt)
+{ flux_correct2_body(f, c, L, dim_arg, dt); }
 
 // snapshot of the parent zones cs-3 .. ce+3 around the child in x1 and x2, taken when the parent "sends" (smr.c Step 1 of Prolongate)
-__global__ void __launch_bounds__(S2_W*S2_R)
-k2d_box_copy(DevGrid c, Link L, Real *box)
+__device__ __forceinline__ void box_copy2_body(const DevGrid &c, const Link &L, Real *box)
 {
   const int b0 = L.n[0] + 6, b1 = L.n[1] + 6;
   const int i = (int)blockIdx.x*S2_W + (int)threadIdx.x, j = (int)blockIdx.y*S2_R + (int)threadIdx.y;
@@ -318,6 +321,24 @@ k2d_box_copy(DevGrid c, Link L, Real *box)
 #pragma unroll
   for (int v = 0; v < 5; v++) box[(long)v*nb + (long)j*b0 + i] = fld(c, c.U, v)[m];
 }
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_box_copy(DevGrid c, Link L, Real *box)
+{ box_copy2_body(c, L, box); }
+
+// ---- the same kernels for a step queued by aa_mesh_run_2d: the Mesh's ONE clock (hydro2d_launch.h Run2D, in device memory) is read
+// at the top, as the *_dc entry points of hydro2d_kernels.hip do.  Restriction OVERWRITES the parent with a function of the child, but
+// the flux correction ADDS to the parent: behind the stop (`live` = 0) both return before any store, and dt is the clock's.  The
+// snapshot for the prolongation stands behind k2d_mesh_advance, which has already written the NEXT step's `live`: it asks `stepped`,
+// whether the step in front of that kernel was taken (see mesh_queue_step_2d for why a snapshot behind a stop must not be retaken).
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_restrict_dc(DevGrid f, DevGrid c, Link L, const Run2D *rc)
+{ if (!rc->c.live) return; restrict2_body(f, c, L); }
+__global__ void __launch_bounds__(S2_W)
+k2d_flux_correct_dc(DevGrid f, DevGrid c, Link L, int dim_arg, const Run2D *rc)
+{ if (!rc->c.live) return; flux_correct2_body(f, c, L, dim_arg, rc->c.dt); }
+__global__ void __launch_bounds__(S2_W*S2_R)
+k2d_box_copy_dc(DevGrid c, Link L, Real *box, const Run2D *rc)
+{ if (!rc->stepped) return; box_copy2_body(c, L, box); }
 
 // one thread = one parent zone under 2x2 ghost zones of the child.  ProCon (smr.c:3068) on a 2-D Grid: the planes below and above
 // are copies of the plane itself (Step 3a, nDim == 2), so the x3 slope is mcd_slope of equal values = 0 and its term -0.25*0 adds
@@ -450,6 +471,13 @@ struct aa_mesh {
   double tcoarse = 0;              // ionrad_3d.c:44
   double time = 0, dt = 0; int nstep = 0;   // MeshS
   CutMesh *cut = nullptr;          // the levels are composite handles cut at the same root planes (aa_create_cut): see the end of this file
+  bool local = false;              // made by aa_mesh_create_local: one rank's stack of slabs
+  // aa_mesh_run_2d (a Mesh of 2-D Grids): steps queued per read of the clock (AA_2D_BATCH when the Mesh was made; 0: it loops over
+  // aa_mesh_step), the ONE clock of all levels in device memory, its page-locked mirror and that one's device address (made by the
+  // first call that reaches the device), and the Grids as k2d_mesh_advance sees them
+  int batch_2d = 0;
+  Run2D *run2d_dev = nullptr; RunClock *clock = nullptr, *clock_dev = nullptr;
+  MeshClockTab tab;
 };
 
 extern "C" {
@@ -478,6 +506,11 @@ static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out, bool may_ove
   for (int l = 0; l < m->nl; l++) aa_set_stream(m->lev[l], (void*)m->st);
   { const char *ev = getenv("AA_MESH_OVERLAP"); m->overlap = may_overlap && (ev ? atoi(ev) != 0 : true); }
   { const char *ev = getenv("AA_SMR_ONE_LAUNCH"); m->one_launch = ev ? atoi(ev) != 0 : true; }
+  if (m->two_d) {      // AA_2D_BATCH as aa_create reads it for a Grid, with the Mesh's own default
+    const char *ev = getenv("AA_2D_BATCH");
+    m->batch_2d = ev ? atoi(ev) : AA_2D_MESH_BATCH_DEFAULT;
+    if (m->batch_2d < 0 || m->batch_2d > 1024) { const int v = m->batch_2d; aa_mesh_destroy(m); return aa_fail(-1, "[aa_mesh_create_2d]: AA_2D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
+  }
   if (m->overlap && m->nl > 1) {
     e = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
     for (int l = 1; l < m->nl && e == hipSuccess; l++) {
@@ -657,6 +690,7 @@ static int mesh_create_local(int nlevels, aa_grid **levels, const int *links, aa
   if ((nlevels > 1 && !links) || !out) return aa_fail(-1, "[aa_mesh_create_local]: bad arguments");
   aa_mesh *m = mesh_alloc(nlevels, levels);
   if (!m) return -1;
+  m->local = true;
   // links join grid l+1 to grid l here (par[l] = l): ONE Domain per level, a strict chain (mesh_alloc alone would also take siblings)
   for (int l = 0; l < nlevels; l++)
     if (m->lev[l]->level != l) { mesh_drop(m); return aa_fail(-1, "[aa_mesh_create_local]: grid %d is on level %d: a rank's stack holds one Domain per level", l, levels[l]->level); }
@@ -687,6 +721,8 @@ void aa_mesh_destroy(aa_mesh *m)      // the levels stay alive and go back to th
   for (int l = 1; l < m->nl; l++) { if (m->side[l]) hipStreamDestroy(m->side[l]); if (m->ev_join[l]) hipEventDestroy(m->ev_join[l]); }
   if (m->ev_fork) hipEventDestroy(m->ev_fork);
   if (m->own_stream) hipStreamDestroy(m->st);
+  if (m->run2d_dev) hipFree(m->run2d_dev);
+  if (m->clock) hipHostFree(m->clock);
   delete m;
 }
 
@@ -977,6 +1013,160 @@ int aa_mesh_step(aa_mesh *m, int *niter)
   if ((rc = aa_mesh_new_dt(m))) return rc;                            // :629
   for (int l = 0; l < m->nl; l++) if ((rc = aa_bvals_mhd(m->lev[l]))) return rc;   // :635-644
   return aa_mesh_prolongate(m);                                       // :647
+}
+
+// ---- aa_mesh_run_2d: whole passes of aa_mesh_step's loop for a Mesh of 2-D Grids with ONE clock in device memory ----------------
+// (the frame -- refusals of span and tlim, the loop over single steps, seed / queue / read the clock -- is run.hip's run_frame)
+static int mesh_run_buffers(aa_mesh *m)
+{
+  if (m->clock) return 0;
+  RunClock *h = nullptr, *hd = nullptr; Run2D *d = nullptr;
+  if (hipHostMalloc(&h, sizeof(RunClock), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || hipMalloc(&d, sizeof(Run2D)) != hipSuccess) {
+    if (h) hipHostFree(h);
+    (void)hipGetLastError();
+    return aa_fail(-2, "[aa_mesh_run_2d]: clock buffers");
+  }
+  memset(h, 0, sizeof(RunClock));
+  m->clock = h; m->clock_dev = hd; m->run2d_dev = d;
+  m->tab.n = m->nl; m->tab.pad = 0;
+  for (int l = 0; l < AA_2D_MESH_GRIDS; l++) {
+    const bool in = l < m->nl;
+    m->tab.sc[l] = in ? m->lev[l]->sc : nullptr;
+    m->tab.dx[2*l] = in ? m->lev[l]->d.dx[0] : 0.0; m->tab.dx[2*l + 1] = in ? m->lev[l]->d.dx[1] : 0.0;
+  }
+  return 0;
+}
+
+// One queued step: aa_mesh_step's order with no host in it.  Every kernel in front of k2d_mesh_advance reads dt and `live` from
+// the Mesh's clock and stores nothing behind the stop.
+//  * the integrator chain of every level, the update kernel in its flux-keeping form.  new_dt's maxima ride on it where the Grid
+//    has no child: nothing writes such a Grid between its update and new_dt (pinned zones are refused).  A Grid WITH children is
+//    rewritten by restriction and flux correction: its update kernel leaves no maxima, and k_cfl sweeps it behind the last
+//    restrict_correct pair.  k_cfl only raises the Grid's own maxima (atomic MAX); behind a stop that is all it does, and the next
+//    call's seed zeroes them again (aa_mesh_new_dt zeroes them itself).  MAX over the same doubles is order-free: dt is the same bits.
+//  * restriction and flux correction, finest pair first, both behind the `live` guard (the correction ADDS to the parent).
+//  * k2d_mesh_advance: nstep++, time += dt, new_dt over the Grids, the stop rule; `stepped` = this step was taken.
+//  * bvals_mhd of every level, then the snapshots around every child (k2d_box_copy_dc) and the prolongation.  What they write
+//    behind a stop, with U's active zones untouched:
+//      - k_bc takes no dt and is not predicated.  Every level has four or more zones per direction (else: step by step, below), so
+//        a ghost zone it writes is a copy of an ACTIVE zone (x1 pass) or of a row whose x1 ghost zones are either written by that
+//        pass just before or lie on a fine/coarse side -- and then the zone copied to is a corner the prolongation of that side
+//        overwrites again (its region spans the other direction's ghost zones).  So where k_bc is the last writer of a ghost zone
+//        it writes again what is there.
+//      - k2d_prolong is a function of the snapshot `box` alone, so it writes again what is there as long as the snapshot is the
+//        one of the last step taken.  The snapshot itself is NOT a function of an unchanged state: it is taken before the parent's
+//        own ghost zones are prolonged (smr.c Prolongate, Step 1), and a child two zones from its parent's fine/coarse side has
+//        one of those ghost zones in its snapshot -- the value of the step before while the step is taken, the fresh one if the
+//        snapshot were retaken behind the stop.  So k2d_box_copy_dc is predicated on `stepped` and the boxes stay as they are.
+//    A following aa_mesh_step, an output or a restart dump therefore sees the state the last step taken left.
+// Everything is a plain launch on the Mesh's ONE stream, in stream order; no kernel waits on memory or on another workgroup.  The
+// fork of the levels onto their side streams (aa_mesh_step, AA_MESH_OVERLAP) is dropped here: with no host visit between the steps
+// its two event hand-overs per level and step cost more than the overlap of these small chains gains (203 us per
+// step of the reference's deck on one stream against 225 - 232 with the fork).
+static int mesh_queue_step_2d(aa_mesh *m)
+{
+  const Run2D *rc = m->run2d_dev;
+  for (int l = 0; l < m->nl; l++) {
+    bool parent = false;
+    for (int c = 0; c + 1 < m->nl; c++) if (m->par[c] == l) parent = true;
+    queue_chain_2d(m->lev[l], rc, parent ? nullptr : m->lev[l]->sc);      // (run.hip: the chain aa_run_2d queues, flux-keeping here; on m->st)
+  }
+  for (int q = 0; q + 1 < m->nl; q++) {                              // RestrictCorrect, finest pair first
+    const int l = m->f2c[q];
+    aa_grid *P = m->lev[m->par[l]], *C = m->lev[l + 1];
+    const Link &L = m->link[l];
+    Scope s(P, "smr_restrict_correct");
+    hipLaunchKernelGGL(k2d_restrict_dc, dim3(nblk(L.n[0], S2_W), nblk(L.n[1], S2_R)), dim3(S2_W, S2_R), 0, m->st, C->d, P->d, L, rc);
+    const int nmax = L.n[0] > L.n[1] ? L.n[0] : L.n[1];
+    if (m->one_launch) {
+      if (L.corr[0] || L.corr[1] || L.corr[2] || L.corr[3])
+        hipLaunchKernelGGL(k2d_flux_correct_dc, dim3(nblk(nmax, S2_W), 4), dim3(S2_W), 0, m->st, C->d, P->d, L, -1, rc);
+    } else
+    for (int dim = 0; dim < 4; dim++)
+      if (L.corr[dim]) hipLaunchKernelGGL(k2d_flux_correct_dc, dim3(nblk(L.n[1 - (dim >> 1)], S2_W)), dim3(S2_W), 0, m->st, C->d, P->d, L, dim, rc);
+  }
+  for (int l = 0; l < m->nl; l++) {                                  // new_dt's maxima of the Grids with children
+    bool parent = false;
+    for (int c = 0; c + 1 < m->nl; c++) if (m->par[c] == l) parent = true;
+    if (parent) { Scope s(m->lev[l], "new_dt"); launch_cfl(m->lev[l]->d, m->lev[l]->sc, m->st); }
+  }
+  { Scope s(m->lev[0], "smr_advance"); launch_2d_mesh_advance(m->run2d_dev, m->tab, m->clock_dev, m->st); }
+  for (int l = 0; l < m->nl; l++) {
+    aa_grid *g = m->lev[l];
+    Scope s(g, "bvals_mhd");
+    for (int a = 0; a < 2; a++) launch_bc_dir(g->d, g->p.nscal, a, g->p.bc[2*a], g->p.bc[2*a + 1], m->st);
+  }
+  for (int l = 0; l < m->nl; l++) {                                  // Prolongate, in the order of aa_mesh_prolongate
+    for (int c = 0; c + 1 < m->nl; c++) {
+      if (m->par[c] != l) continue;
+      const Link &L = m->link[c];
+      hipLaunchKernelGGL(k2d_box_copy_dc, dim3(nblk(L.n[0] + 6, S2_W), nblk(L.n[1] + 6, S2_R)), dim3(S2_W, S2_R), 0, m->st, m->lev[l]->d, L, m->box[c], rc);
+    }
+    if (l == 0) continue;
+    aa_grid *C = m->lev[l];
+    const Link &L = m->link[l - 1];
+    Scope s(C, "smr_prolongate");
+    const int c0 = (C->p.Nx[0] + 2*NG)/2, c1 = (C->p.Nx[1] + 2*NG)/2;
+    if (m->one_launch) {
+      if (L.prol[0] || L.prol[1] || L.prol[2] || L.prol[3])
+        hipLaunchKernelGGL(k2d_prolong, dim3(nblk(c0, S2_W), nblk(c1, S2_R), 4), dim3(S2_W, S2_R), 0, m->st, C->d, L, m->box[l - 1], -1);
+    } else
+    for (int dim = 0; dim < 4; dim++) {
+      if (!L.prol[dim]) continue;
+      const int n0 = (dim >> 1) == 0 ? NG/2 : c0, n1 = (dim >> 1) == 1 ? NG/2 : c1;
+      hipLaunchKernelGGL(k2d_prolong, dim3(nblk(n0, S2_W), nblk(n1, S2_R)), dim3(S2_W, S2_R), 0, m->st, C->d, L, m->box[l - 1], dim);
+    }
+  }
+  return 0;
+}
+
+static int mesh_run_step(void *self) { return aa_mesh_step((aa_mesh*)self, nullptr); }
+static int mesh_run_begin(void *self, const RunClock &seed, double t_stop, double tlim, int nstep_stop, RunClock **clock)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  if (int rc = mesh_run_buffers(m)) return rc;
+  for (int l = 0; l < m->nl; l++) { m->lev[l]->cfl_ready = false; m->lev[l]->active_dirty = true; }
+  const Run2D v = {seed, t_stop, tlim, m->lev[0]->p.cour_no, nstep_stop, 0};
+  launch_2d_mesh_seed(m->run2d_dev, v, m->tab, m->st);
+  *clock = m->clock;
+  return 0;
+}
+static int mesh_run_batch(void *self, double, double, int)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  for (int k = 0; k < m->batch_2d; k++) { int rc = mesh_queue_step_2d(m); if (rc) return rc; }
+  return 0;
+}
+// every level's copy of MeshS, as aa_mesh_step and aa_mesh_new_dt leave them
+static void mesh_run_end(void *self)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  for (int l = 0; l < m->nl; l++) { m->lev[l]->time = m->time; m->lev[l]->nstep = m->nstep; m->lev[l]->dt = m->dt; }
+}
+
+int aa_mesh_run_2d_batch(const aa_mesh *m) { return m && m->two_d && !m->cut ? m->batch_2d : 0; }
+
+int aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{
+  if (!m) return aa_fail(-1, "[aa_mesh_run_2d]: null argument");
+  if (m->cut) return aa_fail(-1, "[aa_mesh_run_2d]: this Mesh is cut into slabs: its levels step together on their slabs' streams, aa_mesh_step");
+  if (m->local) return aa_fail(-1, "[aa_mesh_run_2d]: this Mesh is one rank's stack of slabs (aa_mesh_create_local): the ranks agree on dt between steps, aa_mesh_step");
+  if (!m->two_d) return aa_fail(-1, "[aa_mesh_run_2d]: this is a Mesh of 3-D Grids: only a Mesh of 2-D Grids (aa_mesh_create_2d) runs many steps per host visit");
+  bool small = false;
+  for (int l = 0; l < m->nl; l++) {
+    const aa_grid *g = m->lev[l];
+    if (g->npin > 0) return aa_fail(-1, "[aa_mesh_run_2d]: grid %d (level %d) has pinned zones: such a Mesh steps one at a time, aa_mesh_step", l, g->level);
+    if (g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST) small = true;
+  }
+  RunOps o;
+  o.who = "aa_mesh_run_2d"; o.owner = "root"; o.self = m; o.time = &m->time; o.dt = &m->dt; o.nstep = &m->nstep; o.tlim = m->lev[0]->p.tlim;
+  // step by step: the knob at 0, more Grids than the advance kernel's table holds, or a level with fewer zones than ghost zones
+  // along a direction (mesh_queue_step_2d: a boundary kernel reads ghost zones there)
+  o.stepwise = m->batch_2d == 0 || m->nl > AA_2D_MESH_GRIDS || small;
+  o.step = mesh_run_step; o.begin = mesh_run_begin; o.batch = mesh_run_batch; o.end = mesh_run_end; o.st = m->st;
+  o.host_syncs = &m->lev[0]->host_syncs;
+  return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }
 
 

@@ -1,5 +1,5 @@
 /* time_step.h -- the time-step rule of new_dt.c:156-185 and the loop condition of main.c:519, once, for host and device
- * (C99 and C++, no HIP include; the drop-in shim, the C library, k1d_run and k2d_advance all call these).
+ * (C99 and C++, no HIP include; the drop-in shim, the C library, k1d_run, k2d_advance and k2d_mesh_advance all call these).
  *
  * However the maxima of |v| + a reach the caller -- one Grid, slabs, the levels of a Mesh, MPI ranks, a kernel that keeps the
  * clock on the device -- the operations, their order and their comparison forms are the ones written here:
@@ -12,6 +12,7 @@
  *   dt_clip        :183-185  ... and this half, the clip at tlim, behind it
  *   dt_pick        :167-185  the two composed
  *   run_live       main.c:519 as the run calls use it: time < t_stop && nstep != nstep_stop && dt > 0.0 (a NaN dt stops)
+ *   run_advance_levels        main.c:618-629 of a Mesh: nstep++, time += dt, the fold over its Grids, the pick, run_live
  * No operation is contracted with another (the pragma inside every body: a file-scope one would reach the including file).
  * (driver.py holds pick_dt / fold_levels for the Python drivers; tests/test_time_step.py runs one table of cases through both;
  * oracle/athena_oracle.c keeps its own text: it is what the library is tested against.)
@@ -82,6 +83,23 @@ TS_FN double dt_pick(int nstep, double dt, double dt_cfl, double time, double tl
 TS_FN int run_live(double time, double t_stop, int nstep, int nstep_stop, double dt)
 {
   return time < t_stop && nstep != nstep_stop && dt > 0.0;
+}
+
+/* main.c:618-629 for the Grids of a Mesh whose loop is on the device (aa_mesh_run_2d; k2d_mesh_advance calls this, and
+ * aa_mesh_step + aa_mesh_new_dt are the same operations on the host): nstep++, time += dt, then new_dt.c:32 over the Grids in the
+ * Mesh's order -- the maxima carried from Grid to Grid, every Grid's own dx, ndir directions -- the pick with the clip at tlim,
+ * and whether the call's loop goes on.  max_v and dx hold ndir doubles per Grid. */
+TS_FN void run_advance_levels(RunClock *c, double t_stop, double tlim, double cour_no, int nstep_stop,
+                              int ngrid, int ndir, const double *max_v, const double *dx)
+{
+  TS_NO_CONTRACT
+  double cum[3] = {0.0, 0.0, 0.0}, max_dti = 0.0;
+  int l;
+  c->nstep++;
+  c->time += c->dt;
+  for (l = 0; l < ngrid; l++) max_dti = dt_fold_level(max_dti, cum, max_v + ndir*l, dx + ndir*l, ndir);
+  c->dt = dt_pick(c->nstep, c->dt, dt_courant(cour_no, max_dti), c->time, tlim);
+  c->live = run_live(c->time, t_stop, c->nstep, nstep_stop, c->dt);
 }
 
 #endif

@@ -120,6 +120,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_mesh_restrict_correct": (I, [P]), "aa_mesh_ionrad_restrict_correct": (I, [P]),
         "aa_mesh_prolongate": (I, [P]), "aa_mesh_new_dt": (I, [P]), "aa_mesh_ion_radtransfer": (I, [P, I, ip]),
         "aa_mesh_start": (I, [P]), "aa_mesh_step": (I, [P, ip]),
+        "aa_mesh_run_2d": (I, [P, D, D, I, ip]), "aa_mesh_run_2d_batch": (I, [P]),
         "aa_mesh_ionflux_prolong": (I, [P, I]), "aa_mesh_create_local": (I, [I, C.POINTER(P), ip, C.POINTER(P)]),
         "aa_flux_x3_export": (I, [P, I, P]), "aa_flux_x3_apply": (I, [P, I, I, I, I, I, P]), "aa_cfl_max_v": (I, [P, dp]),
         "aa_test_fluxes": (I, [I, D, I, dp, dp, dp, dp]),
@@ -880,6 +881,7 @@ class Mesh:
             arr = (C.c_int * max(1, len(flat)))(*flat)
             self._chk(self.L.aa_mesh_create_local(n, hs, arr, C.byref(h)))
         self._h = h
+        self.links = links                      # a rank's stack of slabs (run_2d refuses it)
         for g in self.lev:
             g.in_mesh = True                    # (the levels step together: Grid.can_run_2d says no)
 
@@ -974,3 +976,25 @@ class Mesh:
         it = (C.c_int * len(self.lev))()
         self._chk(self.L.aa_mesh_step(self._h, it))
         return list(it)
+
+    def run_2d_batch(self) -> int:
+        """steps run_2d queues per read-back on this Mesh (AA_2D_BATCH when the Mesh was made, else the Mesh's own default; 0: it
+        steps one at a time)"""
+        return int(self.L.aa_mesh_run_2d_batch(self._h))
+
+    def can_run_2d(self) -> bool:
+        """whether run_2d queues steps on this Mesh: every level 2-D, not cut into slabs, not a rank's stack (links), no level with
+        pinned zones -- the refusals of aa_mesh_run_2d -- and a batch above 0"""
+        return (all(g.ndim == 2 for g in self.lev) and self.cuts is None and self.links is None
+                and all(g.npin == 0 for g in self.lev) and self.run_2d_batch() > 0)
+
+    def run_2d(self, t_stop: float, tlim: float | None = None, nstep_stop: int | None = None) -> int:
+        """Whole passes of step()'s loop on a Mesh of 2-D Grids with ONE clock on the device for all levels (aa_mesh_run_2d):
+        AA_2D_BATCH steps are queued per read-back; until time >= t_stop, nstep == nstep_stop or dt <= 0; new_dt clips at tlim
+        (default: the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the same bits as that many
+        step() calls.  AthenaError on a Mesh of 3-D Grids, one cut into slabs or made from links, a level with pinned zones."""
+        n = C.c_int()
+        tlim = self.lev[0].cfg.run.tlim if tlim is None else tlim
+        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
+        self._chk(self.L.aa_mesh_run_2d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
+        return n.value

@@ -297,6 +297,20 @@ int  aa_mesh_ion_radtransfer(aa_mesh *m, int level, int *niter); /* ionrad_3d.c:
 int  aa_mesh_ionflux_prolong(aa_mesh *m, int level); /* ionrad_prolong_snd(level-1) + _rcv(level) alone    */
 int  aa_mesh_start(aa_mesh *m);                   /* main.c:395-447                                  */
 int  aa_mesh_step(aa_mesh *m, int *niter);        /* one pass of main.c:519-669; niter[nlevels]      */
+/* Many passes of aa_mesh_step's loop per host visit for a Mesh of 2-D Grids (aa_mesh_create_2d): the semantics of aa_run_2d -- until
+ * time >= t_stop, nstep == nstep_stop (the Mesh's absolute step count, 0 .. 2^20 steps ahead) or dt <= 0 -- with ONE clock in device
+ * memory for all levels.  AA_2D_BATCH steps (environment when the Mesh is made; the Mesh has a default of its own,
+ * csrc/hydro2d_launch.h) are queued as plain launches: the integrator chain of every level, restriction and flux correction,
+ * new_dt's maxima, one wavefront that advances the clock over all levels (k2d_mesh_advance; csrc/time_step.h), bvals_mhd,
+ * prolongation; then the host reads the clock ONCE and queues again while the run is live.  Steps queued behind the stop change
+ * nothing.  The same bits as that many aa_mesh_step calls; afterwards the Mesh's and every level's time / dt / nstep are set as
+ * aa_mesh_new_dt leaves them.  *nsteps_done: steps taken.  An error, each message beginning [aa_mesh_run_2d]: a null Mesh, a Mesh
+ * of 3-D Grids, a Mesh made by aa_mesh_create_local or cut into slabs, a level with pinned zones, a tlim other than the root's,
+ * nstep_stop outside nstep .. nstep + 2^20.  AA_2D_BATCH=0: the same call loops over aa_mesh_step; so it does on a Mesh with more
+ * Grids than the advance kernel's argument table holds (16, the most a Mesh can have today) or with a level of fewer than four
+ * zones along a direction.  aa_run_2d on a level of a Mesh stays an error.                                                        */
+int  aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+int  aa_mesh_run_2d_batch(const aa_mesh *m);      /* steps queued per read-back on this Mesh; 0: it steps one at a time */
 
 /* Multi-GPU SMR: every level is cut into x3 slabs at the SAME root planes, so that restriction, the
  * radiation hand-off and prolongation stay inside a rank.  aa_mesh_create_local builds one rank's stack
