@@ -193,6 +193,12 @@ int aa_create(const aa_params *p, aa_grid **out)
     g->batch_2d = e ? atoi(e) : AA_2D_BATCH_DEFAULT;
     if (g->batch_2d < 0 || g->batch_2d > 1024) { const int v = g->batch_2d; delete g; return fail(-1, "[aa_create]: AA_2D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
   }
+  if (!two_d && !one_d) {
+    // AA_3D_BATCH: steps aa_run_3d queues between two reads of the device clock (1 .. 1024); 0: it loops over aa_step; same bits
+    const char *e = getenv("AA_3D_BATCH");
+    g->batch_3d = e ? atoi(e) : AA_3D_BATCH_DEFAULT;
+    if (g->batch_3d < 0 || g->batch_3d > 1024) { const int v = g->batch_3d; delete g; return fail(-1, "[aa_create]: AA_3D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
+  }
   if (one_d) {
     d.N2 = 1; d.js = d.je = 0;
     // AA_1D_RESIDENT=0: aa_run_1d steps one launch at a time (k1d_step) instead of many steps in one launch (k1d_run); same bits
@@ -311,7 +317,7 @@ void aa_destroy(aa_grid *g)
   if (g->pin_mask) hipFree(g->pin_mask);
   if (g->cfl_part) hipFree(g->cfl_part);
   if (g->fofc_list) hipFree(g->fofc_list);
-  if (g->clock) { hipHostFree(g->clock); hipFree(g->run2d_dev); }      // (run.hip run_buffers; run2d_dev: null on a 1-D Grid)
+  if (g->clock) { hipHostFree(g->clock); hipFree(g->run2d_dev); hipFree(g->run3d_dev); }      // (run.hip run_buffers; run2d_dev / run3d_dev: null on Grids of the other shapes)
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);

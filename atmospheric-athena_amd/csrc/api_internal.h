@@ -8,6 +8,7 @@
 #include "grid.h"
 #include "hydro1d_launch.h"
 #include "hydro2d_launch.h"
+#include "hydro3d_launch.h"
 #include "ion_subcycle.h"
 
 int aa_fail(int code, const char *fmt, ...);   // records the message aa_last_error() returns
@@ -51,8 +52,10 @@ struct aa_grid {
   bool one_d = false;                  // Nx2 = Nx3 = 1 in a 1-D root Domain: the 1-D integrators (hydro1d_kernels.hip); U 5 | LR 5 (the second U buffer)
   bool resident_1d = true;             //   ... AA_1D_RESIDENT=0 (read by aa_create): aa_run_1d steps one launch at a time instead of keeping the Grid in one workgroup's LDS (k1d_run)
   int batch_2d = 0;                    // a 2-D Grid: steps aa_run_2d queues between two reads of the clock (AA_2D_BATCH, read by aa_create; 0: it loops over aa_step)
-  RunClock *clock = nullptr, *clock_dev = nullptr;   // time, dt, nstep, live of aa_run_1d / aa_run_2d (time_step.h): pinned, device-visible host memory and its device address ...
+  int batch_3d = 0;                    // a 3-D Grid: steps aa_run_3d queues between two reads of the clock (AA_3D_BATCH, read by aa_create; 0: it loops over aa_step)
+  RunClock *clock = nullptr, *clock_dev = nullptr;   // time, dt, nstep, live of aa_run_1d / aa_run_2d / aa_run_3d (time_step.h): pinned, device-visible host memory and its device address ...
   aa::Run2D *run2d_dev = nullptr;      //   ... and the 2-D call's clock in device memory (hydro2d_launch.h); made by the first run call that reaches the device (run.hip)
+  aa::Run3D *run3d_dev = nullptr;      //   ... and the 3-D call's (hydro_launch.h), likewise
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke
   double inner_dt = 0.0;               //   ... with this dt
   bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): aa_params.ion_path, else LaunchCfg ion_fused; a sweep along x2 turns it off

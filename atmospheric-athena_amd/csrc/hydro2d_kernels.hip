@@ -395,20 +395,9 @@ k2d_step_keep(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars
 { step_body<MODE, CFL, true>(g, dt, c1, c2, edge, sc, &kp); }
 
 // ---- the device clock (aa_run_2d; hydro2d_launch.h Run2D) ------------------------------------------------------------------
-// dt/dx and dt/2dx of the update kernels as the launch wrappers below evaluate them on the host for the kernels that take dt as an
-// argument: one IEEE division, one multiplication by 0.5, never contracted with anything around them -- so c1 and c2 are the same
-// bits.  (Every other use of dt -- recon_zone, correct_body -- is evaluated on the device in either form, by the same code.)
-AA_DEV Real dt_over_dx(Real dt, Real dx)
-{
-#pragma clang fp contract(off)
-  return dt/dx;
-}
-AA_DEV Real half_dt_over_dx(Real dt, Real dx)
-{
-#pragma clang fp contract(off)
-  const Real q = dt/dx;
-  return 0.5*q;
-}
+// dt/dx and dt/2dx of the update kernels (time_step.h dt_over_dx / half_dt_over_dx) are the bits the launch wrappers below form on
+// the host for the kernels that take dt as an argument.  (Every other use of dt -- recon_zone, correct_body -- is evaluated on the
+// device in either form, by the same code.)
 // The *_dc entry points: `live` and dt in one uniform load at the top (the clock is written by k2d_advance / k2d_seed, kernels in
 // front of this one on the same stream, and by nobody while this one runs); a step queued behind the stop returns here, before
 // any store and before any barrier (the whole grid takes the same branch).

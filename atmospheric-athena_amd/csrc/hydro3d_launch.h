@@ -1,0 +1,35 @@
+// hydro3d_launch.h -- the device clock of aa_run_3d and the launch interface of what reads and writes it: the *_dc entries of the
+// default 3-D CTU chain (hydro_kernels.hip) and the clock's own two kernels (hydro3d_clock.hip).  Kept apart from grid.h and
+// hydro_launch.h, as hydro2d_launch.h is: the chain that takes dt as a kernel argument (aa_step) is declared there.
+#pragma once
+#include "grid.h"
+#include "time_step.h"
+
+// steps aa_run_3d queues between two reads of the clock where AA_3D_BATCH is not set (0: one aa_step at a time); DESIGN section 8
+#define AA_3D_BATCH_DEFAULT 8
+
+namespace aa {
+
+// The clock (time_step.h RunClock) of a 3-D Grid while aa_run_3d has steps queued, with the call's limits, in DEVICE memory -- the
+// Run2D of hydro2d_launch.h with the six StepRatios of the step beside dt: the 3-D kernels keep dt/dx_d and half of it in scalar
+// registers (hydro_kernels.hip StepRatios), so the *_dc entries fetch them by uniform loads instead of dividing per lane.  k3d_seed
+// and k3d_advance form them once, in one thread, with the operations of step_ratios() (time_step.h dt_over_dx / half_dt_over_dx).
+// live = 0: the call's stop rule has fired; what is queued behind it returns without a store.
+struct Run3D {
+  RunClock c;                       // dt and live lead: one 16-byte uniform load
+  Real dtodx[3], q[3];              // of c.dt: dt/dx_d, 0.5*(dt/dx_d)
+  Real t_stop, tlim, cour_no;       // of the call: main.c's loop condition, new_dt.c's clip and CourNo
+  int nstep_stop, pad;
+};
+// hydro3d_clock.hip: the clock of a call (v.dtodx / v.q are formed by the kernel); new_dt's maxima zeroed
+void launch_3d_seed(const DevGrid &g, Run3D *rc, const Run3D &v, DevScalars *sc, hipStream_t st);
+// ... and nstep++, time += dt, new_dt with the clip at tlim, the maxima zeroed again, the next step's ratios, the stop rule; `out`: the host's mirror
+void launch_3d_advance(const DevGrid &g, Run3D *rc, DevScalars *sc, RunClock *out, hipStream_t st);
+// hydro_kernels.hip (namespace aa only: a Grid with a cooling function steps one aa_step at a time): the chain aa_integrate_3d_ctu
+// launches by default, dt and the ratios from the clock, same launch geometry
+void launch_sweep_x2_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, hipStream_t st);       // as launch_sweep(.., 1, ..)
+bool correct_all_dc_built(int nscal, bool grav);      // false: this build has no k_correct_all_dc for the combination (it would spill): aa_step
+void launch_correct_all_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, hipStream_t st);    // as launch_correct_all(.., x3f = true, ..): tile-edge x1 fluxes, k_correct_all, k_eta_edges
+void launch_flux2_update_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, DevScalars *sc, hipStream_t st);   // as launch_flux2_update(.., sc): always with new_dt's maxima
+
+}  // namespace aa

@@ -19,6 +19,7 @@
 // MFMA is not used.
 #include <stdlib.h>
 #include "grid.h"
+#include "hydro3d_launch.h"
 #include "hydro_dev.h"
 
 // Compiled twice: as it stands into namespace aa, and with -DAA_COOLING=1 into namespace aa_cool -- the same kernels with the
@@ -357,54 +358,21 @@ k_slopes_march(DevGrid g, const Real *src, int chunk)
 #ifndef SW_OCC
 #define SW_OCC 3
 #endif
-template <int NS, int D, bool GRAV, int MODE, int ORD>
-__global__ void __launch_bounds__(256, SW_OCC)      // 3 waves per SIMD (168 VGPRs): the kernel is VALU-bound and sits right at that edge
-k_sweep_march(DevGrid g, const Real *src, Real dt, int chunk, int toff, int tcnt)
-{
-  static_assert(D == 1 || D == 2, "march kernel is for the strided directions");
-  // transverse lines toff .. toff+tcnt-1 of the (D == 1 ? ke - ks : je - js) + 5 (the launcher passes all of them, or
-  // for x2 a range of k-planes: see launch_sweep)
-  const int tlo = (D == 1 ? g.ks : g.js) - 2 + toff;
-  const int nt  = tcnt;
-  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
-  // lanes on whole 128-byte lines: a row of slots starts on the line that holds is-2 and is a whole number of lines long (a
-  // wavefront's 64 lanes are four whole lines of one or two rows; the lanes off the ends of [is-2, ie+2] leave)
-  const int nq = march_slots(g);
-  if (lin >= (long)nq*nt) return;
-  const int q = (int)(lin % nq);
-  int i;
-  const int t = tlo + (int)(lin / nq);
-  if (!march_cell(g, q, i)) return;
-  const int lo = (D == 1 ? g.js : g.ks), hi = (D == 1 ? g.je : g.ke);
-  const int f0 = lo - 1 + blockIdx.y*chunk;                    // first interface of this chunk
-  int f1 = f0 + chunk - 1; if (f1 > hi + 2) f1 = hi + 2;
-  if (f0 > f1) return;
-  const long s = stride<D>(g);
-  const long base = (D == 1) ? ((long)t*g.sK + i) : ((long)t*g.sJ + i);
-  const Real dtodx = dt/g.dx[D];
-
-  // ONE inlined instance of the reconstruction serves every cell, also the cell below the chunk's
-  // first interface (iteration f0-1, whose face work is skipped): with fused multiply-adds allowed, two
-  // instances may round differently, and the result must not depend on where the chunks start (the
-  // chunk size follows the Grid size, hence the decomposition).
-  Real wm[6], w[6], wp[6], wl_cur[6], wl_next[6], wr[6], u[6];
-  load_sweep<D, NS>(src, g.nc, base + (long)(f0 - 2)*s, u); cons_to_prim<NS>(u, w,  g.Gamma_1);
-  load_sweep<D, NS>(src, g.nc, base + (long)(f0 - 1)*s, u); cons_to_prim<NS>(u, wp, g.Gamma_1);
-#pragma unroll
-  for (int n = 0; n < 6; n++) wl_cur[n] = 0.0;
-#pragma nounroll
-  for (int f = f0 - 1; f <= f1; f++) {
-    long mf = base + (long)f*s;
-    asm volatile("" : "+v"(mf));     // one index for all fields instead of a strength-reduced pointer per field
-#pragma unroll
-    for (int n = 0; n < 6; n++) { wm[n] = w[n]; w[n] = wp[n]; }
-    load_sweep<D, NS>(src, g.nc, mf + s, u); cons_to_prim<NS>(u, wp, g.Gamma_1);
-    recon_cell<NS, MODE != MODE_VL, ORD, D>(g, mf, wm, w, wp, dtodx, wl_next, wr);  // cell f -> Wl[f+1], Wr[f]
-    if (f >= f0) face_work<NS, D, GRAV, MODE>(g, mf, i, D == 1 ? f : t, D == 1 ? t : f, dt, wl_cur, wr);
-#pragma unroll
-    for (int n = 0; n < 6; n++) wl_cur[n] = wl_next[n];
-  }
-}
+// aa_run_3d (csrc/run.hip) queues many steps without the host in between: the four kernels of the default CTU chain that take dt --
+// k_sweep_march, k_x1_edge_flux, k_correct_all, k_flux2_update -- have a second entry point, *_dc, which takes dt (and the
+// StepRatios) from the device clock (hydro3d_launch.h Run3D) instead of kernel arguments.  Each of the four lives in a header of its
+// own that this file compiles twice: as it stands, the entry with by-value arguments, and with AA_CLOCK_ENTRY, the *_dc entry.  One
+// text, so the two entries of a kernel have the same body token for token, and the by-value entries are instruction for
+// instruction what they were before the second ones existed (profiles/compare_device_asm.py).  A body function shared by two
+// __global__ wrappers does not give that: k_correct_all, which sits at the 256-register limit, moved by up to ten registers and
+// three instantiations went to scratch; k_sweep_march kept its registers but contracted four other multiply-adds in the default
+// build, which changes bits.
+#include "sweep_march_kernel.h"
+#if !AA_COOLING
+#define AA_CLOCK_ENTRY 1
+#include "sweep_march_kernel.h"
+#undef AA_CLOCK_ENTRY
+#endif
 
 // ---- x2 / x3 sweeps on an LDS tile (used for the correct pass) ------------------------------------
 // A block of 64 x BT threads owns 64 independent columns (consecutive i) and BT consecutive cells
@@ -749,381 +717,27 @@ AA_DEV void cell_states(const DevGrid &g, long m, Real dt, Real dtodx, const Rea
 // which keeps its result where the x1 flux array was: [variable][edge][k][j].  Same arithmetic, same bits.
 __host__ __device__ static inline int x1_edges(const DevGrid &g) { return (g.ie + 2 - (g.is - 16))/64; }   // edge b = 1 .. : face is-16+64b <= ie+2
 AA_DEV long x1_edge_index(const DevGrid &g, int nbe, int v, int b, int j, int k) { return (((long)v*nbe + (b - 1))*g.N3 + k)*g.N2 + j; }
-template <int NS, bool GRAV, int ORD>
-__global__ void __launch_bounds__(64)
-k_x1_edge_flux(DevGrid g, Real dt)
+// k_x1_edge_flux and k_correct_all live in correct_all_kernels.h, which is compiled twice: as it stands -- the entries that take dt
+// and the StepRatios as kernel arguments -- and with AA_CLOCK_ENTRY, the *_dc entries of a queued step (aa_run_3d), which read both
+// from the device clock.  One text, so the two entries of a kernel have the same body token for token, and the by-value entries
+// are what they were before the second ones existed (k_correct_all sits at the 256-register limit: as a body function shared by
+// two entries its allocation moved by up to ten registers and three instantiations went to scratch).
+#if !AA_COOLING
+// the clock's ratios by uniform loads (the six doubles behind dt): scalar registers, as the by-value StepRatios
+AA_DEV StepRatios clock_ratios(const Run3D *rc)
 {
-  // lanes along j: the stores on whole lines (the loads are one sector per zone pair either way)
-  const int j = g.js - 1 + blockIdx.x*64 + threadIdx.x, k = g.ks - 1 + blockIdx.y, b = 1 + blockIdx.z;
-  if (j > g.je + 1) return;
-  const int nbe = x1_edges(g), i0 = g.is - 16 + 64*b;
-  const long m = (long)k*g.sK + (long)j*g.sJ + i0;
-  Real wa[6], wb[6], wc[6], wd[6], wl[6], wr[6], wx[6];
-  load_prim_sweep<NS, 0>(g, m - 2, wa); load_prim_sweep<NS, 0>(g, m - 1, wb);
-  load_prim_sweep<NS, 0>(g, m, wc);     load_prim_sweep<NS, 0>(g, m + 1, wd);
-  cell_recon<NS, 0, GRAV, ORD>(g, m - 1, dt, wa, wb, wc, wl, wx);      // zone i0-1: its left state belongs to face i0
-  cell_recon<NS, 0, GRAV, ORD>(g, m, dt, wb, wc, wd, wx, wr);          // zone i0: its right state
-  Real ul[6], ur[6], f[6];
-  prim_to_cons<NS>(wl, ul, g.Gamma_1, g.rGamma_1);
-  prim_to_cons<NS>(wr, ur, g.Gamma_1, g.rGamma_1);
-  flux_roe<NS>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
+  StepRatios sr;
 #pragma unroll
-  for (int n = 0; n < 5 + NS; n++) g.F[x1_edge_index(g, nbe, gv<0>(n), b, j, k)] = f[n];
+  for (int d = 0; d < 3; d++) { sr.dtodx[d] = rc->dtodx[d]; sr.q[d] = rc->q[d]; }
+  return sr;
 }
-template <int NS, bool GRAV, int ORD, bool X3F>
-__global__ void __launch_bounds__(64*CA_TJ, (X3F && NS && GRAV) ? 2 : 1)
-k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
-{
-  __shared__ Real s_w[CA_TJ][6][64];
-  __shared__ Real s_l[CA_TJ][64];
-  // X3F: the x3 states of zone k+1 wait here while zone k is corrected (each thread its own slots, no barrier): 24
-  // registers that the 6-variable gravity kernel does not have at 2 waves per SIMD (it spilled 16 to scratch)
-  // (with the x1 first pass on board: two sets of 12 slots taken in turn, so that the states of zone k need no registers
-  //  between the iterations nor under the x1 Riemann problem: they are read where they are used)
-  __shared__ Real s_park[X3F ? 24 : 1][CA_TJ][64];
-  // ... and in the 6-variable gravity kernel, which spilled three registers, the x1 / x2 frame pressures of planes k+1 and k+2 wait
-  // there too (each thread its own slots): no scratch, 18.53 -> 18.18 ms at 512^3 (same-box ABAB x 3 against keeping them in registers)
-  constexpr bool PARK2 = X3F && NS && GRAV;
-  __shared__ Real s_pp[PARK2 ? 4 : 1][CA_TJ][64];
-  // The zones a tile needs from its neighbours (lane 0's lower / lane 63's upper x1 neighbour, row 0's lower / row CA_TJ-1's
-  // upper x2 neighbour) are requested at the head of the iteration with everything else and wait here for their block: a load
-  // issued inside a block would have to wait for the face-state stores of the block before it (loads and stores retire
-  // through one counter).  s_h1: per wave, the 6 + 6 conserved variables of the two x1 neighbours, fetched by lanes 0..11.
-  // X1F: and behind them the first-pass x1 fluxes of the tile's two edge faces (lanes 12..23)
-  constexpr bool X1F = X3F;      // the x1 first pass comes with the x3 one; the name marks what belongs to which
-  __shared__ Real s_h1[CA_TJ][X1F ? 24 : 12];
-  __shared__ Real s_h2[2][6][64];
-  constexpr int NV = 5 + NS;
-  const int lane = threadIdx.x, row = threadIdx.y;
-  // Zones s-1 .. e+1 in every direction get their face states.  Tiles do NOT overlap in x1 / x2 (round 1's did by one
-  // provider lane / row: 64x4 threads for 63x3 zones, 35 % more threads, loads and arithmetic than zones) and start on a
-  // 128-byte line (zone is - 16: the rows' first active zone is line-aligned).  What a tile cannot do alone is the eta of
-  // its own lowest x1 / x2 faces (lane 0, row 0), which needs lambda_l of the zone in the tile before: there the zone
-  // stores its lambda_r in the face's eta slot, the zone before (lane 63 / row CA_TJ-1) its lambda_l in an edge array,
-  // and k_eta_edges turns the pairs into etas afterwards (1/64 + 1/CA_TJ of the faces, < 10 B/zone).
-  // (Tried and dropped: an XCD-aware blockIdx -> tile map that gives each XCD one contiguous run of tiles, so that the tiles
-  //  either side of an edge share an L2.  Measured ABAB at 512^3: 21.3 vs 20.3 ms here, 15.1 vs 14.9 ms in k_flux2_update —
-  //  the plain map, which spreads neighbouring tiles over all eight XCDs and memory channels, is the faster one.)
-  const int i = g.is - 16 + blockIdx.x*64 + lane, j = g.js - 1 + blockIdx.y*CA_TJ + row;
-  const int k0 = g.ks - 1 + blockIdx.z*kchunk;
-  int k1 = k0 + kchunk - 1; if (k1 > g.ke + 1) k1 = g.ke + 1;
-  const int kstart = (blockIdx.z == 0) ? k0 : k0 - 1;          // one provider plane below a later chunk
-  // idle threads beyond the Grid keep valid addresses (their neighbours may read what they load)
-  // (X1F: zone ie+2 gives its right state to the first-pass flux of face ie+2, so the lane of zone ie+3 holds that zone)
-  const int imax = g.ie + (X1F ? 3 : 2);
-  const int ic = (i <= imax) ? (i < 0 ? 0 : i) : imax, jc = (j <= g.je + 2) ? j : g.je + 2;
-  const long mcol = (long)jc*g.sJ + ic;
-  const int iW = i - lane, iE = i - lane + 63;                 // lane 0's and lane 63's zone, clamped like ic
-  const int icW = (iW <= imax) ? (iW < 0 ? 0 : iW) : imax, icE = (iE <= imax) ? (iE < 0 ? 0 : iE) : imax;
-  const int nbe = x1_edges(g);
-  const bool in = (i >= g.is - 1) && (i <= g.ie + 1) && (j <= g.je + 1);
-  const bool do1 = in, do2 = in, do3 = in;
-  Real q[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) q[d] = sr.q[d];
-
-  // X3F: the x3 FIRST pass rides on the march (k_sweep_march<2> is not launched, its fluxes never reach HBM): the
-  // transverse differences a zone needs of the x3 first-pass flux are those of its own column, and the reconstruction
-  // + gravity kick of a zone along x3 is the same for the first pass and for the correct pass.  Iteration k
-  // reconstructs zone k+1 (A), solves face k+1 from the left state zone k kept and the right state of zone k+1 (B),
-  // and then corrects zone k in all three directions (C).  A chunk starts two planes early with A only, then A + B: one
-  // instance of every piece of arithmetic, whatever the chunking (see k_sweep_march).
-  // The window: wc = zone k, wn = k+1 (and wm3 = k-1 without X3F, wn2 = k+2 with it).
-  Real wm3[6], wc[6], wn[6], wn2[6], pc0 = 0.0, pc1 = 0.0, pn0, pn1, pn20 = 0.0, pn21 = 0.0, f3[6], lam3 = 0.0;
-  Real wl3[6], wr3[6];                                          // X3F: kicked x3 states of zone k (left -> face k+1, right -> face k)
-  const int kbeg = X3F ? kstart - 2 : kstart;
-  if (X3F) {
-    load_prim3<NS>(g, (long)kbeg*g.sK + mcol, wn, pn0, pn1);
-    load_prim3<NS>(g, (long)(kbeg + 1)*g.sK + mcol, wn2, pn20, pn21);
-    if constexpr (PARK2) { s_pp[0][row][lane] = pn0; s_pp[1][row][lane] = pn1; s_pp[2][row][lane] = pn20; s_pp[3][row][lane] = pn21; }
-#pragma unroll
-    for (int v = 0; v < 6; v++) { f3[v] = 0.0; wl3[v] = 1.0; wr3[v] = 1.0; wc[v] = 1.0; }
-  } else {
-    load_prim3<NS>(g, (long)(kstart - 1)*g.sK + mcol, wc, pn0, pn1);
-    load_prim3<NS>(g, (long)kstart*g.sK + mcol, wn, pn0, pn1);
-#pragma unroll
-    for (int v = 0; v < 6; v++) f3[v] = (v < NV) ? Ff(g, 2, v)[(long)kstart*g.sK + mcol] : 0.0;
-  }
-#pragma nounroll
-  for (int k = kbeg; k <= k1; k++) {
-    long m = (long)k*g.sK + mcol;
-    asm volatile("" : "+v"(m));                   // one index for all fields (see k_flux2_update)
-    const bool full = (k >= k0);                  // block-uniform; the provider plane does x3 only
-    const int pk = (k & 1) ? 12 : 0;              // X3F: the s_park slots of zone k (those of zone k+1: 12 - pk)
-    const bool zone = (k >= kstart);              // block-uniform; X3F: the two planes before do the first pass only
-    Real f3n[6], wlN[6], wrN[6];
-#pragma unroll
-    for (int v = 0; v < 6; v++) { f3n[v] = 0.0; wlN[v] = 1.0; wrN[v] = 1.0; }
-    // first-pass fluxes across the zone
-    CellFlux cf;
-#pragma unroll
-    for (int v = 0; v < 6; v++) { cf.dF[0][v] = 0.0; cf.dF[1][v] = 0.0; cf.dF[2][v] = 0.0; }
-    Real mlo[3], mhi[3];
-    Real hv1 = 0.0;
-    // What the zone needs behind its x1 Riemann problem is requested in front of it where the registers allow: the wait would
-    // otherwise come behind it with nothing left to do.  So the x2 first-pass fluxes are: k_correct_all 22.6 -> 20.2 ms at 512^3, three
-    // registers in scratch.  (The potentials and the x2 neighbour rows as well: tens of registers in scratch, a loss -- also with the
-    // potentials parked in LDS; profiles/r04_x1f_ab.txt.)  The scalar kernel without gravity (ifront) has no room for it at two waves
-    // per SIMD and requests them where they are used.
-    constexpr bool EARLY_F = X1F && !(NS && !GRAV);
-    Real hv2[6];
-#pragma unroll
-    for (int v = 0; v < 6; v++) hv2[v] = 0.0;
-    const bool edge_row = (row == 0) || (row == CA_TJ - 1);
-    // the x1 neighbour zones and edge fluxes of plane kk (lanes 0..23 of every wave)
-    auto x1_halo = [&](int kk) -> Real {
-      Real h = 0.0;
-      if (lane < 12) {
-        const int v = lane % 6, east = lane / 6;
-        if (v < NV) h = Uf(g, v)[(long)kk*g.sK + (long)jc*g.sJ + (east ? icE + 1 : icW - 1)];
-      } else if (lane < 24) {
-        const int v = (lane - 12) % 6, b = (int)blockIdx.x + (lane - 12)/6;      // the tile's lower edge face, then its upper one
-        if (v < NV && b >= 1 && b <= nbe) h = g.F[x1_edge_index(g, nbe, v, b, jc, kk)];
-      }
-      return h;
-    };
-    // requested here, used behind the x3 first pass (the provider plane too: its x3 states take x1 fluxes made here)
-    if (X1F && zone) hv1 = x1_halo(k);
-    if (X3F) {
-#pragma unroll
-      for (int n = 0; n < 6; n++) { wc[n] = wn[n]; wn[n] = wn2[n]; }
-      if constexpr (PARK2) { pc0 = s_pp[0][row][lane]; pc1 = s_pp[1][row][lane]; s_pp[0][row][lane] = s_pp[2][row][lane]; s_pp[1][row][lane] = s_pp[3][row][lane]; }
-      else { pc0 = pn0; pc1 = pn1; pn0 = pn20; pn1 = pn21; }
-      load_prim3<NS>(g, m + 2*g.sK, wn2, pn20, pn21);
-      if constexpr (PARK2) { s_pp[2][row][lane] = pn20; s_pp[3][row][lane] = pn21; }
-      if (do3) {
-        {   // (A) zone k+1 along x3
-          Real wm[6], ws[6], wp[6];
-          to_sweep<2>(wc, wc[4], wm); to_sweep<2>(wn, wn[4], ws); to_sweep<2>(wn2, wn2[4], wp);
-          cell_recon<NS, 2, GRAV, ORD>(g, m + g.sK, dt, sr.dtodx[2], wm, ws, wp, wlN, wrN);
-        }
-        // (the states of zone k+1 go to their slots before (B): the left one is not needed in it)
-#pragma unroll
-        for (int n = 0; n < NV; n++) { s_park[12 - pk + n][row][lane] = wlN[n]; s_park[12 - pk + 6 + n][row][lane] = wrN[n]; }
-        if (k >= kstart - 1) {   // (B) first-pass flux of face k+1 (face_work<MODE_FLUX1>), sweep frame -> global variables
-          Real ul[6], ur[6], f[6];
-#pragma unroll
-          for (int n = 0; n < 6; n++) wl3[n] = (n < NV) ? s_park[pk + n][row][lane] : 0.0;
-          prim_to_cons<NS>(wl3, ul, g.Gamma_1, g.rGamma_1);
-          prim_to_cons<NS>(wrN, ur, g.Gamma_1, g.rGamma_1);
-          flux_roe<NS>(ul, ur, wl3, wrN, 0.0, g.Gamma, g.Gamma_1, f);
-#pragma unroll
-          for (int n = 0; n < NV; n++) f3n[gv<2>(n)] = f[n];
-        }
-      }
-      if (!do3) {
-#pragma unroll
-        for (int n = 0; n < NV; n++) { s_park[12 - pk + n][row][lane] = wlN[n]; s_park[12 - pk + 6 + n][row][lane] = wrN[n]; }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-#pragma unroll
-      for (int n = 0; n < 6; n++) { wm3[n] = wc[n]; wc[n] = wn[n]; }
-      pc0 = pn0; pc1 = pn1;
-      load_prim3<NS>(g, m + g.sK, wn, pn0, pn1);
-    }
-    if (!X1F && full) {
-      if (lane < 12) {
-        const int v = lane % 6, east = lane / 6;
-        if (v < NV) hv1 = Uf(g, v)[(long)k*g.sK + (long)jc*g.sJ + (east ? icE + 1 : icW - 1)];
-      }
-    }
-    Real wl1[6], wr1[6];                          // X1F: the zone's kicked x1 states
-#pragma unroll
-    for (int v = 0; v < 6; v++) { wl1[v] = 1.0; wr1[v] = 1.0; }
-    // X1F: what the zone needs behind its x1 Riemann problem (x2 first-pass fluxes, potentials, the x2 neighbour rows) is requested
-    // in front of it -- the wait would otherwise come after it with nothing left to do (EARLY_F; without it: requested where it is used)
-    Real eb0[6], eb1[6];
-#pragma unroll
-    for (int v = 0; v < 6; v++) { eb0[v] = 0.0; eb1[v] = 0.0; }
-    if (EARLY_F && zone) {
-#pragma unroll
-      for (int v = 0; v < NV; v++) { eb0[v] = Ff(g, 1, v)[m]; eb1[v] = Ff(g, 1, v)[m + g.sJ]; }
-    }
-    if (X1F && zone) {   // ---- the x1 first pass, before anything else of the zone is formed: its fluxes correct the x2 and x3 states ----
-      if (lane < 24) s_h1[row][lane] = hv1;
-      __builtin_amdgcn_sched_barrier(0);
-      Real wm[6], wp[6], ws[6];
-      to_sweep<0>(wc, pc0, ws);
-#pragma unroll
-      for (int n = 0; n < 6; n++) { wm[n] = __shfl_up(ws[n], 1); wp[n] = __shfl_down(ws[n], 1); }
-      if (lane == 0 || lane == 63) {      // the neighbour zone of the tile before / after, exactly as the sweeps convert it
-        Real u[6];
-#pragma unroll
-        for (int v = 0; v < 6; v++) u[v] = (v < NV) ? s_h1[row][(lane ? 6 : 0) + v] : 0.0;
-        Real wh[6];
-        cons_to_prim<NS>(u, wh, g.Gamma_1);
-#pragma unroll
-        for (int v = 0; v < 6; v++) { if (lane == 0) wm[v] = wh[v]; else wp[v] = wh[v]; }
-      }
-      if (GRAV) {      // (the zone's kicks along x1; formed again with the others below)
-        const Real phic = Pf(g, 0)[m], phir = Pf(g, 1)[m + stride_rt(g, 0)], phil = Pf(g, 1)[m], dtodx = sr.dtodx[0];
-        cf.kl[0] = dtodx*(phir - phic); cf.kr[0] = dtodx*(phic - phil);
-      }
-      cell_recon<NS, 0, GRAV, ORD>(g, m, dt, sr.dtodx[0], cf, wm, ws, wp, wl1, wr1);
-      {   // first-pass flux of the zone's upper face (face_work<MODE_FLUX1>): its right state is the lane above's
-        Real wrE[6], ul[6], ur[6], f[6];
-#pragma unroll
-        for (int n = 0; n < 6; n++) wrE[n] = __shfl_down(wr1[n], 1);
-        prim_to_cons<NS>(wl1, ul, g.Gamma_1, g.rGamma_1);
-        prim_to_cons<NS>(wrE, ur, g.Gamma_1, g.rGamma_1);
-        flux_roe<NS>(ul, ur, wl1, wrE, 0.0, g.Gamma, g.Gamma_1, f);
-#pragma unroll
-        for (int n = 0; n < NV; n++) {
-          const Real fu = (lane == 63) ? s_h1[row][18 + gv<0>(n)] : f[n];      // the tile's edge faces: k_x1_edge_flux
-          Real flo = __shfl_up(fu, 1);
-          if (lane == 0) flo = s_h1[row][12 + gv<0>(n)];
-          cf.dF[0][gv<0>(n)] = fu - flo;
-          if (gv<0>(n) == 0) { mlo[0] = flo; mhi[0] = fu; }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (full) {
-      if (edge_row) {
-        const long m2 = (row == 0) ? m - g.sJ : m + g.sJ;
-#pragma unroll
-        for (int v = 0; v < NV; v++) hv2[v] = Uf(g, gv<1>(v))[m2];
-      }
-    }
-    if (zone) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const Real a0 = X1F ? 0.0 : Ff(g, 0, v)[m], a1 = X1F ? 0.0 : Ff(g, 0, v)[m + 1];
-      const Real b0 = EARLY_F ? eb0[v] : Ff(g, 1, v)[m], b1 = EARLY_F ? eb1[v] : Ff(g, 1, v)[m + g.sJ];
-      const Real c0 = f3[v], c1 = X3F ? f3n[v] : Ff(g, 2, v)[m + g.sK];
-      if (!X1F) cf.dF[0][v] = a1 - a0;
-      cf.dF[1][v] = b1 - b0; cf.dF[2][v] = c1 - c0;
-      if (v == 0) { if (!X1F) { mlo[0] = a0; mhi[0] = a1; } mlo[1] = b0; mhi[1] = b1; mlo[2] = c0; mhi[2] = c1; }
-      if (!X3F) f3[v] = c1;
-    }
-    if (GRAV) {
-      const Real dc = wc[0], phic = Pf(g, 0)[m];
-#pragma unroll
-      for (int e = 0; e < 3; e++) {
-        const Real phir = Pf(g, 1 + e)[m + stride_rt(g, e)], phil = Pf(g, 1 + e)[m];
-        cf.gm[e] = q[e]*(phir - phil)*dc;
-        cf.ge[e] = q[e]*(mlo[e]*(phic - phil) + mhi[e]*(phir - phic));
-        const Real dtodx = sr.dtodx[e];
-        cf.kl[e] = dtodx*(phir - phic); cf.kr[e] = dtodx*(phic - phil);
-      }
-    }
-    // the neighbour zones go to their (wave-private) LDS slots HERE, before the first face-state store of the iteration: the
-    // wait for these loads would otherwise sit behind the x3 block's twelve stores and drain them (loads and stores retire
-    // through ONE in-order counter: the ISA had an s_waitcnt vmcnt(0) in the middle of every iteration; 18.5 -> 18.3 ms).
-    // (Tried on top and dropped, round 3: the x2 block's -- and the x1 block's -- twelve face states parked in LDS and stored at
-    //  the head of the NEXT iteration behind its loads, so that no load wait sits behind fresh stores: 18.6-18.9 / 19.5-19.7
-    //  against 18.3-18.5 ms.  The write latency is not what this kernel waits for; it moves its 92 GB at 5 TB/s.)
-    if (full) {
-      if (!X1F && lane < 12) s_h1[row][lane] = hv1;
-      if (edge_row) {
-#pragma unroll
-        for (int v = 0; v < NV; v++) s_h2[row ? 1 : 0][v][lane] = hv2[v];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (X1F && full) {   // ---- x1: the states reconstructed above take their corrections ----
-      Real ll = 0.0, lr = 0.0;
-      if (do1) cell_finish<NS, 0, GRAV>(g, m, q, cf, wl1, wr1, true, ll, lr);
-      const Real lprev = __shfl_up(ll, 1);
-      if (do1) {
-        if (lane > 0) { if (i > g.is - 1) Ef(g, 0)[m] = 0.5*fabs(lr - lprev); }
-        else Ef(g, 0)[m] = lr;                        // tile edge: k_eta_edges finishes this face
-        if (lane == 63) Ef(g, 3)[m] = ll;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (do3) {   // ---- x3 in front of x2 (and of x1 where the x1 first pass is not on board): what only this block needs (the plane below / the states zone k kept) is dead under the others ----
-      Real ll, lr;
-      if (X3F) {
-#pragma unroll
-        for (int n = 0; n < 6; n++) { wl3[n] = (n < NV) ? s_park[pk + n][row][lane] : 0.0; wr3[n] = (n < NV) ? s_park[pk + 6 + n][row][lane] : 0.0; }
-      }
-      if (X3F) cell_finish<NS, 2, GRAV>(g, m, q, cf, wl3, wr3, full, ll, lr);
-      else {
-        Real wm[6], ws[6], wp[6];
-        to_sweep<2>(wm3, wm3[4], wm); to_sweep<2>(wc, wc[4], ws); to_sweep<2>(wn, wn[4], wp);
-        cell_states<NS, 2, GRAV, ORD>(g, m, dt, sr.dtodx[2], q, cf, wm, ws, wp, full, ll, lr);
-      }
-      if (full && k > g.ks - 1) Ef(g, 2)[m] = 0.5*fabs(lr - lam3);      // lam3 = lambda_l the zone below gave to this zone's lower face
-      lam3 = ll;
-      if ((GRAV || AA_COOLING) && full) {   // d^{n+1/2}, :2104-2125
-        const Real dh = wc[0] - q[0]*cf.dF[0][0] - q[1]*cf.dF[1][0] - q[2]*cf.dF[2][0];
-        g.dhalf[m] = dh;
-#if AA_COOLING
-        g.phalf[m] = p_half(g, m, q, cf.dF, GRAV, cf.gm, dh);      // P^{n+1/2}, :2133-2266
 #endif
-      }
-    }
-    if (full) {
-      if (!X1F) {   // ---- x1: neighbours by shuffle ----
-        Real wm[6], wp[6], ws[6], ll = 0.0, lr = 0.0;
-        to_sweep<0>(wc, pc0, ws);
-#pragma unroll
-        for (int n = 0; n < 6; n++) { wm[n] = __shfl_up(ws[n], 1); wp[n] = __shfl_down(ws[n], 1); }
-        if (lane == 0 || lane == 63) {      // the neighbour zone of the tile before / after, exactly as the sweeps convert it
-          Real u[6];
-#pragma unroll
-          for (int v = 0; v < 6; v++) u[v] = (v < NV) ? s_h1[row][(lane ? 6 : 0) + v] : 0.0;
-          Real wh[6];
-          cons_to_prim<NS>(u, wh, g.Gamma_1);
-#pragma unroll
-          for (int v = 0; v < 6; v++) { if (lane == 0) wm[v] = wh[v]; else wp[v] = wh[v]; }
-        }
-        if (do1) cell_states<NS, 0, GRAV, ORD>(g, m, dt, sr.dtodx[0], q, cf, wm, ws, wp, true, ll, lr);
-        const Real lprev = __shfl_up(ll, 1);
-        if (do1) {
-          if (lane > 0) { if (i > g.is - 1) Ef(g, 0)[m] = 0.5*fabs(lr - lprev); }
-          else Ef(g, 0)[m] = lr;                        // tile edge: k_eta_edges finishes this face
-          if (lane == 63) Ef(g, 3)[m] = ll;
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      {   // ---- x2: neighbours through LDS ----
-        Real wm[6], wp[6], ws[6], ll = 0.0, lr = 0.0;
-        to_sweep<1>(wc, pc1, ws);
-#pragma unroll
-        for (int n = 0; n < NV; n++) s_w[row][n][lane] = ws[n];
-        __syncthreads();
-        if (row == 0) {
-          Real u[6];
-#pragma unroll
-          for (int v = 0; v < 6; v++) u[v] = (v < NV) ? s_h2[0][v][lane] : 0.0;
-          cons_to_prim<NS>(u, wm, g.Gamma_1);
-        } else {
-#pragma unroll
-          for (int n = 0; n < NV; n++) wm[n] = s_w[row - 1][n][lane];
-          if (!NS) wm[5] = 0.0;
-        }
-        if (row == CA_TJ - 1) {
-          Real u[6];
-#pragma unroll
-          for (int v = 0; v < 6; v++) u[v] = (v < NV) ? s_h2[1][v][lane] : 0.0;
-          cons_to_prim<NS>(u, wp, g.Gamma_1);
-        } else {
-#pragma unroll
-          for (int n = 0; n < NV; n++) wp[n] = s_w[row + 1][n][lane];
-          if (!NS) wp[5] = 0.0;
-        }
-        if (do2) cell_states<NS, 1, GRAV, ORD>(g, m, dt, sr.dtodx[1], q, cf, wm, ws, wp, true, ll, lr);
-        s_l[row][lane] = ll;
-        __syncthreads();
-        if (do2) {
-          if (row > 0) Ef(g, 1)[m] = 0.5*fabs(lr - s_l[row - 1][lane]);
-          else if (j > g.js - 1) Ef(g, 1)[m] = lr;      // tile edge, as for x1
-          if (row == CA_TJ - 1) Ef(g, 4)[m] = ll;
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    }
-    if (X3F) {
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int n = 0; n < 6; n++) f3[n] = f3n[n];
-    }
-  }
-}
+#include "correct_all_kernels.h"
+#if !AA_COOLING
+#define AA_CLOCK_ENTRY 1
+#include "correct_all_kernels.h"
+#undef AA_CLOCK_ENTRY
+#endif
 
 // eta of the faces on the tile edges of k_correct_all: the face's slot holds lambda_r of the zone above it, the edge
 // array lambda_l of the zone below (same expression as inside the tile: integrate_3d_ctu.c:2300-2343)
@@ -1435,202 +1049,12 @@ AA_DEV bool on_plane(const KeepPlanes &kp, int d, int x)
 // CFL: the zone's contribution to new_dt's maxima is taken from the updated state while it is in registers (k_cfl would
 // read the five fields again: 0.9 ms at 512^3); zones marked in `pinmask` are left out, the caller adds them after it
 // has overwritten them (k_pinned_cfl).
-template <int NS, bool GRAV, bool KEEP, bool CFL>
-__global__ void __launch_bounds__(64*FU_TJ)
-k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp, DevScalars *sc, const unsigned char *pinmask, StepRatios sr)
-{
-  // (two copies of the exchange arrays, used in turn: ONE barrier per plane instead of a second one that only kept the
-  //  next plane's writers off this plane's readers -- 8 wavefronts, a whole CU, wait at every barrier of this block)
-  __shared__ Real s_f2[2][FU_TJ][6][64];
-  __shared__ Real s_f1e[2][FU_TJ - 1][6], s_f1s[2][FU_TJ - 1][6];
-  // The lower x3 flux of the zone -- live across the whole iteration in 12 registers -- waits in the thread's own LDS slots: the
-  // 6-variable gravity kernel then holds 246 registers without scratch, and the scaling-free quotients / square roots of the
-  // solver (x_div, x_sqrt: hydro_dev.h), which cost it three spilled registers and 4 % before, pay: 13.77 -> 13.45 ms at 512^3
-  // (same-box ABAB x 3; parked alone 13.70).
-  __shared__ Real s_f3[6][FU_TJ][64];
-  const int lane = threadIdx.x, row = threadIdx.y;
-  // Tiles of 64 x (FU_TJ - 1) zones; the rows start on a 128-byte line (zone is) and do not overlap in x1: with a stride
-  // of 63 zones every 512-byte row request touched a fifth line and 512 zones took 9 tiles (rocprofv3: 559 B/zone fetched
-  // for 400 needed).  Every lane solves the LOWER x1 face of its zone; the one face a row lacks, the upper face of lane
-  // 63, is solved by the wavefront of the last thread row (which owns no zones: it solves the x2 faces above the tile and
-  // would idle during the x1 phase), lane r for zone row r, with the same software pipeline, and handed over through LDS
-  // behind the barrier the x2 phase has anyway.
-  const int i0 = g.is + blockIdx.x*64;
-  const int i = i0 + lane, j0 = g.js + blockIdx.y*(FU_TJ - 1), j = j0 + row;
-  const int k0 = g.ks + blockIdx.z*kchunk;
-  int k1 = k0 + kchunk - 1; if (k1 > g.ke) k1 = g.ke;
-  constexpr int NV = 5 + NS;
-  const bool cell = (row < FU_TJ - 1) && (i <= g.ie) && (j <= g.je);
-  const bool edge = (row == FU_TJ - 1) && (lane < FU_TJ - 1) && (j0 + lane <= g.je) && (i0 + 64 <= g.ie + 1);   // x1 face i0+64 of row `lane`
-  const bool need1 = ((row < FU_TJ - 1) && (j <= g.je) && (i <= g.ie + 1)) || edge;     // lower x1 face of (i,j) / the edge face
-  const bool need2 = (i <= g.ie) && (j <= g.je + 1);                                     // lower x2 face of (i,j)
-  const bool last = (row < FU_TJ - 1) && (lane == 63) && (i < g.ie + 1);                 // its upper x1 face comes from the edge wavefront
-  // clamp the column of idle threads into the Grid so that shuffles / barriers stay uniform
-  const int ic = (i <= g.ie + 1) ? i : g.ie + 1, jc = (j <= g.je + 1) ? j : g.je + 1;
-  const long mcol = (long)jc*g.sJ + ic;
-  // where this thread's x1 face is, relative to its zone: 0, or for the edge wavefront the hop to (i0 + 64, j0 + lane)
-  const long m1off = edge ? ((long)(j0 + lane)*g.sJ + (i0 + 64)) - mcol : 0L;
-  Real dtodx[3];
-#pragma unroll
-  for (int d = 0; d < 3; d++) dtodx[d] = sr.dtodx[d];
-  // per direction: flux differences (hi - lo) of all components + the two mass fluxes (gravity)
-  Real f3lo[6], d1[6], d2[6], d3[6], m1lo = 0.0, m1hi = 0.0, m2lo = 0.0, m2hi = 0.0, m3hi = 0.0;
-  // CFL: the thread's running maxima live in LDS (its own three slots), not in registers carried round the loop: the
-  // 6-variable gravity kernel has none to spare (6 spilled, 16.1 against 14.0 ms)
-  __shared__ Real s_cmx[CFL ? 3 : 1][CFL ? FU_TJ : 1][CFL ? 64 : 1];
-  if (CFL) { s_cmx[0][row][lane] = 0.0; s_cmx[1][row][lane] = 0.0; s_cmx[2][row][lane] = 0.0; }
-#pragma unroll
-  for (int n = 0; n < 6; n++) f3lo[n] = 0.0;
-  const bool keep1 = KEEP && need1 && on_plane(kp, 0, edge ? i0 + 64 : i), keep2 = KEEP && need2 && on_plane(kp, 1, j);
-  if (cell) {                                                                   // face k0
-    face_flux2<NS, 2>(g, (long)k0*g.sK + mcol, f3lo);
-    // (only the first chunk keeps its face k0: every later chunk's is face k1+1 of the chunk below, kept there by the loop's instance of
-    //  the solver -- in the default build this instance may contract its multiply-adds differently, and two writers of one word with
-    //  last-bit-different values made the flux a level's parent reads depend on which block finished last: round 4, found as a
-    //  run-to-run difference of 1e-16 on the levels of a Mesh in the default build)
-    if (KEEP && blockIdx.z == 0 && on_plane(kp, 2, k0)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, (long)k0*g.sK + mcol, f3lo);
-  }
-#pragma unroll
-  for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3lo[n];
-  // Software pipeline: the operands of the NEXT Riemann problem are requested before the current one is
-  // solved (x2's during the x1 solve, x3's during x2's, the next zone's x1's during x3's), so that with two
-  // wavefronts per SIMD the memory pipe is not idle while a wavefront computes.
-  FaceIn in1, in2;
-  {
-    long m0 = (long)k0*g.sK + mcol + m1off;
-    asm volatile("" : "+v"(m0));
-    if (need1) face_load<NS, 0>(g, m0, in1);
-  }
-  for (int k = k0; k <= k1; k++) {
-    // (opaque to the optimiser: otherwise every one of the ~60 field pointers becomes its own
-    //  strength-reduced 64-bit induction variable and the kernel spills)
-    long m = (long)k*g.sK + mcol;
-    asm volatile("" : "+v"(m));
-    const int pb = k & 1;
-    if (need2) face_load<NS, 1>(g, m, in2);
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      Real f[6];
-#pragma unroll
-      for (int n = 0; n < 6; n++) f[n] = 0.0;
-      if (need1) face_solve<NS>(g, in1, f);
-      if (keep1) store_sweep<0, NS>(Ff(g, 0, 0), g.nc, m + m1off, f);
-#pragma unroll
-      for (int n = 0; n < NV; n++) d1[n] = __shfl_down(f[n], 1) - f[n];
-      m1lo = f[0]; m1hi = __shfl_down(f[0], 1);
-      if (edge) {
-#pragma unroll
-        for (int n = 0; n < NV; n++) s_f1e[pb][lane][n] = f[n];
-      }
-      if (last) {
-#pragma unroll
-        for (int n = 0; n < NV; n++) s_f1s[pb][row][n] = f[n];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (cell) face_load<NS, 2>(g, m + g.sK, in1);           // (in1 is free: reused for the x3 face)
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      Real f[6];
-#pragma unroll
-      for (int n = 0; n < 6; n++) f[n] = 0.0;
-      if (need2) face_solve<NS>(g, in2, f);
-      if (keep2) store_sweep<1, NS>(Ff(g, 1, 0), g.nc, m, f);
-#pragma unroll
-      for (int n = 0; n < NV; n++) s_f2[pb][row][n][lane] = f[n];
-      __syncthreads();
-      if (row < FU_TJ - 1) {
-#pragma unroll
-        for (int n = 0; n < NV; n++) d2[n] = s_f2[pb][row + 1][n][lane] - f[n];
-        m2hi = s_f2[pb][row + 1][0][lane];
-      }
-      m2lo = f[0];
-      if (last) {           // the same subtraction as in the other lanes, operands through LDS
-#pragma unroll
-        for (int n = 0; n < NV; n++) d1[n] = s_f1e[pb][row][n] - s_f1s[pb][row][n];
-        m1hi = s_f1e[pb][row][0];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // The potentials and d^{n+1/2} of the zone's update are requested in front of the x3 Riemann problem
-    // instead of behind it (same-box, 512^3: 13.45 -> 13.15 ms; the conserved variables instead 13.26, both 14.57: four registers in
-    // scratch -- profiles/r04_x1f_ab.txt item 7)
-    Real ep[7], edh = 0.0;
-#pragma unroll
-    for (int v = 0; v < 7; v++) ep[v] = 0.0;
-    if (GRAV && cell) {
-      ep[0] = Pf(g, 0)[m]; edh = dhalf[m];
-      ep[1] = Pf(g, 1)[m + 1]; ep[2] = Pf(g, 1)[m]; ep[3] = Pf(g, 2)[m + g.sJ]; ep[4] = Pf(g, 2)[m]; ep[5] = Pf(g, 3)[m + g.sK]; ep[6] = Pf(g, 3)[m];
-    }
-    Real f3[6];
-#pragma unroll
-    for (int n = 0; n < 6; n++) f3[n] = 0.0;
-    if (cell) face_solve<NS>(g, in1, f3);
-    __builtin_amdgcn_sched_barrier(0);
-    if (need1 && k < k1) face_load<NS, 0>(g, m + m1off + g.sK, in1);  // the next zone's x1 face
-    __builtin_amdgcn_sched_barrier(0);
-    if (cell) {
-      if (KEEP && on_plane(kp, 2, k + 1)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, m + g.sK, f3);
-#pragma unroll
-      for (int n = 0; n < NV; n++) { f3lo[n] = s_f3[n][row][lane]; d3[n] = f3[n] - f3lo[n]; }
-      m3hi = f3[0];
-      const Real m3lo = f3lo[0];
-#pragma unroll
-      for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3[n];
-      Real u[6];
-#pragma unroll
-      for (int v = 0; v < NV; v++) u[v] = Uf(g, v)[m];
-      // (the mask byte with the zone's other operands, not behind the stores of U: a load that is consumed at once waits
-      //  for everything issued before it, i.e. the wave sat out the six stores' round trip in every plane)
-      unsigned char pinned = 0;
-      if (CFL && pinmask) pinned = pinmask[m];
-      if (GRAV) {   // :2741-2782, with the mass fluxes (sweep component 0) of the faces just solved
-        const Real phic = ep[0], dh = edh;
-        { const Real phir = ep[1], phil = ep[2];
-          u[1] -= dtodx[0]*(phir - phil)*dh;
-          u[4] -= dtodx[0]*(m1lo*(phic - phil) + m1hi*(phir - phic)); }
-        { const Real phir = ep[3], phil = ep[4];
-          u[2] -= dtodx[1]*(phir - phil)*dh;
-          u[4] -= dtodx[1]*(m2lo*(phic - phil) + m2hi*(phir - phic)); }
-        { const Real phir = ep[5], phil = ep[6];
-          u[3] -= dtodx[2]*(phir - phil)*dh;
-          u[4] -= dtodx[2]*(m3lo*(phic - phil) + m3hi*(phir - phic)); }
-      }
-#if AA_COOLING
-      u[4] -= dt*cool_koyinut(dhalf[m], g.phalf[m], dt, g.Gamma_1);      // Step 11c, :2943-2953
+#include "flux2_update_kernel.h"
+#if !AA_COOLING
+#define AA_CLOCK_ENTRY 1
+#include "flux2_update_kernel.h"      // (k_flux2_update_dc: instantiated without kept planes, with new_dt's maxima)
+#undef AA_CLOCK_ENTRY
 #endif
-      // :2981-3050, x1 then x2 then x3; sweep component n of direction D is global variable gv<D>(n)
-#pragma unroll
-      for (int n = 0; n < NV; n++) u[gv<0>(n)] -= dtodx[0]*d1[n];
-#pragma unroll
-      for (int n = 0; n < NV; n++) u[gv<1>(n)] -= dtodx[1]*d2[n];
-#pragma unroll
-      for (int n = 0; n < NV; n++) u[gv<2>(n)] -= dtodx[2]*d3[n];
-#pragma unroll
-      for (int v = 0; v < NV; v++) Uf(g, v)[m] = u[v];
-      if (CFL) {
-        if (!pinned) {
-          Real cmx[3] = {s_cmx[0][row][lane], s_cmx[1][row][lane], s_cmx[2][row][lane]};
-          cfl_zone(u[0], u[1], u[2], u[3], u[4], g.Gamma, g.Gamma_1, cmx);
-          s_cmx[0][row][lane] = cmx[0]; s_cmx[1][row][lane] = cmx[1]; s_cmx[2][row][lane] = cmx[2];
-        }
-      }
-    }
-  }
-  if (CFL) {       // block maximum -> 3 atomics (MAX of non-negative doubles on their bit patterns: order-free)
-    Real *red = &s_cmx[0][0][0];           // [d][row][lane] = [d*64*FU_TJ + t]
-    const int t = row*64 + lane;
-    __syncthreads();
-    for (int w = 32*FU_TJ; w > 0; w >>= 1) {
-      if (t < w) {
-#pragma unroll
-        for (int d = 0; d < 3; d++) red[d*64*FU_TJ + t] = rmax(red[d*64*FU_TJ + t], red[d*64*FU_TJ + t + w]);
-      }
-      __syncthreads();
-    }
-    if (t == 0) for (int d = 0; d < 3; d++) atomic_max_pos(&sc->max_v[d], red[d*64*FU_TJ]);
-  }
-}
 
 // the zones Userwork has just overwritten (k_pinned) join the maxima k_flux2_update<CFL> left them out of
 __global__ void k_pinned_cfl(DevGrid g, long long n, const long long *idx, DevScalars *sc)
@@ -2312,8 +1736,9 @@ unsigned reduce_blocks(long n)
 static inline unsigned nblk8(long n, int b) { unsigned x = nblk(n, b); return ((x + 7u)/8u)*8u; }   // for xcd_block()
 
 template <int NS, bool GRAV, int MODE, int ORD>
-static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, hipStream_t st, int koff = 0, int kcnt = -1)
+static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, hipStream_t st, int koff = 0, int kcnt = -1, const Run3D *rc = nullptr)
 {
+  // (rc: the x2 first pass of a queued step -- the same launch, the entry that reads dt from the device clock)
   // (koff, kcnt): for the x1 and x2 sweeps, the k-planes ks-2+koff .. +kcnt-1 only (every pencil is on its own: any
   // partition of the planes gives the same bits)
   const int nk_all = g.ke - g.ks + 5;
@@ -2362,14 +1787,20 @@ static void sweep_impl_o(const HostGrid &g, const Real *src, int dir, Real dt, h
     int chunk = g.cfg.sw_chunk > 0 ? g.cfg.sw_chunk : SW_CHUNK;          // (AA_SW_CHUNK overrides)
     if (g.cfg.sw_chunk <= 0) while (chunk > 4 && (long)nblk(ni*nt, 64)*((nfaces + chunk - 1)/chunk) < 4096) chunk >>= 1;
     dim3 grid(nblk(ni*nt, 64), (nfaces + chunk - 1)/chunk);
+#if !AA_COOLING
+    if constexpr (MODE == MODE_FLUX1) if (rc && dir == 1) {
+      hipLaunchKernelGGL((k_sweep_march_dc<NS, 1, GRAV, MODE_FLUX1, ORD>), grid, dim3(64), 0, st, g, src, rc, chunk, toff, (int)nt);
+      return;
+    }
+#endif
     with_dir12(dir, [&](auto D) { hipLaunchKernelGGL((k_sweep_march<NS, D, GRAV, MODE, ORD>), grid, dim3(64), 0, st, g, src, dt, chunk, toff, (int)nt); });
   }
 }
 template <int NS, bool GRAV, int MODE>
-static void sweep_impl(const HostGrid &g, const Real *src, int dir, Real dt, hipStream_t st, int koff = 0, int kcnt = -1)
+static void sweep_impl(const HostGrid &g, const Real *src, int dir, Real dt, hipStream_t st, int koff = 0, int kcnt = -1, const Run3D *rc = nullptr)
 {
   // third order: the slope arrays were filled from the state the sweep reconstructs (U; U^{n+1/2} for the van Leer corrector)
-  with_ord(g.slope != nullptr, [&](auto ORD) { sweep_impl_o<NS, GRAV, MODE, ORD>(g, src, dir, dt, st, koff, kcnt); });
+  with_ord(g.slope != nullptr, [&](auto ORD) { sweep_impl_o<NS, GRAV, MODE, ORD>(g, src, dir, dt, st, koff, kcnt, rc); });
 }
 template <int NS>
 static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *src)
@@ -2392,19 +1823,23 @@ static void slopes_impl(const HostGrid &g, int dir, hipStream_t st, const Real *
 }
 // the first-pass x1 fluxes of the faces between the tiles of k_correct_all (needs U only: the caller may run it beside the x2 sweep)
 template <int NS, bool GRAV>
-static void x1_edges_impl(const HostGrid &g, Real dt, hipStream_t st)
+static void x1_edges_impl(const HostGrid &g, Real dt, hipStream_t st, const Run3D *rc = nullptr)
 {
   if (x1_edges(g) <= 0) return;
   const int nj = g.je - g.js + 3, nk = g.ke - g.ks + 3;
   dim3 ge(nblk(nj, 64), nk, x1_edges(g));
+#if !AA_COOLING
+  if (rc) { with_ord(g.slope != nullptr, [&](auto ORD) { hipLaunchKernelGGL((k_x1_edge_flux_dc<NS, GRAV, ORD>), ge, dim3(64), 0, st, g, rc); }); return; }
+#endif
   with_ord(g.slope != nullptr, [&](auto ORD) { hipLaunchKernelGGL((k_x1_edge_flux<NS, GRAV, ORD>), ge, dim3(64), 0, st, g, dt); });
 }
 void launch_x1_edges(const HostGrid &g, int nscal, Real dt, bool grav, hipStream_t st)
 { with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { x1_edges_impl<NS, GRAV>(g, dt, st); }); }
 // the correct passes of all three directions in one kernel (after the three first passes; x3f: after those of x2 and the tile-edge x1 fluxes)
 template <int NS, bool GRAV>
-static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t st, bool edges_done)
+static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t st, bool edges_done, const Run3D *rc = nullptr)
 {
+  // (rc: a queued step, x3f only -- the same three launches, dt and the ratios from the device clock)
   const int ni = g.ie - g.is + 3, nj = g.je - g.js + 3, nk = g.ke - g.ks + 3;    // zones s-1 .. e+1
   // planes per block: with the x3 first pass on board a chunk starts three planes early (two of first-pass work only and the
   // provider plane), so longer chunks pay: 64 planes 19.7 against 20.0 - 20.6 ms for 32 at 512^3 (128: 20.4, 16: 20.2);
@@ -2416,10 +1851,20 @@ static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t s
   // with 8 planes, 1.30 against 1.65 ms at 192^3; 256^3 with 16, 2.80 against 3.09; 320^3 with 32; from 384^3 on with 64)
   if (kc_env <= 0) while (kc > 8 && (long)nblk(ni + 15, 64)*nblk(nj, CA_TJ)*((nk + kc - 1)/kc) < 4096) kc >>= 1;
   dim3 grid(nblk(ni + 15, 64), nblk(nj, CA_TJ), (nk + kc - 1)/kc), blk(64, CA_TJ);
-  if (x3f && !edges_done) x1_edges_impl<NS, GRAV>(g, dt, st);
+  if (x3f && !edges_done) x1_edges_impl<NS, GRAV>(g, dt, st, rc);
+#if !AA_COOLING
+  if (rc) {
+    // (a combination correct_all_dc_built() names is not instantiated: aa_run_3d steps such a Grid one aa_step at a time)
+    if constexpr (AA_FAST_DIV || !(NS && GRAV))
+      with_ord(g.slope != nullptr, [&](auto ORD) { hipLaunchKernelGGL((k_correct_all_dc<NS, GRAV, ORD, true>), grid, blk, 0, st, g, rc, kc); });
+    else abort();
+  } else
+#endif
+  {
   const StepRatios sr = step_ratios(g, dt);
   with_flag(x3f, [&](auto X3F) { with_ord(g.slope != nullptr, [&](auto ORD) {
     hipLaunchKernelGGL((k_correct_all<NS, GRAV, ORD, X3F>), grid, blk, 0, st, g, dt, kc, sr); }); });
+  }
   const long nb1 = (g.ie + 1 - (g.is - 16))/64, nb2 = (g.je + 1 - (g.js - 1))/CA_TJ;
   {
     const long c0 = nb1 > 0 ? nb1*nj*nk : 0, c1 = nb2 > 0 ? (long)ni*nb2*nk : 0;      // (a direction without inner tile edges returns at once)
@@ -2428,6 +1873,16 @@ static void correct_all_impl(const HostGrid &g, Real dt, bool x3f, hipStream_t s
 }
 void launch_correct_all(const HostGrid &g, int nscal, Real dt, bool grav, bool x3f, hipStream_t st, bool edges_done)
 { with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { correct_all_impl<NS, GRAV>(g, dt, x3f, st, edges_done); }); }
+#if !AA_COOLING
+// In the strict build (-ffp-contract=off) the 6-variable gravity k_correct_all<1, true, *, true> holds 256 registers WITH 20 bytes of
+// scratch per lane, in either entry (profiles/run3d_kernel_budget.md; the default build holds 256 without).  A spilling kernel is
+// not built a second time: with a passive scalar and a static potential the strict library has no entry on the device clock.
+bool correct_all_dc_built(int nscal, bool grav) { return AA_FAST_DIV || !(nscal && grav); }
+void launch_correct_all_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, hipStream_t st)
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { correct_all_impl<NS, GRAV>(g, 0.0, true, st, false, rc); }); }
+void launch_sweep_x2_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, hipStream_t st)
+{ with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { sweep_impl<NS, GRAV, MODE_FLUX1>(g, g.U, 1, 0.0, st, 0, -1, rc); }); }
+#endif
 
 void launch_slopes(const HostGrid &g, int nscal, int dir, hipStream_t st, const Real *src)
 { if (!src) src = g.U; with_ns(nscal, [&](auto NS) { slopes_impl<NS>(g, dir, st, src); }); }
@@ -2478,18 +1933,29 @@ void launch_pinned_cfl(const DevGrid &g, long long n, const long long *idx, DevS
 void launch_pin_mask(const DevGrid &g, long long n, const long long *idx, unsigned char *mask, hipStream_t st)
 { if (n > 0) hipLaunchKernelGGL(k_pin_mask, dim3(nblk(n, 256)), dim3(256), 0, st, g, n, idx, mask); }
 // fused second-pass fluxes + update (CTU); `keep`: the face planes whose fluxes are stored as well; sc: and new_dt's maxima
-void launch_flux2_update(const HostGrid &g, int nscal, Real dt, bool grav, const KeepPlanes *keep, hipStream_t st, DevScalars *sc, const unsigned char *pinmask)
+static void flux2_update_impl(const HostGrid &g, int nscal, Real dt, bool grav, const KeepPlanes *keep, hipStream_t st, DevScalars *sc, const unsigned char *pinmask,
+                              const Run3D *rc)
 {
+  // (rc: a queued step -- the same launch, dt and the ratios from the device clock; no kept planes, no pinned zones, always sc)
   const int ni = g.ie - g.is + 1, nj = g.je - g.js + 1, nk = g.ke - g.ks + 1;
   const int kc_env = g.cfg.fu_kc;
   int kc = kc_env > 0 ? kc_env : 32;
   if (kc_env <= 0) while (kc > 4 && (long)nblk(ni, 64)*nblk(nj, FU_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
   dim3 grid(nblk(ni, 64), nblk(nj, FU_TJ - 1), (nk + kc - 1)/kc), blk(64, FU_TJ);
+#if !AA_COOLING
+  if (rc) { with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { hipLaunchKernelGGL((k_flux2_update_dc<NS, GRAV, false, true>), grid, blk, 0, st, g, g.dhalf, rc, kc, sc); }); return; }
+#endif
   const bool keeps = keep && keep->n;
   const KeepPlanes kp = keeps ? *keep : KeepPlanes{0, {{0}}};
   with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { with_flag(keeps, [&](auto KEEP) { with_flag(sc != nullptr, [&](auto CFL) {
     hipLaunchKernelGGL((k_flux2_update<NS, GRAV, KEEP, CFL>), grid, blk, 0, st, g, g.dhalf, dt, kc, kp, sc, pinmask, step_ratios(g, dt)); }); }); });
 }
+void launch_flux2_update(const HostGrid &g, int nscal, Real dt, bool grav, const KeepPlanes *keep, hipStream_t st, DevScalars *sc, const unsigned char *pinmask)
+{ flux2_update_impl(g, nscal, dt, grav, keep, st, sc, pinmask, nullptr); }
+#if !AA_COOLING
+void launch_flux2_update_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, DevScalars *sc, hipStream_t st)
+{ flux2_update_impl(g, nscal, 0.0, grav, nullptr, st, sc, nullptr, rc); }
+#endif
 
 long update_blocks(const DevGrid &g)
 { return (long)nblk8((long)(g.ie - g.is + 1)*(g.je - g.js + 1)*(g.ke - g.ks + 1), 256); }

@@ -54,4 +54,3 @@ void launch_test_lr(int nscal, Real gamma, int n, const Real *W, Real dt, Real d
 void launch_test_xdiv(int n, const Real *a, const Real *b, Real *out, hipStream_t st);     // out[5][n]: x_div, a/b, x_sqrt, sqrt, x_div_r
 void launch_test_lr_ppm(int nscal, Real gamma, int n, const Real *W, Real dt, Real dx, int il, int iu,
                         Real *Wl, Real *Wr, hipStream_t st);
-

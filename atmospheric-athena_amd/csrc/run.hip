@@ -1,8 +1,9 @@
-// run.hip -- the C-ABI of the run calls (include/athena_amd.h: aa_run_1d, aa_run_2d): main.c:519-669 until time >= t_stop,
+// run.hip -- the C-ABI of the run calls (include/athena_amd.h: aa_run_1d, aa_run_2d, aa_run_3d): main.c:519-669 until time >= t_stop,
 // nstep == nstep_stop or dt <= 0 with the loop's clock on the device -- a 1-D Grid in ONE launch (hydro1d_kernels.hip k1d_run), a 2-D
-// Grid as AA_2D_BATCH queued steps per read of the clock (hydro2d_kernels.hip k2d_advance) -- or, with the knob of either at 0, step
-// by step.  One body behind both names: the refusals, the fallback and the seed / synchronise / read-back frame are written once
-// (run_frame, which aa_mesh_run_2d of smr.hip shares for the Grids of a 2-D Mesh on one clock).
+// Grid as AA_2D_BATCH queued steps per read of the clock (hydro2d_kernels.hip k2d_advance), a 3-D hydro Grid on the default CTU chain
+// as AA_3D_BATCH queued steps (hydro_kernels.hip k3d_advance; what that chain does not cover loops over aa_step) -- or, with the
+// knob of any at 0, step by step.  One body behind the three names: the refusals, the fallback and the seed / synchronise / read-back
+// frame are written once (run_frame, which aa_mesh_run_2d of smr.hip shares for the Grids of a 2-D Mesh on one clock).
 // The rule of the step and the loop condition are those of time_step.h, on the host and in the two kernels.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -11,20 +12,21 @@
 using namespace aa;
 
 // The clock of a run call: ONE page-locked, device-visible RunClock per Grid -- k1d_run reads and writes it in place; k2d_advance
-// copies the clock it keeps in device memory (Run2D, 2-D Grids only) into it for the host's one read per batch.  Made by the first
-// call that reaches the device; aa_destroy frees them.
+// copies the clock it keeps in device memory (Run2D, 2-D Grids only) into it for the host's one read per batch, and k3d_advance
+// does the same from the Run3D of a 3-D Grid.  Made by the first call that reaches the device; aa_destroy frees them.
 static int run_buffers(aa_grid *g, const char *who)
 {
   if (g->clock) return 0;
-  RunClock *h = nullptr, *hd = nullptr; Run2D *d = nullptr;
+  RunClock *h = nullptr, *hd = nullptr; Run2D *d = nullptr; Run3D *d3 = nullptr;
   if (hipHostMalloc(&h, sizeof(RunClock), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || (g->two_d && hipMalloc(&d, sizeof(Run2D)) != hipSuccess)) {
+      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || (g->two_d && hipMalloc(&d, sizeof(Run2D)) != hipSuccess) ||
+      (!g->two_d && !g->one_d && hipMalloc(&d3, sizeof(Run3D)) != hipSuccess)) {
     if (h) hipHostFree(h);
     (void)hipGetLastError();
     return aa_fail(-2, "[%s]: clock buffers", who);
   }
   memset(h, 0, sizeof(RunClock));
-  g->clock = h; g->clock_dev = hd; g->run2d_dev = d;
+  g->clock = h; g->clock_dev = hd; g->run2d_dev = d; g->run3d_dev = d3;
   return 0;
 }
 
@@ -62,6 +64,47 @@ static void queue_step_2d(aa_grid *g)
     for (int a = 0; a < 2; a++) launch_bc_dir(d, g->p.nscal, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
 }
 
+// Whether aa_run_3d queues this Grid's steps: what aa_integrate_3d_ctu launches BY DEFAULT for one hydro Grid on one device -- the x2
+// march, the tile-edge x1 fluxes, k_correct_all with both other first passes on board, k_flux2_update with new_dt's maxima -- is the
+// chain whose kernels have entries on the device clock.  Everything else loops over aa_step, with the same results: the van Leer
+// integrator (and fofc with it), a cooling function (namespace aa_cool), ion radiation, the tile kernels of a small Grid
+// (AA_CORRECT_ALL off), AA_X3_FUSED=0, AA_FUSED_UPDATE=0, AA_CFL_FUSED=0, AA_EDGE_OVERLAP=1 (a second stream), first-pass sweeps
+// already done by aa_integrate_begin, a direction with fewer zones than ghost zones (queue_step_3d says why), and in the strict
+// build a passive scalar together with a static potential (correct_all_dc_built: that k_correct_all needs scratch there).
+static bool queues_3d(const aa_grid *g)
+{
+  const LaunchCfg &c = g->d.cfg;
+  const bool x3_fused = c.x3_fused_mode >= 0 ? c.x3_fused_mode != 0 : true;      // (api.hip x3_fused)
+  return !g->one_d && !g->two_d && g->slab.empty() && g->batch_3d > 0 && (g->p.integrator == 0 || g->p.integrator == 2) && !g->fofc &&
+         !g->cool && !g->p.ion && c.correct_all && x3_fused && c.fused_update && c.cfl_step && !c.edge_overlap && !g->inner_swept &&
+         g->d.Nx1 >= AA_NGHOST && g->d.Nx2 >= AA_NGHOST && g->d.Nx3 >= AA_NGHOST && correct_all_dc_built(g->p.nscal, g->grav);
+}
+
+// one step of the 3-D queue: aa_integrate_3d_ctu's default chain with dt and the StepRatios from the clock, bvals_mhd, k3d_advance
+// (main.c:572-644 without Userwork_in_loop: a Grid with pinned zones is refused).  The stage names are those of
+// aa_integrate_3d_ctu / aa_bvals_mhd.  Plain launches in stream order; nothing is captured, nothing launched cooperatively, no kernel
+// waits on memory or on another workgroup; the host reads the clock only behind run_frame's hipStreamSynchronize.
+static void queue_step_3d(aa_grid *g)
+{
+  const HostGrid &d = g->d; const int ns = g->p.nscal; const Run3D *rc = g->run3d_dev;
+  if (d.slope) { Scope s(g, "ppm_slopes"); for (int dir = 0; dir < 3; dir++) launch_slopes(d, ns, dir, g->st, nullptr); }
+  { Scope s(g, "sweep_x2"); launch_sweep_x2_dc(d, ns, rc, g->grav, g->st); }
+  { Scope s(g, "correct_all"); launch_correct_all_dc(d, ns, rc, g->grav, g->st); }
+  if (g->p.integrator == 2) { Scope s(g, "no_h_correction"); (void)hipMemsetAsync(d.eta, 0, (size_t)3*d.nc*sizeof(Real), g->st); }
+  { Scope s(g, "flux2_update"); launch_flux2_update_dc(d, ns, rc, g->grav, g->sc, g->st); }
+  // What takes no dt is not predicated: k_slopes* (slope arrays), k_eta_edges and the eta memset (eta arrays) write scratch of the
+  // step that the next taken step fills again before it reads it, and behind the stop there is no such step in this call.  The
+  // boundary kernels write U.  k_bc_shell gives every ghost zone the value of ONE source zone, found by mapping its ghost
+  // coordinates into the active range (k_bc, one pass per direction, does the same in three copies); with AA_NGHOST or more zones
+  // in every direction that source is an ACTIVE zone, never itself a target.  Behind a stopped step the active zones are untouched,
+  // so the kernel writes again what the last taken step's boundary pass wrote: idempotent, in either form (AA_BC_ONE).  A Grid
+  // with fewer zones along a direction has ghost zones among its sources and steps one at a time (queues_3d).
+  { Scope s(g, "bvals_mhd");
+    if (d.cfg.bc_one) launch_bc_shell(d, ns, g->p.bc, g->st);
+    else for (int a = 0; a < 3; a++) launch_bc_dir(d, ns, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
+  { Scope s(g, "run3d_advance"); launch_3d_advance(d, g->run3d_dev, g->sc, g->clock_dev, g->st); }
+}
+
 // ---- the frame of every run call (api_internal.h RunOps): the span and tlim refusals, the loop over single steps, and the seed /
 // queue / synchronise / read the clock loop.  aa_run_1d and aa_run_2d come here through run_to_time, aa_mesh_run_2d from smr.hip.
 int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
@@ -83,7 +126,7 @@ int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *
   const RunClock seed = {*o.dt, 1, *o.nstep, *o.time};
   if (int rc = o.begin(o.self, seed, t_stop, tlim, nstep_stop, &clock)) return rc;
   // Every launch ends whatever the data are, so the queue drains.  1-D: the one launch runs to the stop and leaves live = 0.  2-D: a
-  // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call).
+  // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call); 3-D likewise (AA_3D_BATCH).
   do {
     if (int rc = o.batch(o.self, t_stop, tlim, nstep_stop)) return rc;
     HIPCHK(hipGetLastError());
@@ -101,10 +144,13 @@ static int grid_step(void *self) { return aa_step((aa_grid*)self, nullptr); }
 static int grid_begin(void *self, const RunClock &seed, double t_stop, double tlim, int nstep_stop, RunClock **clock)
 {
   aa_grid *g = (aa_grid*)self;
-  if (int rc = run_buffers(g, g->one_d ? "aa_run_1d" : "aa_run_2d")) return rc;
+  if (int rc = run_buffers(g, g->one_d ? "aa_run_1d" : g->two_d ? "aa_run_2d" : "aa_run_3d")) return rc;
   g->cfl_ready = false; g->active_dirty = true;
   if (g->one_d) *g->clock = seed;
-  else {
+  else if (!g->two_d) {
+    Run3D v = {seed, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, t_stop, tlim, g->p.cour_no, nstep_stop, 0};      // (k3d_seed forms the ratios)
+    launch_3d_seed(g->d, g->run3d_dev, v, g->sc, g->st);
+  } else {
     const Run2D v = {seed, t_stop, tlim, g->p.cour_no, nstep_stop, 0};
     launch_2d_seed(g->run2d_dev, v, g->sc, g->st);
   }
@@ -117,7 +163,8 @@ static int grid_batch(void *self, double t_stop, double tlim, int nstep_stop)
   if (g->one_d) {
     Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
     launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->clock_dev, g->st);
-  } else for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
+  } else if (g->two_d) for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
+  else for (int k = 0; k < g->batch_3d; k++) queue_step_3d(g);
   return 0;
 }
 
@@ -130,18 +177,22 @@ static int run_to_time(aa_grid *g, const char *who, int ndim, double t_stop, dou
     // (before the knob is looked at: AA_1D_RESIDENT=0 does not lift it)
     if (g->d.Nx1 > run1d_cap())
       return aa_fail(-1, "[%s]: a 1-D Grid of %d zones is above the %d the resident kernel keeps in one workgroup's LDS: aa_step", who, g->d.Nx1, run1d_cap());
+  } else if (ndim == 3) {
+    if (g->one_d) return aa_fail(-1, "[%s]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_run_1d", who);
+    if (g->two_d) return aa_fail(-1, "[%s]: this is a 2-D Grid (Nx3 = 1): aa_run_2d", who);
+    if (!g->slab.empty()) return aa_fail(-1, "[%s]: a Grid cut into slabs steps one at a time: aa_step", who);
   } else {
     if (g->one_d) return aa_fail(-1, "[%s]: this is a 1-D Grid (Nx2 = Nx3 = 1): aa_run_1d", who);
     if (!g->two_d) return aa_fail(-1, "[%s]: this is a 3-D Grid: only 1-D and 2-D Grids run many steps per host visit", who);
   }
   if (g->npin > 0) return aa_fail(-1, "[%s]: a %d-D Grid with pinned zones steps one at a time: aa_step", who, ndim);
-  if (g->keep_flux || g->level > 0)      // (2-D only: a 1-D Grid is never a level of a Mesh)
+  if (g->keep_flux || g->level > 0)      // (2-D and 3-D: a 1-D Grid is never a level of a Mesh)
     return aa_fail(-1, "[%s]: this Grid is a level of a Mesh (level %d): the levels step together, aa_mesh_step", who, g->level);
   // step by step: either knob at 0, or fewer zones than ghost zones along a direction of a 2-D Grid (a boundary kernel reads ghost
   // zones there, see queue_step_2d)
   RunOps o;
   o.who = who; o.owner = "Grid"; o.self = g; o.time = &g->time; o.dt = &g->dt; o.nstep = &g->nstep; o.tlim = g->p.tlim;
-  o.stepwise = ndim == 1 ? !g->resident_1d : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST);
+  o.stepwise = ndim == 1 ? !g->resident_1d : ndim == 3 ? !queues_3d(g) : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST);
   o.step = grid_step; o.begin = grid_begin; o.batch = grid_batch; o.end = nullptr; o.st = g->st; o.host_syncs = &g->host_syncs;
   return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }
@@ -154,5 +205,8 @@ int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nstep
 { return run_to_time(g, "aa_run_1d", 1, t_stop, tlim, nstep_stop, nsteps_done); }
 int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
 { return run_to_time(g, "aa_run_2d", 2, t_stop, tlim, nstep_stop, nsteps_done); }
+int aa_run_3d_batch(const aa_grid *g) { return g && queues_3d(g) ? g->batch_3d : 0; }
+int aa_run_3d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{ return run_to_time(g, "aa_run_3d", 3, t_stop, tlim, nstep_stop, nsteps_done); }
 
 }  // extern "C"

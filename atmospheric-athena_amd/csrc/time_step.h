@@ -13,6 +13,7 @@
  *   dt_pick        :167-185  the two composed
  *   run_live       main.c:519 as the run calls use it: time < t_stop && nstep != nstep_stop && dt > 0.0 (a NaN dt stops)
  *   run_advance_levels        main.c:618-629 of a Mesh: nstep++, time += dt, the fold over its Grids, the pick, run_live
+ *   dt_over_dx, half_dt_over_dx   the update kernels' dt/dx and 0.5*(dt/dx) as the host's launch wrappers form them
  * No operation is contracted with another (the pragma inside every body: a file-scope one would reach the including file).
  * (driver.py holds pick_dt / fold_levels for the Python drivers; tests/test_time_step.py runs one table of cases through both;
  * oracle/athena_oracle.c keeps its own text: it is what the library is tested against.)
@@ -83,6 +84,40 @@ TS_FN double dt_pick(int nstep, double dt, double dt_cfl, double time, double tl
 TS_FN int run_live(double time, double t_stop, int nstep, int nstep_stop, double dt)
 {
   return time < t_stop && nstep != nstep_stop && dt > 0.0;
+}
+
+/* dt/dx and dt/2dx of the update kernels as the launch wrappers evaluate them on the host for the kernels that take dt as an
+ * argument: one IEEE division, one multiplication by 0.5, never contracted with anything around them -- so a kernel that keeps the
+ * clock on the device (k2d_step_dc; k3d_seed / k3d_advance for the StepRatios of the 3-D kernels) forms the same bits. */
+TS_FN double dt_over_dx(double dt, double dx)
+{
+  TS_NO_CONTRACT
+  return dt/dx;
+}
+TS_FN double half_dt_over_dx(double dt, double dx)
+{
+  TS_NO_CONTRACT
+  const double q = dt/dx;
+  return 0.5*q;
+}
+/* ... the six of a 3-D step (hydro_kernels.hip StepRatios), for the clock of aa_run_3d */
+TS_FN void run_step_ratios(double dt, const double *dx, double *dtodx, double *q)
+{
+  int d;
+  for (d = 0; d < 3; d++) { dtodx[d] = dt_over_dx(dt, dx[d]); q[d] = half_dt_over_dx(dt, dx[d]); }
+}
+
+/* main.c:618-629 for ONE Grid whose loop is on the device (aa_run_3d; k3d_advance calls this, and aa_step + aa_new_dt_local +
+ * aa_new_dt are the same operations on the host): nstep++, time += dt, the fold over the Grid's ndir directions, the pick with
+ * the clip at tlim, and whether the call's loop goes on. */
+TS_FN void run_advance_grid(RunClock *c, double t_stop, double tlim, double cour_no, int nstep_stop,
+                            int ndir, const double *max_v, const double *dx)
+{
+  TS_NO_CONTRACT
+  c->nstep++;
+  c->time += c->dt;
+  c->dt = dt_pick(c->nstep, c->dt, dt_courant(cour_no, dt_fold(0.0, max_v, dx, ndir)), c->time, tlim);
+  c->live = run_live(c->time, t_stop, c->nstep, nstep_stop, c->dt);
 }
 
 /* main.c:618-629 for the Grids of a Mesh whose loop is on the device (aa_mesh_run_2d; k2d_mesh_advance calls this, and

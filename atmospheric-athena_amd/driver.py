@@ -119,14 +119,19 @@ class HipEngine:
     def can_batch(self) -> bool:
         """a 1-D Grid aa_run_1d takes (it fits the resident kernel and has no pinned zones): run_local takes whole stretches of the
         main loop in one launch; or a 2-D Grid aa_run_2d takes (no pinned zones, not a level of a Mesh) unless AA_2D_BATCH=0:
-        run_local queues AA_2D_BATCH steps per read-back; every other Grid steps one at a time"""
+        run_local queues AA_2D_BATCH steps per read-back; or a 3-D hydro Grid aa_run_3d queues (the default CTU chain, no pinned
+        zones, no slabs, not a level of a Mesh) unless AA_3D_BATCH=0; every other Grid steps one at a time"""
         if self.g.ndim == 2:
             return self.g.run_2d_batch() != 0 and self.g.can_run_2d()
+        if self.g.ndim == 3 and hasattr(self.g, "can_run_3d"):      # (a Grid object without the 3-D call steps one at a time, as before it existed)
+            return self.g.can_run_3d() and self.g.run_3d_batch() != 0
         return self.g.can_run_until()
 
     def run_local(self, t_stop: float, tlim: float, nstep_stop) -> int:
         if self.g.ndim == 2:
             return self.g.run_2d(t_stop, tlim, nstep_stop)
+        if self.g.ndim == 3:
+            return self.g.run_3d(t_stop, tlim, nstep_stop)
         return self.g.run_until(t_stop, tlim, nstep_stop)
     def start_local(self): self.g.start()
     def resume_local(self): self.g.resume()
@@ -747,12 +752,12 @@ class Driver(_Runner):
 
     def may_batch(self) -> bool:
         """whether advance() may take several steps in one call (outputs.run asks): one rank, and a 1-D Grid the resident kernel
-        holds (aa_run_1d) or a 2-D Grid whose steps queue with the time step picked on the device (aa_run_2d)"""
+        holds (aa_run_1d) or a 2-D / 3-D hydro Grid whose steps queue with the time step picked on the device (aa_run_2d, aa_run_3d)"""
         return not self.distributed and hasattr(self.eng, "can_batch") and self.eng.can_batch()
 
     def advance(self, t_stop: float, nstep_stop=None) -> int:
         """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit), in one launch
-        (aa_run_1d) or as queued steps with one read-back per batch (aa_run_2d); the same bits as that many step() calls.
+        (aa_run_1d) or as queued steps with one read-back per batch (aa_run_2d, aa_run_3d); the same bits as that many step() calls.
         -> the steps taken"""
         far = self.nstep + (1 << 20)              # (aa_run_1d / aa_run_2d cover 2^20 steps per call at the most; the caller's loop goes on)
         n = self.eng.run_local(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))

@@ -103,6 +103,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_integrate_2d_ctu": (I, [P]), "aa_integrate_2d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
         "aa_integrate_1d_ctu": (I, [P]), "aa_integrate_1d_vl": (I, [P]), "aa_run_1d": (I, [P, D, D, I, ip]),
         "aa_run_2d": (I, [P, D, D, I, ip]), "aa_run_2d_batch": (I, [P]),
+        "aa_run_3d": (I, [P, D, D, I, ip]), "aa_run_3d_batch": (I, [P]),
         "aa_run_1d_cap": (I, []), "aa_step_1d_block": (I, []),
         "aa_start": (I, [P]), "aa_step": (I, [P, ip]),
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
@@ -458,7 +459,7 @@ class Grid:
         n = C.c_int(); self._chk(self.L.aa_step(self._h, C.byref(n))); return n.value
 
     def _run(self, call, t_stop, tlim, nstep_stop) -> int:
-        """the arguments of aa_run_1d / aa_run_2d: tlim None is the deck's, nstep_stop None is 2^20 steps ahead -> the steps taken"""
+        """the arguments of aa_run_1d / aa_run_2d / aa_run_3d: tlim None is the deck's, nstep_stop None is 2^20 steps ahead -> the steps taken"""
         n = C.c_int()
         tlim = self.cfg.run.tlim if tlim is None else tlim
         stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
@@ -493,6 +494,24 @@ class Grid:
         the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the same bits as that many step()
         calls.  AthenaError on a Grid that is not 2-D, has pinned zones or is a level of a Mesh (can_run_2d)."""
         return self._run(self.L.aa_run_2d, t_stop, tlim, nstep_stop)
+
+    def run_3d_batch(self) -> int:
+        """steps run_3d queues per read-back on this Grid (AA_3D_BATCH when the Grid was made); 0: it steps one at a time -- the
+        knob at 0, or a Grid off the default CTU chain (van Leer, cooling, ion radiation, a kernel switch, fewer than 4 zones along
+        a direction) -- or the Grid is not 3-D"""
+        return int(self.L.aa_run_3d_batch(self._h))
+
+    def can_run_3d(self) -> bool:
+        """whether run_3d takes this Grid: 3-D, no pinned zones, not cut into slabs, not a level of a Mesh -- the refusals of aa_run_3d"""
+        return self.ndim == 3 and self.npin == 0 and not self._composite and not self.in_mesh and self.cfg.level == 0
+
+    def run_3d(self, t_stop: float, tlim: float | None = None, nstep_stop: int | None = None) -> int:
+        """Whole passes of the main loop on a 3-D hydro Grid with the time step picked on the device (aa_run_3d): AA_3D_BATCH steps
+        of the default CTU chain are queued per read-back instead of one; until time >= t_stop, nstep == nstep_stop or dt <= 0;
+        new_dt clips at tlim (default: the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the
+        same bits as that many step() calls (a Grid with run_3d_batch() == 0 takes them one at a time).  AthenaError on a Grid
+        that is not 3-D, has pinned zones, is cut into slabs or is a level of a Mesh (can_run_3d)."""
+        return self._run(self.L.aa_run_3d, t_stop, tlim, nstep_stop)
 
     # ---- phases ----------------------------------------------------------------------
     def new_dt_local(self) -> float:

@@ -159,9 +159,9 @@ int aa_integrate_1d_vl(aa_grid *g);                 /* integrate_1d_vl.c        
  * Grid's absolute step count; at most 2^20 steps ahead) or dt <= 0.  The Grid must have been started (aa_start / aa_resume).  The
  * same bits as that many aa_step calls.  *nsteps_done: steps taken.  An error on a Grid that is not 1-D, has more than
  * aa_run_1d_cap() active zones (one workgroup's LDS), or has pinned zones.  AA_1D_RESIDENT=0 in the environment at aa_create:
- * the same call steps one launch at a time.  aa_run_1d and aa_run_2d are one body (csrc/run.hip) with the rule of csrc/time_step.h;
+ * the same call steps one launch at a time.  aa_run_1d, aa_run_2d and aa_run_3d are one body (csrc/run.hip) with the rule of csrc/time_step.h;
  * the first of them that reaches the device makes the Grid's clock (one page-locked time / dt / nstep / "live" record for both,
- * and the 2-D call's copy in device memory); a Grid that never calls them allocates none.                                     */
+ * and the 2-D / 3-D call's copy in device memory); a Grid that never calls them allocates none.                                     */
 int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 /* Many steps of a 2-D Grid per host visit (csrc/hydro2d_kernels.hip k2d_advance): the same loop and the same stop rules as aa_run_1d,
  * with the time step picked on the device -- AA_2D_BATCH steps (environment at aa_create; default 32) are queued as plain launches,
@@ -171,6 +171,17 @@ int aa_run_1d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nstep
  * one aa_step at a time.                                                                                                        */
 int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 int aa_run_2d_batch(const aa_grid *g);              /* steps queued per read-back on this Grid (0: one aa_step at a time; not 2-D: 0) */
+/* Many steps of a 3-D hydro Grid per host visit (csrc/hydro_kernels.hip k3d_advance): the signature, loop and stop rules of aa_run_2d.
+ * AA_3D_BATCH steps (environment at aa_create; default 8) of the chain aa_integrate_3d_ctu launches by default -- integrators 0 and
+ * 2, second or third order, NSCALARS 0 or 1, with or without a static potential -- are queued as plain launches whose kernels read
+ * dt and dt/dx from a clock in device memory; the host reads that clock once per batch.  The same bits as that many aa_step calls.
+ * What the chain does not cover takes those aa_step calls inside the same call (aa_run_3d_batch() == 0): the van Leer integrator and
+ * fofc, a cooling function, ion radiation, AA_CORRECT_ALL off (the default below 4e5 zones), AA_X3_FUSED=0, AA_FUSED_UPDATE=0,
+ * AA_CFL_FUSED=0, AA_EDGE_OVERLAP=1, a pending aa_integrate_begin, fewer than AA_NGHOST zones along a direction, AA_3D_BATCH=0.
+ * An error on a Grid that is 1-D or 2-D (they have their own calls), has pinned zones, is cut into slabs or is a level of an
+ * aa_mesh, for tlim other than the Grid's, and for nstep_stop outside nstep .. nstep + 2^20.                                   */
+int aa_run_3d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+int aa_run_3d_batch(const aa_grid *g);              /* steps queued per read-back on this Grid (0: one aa_step at a time; not 3-D: 0) */
 int aa_run_1d_cap(void);                            /* most active zones aa_run_1d keeps resident */
 int aa_step_1d_block(void);                         /* TEST HOOK: active zones per block of the per-step kernel (the fixtures'
                                                        sizes sit either side of it); nothing in the product calls it */
