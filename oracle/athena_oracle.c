@@ -47,7 +47,9 @@ long orc_dbg_hlle = 0, orc_dbg_supersonic = 0;
 /* the branch census of the hydro step (tests/hydromatrix.py CLASSES, in this order): one slot per class and sweep direction.
  * The integrators set orc_dbg_dir before each sweep; the function-level entry points count under direction 0. */
 enum { DBG_FL, DBG_FR, DBG_HLLE_D, DBG_HLLE_P, DBG_ETAH_WINS, DBG_ETAH_NOT, DBG_LIM_ZERO, DBG_LIM_2LIM1, DBG_LIM_LIM2,
-       DBG_CLAMP, DBG_TR_EV0, DBG_TR_VXP, DBG_TR_VXM, DBG_TR_EV4, DBG_PFLOOR, DBG_PPM_FLAT, DBG_PPM_STEEP, DBG_NCLASS };
+       DBG_CLAMP, DBG_TR_EV0, DBG_TR_VXP, DBG_TR_VXM, DBG_TR_EV4, DBG_PFLOOR, DBG_PPM_FLAT, DBG_PPM_STEEP,
+       DBG_SCAL_L, DBG_SCAL_R,   /* the Roe path's scalar flux: from the left state (F[0] >= 0), from the right */
+       DBG_NCLASS };
 long orc_dbg_class[DBG_NCLASS][3];
 int orc_dbg_dir = 0;
 static int dbg_hpass = 0;     /* set while the second-pass (H-corrected) fluxes are solved: only those faces count for the etah classes */
@@ -245,7 +247,7 @@ static void flux_roe(const C1 *Ul, const C1 *Ur, const P1 *Wl, const P1 *Wr, Rea
   F[4] = 0.5*(Fl[4] + Fr[4]); F[4] -= coeff[0]*(h - v1*a); F[4] -= coeff[1]*v2; F[4] -= coeff[2]*v3;
   F[4] -= coeff[3]*(0.5*vsq); F[4] -= coeff[4]*(h + v1*a);
   F[5] = 0.0;
-  if (nscal) F[5] = (F[0] >= 0.0) ? F[0]*Wl->r : F[0]*Wr->r;                /* :316-320 */
+  if (nscal) { CNT(F[0] >= 0.0 ? DBG_SCAL_L : DBG_SCAL_R); F[5] = (F[0] >= 0.0) ? F[0]*Wl->r : F[0]*Wr->r; }                /* :316-320 */
 }
 
 /* ------------------------------------------------------------------------------------ */

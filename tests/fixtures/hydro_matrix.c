@@ -15,9 +15,11 @@
  *             pressure floor acts from the first step
  *   quiet gas density 1 ... 1.5, pressure 1 ... 1.2 and a shear of a few per cent of the sound speed in all three velocities,
  *             by patterns of co-prime periods, different per direction
+ *   scalar    (configurations with NSCALARS > 0) s = d*r, the concentration r = 0.125 ... 0.875 by a pattern of period 7 (co-prime
+ *             to the block cycle, another value across every face along each axis, exact in binary)
  * tests/hydromatrix.py states the same expressions in numpy, operation by operation.
  * Keys: <problem> dvac, pvac (gamma is read by the reference's main); seed (optional, default 0): a seed other than 0 moves every
- * conserved variable of every zone by one unit in the last place, up or down by a shift-register sequence -- the 1-ulp twins by
+ * conserved variable (the scalar included) of every zone by one unit in the last place, up or down by a shift-register sequence -- the 1-ulp twins by
  * which tests/golden/make_golden_hydromatrix.py measures how well conditioned a run of the reference is.
  */
 #include <math.h>
@@ -52,9 +54,12 @@ void problem(DomainS *pDomain)
     pG->U[k][j][i].d = d;
     pG->U[k][j][i].M1 = d*v1; pG->U[k][j][i].M2 = d*v2; pG->U[k][j][i].M3 = d*v3;
     pG->U[k][j][i].E = p/Gamma_1 + 0.5*d*(v1*v1 + v2*v2 + v3*v3);
+#if (NSCALARS > 0)
+    pG->U[k][j][i].s[0] = d*(0.125 + 0.125*(Real)((a + 3*b + 5*c) % 7));
+#endif
     if (seed != 0) {
       Real *q = (Real*)&(pG->U[k][j][i]); int n;
-      for (n = 0; n < 5; n++) { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; q[n] = nextafter(q[n], (rs & 1024) ? 1.0e300 : -1.0e300); }
+      for (n = 0; n < 5 + NSCALARS; n++) { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; q[n] = nextafter(q[n], (rs & 1024) ? 1.0e300 : -1.0e300); }
     }
   }
 }

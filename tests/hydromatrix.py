@@ -12,9 +12,16 @@ receding flows run across it.  With PVAC < 0 its total energy lies below the kin
 the pressure floor of Cons1D_to_Prim1D then acts from the first step; only the configurations that survive it are run so.  A small
 shear of all three velocities by integer patterns of co-prime periods keeps every momentum non-uniform and different per direction.
 
+With a passive scalar (nscal = 1: the NS = 1 instantiations of every hydro kernel) the sixth column is s = d * r, the concentration
+r = 0.125 + 0.125 * ((a + 3 b + 5 c) % 7): period 7, co-prime to the block cycle, another value across every face along each axis,
+exact in binary.  The scalar is passive: the reference's hydro columns, dt and time of such a run equal the scalar-free run's bit for
+bit (asserted by tests/golden/make_golden_hydromatrix.py), so a scalar fixture hydromatrix_s1_* stores the sixth column only and names
+its base fixture; `load` puts the two together.
+
 A failing GPU comparison is read with the census: the first differing zone's faces are classified by `face_classes` on the
 state before the step (supersonic return, HLLE, Roe), which names the branch of the kernel to look at."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -30,12 +37,13 @@ NSTEP = 3
 # the classes of orc_dbg_class, in its order (oracle/athena_oracle.c)
 CLASSES = ("F=Fl", "F=Fr", "HLLE u0<=0", "HLLE p_inter<0", "etah wins a wave", "etah loses a wave", "limiter zero", "limiter 2 lim1",
            "limiter lim2", "clamp acts", "trace ev0>=0", "trace vx>=0", "trace vx<=0", "trace ev4<=0", "pressure floor",
-           "ppm flat", "ppm steepened")
+           "ppm flat", "ppm steepened", "scalar from the left", "scalar from the right")
 ROE = CLASSES[:4]
 HCORR = CLASSES[4:6]
 RECON = CLASSES[6:10]
 TRACE = CLASSES[10:14]
 PPM = CLASSES[15:17]
+SCALAR = CLASSES[17:19]      # the Roe path's scalar flux: F[0] >= 0 takes the left state's concentration, F[0] < 0 the right's
 MIN_COUNT = 32
 
 
@@ -56,8 +64,13 @@ def near_vacuum(a, b, c):
     return (a // BLK + b // BLK + c // BLK) % 5 == 1
 
 
-def pattern(nx, gamma, level=0, disp=(0, 0, 0), dvac=DVAC, pvac=PVAC):
-    """Initial state of tests/fixtures/hydro_matrix.c on the active zones [k][j][i][6]"""
+def concentration(a, b, c):
+    """the scalar over the density of the root zone (a, b, c)"""
+    return 0.125 + 0.125 * ((a + 3 * b + 5 * c) % 7).astype(np.float64)
+
+
+def pattern(nx, gamma, level=0, disp=(0, 0, 0), dvac=DVAC, pvac=PVAC, nscal=0):
+    """Initial state of tests/fixtures/hydro_matrix.c on the active zones [k][j][i][6]; the sixth column is zero without a scalar"""
     a, b, c = root_indices(nx, level, disp)
     d = 1.0 + 0.125 * ((a + 2 * b + 3 * c) % 5).astype(np.float64)
     p = 1.0 + 0.1 * ((2 * a + b + c) % 3).astype(np.float64)
@@ -72,6 +85,8 @@ def pattern(nx, gamma, level=0, disp=(0, 0, 0), dvac=DVAC, pvac=PVAC):
     U = np.zeros(d.shape + (6,))
     U[..., 0] = d; U[..., 1] = d * v[0]; U[..., 2] = d * v[1]; U[..., 3] = d * v[2]
     U[..., 4] = p / (gamma - 1.0) + 0.5 * d * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    if nscal:
+        U[..., 5] = d * concentration(a, b, c)
     return U
 
 
@@ -133,22 +148,55 @@ def smr_overrides(case, cour_no=0.4):
     return o + [f"time/cour_no={cour_no}"]
 
 
-def make_sim(cfg, nx):
+def make_sim(cfg, nx, nscal=0):
     """The oracle set up like the reference configuration CFG[cfg] built on tests/fixtures/hydro_matrix.c: blast deck, periodic"""
     _, integrator, order, cour, dvac, pvac = CFG[cfg]
-    s = orc.make_sim("blast", overrides(nx, cour), integrator=integrator, order=order)
-    s.active[...] = pattern(nx, s.grid.run.gamma, dvac=dvac, pvac=pvac)
+    s = orc.make_sim("blast", overrides(nx, cour), integrator=integrator, order=order, nscal=nscal)
+    s.active[...] = pattern(nx, s.grid.run.gamma, dvac=dvac, pvac=pvac, nscal=nscal)
     return s
 
 
-def make_mesh(tag):
+def make_mesh(tag, nscal=0):
     """The oracle's nested levels (3-D only) set up like the reference's blast_smr configuration on the problem file"""
     _, integrator, case, cour, dvac, pvac = SMR_CFG[tag]
-    m = orc.make_mesh("blast", None, smr_overrides(case, cour), integrator=integrator)
+    m = orc.make_mesh("blast", None, smr_overrides(case, cour), integrator=integrator, nscal=nscal)
     for s in m.lev:
         g = s.grid
-        s.active[...] = pattern(g.Nx, g.run.gamma, g.level, g.disp if g.level else (0, 0, 0), dvac, pvac)
+        s.active[...] = pattern(g.Nx, g.run.gamma, g.level, g.disp if g.level else (0, 0, 0), dvac, pvac, nscal)
     return m
+
+
+# ---- the fixtures ----------------------------------------------------------------------------------------------------
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SCAL_CFG = tuple(CFG)        # the single-level configurations with a scalar fixture on both SHAPES_3D
+SCAL_SMR = ("3d_ctu",)       # the nested cases with one
+
+
+def fixture_name(cfg, nx, nscal=0):
+    return ("hydromatrix_s1_" if nscal else "hydromatrix_") + cfg + "_" + "x".join(str(n) for n in (nx if nx[2] > 1 else nx[:2])) + f"_n{NSTEP}"
+
+
+def smr_fixture_name(tag, nscal=0):
+    return ("hydromatrix_s1_smr_" if nscal else "hydromatrix_smr_") + tag + f"_n{NSTEP}"
+
+
+def load(name):
+    """-> a fixture as a dict of arrays.  A scalar fixture (hydromatrix_s1_*: s0, s -- or s0_<l>, s_<l> per level -- and the name of
+    its base) comes back as its base's entries with U0 / U (U0_<l> / U_<l>) widened to six columns and nscal = 1"""
+    z = np.load(os.path.join(GOLD, name + ".npz"))
+    g = {k: z[k] for k in z.files}
+    if "base" not in g:
+        g.setdefault("nscal", np.array(0))
+        return g
+    out = load(str(g["base"]))
+    for k, v in g.items():
+        head, _, level = k.partition("_")
+        if head in ("s0", "s"):
+            u = ("U0" if head == "s0" else "U") + ("_" + level if level else "")
+            out[u] = np.concatenate([out[u], v[..., None]], axis=-1)
+        else:
+            out[k] = v
+    return out
 
 
 def face_classes(U, axis, gamma):
@@ -183,9 +231,9 @@ def counters():
     return np.ctypeslib.as_array(arr).reshape(n, 3)
 
 
-def census(cfg, nx, nstep=NSTEP):
+def census(cfg, nx, nstep=NSTEP, nscal=0):
     """-> (counts [step][class][direction] of the oracle's run, the Sim after it)"""
-    s = make_sim(cfg, nx).start()
+    s = make_sim(cfg, nx, nscal).start()
     cnt = counters()
     out = np.zeros((nstep,) + cnt.shape, dtype=np.int64)
     for n in range(nstep):
@@ -195,9 +243,9 @@ def census(cfg, nx, nstep=NSTEP):
     return out, s
 
 
-def census_mesh(tag, nstep=NSTEP):
+def census_mesh(tag, nstep=NSTEP, nscal=0):
     """-> counts [step][class][direction] of the oracle's nested run `tag`, all levels together"""
-    m = make_mesh(tag).start()
+    m = make_mesh(tag, nscal).start()
     cnt = counters()
     out = np.zeros((nstep,) + cnt.shape, dtype=np.int64)
     for n in range(nstep):
@@ -213,12 +261,12 @@ def floored_zones(U, gamma):
     return int((P <= 1.0e-20).sum())
 
 
-def required(cfg):
+def required(cfg, nscal=0):
     """the classes a run of configuration `cfg` has to reach MIN_COUNT times per sweep direction and step"""
-    return required_for(*CFG[cfg][1:3], CFG[cfg][5])
+    return required_for(*CFG[cfg][1:3], CFG[cfg][5], nscal)
 
 
-def required_for(integrator, order, pvac):
+def required_for(integrator, order, pvac, nscal=0):
     need = list(ROE) + list(RECON)
     if integrator != "vl":
         need += list(TRACE)                    # (van Leer reconstructs without tracing)
@@ -228,4 +276,29 @@ def required_for(integrator, order, pvac):
         need.append("pressure floor")
     if order == 3:
         need += list(PPM)
+    if nscal:
+        need += list(SCALAR)
     return need
+
+
+def scalar_faces(U, axis, gamma):
+    """-> counts (Roe flux, F = Fl, F = Fr, HLLE) of the first-order faces along `axis` of a six-column state across which the
+    concentration s / d differs: the faces on which a scalar flux taken from the wrong side would show.  (The scalar flux has one
+    rule per exit of the solver; the HLLE fallback's is the same whichever test sent the face there.)"""
+    r = U[..., 5] / U[..., 0]
+    differ = r != np.roll(r, -1, axis=2 - axis)
+    n = np.bincount(face_classes(U[..., :5], axis, gamma)[differ].ravel(), minlength=5)
+    return np.array([n[0], n[1], n[2], n[3] + n[4]])
+
+
+def describe_zone(U0, zone, gamma):
+    """the outcome of the Roe solver on the six first-order faces of `zone` [k, j, i] of the state U0 before the first step, as a
+    line to print beside a failing comparison: it names the branch of the kernel to look at"""
+    names = ("Roe", "F=Fl", "F=Fr", "HLLE u0<=0", "HLLE p_inter<0")
+    k, j, i = (int(z) for z in zone)
+    out = []
+    for ax in range(3 if U0.shape[0] > 1 else 2):
+        cls = face_classes(U0[..., :5], ax, gamma)
+        lo = [k, j, i]; lo[2 - ax] = (lo[2 - ax] - 1) % U0.shape[2 - ax]
+        out.append(f"x{ax + 1} lower {names[cls[tuple(lo)]]}, upper {names[cls[k, j, i]]}")
+    return f"zone [k, j, i] = {[k, j, i]}: " + "; ".join(out)

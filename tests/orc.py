@@ -222,11 +222,14 @@ class Sim:
     def ion_dt_hydro(self): return self.L.orc_ion_dt_hydro(self.h)
 
 
-def make_sim(problem, overrides=None, rank=0, nranks=1, integrator="ctu", order=2):
+def make_sim(problem, overrides=None, rank=0, nranks=1, integrator="ctu", order=2, nscal=None):
+    """nscal: the number of passive scalars where it is not the problem's own (a hydro-only NSCALARS = 1 configuration on the blast deck)"""
     aa = importlib.import_module("atmospheric-athena_amd")
     run = aa.config.load(os.path.join(DECKS, "athinput." + problem), overrides, problem)
     run.integrator = integrator
     run.order = order
+    if nscal is not None:
+        run.nscal = nscal
     return Sim(aa.config.slab(run, rank, nranks)).problem()
 
 
@@ -347,12 +350,14 @@ def deck_for(problem, g):
     return f.name
 
 
-def make_mesh(problem, deck_path=None, overrides=None, integrator="ctu", order=2):
+def make_mesh(problem, deck_path=None, overrides=None, integrator="ctu", order=2, nscal=None):
     aa = importlib.import_module("atmospheric-athena_amd")
     par = aa.athinput.ParTable.from_file(deck_path or os.path.join(DECKS, "athinput." + problem)).cmdline(overrides)
     run = aa.config.from_par(par, problem)
     run.integrator = integrator
     run.order = order
+    if nscal is not None:
+        run.nscal = nscal
     return Mesh(aa.config.levels(par, run)).problem()
 
 

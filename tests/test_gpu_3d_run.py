@@ -82,15 +82,17 @@ def sphere(nx, strict):
     return g
 
 
-def matrix(cfg, nx, strict):
+def matrix(cfg, nx, strict, nscal=0):
     """the designed state of tests/hydromatrix.py, as test_gpu_hydro_branches.run_single sets it up"""
     aa, lib = pkg(), pkg("lib")
     _, integrator, order, cour, dvac, pvac = hm.CFG[cfg]
     run = aa.config.load(os.path.join(orc.DECKS, "athinput.blast"), hm.overrides(nx, cour), "blast", integrator)
     run.order = order
-    g = lib.setup_problem(aa.config.slab(run), 0, strict)
+    run.nscal = nscal
+    g = lib.Grid(aa.config.slab(run), 0, strict) if nscal else lib.setup_problem(aa.config.slab(run), 0, strict)
+    assert g.nvar == 5 + nscal
     blk = g.new_host_block()
-    active(blk)[...] = hm.pattern(nx, run.gamma, dvac=dvac, pvac=pvac)[..., :5]
+    active(blk)[...] = hm.pattern(nx, run.gamma, dvac=dvac, pvac=pvac, nscal=nscal)[..., :5 + nscal]
     g.upload(blk)
     g.start()
     return g
@@ -124,6 +126,10 @@ def per_step(make, n):
 
 # ---- 1. the fixtures: the reference's states, and the per-step path's bits -------------------------------------------------------
 FIXTURES = ["blast_16x16x16_n5", "blast_12x20x16_n4"] + [f"hydromatrix_{c}_{s}_n3" for c in ("ctu", "noh", "ppm") for s in ("24x20x16", "67x10x9")]
+# with a passive scalar (the *_dc entries of the NS = 1 kernels without a potential): CTU on both Grids, no-H and PPM across the tile edge
+# (measured on an MI355X: the strict build bit for bit over six columns, queued and by size; the default build 6.1e-16 ... 2.0e-15 of
+#  each field's maximum with no zone beyond 1e-9, against twins of 4.7e-4 ... 8.7e-3)
+FIXTURES += ["hydromatrix_s1_ctu_24x20x16_n3", "hydromatrix_s1_ctu_67x10x9_n3", "hydromatrix_s1_noh_67x10x9_n3", "hydromatrix_s1_ppm_67x10x9_n3"]
 
 
 @pytest.mark.parametrize("strict", [True, False], ids=["strict", "default"])
@@ -137,11 +143,13 @@ def test_run_3d_reproduces_the_reference_and_the_per_step_path(name, chain, stri
     n = int(fx["nstep"])
     nx = tuple(int(x) for x in fx["nx"])
     cfg = str(fx["cfg"]) if "cfg" in fx else None
-    make = (lambda: matrix(cfg, nx, strict)) if cfg else (lambda: blast(nx, strict))
+    nscal = int(fx["nscal"]) if cfg else 0
+    make = (lambda: matrix(cfg, nx, strict, nscal)) if cfg else (lambda: blast(nx, strict))
     g = make()
     assert g.can_run_3d() and g.run_3d_batch() == (2 if chain == "queued" else 0)
     if cfg:
-        assert np.array_equal(active(g.download())[..., :5], fx["U0"]), "the uploaded pattern is the fixture's U0"
+        assert fx["U"].shape[-1] == 5 + nscal
+        assert np.array_equal(active(g.download())[..., :5 + nscal], fx["U0"]), "the uploaded pattern is the fixture's U0"
     dt0 = g.dt
     g.host_syncs(True)
     assert g.run_3d(FAR, nstep_stop=n) == n
@@ -162,7 +170,7 @@ def test_run_3d_reproduces_the_reference_and_the_per_step_path(name, chain, stri
         assert np.array_equal(Ua, fx["U"][..., :nv]), float(err.max())
         assert s[0][0] == float(fx["time"]) and s[0][1] == float(fx["dt"])
     elif cfg:
-        w, nf, nz = twins.hydro_matrix(cfg, nx)
+        w, nf, nz = twins.hydro_matrix(cfg, nx, nscal)
         hold_default(f"{name} {chain}", [err], w, nf / nz)
     else:
         assert float(err.max()) < 1e-11, err.max(axis=(0, 1, 2))

@@ -28,8 +28,18 @@ energy there, as in the single-level van Leer runs, the REFERENCE's own 1-ulp tw
 the first child's side (a decision on the rounding noise of a floored pressure; tests/hydromatrix.py SMR_CFG): that run
 ("2d_vl_floor") is held in the strict build only, which has to follow the reference decision for decision.
 
+With a passive scalar (the NS = 1 instantiations of every hydro kernel, without a potential; the scalar fixtures hydromatrix_s1_*,
+sections 4 and 5 below): the same chains on six variables, the concentration another one across every face.  The rules are the
+same ones over six columns: the strict build bit for bit, the default build against the oracle's twins of the six-variable run.
+Measured on an MI355X (the strict build is bit for bit in all 29 cases, six columns, time, dt and dt0): the twins of the six-variable
+CTU, no-H and PPM runs spread by 4.7e-4 ... 1.0e-2 with nearly every zone beyond 1e-9, those of the van Leer runs by 1.9e-15 ...
+2.7e-15 with none.  The default build differs by 6.5e-16 ... 2.0e-15 under CTU (with and without H-correction, every chain),
+6.1e-16 ... 6.7e-16 under PPM, 1.1e-15 ... 1.8e-15 under van Leer and 9.2e-16 ... 9.3e-16 under van Leer + PPM, no zone beyond 1e-9
+in any single-level case; the nested case by 8.0e-16 on either schedule and by 9.6e-9 in 6 zones of the child on the big-grid
+kernels, as without the scalar.
+
 A failure is read with hydromatrix.face_classes on the state before the step: the first differing zone's faces name the branch
-(supersonic return, HLLE, Roe) of the kernel to look at."""
+(supersonic return, HLLE, Roe) of the kernel to look at; the scalar tests print that line themselves (hydromatrix.describe_zone)."""
 import importlib
 import os
 
@@ -61,10 +71,9 @@ _fx = {}
 
 
 def fixture(name):
-    """the npz as a dict, read once and shared (nobody writes into it)"""
+    """the npz as a dict (a scalar fixture put together with its base: six columns), read once and shared (nobody writes into it)"""
     if name not in _fx:
-        z = np.load(os.path.join(GOLD, name + ".npz"))
-        _fx[name] = {k: z[k] for k in z.files}
+        _fx[name] = hm.load(name)
         for a in _fx[name].values():
             a.setflags(write=False)
     return _fx[name]
@@ -100,16 +109,18 @@ def hold_default(label, errs, twin_worst, twin_share):
     assert worst < CEILING, (label, worst)
 
 
-def run_single(aa, lib, cfg, nx, strict):
+def run_single(aa, lib, cfg, nx, strict, nscal=0):
     """upload the pattern, start(), NSTEP steps -> (U of the active zones, time, dt, dt0)"""
     _, integrator, order, cour, dvac, pvac = hm.CFG[cfg]
     deck = os.path.join(orc.DECKS, "athinput.blast2d" if nx[2] == 1 else "athinput.blast")
     run = aa.config.load(deck, hm.overrides(nx, cour), "blast", integrator)
     run.order = order
-    g = lib.setup_problem(aa.config.slab(run), 0, strict)
+    run.nscal = nscal           # (the blast deck on a hydro-only NSCALARS = 1 configuration: no problem generator, the pattern is the state)
+    g = lib.Grid(aa.config.slab(run), 0, strict) if nscal else lib.setup_problem(aa.config.slab(run), 0, strict)
     try:
+        assert g.nvar == 5 + nscal
         blk = g.new_host_block()
-        active(blk)[...] = hm.pattern(nx, run.gamma, dvac=dvac, pvac=pvac)[..., :5]
+        active(blk)[...] = hm.pattern(nx, run.gamma, dvac=dvac, pvac=pvac, nscal=nscal)[..., :5 + nscal]
         g.upload(blk)
         g.start()
         dt0 = g.dt
@@ -120,12 +131,25 @@ def run_single(aa, lib, cfg, nx, strict):
         g.close()
 
 
-def check_single(aa, lib, cfg, nx, strict, label):
-    name = f"hydromatrix_{cfg}_" + "x".join(str(n) for n in (nx if nx[2] > 1 else nx[:2])) + f"_n{hm.NSTEP}"
-    fx = fixture(name)
-    assert np.array_equal(hm.pattern(nx, hm.gamma(nx[2]), dvac=hm.CFG[cfg][4], pvac=hm.CFG[cfg][5])[..., :5], fx["U0"]), "the uploaded pattern is the fixture's U0"
-    U, time, dt, dt0 = run_single(aa, lib, cfg, nx, strict)
+def name_the_branch(label, U0s, errs, gam, beyond=0.0):
+    """print the first zone of each level whose error lies beyond `beyond`, and the outcome of the Roe solver on its faces in the
+    state before the first step: which branch of the kernel to look at"""
+    for l, (U0, e) in enumerate(zip(U0s, errs)):
+        bad = np.argwhere((e > beyond).any(axis=-1))
+        if len(bad):
+            print(f"{label}: level {l}, {len(bad)} zones differ, errors per field of the first {e[tuple(bad[0])].tolist()}; "
+                  + hm.describe_zone(U0, bad[0], gam))
+
+
+def check_single(aa, lib, cfg, nx, strict, label, nscal=0):
+    nv = 5 + nscal
+    fx = fixture(hm.fixture_name(cfg, nx, nscal))
+    assert fx["U"].shape[-1] == nv
+    assert np.array_equal(hm.pattern(nx, hm.gamma(nx[2]), dvac=hm.CFG[cfg][4], pvac=hm.CFG[cfg][5], nscal=nscal)[..., :nv], fx["U0"]), "the uploaded pattern is the fixture's U0"
+    U, time, dt, dt0 = run_single(aa, lib, cfg, nx, strict, nscal)
     err = errors(U, fx["U"])
+    if nscal:
+        name_the_branch(label, [fx["U0"]], [err], hm.gamma(nx[2]), 0.0 if strict else 1e-9)
     if strict:
         print(f"{label} strict: max error {err.max():.3e}, dt0 {dt0!r} dt {dt!r} time {time!r}")
         assert dt0 == float(fx["dt0"])
@@ -134,7 +158,7 @@ def check_single(aa, lib, cfg, nx, strict, label):
     else:
         assert abs(dt0 / float(fx["dt0"]) - 1) < 1e-12
         if nx[2] > 1:
-            w, n, nz = twins.hydro_matrix(cfg, nx)
+            w, n, nz = twins.hydro_matrix(cfg, nx, nscal)
             hold_default(label, [err], w, n / nz)
         else:
             hold_default(label, [err], *twins.hydro_matrix(cfg))
@@ -178,7 +202,7 @@ def test_2d_integrators_on_the_designed_state(aa, lib, cfg, nx, cfl_fused, stric
 
 
 # ---- 3. nested levels -----------------------------------------------------------------------------------------------------------
-def run_mesh(aa, lib, tag, strict):
+def run_mesh(aa, lib, tag, strict, nscal=0):
     """upload the pattern on every level, aa_mesh_start, NSTEP steps -> (whole blocks of every level, time, dt, dt0, the Grids' configs)"""
     _, integrator, case, cour, dvac, pvac = hm.SMR_CFG[tag]
     two_d = case[0][2] == 1
@@ -186,12 +210,15 @@ def run_mesh(aa, lib, tag, strict):
     ov = hm.smr_overrides(case, cour)
     par = aa.athinput.ParTable.from_file(deck).cmdline(ov)
     run = aa.config.load(deck, ov, "blast", integrator)
-    m = lib.Mesh((aa.config.levels_2d if two_d else aa.config.levels)(par, run), 0, strict)
+    run.nscal = nscal
+    # (the blast generator has no scalar and refuses NSCALARS = 1: with one the levels are created without it, the pattern is the state)
+    m = lib.Mesh((aa.config.levels_2d if two_d else aa.config.levels)(par, run), 0, strict, initial=not nscal)
     try:
         for g in m.lev:
             c = g.cfg
             blk = g.new_host_block()
-            active(blk)[...] = hm.pattern(tuple(c.Nx), run.gamma, c.level, tuple(c.disp) if c.level else (0, 0, 0), dvac, pvac)[..., :5]
+            assert g.nvar == 5 + nscal
+            active(blk)[...] = hm.pattern(tuple(c.Nx), run.gamma, c.level, tuple(c.disp) if c.level else (0, 0, 0), dvac, pvac, nscal)[..., :5 + nscal]
             g.upload(blk)
         m.start()
         dt0 = m.dt
@@ -219,14 +246,21 @@ def test_nested_levels_on_the_designed_state(aa, lib, tag, knobs, strict, monkey
     boundaries, strict build only).  Every side of every child lies on a block edge across
     which the flow recedes: the fluxes kept for the flux correction come from HLLE, upwind and Roe faces."""
     set_knobs(monkeypatch, knobs)
-    fx = fixture(f"hydromatrix_smr_{tag}_n{hm.NSTEP}")
+    check_mesh(aa, lib, tag, strict, f"nested {tag} {knobs}")
+
+
+def check_mesh(aa, lib, tag, strict, label, nscal=0):
+    nv = 5 + nscal
+    fx = fixture(hm.smr_fixture_name(tag, nscal))
     _, integrator, case, cour, dvac, pvac = hm.SMR_CFG[tag]
     for l in range(int(fx["nlevels"])):
-        U0 = hm.pattern(tuple(fx["nxs"][l]), hm.gamma(case[0][2]), int(fx["levels"][l]), tuple(fx["disp"][l]), dvac, pvac)
-        assert np.array_equal(U0[..., :5], fx[f"U0_{l}"]), f"the uploaded pattern is the fixture's U0, level {l}"
-    blocks, time, dt, dt0 = run_mesh(aa, lib, tag, strict)
+        U0 = hm.pattern(tuple(fx["nxs"][l]), hm.gamma(case[0][2]), int(fx["levels"][l]), tuple(fx["disp"][l]), dvac, pvac, nscal)
+        assert fx[f"U_{l}"].shape[-1] == nv
+        assert np.array_equal(U0[..., :nv], fx[f"U0_{l}"]), f"the uploaded pattern is the fixture's U0, level {l}"
+    blocks, time, dt, dt0 = run_mesh(aa, lib, tag, strict, nscal)
     errs = [errors(active(U), fx[f"U_{l}"]) for l, U in enumerate(blocks)]
-    label = f"nested {tag} {knobs}"
+    if nscal:
+        name_the_branch(label, [fx[f"U0_{l}"] for l in range(len(blocks))], errs, hm.gamma(case[0][2]), 0.0 if strict else 1e-9)
     if strict:
         print(f"{label} strict: max error per level {[float(e.max()) for e in errs]}, dt0 {dt0!r} dt {dt!r}")
         assert dt0 == float(fx["dt0"])
@@ -234,22 +268,51 @@ def test_nested_levels_on_the_designed_state(aa, lib, tag, knobs, strict, monkey
             assert np.array_equal(active(U), fx[f"U_{l}"]), (label, l, np.argwhere((active(U) != fx[f"U_{l}"]).any(axis=-1))[:4].tolist())
         assert time == float(fx["time"]) and dt == float(fx["dt"])
         if case[0][2] > 1:          # the whole blocks, ghost zones as Prolongate left them, against the oracle
-            o = oracle_mesh_blocks(tag)
+            o = oracle_mesh_blocks(tag, nscal)
             for l, U in enumerate(blocks):
                 assert np.array_equal(U, o[l]), (label, "whole block", l, np.argwhere((U != o[l]).any(axis=-1))[:4].tolist())
     else:
         assert abs(dt0 / float(fx["dt0"]) - 1) < 1e-12
         cfg = {"ctu": "ctu", "vl": "vl"}[integrator]
-        hold_default(label, errs, *twins.hydro_matrix(cfg))
+        hold_default(label, errs, *twins.hydro_matrix(cfg, None, nscal))
 
 
 _oracle_blocks = {}
 
 
-def oracle_mesh_blocks(tag):
-    if tag not in _oracle_blocks:
-        m = hm.make_mesh(tag).start()
+def oracle_mesh_blocks(tag, nscal=0):
+    if (tag, nscal) not in _oracle_blocks:
+        m = hm.make_mesh(tag, nscal).start()
         for _ in range(hm.NSTEP):
             m.step()
-        _oracle_blocks[tag] = [s.U[..., :5].copy() for s in m.lev]
-    return _oracle_blocks[tag]
+        _oracle_blocks[tag, nscal] = [s.U[..., :5 + nscal].copy() for s in m.lev]
+    return _oracle_blocks[tag, nscal]
+
+
+# ---- 4. one level, 3-D, with a passive scalar ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "default"])
+@pytest.mark.parametrize("nx", hm.SHAPES_3D, ids=["x".join(map(str, s)) for s in hm.SHAPES_3D])
+@pytest.mark.parametrize("cfg,knobs", CASES_3D, ids=ids(CASES_3D))
+def test_3d_kernel_chains_with_a_passive_scalar(aa, lib, cfg, knobs, nx, strict, monkeypatch):
+    """Every chain of section 1 on six variables: the NS = 1 instantiations without a potential (the ones every scalar run without
+    gravity takes).  The concentration differs across every face, so the scalar flux's rule behind each exit of the Roe solver
+    (upwind returns, HLLE, the Roe path's choice by the sign of the mass flux), the sixth column of the reconstruction and the
+    tracing, and the sixth variable's way through tiles, halos and parked fluxes all carry data, differently along x1, x2 and x3.
+    67x10x9 crosses the 64-lane tile edge along x1 with every extent off the tile sizes: the smallest Grid on which k_correct_all's
+    x1 halo of the sixth variable and its tile-edge fluxes are read; 24x20x16 has several rows of tiles along x2."""
+    set_knobs(monkeypatch, knobs)
+    check_single(aa, lib, cfg, nx, strict, f"scalar {cfg} {knobs} {nx}", nscal=1)
+
+
+# ---- 5. nested levels with a passive scalar ----------------------------------------------------------------------------------------
+SMR_SCALAR = [(t, k) for t, k in SMR_CASES if t in hm.SCAL_SMR]
+
+
+@pytest.mark.parametrize("strict", [True, False], ids=["strict", "default"])
+@pytest.mark.parametrize("tag,knobs", SMR_SCALAR, ids=ids(SMR_SCALAR))
+def test_nested_levels_with_a_passive_scalar(aa, lib, tag, knobs, strict, monkeypatch):
+    """The 3-D nested case on six variables under its three knob sets: restriction, prolongation (the scalar's slopes) and flux
+    correction of the sixth column.  Strict build: every level's active zones against the fixture and the whole blocks, ghost zones
+    as the prolongation left them, against the oracle; default build: the single-level twins of the six-variable CTU run."""
+    set_knobs(monkeypatch, knobs)
+    check_mesh(aa, lib, tag, strict, f"scalar nested {tag} {knobs}", nscal=1)

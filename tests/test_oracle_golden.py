@@ -164,19 +164,28 @@ def _hydromatrix(name, g):
     every branch of the Roe solver, the reconstruction and the tracing.  3-D runs, one level or nested: the oracle reaches the
     reference's state bit for bit, and its live counters of the Roe solver's four exits equal, step by step, the execution counts
     gcov read from the reference's own run (cov_roe) -- the same faces are solved, the same branches taken.  2-D runs (the oracle
-    has no 2-D path): the fixture starts from the pattern and stays finite with positive density."""
+    has no 2-D path): the fixture starts from the pattern and stays finite with positive density.  A scalar fixture
+    (hydromatrix_s1_*, put together with its base by hydromatrix.load) is reproduced over six columns, and its concentration s / d
+    stays finite within the range the fixture records."""
+    g = hydromatrix.load(name)
+    nscal = int(g["nscal"]); nv = 5 + nscal
+    if nscal:
+        states = [g[k] for k in g if k == "U" or k.startswith("U_")]
+        r = [U[..., 5] / U[..., 0] for U in states]
+        assert all(np.isfinite(x).all() for x in r)
+        assert [min(float(x.min()) for x in r), max(float(x.max()) for x in r)] == g["conc_range"].tolist()
     cnt = hydromatrix.counters()
-    if "nlevels" in g.files:
+    if "nlevels" in g:
         _, integrator, case, cour, dvac, pvac = hydromatrix.SMR_CFG[str(g["tag"])]
         assert (float(g["dvac"]), float(g["pvac"])) == (dvac, pvac)
         gam = hydromatrix.gamma(case[0][2])
         for l in range(int(g["nlevels"])):
-            U0 = hydromatrix.pattern(tuple(g["nxs"][l]), gam, int(g["levels"][l]), tuple(g["disp"][l]), dvac, pvac)
-            assert _same(U0[..., :5], g[f"U0_{l}"]), f"initial condition, level {l}"
+            U0 = hydromatrix.pattern(tuple(g["nxs"][l]), gam, int(g["levels"][l]), tuple(g["disp"][l]), dvac, pvac, nscal)
+            assert _same(U0[..., :nv], g[f"U0_{l}"]), f"initial condition, level {l}"
             assert np.isfinite(g[f"U_{l}"]).all() and (g[f"U_{l}"][..., 0] > 0).all() and (g[f"U0_{l}"][..., 0] > 0).all()
         if case[0][2] == 1:
             return
-        m = hydromatrix.make_mesh(str(g["tag"]))
+        m = hydromatrix.make_mesh(str(g["tag"]), nscal)
         m.start()
         assert m.dt == float(g["dt0"])
         for n in range(int(g["nstep"])):
@@ -185,7 +194,7 @@ def _hydromatrix(name, g):
             assert cnt[:4].sum(axis=1).tolist() == g["cov_roe"][n].tolist(), f"exits of the Roe solver in step {n + 1}"
         assert m.time == float(g["time"]) and m.dt == float(g["dt"])
         for l, s in enumerate(m.lev):
-            assert _same(s.active[..., :5], g[f"U_{l}"]), f"level {l}"
+            assert _same(s.active[..., :nv], g[f"U_{l}"]), f"level {l}"
         return
     cfg, nx = str(g["cfg"]), tuple(int(n) for n in g["nx"])
     dvac, pvac = hydromatrix.CFG[cfg][4:]
@@ -194,8 +203,8 @@ def _hydromatrix(name, g):
     if nx[2] == 1:
         assert _same(hydromatrix.pattern(nx, hydromatrix.gamma(1), dvac=dvac, pvac=pvac)[..., :5], g["U0"]), "initial condition"
         return
-    s = hydromatrix.make_sim(cfg, nx)
-    assert _same(s.active[..., :5], g["U0"]), "initial condition"
+    s = hydromatrix.make_sim(cfg, nx, nscal)
+    assert _same(s.active[..., :nv], g["U0"]), "initial condition"
     s.start()
     assert s.dt == float(g["dt0"])
     for n in range(int(g["nstep"])):
@@ -203,7 +212,7 @@ def _hydromatrix(name, g):
         s.step()
         assert cnt[:4].sum(axis=1).tolist() == g["cov_roe"][n].tolist(), f"exits of the Roe solver in step {n + 1}"
     assert s.time == float(g["time"]) and s.dt == float(g["dt"])
-    assert _same(s.active[..., :5], g["U"])
+    assert _same(s.active[..., :nv], g["U"])
 
 
 SMALL_GRID_MIN = 8
@@ -228,9 +237,14 @@ def test_hydro_matrix_covers_every_branch(name):
                        is asked for SMALL_GRID_MIN = 8 times per direction (32 scaled by the faces is 6.6), the returns 32 times.
                        The 2-D van Leer fixtures hold >= 32 zones whose pressure is floored in the first state.
     At least 5 % of the zones of the first state lie in supersonic blocks.  Every side of every child Domain holds an HLLE face, and
-    at least two sides of every child an upwind face (first-order Riemann problems of the root's last stored state across the outline)."""
-    g = np.load(os.path.join(GOLD, name + ".npz"))
-    nested = "nlevels" in g.files
+    at least two sides of every child an upwind face (first-order Riemann problems of the root's last stored state across the outline).
+      with a scalar    (hydromatrix_s1_*) also the Roe path's scalar flux taken from the left state (F[0] >= 0) and from the right,
+                       per direction and step; and on the first state, per direction, at least 32 faces of each outcome of the Roe
+                       solver (Roe flux, F = Fl, F = Fr, HLLE) ACROSS WHICH THE CONCENTRATION DIFFERS
+                       -- a scalar flux taken from the wrong side shows only there."""
+    g = hydromatrix.load(name)
+    nscal = int(g["nscal"])
+    nested = "nlevels" in g
     nx = tuple(int(n) for n in (g["nxs"][0] if nested else g["nx"]))
     gam = hydromatrix.gamma(nx[2])
     ndir = 2 if nx[2] == 1 else 3
@@ -244,6 +258,10 @@ def test_hydro_matrix_covers_every_branch(name):
     if nested or ndir == 2:
         hlle_min = SMALL_GRID_MIN if U0[..., 0].size < 1000 else hydromatrix.MIN_COUNT
         assert all((f[:2] >= hydromatrix.MIN_COUNT).all() and (f[2:] >= hlle_min).all() for f in first), first
+    if nscal:
+        across = [hydromatrix.scalar_faces(U0, ax, gam) for ax in range(ndir)]
+        print(name, "first-order faces across which the concentration differs, per direction (Roe, Fl, Fr, HLLE):", [f.tolist() for f in across])
+        assert all((f >= hydromatrix.MIN_COUNT).all() for f in across), across
     pvac = float(g["pvac"])
     floored = hydromatrix.floored_zones(U0, gam)
     print(name, "zones of the first state with a floored pressure:", floored)
@@ -273,19 +291,19 @@ def test_hydro_matrix_covers_every_branch(name):
             assert sides_with_upwind >= 2, (name, l, sides_with_upwind)
         if ndir == 3:           # the oracle runs the nested 3-D case: its full census, all levels together
             _, integrator, case, cour, dvac, pvac = hydromatrix.SMR_CFG[str(g["tag"])]
-            cnt = hydromatrix.census_mesh(str(g["tag"]))
+            cnt = hydromatrix.census_mesh(str(g["tag"]), nscal=nscal)
             table = {c: cnt[:, i, :].min(axis=0).tolist() for i, c in enumerate(hydromatrix.CLASSES)}
             print(name, "fewest per step, by direction:", table)
-            for c in hydromatrix.required_for(integrator, 2, pvac):
+            for c in hydromatrix.required_for(integrator, 2, pvac, nscal):
                 assert min(table[c]) >= hydromatrix.MIN_COUNT, (name, c, table[c])
         return
     if ndir == 2:
         return
     cfg = str(g["cfg"])
-    cnt, _ = hydromatrix.census(cfg, nx)
+    cnt, _ = hydromatrix.census(cfg, nx, nscal=nscal)
     table = {c: cnt[:, i, :].min(axis=0).tolist() for i, c in enumerate(hydromatrix.CLASSES)}
     print(name, "fewest per step, by direction:", table)
-    for c in hydromatrix.required(cfg):
+    for c in hydromatrix.required(cfg, nscal):
         assert min(table[c]) >= hydromatrix.MIN_COUNT, (name, c, table[c])
 
 

@@ -99,25 +99,26 @@ def ion_matrix(tceil=None):
 
 
 @functools.lru_cache(maxsize=None)
-def hydro_matrix(cfg, nx=None):
+def hydro_matrix(cfg, nx=None, nscal=0):
     """-> (largest spread, largest number of zones beyond 1e-9, zones of the Grid) over the twins of the 3 steps of the designed hydro
-    state (tests/hydromatrix.py) in configuration `cfg` on the Grid `nx`.  nx = None: the larger of either figure over the two 3-D
+    state (tests/hydromatrix.py) in configuration `cfg` on the Grid `nx`; with nscal = 1 the six-variable run, all six fields twinned
+    and the figures taken over six columns.  nx = None: the larger of either figure over the two 3-D
     Grids, the number of zones as a share of the Grid (-> (spread, share)) -- what the 2-D and the nested runs, which the oracle cannot
     twin, are held to.  On this state a 1-ulp change moves Roe -> HLLE and upwind decisions by design, so the spread is what any
     arithmetic that differs from the reference's in the last bit (fused multiply-adds) can be held to."""
     import hydromatrix
     if nx is None:
-        figs = [hydro_matrix(cfg, s) for s in hydromatrix.SHAPES_3D]
+        figs = [hydro_matrix(cfg, s, nscal) for s in hydromatrix.SHAPES_3D]
         return max(f[0] for f in figs), max(f[1] / f[2] for f in figs)
 
     def advance(seed):
-        s = hydromatrix.make_sim(cfg, nx)
+        s = hydromatrix.make_sim(cfg, nx, nscal)
         if seed:
-            perturb(s.active[..., :5], seed)
+            perturb(s.active[..., :5 + nscal], seed)
         s.start()
         for _ in range(hydromatrix.NSTEP):
             s.step()
-        return s.active[..., :5].copy()
+        return s.active[..., :5 + nscal].copy()
 
     base = advance(0)
     worst, nflip = 0.0, 0
