@@ -206,7 +206,7 @@ void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevS
 void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
 }
 
-// run.hip: the frame the run calls share -- aa_run_1d / aa_run_2d for a Grid, aa_mesh_run_2d (smr.hip) for a Mesh of 2-D Grids: the
+// run.hip: the frame the run calls share -- aa_run_1d / aa_run_2d / aa_run_3d for a Grid, aa_mesh_run_2d / aa_mesh_run_3d (smr.hip) for a Mesh: the
 // refusals of span and tlim, the loop over single steps (stepwise), else begin -> { batch, synchronise `st`, read the clock } while it
 // is live -> the host's time / dt / nstep from the clock -> end.
 struct RunOps {
@@ -225,6 +225,13 @@ int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *
 // run.hip: the integrator's chain of a 2-D Grid on the device clock `rc`, on g->st (a level of a Mesh: the flux-keeping update kernel;
 // sc == nullptr: without new_dt's maxima)
 void queue_chain_2d(aa_grid *g, const aa::Run2D *rc, aa::DevScalars *sc);
+// run.hip: whether a 3-D Grid's step is the chain whose kernels have entries on the device clock (everything aa_run_3d asks before it
+// queues, but the batch): asked of a stand-alone Grid and of every level of a Mesh ...
+bool on_queued_chain_3d(const aa_grid *g);
+// ... that chain on the clock `rc`, on g->st (a level of a Mesh: the flux-keeping update kernel; sc == nullptr: without new_dt's maxima),
+// and the boundary pass behind it
+void queue_chain_3d(aa_grid *g, const aa::Run3D *rc, aa::DevScalars *sc);
+void queue_bvals_3d(aa_grid *g);
 
 // new state from outside (an upload, a restart section): the next ion step's speculating entry is the dense one
 static inline void ion_lean_forget(aa_grid *g) { g->ion_lean_next = false; for (aa_grid *c : g->slab) c->ion_lean_next = false; }

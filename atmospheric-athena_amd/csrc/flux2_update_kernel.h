@@ -1,21 +1,32 @@
 // flux2_update_kernel.h -- k_flux2_update of hydro_kernels.hip (which says in front of k_sweep_march's #include lines why the kernel
-// lives here).  No include guard: compiled twice --
+// lives here).  No include guard: compiled three times --
 //   as it stands          k_flux2_update(g, dhalf, dt, kchunk, kp, sc, pinmask, sr): dt and the StepRatios are kernel arguments
-//   AA_CLOCK_ENTRY        k_flux2_update_dc(g, dhalf, rc, kchunk, sc): one uniform load of `live` and dt from the device clock
+//   AA_CLOCK_ENTRY 1      k_flux2_update_dc(g, dhalf, rc, kchunk, sc): one uniform load of `live` and dt from the device clock
 //                         (hydro3d_launch.h Run3D) at the top, then the ratios by uniform loads; a step queued behind the stop
 //                         returns there, before any store and before any barrier (the whole grid takes the same branch).  A
-//                         queued step keeps no flux planes and has no pinned zones (aa_run_3d refuses a level of a Mesh and a
-//                         Grid with pinned zones): instantiated with KEEP = false, CFL = true only.
-// Below the opening brace the two are one text.
+//                         step queued by aa_run_3d keeps no flux planes and has no pinned zones (it refuses a level of a Mesh and
+//                         a Grid with pinned zones): instantiated with KEEP = false, CFL = true only.
+//   AA_CLOCK_ENTRY 2      k_flux2_update_keep_dc(g, dhalf, rc, kchunk, sc, kp): the same entry for a level of a Mesh
+//                         (aa_mesh_run_3d, smr.hip mesh_queue_step_3d) -- the KeepPlanes a kernel argument beside the clock, as in
+//                         the by-value entry.  An entry of its own, so that the kernel arguments and with them the device code of
+//                         k_flux2_update_dc stay what they were.  Instantiated with KEEP = true; CFL = true for a Grid without
+//                         children, CFL = false for one whose new_dt maxima k_cfl takes behind RestrictCorrect.
+// Below the opening brace the three are one text.
 template <int NS, bool GRAV, bool KEEP, bool CFL>
 __global__ void __launch_bounds__(64*FU_TJ)
 #ifdef AA_CLOCK_ENTRY
+#if AA_CLOCK_ENTRY == 2
+k_flux2_update_keep_dc(DevGrid g, const Real *dhalf, const Run3D *rc, int kchunk, DevScalars *sc, KeepPlanes kp)
+{
+  if (!rc->c.live) return;
+#else
 k_flux2_update_dc(DevGrid g, const Real *dhalf, const Run3D *rc, int kchunk, DevScalars *sc)
 {
   if (!rc->c.live) return;
+  const KeepPlanes kp = {0, {{0}}};
+#endif
   const Real dt = rc->c.dt;
   const StepRatios sr = clock_ratios(rc);
-  const KeepPlanes kp = {0, {{0}}};
   const unsigned char *const pinmask = nullptr;
 #else
 k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp, DevScalars *sc, const unsigned char *pinmask, StepRatios sr)

@@ -1054,6 +1054,9 @@ AA_DEV bool on_plane(const KeepPlanes &kp, int d, int x)
 #define AA_CLOCK_ENTRY 1
 #include "flux2_update_kernel.h"      // (k_flux2_update_dc: instantiated without kept planes, with new_dt's maxima)
 #undef AA_CLOCK_ENTRY
+#define AA_CLOCK_ENTRY 2
+#include "flux2_update_kernel.h"      // (k_flux2_update_keep_dc: a level of a Mesh -- kept planes, with or without the maxima)
+#undef AA_CLOCK_ENTRY
 #endif
 
 // the zones Userwork has just overwritten (k_pinned) join the maxima k_flux2_update<CFL> left them out of
@@ -1933,16 +1936,29 @@ void launch_pinned_cfl(const DevGrid &g, long long n, const long long *idx, DevS
 void launch_pin_mask(const DevGrid &g, long long n, const long long *idx, unsigned char *mask, hipStream_t st)
 { if (n > 0) hipLaunchKernelGGL(k_pin_mask, dim3(nblk(n, 256)), dim3(256), 0, st, g, n, idx, mask); }
 // fused second-pass fluxes + update (CTU); `keep`: the face planes whose fluxes are stored as well; sc: and new_dt's maxima
+// The instances of k_flux2_update_keep_dc this build has: one that needs scratch is not built (flux2_update_keep_dc_built; the
+// figures are in profiles/mesh_run3d_kernel_budget.md), and a Mesh with such a level steps one aa_mesh_step at a time.
+#define AA_FLUX2_KEEP_DC_BUILT(NS, GRAV) true
 static void flux2_update_impl(const HostGrid &g, int nscal, Real dt, bool grav, const KeepPlanes *keep, hipStream_t st, DevScalars *sc, const unsigned char *pinmask,
                               const Run3D *rc)
 {
-  // (rc: a queued step -- the same launch, dt and the ratios from the device clock; no kept planes, no pinned zones, always sc)
+  // (rc: a queued step -- the same launch, dt and the ratios from the device clock; no pinned zones.  A stand-alone Grid: no kept
+  //  planes, always sc; a level of a Mesh: `keep`, sc only where the Grid has no child)
   const int ni = g.ie - g.is + 1, nj = g.je - g.js + 1, nk = g.ke - g.ks + 1;
   const int kc_env = g.cfg.fu_kc;
   int kc = kc_env > 0 ? kc_env : 32;
   if (kc_env <= 0) while (kc > 4 && (long)nblk(ni, 64)*nblk(nj, FU_TJ - 1)*((nk + kc - 1)/kc) < 1024) kc >>= 1;
   dim3 grid(nblk(ni, 64), nblk(nj, FU_TJ - 1), (nk + kc - 1)/kc), blk(64, FU_TJ);
 #if !AA_COOLING
+  if (rc && keep) {
+    const KeepPlanes kpd = *keep;
+    with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { with_flag(sc != nullptr, [&](auto CFL) {
+      // (a combination flux2_update_keep_dc_built() names is not instantiated: aa_mesh_run_3d steps such a Mesh one aa_mesh_step at a time)
+      if constexpr (AA_FLUX2_KEEP_DC_BUILT(NS, GRAV))
+        hipLaunchKernelGGL((k_flux2_update_keep_dc<NS, GRAV, true, CFL>), grid, blk, 0, st, g, g.dhalf, rc, kc, sc, kpd);
+      else abort(); }); });
+    return;
+  }
   if (rc) { with_ns_grav(nscal, grav, [&](auto NS, auto GRAV) { hipLaunchKernelGGL((k_flux2_update_dc<NS, GRAV, false, true>), grid, blk, 0, st, g, g.dhalf, rc, kc, sc); }); return; }
 #endif
   const bool keeps = keep && keep->n;
@@ -1955,6 +1971,10 @@ void launch_flux2_update(const HostGrid &g, int nscal, Real dt, bool grav, const
 #if !AA_COOLING
 void launch_flux2_update_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, DevScalars *sc, hipStream_t st)
 { flux2_update_impl(g, nscal, 0.0, grav, nullptr, st, sc, nullptr, rc); }
+// ... of a level of a Mesh: the second-pass fluxes on the planes of `kp` stay in F; sc == nullptr: without new_dt's maxima
+bool flux2_update_keep_dc_built(int nscal, bool grav) { return nscal ? (grav ? AA_FLUX2_KEEP_DC_BUILT(1, true) : AA_FLUX2_KEEP_DC_BUILT(1, false)) : (grav ? AA_FLUX2_KEEP_DC_BUILT(0, true) : AA_FLUX2_KEEP_DC_BUILT(0, false)); }
+void launch_flux2_update_keep_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
+{ flux2_update_impl(g, nscal, 0.0, grav, &kp, st, sc, nullptr, rc); }
 #endif
 
 long update_blocks(const DevGrid &g)

@@ -3,7 +3,7 @@
 // Grid as AA_2D_BATCH queued steps per read of the clock (hydro2d_kernels.hip k2d_advance), a 3-D hydro Grid on the default CTU chain
 // as AA_3D_BATCH queued steps (hydro_kernels.hip k3d_advance; what that chain does not cover loops over aa_step) -- or, with the
 // knob of any at 0, step by step.  One body behind the three names: the refusals, the fallback and the seed / synchronise / read-back
-// frame are written once (run_frame, which aa_mesh_run_2d of smr.hip shares for the Grids of a 2-D Mesh on one clock).
+// frame are written once (run_frame, which aa_mesh_run_2d and aa_mesh_run_3d of smr.hip share for the Grids of a Mesh on one clock).
 // The rule of the step and the loop condition are those of time_step.h, on the host and in the two kernels.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -71,27 +71,46 @@ static void queue_step_2d(aa_grid *g)
 // (AA_CORRECT_ALL off), AA_X3_FUSED=0, AA_FUSED_UPDATE=0, AA_CFL_FUSED=0, AA_EDGE_OVERLAP=1 (a second stream), first-pass sweeps
 // already done by aa_integrate_begin, a direction with fewer zones than ghost zones (queue_step_3d says why), and in the strict
 // build a passive scalar together with a static potential (correct_all_dc_built: that k_correct_all needs scratch there).
-static bool queues_3d(const aa_grid *g)
+// The part of that which is the Grid's own -- asked of a stand-alone Grid here and of every level of a Mesh by aa_mesh_run_3d
+// (smr.hip), which adds what a level needs on top: the flux-keeping update entry (flux2_update_keep_dc_built).  (p.ion keeps a
+// level off the queue as it does a Grid: with a plane on the root, the radiation step of aa_mesh_step comes first.)
+bool on_queued_chain_3d(const aa_grid *g)
 {
   const LaunchCfg &c = g->d.cfg;
   const bool x3_fused = c.x3_fused_mode >= 0 ? c.x3_fused_mode != 0 : true;      // (api.hip x3_fused)
-  return !g->one_d && !g->two_d && g->slab.empty() && g->batch_3d > 0 && (g->p.integrator == 0 || g->p.integrator == 2) && !g->fofc &&
+  return !g->one_d && !g->two_d && g->slab.empty() && (g->p.integrator == 0 || g->p.integrator == 2) && !g->fofc &&
          !g->cool && !g->p.ion && c.correct_all && x3_fused && c.fused_update && c.cfl_step && !c.edge_overlap && !g->inner_swept &&
          g->d.Nx1 >= AA_NGHOST && g->d.Nx2 >= AA_NGHOST && g->d.Nx3 >= AA_NGHOST && correct_all_dc_built(g->p.nscal, g->grav);
 }
+static bool queues_3d(const aa_grid *g) { return g->batch_3d > 0 && on_queued_chain_3d(g); }
 
 // one step of the 3-D queue: aa_integrate_3d_ctu's default chain with dt and the StepRatios from the clock, bvals_mhd, k3d_advance
 // (main.c:572-644 without Userwork_in_loop: a Grid with pinned zones is refused).  The stage names are those of
 // aa_integrate_3d_ctu / aa_bvals_mhd.  Plain launches in stream order; nothing is captured, nothing launched cooperatively, no kernel
 // waits on memory or on another workgroup; the host reads the clock only behind run_frame's hipStreamSynchronize.
-static void queue_step_3d(aa_grid *g)
+// (the chain and the boundary pass are queue_chain_3d / queue_bvals_3d, which the levels of a Mesh share: smr.hip mesh_queue_step_3d)
+void queue_chain_3d(aa_grid *g, const Run3D *rc, DevScalars *sc)
 {
-  const HostGrid &d = g->d; const int ns = g->p.nscal; const Run3D *rc = g->run3d_dev;
+  const HostGrid &d = g->d; const int ns = g->p.nscal;
   if (d.slope) { Scope s(g, "ppm_slopes"); for (int dir = 0; dir < 3; dir++) launch_slopes(d, ns, dir, g->st, nullptr); }
   { Scope s(g, "sweep_x2"); launch_sweep_x2_dc(d, ns, rc, g->grav, g->st); }
   { Scope s(g, "correct_all"); launch_correct_all_dc(d, ns, rc, g->grav, g->st); }
   if (g->p.integrator == 2) { Scope s(g, "no_h_correction"); (void)hipMemsetAsync(d.eta, 0, (size_t)3*d.nc*sizeof(Real), g->st); }
-  { Scope s(g, "flux2_update"); launch_flux2_update_dc(d, ns, rc, g->grav, g->sc, g->st); }
+  { Scope s(g, "flux2_update");
+    if (g->keep_flux) launch_flux2_update_keep_dc(d, ns, rc, g->grav, sc, g->keep, g->st);      // a level of a Mesh; sc == nullptr: without new_dt's maxima
+    else launch_flux2_update_dc(d, ns, rc, g->grav, sc, g->st); }
+}
+void queue_bvals_3d(aa_grid *g)
+{
+  const HostGrid &d = g->d; const int ns = g->p.nscal;
+  Scope s(g, "bvals_mhd");
+  if (d.cfg.bc_one) launch_bc_shell(d, ns, g->p.bc, g->st);
+  else for (int a = 0; a < 3; a++) launch_bc_dir(d, ns, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st);
+}
+static void queue_step_3d(aa_grid *g)
+{
+  const HostGrid &d = g->d;
+  queue_chain_3d(g, g->run3d_dev, g->sc);
   // What takes no dt is not predicated: k_slopes* (slope arrays), k_eta_edges and the eta memset (eta arrays) write scratch of the
   // step that the next taken step fills again before it reads it, and behind the stop there is no such step in this call.  The
   // boundary kernels write U.  k_bc_shell gives every ghost zone the value of ONE source zone, found by mapping its ghost
@@ -99,9 +118,7 @@ static void queue_step_3d(aa_grid *g)
   // in every direction that source is an ACTIVE zone, never itself a target.  Behind a stopped step the active zones are untouched,
   // so the kernel writes again what the last taken step's boundary pass wrote: idempotent, in either form (AA_BC_ONE).  A Grid
   // with fewer zones along a direction has ghost zones among its sources and steps one at a time (queues_3d).
-  { Scope s(g, "bvals_mhd");
-    if (d.cfg.bc_one) launch_bc_shell(d, ns, g->p.bc, g->st);
-    else for (int a = 0; a < 3; a++) launch_bc_dir(d, ns, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
+  queue_bvals_3d(g);
   { Scope s(g, "run3d_advance"); launch_3d_advance(d, g->run3d_dev, g->sc, g->clock_dev, g->st); }
 }
 
@@ -148,7 +165,7 @@ static int grid_begin(void *self, const RunClock &seed, double t_stop, double tl
   g->cfl_ready = false; g->active_dirty = true;
   if (g->one_d) *g->clock = seed;
   else if (!g->two_d) {
-    Run3D v = {seed, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, t_stop, tlim, g->p.cour_no, nstep_stop, 0};      // (k3d_seed forms the ratios)
+    Run3D v = {seed, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, t_stop, tlim, g->p.cour_no, nstep_stop, 0};      // (k3d_seed forms the ratios; `stepped` is a Mesh's)
     launch_3d_seed(g->d, g->run3d_dev, v, g->sc, g->st);
   } else {
     const Run2D v = {seed, t_stop, tlim, g->p.cour_no, nstep_stop, 0};

@@ -47,80 +47,17 @@ struct Link {                 // level l+1 seen from level l (init_grid.c: CGrid
 
 __device__ __forceinline__ Real *fld(const DevGrid &g, Real *base, int v) { return base + (long)v*g.nc; }
 
-// ---- restriction: 2x2x2 fine zones -> one parent zone, summed as smr.c:1391-1458 -------------
-// varmask bit v = restrict variable v (RestrictCorrect: all; ionradRestrictCorrect: E and s0)
-__global__ void __launch_bounds__(256)
-k_restrict(DevGrid f, DevGrid c, Link L, unsigned varmask)
-{
-  const long n = (long)L.n[0]*L.n[1]*L.n[2];
-  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
-  if (lin >= n) return;
-  const int a = (int)(lin % L.n[0]), b = (int)((lin / L.n[0]) % L.n[1]), cc = (int)(lin / ((long)L.n[0]*L.n[1]));
-  const long mc = (long)(L.cs[2] + cc)*c.sK + (long)(L.cs[1] + b)*c.sJ + (L.cs[0] + a);
-  const long mf = (long)(f.ks + 2*cc)*f.sK + (long)(f.js + 2*b)*f.sJ + (f.is + 2*a);
-  for (int v = 0; v < 6; v++) {
-    if (!(varmask >> v & 1u)) continue;
-    const Real *q = fld(f, f.U, v) + mf;
-    Real s = q[0] + q[1];
-    s += q[f.sJ] + q[f.sJ + 1];
-    s += q[f.sK] + q[f.sK + 1] + q[f.sK + f.sJ] + q[f.sK + f.sJ + 1];
-    s *= 0.125;
-    fld(c, c.U, v)[mc] = s;
-  }
-}
-
-// ---- flux correction (smr.c:1277-1340) on the parent zones just outside the child, one side per
-// launch; the child's flux through a parent face is the average of its 2x2 faces (:1464-1640) ----
-__global__ void __launch_bounds__(256)
-k_flux_correct(DevGrid f, DevGrid c, Link L, int dim_arg, int nvar, Real dt)
-{
-  // dim_arg < 0: all sides in one launch, side = blockIdx.y (the sides correct disjoint parent zones: the zone outside each face)
-  const int dim = (dim_arg >= 0) ? dim_arg : (int)blockIdx.y;
-  if (dim_arg < 0 && !L.corr[dim]) return;
-  const int d = dim >> 1, d1 = (d == 0) ? 1 : 0, d2 = (d == 2) ? 1 : 2;      // fast, slow transverse
-  const long n = (long)L.n[d1]*L.n[d2];
-  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
-  if (lin >= n) return;
-  const int a = (int)(lin % L.n[d1]), b = (int)(lin / L.n[d1]);
-  const long sc[3] = {1, c.sJ, c.sK}, sf[3] = {1, f.sJ, f.sK};
-  const int flo[3] = {f.is, f.js, f.ks}, fhi[3] = {f.ie, f.je, f.ke};
-  int ic[3]; ic[d1] = L.cs[d1] + a; ic[d2] = L.cs[d2] + b;
-  Real q;
-  long mface_c, mcell, mface_f;
-  if (dim & 1) { ic[d] = L.ce[d] + 1; q =  (dt/c.dx[d]); }
-  else         { ic[d] = L.cs[d] - 1; q = -(dt/c.dx[d]); }
-  mcell = ic[2]*sc[2] + ic[1]*sc[1] + ic[0];
-  ic[d] = (dim & 1) ? L.ce[d] + 1 : L.cs[d];
-  mface_c = ic[2]*sc[2] + ic[1]*sc[1] + ic[0];
-  {
-    int jf[3]; jf[d1] = flo[d1] + 2*a; jf[d2] = flo[d2] + 2*b; jf[d] = (dim & 1) ? fhi[d] + 1 : flo[d];
-    mface_f = jf[2]*sf[2] + jf[1]*sf[1] + jf[0];
-  }
-  for (int v = 0; v < nvar; v++) {
-    const Real mine = fld(c, c.F, d*6 + v)[mface_c];
-    const Real *qf = fld(f, f.F, d*6 + v) + mface_f;
-    Real fine = qf[0] + qf[sf[d1]];
-    fine += qf[sf[d2]] + qf[sf[d2] + sf[d1]];
-    fine *= 0.25;
-    fld(c, c.U, v)[mcell] -= q*(mine - fine);
-  }
-}
+// ---- restriction, flux correction and the snapshot for the prolongation: smr_coupling_kernels.h, compiled twice -- as it stands
+// (k_restrict, k_flux_correct, k_box_copy: dt a kernel argument) and with AA_CLOCK_ENTRY (k_restrict_dc, k_flux_correct_dc,
+// k_box_copy_dc: the entries of a step queued by aa_mesh_run_3d, which read the device clock at the top).  One text, two entries:
+// a body shared through an inlined function moved the by-value kernels' code (k_flux_correct's index tables went to LDS).
+#include "smr_coupling_kernels.h"
+#define AA_CLOCK_ENTRY 1
+#include "smr_coupling_kernels.h"
+#undef AA_CLOCK_ENTRY
 
 // ---- prolongation ----------------------------------------------------------------------------
-// snapshot of the parent zones cs-3 .. ce+3 around the child, taken when the parent "sends"
-// (smr.c:2397-2470: before the parent's own ghost zones are refreshed in the same call)
-__global__ void __launch_bounds__(256)
-k_box_copy(DevGrid c, Link L, Real *box)
-{
-  const int b0 = L.n[0] + 6, b1 = L.n[1] + 6, b2 = L.n[2] + 6;
-  const long nb = (long)b0*b1*b2;
-  const long lin = (long)blockIdx.x*blockDim.x + threadIdx.x;
-  if (lin >= nb) return;
-  const int i = (int)(lin % b0), j = (int)((lin / b0) % b1), k = (int)(lin / ((long)b0*b1));
-  const long m = (long)(L.cs[2] - 3 + k)*c.sK + (long)(L.cs[1] - 3 + j)*c.sJ + (L.cs[0] - 3 + i);
-  for (int v = 0; v < 6; v++) box[(long)v*nb + lin] = fld(c, c.U, v)[m];
-}
-
+// (the snapshot of the parent zones around the child, k_box_copy, is in smr_coupling_kernels.h)
 __device__ __forceinline__ Real mcd_slope(const Real vl, const Real vc, const Real vr)   // smr.c:3478
 {
   const Real dvl = (vc - vl), dvr = (vr - vc);
@@ -478,6 +415,12 @@ struct aa_mesh {
   int batch_2d = 0;
   Run2D *run2d_dev = nullptr; RunClock *clock = nullptr, *clock_dev = nullptr;
   MeshClockTab tab;
+  // aa_mesh_run_3d (a Mesh of 3-D Grids): AA_3D_BATCH when the Mesh was made (0: it loops over aa_mesh_step), ONE device array with a
+  // Run3D per Grid (hydro3d_launch.h MeshClockTab3 says why one each), and the Grids as k3d_mesh_advance sees them; `clock` and
+  // `clock_dev` above are the mirror of either call (a Mesh is 2-D or 3-D)
+  int batch_3d = 0;
+  Run3D *run3d_dev = nullptr;
+  MeshClockTab3 tab3;
 };
 
 extern "C" {
@@ -510,6 +453,11 @@ static int mesh_finish(aa_mesh *m, aa_grid **levels, aa_mesh **out, bool may_ove
     const char *ev = getenv("AA_2D_BATCH");
     m->batch_2d = ev ? atoi(ev) : AA_2D_MESH_BATCH_DEFAULT;
     if (m->batch_2d < 0 || m->batch_2d > 1024) { const int v = m->batch_2d; aa_mesh_destroy(m); return aa_fail(-1, "[aa_mesh_create_2d]: AA_2D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
+  }
+  if (!m->two_d) {     // AA_3D_BATCH likewise (a rank's stack of slabs and a cut Mesh never queue: aa_mesh_run_3d refuses them)
+    const char *ev = getenv("AA_3D_BATCH");
+    m->batch_3d = ev ? atoi(ev) : AA_3D_MESH_BATCH_DEFAULT;
+    if (m->batch_3d < 0 || m->batch_3d > 1024) { const int v = m->batch_3d; aa_mesh_destroy(m); return aa_fail(-1, "[aa_mesh_create]: AA_3D_BATCH=%d: must be 0 (step by step) or 1..1024", v); }
   }
   if (m->overlap && m->nl > 1) {
     e = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming);
@@ -722,6 +670,7 @@ void aa_mesh_destroy(aa_mesh *m)      // the levels stay alive and go back to th
   if (m->ev_fork) hipEventDestroy(m->ev_fork);
   if (m->own_stream) hipStreamDestroy(m->st);
   if (m->run2d_dev) hipFree(m->run2d_dev);
+  if (m->run3d_dev) hipFree(m->run3d_dev);
   if (m->clock) hipHostFree(m->clock);
   delete m;
 }
@@ -1165,6 +1114,174 @@ int aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *
   // along a direction (mesh_queue_step_2d: a boundary kernel reads ghost zones there)
   o.stepwise = m->batch_2d == 0 || m->nl > AA_2D_MESH_GRIDS || small;
   o.step = mesh_run_step; o.begin = mesh_run_begin; o.batch = mesh_run_batch; o.end = mesh_run_end; o.st = m->st;
+  o.host_syncs = &m->lev[0]->host_syncs;
+  return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
+}
+
+// ---- aa_mesh_run_3d: the same for a Mesh of 3-D Grids whose levels are all on the default CTU chain (run.hip on_queued_chain_3d) ---
+static int mesh_run_buffers_3d(aa_mesh *m)
+{
+  if (m->clock) return 0;
+  RunClock *h = nullptr, *hd = nullptr; Run3D *d = nullptr;
+  if (hipHostMalloc(&h, sizeof(RunClock), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || hipMalloc(&d, (size_t)m->nl*sizeof(Run3D)) != hipSuccess) {
+    if (h) hipHostFree(h);
+    (void)hipGetLastError();
+    return aa_fail(-2, "[aa_mesh_run_3d]: clock buffers");
+  }
+  memset(h, 0, sizeof(RunClock));
+  m->clock = h; m->clock_dev = hd; m->run3d_dev = d;
+  m->tab3.n = m->nl; m->tab3.pad = 0;
+  for (int l = 0; l < AA_3D_MESH_GRIDS; l++) {
+    const bool in = l < m->nl;
+    m->tab3.sc[l] = in ? m->lev[l]->sc : nullptr;
+    for (int d3 = 0; d3 < 3; d3++) m->tab3.dx[3*l + d3] = in ? m->lev[l]->d.dx[d3] : 0.0;
+  }
+  return 0;
+}
+
+static bool mesh_has_child(const aa_mesh *m, int l)
+{
+  for (int c = 0; c + 1 < m->nl; c++) if (m->par[c] == l) return true;
+  return false;
+}
+
+// One queued step of a 3-D Mesh: mesh_queue_step_2d's schedule and invariants with the 3-D kernels.  Grid l reads dt, `live` and
+// the six ratios of ITS dx from the l-th Run3D of the Mesh's array (k3d_mesh_advance keeps time, dt, nstep, `live` and `stepped`
+// equal in all of them); the coupling kernels, which join two Grids, read the parent's.
+//  * the default CTU chain of every level (run.hip queue_chain_3d: the x2 march, k_correct_all with the other first passes on
+//    board, k_flux2_update_keep_dc -- the second-pass fluxes on the level's boundary planes and its children's outlines stay in F).
+//    new_dt's maxima ride on the update where the Grid has no child (CFL = true); a Grid WITH children runs the CFL = false
+//    instance -- restriction and flux correction rewrite it -- and k_cfl sweeps it behind the last RestrictCorrect pair.  cfl_zone
+//    is never contracted (hydro_kernels.hip), and MAX over the same doubles is order-free: dt is the bits of aa_mesh_new_dt.
+//    Behind a stop k_cfl only raises the Grid's own maxima, which the next call's seed (or aa_mesh_new_dt) zeroes.
+//  * k_restrict_dc / k_flux_correct_dc, finest pair first, behind the `live` guard.
+//  * k3d_mesh_advance: nstep++, time += dt, new_dt over the Grids, every Grid's next ratios, the stop rule, `stepped`.
+//  * bvals_mhd of every level, the snapshots around every child (k_box_copy_dc, behind `stepped`), the prolongation.
+// What is not predicated takes no dt, and behind a stop -- U's active zones untouched, F and the boxes untouched -- it writes what
+// is already there or scratch of the step:
+//      - k_slopes*, k_eta_edges, the eta memset: slope and eta arrays, which the next taken step fills before it reads them.
+//      - the boundary kernels (k_bc_shell, or k_bc in three passes x1, x2, x3).  Every level has AA_NGHOST or more zones along
+//        every direction (else: step by step).  A side is either a physical boundary (flag != 0) or fine/coarse (flag 0: the
+//        kernels leave it alone; six sides, any mixture).  A ghost zone they write lies outside the active range along one, two
+//        or three directions (faces, edges, corners); its source has the coordinates along the physical directions mapped into
+//        the active range and the others kept.  If the zone is ghost along physical directions only, the source is an ACTIVE
+//        zone, untouched behind the stop.  If it is also ghost along a fine/coarse direction, the source is a prolonged ghost
+//        zone -- and the zone itself lies in the region the prolongation of that side writes behind the boundary pass in the
+//        same step (k_prolong's region of a side spans the ghost zones of the other two directions), so the boundary kernel
+//        is not its last writer.  The three-pass form writes the same zones from the same sources pass by pass.
+//      - k_prolong is a function of the snapshot `box` alone, and the box is retaken only behind a step that was taken: a child
+//        whose outline lies two parent zones from the parent's own fine/coarse side has prolonged ghost zones of the PARENT in its
+//        snapshot, taken (smr.c Prolongate, Step 1) before the parent's prolongation of the same call refreshes them -- a
+//        snapshot retaken behind the stop would hold the fresh ones.  So the boxes stay, and k_prolong writes again what is there.
+//    A following aa_mesh_step, an output or a restart dump therefore sees the state the last step taken left.
+// Plain launches on the Mesh's ONE stream, in stream order; the fork of the levels onto side streams (aa_mesh_step,
+// AA_MESH_OVERLAP) is dropped as in 2-D.  Nothing is captured, nothing launched cooperatively, no kernel waits on memory or on
+// another workgroup; the host reads the clock only behind run_frame's hipStreamSynchronize.
+static int mesh_queue_step_3d(aa_mesh *m)
+{
+  Run3D *rcs = m->run3d_dev;
+  for (int l = 0; l < m->nl; l++) queue_chain_3d(m->lev[l], rcs + l, mesh_has_child(m, l) ? nullptr : m->lev[l]->sc);   // (on m->st: every level's stream)
+  for (int q = 0; q + 1 < m->nl; q++) {                              // RestrictCorrect, finest pair first
+    const int l = m->f2c[q];
+    aa_grid *P = m->lev[m->par[l]], *C = m->lev[l + 1];
+    const Link &L = m->link[l];
+    const Run3D *rc = rcs + m->par[l];
+    const int nvar = 5 + P->p.nscal;
+    Scope s(P, "smr_restrict_correct");
+    hipLaunchKernelGGL(k_restrict_dc, dim3(nblk((long)L.n[0]*L.n[1]*L.n[2], 256)), dim3(256), 0, m->st, C->d, P->d, L, (1u << nvar) - 1u, rc);
+    if (m->one_launch) {
+      long nmax = 0;
+      for (int dim = 0; dim < 6; dim++) {
+        const int d = dim >> 1, d1 = (d == 0) ? 1 : 0, d2 = (d == 2) ? 1 : 2;
+        if (L.corr[dim]) { const long n = (long)L.n[d1]*L.n[d2]; if (n > nmax) nmax = n; }
+      }
+      if (nmax > 0) hipLaunchKernelGGL(k_flux_correct_dc, dim3(nblk(nmax, 256), 6), dim3(256), 0, m->st, C->d, P->d, L, -1, nvar, rc);
+    } else
+    for (int dim = 0; dim < 6; dim++) {
+      if (!L.corr[dim]) continue;
+      const int d = dim >> 1, d1 = (d == 0) ? 1 : 0, d2 = (d == 2) ? 1 : 2;
+      hipLaunchKernelGGL(k_flux_correct_dc, dim3(nblk((long)L.n[d1]*L.n[d2], 256)), dim3(256), 0, m->st, C->d, P->d, L, dim, nvar, rc);
+    }
+  }
+  for (int l = 0; l < m->nl; l++)                                    // new_dt's maxima of the Grids with children
+    if (mesh_has_child(m, l)) { Scope s(m->lev[l], "new_dt"); launch_cfl(m->lev[l]->d, m->lev[l]->sc, m->st); }
+  { Scope s(m->lev[0], "smr_advance"); launch_3d_mesh_advance(rcs, m->tab3, m->clock_dev, m->st); }
+  for (int l = 0; l < m->nl; l++) queue_bvals_3d(m->lev[l]);
+  for (int l = 0; l < m->nl; l++) {                                  // Prolongate, in the order of aa_mesh_prolongate
+    for (int c = 0; c + 1 < m->nl; c++) {
+      if (m->par[c] != l) continue;
+      const Link &L = m->link[c];
+      const long nb = (long)(L.n[0] + 6)*(L.n[1] + 6)*(L.n[2] + 6);
+      hipLaunchKernelGGL(k_box_copy_dc, dim3(nblk(nb, 256)), dim3(256), 0, m->st, m->lev[l]->d, L, m->box[c], rcs + l);
+    }
+    if (l == 0) continue;
+    aa_grid *C = m->lev[l];
+    const Link &L = m->link[l - 1];
+    const int nvar = 5 + C->p.nscal;
+    Scope s(C, "smr_prolongate");
+    long cnt[6], nmax = 0;
+    for (int dim = 0; dim < 6; dim++) {
+      cnt[dim] = 0;
+      if (!L.prol[dim]) continue;
+      cnt[dim] = 1;
+      for (int d = 0; d < 3; d++) cnt[dim] *= (d == (dim >> 1)) ? NG/2 : (C->p.Nx[d] + 2*NG)/2;
+      if (cnt[dim] > nmax) nmax = cnt[dim];
+    }
+    if (m->one_launch) {
+      if (nmax > 0) hipLaunchKernelGGL(k_prolong, dim3(nblk(nmax, 128), 6), dim3(128), 0, m->st, C->d, L, m->box[l - 1], -1, nvar);
+    } else
+    for (int dim = 0; dim < 6; dim++)
+      if (cnt[dim] > 0) hipLaunchKernelGGL(k_prolong, dim3(nblk(cnt[dim], 128)), dim3(128), 0, m->st, C->d, L, m->box[l - 1], dim, nvar);
+  }
+  return 0;
+}
+
+static int mesh_run_begin_3d(void *self, const RunClock &seed, double t_stop, double tlim, int nstep_stop, RunClock **clock)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  if (int rc = mesh_run_buffers_3d(m)) return rc;
+  for (int l = 0; l < m->nl; l++) { m->lev[l]->cfl_ready = false; m->lev[l]->active_dirty = true; }
+  const Run3D v = {seed, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, t_stop, tlim, m->lev[0]->p.cour_no, nstep_stop, 0};      // (k3d_mesh_seed forms every Grid's ratios)
+  launch_3d_mesh_seed(m->run3d_dev, v, m->tab3, m->st);
+  *clock = m->clock;
+  return 0;
+}
+static int mesh_run_batch_3d(void *self, double, double, int)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  for (int k = 0; k < m->batch_3d; k++) { int rc = mesh_queue_step_3d(m); if (rc) return rc; }
+  return 0;
+}
+
+// whether aa_mesh_run_3d queues this Mesh's steps: the knob above 0, the table holds the Grids, and every level is on the chain
+// whose kernels have entries on the device clock, the flux-keeping update entry included
+static bool mesh_queues_3d(const aa_mesh *m)
+{
+  if (!m || m->two_d || m->cut || m->local || m->batch_3d == 0 || m->nl > AA_3D_MESH_GRIDS) return false;
+  for (int l = 0; l < m->nl; l++) {
+    const aa_grid *g = m->lev[l];
+    if (!on_queued_chain_3d(g) || !flux2_update_keep_dc_built(g->p.nscal, g->grav)) return false;
+  }
+  return true;
+}
+
+int aa_mesh_run_3d_batch(const aa_mesh *m) { return mesh_queues_3d(m) ? m->batch_3d : 0; }
+
+int aa_mesh_run_3d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
+{
+  if (!m) return aa_fail(-1, "[aa_mesh_run_3d]: null argument");
+  if (m->cut) return aa_fail(-1, "[aa_mesh_run_3d]: this Mesh is cut into slabs: its levels step together on their slabs' streams, aa_mesh_step");
+  if (m->local) return aa_fail(-1, "[aa_mesh_run_3d]: this Mesh is one rank's stack of slabs (aa_mesh_create_local): the ranks agree on dt between steps, aa_mesh_step");
+  if (m->two_d) return aa_fail(-1, "[aa_mesh_run_3d]: this is a Mesh of 2-D Grids (aa_mesh_create_2d): aa_mesh_run_2d");
+  for (int l = 0; l < m->nl; l++) {
+    const aa_grid *g = m->lev[l];
+    if (g->npin > 0) return aa_fail(-1, "[aa_mesh_run_3d]: grid %d (level %d) has pinned zones: such a Mesh steps one at a time, aa_mesh_step", l, g->level);
+  }
+  RunOps o;
+  o.who = "aa_mesh_run_3d"; o.owner = "root"; o.self = m; o.time = &m->time; o.dt = &m->dt; o.nstep = &m->nstep; o.tlim = m->lev[0]->p.tlim;
+  o.stepwise = !mesh_queues_3d(m);
+  o.step = mesh_run_step; o.begin = mesh_run_begin_3d; o.batch = mesh_run_batch_3d; o.end = mesh_run_end; o.st = m->st;
   o.host_syncs = &m->lev[0]->host_syncs;
   return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }

@@ -867,14 +867,17 @@ class MeshRun(_Runner):
 
     def may_batch(self) -> bool:
         """whether advance() may take several steps in one call (outputs.run asks on every pass): a Mesh of 2-D Grids whose steps
-        queue with one clock on the device for all levels (aa_mesh_run_2d; lib.Mesh.can_run_2d)"""
-        return hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d()
+        queue with one clock on the device for all levels (aa_mesh_run_2d; lib.Mesh.can_run_2d), or a one-process Mesh of 3-D Grids
+        whose levels are all on the queued hydro chain (aa_mesh_run_3d; lib.Mesh.can_run_3d)"""
+        return ((hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d())
+                or (hasattr(self.mesh, "can_run_3d") and self.mesh.can_run_3d()))
 
     def advance(self, t_stop: float, nstep_stop=None) -> int:
         """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit) as queued steps with one
-        read-back per batch (aa_mesh_run_2d); the same bits as that many step() calls.  -> the steps taken"""
+        read-back per batch (aa_mesh_run_2d / aa_mesh_run_3d); the same bits as that many step() calls.  -> the steps taken"""
         far = self.nstep + (1 << 20)              # (a call covers 2^20 steps at the most; the caller's loop goes on)
-        return self.mesh.run_2d(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
+        run = self.mesh.run_2d if hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d() else self.mesh.run_3d
+        return run(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
 
     def write_dump(self, out, outputs):
         if getattr(outputs, "overlap", False):    # every level's Grid with its own snapshot slots; a level without the route writes now

@@ -122,6 +122,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_mesh_prolongate": (I, [P]), "aa_mesh_new_dt": (I, [P]), "aa_mesh_ion_radtransfer": (I, [P, I, ip]),
         "aa_mesh_start": (I, [P]), "aa_mesh_step": (I, [P, ip]),
         "aa_mesh_run_2d": (I, [P, D, D, I, ip]), "aa_mesh_run_2d_batch": (I, [P]),
+        "aa_mesh_run_3d": (I, [P, D, D, I, ip]), "aa_mesh_run_3d_batch": (I, [P]),
         "aa_mesh_ionflux_prolong": (I, [P, I]), "aa_mesh_create_local": (I, [I, C.POINTER(P), ip, C.POINTER(P)]),
         "aa_flux_x3_export": (I, [P, I, P]), "aa_flux_x3_apply": (I, [P, I, I, I, I, I, P]), "aa_cfl_max_v": (I, [P, dp]),
         "aa_test_fluxes": (I, [I, D, I, dp, dp, dp, dp]),
@@ -1016,4 +1017,28 @@ class Mesh:
         tlim = self.lev[0].cfg.run.tlim if tlim is None else tlim
         stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
         self._chk(self.L.aa_mesh_run_2d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
+        return n.value
+
+    def run_3d_batch(self) -> int:
+        """steps run_3d queues per read-back on this Mesh (AA_3D_BATCH when the Mesh was made, else the Mesh's own default); 0: it
+        steps one at a time -- the knob at 0, or a level off the chain whose kernels read the device clock (van Leer, cooling, ion
+        radiation, the tile kernels of a small level, ...: include/athena_amd.h)"""
+        return int(self.L.aa_mesh_run_3d_batch(self._h))
+
+    def can_run_3d(self) -> bool:
+        """whether run_3d queues steps on this Mesh: every level 3-D, not cut into slabs, not a rank's stack (links), no level with
+        pinned zones -- the refusals of aa_mesh_run_3d -- and a batch above 0"""
+        return (all(g.ndim == 3 for g in self.lev) and self.cuts is None and self.links is None
+                and all(g.npin == 0 for g in self.lev) and self.run_3d_batch() > 0)
+
+    def run_3d(self, t_stop: float, tlim: float | None = None, nstep_stop: int | None = None) -> int:
+        """Whole passes of step()'s loop on a Mesh of 3-D Grids with the time step picked on the device for all levels
+        (aa_mesh_run_3d): AA_3D_BATCH steps are queued per read-back; until time >= t_stop, nstep == nstep_stop or dt <= 0; new_dt
+        clips at tlim (default: the deck's).  nstep_stop None: 2^20 steps ahead at the most.  Returns the steps taken; the same
+        bits as that many step() calls (a Mesh whose batch is 0 takes them one at a time inside the call).  AthenaError on a Mesh
+        of 2-D Grids, one cut into slabs or made from links, a level with pinned zones."""
+        n = C.c_int()
+        tlim = self.lev[0].cfg.run.tlim if tlim is None else tlim
+        stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
+        self._chk(self.L.aa_mesh_run_3d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
         return n.value

@@ -322,6 +322,21 @@ int  aa_mesh_step(aa_mesh *m, int *niter);        /* one pass of main.c:519-669;
  * zones along a direction.  aa_run_2d on a level of a Mesh stays an error.                                                        */
 int  aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 int  aa_mesh_run_2d_batch(const aa_mesh *m);      /* steps queued per read-back on this Mesh; 0: it steps one at a time */
+/* The 3-D twin, for a Mesh of 3-D Grids (aa_mesh_create) on one device: the semantics of aa_mesh_run_2d with AA_3D_BATCH steps
+ * (environment when the Mesh is made, 0 or 1..1024; the Mesh has a default of its own, csrc/hydro3d_launch.h) queued per read of
+ * the clock.  A queued step is aa_mesh_step's order on the Mesh's one stream: the default CTU chain of every level with dt and the
+ * ratios dt/dx of ITS zones from the device clock (every Grid has a clock record of its own in one device array; the update
+ * kernel keeps the second-pass fluxes of the level boundaries), restriction and flux correction finest pair first, new_dt's
+ * maxima, one wavefront that advances the clock over all levels (k3d_mesh_advance; csrc/time_step.h), bvals_mhd, prolongation.
+ * The same bits as that many aa_mesh_step calls.  An error, each message beginning [aa_mesh_run_3d]: a null Mesh, a Mesh of 2-D
+ * Grids, a Mesh made by aa_mesh_create_local or cut into slabs, a level with pinned zones, a tlim other than the root's,
+ * nstep_stop outside nstep .. nstep + 2^20.  The same call loops over aa_mesh_step, with the same results, when any level is off
+ * the chain aa_run_3d queues for a Grid: AA_3D_BATCH=0, the van Leer integrator, a cooling function, ion radiation, the tile kernels
+ * of a small level (AA_CORRECT_ALL off: the default below 4e5 zones), AA_X3_FUSED=0, AA_FUSED_UPDATE=0, AA_CFL_FUSED=0,
+ * AA_EDGE_OVERLAP=1, fewer than four zones along a direction, more Grids than the advance kernel's table holds (16), a kernel
+ * combination this build does not instantiate.  aa_run_3d on a level of a Mesh and aa_mesh_run_2d on a 3-D Mesh stay errors.      */
+int  aa_mesh_run_3d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+int  aa_mesh_run_3d_batch(const aa_mesh *m);      /* steps queued per read-back on this Mesh; 0: it steps one at a time */
 
 /* Multi-GPU SMR: every level is cut into x3 slabs at the SAME root planes, so that restriction, the
  * radiation hand-off and prolongation stay inside a rank.  aa_mesh_create_local builds one rank's stack

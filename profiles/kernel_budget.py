@@ -51,9 +51,12 @@ def read(path):
 
 def twin_of(name):
     """the by-value entry a *_dc entry shares its body with"""
-    m = re.match(r"(aa::)(k_sweep_march|k_x1_edge_flux|k_correct_all|k_flux2_update)_dc<(.*)>", name)
+    m = re.match(r"(aa::)(k_sweep_march|k_x1_edge_flux|k_correct_all|k_flux2_update)(?:_keep)?_dc<(.*)>", name)
     if m:
         return "%s%s<%s>" % m.group(1, 2, 3)
+    m = re.match(r"(\(anonymous namespace\)::)(k_restrict|k_flux_correct|k_box_copy)_dc$", name)      # smr_coupling_kernels.h
+    if m:
+        return m.group(1) + m.group(2)
     return None
 
 
