@@ -318,6 +318,7 @@ void aa_destroy(aa_grid *g)
   if (g->cfl_part) hipFree(g->cfl_part);
   if (g->fofc_list) hipFree(g->fofc_list);
   if (g->clock) { hipHostFree(g->clock); hipFree(g->run2d_dev); hipFree(g->run3d_dev); }      // (run.hip run_buffers; run2d_dev / run3d_dev: null on Grids of the other shapes)
+  hst_free_grid(g); hst_free_sched(g->hst);      // (run.hip: the buffers of an armed history schedule, if one was ever armed)
   if (g->d.phalf) hipFree(g->d.phalf);
   if (g->side) hipStreamDestroy(g->side);
   if (g->ev_fork) hipEventDestroy(g->ev_fork);

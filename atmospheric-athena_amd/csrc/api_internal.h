@@ -15,6 +15,18 @@ int aa_fail(int code, const char *fmt, ...);   // records the message aa_last_er
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
   return aa_fail(-2, "[athena_amd] HIP error %s at %s:%d: %s", #x, __FILE__, __LINE__, hipGetErrorString(e_)); } while (0)
 
+// A history schedule of a run call (run.hip: aa_run_hst_arm for a Grid, smr.hip: aa_mesh_run_hst_arm for a Mesh -- ONE for all its
+// Grids).  armed: for the next run call, which takes it over (active) and disarms it whatever it returns.  t_next: as armed, then
+// the schedule's behind the call.  sched: the device's copy (only k_hst_row writes it, behind k_hst_seed); mirror / mirror_dev:
+// the page-locked copy k_hst_row leaves for the host and its device address, read behind run_frame's synchronise like the clock;
+// cap: rows of every Grid's ring -- the steps of one batch; drained: rows of this call already taken from the rings.
+struct HstRun {
+  bool armed = false, active = false;
+  double t_next = 0, dt_out = 0; int nlim = -1;
+  HstSched *sched = nullptr, *mirror = nullptr, *mirror_dev = nullptr;
+  int cap = 0, drained = 0;
+};
+
 struct ProfEntry { std::string name; std::vector<hipEvent_t> ev; double total_ms = 0; long long launches = 0; };
 
 struct aa_grid {
@@ -56,6 +68,14 @@ struct aa_grid {
   RunClock *clock = nullptr, *clock_dev = nullptr;   // time, dt, nstep, live of aa_run_1d / aa_run_2d / aa_run_3d (time_step.h): pinned, device-visible host memory and its device address ...
   aa::Run2D *run2d_dev = nullptr;      //   ... and the 2-D call's clock in device memory (hydro2d_launch.h); made by the first run call that reaches the device (run.hip)
   aa::Run3D *run3d_dev = nullptr;      //   ... and the 3-D call's (hydro_launch.h), likewise
+  // history rows of a run call with a schedule armed (run.hip): this Grid's schedule (a level of a Mesh uses the Mesh's), the partial
+  // rows of k_history_dc in device memory of their own (1024 x 9 doubles: the face-state area is the queued steps'), the page-locked
+  // ring k_hst_row appends a batch's rows to with its device address, and the rows of the last armed call on the host, AA_HST_ROW
+  // doubles each (aa_run_hst_rows / aa_mesh_run_hst_rows).  Made by the first arming; a Grid that is never armed allocates none.
+  HstRun hst;
+  aa::Real *hst_part = nullptr;
+  double *hst_ring = nullptr, *hst_ring_dev = nullptr; int hst_ring_cap = 0;
+  std::vector<double> hst_rows;
   bool inner_swept = false;            // aa_integrate_begin has done the first-pass x1 / x2 sweeps of the planes ks .. ke
   double inner_dt = 0.0;               //   ... with this dt
   bool ion_fused = false;              // one-kernel radiation sub-cycle with the scan sweep (ion_pass.hip): aa_params.ion_path, else LaunchCfg ion_fused; a sweep along x2 turns it off
@@ -220,8 +240,29 @@ struct RunOps {
   int (*batch)(void *self, double t_stop, double tlim, int nstep_stop);   // the launches between two reads of the clock
   void (*end)(void *self);             // (may be null) the host's clock has been set
   hipStream_t st; int *host_syncs;
+  // a history schedule this call has taken over (null: none; then nothing below is called and the call does what it did without):
+  // stepwise, the frame applies hst_row_due on the host behind every step and hst_row takes every Grid's row from aa_history;
+  // queued, hst_begin seeds the device's schedule behind `begin`, the batch queues k_history_dc / k_hst_row behind every step
+  // (hst->active), and hst_drain takes the rows a batch left from the rings behind every synchronise
+  HstRun *hst = nullptr;
+  int (*hst_row)(void *self) = nullptr;
+  int (*hst_begin)(void *self, int nstep) = nullptr;
+  void (*hst_drain)(void *self) = nullptr;
 };
 int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
+// run.hip: the pieces of a history schedule a Grid and a Mesh share -- the buffers of one Grid (`cap` rows in its ring) and of a
+// schedule, made on first use and freed by hst_free_grid / hst_free_sched; a row of aa_history appended on the host; the rows of
+// rounds [h.drained, mirror->nrows) from a Grid's ring; and the two launches (run.hip k_hst_seed, k_hst_row)
+int hst_grid_buffers(aa_grid *g, int cap, const char *who);
+int hst_sched_buffers(HstRun &h, const char *who);
+void hst_free_grid(aa_grid *g);
+void hst_free_sched(HstRun &h);
+int hst_row_host(aa_grid *g, double time, double dt);
+void hst_drain_grid(aa_grid *g, const HstRun &h);
+void launch_hst_seed(HstRun &h, int nstep, hipStream_t st);
+// ... behind launch_history_dc's `nb` partial rows of `g`: the row, if one is due; commit: this launch also moves the schedule on
+// (the last of a Mesh's Grids; a stand-alone Grid's only one)
+void launch_hst_row(aa_grid *g, int nb, const RunClock *clock, double tlim, const HstRun &h, bool commit, hipStream_t st);
 // run.hip: the integrator's chain of a 2-D Grid on the device clock `rc`, on g->st (a level of a Mesh: the flux-keeping update kernel;
 // sc == nullptr: without new_dt's maxima)
 void queue_chain_2d(aa_grid *g, const aa::Run2D *rc, aa::DevScalars *sc);

@@ -46,6 +46,11 @@ void launch_flux2_update_dc(const HostGrid &g, int nscal, const Run3D *rc, bool 
 // `kp` stay in F; sc == nullptr: without new_dt's maxima (a Grid with children: k_cfl takes them behind RestrictCorrect)
 bool flux2_update_keep_dc_built(int nscal, bool grav);      // false: this build has no k_flux2_update_keep_dc for the combination (it would spill): aa_mesh_step
 void launch_flux2_update_keep_dc(const HostGrid &g, int nscal, const Run3D *rc, bool grav, DevScalars *sc, const KeepPlanes &kp, hipStream_t st);
+// history_dc.hip, for 2-D and 3-D Grids alike: launch_history behind a queued step of a run call with a history schedule armed
+// (k_history_dc: the body and the launch geometry of k_history; nothing is stored unless the step in front was taken and a row is
+// due -- time_step.h hst_row_due on `clock`, the RunClock at the head of the call's Run2D / Run3D, and `sched`).  Returns the
+// number of partial rows, the same as launch_history's.
+int launch_history_dc(const DevGrid &g, int nscal, Real *partial, const RunClock *clock, Real tlim, const HstSched *sched, hipStream_t st);
 // hydro3d_clock.hip: the clocks of a Mesh's Grids (rc[0 .. tab.n - 1]) for a call, the ratios of every Grid's own dx, the maxima zeroed ...
 void launch_3d_mesh_seed(Run3D *rc, const Run3D &v, const MeshClockTab3 &tab, hipStream_t st);
 // ... and main.c:618-629 over all Grids (time_step.h run_advance_levels, three directions), every Grid's next ratios, `stepped`; `out`: the host's mirror

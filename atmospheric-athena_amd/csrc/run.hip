@@ -5,6 +5,8 @@
 // knob of any at 0, step by step.  One body behind the three names: the refusals, the fallback and the seed / synchronise / read-back
 // frame are written once (run_frame, which aa_mesh_run_2d and aa_mesh_run_3d of smr.hip share for the Grids of a Mesh on one clock).
 // The rule of the step and the loop condition are those of time_step.h, on the host and in the two kernels.
+// aa_run_hst_arm / aa_run_hst_rows: the history rows of the next run call without a stop (k_hst_row here, k_history_dc of
+// history_dc.hip behind every queued step; aa_history behind every single step), by time_step.h hst_row_due in both forms.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "api_internal.h"
@@ -30,6 +32,121 @@ static int run_buffers(aa_grid *g, const char *who)
   return 0;
 }
 
+// ---- history rows behind queued steps (aa_run_hst_arm; time_step.h HstSched / hst_row_due) -----------------------------------------
+// the schedule of a call, and its mirror for the host
+__global__ void __launch_bounds__(64)
+k_hst_seed(HstSched *s, HstSched *mirror, HstSched v)
+{
+  if (threadIdx.x != 0) return;
+  *s = v; *mirror = v;
+}
+// One workgroup behind k_history_dc, with that kernel's predicate on the same clock and the same schedule: nothing to do behind a
+// step that was not taken.  Behind a taken step with a row due, lane q < 9 adds column q of the `nb` partial rows in block order
+// and multiplies by dVol -- the loop of aa_history on the host (api.hip), one addition after the other, nothing contracted -- and
+// the row {time, dt, sums[9]} goes to slot nrows % cap of the ring, time and dt being the clock's behind the advance kernel.  The
+// launch with `commit` (a Grid's only one; the last of a Mesh's Grids, the others leaving the schedule as they found it) then
+// writes the schedule -- it is its only writer behind the seed -- and the mirror: the next time, the row count, the step seen.
+// Launch rule as k1d_run states it: a plain launch in stream order; the barrier is reached by all 64 lanes (the early return is
+// uniform), nothing waits on memory or on another workgroup, no atomics.
+__global__ void __launch_bounds__(64)
+k_hst_row(const Real *partial, int nb, Real dVol, const RunClock *clock, Real tlim, HstSched *sched, HstSched *mirror,
+          Real *ring, int cap, int commit)
+{
+#pragma clang fp contract(off)
+  const RunClock c = *clock; HstSched s = *sched;
+  if (c.nstep == s.nstep_seen) return;
+  const int lane = threadIdx.x;
+  const int due = hst_row_due(c.time, c.nstep, tlim, s.nlim, s.dt_out, &s.t_next);
+  if (due) {
+    Real *row = ring + (long)(s.nrows % cap)*AA_HST_ROW;
+    if (lane < 9) {
+      Real sum = 0.0;
+      for (int b = 0; b < nb; b++) sum += partial[(long)b*9 + lane];
+      row[2 + lane] = dVol*sum;
+    } else if (lane == 9) row[0] = c.time;
+    else if (lane == 10) row[1] = c.dt;
+  }
+  __syncthreads();                                   // every lane has read the schedule
+  if (!commit || lane != 0) return;
+  s.nrows += due; s.nstep_seen = c.nstep;
+  *sched = s; *mirror = s;
+}
+
+int hst_grid_buffers(aa_grid *g, int cap, const char *who)
+{
+  if (cap < 1) cap = 1;
+  if (g->hst_ring && g->hst_ring_cap >= cap) return 0;
+  hst_free_grid(g);
+  double *h = nullptr, *hd = nullptr; Real *p = nullptr;
+  if (hipHostMalloc(&h, (size_t)cap*AA_HST_ROW*sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&hd, h, 0) != hipSuccess || hipMalloc(&p, (size_t)1024*9*sizeof(Real)) != hipSuccess) {
+    if (h) hipHostFree(h);
+    (void)hipGetLastError();
+    return aa_fail(-2, "[%s]: history row buffers", who);
+  }
+  g->hst_ring = h; g->hst_ring_dev = hd; g->hst_ring_cap = cap; g->hst_part = p;
+  return 0;
+}
+int hst_sched_buffers(HstRun &h, const char *who)
+{
+  if (h.sched) return 0;
+  HstSched *d = nullptr, *m = nullptr, *md = nullptr;
+  if (hipHostMalloc(&m, sizeof(HstSched), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&md, m, 0) != hipSuccess || hipMalloc(&d, sizeof(HstSched)) != hipSuccess) {
+    if (m) hipHostFree(m);
+    (void)hipGetLastError();
+    return aa_fail(-2, "[%s]: history schedule buffers", who);
+  }
+  memset(m, 0, sizeof(HstSched));
+  h.sched = d; h.mirror = m; h.mirror_dev = md;
+  return 0;
+}
+void hst_free_grid(aa_grid *g)
+{
+  if (g->hst_ring) hipHostFree(g->hst_ring);
+  if (g->hst_part) hipFree(g->hst_part);
+  g->hst_ring = g->hst_ring_dev = nullptr; g->hst_part = nullptr; g->hst_ring_cap = 0;
+}
+void hst_free_sched(HstRun &h)
+{
+  if (h.mirror) hipHostFree(h.mirror);
+  if (h.sched) hipFree(h.sched);
+  h.sched = h.mirror = h.mirror_dev = nullptr;
+}
+int hst_row_host(aa_grid *g, double time, double dt)
+{
+  double row[AA_HST_ROW] = {time, dt};
+  if (int rc = aa_history(g, row + 2)) return rc;
+  g->hst_rows.insert(g->hst_rows.end(), row, row + AA_HST_ROW);
+  return 0;
+}
+void hst_drain_grid(aa_grid *g, const HstRun &h)
+{
+  for (int r = h.drained; r < h.mirror->nrows; r++) {
+    const double *row = g->hst_ring + (size_t)(r % h.cap)*AA_HST_ROW;
+    g->hst_rows.insert(g->hst_rows.end(), row, row + AA_HST_ROW);
+  }
+}
+void launch_hst_seed(HstRun &h, int nstep, hipStream_t st)
+{
+  const HstSched v = {h.t_next, h.dt_out, h.nlim, 0, nstep, 0};
+  h.drained = 0;
+  hipLaunchKernelGGL(k_hst_seed, dim3(1), dim3(64), 0, st, h.sched, h.mirror_dev, v);
+}
+void launch_hst_row(aa_grid *g, int nb, const RunClock *clock, double tlim, const HstRun &h, bool commit, hipStream_t st)
+{
+  const double dVol = g->d.dx[0]*g->d.dx[1]*g->d.dx[2];      // (aa_history's expression)
+  hipLaunchKernelGGL(k_hst_row, dim3(1), dim3(64), 0, st, g->hst_part, nb, dVol, clock, tlim, h.sched, h.mirror_dev,
+                     g->hst_ring_dev, h.cap, commit ? 1 : 0);
+}
+// the two launches behind a queued step of a stand-alone Grid (clock: the RunClock at the head of its Run2D / Run3D)
+static void queue_hst(aa_grid *g, const RunClock *clock, double tlim)
+{
+  Scope s(g, "hst_row");
+  const int nb = launch_history_dc(g->d, g->p.nscal, g->hst_part, clock, tlim, g->hst.sched, g->st);
+  launch_hst_row(g, nb, clock, tlim, g->hst, true, g->st);
+}
+
 // The integrator's chain of a 2-D Grid on the clock `rc`, on g->st.  The stage names are those of aa_integrate_2d_*.  A stand-alone
 // Grid (aa_run_2d: its own clock, new_dt's maxima always on board) and a level of a Mesh (aa_mesh_run_2d in smr.hip: the Mesh's one
 // clock, the update kernel in its flux-keeping form, sc == nullptr where the level's maxima are taken later) share it.
@@ -52,7 +169,7 @@ void queue_chain_2d(aa_grid *g, const Run2D *rc, DevScalars *sc)
 
 // one step of the queue: the integrator's chain with new_dt's maxima on board, k2d_advance, bvals_mhd (main.c:572-644 without
 // Userwork_in_loop: a Grid with pinned zones is refused).  The stage names are those of aa_integrate_2d_* / aa_bvals_mhd.
-static void queue_step_2d(aa_grid *g)
+static void queue_step_2d(aa_grid *g, double tlim)
 {
   const HostGrid &d = g->d;
   queue_chain_2d(g, g->run2d_dev, g->sc);
@@ -62,6 +179,8 @@ static void queue_step_2d(aa_grid *g)
   // step -- U untouched -- they write again what is there: idempotent.  (Grids with fewer zones step one at a time, below.)
   { Scope s(g, "bvals_mhd");
     for (int a = 0; a < 2; a++) launch_bc_dir(d, g->p.nscal, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st); }
+  // (only while a history schedule is armed: with none a queued step launches what it always did)
+  if (g->hst.active) queue_hst(g, &g->run2d_dev->c, tlim);
 }
 
 // Whether aa_run_3d queues this Grid's steps: what aa_integrate_3d_ctu launches BY DEFAULT for one hydro Grid on one device -- the x2
@@ -107,7 +226,7 @@ void queue_bvals_3d(aa_grid *g)
   if (d.cfg.bc_one) launch_bc_shell(d, ns, g->p.bc, g->st);
   else for (int a = 0; a < 3; a++) launch_bc_dir(d, ns, a, g->p.bc[2*a], g->p.bc[2*a + 1], g->st);
 }
-static void queue_step_3d(aa_grid *g)
+static void queue_step_3d(aa_grid *g, double tlim)
 {
   const HostGrid &d = g->d;
   queue_chain_3d(g, g->run3d_dev, g->sc);
@@ -120,6 +239,7 @@ static void queue_step_3d(aa_grid *g)
   // with fewer zones along a direction has ghost zones among its sources and steps one at a time (queues_3d).
   queue_bvals_3d(g);
   { Scope s(g, "run3d_advance"); launch_3d_advance(d, g->run3d_dev, g->sc, g->clock_dev, g->st); }
+  if (g->hst.active) queue_hst(g, &g->run3d_dev->c, tlim);      // (as queue_step_2d)
 }
 
 // ---- the frame of every run call (api_internal.h RunOps): the span and tlim refusals, the loop over single steps, and the seed /
@@ -132,8 +252,13 @@ int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *
     return aa_fail(-1, "[%s]: nstep_stop=%d from nstep=%d: a call covers 0 .. 2^20 steps", who, nstep_stop, *o.nstep);
   if (tlim != o.tlim) return aa_fail(-1, "[%s]: tlim=%.17g, but the %s was created with %.17g (new_dt clips at that one)", who, tlim, o.owner, o.tlim);
   const int nstep0 = *o.nstep;
+  HstRun *h = o.hst;
   if (o.stepwise) {
-    while (run_live(*o.time, t_stop, *o.nstep, nstep_stop, *o.dt)) { int rc = o.step(o.self); if (rc) return rc; }
+    while (run_live(*o.time, t_stop, *o.nstep, nstep_stop, *o.dt)) {
+      int rc = o.step(o.self); if (rc) return rc;
+      // data_output's rule for the armed block behind the step, on the host: the same function the kernels of the queued form call
+      if (h && hst_row_due(*o.time, *o.nstep, tlim, h->nlim, h->dt_out, &h->t_next)) { rc = o.hst_row(o.self); if (rc) return rc; }
+    }
     if (nsteps_done) *nsteps_done = *o.nstep - nstep0;
     return 0;
   }
@@ -142,6 +267,7 @@ int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *
   RunClock *clock = nullptr;
   const RunClock seed = {*o.dt, 1, *o.nstep, *o.time};
   if (int rc = o.begin(o.self, seed, t_stop, tlim, nstep_stop, &clock)) return rc;
+  if (h) { if (int rc = o.hst_begin(o.self, seed.nstep)) return rc; }
   // Every launch ends whatever the data are, so the queue drains.  1-D: the one launch runs to the stop and leaves live = 0.  2-D: a
   // step behind the stop costs its launches and nothing else (up to AA_2D_BATCH - 1 of them per call); 3-D likewise (AA_3D_BATCH).
   do {
@@ -149,7 +275,10 @@ int run_frame(const RunOps &o, double t_stop, double tlim, int nstep_stop, int *
     HIPCHK(hipGetLastError());
     (*o.host_syncs)++;
     HIPCHK(hipStreamSynchronize(o.st));
+    // the rows this batch left (at most one per step) move to the host's memory: the rings never hold more than a batch
+    if (h) { o.hst_drain(o.self); h->drained = h->mirror->nrows; }
   } while (clock->live);
+  if (h) h->t_next = h->mirror->t_next;
   *o.time = clock->time; *o.dt = clock->dt; *o.nstep = clock->nstep;
   if (o.end) o.end(o.self);
   if (nsteps_done) *nsteps_done = *o.nstep - nstep0;
@@ -180,15 +309,24 @@ static int grid_batch(void *self, double t_stop, double tlim, int nstep_stop)
   if (g->one_d) {
     Scope s(g, g->p.integrator == 1 ? "vl1d_run" : "ctu1d_run");
     launch_1d_run(g->d, g->p.integrator == 1, g->p.order == 3, g->p.bc[0], g->p.bc[1], g->p.cour_no, t_stop, tlim, nstep_stop, g->clock_dev, g->st);
-  } else if (g->two_d) for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g);
-  else for (int k = 0; k < g->batch_3d; k++) queue_step_3d(g);
+  } else if (g->two_d) for (int k = 0; k < g->batch_2d; k++) queue_step_2d(g, tlim);
+  else for (int k = 0; k < g->batch_3d; k++) queue_step_3d(g, tlim);
   return 0;
 }
+
+// ... and its history schedule, where the call has one
+static int grid_hst_row(void *self) { aa_grid *g = (aa_grid*)self; return hst_row_host(g, g->time, g->dt); }
+static int grid_hst_begin(void *self, int nstep) { aa_grid *g = (aa_grid*)self; launch_hst_seed(g->hst, nstep, g->st); return 0; }
+static void grid_hst_drain(void *self) { aa_grid *g = (aa_grid*)self; hst_drain_grid(g, g->hst); }
 
 // `who`: the entry's name for its messages; ndim: the Grids it takes
 static int run_to_time(aa_grid *g, const char *who, int ndim, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
 {
   if (!g) return aa_fail(-1, "[%s]: null argument", who);
+  // a schedule armed for this call is taken over here and disarmed, whatever the call returns
+  struct Disarm { HstRun &h; ~Disarm() { h.active = false; } } disarm = {g->hst};
+  g->hst.active = g->hst.armed; g->hst.armed = false;
+  if (g->hst.active) g->hst_rows.clear();
   if (ndim == 1) {
     if (!g->one_d) return aa_fail(-1, "[%s]: this is a %s Grid: only a 1-D Grid runs many steps per launch", who, g->two_d ? "2-D" : "3-D");
     // (before the knob is looked at: AA_1D_RESIDENT=0 does not lift it)
@@ -211,6 +349,7 @@ static int run_to_time(aa_grid *g, const char *who, int ndim, double t_stop, dou
   o.who = who; o.owner = "Grid"; o.self = g; o.time = &g->time; o.dt = &g->dt; o.nstep = &g->nstep; o.tlim = g->p.tlim;
   o.stepwise = ndim == 1 ? !g->resident_1d : ndim == 3 ? !queues_3d(g) : (g->batch_2d == 0 || g->d.Nx1 < AA_NGHOST || g->d.Nx2 < AA_NGHOST);
   o.step = grid_step; o.begin = grid_begin; o.batch = grid_batch; o.end = nullptr; o.st = g->st; o.host_syncs = &g->host_syncs;
+  if (g->hst.active) { o.hst = &g->hst; o.hst_row = grid_hst_row; o.hst_begin = grid_hst_begin; o.hst_drain = grid_hst_drain; }
   return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }
 
@@ -225,5 +364,32 @@ int aa_run_2d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nstep
 int aa_run_3d_batch(const aa_grid *g) { return g && queues_3d(g) ? g->batch_3d : 0; }
 int aa_run_3d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
 { return run_to_time(g, "aa_run_3d", 3, t_stop, tlim, nstep_stop, nsteps_done); }
+
+int aa_run_hst_arm(aa_grid *g, double t_next, double dt_out, int nlim)
+{
+  const char *who = "aa_run_hst_arm";
+  if (!g) return aa_fail(-1, "[%s]: null argument", who);
+  if (g->one_d) return aa_fail(-1, "[%s]: this is a 1-D Grid: aa_run_1d keeps the whole loop in one launch and would add the sums in another order; its history rows stay stop times", who);
+  if (!g->slab.empty()) return aa_fail(-1, "[%s]: a Grid cut into slabs steps one at a time: aa_step, aa_history", who);
+  if (g->keep_flux || g->level > 0)
+    return aa_fail(-1, "[%s]: this Grid is a level of a Mesh (level %d): aa_mesh_run_hst_arm", who, g->level);
+  const int cap = g->two_d ? g->batch_2d : g->batch_3d;      // rows of one batch; 0: the call steps one at a time and needs no device buffer
+  if (cap > 0) {
+    if (int rc = hst_grid_buffers(g, cap, who)) return rc;
+    if (int rc = hst_sched_buffers(g->hst, who)) return rc;
+  }
+  g->hst.t_next = t_next; g->hst.dt_out = dt_out; g->hst.nlim = nlim < 0 ? -1 : nlim; g->hst.cap = cap;
+  g->hst.armed = true;
+  return 0;
+}
+int aa_run_hst_rows(aa_grid *g, int cap, double *rows, int *nrows, double *t_next)
+{
+  if (!g) return aa_fail(-1, "[aa_run_hst_rows]: null argument");
+  const int n = (int)(g->hst_rows.size()/AA_HST_ROW);
+  if (rows && cap > 0) memcpy(rows, g->hst_rows.data(), (size_t)(n < cap ? n : cap)*AA_HST_ROW*sizeof(double));
+  if (nrows) *nrows = n;
+  if (t_next) *t_next = g->hst.t_next;
+  return 0;
+}
 
 }  // extern "C"

@@ -421,6 +421,9 @@ struct aa_mesh {
   int batch_3d = 0;
   Run3D *run3d_dev = nullptr;
   MeshClockTab3 tab3;
+  // aa_mesh_run_hst_arm: the ONE history schedule of the Mesh (api_internal.h HstRun; every Grid keeps its own partial rows, ring
+  // and rows)
+  HstRun hst;
 };
 
 extern "C" {
@@ -672,6 +675,7 @@ void aa_mesh_destroy(aa_mesh *m)      // the levels stay alive and go back to th
   if (m->run2d_dev) hipFree(m->run2d_dev);
   if (m->run3d_dev) hipFree(m->run3d_dev);
   if (m->clock) hipHostFree(m->clock);
+  hst_free_sched(m->hst);
   delete m;
 }
 
@@ -987,6 +991,19 @@ static int mesh_run_buffers(aa_mesh *m)
   return 0;
 }
 
+// The history rows of a queued step, where the call has a schedule armed: behind the step's boundary pass and prolongation (both
+// write ghost zones only; the sums are over active zones) and in front of the next step's first kernel.  k_history_dc for every
+// Grid in the Mesh's order, each into its own partial rows; then k_hst_row for the Grids in turn, each into its own ring at the
+// schedule's row count -- all of them evaluate the rule on the Mesh's clock (a 3-D Mesh: the first Grid's, they are kept equal) and
+// on the schedule as the step before left it; only the last launch moves the schedule on.
+static void mesh_queue_hst(aa_mesh *m, const RunClock *clock, double tlim)
+{
+  Scope s(m->lev[0], "hst_row");
+  int nb[AA_MAXLEV];
+  for (int l = 0; l < m->nl; l++) nb[l] = launch_history_dc(m->lev[l]->d, m->lev[l]->p.nscal, m->lev[l]->hst_part, clock, tlim, m->hst.sched, m->st);
+  for (int l = 0; l < m->nl; l++) launch_hst_row(m->lev[l], nb[l], clock, tlim, m->hst, l == m->nl - 1, m->st);
+}
+
 // One queued step: aa_mesh_step's order with no host in it.  Every kernel in front of k2d_mesh_advance reads dt and `live` from
 // the Mesh's clock and stores nothing behind the stop.
 //  * the integrator chain of every level, the update kernel in its flux-keeping form.  new_dt's maxima ride on it where the Grid
@@ -1013,7 +1030,7 @@ static int mesh_run_buffers(aa_mesh *m)
 // fork of the levels onto their side streams (aa_mesh_step, AA_MESH_OVERLAP) is dropped here: with no host visit between the steps
 // its two event hand-overs per level and step cost more than the overlap of these small chains gains (203 us per
 // step of the reference's deck on one stream against 225 - 232 with the fork).
-static int mesh_queue_step_2d(aa_mesh *m)
+static int mesh_queue_step_2d(aa_mesh *m, double tlim)
 {
   const Run2D *rc = m->run2d_dev;
   for (int l = 0; l < m->nl; l++) {
@@ -1067,6 +1084,7 @@ static int mesh_queue_step_2d(aa_mesh *m)
       hipLaunchKernelGGL(k2d_prolong, dim3(nblk(n0, S2_W), nblk(n1, S2_R)), dim3(S2_W, S2_R), 0, m->st, C->d, L, m->box[l - 1], dim);
     }
   }
+  if (m->hst.active) mesh_queue_hst(m, &m->run2d_dev->c, tlim);      // (with no schedule armed the step launches what it always did)
   return 0;
 }
 
@@ -1081,10 +1099,10 @@ static int mesh_run_begin(void *self, const RunClock &seed, double t_stop, doubl
   *clock = m->clock;
   return 0;
 }
-static int mesh_run_batch(void *self, double, double, int)
+static int mesh_run_batch(void *self, double, double tlim, int)
 {
   aa_mesh *m = (aa_mesh*)self;
-  for (int k = 0; k < m->batch_2d; k++) { int rc = mesh_queue_step_2d(m); if (rc) return rc; }
+  for (int k = 0; k < m->batch_2d; k++) { int rc = mesh_queue_step_2d(m, tlim); if (rc) return rc; }
   return 0;
 }
 // every level's copy of MeshS, as aa_mesh_step and aa_mesh_new_dt leave them
@@ -1094,11 +1112,34 @@ static void mesh_run_end(void *self)
   for (int l = 0; l < m->nl; l++) { m->lev[l]->time = m->time; m->lev[l]->nstep = m->nstep; m->lev[l]->dt = m->dt; }
 }
 
+// the Mesh's history schedule behind run_frame (api_internal.h RunOps): a row of every Grid from aa_history behind a single step;
+// the seed of the device's schedule; every Grid's rows of a batch from its ring
+static int mesh_hst_row(void *self)
+{
+  aa_mesh *m = (aa_mesh*)self;
+  for (int l = 0; l < m->nl; l++) if (int rc = hst_row_host(m->lev[l], m->time, m->dt)) return rc;
+  return 0;
+}
+static int mesh_hst_begin(void *self, int nstep) { aa_mesh *m = (aa_mesh*)self; launch_hst_seed(m->hst, nstep, m->st); return 0; }
+static void mesh_hst_drain(void *self) { aa_mesh *m = (aa_mesh*)self; for (int l = 0; l < m->nl; l++) hst_drain_grid(m->lev[l], m->hst); }
+// a schedule armed for this call is taken over and disarmed, whatever the call returns
+struct MeshHstCall {
+  aa_mesh *m;
+  explicit MeshHstCall(aa_mesh *m_) : m(m_) {
+    m->hst.active = m->hst.armed; m->hst.armed = false;
+    if (m->hst.active) for (int l = 0; l < m->nl; l++) m->lev[l]->hst_rows.clear();
+  }
+  ~MeshHstCall() { m->hst.active = false; }
+  void hooks(RunOps &o) const
+  { if (m->hst.active) { o.hst = &m->hst; o.hst_row = mesh_hst_row; o.hst_begin = mesh_hst_begin; o.hst_drain = mesh_hst_drain; } }
+};
+
 int aa_mesh_run_2d_batch(const aa_mesh *m) { return m && m->two_d && !m->cut ? m->batch_2d : 0; }
 
 int aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
 {
   if (!m) return aa_fail(-1, "[aa_mesh_run_2d]: null argument");
+  MeshHstCall hst(m);
   if (m->cut) return aa_fail(-1, "[aa_mesh_run_2d]: this Mesh is cut into slabs: its levels step together on their slabs' streams, aa_mesh_step");
   if (m->local) return aa_fail(-1, "[aa_mesh_run_2d]: this Mesh is one rank's stack of slabs (aa_mesh_create_local): the ranks agree on dt between steps, aa_mesh_step");
   if (!m->two_d) return aa_fail(-1, "[aa_mesh_run_2d]: this is a Mesh of 3-D Grids: only a Mesh of 2-D Grids (aa_mesh_create_2d) runs many steps per host visit");
@@ -1115,6 +1156,7 @@ int aa_mesh_run_2d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *
   o.stepwise = m->batch_2d == 0 || m->nl > AA_2D_MESH_GRIDS || small;
   o.step = mesh_run_step; o.begin = mesh_run_begin; o.batch = mesh_run_batch; o.end = mesh_run_end; o.st = m->st;
   o.host_syncs = &m->lev[0]->host_syncs;
+  hst.hooks(o);
   return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
 }
 
@@ -1178,7 +1220,7 @@ static bool mesh_has_child(const aa_mesh *m, int l)
 // Plain launches on the Mesh's ONE stream, in stream order; the fork of the levels onto side streams (aa_mesh_step,
 // AA_MESH_OVERLAP) is dropped as in 2-D.  Nothing is captured, nothing launched cooperatively, no kernel waits on memory or on
 // another workgroup; the host reads the clock only behind run_frame's hipStreamSynchronize.
-static int mesh_queue_step_3d(aa_mesh *m)
+static int mesh_queue_step_3d(aa_mesh *m, double tlim)
 {
   Run3D *rcs = m->run3d_dev;
   for (int l = 0; l < m->nl; l++) queue_chain_3d(m->lev[l], rcs + l, mesh_has_child(m, l) ? nullptr : m->lev[l]->sc);   // (on m->st: every level's stream)
@@ -1234,6 +1276,7 @@ static int mesh_queue_step_3d(aa_mesh *m)
     for (int dim = 0; dim < 6; dim++)
       if (cnt[dim] > 0) hipLaunchKernelGGL(k_prolong, dim3(nblk(cnt[dim], 128)), dim3(128), 0, m->st, C->d, L, m->box[l - 1], dim, nvar);
   }
+  if (m->hst.active) mesh_queue_hst(m, &rcs[0].c, tlim);      // (as mesh_queue_step_2d)
   return 0;
 }
 
@@ -1247,10 +1290,10 @@ static int mesh_run_begin_3d(void *self, const RunClock &seed, double t_stop, do
   *clock = m->clock;
   return 0;
 }
-static int mesh_run_batch_3d(void *self, double, double, int)
+static int mesh_run_batch_3d(void *self, double, double tlim, int)
 {
   aa_mesh *m = (aa_mesh*)self;
-  for (int k = 0; k < m->batch_3d; k++) { int rc = mesh_queue_step_3d(m); if (rc) return rc; }
+  for (int k = 0; k < m->batch_3d; k++) { int rc = mesh_queue_step_3d(m, tlim); if (rc) return rc; }
   return 0;
 }
 
@@ -1271,6 +1314,7 @@ int aa_mesh_run_3d_batch(const aa_mesh *m) { return mesh_queues_3d(m) ? m->batch
 int aa_mesh_run_3d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done)
 {
   if (!m) return aa_fail(-1, "[aa_mesh_run_3d]: null argument");
+  MeshHstCall hst(m);
   if (m->cut) return aa_fail(-1, "[aa_mesh_run_3d]: this Mesh is cut into slabs: its levels step together on their slabs' streams, aa_mesh_step");
   if (m->local) return aa_fail(-1, "[aa_mesh_run_3d]: this Mesh is one rank's stack of slabs (aa_mesh_create_local): the ranks agree on dt between steps, aa_mesh_step");
   if (m->two_d) return aa_fail(-1, "[aa_mesh_run_3d]: this is a Mesh of 2-D Grids (aa_mesh_create_2d): aa_mesh_run_2d");
@@ -1283,7 +1327,36 @@ int aa_mesh_run_3d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *
   o.stepwise = !mesh_queues_3d(m);
   o.step = mesh_run_step; o.begin = mesh_run_begin_3d; o.batch = mesh_run_batch_3d; o.end = mesh_run_end; o.st = m->st;
   o.host_syncs = &m->lev[0]->host_syncs;
+  hst.hooks(o);
   return run_frame(o, t_stop, tlim, nstep_stop, nsteps_done);
+}
+
+// ---- the history schedule of the next aa_mesh_run_2d / aa_mesh_run_3d call (run.hip has a Grid's: aa_run_hst_arm) -----------------
+int aa_mesh_run_hst_arm(aa_mesh *m, double t_next, double dt_out, int nlim)
+{
+  const char *who = "aa_mesh_run_hst_arm";
+  if (!m) return aa_fail(-1, "[%s]: null argument", who);
+  if (m->cut) return aa_fail(-1, "[%s]: this Mesh is cut into slabs: its levels step together on their slabs' streams, aa_mesh_step and aa_history", who);
+  if (m->local) return aa_fail(-1, "[%s]: this Mesh is one rank's stack of slabs (aa_mesh_create_local): the ranks add their rows on the host, aa_mesh_step and aa_history", who);
+  const int cap = m->two_d ? m->batch_2d : m->batch_3d;      // rows of one batch; 0: the call steps one at a time and needs no device buffer
+  if (cap > 0) {
+    for (int l = 0; l < m->nl; l++) if (int rc = hst_grid_buffers(m->lev[l], cap, who)) return rc;
+    if (int rc = hst_sched_buffers(m->hst, who)) return rc;
+  }
+  m->hst.t_next = t_next; m->hst.dt_out = dt_out; m->hst.nlim = nlim < 0 ? -1 : nlim; m->hst.cap = cap;
+  m->hst.armed = true;
+  return 0;
+}
+int aa_mesh_run_hst_rows(aa_mesh *m, int grid, int cap, double *rows, int *nrows, double *t_next)
+{
+  if (!m) return aa_fail(-1, "[aa_mesh_run_hst_rows]: null argument");
+  if (grid < 0 || grid >= m->nl) return aa_fail(-1, "[aa_mesh_run_hst_rows]: grid=%d of a Mesh of %d Grids", grid, m->nl);
+  const std::vector<double> &r = m->lev[grid]->hst_rows;
+  const int n = (int)(r.size()/AA_HST_ROW);
+  if (rows && cap > 0) memcpy(rows, r.data(), (size_t)(n < cap ? n : cap)*AA_HST_ROW*sizeof(double));
+  if (nrows) *nrows = n;
+  if (t_next) *t_next = m->hst.t_next;
+  return 0;
 }
 
 

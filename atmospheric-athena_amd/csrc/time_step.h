@@ -12,6 +12,7 @@
  *   dt_clip        :183-185  ... and this half, the clip at tlim, behind it
  *   dt_pick        :167-185  the two composed
  *   run_live       main.c:519 as the run calls use it: time < t_stop && nstep != nstep_stop && dt > 0.0 (a NaN dt stops)
+ *   hst_row_due    main.c:524, output.c:509-512: whether a history block fires behind a taken step, and its next time
  *   run_advance_levels        main.c:618-629 of a Mesh: nstep++, time += dt, the fold over its Grids, the pick, run_live
  *   dt_over_dx, half_dt_over_dx   the update kernels' dt/dx and 0.5*(dt/dx) as the host's launch wrappers form them
  * No operation is contracted with another (the pragma inside every body: a file-scope one would reach the including file).
@@ -84,6 +85,25 @@ TS_FN double dt_pick(int nstep, double dt, double dt_cfl, double time, double tl
 TS_FN int run_live(double time, double t_stop, int nstep, int nstep_stop, double dt)
 {
   return time < t_stop && nstep != nstep_stop && dt > 0.0;
+}
+
+/* The schedule of ONE <outputN> block with out_fmt = hst while a run call has it armed (aa_run_hst_arm): the block's next time
+ * and spacing, the loop's nlim (-1: none), the rows made so far in the call, and the step number the schedule has looked at last
+ * (a queued step behind the stop leaves the clock's nstep where it was: no step was taken, nothing is asked). */
+typedef struct HstSched { double t_next, dt_out; int nlim, nrows, nstep_seen, pad; } HstSched;
+
+/* data_output(&Mesh, 0) at the top of the pass that follows a taken step (main.c:524, output.c:509-512) for one block: whether its
+ * row is due behind the step that left `time` and `nstep`, and *t_next advanced by dt_out ONCE if so.  The call is reached only
+ * if the loop goes on (main.c:519): behind the step that ends it -- time >= tlim (a NaN time too), nstep at nlim -- no row is
+ * due, the forced data_output(&Mesh, 1) behind the loop writes that one.  A step that merely ends a run CALL (t_stop < tlim, the
+ * span of 2^20 steps) is not the end of the loop. */
+TS_FN int hst_row_due(double time, int nstep, double tlim, int nlim, double dt_out, double *t_next)
+{
+  TS_NO_CONTRACT
+  if (!(time < tlim) || (nlim >= 0 && nstep >= nlim)) return 0;
+  if (!(time >= *t_next)) return 0;
+  *t_next += dt_out;
+  return 1;
 }
 
 /* dt/dx and dt/2dx of the update kernels as the launch wrappers evaluate them on the host for the kernels that take dt as an

@@ -127,7 +127,22 @@ class HipEngine:
             return self.g.can_run_3d() and self.g.run_3d_batch() != 0
         return self.g.can_run_until()
 
-    def run_local(self, t_stop: float, tlim: float, nstep_stop) -> int:
+    def hst_route(self):
+        """None where a history schedule rides on run_local (lib.Grid.run_hst_arm); else (kind, reason) for the one warning"""
+        if self.g.ndim == 1:
+            return ("1-D", "a 1-D Grid keeps its whole loop in one launch (aa_run_1d sums in another order)")
+        if self.g.composite:
+            return ("slabs", "a Grid cut into slabs inside the library steps one at a time")
+        return None
+
+    def hst_rows(self):
+        """(rows[n][11], t_next) of the run_local call that had a schedule armed"""
+        return self.g.run_hst_rows()
+
+    def run_local(self, t_stop: float, tlim: float, nstep_stop, hst=None) -> int:
+        """hst = (t_next, dt_out, nlim): a history schedule for this call alone (hst_route() is None)"""
+        if hst is not None:
+            self.g.run_hst_arm(*hst)
         if self.g.ndim == 2:
             return self.g.run_2d(t_stop, tlim, nstep_stop)
         if self.g.ndim == 3:
@@ -384,13 +399,14 @@ class _Runner:
                 vol *= Nx[a] * (self.run.dx[a] / float(1 << level))
         return vol
 
-    def _history_row(self, key, rundir, level, domain, out, outputs, sums, vol):
+    def _history_row(self, key, rundir, level, domain, out, outputs, sums, vol, time=None, dt=None):
         """One row of the .hst file of a Domain of volume `vol` (dump_history.c:271-279, :328-361): `sums` are its volume
-        integrals, already added over its Grids; the writer is kept under `key` for the rows to come."""
+        integrals, already added over its Grids; the writer is kept under `key` for the rows to come.  time, dt: of the row
+        where it was made behind an earlier step than the last (a queued run's rows, write_history_rows); default: of now."""
         w = self._hst.get(key)
         if w is None:
             w = self._hst[key] = HistoryWriter(rundir, outputs.basename, level, domain, out.dat_fmt, num=out.num)
-        w.dump(self.time, self.dt, sums, vol, self.run.nscal)
+        w.dump(self.time if time is None else time, self.dt if dt is None else dt, sums, vol, self.run.nscal)
         rel = os.path.relpath(w.path, outputs.dir)
         if rel not in outputs.written:
             outputs.written.append(rel)
@@ -755,12 +771,32 @@ class Driver(_Runner):
         holds (aa_run_1d) or a 2-D / 3-D hydro Grid whose steps queue with the time step picked on the device (aa_run_2d, aa_run_3d)"""
         return not self.distributed and hasattr(self.eng, "can_batch") and self.eng.can_batch()
 
-    def advance(self, t_stop: float, nstep_stop=None) -> int:
+    def hst_route(self):
+        """None where advance(..., hst=) makes the rows of a history block on the device (outputs.run with hst_queued asks); else
+        (kind, reason): the block stays a stop time of the run"""
+        if self.distributed:
+            return ("ranks", "a Driver on several ranks adds the rows of its ranks on the host")
+        if not hasattr(self.eng, "hst_route"):
+            return ("engine", "this engine keeps no state on a device")
+        return self.eng.hst_route()
+
+    def write_history_rows(self, out, outputs) -> int:
+        """the rows the last advance(..., hst=) made, each with its own time and dt, through the block's HistoryWriter -> their
+        number (a row of a block that asks for another level or domain is made and counted, not written: _fires)"""
+        rows, _ = self.eng.hst_rows()
+        for r in rows:
+            if _fires(out, 0):
+                self._history_row(out.n, outputs.dir, 0, 0, out, outputs, r[2:], self._volume(), time=float(r[0]), dt=float(r[1]))
+        return len(rows)
+
+    def advance(self, t_stop: float, nstep_stop=None, hst=None) -> int:
         """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit), in one launch
         (aa_run_1d) or as queued steps with one read-back per batch (aa_run_2d, aa_run_3d); the same bits as that many step() calls.
-        -> the steps taken"""
+        hst = (t_next, dt_out, nlim), where hst_route() is None: a history row behind every step that has one due
+        (write_history_rows).  -> the steps taken"""
         far = self.nstep + (1 << 20)              # (aa_run_1d / aa_run_2d cover 2^20 steps per call at the most; the caller's loop goes on)
-        n = self.eng.run_local(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
+        stop = far if nstep_stop is None else min(int(nstep_stop), far)
+        n = self.eng.run_local(t_stop, self.run.tlim, stop, hst) if hst is not None else self.eng.run_local(t_stop, self.run.tlim, stop)
         self.time, self.dt, self.nstep = self.eng.mesh_state()
         self.niter_trace.extend([0] * n)
         return n
@@ -872,10 +908,34 @@ class MeshRun(_Runner):
         return ((hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d())
                 or (hasattr(self.mesh, "can_run_3d") and self.mesh.can_run_3d()))
 
-    def advance(self, t_stop: float, nstep_stop=None) -> int:
+    def hst_route(self):
+        """None where advance(..., hst=) makes the rows of a history block on the device; else (kind, reason)"""
+        if not hasattr(self.mesh, "run_hst_arm"):
+            return ("engine", "this engine keeps no state on a device")
+        if getattr(self.mesh, "cuts", None) is not None or getattr(self.mesh, "links", None) is not None:
+            return ("slabs", "a Mesh cut into slabs steps one at a time")
+        return None
+
+    def write_history_rows(self, out, outputs) -> int:
+        """the rows the last advance(..., hst=) made: row by row every Domain the block asks for (_fires), as write_history
+        visits them -> the number of rows (of each Grid)"""
+        rows, _ = self.mesh.run_hst_rows()
+        n = len(rows[0]) if rows else 0
+        for i in range(n):
+            for g, r, (l, d) in zip(self.mesh.lev, rows, self.mesh.domain_numbers()):
+                if _fires(out, l, d):
+                    self._history_row((out.n, l, d), outputs.dir, l, d, out, outputs, r[i][2:], self._domain_volume(g.cfg.Nx, l),
+                                      time=float(r[i][0]), dt=float(r[i][1]))
+        return n
+
+    def advance(self, t_stop: float, nstep_stop=None, hst=None) -> int:
         """Whole passes of the main loop until time >= t_stop or nstep == nstep_stop (None: no such limit) as queued steps with one
-        read-back per batch (aa_mesh_run_2d / aa_mesh_run_3d); the same bits as that many step() calls.  -> the steps taken"""
+        read-back per batch (aa_mesh_run_2d / aa_mesh_run_3d); the same bits as that many step() calls.  hst = (t_next, dt_out,
+        nlim), where hst_route() is None: history rows of every Grid behind the steps that have one due (write_history_rows).
+        -> the steps taken"""
         far = self.nstep + (1 << 20)              # (a call covers 2^20 steps at the most; the caller's loop goes on)
+        if hst is not None:
+            self.mesh.run_hst_arm(*hst)
         run = self.mesh.run_2d if hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d() else self.mesh.run_3d
         return run(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
 
@@ -1130,6 +1190,10 @@ class MeshDriver(_Runner):
         if self.distributed:
             s = np.array(self._allreduce(s.reshape(-1), self.dist.ReduceOp.SUM)).reshape(self.NL, 9)
         return s
+
+    def hst_route(self):
+        """(kind, reason): outputs.run with hst_queued keeps the history block a stop time here"""
+        return ("MeshDriver", "a MeshDriver steps its ranks' slabs one at a time and adds their rows on the host")
 
     def write_history(self, out, outputs):
         """One row per level.  The sums are divided by the volume of the whole Domain (:271-279); the lowest rank that holds

@@ -39,6 +39,7 @@ class aa_params(C.Structure):
 
 ION_WORDS = 8     # AA_ION_WORDS of include/athena_amd.h
 TEST_PICK_SCALARS = 16     # AA_TEST_PICK_SCALARS: a row of aa_test_ion_pick's `prev` / `out`
+HST_ROW = 11      # AA_HST_ROW: doubles of a row of aa_run_hst_rows (time, dt, the nine sums of aa_history)
 
 GRAVPOT = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double)
 GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p)      # aa_gather_fn of include/athena_amd.h
@@ -104,6 +105,8 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_integrate_1d_ctu": (I, [P]), "aa_integrate_1d_vl": (I, [P]), "aa_run_1d": (I, [P, D, D, I, ip]),
         "aa_run_2d": (I, [P, D, D, I, ip]), "aa_run_2d_batch": (I, [P]),
         "aa_run_3d": (I, [P, D, D, I, ip]), "aa_run_3d_batch": (I, [P]),
+        "aa_run_hst_arm": (I, [P, D, D, I]), "aa_run_hst_rows": (I, [P, I, dp, ip, dp]),
+        "aa_mesh_run_hst_arm": (I, [P, D, D, I]), "aa_mesh_run_hst_rows": (I, [P, I, I, dp, ip, dp]),
         "aa_run_1d_cap": (I, []), "aa_step_1d_block": (I, []),
         "aa_start": (I, [P]), "aa_step": (I, [P, ip]),
         "aa_new_dt_local": (I, [P, dp]), "aa_ion_begin": (I, [P]), "aa_ion_rates": (I, [P, dp, dp]),
@@ -513,6 +516,23 @@ class Grid:
         same bits as that many step() calls (a Grid with run_3d_batch() == 0 takes them one at a time).  AthenaError on a Grid
         that is not 3-D, has pinned zones, is cut into slabs or is a level of a Mesh (can_run_3d)."""
         return self._run(self.L.aa_run_3d, t_stop, tlim, nstep_stop)
+
+    def run_hst_arm(self, t_next: float, dt_out: float, nlim: int | None = None) -> None:
+        """Arms a history schedule for the NEXT run_2d / run_3d call only (aa_run_hst_arm): behind every step of that call after
+        which the main loop goes on (time < tlim, nstep != nlim; None: no such limit) and time >= t_next, a row is made on the
+        device -- queued or step by step inside the call, the same rows -- and t_next += dt_out ONCE.  The call disarms itself.
+        AthenaError on a 1-D Grid, a Grid cut into slabs, a level of a Mesh."""
+        self._chk(self.L.aa_run_hst_arm(self._h, float(t_next), float(dt_out), -1 if nlim is None else int(nlim)))
+
+    def run_hst_rows(self):
+        """-> (rows, t_next) of the last armed run call (aa_run_hst_rows): rows[n][11] = time, dt and the nine sums of history()
+        behind the n-th step that had a row due; t_next: the schedule's next time behind them"""
+        n, t = C.c_int(), C.c_double()
+        self._chk(self.L.aa_run_hst_rows(self._h, 0, None, C.byref(n), C.byref(t)))
+        rows = np.zeros((n.value, HST_ROW))
+        if n.value:
+            self._chk(self.L.aa_run_hst_rows(self._h, n.value, _dp(rows), C.byref(n), C.byref(t)))
+        return rows, t.value
 
     # ---- phases ----------------------------------------------------------------------
     def new_dt_local(self) -> float:
@@ -1042,3 +1062,21 @@ class Mesh:
         stop = self.nstep + (1 << 20) if nstep_stop is None else int(nstep_stop)
         self._chk(self.L.aa_mesh_run_3d(self._h, float(t_stop), float(tlim), stop, C.byref(n)))
         return n.value
+
+    def run_hst_arm(self, t_next: float, dt_out: float, nlim: int | None = None) -> None:
+        """Grid.run_hst_arm for the next run_2d / run_3d call of this Mesh (aa_mesh_run_hst_arm): ONE schedule for all levels, a
+        row of every Grid where one is due.  AthenaError on a Mesh cut into slabs or made from links."""
+        self._chk(self.L.aa_mesh_run_hst_arm(self._h, float(t_next), float(dt_out), -1 if nlim is None else int(nlim)))
+
+    def run_hst_rows(self):
+        """-> ([rows of Grid 0, rows of Grid 1, ...], t_next) of the last armed run call (aa_mesh_run_hst_rows): every Grid's
+        rows[n][11] = time, dt and the nine sums of its history(), the same n for all"""
+        out, t = [], C.c_double()
+        for l in range(len(self.lev)):
+            n = C.c_int()
+            self._chk(self.L.aa_mesh_run_hst_rows(self._h, l, 0, None, C.byref(n), C.byref(t)))
+            rows = np.zeros((n.value, HST_ROW))
+            if n.value:
+                self._chk(self.L.aa_mesh_run_hst_rows(self._h, l, n.value, _dp(rows), C.byref(n), C.byref(t)))
+            out.append(rows)
+        return out, t.value

@@ -22,6 +22,10 @@ the file written by the thread of dumps.OverlapWriter); the files and ``written`
 only the thread that drives the run calls the library -- ``poll`` and ``finish`` belong to it.  ``overlap_rst=True`` -- a switch
 of its own -- does the same for the restart dump (``overlapped_restart``: the double-precision payload of every Grid from ONE
 snapshot slot per Grid, the file behind the vtk / bin files already queued).
+
+``OutputSet(..., hst_queued=True)`` -- off by default like the two above -- lets `run` keep a target's queued steps going through
+the FIRST ``hst`` block: the block is armed on the device for every advance() (``hst_armed``), its rows come back with the call and
+are written with their own time and dt.  The files are those of the run with the keyword off.
 """
 from __future__ import annotations
 
@@ -60,12 +64,15 @@ class Output:
 class OutputSet:
     def __init__(self, par: ParTable, outs: List[Output], rst: Optional[Output], rundir: str, rank: int, nranks: int,
                  rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False, overlap_max_bytes: int = 8 << 30,
-                 overlap_rst: bool = False):
+                 overlap_rst: bool = False, hst_queued: bool = False):
         """overlap = True: vtk / bin dumps of targets that have the route (see `overlapped_dump`) are written beside the run;
         overlap_max_bytes: the largest payload that may take it (each Grid that dumps keeps two device buffers and two
         page-locked buffers of its payload's size).  overlap_rst = True, independent of `overlap`: the restart dump too (see
-        `overlapped_restart`; one device buffer and one page-locked buffer of the restart payload per Grid, under the same cap)."""
+        `overlapped_restart`; one device buffer and one page-locked buffer of the restart payload per Grid, under the same cap).
+        hst_queued = True, a switch of its own: `run` leaves the first ``hst`` block out of the stop times of a target whose
+        steps queue on the device and takes its rows from there (`hst_armed`; the same files)."""
         self.par, self.outs, self.rst = par, outs, rst
+        self.hst_queued = bool(hst_queued)
         self.overlap, self.overlap_max_bytes = bool(overlap), int(overlap_max_bytes)
         self.overlap_rst = bool(overlap_rst)
         self._writer = None                   # dumps.OverlapWriter, made by the first overlapped dump
@@ -87,7 +94,7 @@ class OutputSet:
     @classmethod
     def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
                  rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False,
-                 overlap_max_bytes: int = 8 << 30, overlap_rst: bool = False) -> "OutputSet":
+                 overlap_max_bytes: int = 8 << 30, overlap_rst: bool = False, hst_queued: bool = False) -> "OutputSet":
         """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
         r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
         rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
@@ -153,19 +160,23 @@ class OutputSet:
             else:
                 outs.append(o)
         return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes,
-                   overlap_rst)
+                   overlap_rst, hst_queued)
 
-    def data_output(self, target, flag: int) -> None:
+    def data_output(self, target, flag: int, settled: Optional[Output] = None) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt
         ONCE (output.c:509-512).  The restart dump goes first, after every block's next number and time have been written
         back into the parameter table (:526-543), so that a restarted run continues the numbering.  With overlapped dumps it
-        begins with a `poll`: the payloads that have arrived go to the writer, the files that are complete give their slots back."""
+        begins with a `poll`: the payloads that have arrived go to the writer, the files that are complete give their slots back.
+        settled: a block whose row for this time is already written and counted (`run` with hst_queued: the device has
+        applied the rule behind this step, t += dt and num += 1 are done) -- it is not asked again."""
         self.poll()
         time = target.time
         fire = []
         for o in self.outs:
             f = bool(flag)
-            if time >= o.t:
+            if o is settled:
+                pass
+            elif time >= o.t:
                 o.t += o.dt
                 f = True
             fire.append(f)
@@ -208,6 +219,26 @@ class OutputSet:
         if (switch, kind) not in self._warned:
             self._warned.add((switch, kind))
             warnings.warn(f"[data_output]: {switch} = True, but {reason}: these dumps are written synchronously (the same files)")
+
+    # ---- history rows from the device (hst_queued; csrc/run.hip aa_run_hst_arm) ----------------------------------------------------
+    def hst_armed(self, target) -> Optional[Output]:
+        """The block `run` arms on the device for the next advance of `target`, or None: hst_queued on, the FIRST ``hst`` block
+        (further ones stay stop times), and a target with the route -- ``hst_route()`` -> None, ``advance(..., hst=)`` and
+        ``write_history_rows(out, self)``: driver.Driver on one rank with a 2-D / 3-D Grid on a device, driver.MeshRun.  Every
+        other target keeps today's path, and the first case of a kind has warned (as `overlap_fallback` does)."""
+        if not self.hst_queued:
+            return None
+        o = next((o for o in self.outs if o.out_fmt == "hst"), None)
+        if o is None:
+            return None
+        why = target.hst_route() if hasattr(target, "hst_route") else ("engine", "this engine keeps no state on a device")
+        if why is not None:
+            if ("hst_queued", why[0]) not in self._warned:
+                self._warned.add(("hst_queued", why[0]))
+                warnings.warn(f"[data_output]: hst_queued = True, but {why[1]}: the history block stays a stop time of the run "
+                              "(the same files)")
+            return None
+        return o
 
     def overlapped_dump(self, source, rel: str, fmt, prim: bool, level=None, domain: int = 0, time=None, dt=None) -> bool:
         """The overlapped route of a target's write_dump for the dump `rel` (relative to this rank's directory) of `source`:
@@ -375,19 +406,39 @@ def run(target, outputs: OutputSet, tlim: float, nlim: int = -1) -> None:
     ``restarted`` set -- skips it), data_output(0) at the top of every pass (:524), forced output after the loop (:743).
     `target`: start(), step(), time, nstep and the writers.  A target that also has ``advance(t_stop, nstep_stop)`` and whose
     ``may_batch()`` says so (driver.Driver on a 1-D Grid) takes every stretch between two output times in ONE call: up to the
-    earliest next time of any block, or tlim.  data_output(0) writes nothing between those times, so the files are the same."""
+    earliest next time of any block, or tlim.  data_output(0) writes nothing between those times, so the files are the same.
+
+    With ``OutputSet(hst_queued=True)`` the first ``hst`` block of such a target (`OutputSet.hst_armed`) is no stop time: its
+    t, dt and nlim go along with advance(), which applies data_output's rule for that block behind every step it takes
+    (csrc/time_step.h hst_row_due) and makes the rows where they are due.  Each row that comes back is written with its own time
+    and dt and counted -- t += dt, num += 1 -- before the next data_output(0), which does not ask that block again for the step
+    the call ended on: a restart dump fired there carries the table the per-step run writes."""
     batch = hasattr(target, "advance") and hasattr(target, "may_batch")
+    armed = getattr(outputs, "hst_armed", None)
     try:
         target.start()
         if not getattr(target, "restarted", False):
             outputs.data_output(target, 1)
+        settled = None
         while target.time < tlim and (nlim < 0 or target.nstep < nlim):
-            outputs.data_output(target, 0)
-            done = 0
+            if settled is not None:
+                outputs.data_output(target, 0, settled)
+            else:
+                outputs.data_output(target, 0)
+            done, settled = 0, None
             if batch and target.may_batch():      # (asked on every pass: zones pinned since the last one end the batching)
-                t_stop = min([tlim] + [o.t for o in outputs.outs] + ([outputs.rst.t] if outputs.rst is not None else []))
+                h = armed(target) if armed is not None else None
+                t_stop = min([tlim] + [o.t for o in outputs.outs if o is not h] + ([outputs.rst.t] if outputs.rst is not None else []))
                 if t_stop > target.time:          # (a block whose next time has already passed fires again on the next pass)
-                    done = target.advance(t_stop, nlim if nlim >= 0 else None)
+                    if h is None:
+                        done = target.advance(t_stop, nlim if nlim >= 0 else None)
+                    else:
+                        done = target.advance(t_stop, nlim if nlim >= 0 else None, hst=(h.t, h.dt, nlim if nlim >= 0 else None))
+                        for _ in range(target.write_history_rows(h, outputs)):
+                            h.t += h.dt
+                            h.num += 1
+                        if done > 0:
+                            settled = h
             if done == 0:                         # ... and a dt that is not positive (or NaN) ends advance() with no step taken:
                 target.step()                     # the single step goes on as the reference does (time = NaN ends the loop)
         outputs.data_output(target, 1)

@@ -182,6 +182,20 @@ int aa_run_2d_batch(const aa_grid *g);              /* steps queued per read-bac
  * aa_mesh, for tlim other than the Grid's, and for nstep_stop outside nstep .. nstep + 2^20.                                   */
 int aa_run_3d(aa_grid *g, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 int aa_run_3d_batch(const aa_grid *g);              /* steps queued per read-back on this Grid (0: one aa_step at a time; not 3-D: 0) */
+/* History rows of the NEXT aa_run_2d / aa_run_3d call, made without a stop: arms the schedule of one <outputN> block with out_fmt = hst
+ * -- its next time `t_next`, its spacing `dt_out`, the loop's nlim (< 0: none) -- for that call alone; the call disarms it whatever it
+ * returns, the caller keeps the block's state.  Behind every step the call takes, data_output(&Mesh, 0) of the following pass is
+ * applied for that block (csrc/time_step.h hst_row_due: main.c:524, output.c:509-512): if the loop goes on -- time < tlim, nstep below
+ * nlim -- and time >= t_next, a row {time, dt, the nine sums of aa_history} is made and t_next += dt_out ONCE.  No row behind the
+ * step that ends the loop (the forced output writes that one); a step that merely ends the CALL (t_stop, the span) is not that end.
+ * Queued (csrc/history_dc.hip k_history_dc, csrc/run.hip k_hst_row: two more launches per queued step, which store nothing unless a
+ * row is due; the rows reach the host with the clock, once per batch) or step by step inside the call (aa_history behind aa_step):
+ * the same rows, bit for bit.  An error on a 1-D Grid (aa_run_1d keeps its loop in one launch and would add in another order), a
+ * Grid cut into slabs, a level of an aa_mesh.  aa_run_hst_rows: up to `cap` rows of AA_HST_ROW doubles of the last armed call into
+ * `rows` (may be NULL), their number into *nrows, the schedule's next time behind them into *t_next.                           */
+#define AA_HST_ROW 11
+int aa_run_hst_arm(aa_grid *g, double t_next, double dt_out, int nlim);
+int aa_run_hst_rows(aa_grid *g, int cap, double *rows, int *nrows, double *t_next);
 int aa_run_1d_cap(void);                            /* most active zones aa_run_1d keeps resident */
 int aa_step_1d_block(void);                         /* TEST HOOK: active zones per block of the per-step kernel (the fixtures'
                                                        sizes sit either side of it); nothing in the product calls it */
@@ -337,6 +351,12 @@ int  aa_mesh_run_2d_batch(const aa_mesh *m);      /* steps queued per read-back 
  * combination this build does not instantiate.  aa_run_3d on a level of a Mesh and aa_mesh_run_2d on a 3-D Mesh stay errors.      */
 int  aa_mesh_run_3d(aa_mesh *m, double t_stop, double tlim, int nstep_stop, int *nsteps_done);
 int  aa_mesh_run_3d_batch(const aa_mesh *m);      /* steps queued per read-back on this Mesh; 0: it steps one at a time */
+/* aa_run_hst_arm / aa_run_hst_rows for the next aa_mesh_run_2d / aa_mesh_run_3d call: ONE schedule for the Mesh (a block's time and
+ * spacing are shared by its levels), the rule applied to the Mesh's clock, a row of every Grid where one is due -- `grid`: the
+ * Grid's index in the Mesh's order; all Grids have the same number of rows.  An error on a Mesh cut into slabs and on one made by
+ * aa_mesh_create_local.                                                                                                      */
+int  aa_mesh_run_hst_arm(aa_mesh *m, double t_next, double dt_out, int nlim);
+int  aa_mesh_run_hst_rows(aa_mesh *m, int grid, int cap, double *rows, int *nrows, double *t_next);
 
 /* Multi-GPU SMR: every level is cut into x3 slabs at the SAME root planes, so that restriction, the
  * radiation hand-off and prolongation stay inside a rank.  aa_mesh_create_local builds one rank's stack
