@@ -106,6 +106,10 @@ static int launch_cfg_read(const aa_params &p, LaunchCfg &c)
   { const char *e = getenv("AA_ION_LEAN");
     c.ion_lean = (!e || !strcmp(e, "auto")) ? -1 : (!strcmp(e, "0") ? 0 : (!strcmp(e, "1") ? 1 : 2));
     if (c.ion_lean == 2) return fail(-1, "[aa_create]: AA_ION_LEAN=%s: must be auto, 0 or 1", e); }
+  // radiation sub-cycles queued per host visit (ion_run_fused): 1 = one read-back per sub-cycle, the launches as they were; same bits
+  c.ion_batch = env("AA_ION_BATCH", 1);
+  if (c.ion_batch < 1 || c.ion_batch > AA_ION_BATCH_MAX)
+    return fail(-1, "[aa_create]: AA_ION_BATCH=%d: must be 1 (a read-back per sub-cycle) or 2..%d", c.ion_batch, AA_ION_BATCH_MAX);
   // ---- not a launch choice of a kernel of the step, kept here all the same: floats per half of the dumps' bounce buffer
   c.dump_chunk = env("AA_DUMP_CHUNK_FLOATS", 1 << 23); if (c.dump_chunk < 4) c.dump_chunk = 4; if (c.dump_chunk > (1 << 28)) c.dump_chunk = 1 << 28;
   return 0;
@@ -1162,6 +1166,61 @@ static int ion_ran(aa_grid *g, const IonSubcycles &r, int *niter_out, double *dt
   return 0;
 }
 
+// ---- LaunchCfg ion_batch: K sub-cycles per host visit.  Which Grids take it: one rank reducing alone with the fused pick, no slabs
+static bool ion_batch_on(const aa_grid *g)
+{ return g->p.ion && g->ion_fused && g->slab.empty() && g->d.cfg.ion_batch > 1 && g->d.cfg.fuse_pick != 0; }
+int aa_set_ion_batch(aa_grid *g, int k)
+{
+  if (k < 1 || k > AA_ION_BATCH_MAX) return fail(-1, "[aa_set_ion_batch]: ion_batch=%d: must be 1 (a read-back per sub-cycle) or 2..%d", k, AA_ION_BATCH_MAX);
+  g->d.cfg.ion_batch = k;
+  for (aa_grid *c : g->slab) c->d.cfg.ion_batch = k;
+  return 0;
+}
+int aa_ion_batch(const aa_grid *g) { return g->slab.empty() ? g->d.cfg.ion_batch : g->slab[0]->d.cfg.ion_batch; }      // (the slabs read the environment)
+// (a Grid whose ion step last came through aa_ion_radtransfer_3d_gather -- a rank of several -- reduces over the ranks every sub-cycle)
+int aa_ion_batch_active(const aa_grid *g) { return (ion_batch_on(g) && !g->ion_gather_entry) ? 1 : 0; }
+int aa_ion_batch_counts(const aa_grid *g, long long *n) { for (int k = 0; k < 3; k++) n[k] = g->ion_batch_n[k]; return 0; }
+
+// The loop behind the first pass and the first pick with the stop rule on the device (k_ion_reduce_pick_q): a visit queues `b`
+// sub-cycles -- each the launches aa_ion_pass(1, 1) + aa_ion_pick(0) would make, in their queued entries -- and reads back once,
+// behind the last pick's publication.  The kernels take cur, flux0 and limit by value: ion_cur moves per QUEUED sub-cycle here and
+// is set to what the EXECUTED ones leave behind the read-back, as are the other words the per-sub-cycle loop keeps.  The first
+// visit is as long as the Grid's previous ion step was (at most K, at least 1: a step behind a one-sub-cycle step is launch for
+// launch the per-sub-cycle loop's), later ones K.
+static int ion_run_queued(aa_grid *g, bool fine, double limit, IonSubcycles *r)
+{
+  const int K = g->d.cfg.ion_batch;
+  const Real flux0 = (g->nradplane > 0) ? ion_flux0(g) : 0.0;
+  const bool fe = g->level > 0 && g->nradplane > 0;
+  const bool pub = g->d.cfg.mailbox && g->mb_dev;
+  int b = g->ion_prev_niter < 1 ? 1 : (g->ion_prev_niter < K ? g->ion_prev_niter : K), queued = 0, rc;
+  const int cur0 = g->ion_cur;
+  for (;;) {
+    { Scope s(g, "ion_pass");
+    for (int i = 0; i < b; i++, queued++) {
+      const bool redo = queued == 0 && g->ion_spec_armed && g->ion_step_lean, last = i == b - 1;
+      g->ion_cur ^= 1;
+      g->mb_prepublished = (last && pub) ? ++g->mb_seq : 0;
+      launch_ion_subcycle_q(g->d, g->ion, redo, flux0, fe, g->sc, g->ion_cur, g->ion_part, g->ion_words, fine ? 1 : 0, limit, g->p.cour_no, g->st,
+                            (last && pub) ? g->mb_dev : nullptr, (last && pub) ? g->mb_seq : 0ULL);
+    } }
+    HIPCHK(hipGetLastError());
+    g->ion_spec_armed = false;
+    if ((rc = fetch_scalars(g))) return rc;
+    g->ion_batch_n[0]++;
+    if (g->sc_host->ion_stop != 0) break;
+    b = K;
+  }
+  const DevScalars &h = *g->sc_host;
+  const int ran = h.ion_niter + (h.ion_stop == ION_STOP_NEG ? 1 : 0);      // sub-cycles whose passes ran
+  g->ion_cur = cur0 ^ (ran & 1); g->ion_pending = true; g->ion_step_updates = ran;
+  g->ion_batch_n[1] += ran; g->ion_batch_n[2] += queued - ran;
+  g->ion_prev_niter = h.ion_niter;
+  if (h.ion_stop == ION_STOP_NEG) { r->rc = fail(-4, "[compute_chem_rates]: negative dt_chem"); return 0; }      // ionrad_3d.c:389-391
+  r->rc = 0; r->niter = h.ion_niter; r->dt_done = h.dt_done; r->cut = h.ion_stop == ION_STOP_CUT;
+  return 0;
+}
+
 // the one-kernel sub-cycle: pass / gather / pick / fetch
 static int ion_run_fused(aa_grid *g, bool fine, double limit, int *niter_out, double *dt_done_out, const IonGather &G = IonGather())
 {
@@ -1176,6 +1235,13 @@ static int ion_run_fused(aa_grid *g, bool fine, double limit, int *niter_out, do
   if ((rc = aa_ion_pass(g, 0, 1, G.fn ? G.words : nullptr))) return rc;      // sweep(0) + rates(0)
   if ((rc = ion_gather(G))) return rc;
   if ((rc = aa_ion_pick(g, all, nr, 1, limit))) return rc;                   // -> dt_0 (stays on the device)
+  if (!G.fn && !g->ion_gather_entry && ion_batch_on(g)) {
+    IonSubcycles q = {0, 0, 0.0, false};
+    if ((rc = ion_run_queued(g, fine, limit, &q))) return rc;
+    if (q.rc) return q.rc;
+    if ((rc = aa_ion_finish(g))) return rc;
+    return ion_ran(g, q, niter_out, dt_done_out);
+  }
   const IonSubcycles r = ion_subcycles(fine, [&](double, double *dt, int *hit, long long *cellcount, double *dt_hydro) -> int {
     // update(n) with the step picked on the device, then -- unless that step was cut back to the limit -- sweep(n+1) and
     // rates(n+1), speculatively: whether the loop goes on is only known from this pass's own reductions
@@ -1188,6 +1254,7 @@ static int ion_run_fused(aa_grid *g, bool fine, double limit, int *niter_out, do
     return 0;
   });
   if (r.rc) return r.rc;
+  g->ion_prev_niter = r.niter;
   if ((rc = aa_ion_finish(g))) return rc;
   return ion_ran(g, r, niter_out, dt_done_out);
 }
@@ -1222,6 +1289,7 @@ static int ion_run_host_picked(aa_grid *g, bool fine, double limit, int *niter_o
 int aa_ion_run(aa_grid *g, int finegrid, double limit, int *niter_out, double *dt_done_out)
 {
   g->cfl_ready = false; g->active_dirty = true;
+  g->ion_gather_entry = false;
   if (g->ion_fused) return ion_run_fused(g, finegrid != 0, limit, niter_out, dt_done_out);
   return g->slab.empty() ? ion_run_phased(g, finegrid != 0, limit, niter_out, dt_done_out)
                          : ion_run_host_picked(g, finegrid != 0, limit, niter_out, dt_done_out);
@@ -1244,6 +1312,7 @@ int aa_ion_radtransfer_3d_gather(aa_grid *g, double *dev_words, const double *de
   if (!g->slab.empty()) return fail(-1, "[aa_ion_radtransfer_3d_gather]: a Grid cut into slabs reduces over its slabs itself (aa_ion_radtransfer_3d)");
   if (!g->ion_fused) return fail(-1, "[aa_ion_radtransfer_3d_gather]: this Grid runs the two-kernel sub-cycle (aa_ion_rates / aa_ion_update)");
   if (gather && (!dev_words || !dev_words_all || nranks < 1)) return fail(-1, "[aa_ion_radtransfer_3d_gather]: word buffers");
+  g->ion_gather_entry = true;
   IonGather G; G.words = dev_words; G.all = dev_words_all; G.nranks = nranks; G.fn = gather; G.ctx = ctx;
   int niter = 0, rc; double dt_done = 0.0;
   if ((rc = ion_run_fused(g, false, g->dt, &niter, &dt_done, G))) return rc;
@@ -1479,6 +1548,52 @@ int aa_test_ion_pick(int n, const double *rec, int first, double limit, int spec
   for (int k = 0; k < 3; k++) pick_scalars_to_row(h[k], out + (size_t)k*AA_TEST_PICK_SCALARS);
   hipFree(d);
   return 0;
+}
+
+// the sub-cycle loop with the stop rule on the device (ion_run_queued's visits) over a script: row 0 of `rec` is the record of the first
+// pass, row r that of the pass of sub-cycle r.  The first pick, then visits of b0, K, K ... queued picks (k_ion_reduce_pick_q over one
+// record each) with a publication behind the last pick of each and no passes in between, until the device says stop.  out: niter, dt_done,
+// stop code, visits, queued picks that left at once; steps: the applied steps in order (n doubles).
+int aa_test_ion_batch(int n, const double *rec, int fine, double limit, double cour_no, int K, int b0, double *out, double *steps)
+{
+  if (n < 2 || n > 4096) return fail(-1, "[aa_test_ion_batch]: n = %d", n);
+  if (K < 1 || K > AA_ION_BATCH_MAX || b0 < 1 || b0 > K) return fail(-1, "[aa_test_ion_batch]: K = %d, first visit %d", K, b0);
+  const size_t nrec = (size_t)n*sizeof(IonPart), nw = AA_ION_WORDS*sizeof(Real), nst = (size_t)(n + AA_ION_BATCH_MAX)*sizeof(Real);      // (a visit may book up to K - 1 sub-cycles past the script before the host sees it has run out)
+  char *d = nullptr;
+  Mailbox *mb = nullptr, *mb_dev = nullptr;
+  HIPCHK(hipMalloc(&d, nrec + nw + nst + sizeof(DevScalars)));
+  if (hipHostMalloc(&mb, sizeof(Mailbox), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer((void**)&mb_dev, mb, 0) != hipSuccess) { hipFree(d); return fail(-2, "[aa_test_ion_batch]: no mailbox"); }
+  memset(mb, 0, sizeof(Mailbox));
+  IonPart *part = (IonPart*)d;
+  Real *w = (Real*)(d + nrec), *st = (Real*)(d + nrec + nw);
+  DevScalars *sc = (DevScalars*)(d + nrec + nw + nst);
+  int rc = 0, visits = 0, queued = 0, b = b0;
+  unsigned long long seq = 0;
+  auto chk = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = fail(-2, "[aa_test_ion_batch]: HIP error %s", hipGetErrorString(e)); return e == hipSuccess; };
+  if (chk(hipMemcpy(part, rec, nrec, hipMemcpyHostToDevice)) && chk(hipMemset(w, 0, nw + nst + sizeof(DevScalars)))) {
+    launch_test_ion_reduce_pick(part, 1, w, sc, 1, limit, 0, 0);
+    for (;;) {
+      for (int i = 0; i < b; i++, queued++) {
+        const int row = (1 + queued < n) ? 1 + queued : n - 1;
+        launch_test_ion_reduce_pick_q(part + row, 1, w, sc, fine, limit, cour_no, st, i == b - 1 ? mb_dev : nullptr, i == b - 1 ? ++seq : 0ULL, 0);
+      }
+      if (!chk(hipDeviceSynchronize())) break;
+      visits++;
+      if (mb->seq != seq) { rc = fail(-2, "[aa_test_ion_batch]: visit %d ended without its stamp", visits); break; }
+      if (mb->s.ion_stop != 0) break;
+      if (1 + queued >= n) { rc = fail(-1, "[aa_test_ion_batch]: the script of %d rows ran out with the loop open", n); break; }
+      b = K;
+    }
+  }
+  if (!rc) {
+    const DevScalars &h = mb->s;
+    const int ran = h.ion_niter + (h.ion_stop == ION_STOP_NEG ? 1 : 0);
+    out[0] = h.ion_niter; out[1] = h.dt_done; out[2] = h.ion_stop; out[3] = visits; out[4] = queued - ran;
+    chk(hipMemcpy(steps, st, (size_t)n*sizeof(Real), hipMemcpyDeviceToHost));
+  }
+  hipHostFree(mb); hipFree(d);
+  return rc;
 }
 
 // ---- history sums (dump_history.c:157-200) ---------------------------------------------------

@@ -52,6 +52,11 @@ struct aa_grid {
   bool ion_step_spec = false, ion_step_lean = false;   // its first pass speculated / did so in the lean form
   int ion_step_updates = 0;            // updating passes queued since aa_ion_begin = sub-cycles
   bool ion_lean_next = false;          // ... and what aa_ion_finish made of it: the step speculated and took ONE sub-cycle, so the next one is lean under `auto`
+  // LaunchCfg ion_batch (api.hip ion_run_queued): sub-cycles of this Grid's previous ion step (0: none since aa_create, an upload or a
+  // restart section -- the first visit of the next one queues 1), and host visits / sub-cycles executed / queued sub-cycles that left at once
+  int ion_prev_niter = 0;
+  bool ion_gather_entry = false;       // the last ion step came through aa_ion_radtransfer_3d_gather (aa_ion_batch_active)
+  long long ion_batch_n[3] = {0, 0, 0};
   long long ion_lean_n[2] = {0, 0};    // speculating first passes queued so far: dense, lean (aa_ion_lean_counts)
   bool cfl_ready = false;              //   ... and has done so for the state as it is now (aa_step arms it by itself: LaunchCfg cfl_step)
   bool active_dirty = true;            // a call since the last full upload / download of U wrote ACTIVE zones on the device (aa_download_ghost_zones then moves the whole block)
@@ -275,7 +280,7 @@ void queue_chain_3d(aa_grid *g, const aa::Run3D *rc, aa::DevScalars *sc);
 void queue_bvals_3d(aa_grid *g);
 
 // new state from outside (an upload, a restart section): the next ion step's speculating entry is the dense one
-static inline void ion_lean_forget(aa_grid *g) { g->ion_lean_next = false; for (aa_grid *c : g->slab) c->ion_lean_next = false; }
+static inline void ion_lean_forget(aa_grid *g) { g->ion_lean_next = false; g->ion_prev_niter = 0; for (aa_grid *c : g->slab) c->ion_lean_next = false; }
 static inline double bits_to_double(unsigned long long b) { double x; memcpy(&x, &b, 8); return x; }
 static inline unsigned long long double_to_bits(double x) { unsigned long long b; memcpy(&b, &x, 8); return b; }
 // new_dt's maxima as the kernels left them, for time_step.h

@@ -89,6 +89,11 @@ struct DevScalars {
   // zones the update left with d < 0 (appended to the candidate list), whether a flux the update read was NaN, what the
   // fix kernel counted while it replayed the reference's scan, the fluxes k_fofc_nanfix replaced, list overflow
   int fofc_n, fofc_nanseen, fofc_negd, fofc_negP, fofc_nan, fofc_ovf;
+  // the sub-cycle loop's own words (LaunchCfg ion_batch; ion_subcycle.h ion_stop_rule): the first pick of an ion step clears them, a
+  // queued pick (k_ion_reduce_pick_q) applies the stop rule behind the update it books, and every queued kernel leaves at once
+  // where ion_stop is set.  ion_stop: 0 open, 1 stopped, 2 stopped and the level's step cut to dt_done, 3 negative dt_chem (the
+  // sub-cycle that met it is not counted); ion_niter: sub-cycles booked by queued picks
+  int ion_stop, ion_niter;
 };
 
 // what one block of k_ion_pass contributes to the reductions of a sub-cycle (all doubles: the record is
@@ -131,7 +136,9 @@ struct LaunchCfg {
   bool ion_spec_on = true;   // AA_ION_SPECULATE=0: the first pass of an ion step never applies an update
   int ion_lean = -1;         // AA_ION_LEAN: the speculating first pass without the entry's dense saves (k_ion_pass<LEAN>): auto (-1): behind a step
                              //   whose speculation stood after one sub-cycle; 0: never; 1: every speculating step
-  int dump_chunk = 1 << 23;  // AA_DUMP_CHUNK_FLOATS: floats per half of the dumps' bounce buffer (4 .. 2^28; dump.hip)
+  int ion_batch = 1;         // AA_ION_BATCH: radiation sub-cycles queued per host visit (1 .. 256; 1: one read-back per sub-cycle, launch for launch
+                             //   what it was; api.hip ion_run_fused)
+  int dump_chunk = 1 << 23; // AA_DUMP_CHUNK_FLOATS: floats per half of the dumps' bounce buffer (4 .. 2^28; dump.hip)
 };
 // the descriptor as the host keeps it: what the kernels get (DevGrid, passed by value: the launch slices it off) + the launch choices
 struct HostGrid : DevGrid { LaunchCfg cfg; unsigned long long *lean_mask = nullptr; };     // lean_mask: k_ion_pass<LEAN>, Nx2*Nx3*ceil(Nx1/64) words
@@ -191,6 +198,14 @@ void launch_ion_pick2(const Real *words, int nranks, DevScalars *sc, int first, 
 // one rank: the fold of the pass's records (k_ion_reduce) and the pick in ONE launch; launch_ion_pass(..., reduce = false) goes before it
 void launch_ion_reduce_pick(const HostGrid &g, const IonPart *part, Real *words, DevScalars *sc, int first, Real dt_limit, hipStream_t st, int spec_armed,
                             Mailbox *mb_dev = nullptr, unsigned long long seq = 0);      // mb_dev: also publish the scalars (stamp seq)
+// a QUEUED sub-cycle (LaunchCfg ion_batch): [the lean form's way back, if `redo`,] the updating pass in both forms, and the fold + pick
+// that also applies the loop's stop rule to the update it books (fine: a refined level; cour_no: dt_hydro = cour_no/max_dti) -- every
+// kernel of it leaves at once where sc->ion_stop is set; mb_dev: the pick also publishes the scalars, stopped or not (stamp seq)
+void launch_ion_subcycle_q(const HostGrid &g, const IonPar &p, bool redo, Real flux0, bool from_edgeflux, DevScalars *sc, int cur, IonPart *part,
+                           Real *words, int fine, Real dt_limit, Real cour_no, hipStream_t st, Mailbox *mb_dev, unsigned long long seq);
+// ... its pick alone over n records the caller wrote (function-level test); steps: where it books, the applied step goes to steps[ion_niter]
+void launch_test_ion_reduce_pick_q(const IonPart *part, int n, Real *words, DevScalars *sc, int fine, Real dt_limit, Real cour_no, Real *steps,
+                                   Mailbox *mb_dev, unsigned long long seq, hipStream_t st);
 void launch_ion_finish(const DevGrid &g, int cur, hipStream_t st);
 void launch_test_explog(int n, const Real *x, Real *ye, Real *yl, hipStream_t st);   // n a multiple of 4
 // function-level test of the folds: k_ion_reduce / k_ion_reduce_pick (no mailbox) over n records the caller wrote

@@ -35,6 +35,7 @@
 // tile kernel of ion_kernels.hip keeps the serial order and remains the path for short rays (Nx1 < 64).
 #include "ion_dev.h"
 #include "ion_tables.h"
+#include "ion_subcycle.h"
 
 namespace aa {
 
@@ -288,12 +289,17 @@ struct Ops { Real d, ke, E, s, fp, e0, x0, vm; unsigned short sg; bool saved; };
 // set, and then IS the non-speculating entry -- same source, same operands -- with every dense store, s_init among them, and
 // U's E and s put back to the floored entry values.  The updating pass behind it (spec_state still 2: from e_init / s_init)
 // finds what the dense form would have left.  Its block records go to a slot nobody folds: the pick has been made from the same numbers.
-template <bool UPD, bool SWP, bool BEG, bool LEAN = false>
+//   QUE: the entry of a QUEUED sub-cycle (LaunchCfg ion_batch: several sub-cycles per host visit), for the two updating forms and the
+// lean form's way back: it leaves at once where a queued pick has ended the loop (sc->ion_stop) and is otherwise the body as it
+// stands, gates included.  The five entries without it keep their instructions (DESIGN.md section 3 has the register table).
+template <bool UPD, bool SWP, bool BEG, bool LEAN = false, bool QUE = false>
 __global__ void __launch_bounds__(256, (UPD && SWP) ? AA_ION_PASS_WAVES : AA_ION_PASS_WAVES_HALF)
 k_ion_pass(DevGrid g, IonPar p_arg, Real flux0, int from_edgeflux, const DevScalars *sc, int cur, IonPart *part, int only_if_hit, Real spec_dt,
            unsigned long long *lmask)
 {
   static_assert(!LEAN || (BEG && SWP && !UPD), "the lean form is a first pass");
+  static_assert(!QUE || (UPD && !BEG) || LEAN, "queued: the updating forms and the lean form's way back");
+  if (QUE && sc->ion_stop != 0) return;
   // an updating pass is launched in both forms -- with and without the sweep of a further sub-cycle -- and the one
   // that does not match what the device picked (sc->limit_hit; the host has not read it yet) leaves at once
   if (UPD && only_if_hit >= 0 && (sc->limit_hit != 0) != (only_if_hit != 0)) return;
@@ -558,10 +564,17 @@ k_ion_reduce(const IonPart *part, int n, Real *words)
 AA_DEV void ion_pick_body(Real dt_chem, Real dt_therm, Real max_dti, Real count, Real neg, DevScalars *sc, int first, Real dt_limit, int spec_armed);
 // ... and, where ONE rank reduces alone, the pick of k_ion_pick2 by the same launch (the same fold, the same arithmetic): a sub-cycle
 // on a small Grid is a handful of launches and one read-back, and every launch less is ~5 us of 40
-__global__ void __launch_bounds__(256)
-k_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int first, Real dt_limit, int spec_armed, Mailbox *mb, unsigned long long seq)
+// QUE: the pick of a QUEUED sub-cycle (LaunchCfg ion_batch).  Where the loop has ended (sc->ion_stop) it folds nothing and books nothing;
+// otherwise it is the pick as it stands (first = 0) and then applies ion_stop_rule to the update it booked.  Either way it
+// publishes where mb is given: the last pick of a host visit carries the visit's ONE publication.
+AA_DEV void ion_stop_body(DevScalars *sc, int fine, Real cour_no, Real *steps);
+template <bool QUE>
+AA_DEV void ion_reduce_pick_body(const IonPart *part, int n, Real *words, DevScalars *sc, int first, Real dt_limit, int spec_armed, Mailbox *mb,
+                                 unsigned long long seq, int fine, Real cour_no, Real *steps)
 {
   __shared__ Real red[5][256];
+  const bool open = !QUE || sc->ion_stop == 0;      // (block-uniform; thread 0 writes the word behind the fold's barriers)
+  if (open) {
   Real a = DBL_MAX, b = DBL_MAX, c = 0.0, d = 0.0, e = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
     const IonPart r = part[i];
@@ -581,8 +594,11 @@ k_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int f
   }
   if (threadIdx.x < 8) words[threadIdx.x] = (threadIdx.x < 5) ? red[threadIdx.x][0] : 0.0;
   // (one rank: k_ion_pick2's fold over ranks is MIN / MAX / + of one operand with its neutral element: the operand itself)
-  if (threadIdx.x == 0)
+  if (threadIdx.x == 0) {
     ion_pick_body(rmin(DBL_MAX, red[0][0]), rmin(DBL_MAX, red[1][0]), rmax(0.0, red[2][0]), 0.0 + red[3][0], rmax(0.0, red[4][0]), sc, first, dt_limit, spec_armed);
+    if (QUE) ion_stop_body(sc, fine, cour_no, steps);
+  }
+  }
   if (mb) {      // ... and the scalars straight into the host's mailbox (grid.h Mailbox, k_publish): the read-back that follows needs no launch
     __threadfence(); __syncthreads();
     constexpr int nw = (int)(sizeof(DevScalars)/sizeof(unsigned long long));
@@ -593,6 +609,12 @@ k_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int f
     if (threadIdx.x == 0) __hip_atomic_store(&mb->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
+__global__ void __launch_bounds__(256)
+k_ion_reduce_pick(const IonPart *part, int n, Real *words, DevScalars *sc, int first, Real dt_limit, int spec_armed, Mailbox *mb, unsigned long long seq)
+{ ion_reduce_pick_body<false>(part, n, words, sc, first, dt_limit, spec_armed, mb, seq, 0, 0.0, nullptr); }
+__global__ void __launch_bounds__(256)
+k_ion_reduce_pick_q(const IonPart *part, int n, Real *words, DevScalars *sc, Real dt_limit, Mailbox *mb, unsigned long long seq, int fine, Real cour_no, Real *steps)
+{ ion_reduce_pick_body<true>(part, n, words, sc, 0, dt_limit, 0, mb, seq, fine, cour_no, steps); }
 
 // ionrad_3d.c:941-967 on the device, over the words of all ranks (AA_ION_WORDS doubles each; one rank: the
 // Grid's own): dt = MIN(dt_therm, dt_chem) cut back to what is left of the hydro step (root) or of the
@@ -625,6 +647,19 @@ AA_DEV void ion_pick_body(Real dt_chem, Real dt_therm, Real max_dti, Real count,
   sc->dt_sel = dt; sc->limit_hit = hit;
   sc->spec_state = (first && spec_armed) ? (hit ? 1 : 2) : 0;      // (see k_ion_pass)
   sc->dt_chem_out = dt_chem; sc->dt_therm_out = dt_therm; sc->neg_out = (neg != 0.0);
+  if (first) { sc->ion_stop = 0; sc->ion_niter = 0; }      // (the loop's own words: ion_stop_body)
+}
+// ionrad_3d.c:982-1012 behind the update ion_pick_body has just booked, on its operands as the host would read them back (aa_ion_fetch):
+// a negative dt_chem behind the applied step ends the loop uncounted, as the host's loop returns in front of the rule; dt_hydro is
+// the host's ONE IEEE division cour_no/max_dti
+AA_DEV void ion_stop_body(DevScalars *sc, int fine, Real cour_no, Real *steps)
+{
+#pragma clang fp contract(off)
+  if (sc->neg_applied) { sc->ion_stop = ION_STOP_NEG; return; }
+  const Real dt_hydro = cour_no/__longlong_as_double((long long)sc->max_dti);
+  if (steps) steps[sc->ion_niter] = sc->dt_applied;
+  sc->ion_niter = sc->ion_niter + 1;
+  sc->ion_stop = ion_stop_rule(fine, sc->hit_applied, (long long)sc->cellcount, dt_hydro, sc->dt_done);
 }
 
 // GridS.EdgeFlux of the last sweep that counted: [k][j][0..Nx1-1] = the flux that entered each zone,
@@ -728,6 +763,19 @@ void launch_ion_lean_redo(const HostGrid &g, const IonPar &p, Real flux0, bool f
 {
   hipLaunchKernelGGL((k_ion_pass<false, true, true, true>), dim3(ion_pass_blocks(g)), dim3(256), 0, st, g, p, flux0, from_edgeflux ? 1 : 0, sc, cur, scratch, -1, -1.0, g.lean_mask);
 }
+void launch_ion_subcycle_q(const HostGrid &g, const IonPar &p, bool redo, Real flux0, bool from_edgeflux, DevScalars *sc, int cur, IonPart *part,
+                           Real *words, int fine, Real dt_limit, Real cour_no, hipStream_t st, Mailbox *mb_dev, unsigned long long seq)
+{
+  const int nb = ion_pass_blocks(g), fe = from_edgeflux ? 1 : 0;
+  const dim3 grid(nb), blk(256);
+  if (redo) hipLaunchKernelGGL((k_ion_pass<false, true, true, true, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur ^ 1, part + nb, -1, -1.0, g.lean_mask);
+  hipLaunchKernelGGL((k_ion_pass<true, true, false, false, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 0, -1.0, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL((k_ion_pass<true, false, false, false, true>), grid, blk, 0, st, g, p, flux0, fe, sc, cur, part, 1, -1.0, (unsigned long long*)nullptr);
+  hipLaunchKernelGGL(k_ion_reduce_pick_q, dim3(1), dim3(256), 0, st, part, nb, words, sc, dt_limit, mb_dev, seq, fine, cour_no, (Real*)nullptr);
+}
+void launch_test_ion_reduce_pick_q(const IonPart *part, int n, Real *words, DevScalars *sc, int fine, Real dt_limit, Real cour_no, Real *steps,
+                                   Mailbox *mb_dev, unsigned long long seq, hipStream_t st)
+{ hipLaunchKernelGGL(k_ion_reduce_pick_q, dim3(1), dim3(256), 0, st, part, n, words, sc, dt_limit, mb_dev, seq, fine, cour_no, steps); }
 void launch_ion_pick2(const Real *words, int nranks, DevScalars *sc, int first, Real dt_limit, hipStream_t st, int spec_armed)
 { hipLaunchKernelGGL(k_ion_pick2, dim3(1), dim3(1), 0, st, words, nranks, sc, first, dt_limit, spec_armed); }
 void launch_ion_finish(const DevGrid &g, int cur, hipStream_t st)

@@ -5,6 +5,7 @@
  * kernel or two, the step picked on the device or on the host, one Grid or a Grid cut into slabs -- the stop rules, their order
  * and the bookkeeping are the ones written here, once:
  *   ion_pick_step   :941-962   the step of a sub-cycle, cut back to what is left of the limit
+ *   ion_stop_rule   :982-1012  whether the loop goes on behind a sub-cycle (host and device: the queued pick of ion_pass.hip calls it too)
  *   ion_subcycles   :919-1012  the loop around a callable that performs one sub-cycle
  *   ion_close_root  :1017-1029 and :1044, what the root level does behind its loop
  * (driver.py holds the same three for the Python drivers; tests/test_ion_subcycles.py runs one table of cases through both.)
@@ -21,6 +22,28 @@ static inline double ion_pick_step(double dt_chem, double dt_therm, double dt_do
   *hit = 0;
   if (dt_done + dt > limit) { dt = limit - dt_done; *hit = 1; }
   return dt;
+}
+
+#ifdef __HIPCC__
+#define ION_FN static inline __host__ __device__
+#else
+#define ION_FN static inline
+#endif
+
+/* :982-1012 behind a sub-cycle, in the reference's order: `hit` = its step was cut back to the limit, `cellcount` and `dt_hydro` the
+ * operands check_range and compute_dt_hydro found behind its update, `dt_done` the time covered with it.  Root: more than
+ * AA_MAXCELLCOUNT cells out of range cut the step (:982-986), else a covered step ends the loop (:989-992), else dt_hydro < dt_done
+ * cuts (:997-1002).  A refined level looks at `hit` alone and always takes the cut (:1008-1012). */
+enum { ION_GO_ON = 0, ION_STOP = 1, ION_STOP_CUT = 2, ION_STOP_NEG = 3 };      /* (3: a negative dt_chem ended the loop in front of the rule) */
+ION_FN int ion_stop_rule(int fine, int hit, long long cellcount, double dt_hydro, double dt_done)
+{
+  if (!fine) {
+    if (cellcount > AA_MAXCELLCOUNT) return ION_STOP_CUT;
+    if (hit) return ION_STOP;
+    if (dt_hydro < dt_done) return ION_STOP_CUT;
+    return ION_GO_ON;
+  }
+  return hit ? ION_STOP_CUT : ION_GO_ON;
 }
 
 struct IonSubcycles {
@@ -44,11 +67,8 @@ static inline IonSubcycles ion_subcycles(bool fine, One &&one)
     if ((r.rc = one(r.dt_done, &dt, &hit, &cellcount, &dt_hydro))) break;
     r.dt_done += dt;                                                      /* :966-967 */
     r.niter++;
-    if (!fine) {
-      if (cellcount > AA_MAXCELLCOUNT) { r.cut = true; break; }           /* :982-986 check_range */
-      if (hit) break;                                                     /* :989-992 the whole hydro step is covered */
-      if (dt_hydro < r.dt_done) { r.cut = true; break; }                  /* :997-1002 */
-    } else if (hit) { r.cut = true; break; }                              /* :1008-1012 tcoarse is covered */
+    const int stop = ion_stop_rule(fine, hit, cellcount, dt_hydro, r.dt_done);
+    if (stop != ION_GO_ON) { r.cut = (stop == ION_STOP_CUT); break; }
   }
   return r;
 }

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import warnings
 from typing import List, Optional
 
 import numpy as np
@@ -423,13 +424,19 @@ class _Runner:
         _outputs.run(self, outputs, self.run.tlim, self.run.nlim)
 
 
+_ION_BATCH_WARNED = False      # Driver(ion_batch=...) with several ranks warns once per process
+
+
 class Driver(_Runner):
     """main() of the reference for one process of an N-process run."""
 
     def __init__(self, run: RunConfig, engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0,
-                 strict: Optional[bool] = None, p2: int = 1, initial: bool = True):
+                 strict: Optional[bool] = None, p2: int = 1, initial: bool = True, ion_batch: Optional[int] = None):
         """p2 > 1: an NGrid_x2 x NGrid_x3 = p2 x (nranks / p2) pencil decomposition (init_mesh.c:526-620) instead of x3 slabs;
-        initial = False: the product engine skips the problem generator (from_restart loads the state)"""
+        initial = False: the product engine skips the problem generator (from_restart loads the state);
+        ion_batch = K (1 .. 256; None: nothing changes): on one rank with an engine on a device the ion step is the library's loop
+        (lib.Grid.ion_radtransfer_3d) with K sub-cycles queued per host visit (lib.Grid.set_ion_batch) instead of the loop written
+        here; same bits.  With several ranks the keyword warns once and the step stays what it was."""
         self.run = run
         self.rank, self.nranks = rank, nranks
         if p2 < 1 or nranks % p2:
@@ -447,6 +454,16 @@ class Driver(_Runner):
         self._hst = {}            # HistoryWriter per <outputN> block with out_fmt = hst
         self._halo = {}           # messages in flight per axis (2: x2, 3: x3): post .. finish
         self._init_collectives(rank, nranks)
+        self.ion_batch = None
+        if ion_batch is not None:
+            global _ION_BATCH_WARNED
+            if nranks > 1:
+                if not _ION_BATCH_WARNED:
+                    warnings.warn("Driver(ion_batch=...): several ranks reduce every sub-cycle over the ranks; the keyword is ignored")
+                    _ION_BATCH_WARNED = True
+            elif hasattr(getattr(self.eng, "g", None), "set_ion_batch"):
+                self.eng.g.set_ion_batch(ion_batch)
+                self.ion_batch = int(ion_batch)
 
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
@@ -709,6 +726,12 @@ class Driver(_Runner):
 
     def ion_radtransfer(self) -> int:   # ionrad_3d.c:862-1047, root level
         e = self.eng
+        if self.ion_batch is not None and not self.distributed:
+            # the loop inside the library (aa_ion_radtransfer_3d: K sub-cycles per host visit where the Grid takes them); the
+            # step it may have cut comes back as the gather branch's does
+            niter = e.g.ion_radtransfer_3d()
+            self.dt = e.mesh_state()[1]
+            return niter
         if getattr(e, "ion_fused", False):
             return self._ion_radtransfer_fused()
         limit = self.dt
@@ -836,8 +859,10 @@ class MeshRun(_Runner):
     aa_mesh_step): what outputs.run / OutputSet.data_output need -- time, nstep, start, step and the three writers, which loop
     over the Domains like dump_vtk / dump_binary / dump_history / dump_restart do."""
 
-    def __init__(self, mesh, run: RunConfig, nslab: int = 1, cuts=None, device: int = 0, strict: Optional[bool] = None):
-        """mesh: a lib.Mesh, or the levels (config.levels) to build one from -- with nslab > 1 / cuts every level cut at the
+    def __init__(self, mesh, run: RunConfig, nslab: int = 1, cuts=None, device: int = 0, strict: Optional[bool] = None,
+                 ion_batch: Optional[int] = None):
+        """ion_batch = K: lib.Mesh.set_ion_batch(K), the radiation sub-cycles every level queues per host visit (None: untouched).
+        mesh: a lib.Mesh, or the levels (config.levels) to build one from -- with nslab > 1 / cuts every level cut at the
         same root x3 planes inside the library, one slab stack per GPU; the outputs go through the composite level handles
         as they are (hst per level, bin / vtk under lev<l>/, one .rst with all levels)."""
         config.check_1d(run, mesh=True)      # (ParError: a 1-D run has no Mesh)
@@ -845,6 +870,8 @@ class MeshRun(_Runner):
             from . import lib
             mesh = lib.Mesh(list(mesh), device, strict, nslab=nslab, cuts=cuts)
         self.mesh, self.run = mesh, run
+        if ion_batch is not None:
+            mesh.set_ion_batch(ion_batch)
         self._hst = {}
         self.restarted = False
         self.par = None

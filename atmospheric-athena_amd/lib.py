@@ -113,6 +113,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_ion_update": (I, [P, D, llp, dp]),
         "aa_ion_is_fused": (I, [P]), "aa_ion_speculate": (I, [P, D]), "aa_ion_pass": (I, [P, I, I, P]), "aa_ion_pick": (I, [P, P, I, I, D]),
         "aa_ion_fetch": (I, [P, dp, ip, dp, dp, llp, dp, ip]), "aa_ion_finish": (I, [P]), "aa_ion_lean_counts": (I, [P, llp]),
+        "aa_set_ion_batch": (I, [P, I]), "aa_ion_batch": (I, [P]), "aa_ion_batch_active": (I, [P]), "aa_ion_batch_counts": (I, [P, llp]),
         "aa_ion_radtransfer_3d_gather": (I, [P, P, P, I, GATHER, P, ip]), "aa_host_syncs": (I, [P, I]),
         "aa_halo_doubles": (LL, [P]), "aa_pack_x3": (I, [P, I, P]), "aa_unpack_x3": (I, [P, I, P]),
         "aa_halo_doubles_x2": (LL, [P]), "aa_pack_x2": (I, [P, I, P]), "aa_unpack_x2": (I, [P, I, P]),
@@ -133,6 +134,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_test_lr_states_ppm": (I, [I, D, I, dp, D, D, I, I, dp, dp]),
         "aa_test_explog": (I, [I, dp, dp, dp]),
         "aa_test_ion_pick": (I, [I, dp, I, D, I, dp, dp, dp]),
+        "aa_test_ion_batch": (I, [I, dp, I, D, D, I, I, dp, dp]),
         "aa_test_xdiv": (I, [I, dp, dp, dp]),
         "aa_history": (I, [P, dp]),
         "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),
@@ -572,6 +574,24 @@ class Grid:
         self._chk(self.L.aa_ion_lean_counts(self._h, n))
         return tuple(int(v) for v in n)
 
+    def set_ion_batch(self, k: int):
+        """radiation sub-cycles queued per host visit (1 .. 256; AA_ION_BATCH when the Grid was made, default 1 = a read-back per
+        sub-cycle): with k > 1 the library's loop (ion_radtransfer_3d, step) applies the stop tests on the device.  Same bits."""
+        self._chk(self.L.aa_set_ion_batch(self._h, int(k)))
+
+    @property
+    def ion_batch(self) -> int: return int(self.L.aa_ion_batch(self._h))
+
+    def ion_batch_active(self) -> bool:
+        """whether this Grid's ion step takes the queued loop: ion_batch > 1 on the one-kernel sub-cycle with the fused pick, one device"""
+        return bool(self.L.aa_ion_batch_active(self._h))
+
+    def ion_batch_counts(self):
+        """(host visits, sub-cycles executed, queued sub-cycles that left at once) of the queued loop since the Grid was made"""
+        n = (C.c_longlong * 3)()
+        self._chk(self.L.aa_ion_batch_counts(self._h, n))
+        return tuple(int(v) for v in n)
+
     def ion_radtransfer_3d_gather(self, dev_words: int, dev_words_all: int, nranks: int, gather) -> int:
         """ion_radtransfer_3d of one rank of a multi-rank run in ONE call: `gather()` is the driver's all-gather of the
         AA_ION_WORDS doubles at dev_words into dev_words_all, called once per pass on this Grid's stream."""
@@ -963,6 +983,11 @@ class Mesh:
         n = C.c_int(); self._chk(self.L.aa_mesh_ion_radtransfer(self._h, level, C.byref(n))); return n.value
 
     def ionflux_prolong(self, level: int): self._chk(self.L.aa_mesh_ionflux_prolong(self._h, level))
+
+    def set_ion_batch(self, k: int):
+        """Grid.set_ion_batch on every level"""
+        for g in self.lev:
+            g.set_ion_batch(k)
 
     def start(self):
         self._chk(self.L.aa_mesh_start(self._h)); return self

@@ -250,6 +250,21 @@ int aa_ion_finish(aa_grid *g);
 /* The speculating first pass has two forms (AA_ION_LEAN; same results bit for bit): n[0], n[1] = first passes queued so far in the dense
  * and in the lean form, n[2] = lean ones the pick refuted, which were then redone densely.  Waits for the Grid's stream.            */
 int aa_ion_lean_counts(aa_grid *g, long long *n);
+/* Sub-cycles per host visit.  aa_ion_radtransfer_3d, aa_step and every level of an aa_mesh run the loop above inside the library;
+ * with K = ion_batch > 1 the stop tests (:982-1012) are applied on the device by the pick itself, a visit queues up to K
+ * sub-cycles whose kernels leave at once behind a stop, and the host reads back once per visit instead of once per sub-cycle.
+ * Same results bit for bit.  The first visit of an ion step is as long as the Grid's previous ion step was (at most K; 1 after
+ * aa_create, an upload or a restart section), so a step behind a one-sub-cycle step makes the launches it made with K = 1.
+ * K: AA_ION_BATCH in the environment at aa_create, 1 .. AA_ION_BATCH_MAX, default 1 = a read-back per sub-cycle; anything else
+ * is refused.  Taken by Grids that run the one-kernel sub-cycle on one device with the fused pick (aa_ion_batch_active); the
+ * others -- the two-kernel sub-cycle, AA_ION_FUSE_PICK=0, a Grid cut into slabs, aa_ion_radtransfer_3d_gather -- keep the
+ * per-sub-cycle loop whatever K is.  aa_ion_batch_counts: n[0] host visits, n[1] sub-cycles executed, n[2] queued sub-cycles
+ * that left at once, of the queued loop since aa_create. */
+#define AA_ION_BATCH_MAX 256
+int aa_set_ion_batch(aa_grid *g, int k);
+int aa_ion_batch(const aa_grid *g);
+int aa_ion_batch_active(const aa_grid *g);
+int aa_ion_batch_counts(const aa_grid *g, long long *n);
 /* ion_radtransfer_3d (ionrad_3d.c:862-1047, root level) of a rank of a multi-rank run in ONE call: the loop above with the
  * driver's collective as a callback.  `gather(ctx)` must all-gather this rank's AA_ION_WORDS doubles at dev_words into
  * dev_words_all (nranks x AA_ION_WORDS, DEVICE memory) on the Grid's stream and return 0; it is called once per pass, between
@@ -395,6 +410,11 @@ int aa_test_explog(int n, const double *x, double *y_exp, double *y_log);  /* th
  * cellcount, dt_chem, dt_therm (the doubles whose bits the words hold), neg_dt_chem, 0. */
 #define AA_TEST_PICK_SCALARS 16
 int aa_test_ion_pick(int n, const double *rec, int first, double limit, int spec_armed, const double *prev, double *words, double *out);
+/* The queued sub-cycle loop (aa_set_ion_batch) over a script, on scratch memory: rec[n][5] = the record of the first pass and of
+ * the pass of every further sub-cycle.  The first pick, then visits of b0, K, K, ... queued picks with one publication each and no
+ * passes in between, until the device stops the loop (an error if the script runs out first).  out[5] = niter, dt_done, stop code
+ * (1 stopped, 2 stopped and cut, 3 negative dt_chem), visits, queued picks that left at once; steps[n]: the applied steps in order. */
+int aa_test_ion_batch(int n, const double *rec, int fine, double limit, double cour_no, int K, int b0, double *out, double *steps);
 
 /* ---- dump_history.c:157-200: volume integrals over the active zones of this Grid, in the column
  *      order of the .hst file: mass, total E, x1/x2/x3 Mom., x1/x2/x3-KE, scalar 0 (0 if NSCALARS=0).
