@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include "field_offsets.h"
 #include <string>
 #include <thread>
 #include <vector>
@@ -214,6 +215,11 @@ int aa_create(const aa_params *p, aa_grid **out)
   // active zones 64 at a time (-2.9 % of a 512^3 step; AA_PITCH_ALIGN=0: dense rows)
   const int pitch_align = d.cfg.pitch_align;
   d.sJ = pitch_align ? ((d.N1 + 15)/16)*16 : d.N1; d.sK = (long)d.sJ*d.N2; d.nc = d.sK*d.N3;
+  // the marching 3-D kernels reach a zone by a 32-bit byte offset from its field's base (field_offsets.h): one code path, no fallback
+  if (!one_d && !two_d && !field_offsets_fit(d.nc, d.sJ, d.sK)) {
+    const long nc = d.nc; delete g;
+    return fail(-1, "[aa_create]: a Grid of %ld zones (ghost zones and row padding included): a field of more than 2^32 bytes is beyond the kernels' 32-bit zone offsets", nc);
+  }
   if (p->level < 0 || p->level > 7) { delete g; return fail(-1, "[aa_create]: level %d out of range", p->level); }
   g->level = p->level;
   Real rootdx[3];
@@ -1486,6 +1492,39 @@ int aa_test_xdiv(int n, const double *a, const double *b, double *out)
 }
 
 // exp / log of the one-kernel sub-cycle (ion_pass.hip) on n values (n a multiple of 4): ye = exp(x), yl = ln|x|
+// the marching kernels' zone accessors at byte offsets 0, 2^31 - 8, 2^31 and 2^32 - 8 of a field of 4 GiB (k_test_zone_offsets).
+// The field lies 2^31 bytes inside its allocation: an offset that a faulty accessor sign-extended (or cut to 31 bits) still lands in
+// memory this call owns, and shows as a word missing where the host looks for it.
+int aa_test_zone_offsets(unsigned stride_bytes, double *stored, double *loaded)
+{
+  if (!stored || !loaded) return fail(-1, "[aa_test_zone_offsets]: null argument");
+  if (stride_bytes % 8u || stride_bytes > (1u << 30)) return fail(-1, "[aa_test_zone_offsets]: stride of %u bytes: a multiple of 8 up to 2^30", stride_bytes);
+  const unsigned off[4] = {0u, 0x7ffffff8u, 0x80000000u, 0xfffffff8u};
+  const size_t front = (size_t)1 << 31, field = (size_t)1 << 32;
+  char *pool = nullptr;
+  Real *out = nullptr;
+  hipError_t e = hipMalloc(&pool, front + field + (size_t)stride_bytes + 64);
+  if (e != hipSuccess) return fail(-2, "[aa_test_zone_offsets]: hipMalloc of 6.5 GB failed: %s", hipGetErrorString(e));
+  if (hipMalloc(&out, 12*sizeof(Real)) != hipSuccess) { hipFree(pool); return fail(-2, "[aa_test_zone_offsets]: hipMalloc"); }
+  char *base = pool + front;
+  int rc = 0;
+  for (int l = 0; l < 4 && !rc; l++)
+    for (int s = 0; s < 2 && !rc; s++)
+      if (hipMemset(base + (size_t)off[l] + (s ? (size_t)stride_bytes : 0), 0, sizeof(Real)) != hipSuccess) rc = -2;
+  if (!rc && hipMemset(out, 0, 12*sizeof(Real)) != hipSuccess) rc = -2;
+  if (!rc) {
+    launch_test_zone_offsets((Real *)base, off, stride_bytes, 0, out, 0);
+    launch_test_zone_offsets((Real *)base, off, stride_bytes, 1, out, 0);
+    if (hipDeviceSynchronize() != hipSuccess) rc = -2;
+  }
+  for (int l = 0; l < 4 && !rc; l++)
+    for (int s = 0; s < 2 && !rc; s++)
+      if (hipMemcpy(stored + 4*s + l, base + (size_t)off[l] + (s ? (size_t)stride_bytes : 0), sizeof(Real), hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  if (!rc && hipMemcpy(loaded, out, 12*sizeof(Real), hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+  hipFree(out); hipFree(pool);
+  return rc ? fail(rc, "[aa_test_zone_offsets]: %s", hipGetErrorString(hipGetLastError())) : 0;
+}
+
 int aa_test_explog(int n, const double *x, double *ye, double *yl)
 {
   if (n <= 0 || n % 4) return fail(-1, "[aa_test_explog]: n must be a positive multiple of 4");

@@ -21,18 +21,28 @@ k_x1_edge_flux(DevGrid g, Real dt)
   const int j = g.js - 1 + blockIdx.x*64 + threadIdx.x, k = g.ks - 1 + blockIdx.y, b = 1 + blockIdx.z;
   if (j > g.je + 1) return;
   const int nbe = x1_edges(g), i0 = g.is - 16 + 64*b;
-  const long m = (long)k*g.sK + (long)j*g.sJ + i0;
+  // (zone i0-1 as the fields moved one zone down: its x1 neighbours stay in the immediates)
+  const ZStr z = zone_strides(g);
+  const unsigned mb = zone_off((long)k*g.sK + (long)j*g.sJ + i0);
   Real wa[6], wb[6], wc[6], wd[6], wl[6], wr[6], wx[6];
-  load_prim_sweep<NS, 0>(g, m - 2, wa); load_prim_sweep<NS, 0>(g, m - 1, wb);
-  load_prim_sweep<NS, 0>(g, m, wc);     load_prim_sweep<NS, 0>(g, m + 1, wd);
-  cell_recon<NS, 0, GRAV, ORD>(g, m - 1, dt, wa, wb, wc, wl, wx);      // zone i0-1: its left state belongs to face i0
-  cell_recon<NS, 0, GRAV, ORD>(g, m, dt, wb, wc, wd, wx, wr);          // zone i0: its right state
+  load_prim_sweep<NS, 0>(g, z, mb, -2, wa); load_prim_sweep<NS, 0>(g, z, mb, -1, wb);
+  load_prim_sweep<NS, 0>(g, z, mb, 0, wc);  load_prim_sweep<NS, 0>(g, z, mb, 1, wd);
+  cell_recon<NS, 0, GRAV, ORD>(g, z, -8L, mb, dt, wa, wb, wc, wl, wx);      // zone i0-1: its left state belongs to face i0
+  cell_recon<NS, 0, GRAV, ORD>(g, z, 0L, mb, dt, wb, wc, wd, wx, wr);       // zone i0: its right state
   Real ul[6], ur[6], f[6];
   prim_to_cons<NS>(wl, ul, g.Gamma_1, g.rGamma_1);
   prim_to_cons<NS>(wr, ur, g.Gamma_1, g.rGamma_1);
   flux_roe<NS>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
+  // (the edge array is [variable][edge][k][j]: the variable on the base, the rest -- 1/64 of a field -- in the offset)
+  unsigned ev8 = (unsigned)nbe*(unsigned)g.N3*(unsigned)g.N2*8u;
+  asm volatile("" : "+s"(ev8));
+  const unsigned eb = zone_off(x1_edge_index(g, nbe, 0, b, j, k));
+  Real fg[6];
 #pragma unroll
-  for (int n = 0; n < 5 + NS; n++) g.F[x1_edge_index(g, nbe, gv<0>(n), b, j, k)] = f[n];
+  for (int n = 0; n < 6; n++) fg[gv<0>(n)] = f[n];
+  FBase fb = (FBase)g.F;
+#pragma unroll
+  for (int v = 0; v < 5 + NS; v++) { zpw(fb, eb)[0] = fg[v]; fb = fup(fb, ev8); }
 }
 template <int NS, bool GRAV, int ORD, bool X3F>
 __global__ void __launch_bounds__(64*CA_TJ, (X3F && NS && GRAV) ? 2 : 1)
@@ -118,8 +128,8 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
   }
 #pragma nounroll
   for (int k = kbeg; k <= k1; k++) {
-    long m = (long)k*g.sK + mcol;
-    asm volatile("" : "+v"(m));                   // one index for all fields (see k_flux2_update)
+    const ZStr z = zone_strides(g);               // the scalar-base accessors (hydro_kernels.hip, field accessors)
+    const unsigned mb = zone_off((long)k*g.sK + mcol);      // one 32-bit offset for all fields (see k_flux2_update)
     const bool full = (k >= k0);                  // block-uniform; the provider plane does x3 only
     const int pk = (k & 1) ? 12 : 0;              // X3F: the s_park slots of zone k (those of zone k+1: 12 - pk)
     const bool zone = (k >= kstart);              // block-uniform; X3F: the two planes before do the first pass only
@@ -161,13 +171,13 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
       for (int n = 0; n < 6; n++) { wc[n] = wn[n]; wn[n] = wn2[n]; }
       if constexpr (PARK2) { pc0 = s_pp[0][row][lane]; pc1 = s_pp[1][row][lane]; s_pp[0][row][lane] = s_pp[2][row][lane]; s_pp[1][row][lane] = s_pp[3][row][lane]; }
       else { pc0 = pn0; pc1 = pn1; pn0 = pn20; pn1 = pn21; }
-      load_prim3<NS>(g, m + 2*g.sK, wn2, pn20, pn21);
+      load_prim3<NS>(g, z, 2L*z.sK8, mb, wn2, pn20, pn21);
       if constexpr (PARK2) { s_pp[2][row][lane] = pn20; s_pp[3][row][lane] = pn21; }
       if (do3) {
         {   // (A) zone k+1 along x3
           Real wm[6], ws[6], wp[6];
           to_sweep<2>(wc, wc[4], wm); to_sweep<2>(wn, wn[4], ws); to_sweep<2>(wn2, wn2[4], wp);
-          cell_recon<NS, 2, GRAV, ORD>(g, m + g.sK, dt, sr.dtodx[2], wm, ws, wp, wlN, wrN);
+          cell_recon<NS, 2, GRAV, ORD>(g, z, (long)z.sK8, mb, dt, sr.dtodx[2], wm, ws, wp, wlN, wrN);
         }
         // (the states of zone k+1 go to their slots before (B): the left one is not needed in it)
 #pragma unroll
@@ -192,7 +202,7 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
 #pragma unroll
       for (int n = 0; n < 6; n++) { wm3[n] = wc[n]; wc[n] = wn[n]; }
       pc0 = pn0; pc1 = pn1;
-      load_prim3<NS>(g, m + g.sK, wn, pn0, pn1);
+      load_prim3<NS>(g, z, (long)z.sK8, mb, wn, pn0, pn1);
     }
     if (!X1F && full) {
       if (lane < 12) {
@@ -209,8 +219,10 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
 #pragma unroll
     for (int v = 0; v < 6; v++) { eb0[v] = 0.0; eb1[v] = 0.0; }
     if (EARLY_F && zone) {
+      FBase b = fbase(g.F, z, 6);
+      const unsigned o = zsite(mb, b);
 #pragma unroll
-      for (int v = 0; v < NV; v++) { eb0[v] = Ff(g, 1, v)[m]; eb1[v] = Ff(g, 1, v)[m + g.sJ]; }
+      for (int v = 0; v < NV; v++) { eb0[v] = zp(b, o)[0]; eb1[v] = zp(fup(b, z.sJ8), o)[0]; b = fnext(b, z); }
     }
     if (X1F && zone) {   // ---- the x1 first pass, before anything else of the zone is formed: its fluxes correct the x2 and x3 states ----
       if (lane < 24) s_h1[row][lane] = hv1;
@@ -229,10 +241,12 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
         for (int v = 0; v < 6; v++) { if (lane == 0) wm[v] = wh[v]; else wp[v] = wh[v]; }
       }
       if (GRAV) {      // (the zone's kicks along x1; formed again with the others below)
-        const Real phic = Pf(g, 0)[m], phir = Pf(g, 1)[m + stride_rt(g, 0)], phil = Pf(g, 1)[m], dtodx = sr.dtodx[0];
+        const FBase p1 = fbase(g.phi, z, 1);
+        const unsigned o = zsite(mb, p1);
+        const Real phic = zp((FBase)g.phi, o)[0], phir = zp(p1, o)[1], phil = zp(p1, o)[0], dtodx = sr.dtodx[0];
         cf.kl[0] = dtodx*(phir - phic); cf.kr[0] = dtodx*(phic - phil);
       }
-      cell_recon<NS, 0, GRAV, ORD>(g, m, dt, sr.dtodx[0], cf, wm, ws, wp, wl1, wr1);
+      cell_recon<NS, 0, GRAV, ORD>(g, z, mb, dt, sr.dtodx[0], cf, wm, ws, wp, wl1, wr1);
       {   // first-pass flux of the zone's upper face (face_work<MODE_FLUX1>): its right state is the lane above's
         Real wrE[6], ul[6], ur[6], f[6];
 #pragma unroll
@@ -253,27 +267,37 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     }
     if (full) {
       if (edge_row) {
-        const long m2 = (row == 0) ? m - g.sJ : m + g.sJ;
+        // (a wavefront is one thread row: which neighbour row it fetches is uniform and goes on the base)
+        FBase b = __builtin_amdgcn_readfirstlane(row) == 0 ? fdn((FBase)g.U, z.sJ8) : fup((FBase)g.U, z.sJ8);
+        Real t[6];
+        const unsigned o = zsite(mb, b);
 #pragma unroll
-        for (int v = 0; v < NV; v++) hv2[v] = Uf(g, gv<1>(v))[m2];
+        for (int v = 0; v < 6; v++) { t[v] = (v < NV) ? zp(b, o)[0] : 0.0; b = fnext(b, z); }
+#pragma unroll
+        for (int v = 0; v < NV; v++) hv2[v] = t[gv<1>(v)];
       }
     }
     if (zone) {
+    FBase fa = (FBase)g.F, fb2 = fbase(g.F, z, 6), fc = fup(fbase(g.F, z, 12), z.sK8);
+    const unsigned o = zsite(mb, fb2);
 #pragma unroll
     for (int v = 0; v < NV; v++) {
-      const Real a0 = X1F ? 0.0 : Ff(g, 0, v)[m], a1 = X1F ? 0.0 : Ff(g, 0, v)[m + 1];
-      const Real b0 = EARLY_F ? eb0[v] : Ff(g, 1, v)[m], b1 = EARLY_F ? eb1[v] : Ff(g, 1, v)[m + g.sJ];
-      const Real c0 = f3[v], c1 = X3F ? f3n[v] : Ff(g, 2, v)[m + g.sK];
+      const Real a0 = X1F ? 0.0 : zp(fa, o)[0], a1 = X1F ? 0.0 : zp(fa, o)[1];
+      const Real b0 = EARLY_F ? eb0[v] : zp(fb2, o)[0], b1 = EARLY_F ? eb1[v] : zp(fup(fb2, z.sJ8), o)[0];
+      const Real c0 = f3[v], c1 = X3F ? f3n[v] : zp(fc, o)[0];
+      fa = fnext(fa, z); fb2 = fnext(fb2, z); fc = fnext(fc, z);
       if (!X1F) cf.dF[0][v] = a1 - a0;
       cf.dF[1][v] = b1 - b0; cf.dF[2][v] = c1 - c0;
       if (v == 0) { if (!X1F) { mlo[0] = a0; mhi[0] = a1; } mlo[1] = b0; mhi[1] = b1; mlo[2] = c0; mhi[2] = c1; }
       if (!X3F) f3[v] = c1;
     }
     if (GRAV) {
-      const Real dc = wc[0], phic = Pf(g, 0)[m];
+      const Real dc = wc[0], phic = zp((FBase)g.phi, o)[0];
+      FBase pf = (FBase)g.phi;
 #pragma unroll
       for (int e = 0; e < 3; e++) {
-        const Real phir = Pf(g, 1 + e)[m + stride_rt(g, e)], phil = Pf(g, 1 + e)[m];
+        pf = fnext(pf, z);
+        const Real phir = (e == 0) ? zp(pf, o)[1] : zp(fup(pf, e == 1 ? z.sJ8 : z.sK8), o)[0], phil = zp(pf, o)[0];
         cf.gm[e] = q[e]*(phir - phil)*dc;
         cf.ge[e] = q[e]*(mlo[e]*(phic - phil) + mhi[e]*(phir - phic));
         const Real dtodx = sr.dtodx[e];
@@ -296,12 +320,12 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
     }
     if (X1F && full) {   // ---- x1: the states reconstructed above take their corrections ----
       Real ll = 0.0, lr = 0.0;
-      if (do1) cell_finish<NS, 0, GRAV>(g, m, q, cf, wl1, wr1, true, ll, lr);
+      if (do1) cell_finish<NS, 0, GRAV>(g, z, mb, q, cf, wl1, wr1, true, ll, lr);
       const Real lprev = __shfl_up(ll, 1);
       if (do1) {
-        if (lane > 0) { if (i > g.is - 1) Ef(g, 0)[m] = 0.5*fabs(lr - lprev); }
-        else Ef(g, 0)[m] = lr;                        // tile edge: k_eta_edges finishes this face
-        if (lane == 63) Ef(g, 3)[m] = ll;
+        // (lane 0 is the tile edge: k_eta_edges finishes this face)
+        if (lane == 0 || i > g.is - 1) zstore((FBase)g.eta, mb, lane > 0 ? 0.5*fabs(lr - lprev) : lr);
+        if (lane == 63) zstore(fbase(g.eta, z, 3), mb, ll);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -311,19 +335,27 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
 #pragma unroll
         for (int n = 0; n < 6; n++) { wl3[n] = (n < NV) ? s_park[pk + n][row][lane] : 0.0; wr3[n] = (n < NV) ? s_park[pk + 6 + n][row][lane] : 0.0; }
       }
-      if (X3F) cell_finish<NS, 2, GRAV>(g, m, q, cf, wl3, wr3, full, ll, lr);
+      if (X3F) cell_finish<NS, 2, GRAV>(g, z, mb, q, cf, wl3, wr3, full, ll, lr);
       else {
         Real wm[6], ws[6], wp[6];
         to_sweep<2>(wm3, wm3[4], wm); to_sweep<2>(wc, wc[4], ws); to_sweep<2>(wn, wn[4], wp);
-        cell_states<NS, 2, GRAV, ORD>(g, m, dt, sr.dtodx[2], q, cf, wm, ws, wp, full, ll, lr);
+        cell_states<NS, 2, GRAV, ORD>(g, z, mb, dt, sr.dtodx[2], q, cf, wm, ws, wp, full, ll, lr);
       }
-      if (full && k > g.ks - 1) Ef(g, 2)[m] = 0.5*fabs(lr - lam3);      // lam3 = lambda_l the zone below gave to this zone's lower face
+      if (full && k > g.ks - 1) zstore(fbase(g.eta, z, 2), mb, 0.5*fabs(lr - lam3));      // lam3 = lambda_l the zone below gave to this zone's lower face
       lam3 = ll;
       if ((GRAV || AA_COOLING) && full) {   // d^{n+1/2}, :2104-2125
         const Real dh = wc[0] - q[0]*cf.dF[0][0] - q[1]*cf.dF[1][0] - q[2]*cf.dF[2][0];
-        g.dhalf[m] = dh;
+        zstore((FBase)g.dhalf, mb, dh);
 #if AA_COOLING
-        g.phalf[m] = p_half(g, m, q, cf.dF, GRAV, cf.gm, dh);      // P^{n+1/2}, :2133-2266
+        {   // P^{n+1/2}, :2133-2266
+          FBase b = fbase(g.U, z, 1);
+          Real um[3], ue;
+          const unsigned o = zsite(mb, b);
+#pragma unroll
+          for (int e = 0; e < 3; e++) { um[e] = zp(b, o)[0]; b = fnext(b, z); }
+          ue = zp(b, o)[0];
+          zpw((FBase)g.phalf, o)[0] = p_half(um, ue, q, cf.dF, GRAV, cf.gm, dh, g.Gamma_1);
+        }
 #endif
       }
     }
@@ -342,12 +374,12 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
 #pragma unroll
           for (int v = 0; v < 6; v++) { if (lane == 0) wm[v] = wh[v]; else wp[v] = wh[v]; }
         }
-        if (do1) cell_states<NS, 0, GRAV, ORD>(g, m, dt, sr.dtodx[0], q, cf, wm, ws, wp, true, ll, lr);
+        if (do1) cell_states<NS, 0, GRAV, ORD>(g, z, mb, dt, sr.dtodx[0], q, cf, wm, ws, wp, true, ll, lr);
         const Real lprev = __shfl_up(ll, 1);
         if (do1) {
-          if (lane > 0) { if (i > g.is - 1) Ef(g, 0)[m] = 0.5*fabs(lr - lprev); }
-          else Ef(g, 0)[m] = lr;                        // tile edge: k_eta_edges finishes this face
-          if (lane == 63) Ef(g, 3)[m] = ll;
+          // (lane 0 is the tile edge: k_eta_edges finishes this face)
+          if (lane == 0 || i > g.is - 1) zstore((FBase)g.eta, mb, lane > 0 ? 0.5*fabs(lr - lprev) : lr);
+          if (lane == 63) zstore(fbase(g.eta, z, 3), mb, ll);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -377,13 +409,13 @@ k_correct_all(DevGrid g, Real dt, int kchunk, StepRatios sr)
           for (int n = 0; n < NV; n++) wp[n] = s_w[row + 1][n][lane];
           if (!NS) wp[5] = 0.0;
         }
-        if (do2) cell_states<NS, 1, GRAV, ORD>(g, m, dt, sr.dtodx[1], q, cf, wm, ws, wp, true, ll, lr);
+        if (do2) cell_states<NS, 1, GRAV, ORD>(g, z, mb, dt, sr.dtodx[1], q, cf, wm, ws, wp, true, ll, lr);
         s_l[row][lane] = ll;
         __syncthreads();
         if (do2) {
-          if (row > 0) Ef(g, 1)[m] = 0.5*fabs(lr - s_l[row - 1][lane]);
-          else if (j > g.js - 1) Ef(g, 1)[m] = lr;      // tile edge, as for x1
-          if (row == CA_TJ - 1) Ef(g, 4)[m] = ll;
+          // (row 0 is the tile edge, as lane 0 for x1)
+          if (row > 0 || j > g.js - 1) zstore(fbase(g.eta, z, 1), mb, row > 0 ? 0.5*fabs(lr - s_l[row - 1][lane]) : lr);
+          if (row == CA_TJ - 1) zstore(fbase(g.eta, z, 4), mb, ll);
         }
       }
       __builtin_amdgcn_sched_barrier(0);

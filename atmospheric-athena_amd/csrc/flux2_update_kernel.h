@@ -76,12 +76,14 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
   for (int n = 0; n < 6; n++) f3lo[n] = 0.0;
   const bool keep1 = KEEP && need1 && on_plane(kp, 0, edge ? i0 + 64 : i), keep2 = KEEP && need2 && on_plane(kp, 1, j);
   if (cell) {                                                                   // face k0
-    face_flux2<NS, 2>(g, (long)k0*g.sK + mcol, f3lo);
+    const ZStr z = zone_strides(g);               // the scalar-base accessors (hydro_kernels.hip, field accessors)
+    const unsigned mb = zone_off((long)k0*g.sK + mcol);
+    face_flux2<NS, 2>(g, z, mb, f3lo);
     // (only the first chunk keeps its face k0: every later chunk's is face k1+1 of the chunk below, kept there by the loop's instance of
     //  the solver -- in the default build this instance may contract its multiply-adds differently, and two writers of one word with
     //  last-bit-different values made the flux a level's parent reads depend on which block finished last: round 4, found as a
     //  run-to-run difference of 1e-16 on the levels of a Mesh in the default build)
-    if (KEEP && blockIdx.z == 0 && on_plane(kp, 2, k0)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, (long)k0*g.sK + mcol, f3lo);
+    if (KEEP && blockIdx.z == 0 && on_plane(kp, 2, k0)) store_sweep<2, NS>(fbase(g.F, z, 12), z, mb, f3lo);
   }
 #pragma unroll
   for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3lo[n];
@@ -90,24 +92,25 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
   // wavefronts per SIMD the memory pipe is not idle while a wavefront computes.
   FaceIn in1, in2;
   {
-    long m0 = (long)k0*g.sK + mcol + m1off;
-    asm volatile("" : "+v"(m0));
-    if (need1) face_load<NS, 0>(g, m0, in1);
+    const ZStr z = zone_strides(g);
+    if (need1) face_load<NS, 0>(g, z, 0L, zone_off((long)k0*g.sK + mcol + m1off), in1);
   }
   for (int k = k0; k <= k1; k++) {
     // (opaque to the optimiser: otherwise every one of the ~60 field pointers becomes its own
     //  strength-reduced 64-bit induction variable and the kernel spills)
-    long m = (long)k*g.sK + mcol;
-    asm volatile("" : "+v"(m));
+    // One 32-bit byte offset for all fields, and the strides by which the fields' scalar bases are formed where they are used
+    // (hydro_kernels.hip, field accessors); mb1: the offset of this thread's x1 face (the edge wavefront's is in another row)
+    const ZStr z = zone_strides(g);
+    const unsigned mb = zone_off((long)k*g.sK + mcol), mb1 = zone_off((long)k*g.sK + mcol + m1off);
     const int pb = k & 1;
-    if (need2) face_load<NS, 1>(g, m, in2);
+    if (need2) face_load<NS, 1>(g, z, 0L, mb, in2);
     __builtin_amdgcn_sched_barrier(0);
     {
       Real f[6];
 #pragma unroll
       for (int n = 0; n < 6; n++) f[n] = 0.0;
       if (need1) face_solve<NS>(g, in1, f);
-      if (keep1) store_sweep<0, NS>(Ff(g, 0, 0), g.nc, m + m1off, f);
+      if (keep1) store_sweep<0, NS>((FBase)g.F, z, mb1, f);
 #pragma unroll
       for (int n = 0; n < NV; n++) d1[n] = __shfl_down(f[n], 1) - f[n];
       m1lo = f[0]; m1hi = __shfl_down(f[0], 1);
@@ -121,14 +124,14 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (cell) face_load<NS, 2>(g, m + g.sK, in1);           // (in1 is free: reused for the x3 face)
+    if (cell) face_load<NS, 2>(g, z, (long)z.sK8, mb, in1);          // (in1 is free: reused for the x3 face)
     __builtin_amdgcn_sched_barrier(0);
     {
       Real f[6];
 #pragma unroll
       for (int n = 0; n < 6; n++) f[n] = 0.0;
       if (need2) face_solve<NS>(g, in2, f);
-      if (keep2) store_sweep<1, NS>(Ff(g, 1, 0), g.nc, m, f);
+      if (keep2) store_sweep<1, NS>(fbase(g.F, z, 6), z, mb, f);
 #pragma unroll
       for (int n = 0; n < NV; n++) s_f2[pb][row][n][lane] = f[n];
       __syncthreads();
@@ -152,18 +155,22 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
 #pragma unroll
     for (int v = 0; v < 7; v++) ep[v] = 0.0;
     if (GRAV && cell) {
-      ep[0] = Pf(g, 0)[m]; edh = dhalf[m];
-      ep[1] = Pf(g, 1)[m + 1]; ep[2] = Pf(g, 1)[m]; ep[3] = Pf(g, 2)[m + g.sJ]; ep[4] = Pf(g, 2)[m]; ep[5] = Pf(g, 3)[m + g.sK]; ep[6] = Pf(g, 3)[m];
+      FBase pf = (FBase)g.phi;
+      const unsigned o = zsite(mb, pf);
+      ep[0] = zp(pf, o)[0]; edh = zp((FBase)dhalf, o)[0];
+      pf = fnext(pf, z); ep[1] = zp(pf, o)[1]; ep[2] = zp(pf, o)[0];
+      pf = fnext(pf, z); ep[3] = zp(fup(pf, z.sJ8), o)[0]; ep[4] = zp(pf, o)[0];
+      pf = fnext(pf, z); ep[5] = zp(fup(pf, z.sK8), o)[0]; ep[6] = zp(pf, o)[0];
     }
     Real f3[6];
 #pragma unroll
     for (int n = 0; n < 6; n++) f3[n] = 0.0;
     if (cell) face_solve<NS>(g, in1, f3);
     __builtin_amdgcn_sched_barrier(0);
-    if (need1 && k < k1) face_load<NS, 0>(g, m + m1off + g.sK, in1);  // the next zone's x1 face
+    if (need1 && k < k1) face_load<NS, 0>(g, z, (long)z.sK8, mb1, in1);  // the next zone's x1 face
     __builtin_amdgcn_sched_barrier(0);
     if (cell) {
-      if (KEEP && on_plane(kp, 2, k + 1)) store_sweep<2, NS>(Ff(g, 2, 0), g.nc, m + g.sK, f3);
+      if (KEEP && on_plane(kp, 2, k + 1)) store_sweep<2, NS>(fup(fbase(g.F, z, 12), z.sK8), z, mb, f3);
 #pragma unroll
       for (int n = 0; n < NV; n++) { f3lo[n] = s_f3[n][row][lane]; d3[n] = f3[n] - f3lo[n]; }
       m3hi = f3[0];
@@ -171,12 +178,16 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
 #pragma unroll
       for (int n = 0; n < NV; n++) s_f3[n][row][lane] = f3[n];
       Real u[6];
+      const unsigned o = zsite(mb, (FBase)g.U);
+      {
+        FBase b = (FBase)g.U;
 #pragma unroll
-      for (int v = 0; v < NV; v++) u[v] = Uf(g, v)[m];
+        for (int v = 0; v < NV; v++) { u[v] = zp(b, o)[0]; b = fnext(b, z); }
+      }
       // (the mask byte with the zone's other operands, not behind the stores of U: a load that is consumed at once waits
       //  for everything issued before it, i.e. the wave sat out the six stores' round trip in every plane)
       unsigned char pinned = 0;
-      if (CFL && pinmask) pinned = pinmask[m];
+      if (CFL && pinmask) pinned = pinmask[zsite(mb, (FBase)pinmask) >> 3];      // (a byte per zone)
       if (GRAV) {   // :2741-2782, with the mass fluxes (sweep component 0) of the faces just solved
         const Real phic = ep[0], dh = edh;
         { const Real phir = ep[1], phil = ep[2];
@@ -190,7 +201,7 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
           u[4] -= dtodx[2]*(m3lo*(phic - phil) + m3hi*(phir - phic)); }
       }
 #if AA_COOLING
-      u[4] -= dt*cool_koyinut(dhalf[m], g.phalf[m], dt, g.Gamma_1);      // Step 11c, :2943-2953
+      u[4] -= dt*cool_koyinut(zp((FBase)dhalf, o)[0], zp((FBase)g.phalf, o)[0], dt, g.Gamma_1);      // Step 11c, :2943-2953
 #endif
       // :2981-3050, x1 then x2 then x3; sweep component n of direction D is global variable gv<D>(n)
 #pragma unroll
@@ -199,8 +210,12 @@ k_flux2_update(DevGrid g, const Real *dhalf, Real dt, int kchunk, KeepPlanes kp,
       for (int n = 0; n < NV; n++) u[gv<1>(n)] -= dtodx[1]*d2[n];
 #pragma unroll
       for (int n = 0; n < NV; n++) u[gv<2>(n)] -= dtodx[2]*d3[n];
+      {
+        FBase b = (FBase)g.U;
+        const unsigned os = zsite(mb, fnext(b, z));      // (behind the branch on the mask byte: a block of its own)
 #pragma unroll
-      for (int v = 0; v < NV; v++) Uf(g, v)[m] = u[v];
+        for (int v = 0; v < NV; v++) { zpw(b, os)[0] = u[v]; b = fnext(b, z); }
+      }
       if (CFL) {
         if (!pinned) {
           Real cmx[3] = {s_cmx[0][row][lane], s_cmx[1][row][lane], s_cmx[2][row][lane]};

@@ -4,6 +4,7 @@
 #pragma once
 #include "grid.h"
 #include "time_step.h"
+#include "field_offsets.h"      // field_offsets_fit: the Grids the marching kernels' 32-bit zone offsets reach (aa_create asks it)
 
 // steps aa_run_3d queues between two reads of the clock where AA_3D_BATCH is not set (0: one aa_step at a time); DESIGN section 8
 #define AA_3D_BATCH_DEFAULT 8

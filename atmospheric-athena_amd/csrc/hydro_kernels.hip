@@ -42,6 +42,36 @@ AA_DEV Real *LRf(const DevGrid &g, int d, int side, int v) { return g.LR + (long
 AA_DEV Real *Ff(const DevGrid &g, int d, int v) { return g.F + (long)(d*6 + v)*g.nc; }
 AA_DEV Real *Ef(const DevGrid &g, int d) { return g.eta + (long)d*g.nc; }
 AA_DEV Real *Pf(const DevGrid &g, int which) { return g.phi + (long)which*g.nc; }   // 0 centre, 1+d face
+// ---- the same fields as the marching kernels address them: scalar base + one 32-bit zone offset --------
+// A field access of a march loop is base + zext(mb) + immediate: `base` a uniform 64-bit byte address in a scalar register pair,
+// `mb` the zone's byte offset inside a field as ONE 32-bit unsigned vector register, formed once per iteration, and the +-1 zone
+// neighbours in the instruction's immediate.  Everything uniform -- which field (multiples of nc), the +-sJ / +-sK / 2 sK
+// neighbours -- is added to the base on the scalar unit, never to the offset.  The strides are made opaque INSIDE the loop body
+// (zone_strides), so that a base is formed where it is used, by a running scalar add from the base before it, and the ~60 bases
+// of a kernel cannot be hoisted out of the loop and spilled into lanes of vector registers.
+// mb < 2^32 for every Grid aa_create accepts (field_offsets_fit, hydro3d_launch.h).
+struct ZStr { unsigned nc8, sJ8, sK8; };            // bytes between two fields of a family, two rows, two planes
+typedef const char *FBase;                          // a field's base: uniform
+AA_DEV ZStr zone_strides(const DevGrid &g)
+{
+  ZStr z = {(unsigned)g.nc*8u, (unsigned)g.sJ*8u, (unsigned)g.sK*8u};
+  asm volatile("" : "+s"(z.nc8), "+s"(z.sJ8), "+s"(z.sK8));
+  return z;
+}
+AA_DEV unsigned zone_off(long m) { unsigned mb = (unsigned)m*8u; asm volatile("" : "+v"(mb)); return mb; }   // zone index -> byte offset
+// The instruction takes the 32-bit offset only where the compiler sees its zero-extension in the basic block of the access (it selects
+// instructions block by block, and an extension made once at the head of the iteration reaches the other blocks as a 64-bit pair
+// and is added to the base by a 64-bit vector add).  So every group of accesses that may sit in a block of its own -- a helper, the
+// body of a branch -- starts from its own copy of the offset: one v_mov per group instead of one 64-bit add per access.  (Tied to
+// the group's base so that two groups' copies are not merged back into one in front of both.)
+AA_DEV unsigned zsite(unsigned mb, FBase b) { asm("" : "+v"(mb) : "s"(b)); return mb; }
+AA_DEV FBase fbase(const Real *fam, const ZStr &z, int n) { return (FBase)fam + (unsigned long)z.nc8*(unsigned)n; }   // field n of a family
+AA_DEV FBase fnext(FBase b, const ZStr &z) { return b + z.nc8; }                                                      // the field behind b
+AA_DEV FBase fup(FBase b, unsigned s) { return b + s; }                                                              // the zone one row / plane up
+AA_DEV FBase fdn(FBase b, unsigned s) { return b - s; }
+AA_DEV const Real *zp(FBase b, unsigned mb) { return (const Real *)(b + mb); }              // [0], [1], [-1]: the zone and its x1 neighbours
+AA_DEV Real *zpw(FBase b, unsigned mb) { return (Real *)(const_cast<char *>(b) + mb); }
+AA_DEV void zstore(FBase b, unsigned mb, Real x) { zpw(b, zsite(mb, b))[0] = x; }      // a store that stands alone in its branch
 // dt/dx_d and half of it, formed by the launcher (the same IEEE quotient the kernels form): as kernel arguments they live in scalar
 // registers; formed in the kernel they took twelve vector registers through the whole march of k_correct_all, six in k_flux2_update
 struct StepRatios { Real dtodx[3], q[3]; };
@@ -78,17 +108,17 @@ AA_DEV void cool_states(const DevGrid &g, Real dt, Real wl[6], Real wr[6])
 }
 // Step 8b: P^{n+1/2} of zone m from U^n, the first-pass flux differences across the zone (global frame) and, with a static
 // potential, q_e (phi_r - phi_l) d
-AA_DEV Real p_half(const DevGrid &g, long m, const Real q[3], const Real dF[3][6], bool grav, const Real gm[3], Real dhalf)
+AA_DEV Real p_half(const Real um[3], Real ue, const Real q[3], const Real dF[3][6], bool grav, const Real gm[3], Real dhalf, Real Gamma_1)
 {
   Real Mh[3];
 #pragma unroll
   for (int e = 0; e < 3; e++) {
-    Mh[e] = Uf(g, 1 + e)[m] - q[0]*dF[0][1 + e] - q[1]*dF[1][1 + e] - q[2]*dF[2][1 + e];
+    Mh[e] = um[e] - q[0]*dF[0][1 + e] - q[1]*dF[1][1 + e] - q[2]*dF[2][1 + e];
     if (grav) Mh[e] -= gm[e];
   }
-  const Real Eh = Uf(g, 4)[m] - q[0]*dF[0][4] - q[1]*dF[1][4] - q[2]*dF[2][4];
+  const Real Eh = ue - q[0]*dF[0][4] - q[1]*dF[1][4] - q[2]*dF[2][4];
   Real ph = Eh - 0.5*(Mh[0]*Mh[0] + Mh[1]*Mh[1] + Mh[2]*Mh[2])/dhalf;
-  ph *= g.Gamma_1;
+  ph *= Gamma_1;
   return ph;
 }
 #endif
@@ -112,6 +142,29 @@ AA_DEV void store_sweep(Real *fam, long nc, long m, const Real in[6])
 #pragma unroll
   for (int n = 0; n < 5 + NS; n++) fam[(long)gv<D>(n)*nc + m] = in[n];
 }
+// the march loops' form: `fam` the base of field 0 of the family (uniform, any +-sJ / +-sK hop already in it), dz the x1 neighbour;
+// the fields are walked in storage order (a running scalar add) and land in the sweep frame by register naming
+template <int D> AA_DEV unsigned zstride(const ZStr &z) { return D == 0 ? 8u : (D == 1 ? z.sJ8 : z.sK8); }
+template <int D, int NS>
+AA_DEV void load_sweep(FBase fam, const ZStr &z, unsigned mb, int dz, Real out[6])
+{
+  Real t[6];
+  mb = zsite(mb, fam);
+#pragma unroll
+  for (int v = 0; v < 6; v++) { t[v] = (v < 5 + NS) ? zp(fam, mb)[dz] : 0.0; fam = fnext(fam, z); }
+#pragma unroll
+  for (int n = 0; n < 6; n++) out[n] = t[gv<D>(n)];
+}
+template <int D, int NS>
+AA_DEV void store_sweep(FBase fam, const ZStr &z, unsigned mb, const Real in[6])
+{
+  Real t[6];
+#pragma unroll
+  for (int n = 0; n < 6; n++) t[gv<D>(n)] = in[n];
+  mb = zsite(mb, fam);
+#pragma unroll
+  for (int v = 0; v < 5 + NS; v++) { zpw(fam, mb)[0] = t[v]; fam = fnext(fam, z); }
+}
 
 // L/R states of one cell: piecewise linear (ORD 2, lr_states_plm.c) or piecewise parabolic (ORD 3,
 // lr_states_ppm.c; the slopes of the cell and of its two neighbours along D come from k_slopes)
@@ -126,6 +179,26 @@ AA_DEV void recon_cell(const DevGrid &g, long mcell, const Real wm[6], const Rea
 #pragma unroll
     for (int n = 0; n < 5 + NS; n++) { const Real *q = Sf(g, D, n) + mcell; Dm[n] = q[-s]; D0[n] = q[0]; Dp[n] = q[s]; }
     if (!NS) { Dm[5] = 0.0; D0[5] = 0.0; Dp[5] = 0.0; }
+    ppm_cell<NS, TRACE>(wm, w, wp, Dm, D0, Dp, dtodx, g.Gamma, wl_next, wr_here);
+  } else plm_cell<NS, TRACE>(wm, w, wp, dtodx, g.Gamma, wl_next, wr_here);
+}
+// the march loops' form: the cell is zone mb of the fields moved by the uniform byte offset uo
+template <int NS, bool TRACE, int ORD, int D>
+AA_DEV void recon_cell(const DevGrid &g, const ZStr &z, long uo, unsigned mb, const Real wm[6], const Real w[6], const Real wp[6], Real dtodx,
+                       Real wl_next[6], Real wr_here[6])
+{
+  if (ORD == 3) {
+    Real Dm[6], D0[6], Dp[6];
+    FBase b = fbase(g.slope, z, D*6) + uo;
+#pragma unroll
+    for (int n = 0; n < 6; n++) {
+      if (n < 5 + NS) {
+        D0[n] = zp(b, mb)[0];
+        if (D == 0) { Dm[n] = zp(b, mb)[-1]; Dp[n] = zp(b, mb)[1]; }
+        else { Dm[n] = zp(fdn(b, zstride<D>(z)), mb)[0]; Dp[n] = zp(fup(b, zstride<D>(z)), mb)[0]; }
+        b = fnext(b, z);
+      } else { Dm[n] = 0.0; D0[n] = 0.0; Dp[n] = 0.0; }
+    }
     ppm_cell<NS, TRACE>(wm, w, wp, Dm, D0, Dp, dtodx, g.Gamma, wl_next, wr_here);
   } else plm_cell<NS, TRACE>(wm, w, wp, dtodx, g.Gamma, wl_next, wr_here);
 }
@@ -242,7 +315,8 @@ AA_DEV void face_correct(const DevGrid &g, long m, int i, int j, int k, Real dt,
         for (int v = 0; v < 6; v++) dF[e][v] = (v < NV) ? Ff(g, e, v)[m + se] - Ff(g, e, v)[m] : 0.0;
         if (GRAV) gm[e] = q[e]*(Pf(g, 1 + e)[m + se] - Pf(g, 1 + e)[m])*Uf(g, 0)[m];
       }
-      g.phalf[m] = p_half(g, m, q, dF, GRAV, gm, dh);
+      const Real um[3] = {Uf(g, 1)[m], Uf(g, 2)[m], Uf(g, 3)[m]};
+      g.phalf[m] = p_half(um, Uf(g, 4)[m], q, dF, GRAV, gm, dh, g.Gamma_1);
     }
 #endif
   }
@@ -268,6 +342,32 @@ AA_DEV void face_work(const DevGrid &g, long m, int i, int j, int k, Real dt, Re
   Real f[6];
   flux_roe<NS>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
   store_sweep<D, NS>(Ff(g, D, 0), g.nc, m, f);
+  if (MODE == MODE_BOTH) face_correct<NS, D, GRAV>(g, m, i, j, k, dt, ul, ur);
+}
+
+// the marching sweeps' form (the face is zone mb of the fields: the accessor rule at the top of the file); the correct pass of the
+// unfused small-Grid chain keeps its 64-bit zone index m
+template <int NS, int D, bool GRAV, int MODE>
+AA_DEV void face_work(const DevGrid &g, const ZStr &z, unsigned mb, long m, int i, int j, int k, Real dt, Real wl[6], Real wr[6])
+{
+  if (GRAV && MODE != MODE_VL) {   // integrate_3d_ctu.c:318-342 (x1), :611-628 (x2), :795-812 (x3)
+    const Real dtodx = dt/g.dx[D];
+    const FBase pc = (FBase)g.phi, pf = fbase(g.phi, z, 1 + D);
+    const unsigned o = zsite(mb, pc);
+    Real phicr = zp(pc, o)[0], phicl = (D == 0) ? zp(pc, o)[-1] : zp(fdn(pc, zstride<D>(z)), o)[0], phifc = zp(pf, o)[0];
+    wl[1] -= dtodx*(phifc - phicl);
+    wr[1] -= dtodx*(phicr - phifc);
+  }
+#if AA_COOLING
+  if (MODE != MODE_VL) cool_states(g, dt, wl, wr);       // :359-368, :662-671, :846-855 (the van Leer integrator has no such term)
+#endif
+  Real ul[6], ur[6];
+  prim_to_cons<NS>(wl, ul, g.Gamma_1, g.rGamma_1);
+  prim_to_cons<NS>(wr, ur, g.Gamma_1, g.rGamma_1);
+  if (MODE == MODE_CORR) { face_correct<NS, D, GRAV>(g, m, i, j, k, dt, ul, ur); return; }
+  Real f[6];
+  flux_roe<NS>(ul, ur, wl, wr, 0.0, g.Gamma, g.Gamma_1, f);
+  store_sweep<D, NS>(fbase(g.F, z, D*6), z, mb, f);
   if (MODE == MODE_BOTH) face_correct<NS, D, GRAV>(g, m, i, j, k, dt, ul, ur);
 }
 
@@ -591,12 +691,8 @@ k_sweep_x1(DevGrid g, const Real *src, Real dt, int koff)
 // between the frames: w (global frame d, V1, V2, V3, P, r) carries the pressure of the x3 sweep, p0 and
 // p1 are the pressures the x1 and x2 sweeps see.
 template <int NS>
-AA_DEV void load_prim3(const DevGrid &g, long m, Real w[6], Real &p0, Real &p1)
+AA_DEV void prim3(const DevGrid &g, const Real u[6], Real w[6], Real &p0, Real &p1)
 {
-  Real u[6];
-#pragma unroll
-  for (int v = 0; v < 5 + NS; v++) u[v] = Uf(g, v)[m];
-  if (!NS) u[5] = 0.0;
 #if AA_FAST_DIV
   const Real di = q_rcp(u[0]);          // as cons_to_prim: the same bits whichever kernel converts the zone
 #else
@@ -610,12 +706,31 @@ AA_DEV void load_prim3(const DevGrid &g, long m, Real w[6], Real &p0, Real &p1)
   p0 = rmax(pa, AA_TINY); p1 = rmax(pb, AA_TINY); w[4] = rmax(pc, AA_TINY);
   w[5] = NS ? u[5]*di : 0.0;
 }
-// sweep-frame primitives of a halo zone, exactly as the sweeps load them
-template <int NS, int D>
-AA_DEV void load_prim_sweep(const DevGrid &g, long m, Real w[6])
+template <int NS>
+AA_DEV void load_prim3(const DevGrid &g, long m, Real w[6], Real &p0, Real &p1)
 {
   Real u[6];
-  load_sweep<D, NS>(g.U, g.nc, m, u);
+#pragma unroll
+  for (int v = 0; v < 5 + NS; v++) u[v] = Uf(g, v)[m];
+  if (!NS) u[5] = 0.0;
+  prim3<NS>(g, u, w, p0, p1);
+}
+template <int NS>
+AA_DEV void load_prim3(const DevGrid &g, const ZStr &z, long uo, unsigned mb, Real w[6], Real &p0, Real &p1)
+{
+  Real u[6];
+  FBase b = (FBase)g.U + uo;
+  mb = zsite(mb, b);
+#pragma unroll
+  for (int v = 0; v < 6; v++) { u[v] = (v < 5 + NS) ? zp(b, mb)[0] : 0.0; b = fnext(b, z); }
+  prim3<NS>(g, u, w, p0, p1);
+}
+// sweep-frame primitives of a halo zone, exactly as the sweeps load them
+template <int NS, int D>
+AA_DEV void load_prim_sweep(const DevGrid &g, const ZStr &z, unsigned mb, int dz, Real w[6])
+{
+  Real u[6];
+  load_sweep<D, NS>((FBase)g.U, z, mb, dz, u);
   cons_to_prim<NS>(u, w, g.Gamma_1);
 }
 // global frame (d, V1, V2, V3, ., r) with the pressure of frame D -> sweep frame of D
@@ -634,13 +749,17 @@ struct CellFlux {            // first-pass fluxes across one zone
 
 // one zone along D, first half: reconstruction + gravity kick = the primitive states the FIRST pass solves its Riemann
 // problems with (face_work): the left state belongs to the zone's upper face, the right state to its lower one
+// (the zone is offset mb of the fields moved by the uniform byte offset uo: the accessor rule at the top of the file)
 template <int NS, int D, bool GRAV, int ORD>
-AA_DEV void cell_recon(const DevGrid &g, long m, Real dt, Real dtodx, const Real wm[6], const Real w[6], const Real wp[6], Real wl[6], Real wr[6])
+AA_DEV void cell_recon(const DevGrid &g, const ZStr &z, long uo, unsigned mb, Real dt, Real dtodx, const Real wm[6], const Real w[6], const Real wp[6],
+                       Real wl[6], Real wr[6])
 {
-  const long sD = stride<D>(g);
-  recon_cell<NS, true, ORD, D>(g, m, wm, w, wp, dtodx, wl, wr);
+  if (ORD == 3) mb = zsite(mb, (FBase)g.slope + uo);      // (the slopes' loads: recon_cell itself is called from the head of k_sweep_march's iteration)
+  recon_cell<NS, true, ORD, D>(g, z, uo, mb, wm, w, wp, dtodx, wl, wr);
   if (GRAV) {
-    const Real phic = Pf(g, 0)[m], phi_up = Pf(g, 1 + D)[m + sD], phi_lo = Pf(g, 1 + D)[m];
+    const FBase pc = (FBase)g.phi + uo, pf = fbase(g.phi, z, 1 + D) + uo;
+    mb = zsite(mb, pc);
+    const Real phic = zp(pc, mb)[0], phi_up = (D == 0) ? zp(pf, mb)[1] : zp(fup(pf, zstride<D>(z)), mb)[0], phi_lo = zp(pf, mb)[0];
     wl[1] -= dtodx*(phi_up - phic);
     wr[1] -= dtodx*(phic - phi_lo);
   }
@@ -649,15 +768,16 @@ AA_DEV void cell_recon(const DevGrid &g, long m, Real dt, Real dtodx, const Real
 #endif
 }
 template <int NS, int D, bool GRAV, int ORD>
-AA_DEV void cell_recon(const DevGrid &g, long m, Real dt, const Real wm[6], const Real w[6], const Real wp[6], Real wl[6], Real wr[6])
-{ cell_recon<NS, D, GRAV, ORD>(g, m, dt, dt/g.dx[D], wm, w, wp, wl, wr); }
+AA_DEV void cell_recon(const DevGrid &g, const ZStr &z, long uo, unsigned mb, Real dt, const Real wm[6], const Real w[6], const Real wp[6], Real wl[6], Real wr[6])
+{ cell_recon<NS, D, GRAV, ORD>(g, z, uo, mb, dt, dt/g.dx[D], wm, w, wp, wl, wr); }
 // the same with the kicks of the zone taken from its CellFlux (formed at the head of the iteration from the potential
 // values loaded there: a load inside the direction blocks would wait for the stores of the block before it)
 template <int NS, int D, bool GRAV, int ORD>
-AA_DEV void cell_recon(const DevGrid &g, long m, Real dt, Real dtodx, const CellFlux &cf, const Real wm[6], const Real w[6], const Real wp[6],
+AA_DEV void cell_recon(const DevGrid &g, const ZStr &z, unsigned mb, Real dt, Real dtodx, const CellFlux &cf, const Real wm[6], const Real w[6], const Real wp[6],
                        Real wl[6], Real wr[6])
 {
-  recon_cell<NS, true, ORD, D>(g, m, wm, w, wp, dtodx, wl, wr);
+  if (ORD == 3) mb = zsite(mb, (FBase)g.slope);
+  recon_cell<NS, true, ORD, D>(g, z, 0L, mb, wm, w, wp, dtodx, wl, wr);
   if (GRAV) { wl[1] -= cf.kl[D]; wr[1] -= cf.kr[D]; }
 #if AA_COOLING
   cool_states(g, dt, wl, wr);
@@ -666,11 +786,10 @@ AA_DEV void cell_recon(const DevGrid &g, long m, Real dt, Real dtodx, const Cell
 // second half: conversion, transverse correction, face states stored; returns the wave speeds eta needs: lam_l of the
 // left state the zone gave to its UPPER face, lam_r of the right state it gave to its LOWER face
 template <int NS, int D, bool GRAV>
-AA_DEV void cell_finish(const DevGrid &g, long m, const Real q[3], const CellFlux &cf, const Real wl[6], const Real wr[6],
+AA_DEV void cell_finish(const DevGrid &g, const ZStr &z, unsigned mb, const Real q[3], const CellFlux &cf, const Real wl[6], const Real wr[6],
                         bool store, Real &lam_l, Real &lam_r)
 {
   constexpr int NV = 5 + NS;
-  const long sD = stride<D>(g);
   Real sl[6], sr[6], ul[6], ur[6];
   prim_to_cons<NS>(wl, sl, g.Gamma_1, g.rGamma_1);
   prim_to_cons<NS>(wr, sr, g.Gamma_1, g.rGamma_1);
@@ -691,9 +810,14 @@ AA_DEV void cell_finish(const DevGrid &g, long m, const Real q[3], const CellFlu
     }
   }
   if (store) {
+    // the left state belongs to the zone's upper face: one zone up along D, in the immediate (x1) or on the base (x2, x3)
+    FBase bl = fbase(g.LR, z, (D*2)*6), br = fbase(g.LR, z, (D*2 + 1)*6);
+    if (D != 0) bl = fup(bl, zstride<D>(z));
+    mb = zsite(mb, bl);
 #pragma unroll
     for (int v = 0; v < NV; v++) {      // written here, read once by the next kernel: non-temporal
-      __builtin_nontemporal_store(ul[v], LRf(g, D, 0, v) + m + sD); __builtin_nontemporal_store(ur[v], LRf(g, D, 1, v) + m);
+      __builtin_nontemporal_store(ul[v], zpw(bl, mb) + (D == 0 ? 1 : 0)); __builtin_nontemporal_store(ur[v], zpw(br, mb));
+      bl = fnext(bl, z); br = fnext(br, z);
     }
   }
 #pragma unroll
@@ -702,12 +826,12 @@ AA_DEV void cell_finish(const DevGrid &g, long m, const Real q[3], const CellFlu
   lam_l = lambda_face(sl, g.Gamma, g.Gamma_1, -1.0);
 }
 template <int NS, int D, bool GRAV, int ORD>
-AA_DEV void cell_states(const DevGrid &g, long m, Real dt, Real dtodx, const Real q[3], const CellFlux &cf, const Real wm[6], const Real w[6],
+AA_DEV void cell_states(const DevGrid &g, const ZStr &z, unsigned mb, Real dt, Real dtodx, const Real q[3], const CellFlux &cf, const Real wm[6], const Real w[6],
                         const Real wp[6], bool store, Real &lam_l, Real &lam_r)
 {
   Real wl[6], wr[6];
-  cell_recon<NS, D, GRAV, ORD>(g, m, dt, dtodx, cf, wm, w, wp, wl, wr);
-  cell_finish<NS, D, GRAV>(g, m, q, cf, wl, wr, store, lam_l, lam_r);
+  cell_recon<NS, D, GRAV, ORD>(g, z, mb, dt, dtodx, cf, wm, w, wp, wl, wr);
+  cell_finish<NS, D, GRAV>(g, z, mb, q, cf, wl, wr, store, lam_l, lam_r);
 }
 
 // With the x3 first pass on board (X3F), k_correct_all also does the x1 FIRST pass: a zone's reconstruction along x1 is the
@@ -757,9 +881,11 @@ AA_DEV void eta_edges(const DevGrid &g)
     i = g.is - 1 + (int)(lin % n1); j = g.js - 1 + CA_TJ*(1 + (int)((lin / n1) % nb)); k = g.ks - 1 + (int)(lin / ((long)n1*nb));
   }
   if (i > g.ie + 1 || j > g.je + 1) return;
-  const long m = (long)k*g.sK + (long)j*g.sJ + i, sD = stride<D>(g);
-  Real *e = Ef(g, D);
-  e[m] = 0.5*fabs(e[m] - Ef(g, 3 + D)[m - sD]);
+  const ZStr z = zone_strides(g);
+  const unsigned mb = zone_off((long)k*g.sK + (long)j*g.sJ + i);
+  const FBase e = fbase(g.eta, z, D), el = fbase(g.eta, z, 3 + D);
+  const Real lam_l = (D == 0) ? zp(el, mb)[-1] : zp(fdn(el, zstride<D>(z)), mb)[0];
+  zpw(e, mb)[0] = 0.5*fabs(zp(e, mb)[0] - lam_l);
 }
 // both directions in one launch (blockIdx.y; they touch different arrays)
 __global__ void __launch_bounds__(256)
@@ -992,18 +1118,30 @@ k_cfl_fold(const Real *part, int nb, DevScalars *sc)
 #endif
 // operands of one second-pass Riemann problem: the corrected face states (sweep frame) and the 9 etas
 struct FaceIn { Real ul[6], ur[6], eta[9]; };
-template <int NS, int D>
-AA_DEV void face_load(const DevGrid &g, long m, FaceIn &in)
+// eta of direction E beside the face along D of zone mb: of the zone below the face (lo) or above it, at its lower face along E or
+// (up) at its upper one -- the hops along x1 in the immediate, those along x2 / x3 on the base
+template <int D, int E>
+AA_DEV Real eta_at(FBase e, const ZStr &z, unsigned mb, bool lo, bool up)
 {
-  const long sD = stride<D>(g), ml = m - sD;
+  int dz = 0;
+  if (lo) { if (D == 0) dz -= 1; else e = fdn(e, zstride<D>(z)); }
+  if (up) { if (E == 0) dz += 1; else e = fup(e, zstride<E>(z)); }
+  return zp(e, mb)[dz];
+}
+// (the face is zone mb of the fields moved by the uniform byte offset uo: the accessor rule at the top of the file)
+template <int NS, int D>
+AA_DEV void face_load(const DevGrid &g, const ZStr &z, long uo, unsigned mb, FaceIn &in)
+{
   constexpr int E1 = (D == 0) ? 1 : 0, E2 = (D == 2) ? 1 : 2;
-  const long s1 = stride<E1>(g), s2 = stride<E2>(g);
-  const Real *e1 = Ef(g, E1), *e2 = Ef(g, E2);
-  in.eta[8] = Ef(g, D)[m];
-  in.eta[0] = e1[ml]; in.eta[1] = e1[m]; in.eta[2] = e1[ml + s1]; in.eta[3] = e1[m + s1];
-  in.eta[4] = e2[ml]; in.eta[5] = e2[m]; in.eta[6] = e2[ml + s2]; in.eta[7] = e2[m + s2];
-  load_sweep<D, NS>(LRf(g, D, 0, 0), g.nc, m, in.ul);
-  load_sweep<D, NS>(LRf(g, D, 1, 0), g.nc, m, in.ur);
+  const FBase e1 = fbase(g.eta, z, E1) + uo, e2 = fbase(g.eta, z, E2) + uo, eD = fbase(g.eta, z, D) + uo;
+  const unsigned o = zsite(mb, eD);
+  in.eta[8] = zp(eD, o)[0];
+  in.eta[0] = eta_at<D, E1>(e1, z, o, true, false); in.eta[1] = eta_at<D, E1>(e1, z, o, false, false);
+  in.eta[2] = eta_at<D, E1>(e1, z, o, true, true);  in.eta[3] = eta_at<D, E1>(e1, z, o, false, true);
+  in.eta[4] = eta_at<D, E2>(e2, z, o, true, false); in.eta[5] = eta_at<D, E2>(e2, z, o, false, false);
+  in.eta[6] = eta_at<D, E2>(e2, z, o, true, true);  in.eta[7] = eta_at<D, E2>(e2, z, o, false, true);
+  load_sweep<D, NS>(fbase(g.LR, z, (D*2)*6) + uo, z, mb, 0, in.ul);
+  load_sweep<D, NS>(fbase(g.LR, z, (D*2 + 1)*6) + uo, z, mb, 0, in.ur);
 }
 template <int NS>
 AA_DEV void face_solve(const DevGrid &g, const FaceIn &in, Real f[6])
@@ -1017,10 +1155,10 @@ AA_DEV void face_solve(const DevGrid &g, const FaceIn &in, Real f[6])
   flux_roe<NS>(in.ul, in.ur, wl, wr, etah, g.Gamma, g.Gamma_1, f);      // (the scaling-free quotients pay here since the x3 flux is parked in LDS: k_flux2_update)
 }
 template <int NS, int D>
-AA_DEV void face_flux2(const DevGrid &g, long m, Real f[6])
+AA_DEV void face_flux2(const DevGrid &g, const ZStr &z, unsigned mb, Real f[6])
 {
   FaceIn in;
-  face_load<NS, D>(g, m, in);
+  face_load<NS, D>(g, z, 0L, mb, in);
   face_solve<NS>(g, in, f);
 }
 
@@ -1701,6 +1839,31 @@ __global__ void k_test_xdiv(int n, const Real *a, const Real *b, Real *out)
   out[2L*n + t] = x_sqrt(x); out[3L*n + t] = sqrt(x);
   out[4L*n + t] = x_div_r(x, y, 1.0/y);                 // with the correctly rounded reciprocal (what the host supplies for gamma-1)
 }
+// The marching kernels' accessors (top of the file) at the ends of the 32-bit offset's range: lane l < 4 takes byte offset t.off[l],
+// phase 0 stores a word there through the accessors -- on `base` and on `base` moved up by the scalar stride -- and phase 1, a launch
+// of its own so that nothing is forwarded, loads the words back the same way, and once more from the zone below through the
+// immediate.  out[3][4]: base, base + stride, immediate.
+struct ZoneOffTest { unsigned off[4]; };
+__global__ void k_test_zone_offsets(Real *base, ZoneOffTest t, unsigned stride, int phase, Real *out)
+{
+  const int l = threadIdx.x;
+  if (l >= 4) return;
+  unsigned mb = (l == 0) ? t.off[0] : (l == 1) ? t.off[1] : (l == 2) ? t.off[2] : t.off[3];
+  asm volatile("" : "+v"(mb));
+  asm volatile("" : "+s"(stride));
+  const FBase b = (FBase)base, b2 = fup(b, stride);
+  if (phase == 0) {
+    zstore(b, mb, 1000.0 + l);
+    zstore(b2, mb, 2000.0 + l);
+  } else {
+    const unsigned o = zsite(mb, b);
+    out[l] = zp(b, o)[0];
+    out[4 + l] = zp(b2, o)[0];
+    const unsigned lo = zsite(mb >= 8u ? mb - 8u : mb, b2);
+    const Real up = zp(b, lo)[1], here = zp(b, lo)[0];      // (both inside the field)
+    out[8 + l] = (mb >= 8u) ? up : here;
+  }
+}
 template <int NS>
 __global__ void k_test_lr_ppm(Real Gamma, int n, const Real *W, Real dt, Real dx, int il, int iu, Real *Wl, Real *Wr)
 {
@@ -1728,6 +1891,11 @@ __global__ void k_test_lr(Real Gamma, int n, const Real *W, Real dt, Real dx, in
 // =============================================================================================
 // host-side launchers
 // =============================================================================================
+void launch_test_zone_offsets(Real *base, const unsigned off[4], unsigned stride, int phase, Real *out, hipStream_t st)
+{
+  ZoneOffTest t; for (int l = 0; l < 4; l++) t.off[l] = off[l];
+  hipLaunchKernelGGL(k_test_zone_offsets, dim3(1), dim3(64), 0, st, base, t, stride, phase, out);
+}
 void launch_test_xdiv(int n, const Real *a, const Real *b, Real *out, hipStream_t st)
 { hipLaunchKernelGGL(k_test_xdiv, dim3((n + 255)/256), dim3(256), 0, st, n, a, b, out); }
 static inline unsigned nblk(long n, int b) { return (unsigned)((n + b - 1)/b); }

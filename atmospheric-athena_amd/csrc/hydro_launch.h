@@ -51,6 +51,7 @@ void launch_test_fluxes(int nscal, Real gamma, int n, const Real *Ul, const Real
                         Real *F, hipStream_t st);
 void launch_test_lr(int nscal, Real gamma, int n, const Real *W, Real dt, Real dx, int il, int iu,
                     Real *Wl, Real *Wr, hipStream_t st);
+void launch_test_zone_offsets(Real *base, const unsigned off[4], unsigned stride, int phase, Real *out, hipStream_t st);   // out[3][4]; hydro_kernels.hip k_test_zone_offsets
 void launch_test_xdiv(int n, const Real *a, const Real *b, Real *out, hipStream_t st);     // out[5][n]: x_div, a/b, x_sqrt, sqrt, x_div_r
 void launch_test_lr_ppm(int nscal, Real gamma, int n, const Real *W, Real dt, Real dx, int il, int iu,
                         Real *Wl, Real *Wr, hipStream_t st);

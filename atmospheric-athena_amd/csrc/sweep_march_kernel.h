@@ -50,13 +50,17 @@ k_sweep_march(DevGrid g, const Real *src, Real dt, int chunk, int toff, int tcnt
   for (int n = 0; n < 6; n++) wl_cur[n] = 0.0;
 #pragma nounroll
   for (int f = f0 - 1; f <= f1; f++) {
-    long mf = base + (long)f*s;
-    asm volatile("" : "+v"(mf));     // one index for all fields instead of a strength-reduced pointer per field
+    // one index for all fields instead of a strength-reduced pointer per field: a 32-bit byte offset on the fields' scalar bases
+    // (hydro_kernels.hip, field accessors); the 64-bit zone index serves the correct pass of the unfused chain alone
+    const ZStr z = zone_strides(g);
+    const unsigned mb = zone_off(base + (long)f*s);
+    long mf = 0;
+    if (MODE == MODE_CORR || MODE == MODE_BOTH) { mf = base + (long)f*s; asm volatile("" : "+v"(mf)); }
 #pragma unroll
     for (int n = 0; n < 6; n++) { wm[n] = w[n]; w[n] = wp[n]; }
-    load_sweep<D, NS>(src, g.nc, mf + s, u); cons_to_prim<NS>(u, wp, g.Gamma_1);
-    recon_cell<NS, MODE != MODE_VL, ORD, D>(g, mf, wm, w, wp, dtodx, wl_next, wr);  // cell f -> Wl[f+1], Wr[f]
-    if (f >= f0) face_work<NS, D, GRAV, MODE>(g, mf, i, D == 1 ? f : t, D == 1 ? t : f, dt, wl_cur, wr);
+    load_sweep<D, NS>(fup((FBase)src, zstride<D>(z)), z, mb, 0, u); cons_to_prim<NS>(u, wp, g.Gamma_1);
+    recon_cell<NS, MODE != MODE_VL, ORD, D>(g, z, 0L, mb, wm, w, wp, dtodx, wl_next, wr);  // cell f -> Wl[f+1], Wr[f]
+    if (f >= f0) face_work<NS, D, GRAV, MODE>(g, z, mb, mf, i, D == 1 ? f : t, D == 1 ? t : f, dt, wl_cur, wr);
 #pragma unroll
     for (int n = 0; n < 6; n++) wl_cur[n] = wl_next[n];
   }

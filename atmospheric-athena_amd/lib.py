@@ -136,6 +136,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_test_ion_pick": (I, [I, dp, I, D, I, dp, dp, dp]),
         "aa_test_ion_batch": (I, [I, dp, I, D, D, I, I, dp, dp]),
         "aa_test_xdiv": (I, [I, dp, dp, dp]),
+        "aa_test_zone_offsets": (I, [C.c_uint, dp, dp]),
         "aa_history": (I, [P, dp]),
         "aa_dump_sections": (I, [P, I]), "aa_dump_section_floats": (LL, [P, I, I]),
         "aa_dump_section": (I, [P, I, I, I, C.POINTER(C.c_float)]),

@@ -399,6 +399,11 @@ int aa_test_lr_states_ppm(int nscal, double gamma, int n, const double *W, doubl
 int aa_test_xdiv(int n, const double *a, const double *b, double *out);  /* csrc/hydro_dev.h x_div / x_sqrt beside the compiler's
                                                                             a/b and sqrt(a): out[5][n] = x_div, a/b, x_sqrt,
                                                                             sqrt, x_div_r(a, b, 1/b) */
+/* The marching kernels' zone accessors (csrc/hydro_kernels.hip: scalar base + 32-bit byte offset + immediate) at byte offsets 0,
+ * 2^31 - 8, 2^31 and 2^32 - 8 of a 4 GiB field: lane l stores 1000 + l there and 2000 + l at the same offset from the base moved up by
+ * stride_bytes; stored[2][4] = the eight words as hipMemcpy finds them, loaded[3][4] = as the accessors load them back (base, base +
+ * stride, and the base's word again from the zone below through the immediate). */
+int aa_test_zone_offsets(unsigned stride_bytes, double *stored, double *loaded);
 int aa_test_explog(int n, const double *x, double *y_exp, double *y_log);  /* the exp / ln of csrc/ion_pass.hip
                                                                              (n a multiple of 4): exp(x), ln|x|  */
 /* The folds and step picks of the radiation sub-cycle on scratch memory (tests/test_gpu_ion_subcycles.py): rec[n][5] = n records
