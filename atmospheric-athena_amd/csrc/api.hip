@@ -318,6 +318,7 @@ void aa_destroy(aa_grid *g)
   hipStreamSynchronize(g->st);
   prof_drain(g);
   dump_release(g);
+  outdata_release(g);
   hipFree(g->pool); hipFree(g->sc); hipHostFree(g->mb);
   for (hipEvent_t ev : g->ev_pool) hipEventDestroy(ev);
   if (g->ion_part) hipFree(g->ion_part);

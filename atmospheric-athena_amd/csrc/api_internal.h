@@ -112,6 +112,9 @@ struct aa_grid {
   // staged: "payload made and EdgeFlux copied" on st, done: "on the host" on dump_st
   struct RstSlot { aa::Real *dev = nullptr, *host = nullptr; size_t cap = 0; bool held = false; hipEvent_t staged = nullptr, done = nullptr; };
   RstSlot rst_snap[AA_RST_SLOTS];
+  // single-variable outputs (outdata.hip): the blocks' minimum / maximum records of a piece with the running record behind them, and
+  // its page-locked copy; made by the first aa_outdata
+  aa::Real *out_part = nullptr; double *out_mm_host = nullptr;
   bool prof = false;
   std::vector<ProfEntry> pe;
   std::vector<hipEvent_t> ev_pool;     // events of drained scopes, reused (a small Grid's step is ~25 scopes: creating 50 events per step showed)
@@ -210,6 +213,7 @@ int slabs_fetch_scalars(aa_grid *g);
 int slabs_ion_finish(aa_grid *g);
 int slabs_history(aa_grid *g, double *sums);
 int slabs_dump_section(aa_grid *g, int fmt, int prim, int section, float *host_dst);
+void outdata_release(aa_grid *g);     // outdata.hip: the minimum / maximum records of a Grid that is going away
 void dump_release(aa_grid *g);        // dump.hip: the bounce buffer of a Grid that is going away
 int dump_prepare(aa_grid *g);         // dump.hip: the bounce buffer, its stream and events, made on first use (shared with restart.hip)
 int dump_stream(aa_grid *g);          // dump.hip: the stream of the dumps' copies alone, made on first use (the snapshots need no bounce buffer)

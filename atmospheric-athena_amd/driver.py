@@ -179,6 +179,9 @@ class HipEngine:
         """dump_vtk / dump_binary of this slab: the payload comes from the device in file order (csrc/dump.hip)"""
         self.g.write_dump(path, fmt, prim, time=time, dt=dt)
 
+    def outdata(self, expr, reduce, lo, hi): return self.g.outdata(expr, reduce, lo, hi)
+    def outdata_gray(self, expr, reduce, lo, hi, dmin, dmax): return self.g.outdata_gray(expr, reduce, lo, hi, dmin, dmax)
+
     def dump_source(self):
         """what takes the snapshots of an overlapped dump (outputs.OutputSet.overlapped_dump / overlapped_restart): this slab's Grid"""
         return self.g
@@ -416,6 +419,11 @@ class _Runner:
         """data_output(&Mesh, flag) of main.c: see outputs.OutputSet.data_output"""
         outputs.data_output(self, flag)
 
+    def single_route(self, outputs):
+        """None where this runner writes the single-variable blocks of OutputSet.from_par(single=True), else the reason it
+        refuses the keyword (asked once, before the first output)"""
+        return f"{type(self).__name__} writes no single-variable outputs"
+
     def main(self, outputs):
         """main.c:501-743: start, forced output (not after a restart), the loop up to <time>tlim / nlim with data_output(0) at
         the top of every pass, forced output.  Every rank of a multi-rank run calls it with its own
@@ -552,6 +560,63 @@ class Driver(_Runner):
             U = _active(self.eng.download())
             dumps.write_dump_from_block(path, out.out_fmt, U, prim=out.prim, gamma=r.gamma, nscal=r.nscal, nx=g.Nx,
                                         minx=g.MinX, dx=r.dx, time=self.time, dt=self.dt)
+
+    def single_route(self, outputs):
+        if self.nranks > 1:
+            return "a Driver on several ranks holds a part of every slice; single-variable outputs take one rank"
+        if self.run.ndim == 1:
+            return "a 1-D Grid (Nx2 = Nx3 = 1) is not built"
+        if getattr(getattr(self.eng, "g", None), "composite", False):
+            return "a Grid cut into slabs inside the library makes no single-variable output (one Grid on one device does)"
+        if any(o.single and o.out == "flux" for o in outputs.outs) and self.run.problem != "ioniz_sphere":
+            return f"out = flux: problem \"{self.run.problem}\" defines no such expression (ioniz_sphere does)"
+        return None
+
+    def write_single(self, out, outputs):
+        """output_vtk / output_tab / output_pgm of this Grid for one single-variable <outputN> block (output.c OutData1/2/3): the
+        payload, its minimum and maximum and the gray bytes from the device where the engine has one (lib.Grid.outdata), else the
+        same arithmetic in numpy over the engine's host block.  A slice that misses the Grid writes no file."""
+        if not _fires(out, 0):
+            return
+        from . import outputs as _o
+        g, r = self.grid, self.run
+        rng = _o.single_ranges(out, g.Nx, g.MinX, r.dx)
+        if rng is None:
+            return
+        reduce, lo, hi = rng
+        shape = _o.payload_shape(reduce, g.Nx)
+        on_device = hasattr(self.eng, "outdata")
+        if on_device:
+            data, dmin, dmax = self.eng.outdata(out.out, reduce, lo, hi)
+        else:
+            U = self.eng.download()
+            first = [config.NGHOST if n > 1 else 0 for n in g.Nx]
+            V = dumps.expr_from_block(U, out.out, r.gamma, self.eng.download_edgeflux() if out.out == "flux" else None)
+            if out.out == "flux":
+                first = [0, 0, 0]
+            full = [(lo[a], hi[a]) if reduce[a] else (0, g.Nx[a] - 1) for a in range(3)]
+            data = dumps.outdata_from_values(V, first, reduce, [f[0] for f in full], [f[1] for f in full])
+            dmin, dmax = dumps.minmax(data)
+        data = np.asarray(data).reshape(shape)
+        fmt = out.out_fmt
+        if fmt == "tab" and len(shape) >= 2 and out.num == 0:       # output_tab.c:198-204, :273-279
+            out.gmin, out.gmax = dmin, dmax
+        else:                                                       # MIN / MAX of the writers (output_vtk.c:112-113, output_pgm.c:87-88)
+            out.gmin = dmin if dmin < out.gmin else out.gmin
+            out.gmax = dmax if dmax > out.gmax else out.gmax
+        if fmt == "vtk":
+            b = dumps.single_vtk_bytes(data, out.id, nx=g.Nx, minx=g.MinX, dx=r.dx, raw_reduce=out.raw_reduce, time=self.time)
+        elif fmt == "tab":
+            b = dumps.single_tab_bytes(data, out.dat_fmt)
+        else:
+            if out.sdmin:
+                dmin = out.dmin
+            if out.sdmax:
+                dmax = out.dmax
+            gray = self.eng.outdata_gray(out.out, reduce, lo, hi, dmin, dmax) if on_device else dumps.pgm_gray(data, dmin, dmax)
+            b = dumps.single_pgm_bytes(gray, shape[1], shape[0])
+        with open(outputs.path(dumps.fname_id(outputs.basename, 0, 0, out.num, out.id, fmt)), "wb") as f:
+            f.write(b)
 
     def write_history(self, out, outputs):
         if not _fires(out, 0):
@@ -966,6 +1031,9 @@ class MeshRun(_Runner):
         run = self.mesh.run_2d if hasattr(self.mesh, "can_run_2d") and self.mesh.can_run_2d() else self.mesh.run_3d
         return run(t_stop, self.run.tlim, far if nstep_stop is None else min(int(nstep_stop), far))
 
+    def single_route(self, outputs):
+        return "a refined mesh (MeshRun) writes no single-variable outputs: they are built for a single-level run"
+
     def write_dump(self, out, outputs):
         if getattr(outputs, "overlap", False):    # every level's Grid with its own snapshot slots; a level without the route writes now
             t, dt = self.time, self.dt
@@ -1187,6 +1255,9 @@ class MeshDriver(_Runner):
             self.eng.set_level_state(l, time, dt, nstep)
 
     # ---- outputs (output.c:498-569; outputs.OutputSet drives these) -----------------------------
+    def single_route(self, outputs):
+        return "a refined mesh over ranks (MeshDriver) writes no single-variable outputs: they are built for a single-level run"
+
     def write_dump(self, out, outputs):
         """dump_vtk / dump_binary under MPI + SMR: one file per level this rank holds zones of, under the rank's directory;
         the header is the slab's own (its DIMENSIONS and ORIGIN, the level's spacing, the Mesh time)."""

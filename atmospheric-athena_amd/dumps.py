@@ -168,6 +168,139 @@ def write_dump_from_block(path: str, fmt, U: np.ndarray, *, prim: bool, gamma: f
     write_dump(path, fmt, lambda i: pay[i], prim=prim, gamma=gamma, nscal=nscal, **kw)
 
 
+# ---- single-variable outputs: output_vtk.c, output_tab.c, output_pgm.c around the payload of OutData1/2/3 (output.c:629-1107) ----
+EXPR = {"d": 0, "M1": 1, "M2": 2, "M3": 3, "E": 4, "V1": 5, "V2": 6, "V3": 7, "P": 8, "cs2": 9, "flux": 10}    # AA_OUT_*
+FLT_EPSILON = float(np.finfo(np.float32).eps)
+
+
+def fname_id(basename: str, level: int, domain: int, num: int, id_: str, ext: str) -> str:
+    """ath_fname(plev, basename, plev, pdom, num_digit, num, id, ext): ``<base>.NNNN.<id>.<ext>``"""
+    name = basename + (f"-lev{level}" if level > 0 else "") + (f"-dom{domain}" if domain > 0 else "")
+    name += ".%0*d.%s.%s" % (NUM_DIGIT, num, id_, ext)
+    return os.path.join(f"lev{level}", name) if level > 0 else name
+
+
+def expr_from_block(U: np.ndarray, expr: str, gamma: float, edgeflux: Optional[np.ndarray] = None) -> np.ndarray:
+    """expr_* of output.c:1109-1233 over a host block ``[k][j][i][var]``, operation by operation (numpy does not contract);
+    flux: the block of EdgeFlux itself (prob/ioniz_sphere.c:356-359)."""
+    if expr == "flux":
+        return np.asarray(edgeflux, dtype=np.float64)
+    d, M1, M2, M3, E = (U[..., c] for c in range(5))
+    with np.errstate(all="ignore"):
+        if expr in ("d", "M1", "M2", "M3", "E"):
+            return np.array(U[..., EXPR[expr]], dtype=np.float64)
+        if expr in ("V1", "V2", "V3"):
+            return U[..., EXPR[expr] - 4] / d
+        e = E - 0.5 * (M1 * M1 + M2 * M2 + M3 * M3) / d
+        if expr == "P":
+            return (gamma - 1.0) * e
+        if expr == "cs2":
+            return gamma * (gamma - 1.0) * e / d
+    raise ValueError(f"[expr_from_block]: expression {expr!r}")
+
+
+def outdata_from_values(V: np.ndarray, first, reduce, lo, hi) -> np.ndarray:
+    """OutData1/2/3 from the expression's values `V` ``[k][j][i]`` over a block whose zone [first[2]][first[1]][first[0]] is the
+    first active one (a block with ghost zones: first = nghost where the direction has them).  Direction a covers the zones
+    lo[a] .. hi[a], counted from the first active one: all active zones where it is kept (reduce[a] false), the slice where it is
+    summed -- in the reference's order, k, j, i ascending from 0.0, then times 1.0/count/count.  A summed range may reach into
+    the ghost zones (see outputs.slice_zones).  -> [n3][n2][n1], a reduced direction with one element."""
+    sub = V[first[2] + lo[2]:first[2] + hi[2] + 1, first[1] + lo[1]:first[1] + hi[1] + 1, first[0] + lo[0]:first[0] + hi[0] + 1]
+    if not any(reduce):
+        return np.ascontiguousarray(sub)
+    n = [1 if reduce[a] else sub.shape[2 - a] for a in range(3)]
+    acc = np.zeros((n[2], n[1], n[0]))
+    factor = 1.0
+    for a in (2, 1, 0):
+        if reduce[a]:
+            factor = factor / float(hi[a] - lo[a] + 1)
+
+    def steps(a):
+        return [slice(q, q + 1) for q in range(sub.shape[2 - a])] if reduce[a] else [slice(None)]
+    with np.errstate(all="ignore"):
+        for sk in steps(2):
+            for sj in steps(1):
+                for si in steps(0):
+                    acc = acc + sub[sk, sj, si]
+        return acc * factor
+
+
+def minmax(data: np.ndarray):
+    """minmax1/2/3 (utils.c:142-197): the fold ``dmin = dmin < x ? dmin : x`` in payload order, so that of elements that compare
+    equal (zeros of either sign) the last stays"""
+    flat = np.asarray(data, dtype=np.float64).reshape(-1)
+    mn, mx = flat.min(), flat.max()
+    return float(flat[np.nonzero(flat == mn)[0][-1]]), float(flat[np.nonzero(flat == mx)[0][-1]])
+
+
+def pgm_gray(data2: np.ndarray, dmin: float, dmax: float) -> np.ndarray:
+    """output_pgm.c:94-122 for the payload ``[nx2][nx1]``: the bytes in file order"""
+    data2 = np.asarray(data2, dtype=np.float64)
+    max_min = (dmax - dmin) * (1.0 + FLT_EPSILON)
+    if not max_min > 0.0:
+        return np.zeros(data2.size, dtype=np.uint8)
+    sfact = 256.0 / max_min
+    with np.errstate(all="ignore"):
+        x = sfact * (data2[::-1, :] - dmin)
+        ok = (x > -2147483649.0) & (x < 2147483648.0)        # (int) of a double outside int, or a NaN: INT_MIN on the reference's host
+        g = np.where(ok, np.trunc(np.where(ok, x, 0.0)), -2147483648.0)
+    return np.clip(g, 0, 255).astype(np.uint8).reshape(-1)
+
+
+def single_vtk_bytes(data: np.ndarray, id_: str, *, nx, minx, dx, raw_reduce, time: float, level: int = 0, domain: int = 0) -> bytes:
+    """output_vtk_2d / output_vtk_3d (output_vtk.c:70-278) for the payload `data` ([nx3][nx2][nx1], or [nx2][nx1] of a 2-D
+    output).  nx, minx, dx: the Grid's; raw_reduce: the block's reduce_x1/2/3 as parse_slice set them (SPACING of a reduced
+    direction is the Grid's whole extent, :142-144)."""
+    data = np.asarray(data)
+    s = "# vtk DataFile Version 2.0\n"
+    s += "Really cool Athena data at time= %e, level= %i, domain= %i\n" % (time, level, domain)
+    s += "BINARY\nDATASET STRUCTURED_POINTS\n"
+    if data.ndim == 2:
+        n2, n1 = data.shape
+        sp = [dx[a] * nx[a] if raw_reduce[a] else dx[a] for a in range(3)]
+        s += "DIMENSIONS %d %d %d\n" % (n1 + 1, n2 + 1, 1)
+        s += "ORIGIN %e %e %e \n" % (minx[0], minx[1], minx[2])
+        s += "SPACING %e %e %e \n" % (sp[0], sp[1], sp[2])
+        s += "CELL_DATA %d \n" % (n1 * n2)
+    else:
+        n3, n2, n1 = data.shape
+        s += "DIMENSIONS %d %d %d\n" % (n1 + 1, n2 + 1, n3 + 1)
+        s += "ORIGIN %e %e %e \n" % (minx[0], minx[1], minx[2])
+        s += "SPACING %e %e %e \n" % (dx[0], dx[1], dx[2])
+        s += "CELL_DATA %d \n" % (n1 * n2 * n3)
+    s += "SCALARS %s float\nLOOKUP_TABLE default\n" % id_
+    with np.errstate(all="ignore"):
+        return s.encode() + data.astype(">f4").tobytes()
+
+
+def single_tab_bytes(data: np.ndarray, dat_fmt: Optional[str] = None) -> bytes:
+    """output_tab_1d/2d/3d (output_tab.c:75-283): the zone indices as (float) in the first columns, the value in the last, every
+    column through ``" " + dat_fmt`` (default ``%12.8e``)"""
+    fmt = " " + (dat_fmt if dat_fmt is not None else "%12.8e")
+    data = np.asarray(data, dtype=np.float64)
+    nd = data.ndim
+    line = fmt * (nd + 1) + "\n"
+    out = []
+    if nd == 1:
+        for i in range(data.shape[0]):
+            out.append(line % (float(i), float(data[i])))
+    elif nd == 2:
+        for j in range(data.shape[0]):
+            for i in range(data.shape[1]):
+                out.append(line % (float(i), float(j), float(data[j, i])))
+    else:
+        for k in range(data.shape[0]):
+            for j in range(data.shape[1]):
+                for i in range(data.shape[2]):
+                    out.append(line % (float(i), float(j), float(k), float(data[k, j, i])))
+    return "".join(out).encode()
+
+
+def single_pgm_bytes(gray: np.ndarray, nx1: int, nx2: int) -> bytes:
+    """output_pgm.c:83: the header in front of the nx1*nx2 gray bytes (pgm_gray, or the device's)"""
+    return b"P5\n%d %d\n255\n" % (nx1, nx2) + np.asarray(gray, dtype=np.uint8).tobytes()
+
+
 class OverlapWriter:
     """Writes dump files on ONE background thread while the run goes on.  Pure Python: the worker touches nothing but the
     arrays of a job (page-locked host memory that a device copy has filled and finished with) and files -- it never calls the

@@ -143,6 +143,8 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_dump_snapshot_bytes": (LL, [P, I]), "aa_dump_snapshot_begin": (I, [P, I, I, I, LL]),
         "aa_dump_snapshot_ready": (I, [P, I]), "aa_dump_snapshot_wait": (I, [P, I]),
         "aa_dump_snapshot_section": (C.c_void_p, [P, I, I, llp]), "aa_dump_snapshot_release": (I, [P, I]),
+        "aa_outdata_dims": (I, [P, I, ip, ip, ip, ip]), "aa_outdata": (I, [P, I, ip, ip, ip, dp, ip, dp, dp]),
+        "aa_outdata_gray": (I, [P, I, ip, ip, ip, D, D, C.POINTER(C.c_ubyte), ip]),
         "aa_rst_sections": (I, [P]), "aa_rst_section_label": (I, [P, I, C.c_char_p, I]), "aa_rst_section_doubles": (LL, [P, I]),
         "aa_rst_section_get": (I, [P, I, dp]), "aa_rst_section_put": (I, [P, I, dp]),
         "aa_rst_section_get_box": (I, [P, I, ip, ip, dp]), "aa_rst_section_put_box": (I, [P, I, ip, ip, dp]),
@@ -676,6 +678,33 @@ class Grid:
             t_, dt_, _ = self.mesh_state()
             time = t_ if time is None else time; dt = dt_ if dt is None else dt
         return dict(nx=g.Nx, minx=g.MinX, dx=dx, time=time, dt=dt, gamma=r.gamma, prim=prim, nscal=r.nscal, level=lev, domain=domain)
+
+    # ---- single-variable outputs (output.c OutData1/2/3, expr_*; csrc/outdata.hip) -------------------------------------------
+    def _outdata_args(self, expr, reduce, lo, hi):
+        from . import dumps
+        ex = dumps.EXPR[expr] if isinstance(expr, str) else int(expr)
+        I3 = C.c_int * 3
+        return ex, I3(*[1 if r else 0 for r in reduce]), I3(*[int(v) for v in lo]), I3(*[int(v) for v in hi]), I3()
+
+    def outdata(self, expr, reduce=(0, 0, 0), lo=(0, 0, 0), hi=(0, 0, 0)):
+        """-> (payload [n3][n2][n1] of doubles, a reduced direction having one element; dmin; dmax) of the expression `expr`
+        ("d" .. "cs2", "flux", or its AA_OUT_* code) over the active zones: reduce[a] sums zones lo[a] .. hi[a] (inclusive, from 0)
+        of direction a and multiplies by 1.0/count, as OutData1/2 do (aa_outdata)."""
+        ex, red, l, h, dims = self._outdata_args(expr, reduce, lo, hi)
+        self._chk(self.L.aa_outdata_dims(self._h, ex, red, l, h, dims))
+        data = np.empty((dims[2], dims[1], dims[0]), dtype=np.float64)
+        dmin, dmax = C.c_double(), C.c_double()
+        self._chk(self.L.aa_outdata(self._h, ex, red, l, h, _dp(data), dims, C.byref(dmin), C.byref(dmax)))
+        return data, dmin.value, dmax.value
+
+    def outdata_gray(self, expr, reduce, lo, hi, dmin: float, dmax: float) -> np.ndarray:
+        """the bytes of the pgm image of the same payload scaled with dmin / dmax, in file order (aa_outdata_gray)"""
+        ex, red, l, h, dims = self._outdata_args(expr, reduce, lo, hi)
+        self._chk(self.L.aa_outdata_dims(self._h, ex, red, l, h, dims))
+        img = np.empty(dims[0] * dims[1] * dims[2], dtype=np.uint8)
+        self._chk(self.L.aa_outdata_gray(self._h, ex, red, l, h, float(dmin), float(dmax),
+                                         img.ctypes.data_as(C.POINTER(C.c_ubyte)), dims))
+        return img
 
     # ---- the same payload beside the run: one kernel, one copy, two slots (csrc/dump.hip aa_dump_snapshot_*) -----------------
     DUMP_SLOTS = 2                       # AA_DUMP_SLOTS

@@ -8,6 +8,12 @@ else the reference knows -- single-variable outputs (``out = d``, ``P``, ``V1`` 
 pdf``, user outputs by ``name =`` -- is refused by ``from_par`` with the block and the value named: a run must not find out at
 its first dump.
 
+``from_par(..., single=True)`` -- off by default -- also reads the single-variable blocks by init_output's rules (output.c:363-471):
+``out = d | M1 .. cs2`` (``flux`` with ``usr_expr_flag``), ``id``, ``dat_fmt``, ``dmin / dmax``, the slices of `parse_slice`, ``ndim``,
+``out_fmt = vtk | tab | pgm``; `slice_search` / `slice_zones` / `single_ranges` are the index search of OutData1/2, and a target's
+``write_single(out, self)`` (driver.Driver: one rank, a 2-D or 3-D Grid) makes the file.  ``ppm``, ``pdf``, ``name =``, ``S``,
+particle expressions and ``tab`` dumps stay refused.
+
 ``data_output(target, flag)`` drives a *target*: anything with ``time`` and the three writers ``write_dump(out, self)``,
 ``write_history(out, self)``, ``write_restart(out, self)``: driver.Driver (one Grid per rank), driver.MeshRun (every level of a
 refined mesh on one GPU) and driver.MeshDriver (a refined mesh over several ranks).  What the three have in common on this side --
@@ -55,10 +61,122 @@ class Output:
     domain: int = -1
     id: str = ""
     dat_fmt: Optional[str] = None
+    # a single-variable output (from_par(single=True)): `out` is the expression; ndim as init_output counts it (output.c:390-411);
+    # xl / xu the slice bounds and raw_reduce the reduce_x1/2/3 flags as parse_slice leaves them; sdmin / sdmax: dmin / dmax are set;
+    # gmin / gmax: the running pair the writers keep (not in the parameter table: a restarted run begins them again, as the
+    # reference's init_output does)
+    single: bool = False
+    ndim: int = 0
+    xl: tuple = (0.0, 0.0, 0.0)
+    xu: tuple = (0.0, 0.0, 0.0)
+    raw_reduce: tuple = (0, 0, 0)
+    sdmin: bool = False
+    sdmax: bool = False
+    dmin: float = 0.0
+    dmax: float = 0.0
+    gmin: float = 1.0e20          # HUGE_NUMBER, defs.h.in:161
+    gmax: float = -1.0e20
 
     @property
     def prim(self) -> bool:
         return self.out == "prim"
+
+
+SINGLE_EXPR = ("d", "M1", "M2", "M3", "E", "V1", "V2", "V3", "P", "cs2")     # getexpr (output.c:1279-1347) for adiabatic hydro
+SINGLE_FMT = ("vtk", "tab", "pgm")
+_PARTICLE_EXPR = ("dpar", "M1par", "M2par", "M3par", "V1par", "V2par", "V3par")
+NGHOST = 4
+
+
+def _atof(s: str) -> float:
+    """atof: the longest numeric prefix, 0.0 where there is none"""
+    import re
+    m = re.match(r"\s*[-+]?(\d+\.?\d*([eE][-+]?\d+)?|\.\d+([eE][-+]?\d+)?|inf(inity)?|nan)", s, re.I)
+    return float(m.group(0)) if m else 0.0
+
+
+def parse_slice(par: ParTable, block: str, ax: str, l: float, u: float):
+    """parse_slice (output.c:1391-1418): ``v`` | ``lo:hi`` | ``:`` | ``lo:`` | ``:hi`` -> (l, u, flag); a missing end keeps the
+    root Domain's"""
+    if not par.exist(block, ax):
+        return l, u, 0
+    expr = par.gets(block, ax)
+    if ":" in expr:
+        a, b = expr.split(":", 1)
+        if b.strip():
+            u = _atof(b)
+        if a.strip():
+            l = _atof(a)
+    else:
+        l = u = _atof(expr)
+    if l > u:
+        raise ParError(f"[parse_slice]: lower slice limit {l!r} > upper {u!r} in {expr}")
+    return l, u, 1
+
+
+def slice_search(l: float, u: float, minx: float, dx: float, n: int):
+    """The index search of OutData1/2 (output.c:763-780 and its siblings) along one direction of `n` active zones from `minx`,
+    with fc_pos's face position ``minx + (Real)(k - ks)*dx``: -> (kstart, kend) counted from the first active zone, or None where
+    the range misses the Grid (``xu < MinX || xl >= MaxX``, MaxX = MinX + Nx*dx, init_grid.c:111)."""
+    if u < minx or l >= minx + float(n) * dx:
+        return None
+    k = 1
+    while l >= minx + float(k) * dx:
+        k += 1
+    start = k - 1
+    k = n - 1
+    while u < minx + float(k) * dx:
+        k -= 1
+    return start, k
+
+
+def slice_zones(l: float, u: float, minx: float, dx: float, n: int):
+    """The zones OutData1/2 SUM for a slice, counted from the first active zone.  The search leaves kstart / kend as indices of the
+    Grid's arrays (they begin at kl+1 = ks+1), and the loops then read ``expr(pgrid, i+il, j+jl, k+kl)`` for k = kstart .. kend
+    (output.c:789-790): the first active index is added twice, so the zones lie nghost = 4 above the slice's own -- the upper
+    slices of a Grid are read from its ghost zones (never past them: kend <= ke).  A direction of one zone has ks = 0: no shift."""
+    r = slice_search(l, u, minx, dx, n)
+    if r is None:
+        return None
+    first = NGHOST if n > 1 else 0
+    return r[0] + first, r[1] + first
+
+
+def single_ranges(out: Output, Nx, minx, dx):
+    """What OutData1/2/3 do for the block `out` on a Grid of Nx zones: -> (reduce, lo, hi) for lib.Grid.outdata /
+    dumps.outdata_from_values -- reduce[a]: direction a is summed over the zones lo[a] .. hi[a] (slice_zones) --, or None where
+    the slice misses the Grid (no file).  A 2-D Grid's output of ndim 2 is the Grid itself (output.c:748-757)."""
+    gdim = sum(1 for v in Nx if v > 1)
+    red, lo, hi = [0, 0, 0], [0, 0, 0], [0, 0, 0]
+    if out.ndim == gdim:
+        return tuple(red), tuple(lo), tuple(hi)
+    rr = out.raw_reduce
+    if out.ndim == 2:                       # OutData2 on a 3-D Grid: x3, else x2, else x1
+        which = [2 if rr[2] else 1 if rr[1] else 0]
+    elif not rr[0]:                         # OutData1: the kept direction is the first that is not reduced
+        which = [2, 1]
+    elif not rr[1]:
+        which = [2, 0]
+    else:
+        which = [1, 0]
+    for a in which:
+        if u_misses(out.xl[a], out.xu[a], minx[a], dx[a], Nx[a]):
+            return None
+    for a in which:
+        red[a] = 1
+        if Nx[a] == 1:                      # output.c:947-949: kstart = kl, kend = ku
+            continue
+        lo[a], hi[a] = slice_zones(out.xl[a], out.xu[a], minx[a], dx[a], Nx[a])
+    return tuple(red), tuple(lo), tuple(hi)
+
+
+def u_misses(l, u, minx, dx, n) -> bool:
+    return u < minx or l >= minx + float(n) * dx
+
+
+def payload_shape(reduce, Nx):
+    """the dimensions of the array the writers get, slowest first: the kept directions of more than one zone"""
+    return tuple(Nx[a] for a in (2, 1, 0) if not reduce[a] and Nx[a] > 1)
 
 
 class OutputSet:
@@ -73,6 +191,8 @@ class OutputSet:
         steps queue on the device and takes its rows from there (`hst_armed`; the same files)."""
         self.par, self.outs, self.rst = par, outs, rst
         self.hst_queued = bool(hst_queued)
+        self.single = False                   # from_par(single=True): single-variable blocks may stand in `outs`
+        self._single_checked = False
         self.overlap, self.overlap_max_bytes = bool(overlap), int(overlap_max_bytes)
         self.overlap_rst = bool(overlap_rst)
         self._writer = None                   # dumps.OverlapWriter, made by the first overlapped dump
@@ -94,8 +214,14 @@ class OutputSet:
     @classmethod
     def from_par(cls, par: ParTable, time: float = 0.0, rundir: str = ".", rank: int = 0, nranks: int = 1,
                  rst_ngrid=None, rst_mesh_ngrid=None, rst_mesh_nproc=None, overlap: bool = False,
-                 overlap_max_bytes: int = 8 << 30, overlap_rst: bool = False, hst_queued: bool = False) -> "OutputSet":
-        """init_output.  Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
+                 overlap_max_bytes: int = 8 << 30, overlap_rst: bool = False, hst_queued: bool = False,
+                 single: bool = False, problem: Optional[str] = None) -> "OutputSet":
+        """init_output.  single = True -- off by default: nothing changes without it -- also takes the single-variable blocks
+        (``out = d | M1 | M2 | M3 | E | V1 | V2 | V3 | P | cs2`` with ``id``, ``x1 / x2 / x3`` slices, ``dmin / dmax``, ``dat_fmt``,
+        ``out_fmt = vtk | tab | pgm``; ``out = flux`` with ``usr_expr_flag = 1`` for a problem whose file defines it -- `problem`, or
+        the target's at the first output) by init_output's rules (output.c:363-471); one rank, a 2-D or 3-D Grid, synchronous.
+
+        Like the reference it completes the parameter table (defaults of the blocks it reads; for rank
         r > 0 ``<job>problem_id`` gains ``-id<r>``, main.c:227-232): the table is what a restart dump carries.
         rst_ngrid = (n1, n2, n3): a one-rank run writes its restart dumps as the n1 x n2 x n3 ranks of the reference would, one
         file per Grid under ``id<r>/`` (Driver.write_restart; x1 cuts are written and read, never run).
@@ -127,6 +253,11 @@ class OutputSet:
                                  f"{len(blocks)} <domainN> blocks)")
             rst_mesh_ngrid = [given[n - 1] for n in blocks]                # level by level, as the reference visits them
             rst_mesh_nproc = restart.mesh_nproc(rst_mesh_ngrid, rst_mesh_nproc)      # (ValueError: Grids no such rank count divides)
+        if single:
+            if nranks > 1:
+                raise ValueError("[init_output]: single = True takes a one-rank run (several ranks would each hold a part of a slice)")
+            if par.geti("domain1", "Nx2") == 1 and par.geti("domain1", "Nx3") == 1:
+                raise ValueError("[init_output]: single = True is not built for a 1-D Grid (Nx2 = Nx3 = 1)")
         if nranks > 1 and rank != 0:
             par.blocks["job"]["problem_id"] = "%s-id%d" % (par.gets("job", "problem_id"), rank)
         maxout = par.geti_def("job", "maxout", MAXOUT_DEFAULT)
@@ -141,6 +272,12 @@ class OutputSet:
                 raise ParError(f"[init_output]: <{block}> name = {par.gets(block, 'name')}: user-defined outputs are not built")
             fmt = par.gets(block, "out_fmt")
             out = par.gets(block, "out") if par.exist(block, "out") else "cons"
+            if single and out not in ("cons", "prim"):
+                if overlap:
+                    raise ValueError(f"[init_output]: <{block}> out = {out}: single-variable outputs are written synchronously; "
+                                     "single = True does not go with overlap = True")
+                outs.append(cls._single_block(par, n, block, fmt, out, time, problem))
+                continue
             if out not in ("cons", "prim"):
                 raise ParError(f"[init_output]: <{block}> out = {out} (out_fmt = {fmt}): single-variable outputs are not built; "
                                "dumps take out = cons or out = prim")
@@ -159,8 +296,61 @@ class OutputSet:
                 rst = o                         # output.c:299-305: kept apart, one per run (the last one named wins)
             else:
                 outs.append(o)
-        return cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes,
+        self = cls(par, outs, rst, rundir, rank, nranks, rst_ngrid, rst_mesh_ngrid, rst_mesh_nproc, overlap, overlap_max_bytes,
                    overlap_rst, hst_queued)
+        self.single = bool(single)
+        return self
+
+    @staticmethod
+    def _single_block(par: ParTable, n: int, block: str, fmt: str, out: str, time: float, problem: Optional[str]) -> Output:
+        """output.c:363-471 for one block whose `out` is neither cons nor prim"""
+        usr = par.geti(block, "usr_expr_flag") if par.exist(block, "usr_expr_flag") else 0
+        if usr:                                 # get_usr_expr: prob/ioniz_sphere.c:241-249 knows "flux" and nothing else
+            if out != "flux":
+                raise ParError(f"[init_output]: <{block}> usr_expr_flag = {usr}, out = {out}: the only user expression built is "
+                               "out = flux (the EdgeFlux of ioniz_sphere)")
+            if problem is not None and problem != "ioniz_sphere":
+                raise ParError(f"[init_output]: <{block}> out = flux: problem \"{problem}\" defines no such expression (ioniz_sphere does)")
+        elif out == "S":
+            raise ParError(f"[init_output]: <{block}> out = S: the entropy calls pow(), whose device version is not the host's to the "
+                           "last bit; it is not built")
+        elif out in _PARTICLE_EXPR:
+            raise ParError(f"[init_output]: <{block}> out = {out}: particle expressions are not built")
+        elif out not in SINGLE_EXPR:
+            raise ParError(f"[init_output]: <{block}> out = {out}: Unknown data expression (built: {', '.join(SINGLE_EXPR)}; "
+                           "flux with usr_expr_flag = 1)")
+        if fmt in ("ppm", "pdf"):
+            why = ("the palette tables are the reference's program text and are not copied" if fmt == "ppm"
+                   else "probability distributions are not built")
+            raise ParError(f"[init_output]: <{block}> out_fmt = {fmt} (out = {out}): {why}")
+        if fmt not in SINGLE_FMT:
+            raise ParError(f"[init_output]: Unsupported {block}/out_fmt={fmt} (built for out = {out}: {', '.join(SINGLE_FMT)})")
+        Nx = [par.geti("domain1", f"Nx{a + 1}") for a in range(3)]
+        ndim = 1 + sum(1 for a in (1, 2) if Nx[a] > 1)
+        xl, xu, rr = [], [], []
+        for a in range(3):
+            l, u, f = parse_slice(par, block, f"x{a + 1}", par.getd("domain1", f"x{a + 1}min"), par.getd("domain1", f"x{a + 1}max"))
+            xl.append(l); xu.append(u); rr.append(f)
+            if f and (a == 0 or Nx[a] > 1):
+                ndim -= 1
+        if ndim <= 0:
+            raise ParError(f"Too many slices specified in {block}")
+        if fmt == "vtk" and ndim == 1:
+            raise ParError(f"[output_vtk]: <{block}> is 1-D: Only able to output 2D or 3D")
+        if fmt == "pgm" and ndim != 2:
+            raise ParError(f"[output_pgm]: <{block}> is {ndim}-D: Output must be a 2D slice")
+        o = Output(n=n, out_fmt=fmt, out=out,
+                   t=par.getd_def(block, "time", time), num=par.geti_def(block, "num", 0), dt=par.getd(block, "dt"),
+                   level=par.geti_def(block, "level", -1), domain=par.geti_def(block, "domain", -1),
+                   id=par.gets(block, "id") if par.exist(block, "id") else f"out{n}",
+                   dat_fmt=par.gets(block, "dat_fmt") if par.exist(block, "dat_fmt") else None,
+                   single=True, ndim=ndim, xl=tuple(xl), xu=tuple(xu), raw_reduce=tuple(rr),
+                   sdmin=par.exist(block, "dmin"), sdmax=par.exist(block, "dmax"),
+                   dmin=par.getd(block, "dmin") if par.exist(block, "dmin") else 0.0,
+                   dmax=par.getd(block, "dmax") if par.exist(block, "dmax") else 0.0)
+        par.blocks[block].setdefault("id", o.id)
+        par.blocks[block].setdefault("out", out)
+        return o
 
     def data_output(self, target, flag: int, settled: Optional[Output] = None) -> None:
         """flag = 1 writes every output; flag = 0 those whose next time has passed.  A block that fires advances by its dt
@@ -170,6 +360,12 @@ class OutputSet:
         settled: a block whose row for this time is already written and counted (`run` with hst_queued: the device has
         applied the rule behind this step, t += dt and num += 1 are done) -- it is not asked again."""
         self.poll()
+        if not self._single_checked and any(o.single for o in self.outs):
+            # before the first file: a target without the route refuses the keyword (``single_route()`` -> None or the reason)
+            why = target.single_route(self) if hasattr(target, "single_route") else "this target writes no single-variable outputs"
+            if why is not None:
+                raise ValueError(f"[data_output]: single = True: {why}")
+            self._single_checked = True
         time = target.time
         fire = []
         for o in self.outs:
@@ -200,6 +396,8 @@ class OutputSet:
             if fo:
                 if o.out_fmt == "hst":
                     target.write_history(o, self)
+                elif o.single:              # (a slice that misses the Grid writes nothing; the number advances all the same)
+                    target.write_single(o, self)
                 else:
                     target.write_dump(o, self)
                 o.num += 1

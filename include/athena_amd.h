@@ -469,6 +469,38 @@ int          aa_dump_snapshot_wait(aa_grid *g, int slot);
 const float *aa_dump_snapshot_section(aa_grid *g, int slot, int section, long long *nfloats);
 int          aa_dump_snapshot_release(aa_grid *g, int slot);
 
+/* ---- output.c:629-1233: the payload of a single-variable output (out = d | M1 | M2 | M3 | E | V1 | V2 | V3 | P | cs2 | flux with
+ *      x1 / x2 / x3 slices) from the ACTIVE zones, in double precision: OutData3 where nothing is reduced, OutData2 / OutData1 where
+ *      one or two directions are.  reduce[a] != 0 sums the expression over the zones lo[a] .. hi[a] (inclusive, counted from 0 over the
+ *      active zones) of direction a in the reference's order and multiplies by 1.0/count[/count]; the caller finds the indices (the
+ *      search of output.c:763-780 with the face positions of fc_pos; the reference then adds the first active index a second time,
+ *      :789-790, so its zones lie nghost above the slice: a range may reach into the ghost zones, which must be current), the
+ *      library refuses a range outside the Grid's arrays.  The same bits from the default and the strict library.
+ *        aa_outdata       dims[3] doubles ([dims[2]][dims[1]][dims[0]], a reduced direction has 1) to host_dst, with the payload's
+ *                         minimum and maximum as minmax1/2/3 (utils.c:142-197) leave them
+ *        aa_outdata_dims  dims alone: what host_dst has to hold
+ *        aa_outdata_gray  the bytes of output_pgm.c:94-122 for the same payload scaled with dmin / dmax (the caller's: the
+ *                         payload's own or the block's fixed ones), dims[0]*dims[1]*dims[2] bytes in file order
+ *      AA_OUT_FLUX is GridS.EdgeFlux[k][j][i] (prob/ioniz_sphere.c:356-359) of a Grid with a radiation plane.  Refused: a Grid cut
+ *      into slabs, a level of an aa_mesh, a 1-D Grid.  Like aa_dump_section the calls stage through the face-state area and the
+ *      bounce buffer and change no state.                                                                                          */
+#define AA_OUT_D    0
+#define AA_OUT_M1   1
+#define AA_OUT_M2   2
+#define AA_OUT_M3   3
+#define AA_OUT_E    4
+#define AA_OUT_V1   5
+#define AA_OUT_V2   6
+#define AA_OUT_V3   7
+#define AA_OUT_P    8
+#define AA_OUT_CS2  9
+#define AA_OUT_FLUX 10
+int aa_outdata_dims(aa_grid *g, int expr, const int reduce[3], const int lo[3], const int hi[3], int dims[3]);
+int aa_outdata(aa_grid *g, int expr, const int reduce[3], const int lo[3], const int hi[3], double *host_dst, int dims[3],
+               double *dmin, double *dmax);
+int aa_outdata_gray(aa_grid *g, int expr, const int reduce[3], const int lo[3], const int hi[3], double dmin, double dmax,
+                    unsigned char *host_dst, int dims[3]);
+
 /* ---- restart.c:463-983 / restart_grids :52-456: the double-precision payload of a restart dump to and from the resident state,
  *      one labelled section at a time, ACTIVE zones [k][j][i] only:
  *        DENSITY | 1-MOMENTUM | 2-MOMENTUM | 3-MOMENTUM | ENERGY | EDGEFLUX (ion radiation; (Nx1+1)(Nx2+1)(Nx3+1)) | SCALAR n
