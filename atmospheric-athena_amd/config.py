@@ -61,6 +61,9 @@ class RunConfig:
     # configure --enable-fofc (FIRST_ORDER_FLUX_CORRECTION): first-order flux correction of the van Leer integrator
     # (integrate_3d_vl.c Steps 10 and 14); off by default
     fofc: bool = False
+    # third-order reconstruction on a 2-D run (Nx3 = 1), opt-in: ``order = 3`` stays refused there (check_2d), this is the switch
+    # that lib.Grid hands to aa_set_order_2d behind aa_create; 2 = off
+    order_2d: int = 2
 
     @property
     def ndim(self) -> int:
@@ -156,9 +159,17 @@ def check_fofc(run: RunConfig, nranks: int = 1, mesh: bool = False) -> None:
 
 def check_2d(run: RunConfig, nranks: int = 1, mesh: bool = False, nslab: int = 1) -> None:
     """What a 2-D run (Nx3 = 1) may be: the CTU integrator at any cour_no, the van Leer integrator up to 0.5 (integrate.c:55-57),
-    second order, no first-order flux correction, one Grid on one device -- what the reference's 2-D targets pin."""
+    second order (third through ``order_2d = 3``, with "ctu" or "vl": the reference's blast_ppm / blast_vl_ppm builds; not with CTU
+    without H-correction, which no third-order build pins), no first-order flux correction, one Grid on one device -- what the
+    reference's 2-D targets pin."""
+    if run.order_2d not in (2, 3):
+        raise ParError(f"[config]: order_2d = {run.order_2d} (2: piecewise linear, 3: piecewise parabolic)")
     if run.ndim != 2:
+        if run.order_2d != 2:
+            raise ParError(f"[config]: order_2d = {run.order_2d} on a {run.ndim}-D run: it is the switch of a 2-D run (Nx3 = 1); a 1-D or 3-D run takes order")
         return
+    if run.order_2d == 3 and run.integrator not in ("ctu", "vl"):
+        raise ParError(f"[config]: order_2d = 3 with \"{run.integrator}\" (CTU without H-correction): no third-order reference build pins it")
     if run.integrator == "vl" and run.cour_no > 0.5:
         raise ParError("<time>cour_no=%e, must be <= 0.5 with 2D VL integrator" % run.cour_no)
     if run.order != 2:
@@ -200,7 +211,7 @@ def check_1d(run: RunConfig, nranks: int = 1, mesh: bool = False, nslab: int = 1
         raise ParError(f"[config]: a 1-D Grid (Nx2 = Nx3 = 1) cannot be cut into {nslab} x3 slabs")
 
 
-def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu", fofc: bool = False) -> RunConfig:
+def load(path: str, overrides=None, problem: Optional[str] = None, integrator: str = "ctu", fofc: bool = False, order_2d: int = 2) -> RunConfig:
     deck = ParTable.from_file(path)
     ndim_deck = sum(1 for d in (1, 2, 3) if deck.geti("domain1", f"Nx{d}") > 1)
     par = deck.cmdline(overrides)
@@ -221,6 +232,7 @@ def load(path: str, overrides=None, problem: Optional[str] = None, integrator: s
         raise ParError(f"[integrate_init]: unknown integrator {integrator}")
     run.integrator = integrator
     run.fofc = bool(fofc)
+    run.order_2d = int(order_2d)
     check_fofc(run)
     check_2d(run)
     check_1d(run)
@@ -324,6 +336,8 @@ def levels_2d(par: ParTable, run: RunConfig) -> List[GridConfig]:
     nd = par.geti_def("job", "num_domains", 1)
     if nd > 1 and run.integrator == "ctu-noh":
         raise ParError("[config]: static mesh refinement on a 2-D Grid with CTU without H-correction: no reference build pins it")
+    if nd > 1 and run.order_2d == 3 and run.integrator != "ctu":
+        raise ParError("[config]: static mesh refinement on a 2-D Grid at third order with the van Leer integrator: no reference build pins it")
     return _levels(par, run, 2)
 
 

@@ -66,6 +66,8 @@ struct aa_grid {
   int level = 0;                       // DomainS.Level: > 0 only as a level of an aa_mesh
   bool two_d = false;                  // Nx3 = 1: the 2-D integrators (hydro2d_kernels.hip); U 5 | LR 20 | F 10 | eta 2 | edge2d
   aa::Real *edge2d = nullptr;          //   ... what the x1 tiles of the 2-D kernels hand each other (grid.h)
+  int order_2d = 2;                    //   ... its effective reconstruction order: 3 after aa_set_order_2d(g, 3) (p.order stays 2 on a 2-D Grid)
+  bool stepped_2d = false;             //   ... an integrator chain of this Grid has been launched (aa_set_order_2d then refuses)
   bool one_d = false;                  // Nx2 = Nx3 = 1 in a 1-D root Domain: the 1-D integrators (hydro1d_kernels.hip); U 5 | LR 5 (the second U buffer)
   bool resident_1d = true;             //   ... AA_1D_RESIDENT=0 (read by aa_create): aa_run_1d steps one launch at a time instead of keeping the Grid in one workgroup's LDS (k1d_run)
   int batch_2d = 0;                    // a 2-D Grid: steps aa_run_2d queues between two reads of the clock (AA_2D_BATCH, read by aa_create; 0: it loops over aa_step)

@@ -1,5 +1,5 @@
 // hydro2d_kernels.hip -- the hydro hot path of a 2-D Grid (Nx3 = 1; gfx950): integrate_2d_ctu.c and integrate_2d_vl.c of the
-// reference for HYDRO, ADIABATIC, CARTESIAN, second order, no gravity, no cooling, no passive scalar.  The per-cell and
+// reference for HYDRO, ADIABATIC, CARTESIAN, second or third order, no gravity, no cooling, no passive scalar.  The per-cell and
 // per-face arithmetic is that of hydro_dev.h, unchanged; this file only restates the 2-D loop nests.
 //
 // Layout (api.hip aa_create): one plane [N2][sJ] per field, no ghost zones along x3 (ks = ke = 0), fields nc = sJ*N2 apart,
@@ -26,6 +26,14 @@
 // aa_run_2d (csrc/api2d.hip) queues many steps without the host in between: every kernel above has a second entry point, *_dc, with
 // the same body, which takes dt from the device clock (hydro2d_launch.h Run2D) instead of a kernel argument and returns at once when
 // the clock has stopped; k2d_advance, one wavefront behind the update kernel, does new_dt and the loop's bookkeeping on the device.
+//
+// Third order (aa_set_order_2d; the reference's --with-order=3): everything that reconstructs -- k2d_edge_wl, k2d_first, and the VL2
+// forms of k2d_edge and k2d_step -- has a second instantiation, ORD = 3, picked on the host (with_ord).  Only recon_zone differs: it
+// reads the five zones m - 2s .. m + 2s from memory, evaluates the three limited slopes the zone's parabola needs and calls ppm_cell
+// (lr_states_ppm.c).  What travels by shuffle, LDS and the edge buffer are face states and fluxes, as before, so the tiling is that
+// of second order.  Stencil bounds: the first pass reconstructs the zones of [is-2, ie+2] x [js-2, je+2], whose five-zone stencils
+// end at is-4 = 0 and ie+4 = N1-1 (js-4 = 0, je+4 = N2-1): exactly the four ghost zones; VL2 reconstructs [is-1, ie+1] x [js-1, je+1]
+// on a U^{n+1/2} that VL1 wrote over [is-3, ie+3] x [js-3, je+3].  Threads outside the range compute on a zone clamped into it.
 #include <hip/hip_runtime.h>
 #include "grid.h"
 #include "hydro_dev.h"
@@ -61,11 +69,22 @@ AA_DEV void store5(Real *b, long nc, long m, const Real u[6])
   for (int v = 0; v < 5; v++) b[(long)v*nc + m] = u[v];
 }
 
-// PLM with characteristic tracing of the zone at m along D (lr_states_plm.c): Wl of its upper face, Wr of its lower face
-template <int D, bool TRACE>
+// the zone at m reconstructed along D: Wl of its upper face, Wr of its lower face.  ORD 2: PLM (lr_states_plm.c) from the zones
+// m - s .. m + s; ORD 3: PPM (lr_states_ppm.c) from m - 2s .. m + 2s, the slopes of m - s, m, m + s evaluated here (the direct form:
+// a zone's slope is evaluated by each of the three zones whose parabola needs it).  TRACE: with characteristic tracing (CTU)
+template <int D, bool TRACE, int ORD>
 AA_DEV void recon_zone(const Real *src, const DevGrid &g, long m, Real dt, Real wl_next[6], Real wr_here[6])
 {
   const long s = D == 0 ? 1L : g.sJ;
+  if (ORD == 3) {
+    Real u[6], w5[5][6], dw[3][6];
+#pragma unroll
+    for (int q = 0; q < 5; q++) { load_cons<D>(src, g.nc, m + (q - 2)*s, u); cons_to_prim<0>(u, w5[q], g.Gamma_1); }
+#pragma unroll
+    for (int q = 0; q < 3; q++) limited_slopes<0>(w5[q], w5[q + 1], w5[q + 2], g.Gamma, dw[q]);
+    ppm_cell<0, TRACE>(w5[1], w5[2], w5[3], dw[0], dw[1], dw[2], dt/g.dx[D], g.Gamma, wl_next, wr_here);
+    return;
+  }
   Real u[6], wm[6], w[6], wp[6];
   load_cons<D>(src, g.nc, m - s, u); cons_to_prim<0>(u, wm, g.Gamma_1);
   load_cons<D>(src, g.nc, m, u);     cons_to_prim<0>(u, w, g.Gamma_1);
@@ -83,6 +102,7 @@ AA_DEV void face_first(const DevGrid &g, const Real wl[6], const Real wr[6], Rea
 
 // ---- CTU, Steps 1 and 2 -------------------------------------------------------------------------------------------------
 // side kernel: the left state of the first x1 face of every tile but the first (the zone below it belongs to the tile before)
+template <int ORD>
 AA_DEV void edge_wl_body(const DevGrid &g, Real dt, Real *edge, int ntx)
 {
   const int jl = g.js - 2, nj = g.je - g.js + 5;
@@ -92,17 +112,19 @@ AA_DEV void edge_wl_body(const DevGrid &g, Real dt, Real *edge, int ntx)
   const int i0 = g.is + 64*(t - 1);
   if (i0 > g.ie + 2) return;
   Real wl[6], wr[6];
-  recon_zone<0, true>(g.U, g, (long)j*g.sJ + i0 - 1, dt, wl, wr);
+  recon_zone<0, true, ORD>(g.U, g, (long)j*g.sJ + i0 - 1, dt, wl, wr);
   const long es = (long)ntx*g.N2;
 #pragma unroll
   for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = wl[v];
 }
 
+template <int ORD>
 __global__ void __launch_bounds__(64)
 k2d_edge_wl(DevGrid g, Real dt, Real *edge, int ntx)
-{ edge_wl_body(g, dt, edge, ntx); }
+{ edge_wl_body<ORD>(g, dt, edge, ntx); }
 
 // L/R states and first-pass fluxes of the lower x1 and x2 face of every zone of [is-2, ie+2] x [js-2, je+2]
+template <int ORD>
 AA_DEV void first_body(const DevGrid &g, Real dt, const Real *edge)
 {
   __shared__ Real sh[5][T2_R][T2_W];
@@ -115,7 +137,7 @@ AA_DEV void first_body(const DevGrid &g, Real dt, const Real *edge)
   const long m = (long)jc*g.sJ + ic;
   Real wl[6], wr[6], wln[6], ul[6], ur[6], f[6];
 
-  recon_zone<1, true>(g.U, g, m, dt, wln, wr);
+  recon_zone<1, true, ORD>(g.U, g, m, dt, wln, wr);
 #pragma unroll
   for (int v = 0; v < 5; v++) sh[v][ty][lane] = wln[v];
   Real wr2[6];
@@ -123,7 +145,7 @@ AA_DEV void first_body(const DevGrid &g, Real dt, const Real *edge)
   for (int v = 0; v < 6; v++) wr2[v] = wr[v];
 
   if (ty > 0) {          // (one row per wavefront: the branch is uniform)
-    recon_zone<0, true>(g.U, g, m, dt, wln, wr);
+    recon_zone<0, true, ORD>(g.U, g, m, dt, wln, wr);
 #pragma unroll
     for (int v = 0; v < 5; v++) wl[v] = __shfl_up(wln[v], 1);
     wl[5] = 0.0;
@@ -149,9 +171,10 @@ AA_DEV void first_body(const DevGrid &g, Real dt, const Real *edge)
   }
 }
 
+template <int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_first(DevGrid g, Real dt, const Real *edge)
-{ first_body(g, dt, edge); }
+{ first_body<ORD>(g, dt, edge); }
 
 // ---- CTU, Steps 5a, 6a and 9a: transverse flux gradients on the face states, then eta1 / eta2 ----------------------------
 // a -= h*(fp - fm) for the five fields, with the transverse flux's components permuted into this face's frame
@@ -213,7 +236,7 @@ k2d_correct(DevGrid g, Real dt, int hcorr)
 
 // ---- the flux of the lower face of zone (j, i) along D, in the sweep frame, for the three fused update kernels -----------
 enum { M_CTU2 = 0, M_VL1 = 1, M_VL2 = 2 };
-template <int MODE, int D>
+template <int MODE, int D, int ORD>
 AA_DEV void face_flux(const DevGrid &g, int i, int j, Real dt, Real f[6])
 {
   const long m = (long)j*g.sJ + i;
@@ -244,10 +267,10 @@ AA_DEV void face_flux(const DevGrid &g, int i, int j, Real dt, Real f[6])
     load_cons<D>(g.U, g.nc, m, u);     cons_to_prim<0>(u, wr, g.Gamma_1);
     face_first(g, wl, wr, ul, ur, f);
   } else {
-    // Steps 7-10: PLM without tracing on U^{n+1/2} (LR fields 0 .. 4), then the flux
+    // Steps 7-10: PLM / PPM without tracing on U^{n+1/2} (LR fields 0 .. 4), then the flux
     Real dump[6];
-    recon_zone<D, false>(g.LR, g, m - s, dt, wl, dump);
-    recon_zone<D, false>(g.LR, g, m, dt, dump, wr);
+    recon_zone<D, false, ORD>(g.LR, g, m - s, dt, wl, dump);
+    recon_zone<D, false, ORD>(g.LR, g, m, dt, dump, wr);
     face_first(g, wl, wr, ul, ur, f);
   }
 }
@@ -257,7 +280,7 @@ template <int MODE> struct Range2 {
 };
 
 // side kernel: the x1 flux of the face above the last lane of every x1 tile
-template <int MODE>
+template <int MODE, int ORD>
 AA_DEV void edge_body(const DevGrid &g, Real dt, Real *edge, int ntx)
 {
   const int X = Range2<MODE>::ext();
@@ -268,16 +291,16 @@ AA_DEV void edge_body(const DevGrid &g, Real dt, Real *edge, int ntx)
   const int i = g.is + 64*(t - Range2<MODE>::toff()) + 64;
   if (i < g.is - X + 1 || i > hi_i + 1) return;
   Real f[6];
-  face_flux<MODE, 0>(g, i, j, dt, f);
+  face_flux<MODE, 0, ORD>(g, i, j, dt, f);
   const long es = (long)ntx*g.N2;
 #pragma unroll
   for (int v = 0; v < 5; v++) edge[v*es + (long)t*g.N2 + j] = f[v];
 }
 
-template <int MODE>
+template <int MODE, int ORD>
 __global__ void __launch_bounds__(64)
 k2d_edge(DevGrid g, Real dt, Real *edge, int ntx)
-{ edge_body<MODE>(g, dt, edge, ntx); }
+{ edge_body<MODE, ORD>(g, dt, edge, ntx); }
 
 // new_dt.c:72-140 for one zone (the operands and their order as in the CFL kernel of the 3-D path; never contracted, so that
 // the maxima are the same bits whichever kernel visits the zone)
@@ -307,7 +330,7 @@ AA_DEV bool on_kept_line(const KeepPlanes &kp, int d, int x)
   for (int q = 0; q < 8; q++) hit = hit || kp.p[d][q] == x;
   return hit;
 }
-template <int MODE, bool CFL, bool KEEP>
+template <int MODE, bool CFL, bool KEEP, int ORD>
 AA_DEV void step_body(const DevGrid &g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc, const KeepPlanes *kp)
 {
   __shared__ Real sh[5][T2_R][T2_W];
@@ -321,7 +344,7 @@ AA_DEV void step_body(const DevGrid &g, Real dt, Real c1, Real c2, const Real *e
   Real f1[6], f2[6], f1p[6], f2p[6];
 
   // x2 flux of the lower face: rows lo_j .. hi_j + 1
-  face_flux<MODE, 1>(g, ic, clampi(j, lo_j, hi_j + 1), dt, f2);
+  face_flux<MODE, 1, ORD>(g, ic, clampi(j, lo_j, hi_j + 1), dt, f2);
 #pragma unroll
   for (int v = 0; v < 5; v++) sh[v][ty][lane] = f2[v];
   if (KEEP) {
@@ -332,7 +355,7 @@ AA_DEV void step_body(const DevGrid &g, Real dt, Real c1, Real c2, const Real *e
   }
   const bool zone = ty < T2_R - 1 && i >= lo_i && i <= hi_i && j <= hi_j;
   if (ty < T2_R - 1) {                                             // (uniform per wavefront)
-    face_flux<MODE, 0>(g, clampi(i, lo_i, hi_i + 1), jc, dt, f1);
+    face_flux<MODE, 0, ORD>(g, clampi(i, lo_i, hi_i + 1), jc, dt, f1);
 #pragma unroll
     for (int v = 0; v < 5; v++) f1p[v] = __shfl_down(f1[v], 1);
     if (lane == 63 && zone) {
@@ -385,14 +408,15 @@ AA_DEV void step_body(const DevGrid &g, Real dt, Real c1, Real c2, const Real *e
     }
   }
 }
-template <int MODE, bool CFL>
+// (ORD: of the reconstruction of M_VL2; the other two modes reconstruct nothing and are instantiated at 2 only)
+template <int MODE, bool CFL, int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc)
-{ step_body<MODE, CFL, false>(g, dt, c1, c2, edge, sc, nullptr); }
-template <int MODE, bool CFL>
+{ step_body<MODE, CFL, false, ORD>(g, dt, c1, c2, edge, sc, nullptr); }
+template <int MODE, bool CFL, int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step_keep(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars *sc, KeepPlanes kp)
-{ step_body<MODE, CFL, true>(g, dt, c1, c2, edge, sc, &kp); }
+{ step_body<MODE, CFL, true, ORD>(g, dt, c1, c2, edge, sc, &kp); }
 
 // ---- the device clock (aa_run_2d; hydro2d_launch.h Run2D) ------------------------------------------------------------------
 // dt/dx and dt/2dx of the update kernels (time_step.h dt_over_dx / half_dt_over_dx) are the bits the launch wrappers below form on
@@ -401,20 +425,22 @@ k2d_step_keep(DevGrid g, Real dt, Real c1, Real c2, const Real *edge, DevScalars
 // The *_dc entry points: `live` and dt in one uniform load at the top (the clock is written by k2d_advance / k2d_seed, kernels in
 // front of this one on the same stream, and by nobody while this one runs); a step queued behind the stop returns here, before
 // any store and before any barrier (the whole grid takes the same branch).
+template <int ORD>
 __global__ void __launch_bounds__(64)
 k2d_edge_wl_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
-{ if (!rc->c.live) return; edge_wl_body(g, rc->c.dt, edge, ntx); }
+{ if (!rc->c.live) return; edge_wl_body<ORD>(g, rc->c.dt, edge, ntx); }
+template <int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_first_dc(DevGrid g, const Run2D *rc, const Real *edge)
-{ if (!rc->c.live) return; first_body(g, rc->c.dt, edge); }
+{ if (!rc->c.live) return; first_body<ORD>(g, rc->c.dt, edge); }
 __global__ void __launch_bounds__(256)
 k2d_correct_dc(DevGrid g, const Run2D *rc, int hcorr)
 { if (!rc->c.live) return; correct_body(g, rc->c.dt, hcorr); }
-template <int MODE>
+template <int MODE, int ORD>
 __global__ void __launch_bounds__(64)
 k2d_edge_dc(DevGrid g, const Run2D *rc, Real *edge, int ntx)
-{ if (!rc->c.live) return; edge_body<MODE>(g, rc->c.dt, edge, ntx); }
-template <int MODE, bool CFL>
+{ if (!rc->c.live) return; edge_body<MODE, ORD>(g, rc->c.dt, edge, ntx); }
+template <int MODE, bool CFL, int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc)
 {
@@ -422,7 +448,7 @@ k2d_step_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc)
   const Real dt = rc->c.dt;
   const Real c1 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[0]) : dt_over_dx(dt, g.dx[0]);
   const Real c2 = MODE == M_VL1 ? half_dt_over_dx(dt, g.dx[1]) : dt_over_dx(dt, g.dx[1]);
-  step_body<MODE, CFL, false>(g, dt, c1, c2, edge, sc, nullptr);
+  step_body<MODE, CFL, false, ORD>(g, dt, c1, c2, edge, sc, nullptr);
 }
 
 // the clock of a call: what aa_run_2d knows on the host, and the maxima zeroed for the first step's update kernel
@@ -452,13 +478,13 @@ k2d_advance(Run2D *rc, DevScalars *sc, Real dx0, Real dx1, RunClock *out)
 
 // ---- the Grids of a 2-D Mesh on one clock (aa_mesh_run_2d, csrc/smr.hip) ----------------------------------------------------------
 // k2d_step_keep behind the clock load: KeepPlanes stays a by-value argument, c1 and c2 are the bits launch_step_keep forms on the host
-template <int MODE, bool CFL>
+template <int MODE, bool CFL, int ORD>
 __global__ void __launch_bounds__(T2_W*T2_R)
 k2d_step_keep_dc(DevGrid g, const Run2D *rc, const Real *edge, DevScalars *sc, KeepPlanes kp)
 {
   if (!rc->c.live) return;
   const Real dt = rc->c.dt;
-  step_body<MODE, CFL, true>(g, dt, dt_over_dx(dt, g.dx[0]), dt_over_dx(dt, g.dx[1]), edge, sc, &kp);
+  step_body<MODE, CFL, true, ORD>(g, dt, dt_over_dx(dt, g.dx[0]), dt_over_dx(dt, g.dx[1]), edge, sc, &kp);
 }
 // the clock of a call, and new_dt's maxima of every Grid zeroed for the first step (lane l: Grid l)
 __global__ void __launch_bounds__(64)
@@ -497,84 +523,92 @@ static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1)/b); 
 
 int ntiles_2d(const DevGrid &g) { return 2 + (g.Nx1 + 2)/64; }      // the most x1 tiles any of the kernels below launches
 
-void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
+// `order` (2 or 3: the Grid's effective reconstruction order, aa_set_order_2d) picks the instantiation of what reconstructs
+void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, int order, hipStream_t st)
 {
   const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);                     // tile -1 (is-64 .. is-1) and the tiles up to ie+2
   const int nj = g.Nx2 + 4;
-  if (ntx > 1) hipLaunchKernelGGL(k2d_edge_wl, dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, dt, edge, ntx);
-  hipLaunchKernelGGL(k2d_first, dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, edge);
+  with_ord(order == 3, [&](auto ORD) {
+    if (ntx > 1) hipLaunchKernelGGL((k2d_edge_wl<ORD>), dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, dt, edge, ntx);
+    hipLaunchKernelGGL((k2d_first<ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, edge);
+  });
 }
+void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, hipStream_t st) { launch_2d_ctu_first(g, dt, edge, 2, st); }
 void launch_2d_ctu_correct(const DevGrid &g, Real dt, bool hcorr, hipStream_t st)
 {
   const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
   hipLaunchKernelGGL(k2d_correct, dim3(ntx, cdiv(g.Nx2 + 4, 4)), dim3(64, 4), 0, st, g, dt, hcorr ? 1 : 0);
 }
-template <int MODE, bool CFL>
+template <int MODE, bool CFL, int ORD = 2>
 static void launch_step(const DevGrid &g, Real dt, Real c1, Real c2, Real *edge, DevScalars *sc, hipStream_t st)
 {
   const int X = Range2<MODE>::ext();
   const int ntx = Range2<MODE>::toff() + (int)cdiv(g.Nx1 + X, 64), nj = g.Nx2 + 2*X;
-  hipLaunchKernelGGL((k2d_edge<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
-  hipLaunchKernelGGL((k2d_step<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, c1, c2, edge, sc);
+  hipLaunchKernelGGL((k2d_edge<MODE, ORD>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
+  hipLaunchKernelGGL((k2d_step<MODE, CFL, ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, c1, c2, edge, sc);
 }
 // the keeping form (KEEP above), for the levels of a Mesh; the side kernel is the same
-template <int MODE, bool CFL>
+template <int MODE, bool CFL, int ORD = 2>
 static void launch_step_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
 {
   const int ntx = (int)cdiv(g.Nx1, 64), nj = g.Nx2;
-  hipLaunchKernelGGL((k2d_edge<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
-  hipLaunchKernelGGL((k2d_step_keep<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, kp);
+  hipLaunchKernelGGL((k2d_edge<MODE, ORD>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, dt, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_keep<MODE, CFL, ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, kp);
 }
 void launch_2d_ctu_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
 { with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep<M_CTU2, CFL>(g, dt, edge, sc, kp, st); }); }
+// (second order only: aa_mesh_create_2d refuses van Leer levels at third order, so the keeping form of VL2 has no ORD = 3 instantiation)
 void launch_2d_vl_flux2_update_keep(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
 { with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep<M_VL2, CFL>(g, dt, edge, sc, kp, st); }); }
 void launch_2d_ctu_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
 { with_flag(sc != nullptr, [&](auto CFL) { launch_step<M_CTU2, CFL>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }
 void launch_2d_vl_predict(const DevGrid &g, Real dt, Real *edge, hipStream_t st)
 { launch_step<M_VL1, false>(g, dt, 0.5*(dt/g.dx[0]), 0.5*(dt/g.dx[1]), edge, nullptr, st); }
-void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st)
-{ with_flag(sc != nullptr, [&](auto CFL) { launch_step<M_VL2, CFL>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }
+void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, int order, hipStream_t st)
+{ with_flag(sc != nullptr, [&](auto CFL) { with_ord(order == 3, [&](auto ORD) { launch_step<M_VL2, CFL, ORD>(g, dt, dt/g.dx[0], dt/g.dx[1], edge, sc, st); }); }); }
+void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, hipStream_t st) { launch_2d_vl_flux2_update(g, dt, edge, sc, 2, st); }
 
 // ---- the same chains on the device clock (aa_run_2d): the launch geometry of the wrappers above, dt from `rc` -------------------
-void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st)
+void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, int order, hipStream_t st)
 {
   const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
   const int nj = g.Nx2 + 4;
-  if (ntx > 1) hipLaunchKernelGGL(k2d_edge_wl_dc, dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, rc, edge, ntx);
-  hipLaunchKernelGGL(k2d_first_dc, dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge);
+  with_ord(order == 3, [&](auto ORD) {
+    if (ntx > 1) hipLaunchKernelGGL((k2d_edge_wl_dc<ORD>), dim3(cdiv((long)nj*(ntx - 1), 64)), dim3(64), 0, st, g, rc, edge, ntx);
+    hipLaunchKernelGGL((k2d_first_dc<ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge);
+  });
 }
 void launch_2d_ctu_correct_dc(const DevGrid &g, const Run2D *rc, bool hcorr, hipStream_t st)
 {
   const int ntx = 1 + (int)cdiv(g.Nx1 + 2, 64);
   hipLaunchKernelGGL(k2d_correct_dc, dim3(ntx, cdiv(g.Nx2 + 4, 4)), dim3(64, 4), 0, st, g, rc, hcorr ? 1 : 0);
 }
-template <int MODE, bool CFL>
+template <int MODE, bool CFL, int ORD = 2>
 static void launch_step_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
 {
   const int X = Range2<MODE>::ext();
   const int ntx = Range2<MODE>::toff() + (int)cdiv(g.Nx1 + X, 64), nj = g.Nx2 + 2*X;
-  hipLaunchKernelGGL((k2d_edge_dc<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
-  hipLaunchKernelGGL((k2d_step_dc<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc);
+  hipLaunchKernelGGL((k2d_edge_dc<MODE, ORD>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_dc<MODE, CFL, ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc);
 }
 void launch_2d_ctu_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
 { launch_step_dc<M_CTU2, true>(g, rc, edge, sc, st); }
 void launch_2d_vl_predict_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st)
 { launch_step_dc<M_VL1, false>(g, rc, edge, nullptr, st); }
-void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st)
-{ launch_step_dc<M_VL2, true>(g, rc, edge, sc, st); }
+void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, int order, hipStream_t st)
+{ with_ord(order == 3, [&](auto ORD) { launch_step_dc<M_VL2, true, ORD>(g, rc, edge, sc, st); }); }
 void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st)
 { hipLaunchKernelGGL(k2d_seed, dim3(1), dim3(64), 0, st, rc, v, sc); }
 void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st)
 { hipLaunchKernelGGL(k2d_advance, dim3(1), dim3(64), 0, st, rc, sc, g.dx[0], g.dx[1], out); }
 
 // ---- the Grids of a 2-D Mesh on one clock (aa_mesh_run_2d): launch_step_keep's geometry, dt from `rc` ----------------------------
-template <int MODE, bool CFL>
+template <int MODE, bool CFL, int ORD = 2>
 static void launch_step_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
 {
   const int ntx = (int)cdiv(g.Nx1, 64), nj = g.Nx2;
-  hipLaunchKernelGGL((k2d_edge_dc<MODE>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
-  hipLaunchKernelGGL((k2d_step_keep_dc<MODE, CFL>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc, kp);
+  hipLaunchKernelGGL((k2d_edge_dc<MODE, ORD>), dim3(cdiv((long)nj*ntx, 64)), dim3(64), 0, st, g, rc, edge, ntx);
+  hipLaunchKernelGGL((k2d_step_keep_dc<MODE, CFL, ORD>), dim3(ntx, cdiv(nj, T2_R - 1)), dim3(T2_W, T2_R), 0, st, g, rc, edge, sc, kp);
 }
 void launch_2d_ctu_flux2_update_keep_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, const KeepPlanes &kp, hipStream_t st)
 { with_flag(sc != nullptr, [&](auto CFL) { launch_step_keep_dc<M_CTU2, CFL>(g, rc, edge, sc, kp, st); }); }

@@ -29,12 +29,16 @@ struct Run2D {
 // the Grids of a Mesh as k2d_mesh_seed / k2d_mesh_advance see them: new_dt's maxima and the zone sizes, in the Mesh's order
 struct MeshClockTab { int n, pad; DevScalars *sc[AA_2D_MESH_GRIDS]; Real dx[2*AA_2D_MESH_GRIDS]; };
 
+// the two chains of grid.h that reconstruct, with the Grid's effective reconstruction order (2: PLM; 3: PPM, aa_set_order_2d): the CTU
+// first pass and the van Leer corrector.  (grid.h's declarations of the same names, without `order`, are the second-order forms.)
+void launch_2d_ctu_first(const DevGrid &g, Real dt, Real *edge, int order, hipStream_t st);
+void launch_2d_vl_flux2_update(const DevGrid &g, Real dt, Real *edge, DevScalars *sc, int order, hipStream_t st);
 void launch_2d_seed(Run2D *rc, const Run2D &v, DevScalars *sc, hipStream_t st);               // the clock of a call; new_dt's maxima zeroed
-void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st);                     // as launch_2d_ctu_first ...
+void launch_2d_ctu_first_dc(const DevGrid &g, const Run2D *rc, Real *edge, int order, hipStream_t st);          // as launch_2d_ctu_first ...
 void launch_2d_ctu_correct_dc(const DevGrid &g, const Run2D *rc, bool hcorr, hipStream_t st);
 void launch_2d_ctu_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st);   // (always with new_dt's maxima)
 void launch_2d_vl_predict_dc(const DevGrid &g, const Run2D *rc, Real *edge, hipStream_t st);
-void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, hipStream_t st);
+void launch_2d_vl_flux2_update_dc(const DevGrid &g, const Run2D *rc, Real *edge, DevScalars *sc, int order, hipStream_t st);
 // nstep++, time += dt, new_dt with the clip at tlim, the maxima zeroed again, the stop rule; `out`: the host's mirror
 void launch_2d_advance(const DevGrid &g, Run2D *rc, DevScalars *sc, RunClock *out, hipStream_t st);
 // the Grids of a 2-D Mesh on ONE clock (aa_mesh_run_2d): the flux-keeping update kernels (sc == nullptr: without new_dt's maxima, for

@@ -153,13 +153,14 @@ static void queue_hst(aa_grid *g, const RunClock *clock, double tlim)
 void queue_chain_2d(aa_grid *g, const Run2D *rc, DevScalars *sc)
 {
   const HostGrid &d = g->d;
+  g->stepped_2d = true;
   if (g->p.integrator == 1) {
     { Scope s(g, "vl2d_predict"); launch_2d_vl_predict_dc(d, rc, g->edge2d, g->st); }
     { Scope s(g, "vl2d_flux2_update");
       if (g->keep_flux) launch_2d_vl_flux2_update_keep_dc(d, rc, g->edge2d, sc, g->keep, g->st);
-      else launch_2d_vl_flux2_update_dc(d, rc, g->edge2d, sc, g->st); }
+      else launch_2d_vl_flux2_update_dc(d, rc, g->edge2d, sc, g->order_2d, g->st); }
   } else {
-    { Scope s(g, "ctu2d_first"); launch_2d_ctu_first_dc(d, rc, g->edge2d, g->st); }
+    { Scope s(g, "ctu2d_first"); launch_2d_ctu_first_dc(d, rc, g->edge2d, g->order_2d, g->st); }
     { Scope s(g, "ctu2d_correct"); launch_2d_ctu_correct_dc(d, rc, g->p.integrator == 0, g->st); }
     { Scope s(g, "ctu2d_flux2_update");
       if (g->keep_flux) launch_2d_ctu_flux2_update_keep_dc(d, rc, g->edge2d, sc, g->keep, g->st);

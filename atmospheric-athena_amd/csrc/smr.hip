@@ -523,6 +523,11 @@ static aa_mesh *mesh_alloc(int nlevels, aa_grid **levels, bool two_d = false)
         mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] has integrator %d, the root %d: the levels of a Mesh share one integrator", l, g->p.integrator, levels[0]->p.integrator); return nullptr; }
       if (g->p.integrator == 2) {
         mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] has integrator = 2 (CTU without H-correction): no reference build with static mesh refinement pins it", l); return nullptr; }
+      // third order (aa_set_order_2d): the reference's order is a build option, one for all Domains; blast_smr_ppm is CTU + H-correction
+      if (g->order_2d != levels[0]->order_2d) {
+        mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] is at order %d, the root at %d: the levels of a Mesh share one reconstruction order (aa_set_order_2d on every level)", l, g->order_2d, levels[0]->order_2d); return nullptr; }
+      if (g->order_2d == 3 && g->p.integrator == 1) {
+        mesh_drop(m); aa_fail(-1, "[aa_mesh_create_2d]: levels[%d] is a van Leer level at third order: no reference build with static mesh refinement pins it (CTU + H-correction only)", l); return nullptr; }
     } else
     if (g->two_d) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] is a 2-D Grid: aa_mesh_create_2d (this is the 3-D constructor)", l); return nullptr; }
     if (g->fofc) { mesh_drop(m); aa_fail(-1, "[aa_mesh_create]: levels[%d] has first-order flux correction on (aa_set_fofc): not available on the Grids of a Mesh", l); return nullptr; }

@@ -303,7 +303,7 @@ class _Runner:
 
     # ---- continuing a run (main.c -r) ------------------------------------------------------------------
     @staticmethod
-    def _resume_head(path, overrides, problem, integrator, order):
+    def _resume_head(path, overrides, problem, integrator, order, order_2d: int = 2):
         """(head of rank 0's file, its parameter table with the overrides on top, the RunConfig built from that)"""
         head0 = restart.read_head(path)
         par = head0["par"].cmdline(overrides)
@@ -311,6 +311,7 @@ class _Runner:
         if integrator not in ("ctu", "vl", "ctu-noh"):
             raise config.ParError(f"[integrate_init]: unknown integrator {integrator}")
         run.integrator, run.order = integrator, order
+        run.order_2d = int(order_2d)      # (a build option of the reference, --with-order, like the integrator: not in the file)
         config.check_2d(run)
         config.check_1d(run)
         return head0, par, run
@@ -476,7 +477,7 @@ class Driver(_Runner):
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
                      engine_factory=None, rank: int = 0, nranks: int = 1, device: int = 0, strict: Optional[bool] = None,
-                     p2: int = 1, regrid: bool = False, fofc: bool = False) -> "Driver":
+                     p2: int = 1, regrid: bool = False, fofc: bool = False, order_2d: int = 2) -> "Driver":
         """``athena -r path [block/key=value ...]`` (main.c:168-173, :216-288; restart_grids, restart.c:52-456).  `path` is
         rank 0's file: every rank takes the parameter table from it, with the overrides on top (an unknown key is an error;
         time/nlim and time/tlim extend a run), and reads its own Grid from restart.rank_path(path, rank).  The problem
@@ -487,8 +488,11 @@ class Driver(_Runner):
         ``<domain1> NGrid_x1/2/3``, x1 cuts included: every rank reads, from every source file that meets its Grid, the part
         that does (restart.scan_sources, restart.box_pieces); time, dt and nstep are rank 0's file's.  `.par` then names the new
         cuts (NGrid_x1 = 1, NGrid_x2 = p2, NGrid_x3 = nranks / p2, no AutoWithNProc), so that a later dump describes itself.
-        Single-level meshes only."""
-        head0, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        Single-level meshes only.
+
+        order_2d = 3 resumes a 2-D run (Nx3 = 1) at third order (config.RunConfig.order_2d): the reference's order is a build option
+        and is not in the file."""
+        head0, par, run = cls._resume_head(path, overrides, problem, integrator, order, order_2d)
         if regrid and run.ndim == 1:
             raise restart.RestartError("[restart_grids]: regrid is not built for a 1-D Grid (Nx2 = Nx3 = 1): it is one Grid on one rank")
         run.fofc = bool(fofc)      # (a build option of the reference like the integrator: not in the file; it carries no state between steps)
@@ -943,7 +947,8 @@ class MeshRun(_Runner):
 
     @classmethod
     def from_restart(cls, path: str, overrides=(), problem: Optional[str] = None, integrator: str = "ctu", order: int = 2,
-                     device: int = 0, strict: Optional[bool] = None, nslab: int = 1, cuts=None, regrid: bool = False) -> "MeshRun":
+                     device: int = 0, strict: Optional[bool] = None, nslab: int = 1, cuts=None, regrid: bool = False,
+                     order_2d: int = 2) -> "MeshRun":
         """Driver.from_restart for a static-mesh-refinement deck: one file holds every Domain, root first (restart.c:531-770).
         nslab / cuts: resume on a Mesh cut into slabs inside the library, whatever wrote the file (lib.Mesh).
 
@@ -952,9 +957,11 @@ class MeshRun(_Runner):
         several Domains on a level included.  Every level reads, section by section, every source Grid's piece straight to the
         device (lib.Grid.read_rst_boxes); a level cut into slabs inside the library takes whole sections only, so one section
         of one level at a time is joined on the host (lib.Grid.read_rst_joined).  `.par` then names the decomposition this
-        run is on (NGrid_x* = 1 in every <domainN>, no AutoWithNProc): its own dumps are read back without the keyword."""
+        run is on (NGrid_x* = 1 in every <domainN>, no AutoWithNProc): its own dumps are read back without the keyword.
+
+        order_2d = 3: every level of a 2-D Mesh resumes at third order (as Driver.from_restart)."""
         from . import lib
-        head, par, run = cls._resume_head(path, overrides, problem, integrator, order)
+        head, par, run = cls._resume_head(path, overrides, problem, integrator, order, order_2d)
         if regrid:
             grids, sources = cls._mesh_sources(head, par, run)
             m = cls(lib.Mesh(grids, device, strict, initial=False, nslab=nslab, cuts=cuts), run)

@@ -102,6 +102,7 @@ def load(strict: bool | None = None) -> C.CDLL:
         "aa_bvals_mhd": (I, [P]), "aa_bvals_mhd_side": (I, [P, I, I]), "aa_bvals_ionrad": (I, [P]), "aa_new_dt": (I, [P]),
         "aa_integrate_3d_ctu": (I, [P]), "aa_integrate_begin": (I, [P]), "aa_cfl_in_update": (I, [P, I]), "aa_integrate_3d_vl": (I, [P]),
         "aa_integrate_2d_ctu": (I, [P]), "aa_integrate_2d_vl": (I, [P]), "aa_ion_radtransfer_3d": (I, [P, ip]),
+        "aa_set_order_2d": (I, [P, I]), "aa_get_order_2d": (I, [P]),
         "aa_integrate_1d_ctu": (I, [P]), "aa_integrate_1d_vl": (I, [P]), "aa_run_1d": (I, [P, D, D, I, ip]),
         "aa_run_2d": (I, [P, D, D, I, ip]), "aa_run_2d_batch": (I, [P]),
         "aa_run_3d": (I, [P, D, D, I, ip]), "aa_run_3d_batch": (I, [P]),
@@ -338,6 +339,13 @@ class Grid:
             self._chk(self.L.aa_create(C.byref(self.params), C.byref(h)))
         self._h = h
         self._keep = []
+        # third order on a 2-D run, opt-in (config.RunConfig.order_2d): the setter behind aa_create, before any state arrives
+        if getattr(grid.run, "order_2d", 2) != 2:
+            try:
+                self.set_order_2d(grid.run.order_2d)
+            except AthenaError:
+                self.close()
+                raise
 
     def _chk(self, rc: int):
         if rc != 0:
@@ -428,6 +436,17 @@ class Grid:
         self._chk(self.L.aa_set_fofc(self._h, 1 if on else 0))
 
     def fofc(self) -> bool: return bool(self.L.aa_get_fofc(self._h))
+
+    def set_order_2d(self, order: int = 3):
+        """configure --with-order on a 2-D Grid (Nx3 = 1), opt-in: 3 = piecewise parabolic (lr_states_ppm.c), 2 = piecewise linear.
+        Before start / resume / the first step and before the Grid joins a Mesh; refused (AthenaError) on 1-D and 3-D Grids (those
+        take aa_params.order), with CTU without H-correction, on a Grid that has stepped and on a level of a Mesh."""
+        self._chk(self.L.aa_set_order_2d(self._h, int(order)))
+
+    @property
+    def order(self) -> int:
+        """the effective reconstruction order: aa_params.order, or what set_order_2d made of a 2-D Grid"""
+        return int(self.L.aa_get_order_2d(self._h))
 
     def fofc_counts(self):
         """(zones that had d < 0, zones that had P < 0, second-order fluxes replaced) of the last integrate_3d_vl"""

@@ -143,11 +143,22 @@ int aa_new_dt(aa_grid *g);                          /* new_dt.c:32              
 int aa_integrate_3d_ctu(aa_grid *g);                /* integrate_3d_ctu.c:110, dt = Grid dt       */
 int aa_integrate_3d_vl(aa_grid *g);                 /* integrate_3d_vl.c:96 (NO_H_CORRECTION)     */
 /* A 2-D Grid (Nx[2] == 1; integrate.c:49-58 picks these by dimension, and so do aa_start / aa_step): HYDRO, ADIABATIC, second
- * order, no gravity / cooling / scalars / ion radiation / fofc / Mesh / slabs (each refused with a message: no reference target pins
- * them in 2-D).  cour_no may exceed 0.5 with the CTU integrator, not with van Leer (integrate.c:55-57).  The 3-D entry points
+ * order (third order: aa_set_order_2d below), no gravity / cooling / scalars / ion radiation / fofc / Mesh / slabs (each refused with a
+ * message: no reference target pins them in 2-D).  cour_no may exceed 0.5 with the CTU integrator, not with van Leer (integrate.c:55-57).  The 3-D entry points
  * return an error on a 2-D Grid and these on a 3-D one.                                                                        */
 int aa_integrate_2d_ctu(aa_grid *g);                /* integrate_2d_ctu.c (integrator 0: + H-correction, 2: without) */
 int aa_integrate_2d_vl(aa_grid *g);                 /* integrate_2d_vl.c (NO_H_CORRECTION)        */
+/* Third-order reconstruction on a 2-D Grid (configure --with-order=3: lr_states_ppm.c under integrate_2d_ctu.c / integrate_2d_vl.c),
+ * opt-in: aa_params.order = 3 stays refused by aa_create on a 2-D Grid, as it always was; a Grid created at order 2 is switched here.
+ * order: 2 or 3.  Call it behind aa_create, before aa_start / aa_resume / the first step and before aa_mesh_create_2d.  Off (2) by
+ * default; with it off every launch is what it was.  At 3, aa_integrate_2d_ctu / _vl, aa_step and aa_run_2d run the third-order
+ * instantiations of the kernels that reconstruct (the CTU first pass; the van Leer corrector, without tracing: lr_states_ppm.c:502-507);
+ * nothing is allocated: the four ghost zones are exactly what the five-zone stencil of the first pass reads.  Errors, each with a
+ * message that begins "[aa_set_order_2d]": a 1-D or 3-D Grid (those take aa_params.order), a value other than 2 or 3, integrator = 2
+ * (CTU without H-correction: no third-order reference build pins it), a Grid that has already stepped, a Grid that belongs to an
+ * aa_mesh.  aa_get_order_2d: the effective order of a 2-D Grid, aa_params.order (0 reads as 2) of any other.                          */
+int aa_set_order_2d(aa_grid *g, int order);
+int aa_get_order_2d(const aa_grid *g);
 /* A 1-D Grid (Nx[1] == Nx[2] == 1 and rootNx[1] == rootNx[2] == 1; integrate.c:36-47): HYDRO, ADIABATIC, second or third order,
  * no gravity / cooling / scalars / ion radiation / fofc / Mesh / slabs (each refused with a message that says 1-D).  cour_no has
  * no limit with the CTU integrator and must be <= 0.5 with van Leer (integrate.c:41-44).  Integrators 0 and 2 are the same code:
@@ -321,7 +332,9 @@ int  aa_mesh_halo_counts(const aa_mesh *m, long long out[3]);       /* all-level
  * on such a Mesh except the radiation ones, which return an error; aa_mesh_step runs aa_integrate_2d_ctu / _vl, and
  * aa_mesh_new_dt carries max_v1 and max_v2 only.  cour_no up to the reference's 0.8 with CTU, <= 0.5 with van Leer.  Refused:
  * a 3-D Grid among the levels (aa_mesh_create is the 3-D constructor, as this one refuses there), levels of mixed
- * integrators, integrator = 2 (no reference build with --enable-smr and without H-correction), a Grid with fofc on.          */
+ * integrators, integrator = 2 (no reference build with --enable-smr and without H-correction), a Grid with fofc on.  Third order
+ * (aa_set_order_2d on every Grid BEFORE this call): accepted where ALL levels are at order 3 with integrator = 0; refused: levels of
+ * mixed order, and van Leer levels at order 3 (no reference build with --enable-smr, --with-order=3 and the van Leer integrator). */
 int  aa_mesh_create_2d(int nlevels, aa_grid **levels, const int *disp, aa_mesh **out);
 void aa_mesh_destroy(aa_mesh *m);
 int  aa_mesh_get_state(const aa_mesh *m, double *time, double *dt, int *nstep);     /* MeshS          */
